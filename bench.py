@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Benchmark of the inferable-quantizer hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|...|resnet50] [--batched T] [--batch N] [--no-cpu] ...
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|...|resnet50] [--batched T] [--batch N]
+                    [--dump-outputs DIR] [--full [--no-cpu] ...] ...
 
 A *step* is one call of the configuration's quantizer (through the public class, hence through the
 C ABI and the gfx950 kernel) on one device-resident synthetic tensor.  Default workload: BASELINE
@@ -28,23 +29,28 @@ Protocol
       - the event behind the FIRST launch to the event behind the LAST gives ``roofline.kernel_us`` / ``achieved`` /
         ``frac``: the average launch period of launches 2..K, bubbles between launches included -- the figure that
         rocprofv3's average kernel duration (profiles/) must agree with.
-  * per-launch evidence (after the timed region, outside it): >= 50 launches with an event between every two;
+  * ``--dump-outputs DIR``: right after the timed region the output(s) of the LAST timed step are written to DIR as .npy
+    (float32; float64 for float64 tensors; a fixed seeded sample of each beyond 64 MB in all -- dump_outputs).  The
+    inputs are the portable synthetic tensors, identical from run to run, so two builds can be compared output for output.
+  * a plain run stops there: set-up, pre-warm, W warm-up steps, the K timed steps, the dump, the line.  Everything
+    below marked --full runs only with ``--full``, after the judged region.
+  * --full, per-launch evidence: >= 50 launches with an event between every two;
     median / mean / p10 / p90 of the per-launch periods are reported under ``roofline.per_launch``.
   * ``roofline.traffic`` is emitted only when profiles/pmc_traffic.json holds counters taken on the SAME kernel
     variant (``mctq_last_launch()``) of the SAME library build (``mctq_build_id()``) this run launched; otherwise null
     with the reason (``traffic_build_id_mismatch``).
-  * the parity check compares the output of the LAST timed step with the CPU oracle.
-  * at N = 1 the default run appends ``batched_16x4096``: the same tensor 16 times in one batched launch, measured
+  * --full, the parity check compares the output of the LAST timed step with the CPU oracle.
+  * --full at N = 1 appends ``batched_16x4096``: the same tensor 16 times in one batched launch, measured
     after the judged region with the same event protocol (``--no-batched-extra`` skips it).
 
 ``--gpus N`` with N > 1 and no RANK in the environment: the script starts ``python -m torch.distributed.run`` on
 itself as a child process (before anything touches the GPU) and relays its output and exit status; launched by
 torch.distributed.run directly it is one rank.  Every rank runs the same per-GPU workload (weak scaling; the path
-needs no collective); ``value`` is the sum over ranks divided by the slowest rank's time.  BASELINE config 5 sharded by
-dim 0 + ONE all-gather (RCCL) is measured outside the timed region and reported as ``sharded_cfg5`` plus the top-level
-``sharded_cfg5_*`` fields (``--gather`` forces it at N = 1 under torchrun).
+needs no collective); ``value`` is the sum over ranks divided by the slowest rank's time.  With --full, BASELINE config 5
+sharded by dim 0 + ONE all-gather (RCCL) is measured outside the timed region and reported as ``sharded_cfg5`` plus the
+top-level ``sharded_cfg5_*`` fields (``--gather`` runs it without --full too, and at N = 1 under torchrun).
 
-Self-verifying at every N: each rank compares the SHA-256 of the output of its last timed step with the REFERENCE's digest
+With --full, self-verifying at every N: each rank compares the SHA-256 of the output of its last timed step with the REFERENCE's digest
 (``ranks_parity_ok``), and of its config-5 shard with the reference's digest of that row block
 (``sharded_cfg5.ranks_shard_digest_ok``); one mismatch -> ``parity_error`` and exit status 3.  Rank 0 runs the
 ``cpu_baseline`` leg at every N.  With N > 1 the job exits non-zero instead of printing a line when RCCL cannot form the
@@ -74,6 +80,8 @@ import bench_dist  # noqa: E402
 HBM_PEAK_GBS = 8000.0           # MI355X HBM3E spec (guide MI355X_MICROARCH.md: 8.0 TB/s; 6.29 TB/s measured copy)
 HBM_COPY_GBS = 6290.0
 BASELINE_METRIC = "elems/s + achieved HBM GB/s, per-channel symmetric 4096×4096 fp32"
+DUMP_BUDGET_BYTES = 64 * 10**6  # --dump-outputs: all .npy files together, headers included
+DUMP_SEED = 0
 
 
 def parse():
@@ -96,7 +104,7 @@ def parse():
     ap.add_argument("--prewarm-seconds", type=float, default=1.0,
                     help="fixed-duration run of the step loop before the warm-up steps (clocks, allocator); declared in the output")
     ap.add_argument("--evidence-launches", type=int, default=200,
-                    help="launches of the per-launch event-pair pass after the timed region (0 = skip)")
+                    help="--full: launches of the per-launch event-pair pass after the timed region (0 = skip)")
     ap.add_argument("--nt", type=int, default=None)
     ap.add_argument("--cached-store-max-mb", type=int, default=None,
                     help="tuning key cached_store_max_mb: outputs up to this size are stored through the caches (default 32)")
@@ -106,7 +114,7 @@ def parse():
     ap.add_argument("--paced", type=int, default=None, help="tuning key paced (include/mctq_hip.h): 0 = per-tensor launches never through flat_paced_kernel")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-batched-extra", action="store_true", help="skip the batched_16x4096 object of the default run")
+    ap.add_argument("--no-batched-extra", action="store_true", help="skip the batched_16x4096 object of a --full run")
     ap.add_argument("--no-eager-extra", action="store_true",
                     help="config 3: skip the eager per-call figure (profiler passes: only the judged kernel's dispatches)")
     ap.add_argument("--gather", action="store_true", help="run the sharded config-5 + all-gather leg even at N = 1 (needs torchrun)")
@@ -136,6 +144,13 @@ def parse():
                          "sharded config-5 leg did not execute with status 7")
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"],
                     help="cpu: dry run of the entry path over gloo (tests); not a measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="after the judged region also run every side leg: the digest parity check (ranks_parity_ok), the "
+                         "per-launch evidence pass, config 3's eager figure, batched_16x4096, the sharded config-5 leg and the "
+                         "CPU baseline.  Without it a run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32, or float64 for float64 "
+                         "tensors); beyond %d MB in all, a fixed seeded sample of every output" % (DUMP_BUDGET_BYTES // 10**6))
     args = ap.parse_args()
     args.batch_given = any(a == "--batch" or a.startswith("--batch=") for a in sys.argv[1:])
     return args
@@ -180,6 +195,28 @@ def per_launch_periods(step, launches: int):
         evs[i + 1].record()
     torch.cuda.synchronize()
     return [evs[i].elapsed_time(evs[i + 1]) * 1e3 for i in range(launches)]
+
+
+def dump_outputs(out_dir: str, y):
+    """--dump-outputs: the output(s) of the last timed step as out_dir/<name>.npy -- ``output`` for one tensor, ``output_000``,
+    ``output_001``, ... for a step that returns several.  float64 tensors are written as float64, all others widened to
+    float32 (exact).  When everything together would exceed DUMP_BUDGET_BYTES, each output is replaced by a sample of flat
+    indices in proportion to its size, drawn once from a generator seeded with DUMP_SEED and the output's position and
+    kept in index order: the same arguments give the same sample on every run and every build."""
+    outs = list(y) if isinstance(y, (list, tuple)) else [y]
+    names = ["output"] if len(outs) == 1 else [f"output_{i:03d}" for i in range(len(outs))]
+    dtypes = [torch.float64 if t.dtype == torch.float64 else torch.float32 for t in outs]
+    data = sum(t.numel() * (8 if dt == torch.float64 else 4) for t, dt in zip(outs, dtypes))
+    data_budget = DUMP_BUDGET_BYTES - 128 * len(outs)     # 128 B: the .npy header of each file
+    os.makedirs(out_dir, exist_ok=True)
+    import numpy as np
+    for i, (t, dt, name) in enumerate(zip(outs, dtypes, names)):
+        a = t.detach().to(dt).cpu().numpy()
+        if data > data_budget:
+            keep = max(1, a.size * data_budget // data)   # this output's share of the budget, in its own elements
+            idx = np.sort(np.random.default_rng([DUMP_SEED, i]).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def batched_plans(quantizer, x0, tensors: int, ring: int):
@@ -244,6 +281,8 @@ def main():
     if args.e2e:
         if args.config != "resnet50" or args.gpus != 1:
             raise SystemExit("--e2e goes with --config resnet50 at --gpus 1")
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: not with --e2e (a step there is a whole forward, not one quantizer output)")
         import bench_e2e
         sys.exit(bench_e2e.main(args))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -446,6 +485,18 @@ def main():
         return ev1                                 # the region's closing synchronize polls this event first
 
     wall = bench_dist.timed_region(run_all, 1, device, dist)
+
+    # ---- the last timed step's output, kept for the dump and the parity check before anything overwrites the ring ----------
+    last_slot = (n_launch - 1) % ring
+    if stream_on:
+        y_last = act_streams[last_slot].outputs       # persistent outputs of the last timed replay
+    elif args.batched:
+        y_last = plan_outs[last_slot]       # persistent outputs; later passes rewrite them with the same values
+    else:
+        y_last = ys[last_slot]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, y_last)
+
     # events on the stream the kernels were launched on; with a steady part the whole-region figure is the host wall clock
     dev_ms = wall * 1e3 if (dry or steady) else ev0.elapsed_time(ev1)
     wall, dev_ms = bench_dist.max_over_ranks([wall, dev_ms], dist, control_plane, device)
@@ -523,8 +574,8 @@ def main():
         dist.all_gather(got, t)
         result["per_rank_kernel_us"] = [float(v[0]) for v in got]
 
-    # ---- config 3: the EAGER per-call figure, always beside a fused-group line (outside the timed region) -------------
-    if args.config == "cfg3" and not dry and not args.batched and not args.no_eager_extra:
+    # ---- config 3 with --full: the EAGER per-call figure beside a fused-group line (outside the timed region) -------------
+    if args.full and args.config == "cfg3" and not dry and not args.batched and not args.no_eager_extra:
         try:
             holder_e = mq.PytorchActivationQuantizationHolder(quantizer).to(device)
             ring_e = max(2, -(-(512 << 20) // alg_bytes) + 1)
@@ -551,8 +602,8 @@ def main():
         except Exception as e:  # noqa: BLE001
             result["eager_us_per_batch"] = {"error": repr(e)[:200]}
 
-    # ---- per-launch evidence pass (outside the timed region) ---------------------------------------------
-    if args.evidence_launches > 0 and graph is None and streams is None and not dry:
+    # ---- --full: per-launch evidence pass (outside the timed region) ---------------------------------------------
+    if args.full and args.evidence_launches > 0 and graph is None and streams is None and not dry:
         try:
             periods = per_launch_periods(step, max(50, args.evidence_launches))[1:]     # first period: event after idle
             periods.sort()
@@ -581,34 +632,24 @@ def main():
         result["roofline"].update(bench_dist.traffic_fields(os.path.join(REPO, "profiles", "pmc_traffic.json"), key,
                                                             kernel_variant, build_id))
 
-    # ---- the last timed step's output, kept for the parity check before anything overwrites the ring ----------
-    last_slot = (n_launch - 1) % ring
-    if dry:
-        y_last = ys[last_slot]
-    elif stream_on:
-        y_last = act_streams[last_slot].outputs       # persistent outputs of the last timed replay
-    elif args.batched:
-        y_last = plan_outs[last_slot]       # persistent outputs; later passes rewrite them with the same values
-    else:
-        y_last = ys[last_slot]
-
-    # ---- every rank: its own last timed output against the REFERENCE's digest of this configuration ------------
+    # ---- --full, every rank: its own last timed output against the REFERENCE's digest of this configuration ------------
     # (tests/golden/full_sha.json: SHA-256 of the reference's float32 output on the same portable input).  The verdict
     # of every rank travels to rank 0 (ranks_parity_ok); one False fails the job.  None = no digest for this workload
     # (16-bit storage, model workloads).
-    own_parity = None
-    want_sha = None if (model_mode or args.dtype != "f32") else bench_dist.golden_output_digest(args.config, wl.shape, args.batch)
-    if want_sha is not None:
-        if isinstance(y_last, (list, tuple)):
-            own_parity = all(bench_dist.sha256_of(y) == want_sha for y in y_last[:2]) and \
-                all(bool(torch.equal(y, y_last[0])) for y in y_last[2:])
-        else:
-            own_parity = bench_dist.sha256_of(y_last) == want_sha
-    result["ranks_parity_ok"] = bench_dist.gather_flags(dist, own_parity, control_plane, device)
-    result["ranks_parity_is"] = ("per rank: SHA-256 of the output of its LAST timed step == the reference's digest "
-                                 "(tests/golden/full_sha.json); null = no digest recorded for this workload / storage type")
-    if any(v is False for v in result["ranks_parity_ok"]):
-        result["parity_error"] = f"ranks_parity_ok = {result['ranks_parity_ok']}: a rank's output differs from the reference's digest"
+    if args.full:
+        own_parity = None
+        want_sha = None if (model_mode or args.dtype != "f32") else bench_dist.golden_output_digest(args.config, wl.shape, args.batch)
+        if want_sha is not None:
+            if isinstance(y_last, (list, tuple)):
+                own_parity = all(bench_dist.sha256_of(y) == want_sha for y in y_last[:2]) and \
+                    all(bool(torch.equal(y, y_last[0])) for y in y_last[2:])
+            else:
+                own_parity = bench_dist.sha256_of(y_last) == want_sha
+        result["ranks_parity_ok"] = bench_dist.gather_flags(dist, own_parity, control_plane, device)
+        result["ranks_parity_is"] = ("per rank: SHA-256 of the output of its LAST timed step == the reference's digest "
+                                     "(tests/golden/full_sha.json); null = no digest recorded for this workload / storage type")
+        if any(v is False for v in result["ranks_parity_ok"]):
+            result["parity_error"] = f"ranks_parity_ok = {result['ranks_parity_ok']}: a rank's output differs from the reference's digest"
 
     # Extra (outside the judged region): the same K independent steps issued round-robin on two HIP streams,
     # which overlaps one kernel's tail with the next one's ramp.  Whole-job rate only; per-kernel durations
@@ -677,8 +718,8 @@ def main():
         except Exception as e:  # noqa: BLE001
             result["extras_error"] = repr(e)[:200]
 
-    # ---- default run at N = 1: the headline tensor 16 times in ONE batched launch (outside the judged region) -------
-    if (not dry and world == 1 and args.config == "cfg2" and args.dtype == "f32" and not args.batched and not args.no_batched_extra
+    # ---- --full at N = 1: the headline tensor 16 times in ONE batched launch (outside the judged region) -------
+    if (args.full and not dry and world == 1 and args.config == "cfg2" and args.dtype == "f32" and not args.batched and not args.no_batched_extra
             and graph is None and streams is None and hasattr(quantizer, "batch_item") and native.fast() is not None):
         try:
             T = 16
@@ -732,11 +773,11 @@ def main():
                 result["sharded_cfg5"] = {"error": repr(e)[:300]}
                 sharded_failed = repr(e)[:300]
 
-    if dist is not None and (args.gather or world > 1):
+    if dist is not None and (args.gather or (world > 1 and args.full)):
         run_sharded_leg(dist, control_plane, 300.0 if control_plane == "gloo" and not dry else 120.0, 4)
 
-    # CPU baseline: on rank 0, at every N (the other ranks are done; they leave through destroy_process_group below)
-    if rank == 0 and not args.no_cpu and not dry and model_mode:
+    # --full, CPU baseline: on rank 0, at every N (the other ranks are done; they leave through destroy_process_group below)
+    if args.full and rank == 0 and not args.no_cpu and not dry and model_mode:
         # CPU baseline of the model workloads: ATen's CPU operator on every weight in turn, oracle-derived parameters
         from oracle import torch_cpu
         fs = [torch_cpu.prepare("WeightsSymmetricInferableQuantizer", kw) for _, kw in weights]
@@ -760,7 +801,7 @@ def main():
                                   "gpu_output_checked": f"all {len(weights)} outputs of the last timed step"}
         if not same:
             result["parity_error"] = "GPU output differs from the CPU oracle"
-    elif rank == 0 and not args.no_cpu and not dry:
+    elif args.full and rank == 0 and not args.no_cpu and not dry:
         from oracle import torch_cpu
         f = torch_cpu.prepare(wl.quantizer, wl.kwargs)
         x_cpu = torch.from_numpy(x_np).to(tdtype)          # the same rounding to the storage type as on the device
@@ -804,8 +845,8 @@ def main():
         if not same:
             result["parity_error"] = "GPU output differs from the CPU oracle"
 
-    if dist is None and world == 1 and not args.no_sharded_extra and not model_mode and "sharded_cfg5" not in result:
-        # N = 1, no launcher: the same leg on a process group of one rank.  A failure here (no RCCL, a stuck init) costs the
+    if args.full and dist is None and world == 1 and not args.no_sharded_extra and not model_mode and "sharded_cfg5" not in result:
+        # --full at N = 1, no launcher: the same leg on a process group of one rank.  A failure here (no RCCL, a stuck init) costs the
         # leg, not the line: the watchdog prints the line as it stands and leaves with status 0.
         try:
             group, own_control = bench_dist.init_single_rank_group(device)

@@ -91,7 +91,7 @@ def test_plain_python_bench_gpus_2_launches_itself_and_emits_the_multi_rank_line
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "5", "--warmup", "2", "--device", "cpu"],
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--full", "--steps", "5", "--warmup", "2", "--device", "cpu"],
                        cwd=repo, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -162,7 +162,7 @@ def test_a_rank_whose_output_differs_from_the_reference_digest_fails_the_job(tmp
             doc = json.loads((d / "full_sha.json").read_text())
             doc["configs"]["cfg1"]["y_sha256"] = "f" * 64
             (d / "full_sha.json").write_text(json.dumps(doc))
-        r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--device", "cpu"],
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--full", "--steps", "3", "--warmup", "1", "--device", "cpu"],
                            cwd=repo, env=_clean_env(MCTQ_BENCH_GOLDEN_DIR=str(d)), capture_output=True, text=True, timeout=600)
         # rank 0 leaves with status 3; torch.distributed.run reports a failed child as its own status 1 and names the
         # child's status in its error table
@@ -216,18 +216,56 @@ def test_the_multi_rank_line_names_every_ranks_device_and_refuses_shared_ones():
 
 
 def test_the_single_rank_line_carries_the_three_sharded_series_too():
-    """compute-only, compute + all-gather and per-link figures at EVERY N.  At N = 1 without a launcher bench.py
+    """compute-only, compute + all-gather and per-link figures at EVERY N.  At N = 1 without a launcher bench.py --full
     forms a process group of one rank in-process and runs the same leg (per-link: null, no link is crossed); --no-sharded-extra
     skips it."""
-    out = _line(_bench(["--steps", "3", "--warmup", "1", "--device", "cpu"]))
+    out = _line(_bench(["--full", "--steps", "3", "--warmup", "1", "--device", "cpu"]))
     assert out["n_gpus"] == 1 and out["rank_devices"] and out["devices_distinct"] is True
     leg = out["sharded_cfg5"]
     assert leg["ranks"] == 1 and leg["gathered_rows_match_local"] is True and leg["ranks_shard_digest_ok"] == [True]
     assert leg["gathered_equals_reference_digest"] is True and "one rank" in leg["process_group"]
     assert out["sharded_cfg5_compute_elems_per_s"] > 0 and out["sharded_cfg5_compute_plus_allgather_elems_per_s"] > 0
     assert "sharded_cfg5_allgather_gbs_per_link" in out and out["sharded_cfg5_allgather_gbs_per_link"] is None
-    out = _line(_bench(["--steps", "3", "--warmup", "1", "--device", "cpu", "--no-sharded-extra"]))
+    out = _line(_bench(["--full", "--steps", "3", "--warmup", "1", "--device", "cpu", "--no-sharded-extra"]))
     assert "sharded_cfg5" not in out
+
+
+def test_a_plain_run_times_the_steps_and_dumps_the_last_output(tmp_path):
+    """Without --full the line carries the judged region's figures and none of the side legs (digest parity, sharded leg,
+    CPU baseline); --dump-outputs writes the last timed step's output, the same bytes on every run -- here the reference's
+    own output of config 1 (tests/golden/full_sha.json)."""
+    import hashlib
+    import numpy as np
+    import bench_dist
+    dumps = []
+    for run in ("a", "b"):
+        out = _line(_bench(["--steps", "4", "--warmup", "1", "--device", "cpu", "--dump-outputs", str(tmp_path / run)]))
+        assert out["steps"] == 4 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+        assert out["unit"] == "elems/s" and out["higher_is_better"] is True and out["dtype"] == "f32" and out["metric"]
+        for key in ("ranks_parity_ok", "sharded_cfg5", "cpu_baseline", "batched_16x4096", "parity_error"):
+            assert key not in out, key
+        assert sorted(os.listdir(tmp_path / run)) == ["output.npy"]
+        dumps.append(np.load(tmp_path / run / "output.npy"))
+    y = dumps[0]
+    assert y.dtype == np.float32 and list(y.shape) == out["config"]["shape"]
+    assert y.tobytes() == dumps[1].tobytes()
+    assert hashlib.sha256(y.tobytes()).hexdigest() == bench_dist.golden_output_digest("cfg1", y.shape)
+
+
+def test_dump_outputs_samples_large_outputs_under_the_budget(tmp_path):
+    """Outputs beyond 64 MB in all are replaced by a fixed seeded sample of flat indices, in index order, float64 kept."""
+    import numpy as np
+    import bench
+    x = torch.arange(4096 * 4096, dtype=torch.float32).reshape(4096, 4096)      # every value is its own flat index
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), [x, torch.zeros(3, dtype=torch.float64)])
+        files = sorted(os.listdir(tmp_path / run))
+        assert files == ["output_000.npy", "output_001.npy"]
+        assert sum(os.path.getsize(tmp_path / run / f) for f in files) <= 64 * 10**6
+    a, b = (np.load(tmp_path / run / "output_000.npy") for run in ("a", "b"))
+    assert a.dtype == np.float32 and a.ndim == 1 and 10**7 < a.size < x.numel() and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0) and a[-1] < x.numel()                          # distinct flat indices, in order
+    assert np.load(tmp_path / "a" / "output_001.npy").dtype == np.float64
 
 
 def test_device_identity_helpers():

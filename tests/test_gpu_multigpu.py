@@ -56,7 +56,7 @@ def test_bench_multi_process_leg_runs_over_rccl_on_one_gpu(lib):
         port = sk.getsockname()[1]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", "1", "--gather", "--steps", "20", "--warmup", "5",
+           "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", "1", "--gather", "--full", "--steps", "20", "--warmup", "5",
            "--no-cpu", "--prewarm-seconds", "0.2", "--evidence-launches", "0"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=REPO)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -109,7 +109,7 @@ def _bench_wrapped(n, *flags, env_extra=None, timeout=1500, wrap_env=True):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.pop("MCTQ_BENCH_WRAP_DEVICES", None)
     env.update(**({"MCTQ_BENCH_WRAP_DEVICES": "1"} if wrap_env else {}), **(env_extra or {}))
-    return subprocess.run([sys.executable, "bench.py", "--gpus", str(n), "--steps", "20", "--warmup", "5", "--prewarm-seconds", "0.1",
+    return subprocess.run([sys.executable, "bench.py", "--gpus", str(n), "--full", "--steps", "20", "--warmup", "5", "--prewarm-seconds", "0.1",
                            "--evidence-launches", "0", *flags], cwd=REPO, env=env, capture_output=True, text=True, timeout=timeout)
 
 
