@@ -485,13 +485,21 @@ int mctq_qlinear_w4a8(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_
  *   key "paced" : the affine per-tensor launch through flat_paced_kernel (flat_kernel's tile under another order of waits: loads
  *                  128 clocks apart, every load landed before the first store, every store completed before the next lane-vector):
  *                  0 = never, 1 (default) = launches that fill 3/4 ... 1 round of resident blocks, where it measured 4-6 % faster
- *                  (48-64 MiB of traffic on this chip; 3-9 % slower outside), 2 = every launch with a full four-vector tile.
+ *                  (48-64 MiB of traffic on this chip; 3-9 % slower outside), 2 = every launch for which launch_flat chooses the
+ *                  four-vector tile (at least two such blocks per CU; smaller tensors keep flat_kernel's narrower tiles).
  *                  The same key sends symmetric float32 per-channel launches of that window (whole-vector rows) through
  *                  shortrows_kernel with paced stores: 2048 x 4096 12.4 -> 11.3 us, 32768 x 256 12.3 -> 11.3 (16-bit: not taken, +3 %)
  *   key "shortrows" : affine per-channel tensors through shortrows_kernel (per-lane parameter reads behind the tile's data loads,
  *                  no LDS window): 0 = never, 1 (default) = where it measured faster (16-bit storage: every short or ragged row
  *                  shape, and long rows of launches that fill 7/8 ... 1 round of resident blocks; float32: rows of 4 ... 31
  *                  elements), 2 = every eligible tensor (rows of at least one lane-vector, fewer than 2^24 elements per row)
+ *   key "filldrain" : symmetric float32 per-channel rows that are a whole number of four-vector tiles (4096 elements) through
+ *                  rows_kernel_finetail: rows_kernel's blocks, the last half round of tiles of the launch cut into four blocks of one
+ *                  lane-vector per lane each, so that the end of the launch is spread over four times as many blocks and CUs:
+ *                  0 = never (rows_kernel), 1 (default) = launches of at least 9/8 rounds of resident blocks (8 per CU), where it
+ *                  measured faster (4096 x 4096 22.2 -> 21.55 us; 1-4 % up to four rounds, 0.2-0.8 % at six and eight), 2 = every
+ *                  eligible launch that reaches the rows shape (those inside the "paced" window go to that kernel first).
+ *                  Launches with a zero-point table and 16-bit storage are never eligible.
  * Only variants a default dispatcher can select are instantiated; every value of every key is exercised by the GPU tests.
  * Returns 0, or MCTQ_E_ARG for an unknown key/value.  Numerical results never depend on it.
  */

@@ -994,6 +994,50 @@ __global__ __launch_bounds__(kThreads) void rowsteps_kernel(const TI* __restrict
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// rows_kernel_finetail (tuning key "filldrain"): rows_kernel's launch for symmetric float32 rows that are a whole number of
+// four-vector tiles, with the END of the launch cut finer.  Tiles are numbered in storage order, tile t = (row t / tiles_per_row,
+// t % tiles_per_row): the first `bulk` tiles are rows_kernel's blocks as they are (256 lanes x 4 lane-vectors, 16 KiB in and
+// out); each tile behind them is FOUR blocks of one lane-vector per lane.  A launch of more than one round of resident blocks ends
+// on whatever blocks are left on whichever CUs, at 3.3-5.5 TB/s against 7.2 TB/s mid-launch; with the last half round of tiles in
+// quarters the same bytes lie on four times as many blocks and every CU keeps work until the end.  Config 2 (4096 x 4096, two
+// rounds) 22.2 -> 21.55 us per launch, 1.125 ... 4 rounds 1-4 % faster, six and eight rounds 0.2-0.8 % (profiles/EXPERIMENTS.md
+// round 7, profiles/r07/; timeline: tools/kbench_filldrain.hip).  What did NOT pay in the library, measured the same way: two
+// tiles per block (+2 %), two-vector pieces (half the gain), a fine HEAD as well (+1 ... +3 %), the pieces in scattered order
+// (gain lost), a tail of a whole round (half the gain), a whole launch of one-vector tiles (+2 ... +8 %).
+// Every block is rows_kernel's one_tile (full tile: no lane guards), the row's scale in a scalar register: the same arithmetic
+// call for call.  The scale is REQUESTED (one scalar load, table pointer in a preloaded argument) in front of the data loads and
+// waited for where one_tile asks for the parameters, behind them: once the compiler has laid the kernel's two branches one behind
+// the other, a table read that follows the other branch's stores would be compiled as a vector load, returning in order behind
+// the tile's data (tests/test_rows_finetail_schedule.py asserts the schedule).  Where it is taken: launch_channels, tuning key "filldrain".
+// ------------------------------------------------------------------------------------------
+template <class TI, class TO, int NT>
+__global__ __launch_bounds__(kThreads) void rows_kernel_finetail(const TI* __restrict__ xs, TO* __restrict__ ys,
+                                                          const float* __restrict__ scales /* = op.scales */,
+                                                          uint32_t tiles_per_row, uint32_t innerv, uint32_t channels,
+                                                          uint32_t bulk, AffineOp op /* symmetric: zps == NULL */) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  constexpr uint32_t TILE = kThreads * 4;
+  const bool fine = blockIdx.x >= bulk;                      // uniform
+  const uint32_t piece = blockIdx.x - bulk;
+  const uint32_t t = fine ? bulk + piece / 4 : blockIdx.x;
+  uint32_t row = t, tile = 0;
+  if (tiles_per_row != 1) {                                  // uniform branch: skip the division for 1 tile/row
+    row = t / tiles_per_row;
+    tile = t - row * tiles_per_row;
+  }
+  uint32_t c = row;
+  if (c >= channels) c = row % channels;                     // uniform; outer == 1 needs no modulo
+  const float s = scales[c];
+  const int64_t rbase = (int64_t)row * innerv;
+  auto get_param = [&]() { return AffineOp::make(s, 0); };   // AffineOp::fetch of a launch without zero points
+  if (!fine)
+    one_tile<true, AffineOp, TI, TO, 4, NT>(op, smem, xs, ys, rbase + tile * TILE + threadIdx.x, rbase + innerv, get_param);
+  else
+    one_tile<true, AffineOp, TI, TO, 1, NT>(op, smem, xs, ys, rbase + tile * TILE + (piece % 4) * kThreads + threadIdx.x,
+                                            rbase + innerv, get_param);
+}
+
 // n / d for n < 2^24 (exactly representable in float32) and a wave-uniform d with r = 1.0f / d: the float quotient
 // is off by at most one, two integer corrections make it exact -- 7 VALU ops instead of the ~25 of a 32-bit
 // unsigned division.  The window kernel's positions are offsets inside one tile (+ one row).
@@ -1086,8 +1130,9 @@ __global__ __launch_bounds__(kThreads) void lastaxis_kernel(const TI* __restrict
 }
 
 // ------------------------------------------------------------------------------------------
-// shortrows (affine quantizers): per-channel rows shorter than a tile that are at least one lane-vector long -- 16-bit
-// tensors whose rows are not whole 8-element vectors (1020- or 4100-wide) or are shorter than 64 elements, float32 rows of
+// shortrows (affine quantizers): per-channel rows of at least one lane-vector laid over tiles of the dense storage -- what
+// launch_channels sends here: 16-bit tensors with short or ragged rows of EVERY length (whole-vector rows of 64 ... 2040 elements
+// included), 16-bit long rows and symmetric float32 rows of launches that fill 7/8 (3/4) ... 1 round, float32 rows of
 // 4 ... 31 elements.  Block b owns elements [b * TILE, (b + 1) * TILE) of the dense [rows][inner] storage; a lane-vector
 // lies in one row or crosses exactly one row boundary.  No LDS window, no block barrier: after the tile's data loads every
 // lane reads its own row's scale (and, where vectors can cross, the next row's) from the L1 / L2-resident tables -- all
@@ -1097,7 +1142,8 @@ __global__ __launch_bounds__(kThreads) void lastaxis_kernel(const TI* __restrict
 // some 200 instructions of row arithmetic lie between two stores; see flat_paced_kernel and the `paced` argument below.)
 // Measured against window_kernel (tools/experiments/chanlast2/, profiles/r06/chanlast2_a.log): bfloat16 16384 x 1020
 // 13.7 -> 12.5 us, 4096 x 4100 13.3 -> 12.3, 1048576 x 16 13.5 -> 13.0, float32 1048576 x 16 23.9 -> 22.1; whole-vector
-// 16-bit rows of 64 ... 2040 elements are equal or slower and stay with the window.  Reading the parameters BEFORE the data
+// 16-bit rows of 64 ... 2040 elements looked equal or slower in that first probe, and 4-9 % FASTER in the A / B of the shipped
+// library (profiles/r06/ab_shortrows3.log: 16384 x 1024 12.6 -> 11.8 us), so they come here too.  Reading the parameters BEFORE the data
 // (vector loads return in order) was slower in every case: the data loads must not wait for the row arithmetic.
 // ------------------------------------------------------------------------------------------
 template <class TI, int U, int NT, bool ZP, bool WHOLE>
@@ -1332,6 +1378,8 @@ extern int g_paced;          // launches of 3/4 ... 1 round under the paced orde
                              // `paced` argument per channel): 0 never, 1 (default) inside that window, 2 whenever the kernel is taken
 extern int g_shortrows;      // rows shorter than a tile through shortrows_kernel: 0 never, 1 (default) where it measured faster, 2 whenever eligible
 extern int g_rowsteps;       // short whole-step rows: 0 rows_kernel, 1 rowsteps_kernel, 2 (default) rowsteps_kernel when its grid is one round
+extern int g_filldrain;      // symmetric float32 rows of whole four-vector tiles with a finer end of the launch (rows_kernel_finetail): 0 never,
+                             // 1 (default) launches of at least 9/8 rounds of resident blocks, 2 whenever eligible
 extern int g_heavy_unroll;   // 0 = automatic
 int fail_arg(const char* msg);
 int check_launch(const char* what);
@@ -1596,6 +1644,26 @@ static int launch_channels(const Op& op, const void* xv, void* yv, int64_t outer
             note<Op, TI, TO>("rowsteps_kernel", U, NT);
           });
           return check_launch("rowsteps launch");
+        }
+      }
+      if constexpr (std::is_same<Op, AffineOp>::value && std::is_same<TI, float>::value && std::is_same<TO, float>::value) {
+        // symmetric float32 rows of whole four-vector tiles: the last half round of tiles as one-vector blocks (rows_kernel_finetail).
+        // Tuning key "filldrain": 0 never, 1 (default) launches of at least 9/8 rounds of resident blocks, 2 whenever eligible.
+        // Measured (A / B in one process against the parent build, profiles/r07/ab_parent_vs_*.log): 2304 x 4096 (9/8 rounds) -2.8 %,
+        // 2560 x 4096 -2.9 %, 3072 x 4096 -3.8 %, 4096 x 4096 / 1024 x 16384 / 256 x 65536 -3.0 %, 6144 x 4096 -2.1 %, 8192 x 4096 and
+        // 4096 x 8192 -1.0 %, 12288 x 4096 -0.7 %, 16384 x 4096 -0.2 %.  Below: launches of 3/4 ... 1 round never get here (paced
+        // shortrows_kernel above), 1280 x 4096 (5/8 of a round: more than half of the launch in quarters) +8 %, 1024 x 4096 and
+        // 512 x 4096 (the whole launch in quarters) +0.8 % / equal -- so the rule starts above one round.
+        const int64_t total = rows * (innerv / (kThreads * 4)), round = 8LL * cu_count();
+        if ((g_filldrain == 2 || (g_filldrain == 1 && total * 8 >= round * 9)) && !op.zps && best_u == 4 &&
+            innerv % (kThreads * 4) == 0 && total * 4 <= 0x7fffffffLL && innerv <= 0x7fffffffLL) {
+          const int64_t tail = total < round / 2 ? total : round / 2, bulk = total - tail;
+          MCTQ_WITH_MODE(nt_mode(n * (int64_t)sizeof(TO)), {
+            hipLaunchKernelGGL((rows_kernel_finetail<TI, TO, NT>), dim3((unsigned)(bulk + tail * 4)), dim3(kThreads), book_bytes, st, x, y,
+                               op.scales, (uint32_t)(innerv / (kThreads * 4)), (uint32_t)innerv, (uint32_t)channels, (uint32_t)bulk, op);
+            note<Op, TI, TO>("rows_kernel_finetail", 4, NT);
+          });
+          return check_launch("rows finetail launch");
         }
       }
       if (!(std::is_same<TI, float>::value && std::is_same<TO, float>::value) && best_u < 2) best_u = 2;   // built: U = 2, 4

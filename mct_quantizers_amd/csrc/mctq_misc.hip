@@ -18,6 +18,7 @@ int g_unroll = 4;
 int g_heavy_unroll = 0;
 int g_rowsteps = 2;           // 2: rowsteps_kernel only where it measured faster (see launch_channels)
 int g_paced = 1;              // launches of 3/4 ... 1 round under the paced order of waits: 0 never, 1 inside the window, 2 whenever the kernel is taken (launch_flat, launch_channels)
+int g_filldrain = 1;          // symmetric float32 rows of whole tiles, last half round of tiles in quarters (rows_kernel_finetail): 0 never, 1 from 9/8 rounds, 2 whenever eligible (launch_channels)
 int g_shortrows = 1;          // short / ragged rows through shortrows_kernel: 0 never, 1 the measured rule, 2 whenever eligible (launch_channels)
 int g_ql_variant = 0;
 int g_ql_band = 0;
@@ -173,6 +174,11 @@ int mctq_set_tuning(const char* key, int32_t value) {
   if (!strcmp(key, "shortrows")) {
     if (value != 0 && value != 1 && value != 2) return fail_arg("shortrows must be 0, 1 or 2");
     g_shortrows = value;
+    return 0;
+  }
+  if (!strcmp(key, "filldrain")) {
+    if (value != 0 && value != 1 && value != 2) return fail_arg("filldrain must be 0, 1 or 2");
+    g_filldrain = value;
     return 0;
   }
   if (!strcmp(key, "rowsteps")) {

@@ -6,7 +6,9 @@ of the two arms compared bit for bit.
 
     python tools/ab_probe.py --a shipped --b sched1 --cases affine          (B = tools/ablate/libmctq_hip_sched1.so)
     python tools/ab_probe.py --a shipped --b shipped:shortrows=3 --cases affine16,affine32
-    python tools/ab_probe.py --a shipped --b lut16wide --cases lut16"""
+    python tools/ab_probe.py --a shipped --b lut16wide --cases lut16
+    python tools/ab_probe.py --a parent --b shipped --cases filldrain,filldrain_edges   (A = another commit's library copied to
+                                                                                          tools/ablate/libmctq_hip_parent.so)"""
 import argparse, ctypes, os, sys, time
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
@@ -36,7 +38,7 @@ def arm(spec):
 
     def apply(reset=False):
         for k, v in keys:
-            assert lib.mctq_set_tuning(k.encode(), {"shortrows": 1, "paced": 1, "rowsteps": 2, "unroll": 4, "nt": 1}.get(k, 0) if reset else int(v)) == 0, (k, v)
+            assert lib.mctq_set_tuning(k.encode(), {"shortrows": 1, "paced": 1, "rowsteps": 2, "unroll": 4, "nt": 1, "filldrain": 1}.get(k, 0) if reset else int(v)) == 0, (k, v)
     return spec, lib, apply
 
 
@@ -100,6 +102,14 @@ PACEDROWS32 = [("pc0", 2048, 4096), ("pc0", 1792, 4096), ("pc0", 1536, 4096), ("
                ("pc0", 131072, 64), ("pc0", 7168, 1024), ("pc0", 1024, 8192), ("pc0", 8192, 1020), ("pc0", 2056, 4096), ("pc0", 1408, 4096)]
 PACEDROWS16 = [("pc0", 4096, 4096), ("pc0", 16384, 1024), ("pc0", 65536, 256), ("pc0", 262144, 64), ("pc0", 14336, 1024), ("pc0", 12288, 1024),
                ("pc0", 1048576, 16), ("pc0", 16384, 1020), ("pc0", 3584, 4096), ("pc0", 4104, 4096)]
+# config 2 and the neighbours a rule for launches of two or more rounds of float32 row tiles could catch (round 7); the per-tensor
+# and bfloat16 launches of the same size are controls that no such rule may move
+FILLDRAIN32 = [("pc0", 4096, 4096), ("pc0", 8192, 4096), ("pc0", 6144, 4096), ("pc0", 4096, 8192), ("pc0", 3072, 4096), ("pc0", 2048, 4096),
+               ("pc0", 16384, 1024), ("pt", 4096, 4096)]
+# ... and where such a rule has to stop: half a round ... 1.25 rounds (3/4 ... 1 round is the paced window's), eight rounds, rows of
+# four tiles, a wrapped channel table
+FILLDRAIN32_EDGES = [("pc0", 512, 4096), ("pc0", 1024, 4096), ("pc0", 1280, 4096), ("pc0", 2304, 4096), ("pc0", 2560, 4096), ("pc0", 12288, 4096),
+                     ("pc0", 16384, 4096), ("pc0", 1024, 16384), ("pc0", 256, 65536)]
 ROUNDS = [("pc0", 8192, 2048), ("pc0", 6144, 4096), ("pc0", 8192, 4096), ("pc0", 12288, 4096), ("pc0", 16384, 4096), ("pc0", 4096, 2048),
           ("pc0", 2048, 3072), ("pc0", 1024, 4096), ("pc0", 512, 4096)]
 
@@ -174,5 +184,9 @@ for c in args.cases.split(","):
     elif c == "ragged32": affine_cases(["f32"], [("pc0", 1048576, 13), ("pc0", 2097152, 7), ("pc0", 1048576, 16)])
     elif c == "rounds16": affine_cases(["bf16"], ROUNDS)
     elif c == "rounds32": affine_cases(["f32"], ROUNDS)
+    elif c == "filldrain":
+        affine_cases(["f32"], FILLDRAIN32)
+        affine_cases(["bf16"], [("pc0", 4096, 4096)])
+    elif c == "filldrain_edges": affine_cases(["f32"], FILLDRAIN32_EDGES)
     elif c == "lut16": lut16_cases()
     else: raise SystemExit(f"unknown case set {c}")
