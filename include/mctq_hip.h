@@ -57,7 +57,9 @@ extern "C" {
 /* v9 (round 6): + mctq_selftest_reciprocal, + tuning keys "shortrows", "paced"; the channel-last (lastaxis) launch and the new launch of
  * short / ragged per-channel rows (shortrows) invert a lane's own scales with a five-instruction exact reciprocal (no signature
  * changed; results are bit-identical). */
-#define MCTQ_ABI_VERSION 9
+/* v10: + codebook-index codes of the LUT quantizers and their decode (mctq_lut_build_index_table, mctq_lut_codes_per_tensor /
+ * _per_channel, mctq_lut_decode_per_tensor / _per_channel); no existing signature or result changed. */
+#define MCTQ_ABI_VERSION 10
 #define MCTQ_E_ARG (-10001)
 
 /* storage types of x (and of y for the affine entry points); arithmetic is always float32 */
@@ -355,6 +357,60 @@ int mctq_lutt_per_channel(const void* x, float* y,
                           const float* table, int32_t entries,
                           float mult, float clip_min, float clip_max,
                           void* stream);
+
+/*
+ * Codebook-index codes of the LUT quantizers and their decode (an extension: the reference has no counterpart, as for the
+ * integer codes of the affine quantizers above).  For an element x with threshold thr (its channel's, or the tensor's):
+ *     t    = clip((x / fl32(thr + eps)) * mult, clip_min, clip_max)          as the mctq_lut_* entry points compute it
+ *     code = first index j (caller's list order) minimising fl32(|t - lut[j]|);  NaN input -> 0       (torch.argmin)
+ *     decode(code) = (lut[code] / mult) * thr                                  two float32 operations
+ * so decode(encode(x)) is bit-identical to the fake-quantized value of the mctq_lut_* / mctq_lutt_* entry points for every
+ * input.  Duplicate centres yield the FIRST occurrence; two different centres at equal distance the one listed first.
+ * Codes are uint8 (MCTQ_CODE_U8, n_lut <= 256) or packed 4-bit (MCTQ_CODE_U4, n_lut <= 16: two codes per byte, element 2j of
+ * the storage order in the low nibble; layouts as for the affine 4-bit codes: per tensor n % 8 == 0, per channel
+ * inner % 8 == 0, or inner == 1 with channels % 8 == 0; x / y 16-byte and codes 4-byte aligned).
+ *   mctq_lut_build_index_table : as mctq_lut_build_table (same K, same thresholds T_k bit for bit, same refusals), but
+ *                            word 1 of entry k is index_below | index_above << 16 (first occurrence of the centre in list
+ *                            order) and the trailer is {0 (index for NaN input), K}.
+ *   mctq_lut_codes_per_tensor / _per_channel : x float32 / float16 / bfloat16 (dtype), codes out.  `lut` (DEVICE, n_lut
+ *                            floats, list order) is always given; `index_table` (DEVICE copy of the table above, `entries`
+ *                            = K) is optional (NULL: the literal scan carrying the index -- any codebook, slower).
+ *                            step_round as mctq_lutt_per_tensor.  5 algorithmic bytes per float32 element (4.5 packed).
+ *   mctq_lut_decode_per_tensor / _per_channel : codes in, y float32 out; every block stages lut[j] / mult once and each
+ *                            element costs one table read and one multiplication by its threshold.  A code >= n_lut
+ *                            (never produced by the encoders) reads as code 0 ... 255 of a zero-padded table.
+ * Conventions of every entry point (caller-owned device pointers, stream order, legal under graph capture, no allocation,
+ * mctq_last_launch / mctq_launch_count, MCTQ_E_ARG without a GPU, empty tensors launch nothing) hold; the size limit above
+ * (2^32 - 8192 elements in short rows) applies to the per-channel encode, and the decode takes at most 2^32 - 8192 elements
+ * per launch in any layout.
+ */
+int mctq_lut_build_index_table(const float* lut_host, int32_t n_lut, float mult, float clip_min, float clip_max,
+                               float* table_host);
+
+int mctq_lut_codes_per_tensor(const void* x, void* codes, int64_t n, int32_t dtype, int32_t code_dtype, int32_t step_round,
+                              float thr_div,
+                              const float* lut, int32_t n_lut,
+                              const float* index_table, int32_t entries,
+                              float mult, float clip_min, float clip_max,
+                              void* stream);
+
+int mctq_lut_codes_per_channel(const void* x, void* codes,
+                               int64_t outer, int64_t channels, int64_t inner, int32_t dtype, int32_t code_dtype,
+                               const float* thresholds, float eps,
+                               const float* lut, int32_t n_lut,
+                               const float* index_table, int32_t entries,
+                               float mult, float clip_min, float clip_max,
+                               void* stream);
+
+int mctq_lut_decode_per_tensor(const void* codes, float* y, int64_t n, int32_t code_dtype,
+                               const float* lut, int32_t n_lut, float mult, float thr_mul,
+                               void* stream);
+
+int mctq_lut_decode_per_channel(const void* codes, float* y,
+                                int64_t outer, int64_t channels, int64_t inner, int32_t code_dtype,
+                                const float* lut, int32_t n_lut, float mult,
+                                const float* thresholds,
+                                void* stream);
 
 /*
  * Threshold-list ("steps") form of the LUT quantizer: INTEGER codebooks whose clip range is too large for the decision

@@ -20,6 +20,12 @@ int mctq_lut_build_table(const float* lut_host, int32_t n_lut, float mult, float
   return 0;
 }
 
+int mctq_lut_build_index_table(const float* lut_host, int32_t n_lut, float mult, float clip_min, float clip_max,
+                               float* table_host) {
+  if (const char* err = mctq_tb::build_index(lut_host, n_lut, mult, clip_min, clip_max, table_host)) return fail_arg(err);
+  return 0;
+}
+
 int mctq_lutt_per_tensor(const void* x, float* y, int64_t n, int32_t dtype, int32_t step_round, float thr_div,
                          float thr_mul, const float* table, int32_t entries, float mult, float clip_min,
                          float clip_max, void* stream) {

@@ -22,6 +22,17 @@ inline float literal(float t, const float* lut, int n) {
   }
   return best_c;
 }
+// the same scan carrying the index beside the best distance: what torch.argmin returns (first minimum in list order,
+// so the FIRST occurrence of a duplicated centre; index 0 for a NaN, whose distances never win a strict '<')
+inline int literal_index(float t, const float* lut, int n) {
+  int best_j = 0;
+  float best_d = fabsf(t - lut[0]);
+  for (int j = 1; j < n; ++j) {
+    const float d = fabsf(t - lut[j]);
+    if (d < best_d) { best_d = d; best_j = j; }
+  }
+  return best_j;
+}
 
 // order-preserving map float <-> uint32 (finite values)
 inline uint32_t f2ord(float f) { uint32_t u; memcpy(&u, &f, 4); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
@@ -65,8 +76,11 @@ inline int table_entries(float cmin, float cmax) {
   return (int)k;
 }
 
-// Fills table[2 * (K + 1)] words; returns NULL on success or a static message.
-inline const char* build(const float* lut, int n_lut, float mult, float clip_min, float clip_max, float* table) {
+// Fills table[2 * (K + 1)] words; returns NULL on success or a static message.  One bisection, two payloads: word 1 of
+// entry k is half2(q_below, q_above) (INDEX false: the value table) or index_below | index_above << 16 (INDEX true: the
+// index table, first occurrence of the centre in list order); the thresholds T_k are the same words either way.
+template <bool INDEX>
+inline const char* build_impl(const float* lut, int n_lut, float mult, float clip_min, float clip_max, float* table) {
   if (!lut || !table) return "NULL pointer";
   if (n_lut < 1 || n_lut > 4096) return "n_lut must be in [1, 4096]";
   int e = 0;
@@ -100,13 +114,27 @@ inline const char* build(const float* lut, int n_lut, float mult, float clip_min
     const float qb = cb / mult, qa = ca / mult;
     const uint16_t hb = f32_to_f16(qb), ha = f32_to_f16(qa);
     if (f16_to_f32(hb) != qb || f16_to_f32(ha) != qa) return "codebook centre not exact in fp16";
-    const uint32_t pair = (uint32_t)hb | ((uint32_t)ha << 16);
+    uint32_t pair = (uint32_t)hb | ((uint32_t)ha << 16);
+    if (INDEX) {
+      // the scan's index is the first occurrence of the centre it returns (a later duplicate never wins the strict '<')
+      const uint32_t ib = (uint32_t)literal_index(lo, lut, n_lut), ia = (uint32_t)literal_index(hi, lut, n_lut);
+      if (lut[ib] != cb || lut[ia] != ca) return "codebook decision is not a single step";
+      pair = ib | (ia << 16);                          // n_lut <= 4096: both fit 16 bits
+    }
     table[2 * k + 0] = T;
     memcpy(&table[2 * k + 1], &pair, 4);
   }
-  table[2 * K + 0] = lut[0] / mult;                  // NaN input: every distance is NaN, argmin = index 0
+  // NaN input: every distance is NaN, argmin = index 0
+  if (INDEX) memset(&table[2 * K + 0], 0, 4);
+  else table[2 * K + 0] = lut[0] / mult;
   table[2 * K + 1] = (float)K;
   return nullptr;
+}
+inline const char* build(const float* lut, int n_lut, float mult, float clip_min, float clip_max, float* table) {
+  return build_impl<false>(lut, n_lut, mult, clip_min, clip_max, table);
+}
+inline const char* build_index(const float* lut, int n_lut, float mult, float clip_min, float clip_max, float* table) {
+  return build_impl<true>(lut, n_lut, mult, clip_min, clip_max, table);
 }
 
 // ---- threshold list ("steps") for integer codebooks of any clip range (LutStepsOp in mctq_kernels.hpp) ----------

@@ -20,12 +20,14 @@ PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REPO = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 # slowest translation units first (they are started in this order; the build's critical path is mctq_batched_lut.hip, ~35 s)
-SOURCES = [os.path.join(CSRC, f) for f in ("mctq_batched_lut.hip", "mctq_lut_steps.hip", "mctq_lut_table.hip", "mctq_lut_scan.hip",
+SOURCES = [os.path.join(CSRC, f) for f in ("mctq_batched_lut.hip", "mctq_lut_steps.hip", "mctq_lut_codes.hip", "mctq_lut_codes_scan.hip",
+                                             "mctq_lut_codes4.hip", "mctq_lut_table.hip", "mctq_lut_scan.hip", "mctq_lut_decode.hip",
                                              "mctq_qlinear.hip", "mctq_batched.hip", "mctq_affine.hip", "mctq_codes.hip",
                                              "mctq_f64.hip", "mctq_grid.hip", "mctq_codes4.hip", "mctq_codes_nhwc.hip",
                                              "mctq_misc.hip")]
 HEADERS = [os.path.join(REPO, "include", "mctq_hip.h"), os.path.join(CSRC, "mctq_kernels.hpp"),
-           os.path.join(CSRC, "mctq_table_builder.h"), os.path.join(CSRC, "mctq_batched.hpp")]
+           os.path.join(CSRC, "mctq_table_builder.h"), os.path.join(CSRC, "mctq_batched.hpp"),
+           os.path.join(CSRC, "mctq_lut_index.hpp")]
 OUT = os.path.join(PKG, "lib", "libmctq_hip.so")
 BINDING_SRC = os.path.join(CSRC, "binding", "mctq_torch.cpp")
 BINDING_OUT = os.path.join(PKG, "lib", "_mctq_torch.so")

@@ -14,7 +14,7 @@ import ctypes
 import os
 import threading
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 DT_F32, DT_F16, DT_BF16, DT_F64 = 0, 1, 2, 3
 CODE_I8, CODE_U8, CODE_I4, CODE_U4 = 0, 1, 2, 3
 FQ_ITEM_PER_TENSOR = 1
@@ -124,6 +124,21 @@ SIGNATURES = {
     "mctq_lut_table_entries": (ctypes.c_int32, [ctypes.c_float, ctypes.c_float]),
     "mctq_lut_build_table": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_float,
                                             ctypes.c_float, ctypes.c_void_p]),
+    "mctq_lut_build_index_table": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_float,
+                                                  ctypes.c_float, ctypes.c_void_p]),
+    "mctq_lut_codes_per_tensor": (ctypes.c_int, [_c_f32p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                                 ctypes.c_int32, ctypes.c_float, _c_f32p, ctypes.c_int32, _c_f32p,
+                                                 ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                                 ctypes.c_void_p]),
+    "mctq_lut_codes_per_channel": (ctypes.c_int, [_c_f32p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                                  ctypes.c_int32, ctypes.c_int32, _c_f32p, ctypes.c_float, _c_f32p,
+                                                  ctypes.c_int32, _c_f32p, ctypes.c_int32, ctypes.c_float, ctypes.c_float,
+                                                  ctypes.c_float, ctypes.c_void_p]),
+    "mctq_lut_decode_per_tensor": (ctypes.c_int, [ctypes.c_void_p, _c_f32p, ctypes.c_int64, ctypes.c_int32, _c_f32p,
+                                                  ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_void_p]),
+    "mctq_lut_decode_per_channel": (ctypes.c_int, [ctypes.c_void_p, _c_f32p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                                   ctypes.c_int32, _c_f32p, ctypes.c_int32, ctypes.c_float, _c_f32p,
+                                                   ctypes.c_void_p]),
     "mctq_lut_steps_f64_bytes": (ctypes.c_int32, [ctypes.c_int32]),
     "mctq_lut_build_steps_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_float,
                                                 ctypes.c_float, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]),
@@ -342,6 +357,24 @@ def build_lut_table(lut_values, mult: float, clip_min: float, clip_max: float):
     lut = np.ascontiguousarray(np.asarray(lut_values, dtype=np.float32).reshape(-1))
     table = np.zeros((k + 1, 2), dtype=np.float32)
     rc = lib.mctq_lut_build_table(lut.ctypes.data, lut.size, mult, clip_min, clip_max, table.ctypes.data)
+    if rc != 0:
+        return None
+    return table
+
+
+def build_lut_index_table(lut_values, mult: float, clip_min: float, clip_max: float):
+    """Host-side INDEX decision table for an integer codebook (numpy float32 [K+1, 2]: the thresholds of
+    ``build_lut_table`` bit for bit; the second word of an entry is index_below | index_above << 16, first occurrence
+    of the centre in list order; trailer {0, K}), or None when the codebook / clip range does not qualify (the literal
+    index scan is used then).  See include/mctq_hip.h: mctq_lut_build_index_table."""
+    import numpy as np
+    lib = load()
+    k = lib.mctq_lut_table_entries(clip_min, clip_max)
+    if k < 0:
+        return None
+    lut = np.ascontiguousarray(np.asarray(lut_values, dtype=np.float32).reshape(-1))
+    table = np.zeros((k + 1, 2), dtype=np.float32)
+    rc = lib.mctq_lut_build_index_table(lut.ctypes.data, lut.size, mult, clip_min, clip_max, table.ctypes.data)
     if rc != 0:
         return None
     return table

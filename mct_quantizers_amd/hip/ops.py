@@ -593,6 +593,202 @@ def make_lut_table(lut_values, mult: float, cmin: float, cmax: float, device):
     return torch.from_numpy(table).to(device)
 
 
+_index_tables = {}
+
+
+def make_lut_index_table(lut_values, mult: float, cmin: float, cmax: float, device):
+    """Device copy of the codebook's INDEX decision table (include/mctq_hip.h: mctq_lut_build_index_table), or None
+    (CPU working device, non-integer codebook, clip range too wide: the literal index scan is used then).  Cached per
+    codebook contents, domain and device: quantizers that share a codebook share the table."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        return None
+    import numpy as np
+    lut = np.ascontiguousarray(np.asarray(lut_values, dtype=np.float32).reshape(-1))
+    key = (lut.tobytes(), float(mult), float(cmin), float(cmax), str(dev))
+    if key in _index_tables:
+        return _index_tables[key]
+    table = native.build_lut_index_table(lut, mult, cmin, cmax)
+    out = None if table is None else torch.from_numpy(table).to(dev)
+    if len(_index_tables) > 256:
+        _index_tables.clear()
+    _index_tables[key] = out
+    return out
+
+
+def _unpacked_shape(codes):
+    return tuple(codes.shape[:-1]) + (codes.shape[-1] * 2,) if codes.dim() and codes.is_contiguous() \
+        else (codes.numel() * 2,)
+
+
+def _check_packed4_layout(shape, axis, what: str):
+    """The layouts the 4-bit kernels take (include/mctq_hip.h), for a CONTIGUOUS tensor of ``shape``."""
+    n = 1
+    for s in shape:
+        n *= s
+    if axis is None:
+        ok = n % 8 == 0
+    else:
+        inner = 1
+        for s in shape[axis + 1:]:
+            inner *= s
+        ok = inner % 8 == 0 or (inner == 1 and shape[axis] % 8 == 0)
+    if not ok:
+        raise ValueError(f"{what}: 4-bit codes need a multiple of 8 elements per tensor, or per channel row (or, with the "
+                         f"channels on the last axis, a multiple of 8 channels); got shape {tuple(shape)}, axis {axis}")
+
+
+def lut_codes(x, lut, thresholds, axis, eps: float, thr_div: float, mult: float, cmin: float, cmax: float,
+              index_table=None, packed4: bool = False, step_round: int = 0):
+    """Codebook-index codes of the LUT quantizers as uint8 (extension, not in the reference).
+
+    ``code = argmin_j |clip((x / fl32(thr + eps)) * mult, cmin, cmax) - lut[j]|`` -- the index ``torch.argmin`` returns
+    in the reference's chain (first minimum in list order, 0 for a NaN input); ``lut_decode`` of it is bit-identical to
+    the fake-quantized tensor.  ``axis`` None = per tensor (``thr_div`` is the host copy of the divisor), otherwise
+    ``thresholds`` float32 [C] and ``eps``.  ``index_table``: ``make_lut_index_table``'s, or None (literal scan).
+    ``packed4`` (at most 16 codebook entries): two codes per byte, element 2j of the storage order in the low nibble, as
+    ``pack4`` (last dimension halved for contiguous tensors).  CPU tensors: the same definition with torch ops."""
+    n_lut = lut.numel()
+    if n_lut > 256:
+        raise ValueError(f"codebook-index codes are 8-bit: at most 256 codebook entries, got {n_lut}")
+    if packed4:
+        if n_lut > 16:
+            raise ValueError(f"4-bit codes take codebooks of at most 16 entries, got {n_lut}")
+        if x.numel() % 2:
+            raise ValueError("4-bit packing needs an even number of elements")
+    if x.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise NotImplementedError(f"lut_codes: codebook-index codes are produced from float32 / float16 / bfloat16 tensors, "
+                                  f"got {x.dtype}")
+    if axis is not None:
+        _check_axis(x, thresholds.numel(), axis)
+    if not x.is_cuda:
+        # CPU tensors: the definition, literally (quantizer_utils.py:126-134 of the reference, index kept)
+        xf = x.float() if step_round == 0 else x          # a float32 threshold tensor promotes the first division
+        lut_c = lut.detach().to(x.device).float().reshape(-1)
+        if axis is None:
+            t = torch.clip((xf / thr_div) * mult, min=cmin, max=cmax)
+        else:
+            shape = [1] * x.dim()
+            shape[axis] = -1
+            thr = thresholds.detach().to(x.device).float().reshape(shape)
+            t = torch.clip((xf / (thr + eps)) * mult, min=cmin, max=cmax)
+        q = torch.argmin(torch.abs(t.unsqueeze(-1) - lut_c), dim=-1).to(torch.uint8)
+        if packed4:
+            if x.is_contiguous() or not _is_dense(x):
+                return pack4(q.contiguous()).reshape(_packed_shape(x))
+            flat = torch.empty(x.numel(), dtype=torch.int16)          # dense, permuted storage: pack in STORAGE order
+            torch.as_strided(flat, x.shape, x.stride()).copy_(q.to(torch.int16))
+            return pack4(flat).reshape(_packed_shape(x))
+        return q
+    dt = _dtype_code(x, "lut_codes")
+    lib = native.load()
+    if not x.is_contiguous():
+        x = _dense_input(x)
+    if axis is not None and not packed4 and x.numel() > _SPLIT_ELEMS and thresholds.numel() > 1:
+        return _split_rows(x, axis, (thresholds.reshape(-1),), torch.uint8,
+                           lambda xp, ps, ax: lut_codes(xp, lut, ps[0], ax, eps, thr_div, mult, cmin, cmax, index_table))
+    if packed4:
+        code = native.CODE_U4
+        y = torch.empty(_packed_shape(x), dtype=torch.uint8, device=x.device)
+    else:
+        code = native.CODE_U8
+        y = torch.empty_like(x, dtype=torch.uint8)
+    lut = _param_on(x, lut, "lut_values", torch.float32)
+    tab_ptr, entries = 0, 0
+    if index_table is not None:
+        index_table = _param_on(x, index_table, "index_table", torch.float32)
+        tab_ptr, entries = index_table.data_ptr(), index_table.shape[0] - 1
+    idx = x.get_device()
+    with (_NOOP if idx == _current_device() else _on_device(idx)):
+        if axis is None:
+            rc = _launch(lib.mctq_lut_codes_per_tensor, x.data_ptr(), y.data_ptr(), x.numel(), dt, code, step_round, thr_div,
+                         lut.data_ptr(), n_lut, tab_ptr, entries, mult, cmin, cmax, _raw_stream(idx))
+        else:
+            thresholds = _param_on(x, thresholds, "thresholds", torch.float32)
+            outer, c, inner = _channel_view(x, axis)
+            rc = _launch(lib.mctq_lut_codes_per_channel, x.data_ptr(), y.data_ptr(), outer, c, inner, dt, code,
+                         thresholds.data_ptr(), eps, lut.data_ptr(), n_lut, tab_ptr, entries, mult, cmin, cmax,
+                         _raw_stream(idx))
+    if rc:
+        native.check(rc, "mctq_lut_codes")
+    return y
+
+
+def lut_decode(codes, lut, thresholds, axis, thr_mul: float, mult: float, packed4: bool = False, shape=None):
+    """float32 tensor ``(lut[codes] / mult) * thr`` of codebook-index codes (``lut_codes``): the fake-quantized tensor, bit
+    for bit.  ``axis`` None = per tensor (``thr_mul``), otherwise ``thresholds`` float32 [C].  uint8 codes keep their
+    sizes and strides (dense permuted codes are walked in storage order) unless ``shape`` reshapes them; ``packed4`` codes
+    are the storage of a CONTIGUOUS tensor of ``shape`` (default: the last dimension doubled)."""
+    if codes.dtype != torch.uint8:
+        raise ValueError(f"codebook-index codes are uint8 tensors, got {codes.dtype}")
+    n_lut = lut.numel()
+    if n_lut > 256 or (packed4 and n_lut > 16):
+        raise ValueError(f"{'4-bit' if packed4 else '8-bit'} codes take codebooks of at most {16 if packed4 else 256} "
+                         f"entries, got {n_lut}")
+    if packed4:
+        shape = _unpacked_shape(codes) if shape is None else tuple(shape)
+    elif shape is not None:
+        shape = tuple(shape)
+    if shape is not None:
+        n = 1
+        for s_ in shape:
+            n *= s_
+        if n != codes.numel() * (2 if packed4 else 1):
+            raise ValueError(f"{codes.numel()} {'bytes of packed ' if packed4 else ''}codes do not fit shape {shape}")
+    if packed4:
+        if axis is not None:
+            _check_axis(torch.empty(shape, device="meta"), thresholds.numel(), axis)
+        if codes.is_cuda:
+            _check_packed4_layout(shape, axis, "lut_decode")
+        c8 = unpack4(codes.contiguous(), False, shape).to(torch.uint8) if not codes.is_cuda else None
+    else:
+        c8 = codes if shape is None else codes.reshape(shape)
+        if axis is not None:
+            _check_axis(c8, thresholds.numel(), axis)
+    if not codes.is_cuda:
+        q = lut.detach().to(codes.device).float().reshape(-1)[c8.long()] / mult
+        if axis is None:
+            return q * thr_mul
+        bshape = [1] * c8.dim()
+        bshape[axis] = -1
+        return q * thresholds.detach().to(codes.device).float().reshape(bshape)
+    lib = native.load()
+    lut = _param_on(codes, lut, "lut_values", torch.float32)
+    if packed4:
+        src = codes if codes.is_contiguous() else codes.contiguous()
+        y = torch.empty(shape, dtype=torch.float32, device=codes.device)
+        geom = y
+        code = native.CODE_U4
+    else:
+        src = _dense_input(c8)
+        if src.numel() > _SPLIT_ELEMS:
+            if axis is not None:
+                return _split_rows(src, axis, (thresholds.reshape(-1),), torch.float32,
+                                   lambda cp, ps, ax: lut_decode(cp, lut, ps[0], ax, thr_mul, mult))
+            flat = torch.as_strided(src, (src.numel(),), (1,), src.storage_offset())
+            out = torch.empty(src.numel(), dtype=torch.float32, device=src.device)
+            step = _SPLIT_ELEMS - _SPLIT_ELEMS % 8
+            for a in range(0, src.numel(), step):
+                out[a:a + step] = lut_decode(flat[a:a + step], lut, None, None, thr_mul, mult)
+            return torch.as_strided(out, src.shape, src.stride())
+        y = torch.empty_like(src, dtype=torch.float32)
+        geom = src
+        code = native.CODE_U8
+    idx = codes.get_device()
+    with (_NOOP if idx == _current_device() else _on_device(idx)):
+        if axis is None:
+            rc = _launch(lib.mctq_lut_decode_per_tensor, src.data_ptr(), y.data_ptr(), y.numel(), code, lut.data_ptr(), n_lut,
+                         mult, thr_mul, _raw_stream(idx))
+        else:
+            thresholds = _param_on(codes, thresholds, "thresholds", torch.float32)
+            outer, c, inner = _channel_view(geom, axis)
+            rc = _launch(lib.mctq_lut_decode_per_channel, src.data_ptr(), y.data_ptr(), outer, c, inner, code, lut.data_ptr(),
+                         n_lut, mult, thresholds.data_ptr(), _raw_stream(idx))
+    if rc:
+        native.check(rc, "mctq_lut_decode")
+    return y
+
+
 def make_lut_steps(lut_values, mult: float, cmin: float, cmax: float, device):
     """Device copy of an integer codebook's sorted threshold list (include/mctq_hip.h: mctq_lut_build_steps), or None.
     The quantizers ask for it only when the decision table does not apply (lut_values_bitwidth > 10)."""

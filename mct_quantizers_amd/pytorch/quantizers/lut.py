@@ -128,10 +128,60 @@ class WeightsLUTSymmetricInferableQuantizer(BaseLUTSymmetricInferableQuantizer):
         # ... or, for clip ranges too wide for the table, into a sorted threshold list (None -> literal scan)
         self._lut_steps_torch = None if self._lut_table_torch is not None else \
             ops.make_lut_steps(self._lut_values_np, *lut_domain(self.lut_values_bitwidth, True), dev)
+        # the same decision boundaries with codebook indices as payload (quantize_to_codes; None -> literal index scan)
+        self._lut_index_table_torch = ops.make_lut_index_table(self._lut_values_np,
+                                                               *lut_domain(self.lut_values_bitwidth, True), dev)
         self.__dict__["_stale"] = False
         self.__dict__["_launch_ready"] = True
 
     _export_function = "WeightsLUTSymmetricF"
+
+    def quantize_to_codes(self, inputs: torch.Tensor, packed4: bool = False):
+        """Extension (not in the reference): the codebook indices of ``inputs`` -- what ``torch.argmin`` returns in the
+        reference's chain, first minimum in list order -- as uint8, plus what dequantizes them:
+        ``(lut_values[codes] / 2^(lut_values_bitwidth - 1)) * thresholds`` == ``self(inputs)`` bit for bit, which is what
+        ``dequantize_codes`` computes in one launch.  ``packed4`` (at most 16 codebook entries): two codes per byte
+        (``ops.unpack4(codes, False)`` undoes it; a permuted tensor is packed in its contiguous order).
+        Returns (codes, lut_values float32 [n_lut], thresholds float32 [C or 1])."""
+        lut, thr, index_table = self._codes_state(packed4)
+        if inputs.dtype is torch.float64:
+            raise NotImplementedError("quantize_to_codes: codebook-index codes are produced from float32 / float16 / "
+                                      "bfloat16 tensors")
+        mult, cmin, cmax = lut_domain(self.lut_values_bitwidth, True)
+        if packed4 and not inputs.is_contiguous():
+            inputs = inputs.contiguous()
+        if self.per_channel:
+            if self.input_rank != inputs.dim():
+                raise RuntimeError(f'input_rank={self.input_rank} does not match a tensor of rank {inputs.dim()}')
+            codes = ops.lut_codes(inputs, lut, thr, self.channel_axis % inputs.dim(), float(self.eps), 0.0, mult, cmin, cmax,
+                                  index_table, packed4)
+        else:
+            codes = ops.lut_codes(inputs, lut, None, None, 0.0, self._thr_div0, mult, cmin, cmax, index_table, packed4)
+        return codes, lut, thr
+
+    def dequantize_codes(self, codes: torch.Tensor, shape=None) -> torch.Tensor:
+        """Extension: the float32 tensor ``self(inputs)`` from the codes ``quantize_to_codes(inputs)`` returned.
+        ``shape``: the tensor's shape (needed for ``packed4`` codes, whose own shape has the last dimension halved);
+        4-bit codes are told from 8-bit ones by their size."""
+        lut, thr, _ = self._codes_state(False)
+        mult = lut_domain(self.lut_values_bitwidth, True)[0]
+        packed4 = _is_packed4(codes, shape)
+        if packed4 and lut.numel() > 16:
+            raise ValueError(f"{codes.numel()} codes do not fit shape {tuple(shape)}")
+        if self.per_channel:
+            rank = len(shape) if shape is not None else codes.dim()
+            if self.input_rank != rank:
+                raise RuntimeError(f'input_rank={self.input_rank} does not match a tensor of rank {rank}')
+            return ops.lut_decode(codes, lut, thr, self.channel_axis % rank, 0.0, mult, packed4, shape)
+        return ops.lut_decode(codes, lut, None, None, self._thr_mul0, mult, packed4, shape)
+
+    def _codes_state(self, packed4: bool):
+        """(codebook float32 [n_lut], thresholds float32 [C or 1], index table | None), current with the attributes."""
+        if self.__dict__.get("_stale") or "_lut_index_table_torch" not in self.__dict__:
+            self._resync()
+        lut = self._lut_values_torch.reshape(-1)
+        _check_codebook(lut.numel(), packed4)
+        return lut, self._threshold_torch.reshape(-1), self._lut_index_table_torch
 
     def batch_item_lut(self, inputs: torch.Tensor):
         """This quantizer's call on ``inputs`` as one entry of a batched LUT launch (``BatchPlan`` item
@@ -196,6 +246,23 @@ class WeightsLUTPOTInferableQuantizer(WeightsLUTSymmetricInferableQuantizer):
         assert _is_pot(self._threshold_np), f'Expected threshold to be power of 2 but is {threshold}'
 
 
+def _check_codebook(n_lut: int, packed4: bool):
+    if n_lut > 256:
+        raise ValueError(f"codebook-index codes are 8-bit: at most 256 codebook entries, got {n_lut}")
+    if packed4 and n_lut > 16:
+        raise ValueError(f"packed4 needs a codebook of at most 16 entries, got {n_lut}")
+
+
+def _is_packed4(codes: torch.Tensor, shape) -> bool:
+    """4-bit codes are half as many bytes as ``shape`` has elements; anything else is checked by ``ops.lut_decode``."""
+    if shape is None:
+        return False
+    n = 1
+    for s in shape:
+        n *= int(s)
+    return n != codes.numel() and n == 2 * codes.numel()
+
+
 def _bounds_in(dt, cmin: float, cmax: float):
     """(clip_min, clip_max) as torch.clip sees them on a tensor of type ``dt``: converted to that type -- or the
     message of the RuntimeError torch raises when a bound does not fit it."""
@@ -235,6 +302,9 @@ class ActivationLutPOTInferableQuantizer(BaseLUTSymmetricInferableQuantizer):
                                                    *lut_domain(self.lut_values_bitwidth, self.signed), dev)
         self._lut_steps_torch = None if self._lut_table_torch is not None else \
             ops.make_lut_steps(self._lut_values_np, *lut_domain(self.lut_values_bitwidth, self.signed), dev)
+        self._lut_index_table_torch = ops.make_lut_index_table(self._lut_values_np,
+                                                               *lut_domain(self.lut_values_bitwidth, self.signed), dev)
+        self._thr_codes_torch = torch.tensor([self._thr_mul0], dtype=torch.float32, device=dev)   # what quantize_to_codes returns
         # pre-packed launch (compiled binding): activations are launch-bound, see ActivationSymmetric.__call__
         plan = False
         fast = ops._fast_mod() if self._lut_table_torch is not None else None
@@ -274,6 +344,37 @@ class ActivationLutPOTInferableQuantizer(BaseLUTSymmetricInferableQuantizer):
         if table is None:
             return None
         return ("lut", inputs, None, None, table, None, 0.0, self._thr_div_by_dtype[dt], self._thr_mul0, mult, cmin, cmax, step)
+
+    def quantize_to_codes(self, inputs: torch.Tensor, packed4: bool = False):
+        """Extension, as ``WeightsLUTSymmetricInferableQuantizer.quantize_to_codes`` for a float32 activation tensor (per
+        tensor): (codes uint8, lut_values float32 [n_lut], threshold float32 [1]) with
+        ``(lut_values[codes] / 2^(lut_values_bitwidth - signed)) * threshold`` == ``self(inputs)`` bit for bit."""
+        lut, thr, index_table = self._codes_state(packed4)
+        if inputs.dtype is not torch.float32:
+            raise NotImplementedError(f"quantize_to_codes of an activation takes float32 tensors, got {inputs.dtype}")
+        mult, cmin, cmax = lut_domain(self.lut_values_bitwidth, self.signed)
+        if packed4 and not inputs.is_contiguous():
+            inputs = inputs.contiguous()
+        codes = ops.lut_codes(inputs, lut, None, None, 0.0, self._thr_div_by_dtype[torch.float32], mult, cmin, cmax,
+                              index_table, packed4)
+        return codes, lut, thr
+
+    def dequantize_codes(self, codes: torch.Tensor, shape=None) -> torch.Tensor:
+        """Extension: the float32 tensor ``self(inputs)`` from the codes ``quantize_to_codes(inputs)`` returned (``shape``
+        as for the weights quantizers)."""
+        lut, _, _ = self._codes_state(False)
+        packed4 = _is_packed4(codes, shape)
+        if packed4 and lut.numel() > 16:
+            raise ValueError(f"{codes.numel()} codes do not fit shape {tuple(shape)}")
+        return ops.lut_decode(codes, lut, None, None, self._thr_mul0, lut_domain(self.lut_values_bitwidth, self.signed)[0],
+                              packed4, shape)
+
+    def _codes_state(self, packed4: bool):
+        if self.__dict__.get("_stale") or "_lut_index_table_torch" not in self.__dict__:
+            self._resync()
+        lut = self.lut_values.reshape(-1)
+        _check_codebook(lut.numel(), packed4)
+        return lut, self._thr_codes_torch, self._lut_index_table_torch
 
     def __call__(self, inputs: torch.Tensor):
         if self.__dict__.get("_stale"):
