@@ -523,6 +523,25 @@ int mctq_qlinear_w4a8(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_
                       int32_t y_quant_max, int64_t M, int64_t N, int64_t K, void* stream);
 
 /*
+ * The same consumer for LUT (codebook) weights of at most 16 entries whose codebook values are int8 (the LUT quantizers
+ * with lut_values_bitwidth <= 8): q(w)[n][k] = float(lut16[idx[n][k]]) * w_scales[n] with w_scales[n] = threshold[n] /
+ * 2^(lut_values_bitwidth - 1), so the product is mctq_qlinear_i8's with w[n][k] = lut16[idx[n][k]], streamed at half a
+ * byte per weight and decoded index -> int8 in registers in front of the matrix instruction (exact: a byte lookup).
+ * w_idx4 [N][K / 2], DEVICE: the codebook indices (mctq_lut_codes_*) in mctq_qlinear_w4a8's consumer layout with
+ * UNSIGNED nibbles 0 .. 15 -- each group of 8 consecutive k is 4 bytes, byte j = idx[k = j] | idx[k = j + 4] << 4.
+ * lut16: a HOST pointer to 16 int8 codebook values in list order, entries beyond the codebook's length 0.  The call
+ * copies them into the kernel's arguments; they are read before it returns and never again.  Under stream capture the
+ * captured launch therefore replays the values of the capture: a graph must be re-captured when the codebook changes.
+ * w_rowsum[n] = sum_k lut16[idx[n][k]].  Everything else -- alignment (a_codes 16-byte, w_idx4 8-byte), K % 16 == 0,
+ * K <= 32768, y_code_dtype < 0 for float32 [M][N] or the next layer's codes -- as for mctq_qlinear_w4a8.
+ * mctq_last_launch names the launch "qlinear_stream_lut4".
+ */
+int mctq_qlinear_lut4a8(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
+                        const uint8_t* w_idx4, const int8_t* lut16, const float* w_scales, const int32_t* w_rowsum,
+                        const float* bias, void* y, int32_t y_code_dtype, float y_scale, int32_t y_zero_point,
+                        int32_t y_quant_min, int32_t y_quant_max, int64_t M, int64_t N, int64_t K, void* stream);
+
+/*
  * Tuning hook (benchmarks only): selects the launch variant used by later calls on any thread.
  *   key "nt"     : 1 = non-temporal loads and stores (default), 2 = non-temporal loads with cached stores
  *   key "cached_store_max_mb" : with nt = 1, outputs of at most this many MiB are stored through the caches

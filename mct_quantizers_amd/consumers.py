@@ -7,6 +7,10 @@ that product are integers times a scale, so on MI355X the product itself can run
 
     y[m][n] = float(sum_k (qa[m][k] - za) * qw[n][k]) * (sa * sw[n]) + bias[n]
 
+LUT (codebook) weights with int8 codebook values are the same product with ``qw[n][k] = lut[index[n][k]]`` and
+``sw[n] = threshold[n] / 2^(lut_values_bitwidth - 1)``; codebooks of at most 16 entries are also kept as packed 4-bit
+indices, which ``mctq_qlinear_lut4a8`` streams at half a byte per weight when there are few rows.
+
 ``QuantizedLinear`` keeps the weight's int8 codes (refreshed when the weight tensor changes), turns the incoming
 activation into codes with the activation quantizer's own parameters (``mctq_fq_codes_per_tensor``) and calls
 ``mctq_qlinear_i8`` (include/mctq_hip.h): 1 byte per weight streamed instead of 4 B read + 4 B written by the
@@ -132,19 +136,99 @@ def qlinear_w4a8(a_codes: torch.Tensor, a_zero_point: int, a_scale: float, w_cod
 _W4_MAX_ROWS = 32          # measured: beyond this the int8 kernels are faster than streaming half the bytes
 
 
+def pack_lut4(indices: torch.Tensor) -> torch.Tensor:
+    """uint8 codebook indices in [0, 15], [N, K] with K % 8 == 0 -> the consumer's 4-bit layout, uint8 [N, K / 2]: per
+    group of 8 consecutive k, byte j = index[j] | (index[j + 4] << 4) (include/mctq_hip.h: mctq_qlinear_lut4a8)."""
+    if indices.dtype != torch.uint8 or indices.dim() != 2 or indices.shape[1] % 8:
+        raise ValueError(f"pack_lut4 takes uint8 indices [N, K] with K % 8 == 0, got {indices.dtype} {tuple(indices.shape)}")
+    if indices.numel() and int(indices.max()) > 15:
+        raise ValueError("pack_lut4: a 4-bit index is at most 15")
+    N, K = indices.shape
+    g = indices.reshape(N, K // 8, 8)
+    return (g[..., 0:4] | (g[..., 4:8] << 4)).reshape(N, K // 2).contiguous()
+
+
+def _lut16_bytes(lut16) -> bytes:
+    """At most 16 integer codebook values in [-128, 127] -> the 16 host bytes mctq_qlinear_lut4a8 reads (zero padded)."""
+    if isinstance(lut16, bytes):
+        if len(lut16) != 16:
+            raise ValueError(f"lut16 as bytes must be 16 bytes long, got {len(lut16)}")
+        return lut16
+    import numpy as np
+    v = np.asarray(lut16.detach().cpu() if isinstance(lut16, torch.Tensor) else lut16, dtype=np.float64).reshape(-1)
+    if v.size > 16 or np.any(v != np.rint(v)) or np.any(v < -128) or np.any(v > 127):
+        raise ValueError("lut16 must hold at most 16 integers in [-128, 127]")
+    out = np.zeros(16, dtype=np.int8)
+    out[:v.size] = v.astype(np.int8)
+    return out.tobytes()
+
+
+def qlinear_lut4a8(a_codes: torch.Tensor, a_zero_point: int, a_scale: float, w_idx4: torch.Tensor, lut16,
+                   w_scales: torch.Tensor, w_rowsum: torch.Tensor, bias: Optional[torch.Tensor],
+                   out_codes=None) -> torch.Tensor:
+    """As ``qlinear_i8`` with ``w_codes[n][k] = lut16[index[n][k]]``, the weights given as packed 4-bit codebook indices
+    (``pack_lut4``) and ``lut16`` as at most 16 int8 codebook values on the host (a sequence, a CPU tensor or 16 bytes);
+    ``w_rowsum`` is the row sum of the looked-up values.  GPU tensors only."""
+    M, K = a_codes.shape
+    N = w_idx4.shape[0]
+    if w_idx4.shape[1] * 2 != K:
+        raise RuntimeError(f"shape mismatch: activations have K={K}, packed weights K={w_idx4.shape[1] * 2}")
+    if K % 16 or K > _MAX_K:
+        raise NotImplementedError(f"mctq_qlinear_lut4a8 needs K % 16 == 0 and K <= {_MAX_K}, got K={K}")
+    if w_idx4.dtype != torch.uint8 or w_idx4.device != a_codes.device:
+        raise TypeError(f"w_idx4 must be a uint8 tensor on {a_codes.device}, got {w_idx4.dtype} on {w_idx4.device}")
+    _check_consumer_operands(a_codes, w_scales, w_rowsum, bias)
+    lut = _lut16_bytes(lut16)
+    lib = native.load()
+    a_codes, w_idx4 = a_codes.contiguous(), w_idx4.contiguous()
+    code = native.CODE_U8 if a_codes.dtype == torch.uint8 else native.CODE_I8
+    if out_codes is None:
+        y = torch.empty((M, N), dtype=torch.float32, device=a_codes.device)
+        ocode, o_scale, o_zp, o_qmin, o_qmax = -1, 1.0, 0, 0, 0
+    else:
+        o_scale, o_zp, o_qmin, o_qmax = out_codes
+        tdt, ocode = ops._code_dtype(o_qmin, o_qmax)
+        y = torch.empty((M, N), dtype=tdt, device=a_codes.device)
+    with ops._maybe_on_device(a_codes):
+        rc = ops._launch(lib.mctq_qlinear_lut4a8, a_codes.data_ptr(), code, int(a_zero_point), float(a_scale),
+                         w_idx4.data_ptr(), lut, w_scales.data_ptr(), w_rowsum.data_ptr(),
+                         None if bias is None else bias.data_ptr(), y.data_ptr(), ocode, float(o_scale), int(o_zp),
+                         int(o_qmin), int(o_qmax), M, N, K, ops._stream(a_codes))
+    if rc:
+        native.check(rc, "mctq_qlinear_lut4a8")
+    return y
+
+
+# measured (tools/lut_consumer_probe.py, table in profiles/EXPERIMENTS.md): the largest probed M at which the packed kernel beats
+# mctq_qlinear_i8 on every probed shape -- at M = 8 it already loses on 28672 x 8192 and 4096 x 11008 (1.04 / 1.05)
+_LUT4_MAX_ROWS = 1
+
+
+def _is_lut_weights(q) -> bool:
+    from mct_quantizers_amd.pytorch.quantizers.lut import WeightsLUTSymmetricInferableQuantizer
+    return isinstance(q, WeightsLUTSymmetricInferableQuantizer)          # LUT-POT derives from it
+
+
 class QuantizedLinear(nn.Module):
     """``activation quantizer -> PytorchQuantizationWrapper(nn.Linear)`` evaluated on integer codes.
 
     ``weights_quantizer``: WeightsSymmetric / WeightsPOT (zero point 0), per tensor or per output channel
-    (``channel_axis`` 0), at most 8 bits.  ``activation_quantizer``: ActivationSymmetric / POT / Uniform, at most
+    (``channel_axis`` 0), at most 8 bits; or WeightsLUTSymmetric / WeightsLUTPOT with ``lut_values_bitwidth`` <= 8 (int8
+    codebook values) and at most 256 codebook entries, per tensor or per output channel.  ``activation_quantizer``: ActivationSymmetric / POT / Uniform, at most
     8 bits.  The float weight stays the module's parameter; its codes are rebuilt when it changes."""
 
     def __init__(self, linear: nn.Linear, weights_quantizer, activation_quantizer):
         super().__init__()
         if not isinstance(linear, nn.Linear):
             raise TypeError("QuantizedLinear wraps torch.nn.Linear")
-        if not hasattr(weights_quantizer, "quantize_to_codes") or not hasattr(weights_quantizer, "threshold_np"):
-            raise TypeError("the weights quantizer must be symmetric or power-of-two (zero point 0)")
+        self._lut_weights = _is_lut_weights(weights_quantizer)
+        if self._lut_weights:
+            if weights_quantizer.lut_values_bitwidth > 8:
+                raise NotImplementedError("codebook values wider than 8 bits")
+            if len(weights_quantizer._lut_values_np.reshape(-1)) > 256:
+                raise NotImplementedError("more than 256 codebook entries")
+        elif not hasattr(weights_quantizer, "quantize_to_codes") or not hasattr(weights_quantizer, "threshold_np"):
+            raise TypeError("the weights quantizer must be symmetric, power-of-two (zero point 0) or a LUT quantizer")
         if weights_quantizer.per_channel and weights_quantizer.channel_axis % 2 != 0:
             raise NotImplementedError("per-channel weight scales must run along the output channels (axis 0)")
         if weights_quantizer.num_bits > 8 or activation_quantizer.num_bits > 8:
@@ -164,6 +248,7 @@ class QuantizedLinear(nn.Module):
         self._a_scale, self._a_zp, self._a_qmin, self._a_qmax = _activation_code_params(activation_quantizer)
         self._w_key = None
         self._w_codes = self._w_scales = self._w_rowsum = self._w_codes4 = None
+        self._w_idx4 = self._lut16 = None                # LUT weights of at most 16 entries: packed indices + host codebook
         # chaining (fuse_linear_consumers(chain=True)): parameters of the activation quantizer that would quantize
         # this layer's output next; the output then leaves as that quantizer's codes
         self.emit_codes_for = None
@@ -184,6 +269,10 @@ class QuantizedLinear(nn.Module):
         key = (w.data_ptr(), w._version, w.device)
         if key == self._w_key:
             return
+        if self._lut_weights:
+            self._refresh_lut_weight_codes(w)
+            self._w_key = key
+            return
         codes, scales, _ = self.weights_quantizer.quantize_to_codes(w.detach())
         if codes.dtype != torch.int8:
             raise RuntimeError("symmetric weight codes are expected to be int8")
@@ -198,6 +287,31 @@ class QuantizedLinear(nn.Module):
         self._w_codes4 = pack_w4(self._w_codes) if (self.weights_quantizer.num_bits <= 4 and w.is_cuda
                                                      and self.in_features % 16 == 0) else None
         self._w_key = key
+
+    def _refresh_lut_weight_codes(self, w):
+        """LUT weights: q(w)[n][k] = (lut[idx] / 2^(B-1)) * thr[n] == float(lut_i8[idx]) * (thr[n] / 2^(B-1)) bit for bit (the
+        divisor is a power of two, so either side rounds once): int8 codes lut_i8[idx] with scales thr / 2^(B-1)."""
+        q = self.weights_quantizer
+        idx, lut, thr = q.quantize_to_codes(w.detach())
+        bits = q.lut_values_bitwidth
+        lut = lut.detach().to(device="cpu", dtype=torch.float32).reshape(-1)
+        if bits > 8 or lut.numel() > 256 or not bool(((lut == lut.round()) & (lut >= -128) & (lut <= 127)).all()):
+            raise RuntimeError("the codebook no longer holds at most 256 int8 values")
+        lut_i8 = lut.to(torch.int8)
+        idx = idx.reshape(self.out_features, self.in_features)           # [O, C, 1, 1] of a pointwise convolution too
+        codes = lut_i8.to(w.device)[idx.long()]
+        scales = thr.detach().to(device=w.device, dtype=torch.float32).reshape(-1) / float(2 ** (bits - 1))
+        if scales.numel() == 1:
+            scales = scales.expand(self.out_features)
+        self._w_codes = codes.contiguous()
+        self._w_scales = scales.contiguous()
+        self._w_rowsum = codes.sum(dim=1, dtype=torch.int32).contiguous()
+        self._w_codes4 = None
+        # a codebook of at most 16 entries is 4 bits per weight: also keep the indices packed, for few rows
+        if lut.numel() <= 16 and w.is_cuda and self.in_features % 16 == 0:
+            self._w_idx4, self._lut16 = pack_lut4(idx), _lut16_bytes(lut_i8)
+        else:
+            self._w_idx4 = self._lut16 = None
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         self._refresh_weight_codes()
@@ -218,6 +332,9 @@ class QuantizedLinear(nn.Module):
         if self._w_codes4 is not None and a_codes.is_cuda and a_codes.shape[0] <= _W4_MAX_ROWS:
             y = qlinear_w4a8(a_codes, self._a_zp, self._a_scale, self._w_codes4, self._w_scales, self._w_rowsum, bias,
                              self.emit_codes_for)
+        elif self._w_idx4 is not None and a_codes.is_cuda and a_codes.shape[0] <= _LUT4_MAX_ROWS:
+            y = qlinear_lut4a8(a_codes, self._a_zp, self._a_scale, self._w_idx4, self._lut16, self._w_scales,
+                               self._w_rowsum, bias, self.emit_codes_for)
         else:
             y = qlinear_i8(a_codes, self._a_zp, self._a_scale, self._w_codes, self._w_scales, self._w_rowsum, bias,
                            self.emit_codes_for)
@@ -302,8 +419,10 @@ def _plain_holder(m) -> bool:
 
 def fuse_linear_consumers(model: nn.Module, chain: bool = False) -> int:
     """In every ``nn.Sequential`` of ``model``: an activation holder directly followed by a wrapped ``nn.Linear`` with
-    a symmetric weights quantizer becomes (Identity, QuantizedLinear).  Returns the number of pairs replaced.
-    Pairs the integer consumer cannot take (other layers, LUT / uniform weights, K % 16 != 0) are left alone.
+    a symmetric, power-of-two or LUT weights quantizer (int8 codebook values, at most 256 entries) becomes (Identity,
+    QuantizedLinear); a wrapped pointwise ``nn.Conv2d`` likewise becomes a QuantizedConv1x1.  Returns the number of pairs
+    replaced.  Pairs the integer consumer cannot take (other layers, uniform weights, LUT weights with
+    ``lut_values_bitwidth`` > 8 or thresholds along another axis than the output channels, K % 16 != 0) are left alone.
 
     ``chain=True``: where one QuantizedLinear feeds the next directly, the float32 tensor between them is never
     materialised -- the first emits the second's activation codes from its epilogue (same codes, bit for bit, as
@@ -331,7 +450,8 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False) -> int:
 def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False):
     """The same rewrite on an arbitrary module graph (MCT-exported models are not ``nn.Sequential``): traces ``model``
     with torch.fx keeping wrappers and holders as leaves, and wherever an activation holder's ONLY consumer is a
-    wrapped ``nn.Linear`` the integer consumer can take, replaces the pair by one ``QuantizedLinear`` node.
+    wrapped ``nn.Linear`` the integer consumer can take (symmetric, power-of-two or LUT weights, as for
+    ``fuse_linear_consumers``), replaces the pair by one ``QuantizedLinear`` node.
     Returns ``(graph_module, pairs_replaced)``.  Holders with several consumers (residual branches) stay."""
     import torch.fx as fx
 

@@ -89,21 +89,50 @@ __device__ __forceinline__ i32x4 ql_unpack4(i32x2 x) {
 }
 __device__ __forceinline__ i32x4 ql_unpack4(i32x4 x) { return x; }       // int8 weights: nothing to do
 
+// 4-bit codebook indices (LUT4): the W4 layout with UNSIGNED nibbles 0..15 that index 16 int8 codebook values.  The
+// codebook travels in the kernel arguments (four dwords, entry j in byte j % 4 of t[j / 4]): no device read joins the
+// dependency chain.  v_perm_b32 D, S0, S1, sel picks byte sel (0..3: of S1, 4..7: of S0) per result byte, so index & 7
+// looks up entries 0..7 in {t[1], t[0]} and entries 8..15 in {t[3], t[2]}; bit 3 of the index, spread to a byte mask
+// (0x08 << 5) - (0x08 >> 3) = 0xFF per byte, chooses between the two: about two VALU operations per weight.
+struct QlLut { int t[4]; };
+__device__ __forceinline__ int ql_lut_bytes(unsigned sel, unsigned mask, const QlLut& c) {
+  const unsigned lo = __builtin_amdgcn_perm((unsigned)c.t[1], (unsigned)c.t[0], sel);
+  const unsigned hi = __builtin_amdgcn_perm((unsigned)c.t[3], (unsigned)c.t[2], sel);
+  return (int)((hi & mask) | (lo & ~mask));
+}
+__device__ __forceinline__ i32x4 ql_unpack_lut4(i32x2 x, const QlLut& c) {
+  i32x4 out;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const unsigned v = (unsigned)x[h];
+    const unsigned b_lo = v & 0x08080808u, b_hi = v & 0x80808080u;       // bit 3 of the indices of k = 0..3 / k = 4..7
+    out[2 * h] = ql_lut_bytes(v & 0x07070707u, (b_lo << 5) - (b_lo >> 3), c);
+    out[2 * h + 1] = ql_lut_bytes((v >> 4) & 0x07070707u, (b_hi << 1) - (b_hi >> 7), c);
+  }
+  return out;
+}
+__device__ __forceinline__ QlLut ql_lut_arg() { return QlLut{{0, 0, 0, 0}}; }
+__device__ __forceinline__ QlLut ql_lut_arg(const QlLut& c) { return c; }
+enum { kQlW8 = 0, kQlW4 = 1, kQlLut4 = 2 };      // weight formats of the streaming kernel
+
 // MT: 16-row tiles of A per pass (1..4).  A_U8: activation codes are uint8 (re-biased to int8 by ^0x80).
-// W4: weights are packed 4-bit codes (above).
-template <int kQlWaves, int MT, bool A_U8, bool W_NT, bool W4 = false>
+// WFMT: kQlW8 int8 weights, kQlW4 packed 4-bit codes, kQlLut4 packed 4-bit codebook indices (above); the codebook of the
+// last is the kernel's one trailing argument, which the other formats do not have.
+template <int kQlWaves, int MT, bool A_U8, bool W_NT, int WFMT = kQlW8, class... Lut>
 __global__ __launch_bounds__(kQlWaves * 64) void qlinear_i8_kernel(
     const int8_t* __restrict__ a, const int8_t* __restrict__ w, const float* __restrict__ w_scales,
     const int32_t* __restrict__ w_rowsum, const float* __restrict__ bias, void* __restrict__ y,
-    int M, int N, int64_t K, int za, float sa, QlOut oq) {
+    int M, int N, int64_t K, int za, float sa, QlOut oq, Lut... lut) {
+  static_assert(sizeof...(Lut) == (WFMT == kQlLut4 ? 1 : 0), "the codebook argument belongs to the LUT4 format");
+  constexpr bool W4 = WFMT == kQlW4, LUT4 = WFMT == kQlLut4, HALF = W4 || LUT4;      // HALF: half a byte per weight
   constexpr int kQlThreads = kQlWaves * 64;
   __shared__ int red[kQlWaves][MT][64][4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r = lane & 15, g = lane >> 4;
   const int n0 = blockIdx.x * 16;
   // rows beyond N / M are clamped to the last valid row: they are loaded and multiplied, never stored
-  const int8_t* wrow = w + (int64_t)min(n0 + r, N - 1) * (W4 ? K / 2 : K);
-  typedef typename std::conditional<W4, i32x2, i32x4>::type WF;     // a weight piece as loaded
+  const int8_t* wrow = w + (int64_t)min(n0 + r, N - 1) * (HALF ? K / 2 : K);
+  typedef typename std::conditional<HALF, i32x2, i32x4>::type WF;     // a weight piece as loaded
   const int64_t kblocks = (K + kQlKBlock - 1) / kQlKBlock;
   const int64_t full_blocks = K / kQlKBlock;
   // this thread's output column in the epilogue is fixed (block size % 16 == 0): fetch its constants now, not
@@ -138,13 +167,15 @@ __global__ __launch_bounds__(kQlWaves * 64) void qlinear_i8_kernel(
         ql_load_row<false, true>(arow[t], k, K, af[t]);
 #endif
       }
-      if constexpr (W4) ql_load_row4<W_NT, true>(wrow, k, K, wf);      // L2-resident activations first, the HBM stream behind them
+      if constexpr (HALF) ql_load_row4<W_NT, true>(wrow, k, K, wf);      // L2-resident activations first, the HBM stream behind them
       else ql_load_row<W_NT, true>(wrow, k, K, wf);
     };
     auto multiply = [&](const WF* wf, const i32x4 (*af)[4]) {
 #pragma unroll
       for (int p = 0; p < 4; ++p) {
-        const i32x4 wv = ql_unpack4(wf[p]);
+        i32x4 wv;
+        if constexpr (LUT4) wv = ql_unpack_lut4(wf[p], ql_lut_arg(lut...));
+        else wv = ql_unpack4(wf[p]);
 #pragma unroll
         for (int t = 0; t < MT; ++t) {
           i32x4 av = af[t][p];
@@ -177,10 +208,18 @@ __global__ __launch_bounds__(kQlWaves * 64) void qlinear_i8_kernel(
     }
     if (full_blocks != kblocks && wave == kQlWaves - 1) {          // ragged end of K: guarded loads, one wave
       const int64_t k = full_blocks * kQlKBlock + 16 * g;
-      if constexpr (W4) ql_load_row4<W_NT, false>(wrow, k, K, wf0);
+      if constexpr (HALF) ql_load_row4<W_NT, false>(wrow, k, K, wf0);
       else ql_load_row<W_NT, false>(wrow, k, K, wf0);
 #pragma unroll
       for (int t = 0; t < MT; ++t) ql_load_row<false, false>(arow[t], k, K, af0[t]);
+      if constexpr (LUT4 && A_U8) {       // a zero index decodes to lut[0], not to 0: beyond K the ACTIVATION must be the zero (code 128)
+#pragma unroll
+        for (int t = 0; t < MT; ++t) {
+#pragma unroll
+          for (int p = 0; p < 4; ++p)
+            if (k + 64 * p >= K) af0[t][p] = i32x4{(int)0x80808080, (int)0x80808080, (int)0x80808080, (int)0x80808080};
+        }
+      }
       multiply(wf0, af0);
     }
 
@@ -375,19 +414,19 @@ static int launch_qlinear_lds(const void* a, const int8_t* w, const float* w_sca
   return check_launch("mctq_qlinear_i8 (LDS-staged activations)");
 }
 
-template <int WAVES, int MT, bool A_U8, bool W4 = false>
+template <int WAVES, int MT, bool A_U8, int WFMT = kQlW8, class... Lut>
 static int launch_qlinear(const void* a, const int8_t* w, const float* w_scales, const int32_t* w_rowsum,
                           const float* bias, void* y, int64_t M, int64_t N, int64_t K, int za, float sa,
-                          const QlOut& oq, hipStream_t stream) {
+                          const QlOut& oq, hipStream_t stream, Lut... lut) {
   const dim3 grid((unsigned)((N + 15) / 16));
   const bool one_pass = M <= 16 * MT;             // weights read exactly once: keep them out of the caches
   if (one_pass)
-    hipLaunchKernelGGL((qlinear_i8_kernel<WAVES, MT, A_U8, true, W4>), grid, dim3(WAVES * 64), 0, stream,
-                       (const int8_t*)a, w, w_scales, w_rowsum, bias, y, (int)M, (int)N, K, za, sa, oq);
+    hipLaunchKernelGGL((qlinear_i8_kernel<WAVES, MT, A_U8, true, WFMT, Lut...>), grid, dim3(WAVES * 64), 0, stream,
+                       (const int8_t*)a, w, w_scales, w_rowsum, bias, y, (int)M, (int)N, K, za, sa, oq, lut...);
   else
-    hipLaunchKernelGGL((qlinear_i8_kernel<WAVES, MT, A_U8, false, W4>), grid, dim3(WAVES * 64), 0, stream,
-                       (const int8_t*)a, w, w_scales, w_rowsum, bias, y, (int)M, (int)N, K, za, sa, oq);
-  note_ql<A_U8>(W4 ? "qlinear_stream_w4" : WAVES == 8 ? "qlinear_stream_8waves" : "qlinear_stream_4waves", MT);
+    hipLaunchKernelGGL((qlinear_i8_kernel<WAVES, MT, A_U8, false, WFMT, Lut...>), grid, dim3(WAVES * 64), 0, stream,
+                       (const int8_t*)a, w, w_scales, w_rowsum, bias, y, (int)M, (int)N, K, za, sa, oq, lut...);
+  note_ql<A_U8>(WFMT == kQlLut4 ? "qlinear_stream_lut4" : WFMT == kQlW4 ? "qlinear_stream_w4" : WAVES == 8 ? "qlinear_stream_8waves" : "qlinear_stream_4waves", MT);
   return check_launch("mctq_qlinear_i8");
 }
 
@@ -1161,6 +1200,53 @@ static int qlinear_dispatch(const void* a_codes, int32_t a_code_dtype, int32_t a
 #undef MCTQ_QLL
 }
 
+// The two entry points that stream half a byte per weight: 4-bit codes (lut == nullptr) or 4-bit indices into *lut.
+static int qlinear_packed4(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
+                           const uint8_t* w_codes4, const QlLut* lut, const float* w_scales, const int32_t* w_rowsum,
+                           const float* bias, void* y, int32_t y_code_dtype, float y_scale, int32_t y_zero_point,
+                           int32_t y_quant_min, int32_t y_quant_max, int64_t M, int64_t N, int64_t K, void* stream) {
+  if (M < 0 || N < 0 || K < 0) return fail_arg("negative extent");
+  if (a_code_dtype != MCTQ_CODE_I8 && a_code_dtype != MCTQ_CODE_U8) return fail_arg("bad a_code_dtype");
+  QlOut oq;
+  oq.mode = 0; oq.inv = oq.zf = oq.lo = oq.hi = 0.0f;
+  if (y_code_dtype >= 0) {
+    if (y_code_dtype != MCTQ_CODE_I8 && y_code_dtype != MCTQ_CODE_U8) return fail_arg("bad y_code_dtype");
+    if (y_quant_min > y_quant_max) return fail_arg("quant_min > quant_max");
+    if (y_code_dtype == MCTQ_CODE_I8 ? (y_quant_min < -128 || y_quant_max > 127) : (y_quant_min < 0 || y_quant_max > 255))
+      return fail_arg("clamp domain does not fit the code type");
+    oq.mode = y_code_dtype == MCTQ_CODE_I8 ? 1 : 2;
+    oq.inv = 1.0f / y_scale;
+    oq.zf = (float)y_zero_point; oq.lo = (float)y_quant_min; oq.hi = (float)y_quant_max;
+  }
+  if (M == 0 || N == 0) return 0;
+  if (!a_codes || !w_codes4 || !w_scales || !w_rowsum || !y) return fail_arg("NULL pointer");
+  if (K % 16 != 0) return fail_arg("K must be a multiple of 16");
+  if ((((uintptr_t)a_codes) & 15u) != 0 || (((uintptr_t)w_codes4) & 7u) != 0)
+    return fail_arg("a_codes must be 16-byte and the packed weights (w_codes4 / w_idx4) 8-byte aligned");
+  if (K > (1 << 15)) return fail_arg("K > 32768 could overflow the int32 accumulator");
+  if (M > INT32_MAX / 2 || N > INT32_MAX / 2) return fail_arg("M or N too large");
+  const bool u8 = a_code_dtype == MCTQ_CODE_U8;
+  const int za = u8 ? a_zero_point - 128 : a_zero_point;
+  const int8_t* w = reinterpret_cast<const int8_t*>(w_codes4);
+  const hipStream_t s = (hipStream_t)stream;
+#define MCTQ_QL4(MT_)                                                                                               \
+  (u8 ? launch_qlinear<8, MT_, true, kQlW4>(a_codes, w, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, s)     \
+      : launch_qlinear<8, MT_, false, kQlW4>(a_codes, w, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, s))
+#define MCTQ_QLUT4(MT_)                                                                                                    \
+  (u8 ? launch_qlinear<8, MT_, true, kQlLut4>(a_codes, w, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, s, *lut)   \
+      : launch_qlinear<8, MT_, false, kQlLut4>(a_codes, w, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, s, *lut))
+  if (lut) {
+    if (M <= 16) return MCTQ_QLUT4(1);
+    if (M <= 32) return MCTQ_QLUT4(2);
+    return MCTQ_QLUT4(4);
+  }
+  if (M <= 16) return MCTQ_QL4(1);
+  if (M <= 32) return MCTQ_QL4(2);
+  return MCTQ_QL4(4);
+#undef MCTQ_QL4
+#undef MCTQ_QLUT4
+}
+
 extern "C" {
 
 int mctq_qlinear_i8(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
@@ -1193,37 +1279,19 @@ int mctq_qlinear_w4a8(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_
                       const uint8_t* w_codes4, const float* w_scales, const int32_t* w_rowsum, const float* bias,
                       void* y, int32_t y_code_dtype, float y_scale, int32_t y_zero_point, int32_t y_quant_min,
                       int32_t y_quant_max, int64_t M, int64_t N, int64_t K, void* stream) {
-  if (M < 0 || N < 0 || K < 0) return fail_arg("negative extent");
-  if (a_code_dtype != MCTQ_CODE_I8 && a_code_dtype != MCTQ_CODE_U8) return fail_arg("bad a_code_dtype");
-  QlOut oq;
-  oq.mode = 0; oq.inv = oq.zf = oq.lo = oq.hi = 0.0f;
-  if (y_code_dtype >= 0) {
-    if (y_code_dtype != MCTQ_CODE_I8 && y_code_dtype != MCTQ_CODE_U8) return fail_arg("bad y_code_dtype");
-    if (y_quant_min > y_quant_max) return fail_arg("quant_min > quant_max");
-    if (y_code_dtype == MCTQ_CODE_I8 ? (y_quant_min < -128 || y_quant_max > 127) : (y_quant_min < 0 || y_quant_max > 255))
-      return fail_arg("clamp domain does not fit the code type");
-    oq.mode = y_code_dtype == MCTQ_CODE_I8 ? 1 : 2;
-    oq.inv = 1.0f / y_scale;
-    oq.zf = (float)y_zero_point; oq.lo = (float)y_quant_min; oq.hi = (float)y_quant_max;
-  }
-  if (M == 0 || N == 0) return 0;
-  if (!a_codes || !w_codes4 || !w_scales || !w_rowsum || !y) return fail_arg("NULL pointer");
-  if (K % 16 != 0) return fail_arg("K must be a multiple of 16");
-  if ((((uintptr_t)a_codes) & 15u) != 0 || (((uintptr_t)w_codes4) & 7u) != 0)
-    return fail_arg("a_codes must be 16-byte and w_codes4 8-byte aligned");
-  if (K > (1 << 15)) return fail_arg("K > 32768 could overflow the int32 accumulator");
-  if (M > INT32_MAX / 2 || N > INT32_MAX / 2) return fail_arg("M or N too large");
-  const bool u8 = a_code_dtype == MCTQ_CODE_U8;
-  const int za = u8 ? a_zero_point - 128 : a_zero_point;
-  const int8_t* w = reinterpret_cast<const int8_t*>(w_codes4);
-  const hipStream_t s = (hipStream_t)stream;
-#define MCTQ_QL4(MT_)                                                                                               \
-  (u8 ? launch_qlinear<8, MT_, true, true>(a_codes, w, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, s)     \
-      : launch_qlinear<8, MT_, false, true>(a_codes, w, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, s))
-  if (M <= 16) return MCTQ_QL4(1);
-  if (M <= 32) return MCTQ_QL4(2);
-  return MCTQ_QL4(4);
-#undef MCTQ_QL4
+  return qlinear_packed4(a_codes, a_code_dtype, a_zero_point, a_scale, w_codes4, nullptr, w_scales, w_rowsum, bias, y,
+                         y_code_dtype, y_scale, y_zero_point, y_quant_min, y_quant_max, M, N, K, stream);
+}
+
+int mctq_qlinear_lut4a8(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
+                        const uint8_t* w_idx4, const int8_t* lut16, const float* w_scales, const int32_t* w_rowsum,
+                        const float* bias, void* y, int32_t y_code_dtype, float y_scale, int32_t y_zero_point,
+                        int32_t y_quant_min, int32_t y_quant_max, int64_t M, int64_t N, int64_t K, void* stream) {
+  if (!lut16) return fail_arg("lut16 is NULL (a HOST pointer to 16 int8 codebook values)");
+  QlLut lut;
+  memcpy(lut.t, lut16, sizeof(lut.t));                // entry j -> byte j % 4 of dword j / 4 (little endian)
+  return qlinear_packed4(a_codes, a_code_dtype, a_zero_point, a_scale, w_idx4, &lut, w_scales, w_rowsum, bias, y,
+                         y_code_dtype, y_scale, y_zero_point, y_quant_min, y_quant_max, M, N, K, stream);
 }
 
 #ifdef MCTQ_QL_STAMP
