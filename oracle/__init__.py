@@ -74,6 +74,34 @@ def oracle_call(cls_name: str, kwargs: dict, x: np.ndarray, return_index: bool =
     raise KeyError(cls_name)
 
 
+def oracle_export_params(cls_name: str, kwargs: dict, ndim: int):
+    """(lo, hi, step, axis, shifted) with which ``O.export_grid`` computes the export branch of an affine quantizer:
+    the parameter arithmetic of the ``O.export_*`` wrappers on its own (float32 vectors for weights, doubles for activations)."""
+    kw = dict(kwargs)
+    nb = kw["num_bits"]
+    axis = kw.get("channel_axis") if kw.get("per_channel") else None
+    if axis is not None:
+        axis %= ndim
+    f32 = np.float32
+    if cls_name in ("WeightsSymmetricInferableQuantizer", "WeightsPOTInferableQuantizer"):
+        thr = np.asarray(kw["threshold"], dtype=np.float64).astype(f32)
+        step = (thr / f32(2 ** (nb - 1))).astype(f32)
+        return -thr, (thr - step).astype(f32), step, axis, False
+    if cls_name == "WeightsUniformInferableQuantizer":
+        _, _, _, _, a, b = O.weights_uniform_params(nb, kw["min_range"], kw["max_range"])
+        a, b = O.fix_range_to_include_zero(a, b, nb)
+        return a, b, ((b - a) / f32(2 ** nb - 1)).astype(f32), axis, False
+    if cls_name in ("ActivationSymmetricInferableQuantizer", "ActivationPOTInferableQuantizer"):
+        thr = float(np.asarray(kw["threshold"])[0])
+        step = thr / (2 ** (nb - 1) if kw["signed"] else 2 ** nb)
+        return (-thr if kw["signed"] else 0.0), thr - step, step, None, False
+    if cls_name == "ActivationUniformInferableQuantizer":
+        _, _, _, _, a, b = O.activation_uniform_params(nb, kw["min_range"], kw["max_range"])
+        a, b = O.adjust_range_to_include_zero_f64(a, b, nb)
+        return a, b, (b - a) / (2 ** nb - 1), None, True
+    raise KeyError(cls_name)
+
+
 def oracle_export_call(cls_name: str, kwargs: dict, x: np.ndarray):
     """What the reference's ``q.enable_custom_impl(); q(x)`` returns while ``torch.jit`` is tracing."""
     kw = dict(kwargs)

@@ -14,6 +14,10 @@ Runs only in the build container: imports sony/mct_quantizers from /root/referen
   * ``full_sha.json``              : SHA-256 of the reference outputs at the full BASELINE
     sizes for the portable synthetic inputs of mct_quantizers_amd/workloads.py.
 
+  * ``export_edges.json`` + ``export_edges.npz`` (``--export-edges``): the export-time arithmetic of the
+    four affine families on the edge-value inputs of oracle/grid_inputs.py (NaN, +-inf, +-0.0 at a zero
+    bound, denormals, ties, bounds), reached through the quantizer classes while tracing.
+
 The fixtures are data only (inputs and expected outputs).  The reference source never
 enters this repository.  Usage:  python tools/gen_golden.py [--skip-full]
 """
@@ -957,8 +961,67 @@ def gen_export():
     print(f"{len(ecases)} export cases, {sum(a.nbytes for a in earrays.values())} array bytes")
 
 
+# ------------------------------------------------------------------------------------------
+# the export arithmetic on the edge values the GPU grid tests run (oracle/grid_inputs.py): NaN, +-inf, +-0.0 at a zero
+# bound, denormals, ties and bounds of every channel's own grid, on shapes of the channel-last and long-row launch routes
+# ------------------------------------------------------------------------------------------
+
+def export_edge_configs():
+    er = np.random.default_rng(20261018)
+    u = lambda lo, hi, n: [float(v) for v in er.uniform(lo, hi, size=n)]   # noqa: E731
+
+    def mins(n):                        # some channels start at exactly zero
+        m = u(-4, -0.1, n)
+        m[::3] = [0.0] * len(m[::3])
+        return m
+    return [
+        ("wsym_last8", "WeightsSymmetricInferableQuantizer", dict(num_bits=8, threshold=u(0.1, 4, 8), per_channel=True, channel_axis=-1), (40, 8)),
+        ("wsym_last12", "WeightsSymmetricInferableQuantizer", dict(num_bits=8, threshold=u(0.1, 4, 12), per_channel=True, channel_axis=-1), (30, 12)),
+        ("wsym_rows1028", "WeightsSymmetricInferableQuantizer", dict(num_bits=8, threshold=u(0.1, 4, 2), per_channel=True, channel_axis=0), (2, 1028)),
+        ("wsym_pt", "WeightsSymmetricInferableQuantizer", dict(num_bits=8, threshold=u(0.3, 4, 1), per_channel=False), (7, 33)),
+        ("wpot_pc0", "WeightsPOTInferableQuantizer", dict(num_bits=4, threshold=[0.5, 2.0, 1.0, 4.0, 0.25], per_channel=True, channel_axis=0), (5, 44)),
+        ("wuni_last8", "WeightsUniformInferableQuantizer", dict(num_bits=8, min_range=mins(8), max_range=u(0.1, 4, 8), per_channel=True, channel_axis=-1), (40, 8)),
+        ("wuni_last12", "WeightsUniformInferableQuantizer", dict(num_bits=8, min_range=mins(12), max_range=u(0.1, 4, 12), per_channel=True, channel_axis=-1), (30, 12)),
+        ("wuni_rows1028", "WeightsUniformInferableQuantizer", dict(num_bits=8, min_range=mins(2), max_range=u(0.1, 4, 2), per_channel=True, channel_axis=0), (2, 1028)),
+        ("wuni_mid", "WeightsUniformInferableQuantizer", dict(num_bits=8, min_range=mins(6), max_range=u(0.1, 4, 6), per_channel=True, channel_axis=1), (5, 6, 7)),
+        ("asym_u", "ActivationSymmetricInferableQuantizer", dict(num_bits=8, threshold=u(0.5, 4, 1), signed=False), (2, 3, 16, 9)),
+        ("asym_s", "ActivationSymmetricInferableQuantizer", dict(num_bits=8, threshold=u(0.5, 4, 1), signed=True), (2, 3, 16, 9)),
+        ("apot_u", "ActivationPOTInferableQuantizer", dict(num_bits=8, threshold=[2.0], signed=False), (3, 101)),
+        ("auni_neg", "ActivationUniformInferableQuantizer", dict(num_bits=8, min_range=[-7.0], max_range=[-1.0]), (2, 3, 12, 12)),
+        ("auni_pos", "ActivationUniformInferableQuantizer", dict(num_bits=8, min_range=[3.0], max_range=[10.0]), (2, 3, 12, 12)),
+        ("auni_mid", "ActivationUniformInferableQuantizer", dict(num_bits=8, min_range=[-2.5], max_range=[3.1]), (2, 3, 12, 12)),
+    ]
+
+
+def gen_export_edges():
+    from oracle import oracle_export_params
+    from oracle.grid_inputs import grid_edge_inputs
+    er = np.random.default_rng(20261019)
+    ecases, earrays = [], {}
+    for name, cls_name, kwargs, shape in export_edge_configs():
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            q = getattr(refq, cls_name)(**kwargs)
+        q.enable_custom_impl()
+        lo, hi, step, axis, _ = oracle_export_params(cls_name, kwargs, len(shape))
+        x = grid_edge_inputs(er, shape, lo, hi, step, axis)
+        y = traced_call(q, torch.from_numpy(x.copy()))
+        cid = f"g{len(ecases):03d}"
+        earrays[cid + "_x"], earrays[cid + "_y"] = x, y.numpy().copy()
+        ecases.append(dict(id=cid, name=name, cls=cls_name, kwargs=kwargs, shape=list(shape)))
+    np.savez_compressed(os.path.join(OUT, "export_edges.npz"), **earrays)
+    meta = dict(reference="sony/mct_quantizers v%s" % ref.__version__, torch=torch.__version__,
+                generator="tools/gen_golden.py --export-edges", inputs="oracle/grid_inputs.py: grid_edge_inputs")
+    with open(os.path.join(OUT, "export_edges.json"), "w") as f:
+        json.dump(dict(meta=meta, cases=ecases), f, indent=1)
+    print(f"{len(ecases)} export edge cases, {sum(a.nbytes for a in earrays.values())} array bytes, "
+          f"{os.path.getsize(os.path.join(OUT, 'export_edges.npz'))} bytes compressed")
+
+
 if __name__ == "__main__":
-    if "--pickles-only" in sys.argv:
+    if "--export-edges" in sys.argv:
+        gen_export_edges()
+    elif "--pickles-only" in sys.argv:
         os.makedirs(OUT, exist_ok=True)
         gen_pickled_reference_models()
     elif "--half-bounds-only" in sys.argv:
@@ -980,6 +1043,7 @@ if __name__ == "__main__":
         gen_half_cases()
         gen_pickled_reference_models()
         gen_export()
+        gen_export_edges()
         gen_f64_cases()
         gen_extra_sha()
         gen_traced_wrapper_pickle()
