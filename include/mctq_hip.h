@@ -542,6 +542,51 @@ int mctq_qlinear_lut4a8(const void* a_codes, int32_t a_code_dtype, int32_t a_zer
                         int32_t y_quant_min, int32_t y_quant_max, int64_t M, int64_t N, int64_t K, void* stream);
 
 /*
+ * Row sums of activation codes: a_rowsum[m] = sum_k (a_codes[m][k] - a_zero_point) as int32 [M], DEVICE -- the per-row
+ * factor of the weight zero point term of mctq_qlinear_i8_zp / mctq_qlinear_w4a8_zp below.  a_codes [M][K] int8 or uint8
+ * (a_code_dtype), DEVICE, 16-byte aligned; K % 16 == 0 and K <= 32768 as for mctq_qlinear_i8; M == 0 returns 0 without a
+ * launch; anything else returns MCTQ_E_ARG with a mctq_last_error text.  Lanes load 16 bytes and sum them with the packed
+ * 8-bit dot product; one block per row up to 64 rows (a 32 KiB row is never walked by one wave alone), one wave per row
+ * beyond; no atomics, the result does not depend on scheduling.  mctq_last_launch names the launch "codes_rowsum".
+ */
+int mctq_codes_rowsum(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, int32_t* a_rowsum, int64_t M,
+                      int64_t K, void* stream);
+
+/*
+ * The integer consumer for weights WITH a zero point per output channel (the uniform weights quantizers, whose codes
+ * (c - zero_point) * scale cover a range [min, max] that need not be symmetric):
+ *     y[m][n] = float( sum_k (a[m][k] - a_zero_point) * (w[n][k] - w_zero_points[n]) ) * (a_scale * w_scales[n]) + bias[n]
+ * w holds int8 codes and w_zero_points int32[N], DEVICE, are in the same domain, each in [-128, 127] (unsigned 8-bit codes c
+ * in 0 .. 255 with zero point z are passed as c - 128 and z - 128; codes of at most 4 bits as c - 8 and z - 8).  The sum is
+ * exact int32 -- |a - za| <= 255, |w - zw| <= 255 and K <= 32768 bound it by 255 * 255 * 32768 = 2 130 739 200 < 2^31 --
+ * and one float32 multiply and one float32 add follow, each rounded once.  It is evaluated as
+ *     sum_k a w  -  a_zero_point * w_rowsum[n]  -  w_zero_points[n] * a_rowsum[m]
+ * with w_rowsum[n] = sum_k w[n][k] as for mctq_qlinear_i8 and a_rowsum int32[M], DEVICE, from mctq_codes_rowsum on the same
+ * a_codes / a_zero_point (same stream, or ordered before this call); the terms reach 2^30, so the kernels add them in
+ * wrapping arithmetic and only the total has to fit.  Both new pointers are required.  y_code_dtype < 0: y is float32
+ * [M][N]; otherwise y holds the next layer's codes as in mctq_qlinear_i8_codes.  Everything else as for mctq_qlinear_i8.
+ * Launch shapes: the weight-streaming and LDS-tiled kernels under the same cost model and "ql_variant" key; the
+ * register-pinned whole-tile kernels do not take zero points, so large whole-tile products run on the ~1.5 POP/s tiled
+ * kernels instead of the 2.2 POP/s ones, and ql_variant 2544 / 2548 / 2560 returns MCTQ_E_ARG here.  mctq_last_launch marks
+ * the form that ran: "...<u8 x i8 zp,...>".
+ */
+int mctq_qlinear_i8_zp(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
+                       const int8_t* w_codes, const float* w_scales, const int32_t* w_rowsum, const float* bias,
+                       void* y, int32_t y_code_dtype, float y_scale, int32_t y_zero_point, int32_t y_quant_min,
+                       int32_t y_quant_max, const int32_t* w_zero_points, const int32_t* a_rowsum, int64_t M, int64_t N,
+                       int64_t K, void* stream);
+
+/*
+ * The same for packed 4-bit codes: mctq_qlinear_w4a8's arguments and layout (two's-complement nibbles in [-8, 7]) plus
+ * w_zero_points int32[N] in the same domain and a_rowsum int32[M] as above; w_rowsum[n] = sum_k code[n][k].
+ */
+int mctq_qlinear_w4a8_zp(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
+                         const uint8_t* w_codes4, const float* w_scales, const int32_t* w_rowsum, const float* bias,
+                         void* y, int32_t y_code_dtype, float y_scale, int32_t y_zero_point, int32_t y_quant_min,
+                         int32_t y_quant_max, const int32_t* w_zero_points, const int32_t* a_rowsum, int64_t M, int64_t N,
+                         int64_t K, void* stream);
+
+/*
  * Tuning hook (benchmarks only): selects the launch variant used by later calls on any thread.
  *   key "nt"     : 1 = non-temporal loads and stores (default), 2 = non-temporal loads with cached stores
  *   key "cached_store_max_mb" : with nt = 1, outputs of at most this many MiB are stored through the caches

@@ -17,6 +17,16 @@ activation into codes with the activation quantizer's own parameters (``mctq_fq_
 fake-quant kernel and 4 B read again by the float32 GEMM.  The result is the exact integer sum scaled once; it
 differs from the reference's float32 product only by that product's own accumulation rounding.
 
+Uniform weights (a range [min, max] with a zero point per output channel) are the product with ``qw[n][k] - zw[n]`` in
+place of ``qw[n][k]``:
+
+    sum_k (qa - za) * (qw - zw[n]) = sum_k qa * qw - za * w_rowsum[n] - zw[n] * a_rowsum[m],   a_rowsum[m] = sum_k (qa[m][k] - za)
+
+-- the kernels' sum and first correction, plus one int32 per activation row (``mctq_codes_rowsum``, one more small launch)
+and one per output channel in the epilogue (``mctq_qlinear_i8_zp`` / ``mctq_qlinear_w4a8_zp``).  The register-pinned
+whole-tile kernels do not take zero points: large whole-tile products with uniform weights run on the ~1.5 POP/s tiled
+kernels, not the 2.2 POP/s ones.
+
 CPU tensors run the same integer arithmetic with torch ops (host logic for tests, bit-identical to the kernel).
 """
 from typing import Optional
@@ -39,21 +49,58 @@ def _activation_code_params(q):
     raise TypeError(f"{type(q).__name__} is not an affine per-tensor activation quantizer")
 
 
-def _check_consumer_operands(a_codes, w_scales, w_rowsum, bias):
-    """The kernels read w_scales / bias as float32 and w_rowsum as int32, all on a_codes' device."""
-    for name, t, dt in (("w_scales", w_scales, torch.float32), ("w_rowsum", w_rowsum, torch.int32), ("bias", bias, torch.float32)):
+def _check_consumer_operands(a_codes, w_scales, w_rowsum, bias, w_zero_points=None):
+    """The kernels read w_scales / bias as float32 and w_rowsum / w_zero_points as int32, all on a_codes' device."""
+    for name, t, dt in (("w_scales", w_scales, torch.float32), ("w_rowsum", w_rowsum, torch.int32), ("bias", bias, torch.float32),
+                        ("w_zero_points", w_zero_points, torch.int32)):
         if t is None:
             continue
         if t.dtype != dt or t.device != a_codes.device or not t.is_contiguous():
             raise TypeError(f"{name} must be a contiguous {dt} tensor on {a_codes.device}, got {t.dtype} on {t.device}")
+    if w_zero_points is not None and w_zero_points.numel() != w_scales.numel():
+        raise RuntimeError(f"w_zero_points has {w_zero_points.numel()} entries for {w_scales.numel()} output channels")
+
+
+def _output_form(out_codes):
+    """(tensor dtype, y_code_dtype, scale, zero_point, qmin, qmax) of the entry points whose ``y_code_dtype < 0`` means float32."""
+    if out_codes is None:
+        return torch.float32, -1, 1.0, 0, 0, 0
+    o_scale, o_zp, o_qmin, o_qmax = out_codes
+    tdt, ocode = ops._code_dtype(o_qmin, o_qmax)
+    return tdt, ocode, o_scale, o_zp, o_qmin, o_qmax
+
+
+def codes_rowsum(a_codes: torch.Tensor, a_zero_point: int) -> torch.Tensor:
+    """a_codes [M, K] int8/uint8 -> int32 [M], ``sum_k (a_codes[m][k] - a_zero_point)``: the per-row factor of the weight
+    zero point term (``qlinear_i8(..., w_zero_points=...)``)."""
+    if a_codes.dim() != 2 or a_codes.dtype not in (torch.int8, torch.uint8):
+        raise TypeError(f"codes_rowsum takes int8 / uint8 codes [M, K], got {a_codes.dtype} {tuple(a_codes.shape)}")
+    M, K = a_codes.shape
+    if a_codes.is_cuda:
+        if K % 16 or K > _MAX_K:
+            raise NotImplementedError(f"mctq_codes_rowsum needs K % 16 == 0 and K <= {_MAX_K}, got K={K}")
+        lib = native.load()
+        a_codes = a_codes.contiguous()
+        code = native.CODE_U8 if a_codes.dtype == torch.uint8 else native.CODE_I8
+        with ops._maybe_on_device(a_codes):
+            out = torch.empty((M,), dtype=torch.int32, device=a_codes.device)
+            rc = ops._launch(lib.mctq_codes_rowsum, a_codes.data_ptr(), code, int(a_zero_point), out.data_ptr(), M, K,
+                             ops._stream(a_codes))
+        if rc:
+            native.check(rc, "mctq_codes_rowsum")
+        return out
+    ops._cpu_route_allowed()
+    return (a_codes.to(torch.int32) - int(a_zero_point)).sum(dim=1, dtype=torch.int32)
 
 
 def qlinear_i8(a_codes: torch.Tensor, a_zero_point: int, a_scale: float, w_codes: torch.Tensor,
                w_scales: torch.Tensor, w_rowsum: torch.Tensor, bias: Optional[torch.Tensor],
-               out_codes=None) -> torch.Tensor:
-    """a_codes [M, K] int8/uint8, w_codes [N, K] int8 (zero point 0) -> float32 [M, N]; with
-    ``out_codes = (scale, zero_point, qmin, qmax)`` the result leaves as the codes of that activation quantizer
-    (int8 / uint8 [M, N]), bit-identical to quantizing the float32 result with ``ops.fq_codes``."""
+               out_codes=None, w_zero_points: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """a_codes [M, K] int8/uint8, w_codes [N, K] int8 (zero point 0 unless ``w_zero_points`` is given) -> float32
+    [M, N]; with ``out_codes = (scale, zero_point, qmin, qmax)`` the result leaves as the codes of that activation quantizer
+    (int8 / uint8 [M, N]), bit-identical to quantizing the float32 result with ``ops.fq_codes``.
+    ``w_zero_points`` (int32 [N], each in [-128, 127]): the weights are ``w_codes[n][k] - w_zero_points[n]``; the row sums
+    of the activation codes are computed first (``codes_rowsum``) and the product runs on ``mctq_qlinear_i8_zp``."""
     M, K = a_codes.shape
     N = w_codes.shape[0]
     if w_codes.shape[1] != K:
@@ -61,11 +108,23 @@ def qlinear_i8(a_codes: torch.Tensor, a_zero_point: int, a_scale: float, w_codes
     if a_codes.is_cuda:
         if K % 16 or K > _MAX_K:
             raise NotImplementedError(f"mctq_qlinear_i8 needs K % 16 == 0 and K <= {_MAX_K}, got K={K}")
-        _check_consumer_operands(a_codes, w_scales, w_rowsum, bias)
+        _check_consumer_operands(a_codes, w_scales, w_rowsum, bias, w_zero_points)
         lib = native.load()
         a_codes, w_codes = a_codes.contiguous(), w_codes.contiguous()
         code = native.CODE_U8 if a_codes.dtype == torch.uint8 else native.CODE_I8
         bias_ptr = None if bias is None else bias.data_ptr()
+        if w_zero_points is not None:
+            a_rowsum = codes_rowsum(a_codes, a_zero_point)
+            tdt, ocode, o_scale, o_zp, o_qmin, o_qmax = _output_form(out_codes)
+            with ops._maybe_on_device(a_codes):
+                y = torch.empty((M, N), dtype=tdt, device=a_codes.device)
+                rc = ops._launch(lib.mctq_qlinear_i8_zp, a_codes.data_ptr(), code, int(a_zero_point), float(a_scale),
+                                 w_codes.data_ptr(), w_scales.data_ptr(), w_rowsum.data_ptr(), bias_ptr, y.data_ptr(),
+                                 ocode, float(o_scale), int(o_zp), int(o_qmin), int(o_qmax), w_zero_points.data_ptr(),
+                                 a_rowsum.data_ptr(), M, N, K, ops._stream(a_codes))
+            if rc:
+                native.check(rc, "mctq_qlinear_i8_zp")
+            return y
         with ops._maybe_on_device(a_codes):
             if out_codes is None:
                 y = torch.empty((M, N), dtype=torch.float32, device=a_codes.device)
@@ -73,8 +132,7 @@ def qlinear_i8(a_codes: torch.Tensor, a_zero_point: int, a_scale: float, w_codes
                                  w_codes.data_ptr(), w_scales.data_ptr(), w_rowsum.data_ptr(), bias_ptr, y.data_ptr(),
                                  M, N, K, ops._stream(a_codes))
             else:
-                o_scale, o_zp, o_qmin, o_qmax = out_codes
-                tdt, ocode = ops._code_dtype(o_qmin, o_qmax)
+                tdt, ocode, o_scale, o_zp, o_qmin, o_qmax = _output_form(out_codes)
                 y = torch.empty((M, N), dtype=tdt, device=a_codes.device)
                 rc = ops._launch(lib.mctq_qlinear_i8_codes, a_codes.data_ptr(), code, int(a_zero_point), float(a_scale),
                                  w_codes.data_ptr(), w_scales.data_ptr(), w_rowsum.data_ptr(), bias_ptr, y.data_ptr(),
@@ -84,7 +142,11 @@ def qlinear_i8(a_codes: torch.Tensor, a_zero_point: int, a_scale: float, w_codes
             native.check(rc, "mctq_qlinear_i8")
         return y
     ops._cpu_route_allowed()
-    acc = (a_codes.to(torch.int32) - int(a_zero_point)) @ w_codes.to(torch.int32).t()
+    w32 = w_codes.to(torch.int32)
+    if w_zero_points is not None:
+        _check_consumer_operands(a_codes, w_scales, None, None, w_zero_points)     # dtype, device, one per output channel
+        w32 = w32 - w_zero_points.to(torch.int32).reshape(-1, 1)
+    acc = (a_codes.to(torch.int32) - int(a_zero_point)) @ w32.t()
     y = acc.to(torch.float32) * (torch.tensor(a_scale, dtype=torch.float64).to(torch.float32) * w_scales)
     if bias is not None:
         y = y + bias
@@ -104,25 +166,34 @@ def pack_w4(codes: torch.Tensor) -> torch.Tensor:
 
 def qlinear_w4a8(a_codes: torch.Tensor, a_zero_point: int, a_scale: float, w_codes4: torch.Tensor,
                  w_scales: torch.Tensor, w_rowsum: torch.Tensor, bias: Optional[torch.Tensor],
-                 out_codes=None) -> torch.Tensor:
-    """As ``qlinear_i8`` with the weights as packed 4-bit codes (``pack_w4``); GPU tensors only."""
+                 out_codes=None, w_zero_points: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """As ``qlinear_i8`` with the weights as packed 4-bit codes (``pack_w4``); GPU tensors only.  ``w_zero_points`` (int32
+    [N], in the codes' domain [-8, 7]) as there, on ``mctq_qlinear_w4a8_zp``."""
     M, K = a_codes.shape
     N = w_codes4.shape[0]
     if w_codes4.shape[1] * 2 != K:
         raise RuntimeError(f"shape mismatch: activations have K={K}, packed weights K={w_codes4.shape[1] * 2}")
     if K % 16 or K > _MAX_K:
         raise NotImplementedError(f"mctq_qlinear_w4a8 needs K % 16 == 0 and K <= {_MAX_K}, got K={K}")
-    _check_consumer_operands(a_codes, w_scales, w_rowsum, bias)
+    _check_consumer_operands(a_codes, w_scales, w_rowsum, bias, w_zero_points)
     lib = native.load()
     a_codes, w_codes4 = a_codes.contiguous(), w_codes4.contiguous()
     code = native.CODE_U8 if a_codes.dtype == torch.uint8 else native.CODE_I8
-    if out_codes is None:
-        y = torch.empty((M, N), dtype=torch.float32, device=a_codes.device)
-        ocode, o_scale, o_zp, o_qmin, o_qmax = -1, 1.0, 0, 0, 0
-    else:
-        o_scale, o_zp, o_qmin, o_qmax = out_codes
-        tdt, ocode = ops._code_dtype(o_qmin, o_qmax)
-        y = torch.empty((M, N), dtype=tdt, device=a_codes.device)
+    if w_zero_points is not None:
+        a_rowsum = codes_rowsum(a_codes, a_zero_point)
+        tdt, ocode, o_scale, o_zp, o_qmin, o_qmax = _output_form(out_codes)
+        with ops._maybe_on_device(a_codes):
+            y = torch.empty((M, N), dtype=tdt, device=a_codes.device)
+            rc = ops._launch(lib.mctq_qlinear_w4a8_zp, a_codes.data_ptr(), code, int(a_zero_point), float(a_scale),
+                             w_codes4.data_ptr(), w_scales.data_ptr(), w_rowsum.data_ptr(),
+                             None if bias is None else bias.data_ptr(), y.data_ptr(), ocode, float(o_scale), int(o_zp),
+                             int(o_qmin), int(o_qmax), w_zero_points.data_ptr(), a_rowsum.data_ptr(), M, N, K,
+                             ops._stream(a_codes))
+        if rc:
+            native.check(rc, "mctq_qlinear_w4a8_zp")
+        return y
+    tdt, ocode, o_scale, o_zp, o_qmin, o_qmax = _output_form(out_codes)
+    y = torch.empty((M, N), dtype=tdt, device=a_codes.device)
     with ops._maybe_on_device(a_codes):
         rc = ops._launch(lib.mctq_qlinear_w4a8, a_codes.data_ptr(), code, int(a_zero_point), float(a_scale),
                          w_codes4.data_ptr(), w_scales.data_ptr(), w_rowsum.data_ptr(),
@@ -182,13 +253,8 @@ def qlinear_lut4a8(a_codes: torch.Tensor, a_zero_point: int, a_scale: float, w_i
     lib = native.load()
     a_codes, w_idx4 = a_codes.contiguous(), w_idx4.contiguous()
     code = native.CODE_U8 if a_codes.dtype == torch.uint8 else native.CODE_I8
-    if out_codes is None:
-        y = torch.empty((M, N), dtype=torch.float32, device=a_codes.device)
-        ocode, o_scale, o_zp, o_qmin, o_qmax = -1, 1.0, 0, 0, 0
-    else:
-        o_scale, o_zp, o_qmin, o_qmax = out_codes
-        tdt, ocode = ops._code_dtype(o_qmin, o_qmax)
-        y = torch.empty((M, N), dtype=tdt, device=a_codes.device)
+    tdt, ocode, o_scale, o_zp, o_qmin, o_qmax = _output_form(out_codes)
+    y = torch.empty((M, N), dtype=tdt, device=a_codes.device)
     with ops._maybe_on_device(a_codes):
         rc = ops._launch(lib.mctq_qlinear_lut4a8, a_codes.data_ptr(), code, int(a_zero_point), float(a_scale),
                          w_idx4.data_ptr(), lut, w_scales.data_ptr(), w_rowsum.data_ptr(),
@@ -209,11 +275,18 @@ def _is_lut_weights(q) -> bool:
     return isinstance(q, WeightsLUTSymmetricInferableQuantizer)          # LUT-POT derives from it
 
 
+def _is_uniform_weights(q) -> bool:
+    from mct_quantizers_amd.pytorch.quantizers.affine import WeightsUniformInferableQuantizer
+    return isinstance(q, WeightsUniformInferableQuantizer)
+
+
 class QuantizedLinear(nn.Module):
     """``activation quantizer -> PytorchQuantizationWrapper(nn.Linear)`` evaluated on integer codes.
 
     ``weights_quantizer``: WeightsSymmetric / WeightsPOT (zero point 0), per tensor or per output channel
-    (``channel_axis`` 0), at most 8 bits; or WeightsLUTSymmetric / WeightsLUTPOT with ``lut_values_bitwidth`` <= 8 (int8
+    (``channel_axis`` 0), at most 8 bits; or WeightsUniform (a zero point per tensor or per output channel, at most 8 bits:
+    unsigned codes c and zero points z are kept as c - 2^(num_bits - 1) and z - 2^(num_bits - 1), both int8-ranged); or
+    WeightsLUTSymmetric / WeightsLUTPOT with ``lut_values_bitwidth`` <= 8 (int8
     codebook values) and at most 256 codebook entries, per tensor or per output channel.  ``activation_quantizer``: ActivationSymmetric / POT / Uniform, at most
     8 bits.  The float weight stays the module's parameter; its codes are rebuilt when it changes."""
 
@@ -222,13 +295,15 @@ class QuantizedLinear(nn.Module):
         if not isinstance(linear, nn.Linear):
             raise TypeError("QuantizedLinear wraps torch.nn.Linear")
         self._lut_weights = _is_lut_weights(weights_quantizer)
+        self._uniform_weights = _is_uniform_weights(weights_quantizer)
         if self._lut_weights:
             if weights_quantizer.lut_values_bitwidth > 8:
                 raise NotImplementedError("codebook values wider than 8 bits")
             if len(weights_quantizer._lut_values_np.reshape(-1)) > 256:
                 raise NotImplementedError("more than 256 codebook entries")
-        elif not hasattr(weights_quantizer, "quantize_to_codes") or not hasattr(weights_quantizer, "threshold_np"):
-            raise TypeError("the weights quantizer must be symmetric, power-of-two (zero point 0) or a LUT quantizer")
+        elif not self._uniform_weights and (not hasattr(weights_quantizer, "quantize_to_codes")
+                                            or not hasattr(weights_quantizer, "threshold_np")):
+            raise TypeError("the weights quantizer must be symmetric, power-of-two (zero point 0), uniform or a LUT quantizer")
         if weights_quantizer.per_channel and weights_quantizer.channel_axis % 2 != 0:
             raise NotImplementedError("per-channel weight scales must run along the output channels (axis 0)")
         if weights_quantizer.num_bits > 8 or activation_quantizer.num_bits > 8:
@@ -249,6 +324,7 @@ class QuantizedLinear(nn.Module):
         self._w_key = None
         self._w_codes = self._w_scales = self._w_rowsum = self._w_codes4 = None
         self._w_idx4 = self._lut16 = None                # LUT weights of at most 16 entries: packed indices + host codebook
+        self._w_zps = None                               # uniform weights: int32 zero points in the stored codes' domain
         # chaining (fuse_linear_consumers(chain=True)): parameters of the activation quantizer that would quantize
         # this layer's output next; the output then leaves as that quantizer's codes
         self.emit_codes_for = None
@@ -273,8 +349,21 @@ class QuantizedLinear(nn.Module):
             self._refresh_lut_weight_codes(w)
             self._w_key = key
             return
-        codes, scales, _ = self.weights_quantizer.quantize_to_codes(w.detach())
-        if codes.dtype != torch.int8:
+        codes, scales, zps = self.weights_quantizer.quantize_to_codes(w.detach())
+        if self._uniform_weights:
+            # unsigned codes c in 0 .. 2^bits - 1 with zero point z: both re-biased by half the domain, so that the codes are
+            # int8 (at most 4 bits: [-8, 7], the packed layout's nibbles) and c - z is unchanged
+            half = 2 ** (self.weights_quantizer.num_bits - 1)
+            if codes.dtype != torch.uint8:
+                raise RuntimeError("uniform weight codes are expected to be uint8")
+            codes = (codes.to(torch.int16) - half).to(torch.int8)
+            zps = zps.to(device=w.device, dtype=torch.int32).reshape(-1) - half
+            if zps.numel() and (int(zps.min()) < -128 or int(zps.max()) > 127):     # (a host read, once per weight change)
+                raise NotImplementedError("a weight zero point lies outside the codes' domain")
+            if zps.numel() == 1:
+                zps = zps.expand(self.out_features)
+            self._w_zps = zps.contiguous()
+        elif codes.dtype != torch.int8:
             raise RuntimeError("symmetric weight codes are expected to be int8")
         codes = codes.reshape(self.out_features, self.in_features)       # [O, C, 1, 1] of a pointwise convolution too
         scales = scales.to(device=w.device, dtype=torch.float32).reshape(-1)
@@ -331,13 +420,13 @@ class QuantizedLinear(nn.Module):
                 bias = bias.to(device=a_codes.device, dtype=torch.float32).contiguous()
         if self._w_codes4 is not None and a_codes.is_cuda and a_codes.shape[0] <= _W4_MAX_ROWS:
             y = qlinear_w4a8(a_codes, self._a_zp, self._a_scale, self._w_codes4, self._w_scales, self._w_rowsum, bias,
-                             self.emit_codes_for)
+                             self.emit_codes_for, self._w_zps)
         elif self._w_idx4 is not None and a_codes.is_cuda and a_codes.shape[0] <= _LUT4_MAX_ROWS:
             y = qlinear_lut4a8(a_codes, self._a_zp, self._a_scale, self._w_idx4, self._lut16, self._w_scales,
                                self._w_rowsum, bias, self.emit_codes_for)
         else:
             y = qlinear_i8(a_codes, self._a_zp, self._a_scale, self._w_codes, self._w_scales, self._w_rowsum, bias,
-                           self.emit_codes_for)
+                           self.emit_codes_for, self._w_zps)
         return y.reshape(*lead, self.out_features)
 
 
@@ -387,10 +476,13 @@ class QuantizedConv1x1(QuantizedLinear):
         return y.reshape(b, h, w_, self.out_features).permute(0, 3, 1, 2)
 
 
-def _consumer_for(wrapper, activation_quantizer):
-    """The integer consumer that can stand in for ``wrapper`` fed by ``activation_quantizer``, or None."""
+def _consumer_for(wrapper, activation_quantizer, uniform_weights=False):
+    """The integer consumer that can stand in for ``wrapper`` fed by ``activation_quantizer``, or None.  Uniform weights
+    only with ``uniform_weights``."""
     layer = getattr(wrapper, "layer", None)
     if list(getattr(wrapper, "weights_quantizers", {})) != ["weight"]:
+        return None
+    if _is_uniform_weights(wrapper.weights_quantizers["weight"]) and not uniform_weights:
         return None
     weight = getattr(wrapper, "weight", None)
     bias = getattr(layer, "bias", None)
@@ -417,12 +509,17 @@ def _plain_holder(m) -> bool:
     return isinstance(m, PytorchActivationQuantizationHolder) and not getattr(m, "quantization_bypass", False)
 
 
-def fuse_linear_consumers(model: nn.Module, chain: bool = False) -> int:
+def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights: bool = False) -> int:
     """In every ``nn.Sequential`` of ``model``: an activation holder directly followed by a wrapped ``nn.Linear`` with
     a symmetric, power-of-two or LUT weights quantizer (int8 codebook values, at most 256 entries) becomes (Identity,
     QuantizedLinear); a wrapped pointwise ``nn.Conv2d`` likewise becomes a QuantizedConv1x1.  Returns the number of pairs
-    replaced.  Pairs the integer consumer cannot take (other layers, uniform weights, LUT weights with
+    replaced.  Pairs the integer consumer cannot take (other layers, LUT weights with
     ``lut_values_bitwidth`` > 8 or thresholds along another axis than the output channels, K % 16 != 0) are left alone.
+
+    ``uniform_weights=True`` also fuses pairs whose weights quantizer is uniform (at most 8 bits, per tensor or per output
+    channel): the product then honours the weights' zero points at the cost of one small launch per forward (the row sums
+    of the activation codes), and large whole-tile products run on the tiled kernels rather than the faster whole-tile
+    ones.  By default such pairs are left alone.
 
     ``chain=True``: where one QuantizedLinear feeds the next directly, the float32 tensor between them is never
     materialised -- the first emits the second's activation codes from its epilogue (same codes, bit for bit, as
@@ -433,7 +530,7 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False) -> int:
             holder, wrapper = seq[i], seq[i + 1]
             if not _plain_holder(holder) or not isinstance(wrapper, PytorchQuantizationWrapper):
                 continue
-            fused = _consumer_for(wrapper, holder.activation_holder_quantizer)
+            fused = _consumer_for(wrapper, holder.activation_holder_quantizer, uniform_weights)
             if fused is None:
                 continue
             seq[i] = _FusedAway()
@@ -447,11 +544,12 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False) -> int:
     return replaced
 
 
-def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False):
+def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weights: bool = False):
     """The same rewrite on an arbitrary module graph (MCT-exported models are not ``nn.Sequential``): traces ``model``
     with torch.fx keeping wrappers and holders as leaves, and wherever an activation holder's ONLY consumer is a
-    wrapped ``nn.Linear`` the integer consumer can take (symmetric, power-of-two or LUT weights, as for
-    ``fuse_linear_consumers``), replaces the pair by one ``QuantizedLinear`` node.
+    wrapped ``nn.Linear`` the integer consumer can take (symmetric, power-of-two or LUT weights, and with
+    ``uniform_weights=True`` uniform weights, as for ``fuse_linear_consumers``), replaces the pair by one
+    ``QuantizedLinear`` node.
     Returns ``(graph_module, pairs_replaced)``.  Holders with several consumers (residual branches) stay."""
     import torch.fx as fx
 
@@ -476,7 +574,7 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False):
         holder = mods.get(src.target)
         if not _plain_holder(holder):
             continue
-        fused = _consumer_for(wrapper, holder.activation_holder_quantizer)
+        fused = _consumer_for(wrapper, holder.activation_holder_quantizer, uniform_weights)
         if fused is None:
             continue
         name = node.target.replace(".", "_") + "_qlinear"

@@ -21,8 +21,9 @@ constexpr int kQlKBlock = 256;          // bytes of K per wave step: 4 lane grou
 extern int g_ql_variant;                // tuning hook "ql_variant": 0 = automatic
 // what the calling thread launched last (mctq_last_launch): "qlinear_<kernel>_<tile>" with the code widths
 template <bool A_U8>
-static void note_ql(const char* shape, int u = 0) {
-  g_note.shape = shape; g_note.op = A_U8 ? "u8 x i8" : "i8 x i8"; g_note.unroll = u; g_note.nt = 0;
+static void note_ql(const char* shape, int u = 0, bool zp = false) {       // zp: the form with weight zero points ran
+  g_note.shape = shape; g_note.op = zp ? (A_U8 ? "u8 x i8 zp" : "i8 x i8 zp") : (A_U8 ? "u8 x i8" : "i8 x i8");
+  g_note.unroll = u; g_note.nt = 0;
   g_note.in_bytes = 1; g_note.out_bytes = 4; ++g_note.count;
   if (g_launch_log) log_launch();
 }
@@ -45,6 +46,42 @@ __device__ __forceinline__ void ql_store(void* __restrict__ y, int64_t idx, floa
     if (o.mode == 1) static_cast<int8_t*>(y)[idx] = (int8_t)(int)q;
     else static_cast<uint8_t*>(y)[idx] = (uint8_t)(int)q;
   }
+}
+
+// Weight zero points (uniform weights, mctq_qlinear_*_zp): per output channel zw[n] in the domain of the int8 codes, and
+// per activation row a_rowsum[m] = sum_k (a[m][k] - za) (mctq_codes_rowsum).  Then
+//     sum_k (a - za) (w - zw[n]) = sum_k a w - za w_rowsum[n] - zw[n] a_rowsum[m]:
+// the kernels' sum and first correction, plus one product per output in the epilogue.  Both pointers null (every other
+// entry point): the branch on them is uniform and the epilogue is the one it was.  The terms reach 2^30 each and it is
+// their total that is known to fit int32 (255 * 255 * 32768 < 2^31), so they are added in wrapping (unsigned) arithmetic.
+struct QlZp {
+  const int32_t* w_zero_points;
+  const int32_t* a_rowsum;
+};
+__device__ __forceinline__ int ql_corrected(int acc, int corr, int zw, const QlZp& zp, int m) {
+  unsigned c = (unsigned)corr;
+  if (zp.a_rowsum) c += (unsigned)zw * (unsigned)zp.a_rowsum[m];
+  return (int)((unsigned)acc - c);
+}
+// Two kernels decide at compile time instead (template flag ZP: qlinear_i8_lds_kernel and qgemm_i8_glds_kernel).  With the
+// run-time test they lost more than a build's spread against itself on mctq_qlinear_i8 (profiles/EXPERIMENTS.md: +3.3 % at
+// 16 x 4096 x 4096, +2.2 % at 256 x 4096 x 4096), so their ZP = false form is the kernel without zero points, and the
+// ZP = true form is instantiated only by the launchers, for a call that brings zero points.
+template <bool ZP>
+__device__ __forceinline__ int ql_corrected(int acc, int corr, int zw, const QlZp& zp, int m) {
+  if constexpr (ZP) return (int)((unsigned)acc - ((unsigned)corr + (unsigned)zw * (unsigned)zp.a_rowsum[m]));
+  else return acc - corr;
+}
+
+// The streaming kernels' epilogue column of this thread (== en at their top), recomputed behind a statement the compiler
+// cannot move: the address of the zero point would otherwise be hoisted out of the loop over row tiles and stay in two
+// registers across the K loop of every launch, zero points or not.  The barrier is an empty asm statement, which binds
+// the compiler by convention only: after a compiler update, compile this unit with -Rpass-analysis=kernel-resource-usage
+// and compare qlinear_i8_kernel's VGPR counts and scratch (0 bytes) with the figures in profiles/EXPERIMENTS.md.
+__device__ __forceinline__ int ql_epilogue_column(int n0, int N) {
+  int c = (int)(threadIdx.x & 15);
+  asm volatile("" : "+v"(c));
+  return min(n0 + c, N - 1);
 }
 
 template <bool NT>
@@ -122,7 +159,7 @@ template <int kQlWaves, int MT, bool A_U8, bool W_NT, int WFMT = kQlW8, class...
 __global__ __launch_bounds__(kQlWaves * 64) void qlinear_i8_kernel(
     const int8_t* __restrict__ a, const int8_t* __restrict__ w, const float* __restrict__ w_scales,
     const int32_t* __restrict__ w_rowsum, const float* __restrict__ bias, void* __restrict__ y,
-    int M, int N, int64_t K, int za, float sa, QlOut oq, Lut... lut) {
+    int M, int N, int64_t K, int za, float sa, QlOut oq, QlZp zp, Lut... lut) {
   static_assert(sizeof...(Lut) == (WFMT == kQlLut4 ? 1 : 0), "the codebook argument belongs to the LUT4 format");
   constexpr bool W4 = WFMT == kQlW4, LUT4 = WFMT == kQlLut4, HALF = W4 || LUT4;      // HALF: half a byte per weight
   constexpr int kQlThreads = kQlWaves * 64;
@@ -230,6 +267,10 @@ __global__ __launch_bounds__(kQlWaves * 64) void qlinear_i8_kernel(
       for (int i = 0; i < 4; ++i) red[wave][t][lane][i] = acc[t][i];
     }
     __syncthreads();
+    // (the zero point is fetched here and not next to e_corr: one more register live across the K loop costs the 4-bit
+    // formats a wave of occupancy or a spill; only the zero-point form waits for it.  The codebook format never has one.)
+    const QlZp zq = LUT4 ? QlZp{nullptr, nullptr} : zp;
+    const int e_zw = zq.a_rowsum ? zq.w_zero_points[ql_epilogue_column(n0, N)] : 0;
     for (int e = threadIdx.x; e < MT * 256; e += kQlThreads) {
       const int t = e >> 8, rem = e & 255;
       const int mi = rem >> 4, ni = rem & 15;                    // row / column inside the 16 x 16 tile
@@ -240,7 +281,7 @@ __global__ __launch_bounds__(kQlWaves * 64) void qlinear_i8_kernel(
       if constexpr (W4) v >>= 4;                                  // the weights entered as 16 * code: exact
       const int m = m0 + 16 * t + mi, n = n0 + ni;
       if (m < M && n < N) {
-        float out = (float)(v - e_corr) * e_scale;
+        float out = (float)ql_corrected(v, e_corr, e_zw, zq, m) * e_scale;
         if (bias) out = out + e_bias;
         ql_store(y, (int64_t)m * N + n, out, oq);
       }
@@ -264,11 +305,11 @@ __global__ __launch_bounds__(kQlWaves * 64) void qlinear_i8_kernel(
 typedef __attribute__((address_space(3))) void ql_lds_void_;
 typedef const __attribute__((address_space(1))) void ql_glb_void_;
 
-template <int kQlWaves, int MT, bool A_U8, bool W_NT>
+template <int kQlWaves, int MT, bool A_U8, bool W_NT, bool ZP = false>
 __global__ __launch_bounds__(kQlWaves * 64) void qlinear_i8_lds_kernel(
     const int8_t* __restrict__ a, const int8_t* __restrict__ w, const float* __restrict__ w_scales,
     const int32_t* __restrict__ w_rowsum, const float* __restrict__ bias, void* __restrict__ y,
-    int M, int N, int64_t K, int za, float sa, QlOut oq) {
+    int M, int N, int64_t K, int za, float sa, QlOut oq, QlZp zp) {
   constexpr int kQlThreads = kQlWaves * 64;
   constexpr int NBUF = kQlWaves * 2 * MT * 4096 <= 128 * 1024 ? 2 : 1;      // double-buffer when it fits 128 KiB
   constexpr int kSlots = MT * 256;                       // 16-byte slots of one A buffer: MT*16 rows x 16 chunks
@@ -380,6 +421,8 @@ __global__ __launch_bounds__(kQlWaves * 64) void qlinear_i8_lds_kernel(
     for (int t = 0; t < MT; ++t)
       lds[(wave * MT + t) * 64 + lane] = acc[t];
     __syncthreads();
+    int e_zw = 0;
+    if constexpr (ZP) e_zw = zp.w_zero_points[ql_epilogue_column(n0, N)];     // here, not at the top: see qlinear_i8_kernel
     for (int e = threadIdx.x; e < MT * 256; e += kQlThreads) {
       const int t = e >> 8, rem = e & 255;
       const int mi = rem >> 4, ni = rem & 15;
@@ -389,7 +432,7 @@ __global__ __launch_bounds__(kQlWaves * 64) void qlinear_i8_lds_kernel(
       for (int wv = 0; wv < kQlWaves; ++wv) v += red[((wv * MT + t) * 64 + src_lane) * 4 + src_reg];
       const int m = m0 + 16 * t + mi, n = n0 + ni;
       if (m < M && n < N) {
-        float out = (float)(v - e_corr) * e_scale;
+        float out = (float)ql_corrected<ZP>(v, e_corr, e_zw, zp, m) * e_scale;
         if (bias) out = out + e_bias;
         ql_store(y, (int64_t)m * N + n, out, oq);
       }
@@ -401,32 +444,33 @@ __global__ __launch_bounds__(kQlWaves * 64) void qlinear_i8_lds_kernel(
 template <int WAVES, int MT, bool A_U8>
 static int launch_qlinear_lds(const void* a, const int8_t* w, const float* w_scales, const int32_t* w_rowsum,
                               const float* bias, void* y, int64_t M, int64_t N, int64_t K, int za, float sa,
-                              const QlOut& oq, hipStream_t stream) {
+                              const QlOut& oq, const QlZp& zp, hipStream_t stream) {
   const dim3 grid((unsigned)((N + 15) / 16));
   const bool one_pass = M <= 16 * MT;
-  if (one_pass)
-    hipLaunchKernelGGL((qlinear_i8_lds_kernel<WAVES, MT, A_U8, true>), grid, dim3(WAVES * 64), 0, stream,
-                       (const int8_t*)a, w, w_scales, w_rowsum, bias, y, (int)M, (int)N, K, za, sa, oq);
-  else
-    hipLaunchKernelGGL((qlinear_i8_lds_kernel<WAVES, MT, A_U8, false>), grid, dim3(WAVES * 64), 0, stream,
-                       (const int8_t*)a, w, w_scales, w_rowsum, bias, y, (int)M, (int)N, K, za, sa, oq);
-  note_ql<A_U8>(WAVES == 8 ? "qlinear_stream_lds_8waves" : "qlinear_stream_lds_4waves", MT);
+#define MCTQ_QL_LDS(NT_, ZP_) \
+  hipLaunchKernelGGL((qlinear_i8_lds_kernel<WAVES, MT, A_U8, NT_, ZP_>), grid, dim3(WAVES * 64), 0, stream, \
+                     (const int8_t*)a, w, w_scales, w_rowsum, bias, y, (int)M, (int)N, K, za, sa, oq, zp)
+  if (zp.a_rowsum) { if (one_pass) MCTQ_QL_LDS(true, true); else MCTQ_QL_LDS(false, true); }
+  else { if (one_pass) MCTQ_QL_LDS(true, false); else MCTQ_QL_LDS(false, false); }
+#undef MCTQ_QL_LDS
+  note_ql<A_U8>(WAVES == 8 ? "qlinear_stream_lds_8waves" : "qlinear_stream_lds_4waves", MT, zp.a_rowsum != nullptr);
   return check_launch("mctq_qlinear_i8 (LDS-staged activations)");
 }
 
 template <int WAVES, int MT, bool A_U8, int WFMT = kQlW8, class... Lut>
 static int launch_qlinear(const void* a, const int8_t* w, const float* w_scales, const int32_t* w_rowsum,
                           const float* bias, void* y, int64_t M, int64_t N, int64_t K, int za, float sa,
-                          const QlOut& oq, hipStream_t stream, Lut... lut) {
+                          const QlOut& oq, const QlZp& zp, hipStream_t stream, Lut... lut) {
   const dim3 grid((unsigned)((N + 15) / 16));
   const bool one_pass = M <= 16 * MT;             // weights read exactly once: keep them out of the caches
   if (one_pass)
     hipLaunchKernelGGL((qlinear_i8_kernel<WAVES, MT, A_U8, true, WFMT, Lut...>), grid, dim3(WAVES * 64), 0, stream,
-                       (const int8_t*)a, w, w_scales, w_rowsum, bias, y, (int)M, (int)N, K, za, sa, oq, lut...);
+                       (const int8_t*)a, w, w_scales, w_rowsum, bias, y, (int)M, (int)N, K, za, sa, oq, zp, lut...);
   else
     hipLaunchKernelGGL((qlinear_i8_kernel<WAVES, MT, A_U8, false, WFMT, Lut...>), grid, dim3(WAVES * 64), 0, stream,
-                       (const int8_t*)a, w, w_scales, w_rowsum, bias, y, (int)M, (int)N, K, za, sa, oq, lut...);
-  note_ql<A_U8>(WFMT == kQlLut4 ? "qlinear_stream_lut4" : WFMT == kQlW4 ? "qlinear_stream_w4" : WAVES == 8 ? "qlinear_stream_8waves" : "qlinear_stream_4waves", MT);
+                       (const int8_t*)a, w, w_scales, w_rowsum, bias, y, (int)M, (int)N, K, za, sa, oq, zp, lut...);
+  note_ql<A_U8>(WFMT == kQlLut4 ? "qlinear_stream_lut4" : WFMT == kQlW4 ? "qlinear_stream_w4" : WAVES == 8 ? "qlinear_stream_8waves" : "qlinear_stream_4waves", MT,
+                zp.a_rowsum != nullptr);
   return check_launch("mctq_qlinear_i8");
 }
 
@@ -463,11 +507,11 @@ __device__ unsigned long long g_ql_stamp[16 * 8];      // per wave of ONE block:
 // tiles run at the copy issue rate, which grows with the waves that issue), group g multiplies the g-th half of the
 // 64-byte sub-steps of every K tile into its own accumulators, and the two partial sums meet in LDS at the end (exact
 // integer sums: the order does not matter).
-template <int BM, int BN, int kTileBK, bool A_U8, int ST = 2, int KG = 1>
+template <int BM, int BN, int kTileBK, bool A_U8, int ST = 2, int KG = 1, bool ZP = false>
 __global__ __launch_bounds__(256 * KG) void qgemm_i8_glds_kernel(
     const int8_t* __restrict__ a, const int8_t* __restrict__ w, const float* __restrict__ w_scales,
     const int32_t* __restrict__ w_rowsum, const float* __restrict__ bias, void* __restrict__ y,
-    int M, int N, int64_t K, int za, float sa, int m_blocks, int n_blocks, int gm, int flags, QlOut oq) {
+    int M, int N, int64_t K, int za, float sa, int m_blocks, int n_blocks, int gm, int flags, QlOut oq, QlZp zp) {
   const bool rotate = (flags & 1) != 0;              // K rotation (below)
   const bool stagger = (flags & 2) != 0;             // half of the waves request the later tile AFTER multiplying (below)
   constexpr int TM = BM / 32, TN = BN / 32;
@@ -644,13 +688,15 @@ __global__ __launch_bounds__(256 * KG) void qgemm_i8_glds_kernel(
   for (int u = 0; u < TN; ++u) {
     const int n = n0 + wn * (BN / 2) + 16 * u + r;
     if (n >= N) continue;
+    int e_zw = 0;
+    if constexpr (ZP) e_zw = zp.w_zero_points[n];                // here, not with e_corr: nothing more stays live across the K loop
 #pragma unroll
     for (int t = 0; t < TM; ++t) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int m = m0 + wm * (BM / 2) + 16 * t + 4 * g + i;
         if (m < M) {
-          float out = (float)(acc[t][u][i] - e_corr[u]) * e_scale[u];
+          float out = (float)ql_corrected<ZP>(acc[t][u][i], e_corr[u], e_zw, zp, m) * e_scale[u];
           if (bias) out = out + e_bias[u];
           ql_store(y, (int64_t)m * N + n, out, oq);
         }
@@ -662,7 +708,7 @@ __global__ __launch_bounds__(256 * KG) void qgemm_i8_glds_kernel(
 template <int BM, int BN, int BK, bool A_U8, int ST = 2, int KG = 1>
 static int launch_glds(const void* a, const int8_t* w, const float* w_scales, const int32_t* w_rowsum,
                        const float* bias, void* y, int64_t M, int64_t N, int64_t K, int za, float sa,
-                       const QlOut& oq, hipStream_t stream) {
+                       const QlOut& oq, const QlZp& zp, hipStream_t stream) {
   const int mbl = (int)((M + BM - 1) / BM), nbl = (int)((N + BN - 1) / BN);
   // tile rows per band: an XCD's chunk of total / 8 consecutive tiles as a gm x (chunk / gm) rectangle with the least
   // gm * BM + (chunk / gm) * BN, i.e. gm ~ sqrt(chunk * BN / BM)   (tuning key "ql_band" overrides)
@@ -673,13 +719,16 @@ static int launch_glds(const void* a, const int8_t* w, const float* w_scales, co
   }
   gm = gm < 1 ? 1 : gm > mbl ? mbl : gm;
   const int flags = (g_ql_rot && gm > 1 ? 1 : 0) | (g_ql_stagger ? 2 : 0);
-  hipLaunchKernelGGL((qgemm_i8_glds_kernel<BM, BN, BK, A_U8, ST, KG>), dim3((unsigned)(mbl * nbl)), dim3(256 * KG), 0, stream,
-                     (const int8_t*)a, w, w_scales, w_rowsum, bias, y, (int)M, (int)N, K, za, sa, mbl, nbl, gm, flags, oq);
+#define MCTQ_QL_GLDS(ZP_) \
+  hipLaunchKernelGGL((qgemm_i8_glds_kernel<BM, BN, BK, A_U8, ST, KG, ZP_>), dim3((unsigned)(mbl * nbl)), dim3(256 * KG), 0, stream, \
+                     (const int8_t*)a, w, w_scales, w_rowsum, bias, y, (int)M, (int)N, K, za, sa, mbl, nbl, gm, flags, oq, zp)
+  if (zp.a_rowsum) MCTQ_QL_GLDS(true); else MCTQ_QL_GLDS(false);
+#undef MCTQ_QL_GLDS
   static char name[48];                              // "qlinear_tiled[_ring]_<BM>x<BN>x<BK>", formatted once per instantiation
   static const bool named = (snprintf(name, sizeof(name), "qlinear_tiled%s%s_%dx%dx%d", ST > 2 || (BM == 128 && BN == 64) ? "_ring" : "",
                                       KG == 2 ? "_8waves" : KG == 4 ? "_16waves" : "", BM, BN, BK), true);
   (void)named;
-  note_ql<A_U8>(name, gm);
+  note_ql<A_U8>(name, gm, zp.a_rowsum != nullptr);
   return check_launch("mctq_qlinear_i8 (tiled, direct-to-LDS)");
 }
 
@@ -1066,17 +1115,72 @@ static int launch_wide(const void* a, const int8_t* w, const float* w_scales, co
   return check_launch("mctq_qlinear_i8 (wide tiles)");
 }
 
+// ------------------------------------------------------------------------------------------------
+// Row sums of activation codes, a_rowsum[m] = sum_k (a[m][k] - za): the per-row factor of the weight zero point term
+// (QlZp).  A lane loads 16 bytes and sums them with four packed dot products against 0x01010101 (v_dot4_i32_i8 /
+// v_dot4_u32_u8: uint8 codes are summed unsigned, no re-bias needed); the lanes' sums meet by wave shuffles and, when a
+// whole block walks one row (BLOCK), the four waves' sums through LDS.  No atomics: integer sums, any order, one result.
+// ------------------------------------------------------------------------------------------------
+constexpr int kRowsumThreads = 256;
+template <bool A_U8, bool BLOCK>
+__global__ __launch_bounds__(kRowsumThreads) void codes_rowsum_kernel(const int8_t* __restrict__ a, int32_t* __restrict__ out,
+                                                                      int M, int K, int za) {
+  constexpr int kWaves = kRowsumThreads / 64;
+  __shared__ int part[kWaves];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int m = BLOCK ? (int)blockIdx.x : (int)blockIdx.x * kWaves + wave;       // grid: M blocks / ceil(M / 4) blocks
+  const bool live = m < M;                                                       // (BLOCK: always)
+  const int8_t* row = a + (int64_t)(live ? m : M - 1) * K;
+  const int first = 16 * (BLOCK ? (int)threadIdx.x : lane), step = 16 * (BLOCK ? kRowsumThreads : 64);
+  int sum = 0;
+  for (int k = first; k < K; k += step) {                                        // K % 16 == 0: a piece that starts inside K ends inside it
+    const i32x4 v = *reinterpret_cast<const i32x4*>(row + k);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if constexpr (A_U8) sum = (int)__builtin_amdgcn_udot4((unsigned)v[i], 0x01010101u, (unsigned)sum, false);
+      else sum = __builtin_amdgcn_sdot4(v[i], 0x01010101, sum, false);
+    }
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off);
+  const unsigned bias = (unsigned)K * (unsigned)za;                              // wraps like the sum it leaves
+  if constexpr (BLOCK) {
+    if (lane == 0) part[wave] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      int total = 0;
+#pragma unroll
+      for (int wv = 0; wv < kWaves; ++wv) total += part[wv];
+      out[m] = (int)((unsigned)total - bias);
+    }
+  } else {
+    if (lane == 0 && live) out[m] = (int)((unsigned)sum - bias);
+  }
+}
+
+// One block per row up to this many rows, one wave per row beyond.  Measured (tools/zp_consumer_probe.py --rowsum-only, both
+// forms forced beside the dispatch, profiles/EXPERIMENTS.md): for K = 1024 / 4096 / 32768 and 1 to 1024 rows both forms take
+// the time of an empty launch (6.2-6.6 us back to back, the forms within 0.2 us of each other in either direction), so the
+// data give no reason to move the crossover; at 4096 rows of 32 KiB, the one cell above that floor, a wave per row wins
+// (19.5 against 20.2 us).  64 stays: a few rows of a long K are not walked by a single wave each.
+#ifndef MCTQ_ROWSUM_BLOCK_ROWS             // timing experiment (tools/zp_consumer_probe.py --rowsum-only): 0 / 1 << 30 force a form
+#define MCTQ_ROWSUM_BLOCK_ROWS 64
+#endif
+constexpr int64_t kRowsumBlockRows = MCTQ_ROWSUM_BLOCK_ROWS;
+
 }  // namespace mctq
 
 using namespace mctq;
 
 static int qlinear_dispatch(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
                             const int8_t* w_codes, const float* w_scales, const int32_t* w_rowsum, const float* bias,
-                            void* y, const QlOut& oq, int64_t M, int64_t N, int64_t K, void* stream) {
+                            void* y, const QlOut& oq, const QlZp& zp, bool with_zp, int64_t M, int64_t N, int64_t K,
+                            void* stream) {
   if (M < 0 || N < 0 || K < 0) return fail_arg("negative extent");
   if (a_code_dtype != MCTQ_CODE_I8 && a_code_dtype != MCTQ_CODE_U8) return fail_arg("bad a_code_dtype");
   if (M == 0 || N == 0) return 0;
   if (!a_codes || !w_codes || !w_scales || !w_rowsum || !y) return fail_arg("NULL pointer");
+  if (with_zp && (!zp.w_zero_points || !zp.a_rowsum)) return fail_arg("w_zero_points and a_rowsum are both required");
   if (K % 16 != 0) return fail_arg("K must be a multiple of 16");
   if ((((uintptr_t)a_codes | (uintptr_t)w_codes) & 15u) != 0) return fail_arg("code matrices must be 16-byte aligned");
   if (K > (1 << 15)) return fail_arg("K > 32768 could overflow the int32 accumulator");
@@ -1085,25 +1189,27 @@ static int qlinear_dispatch(const void* a_codes, int32_t a_code_dtype, int32_t a
   const int za = u8 ? a_zero_point - 128 : a_zero_point;
   const hipStream_t s = (hipStream_t)stream;
 #define MCTQ_QLL(W_, MT_)                                                                                          \
-  (u8 ? launch_qlinear_lds<W_, MT_, true>(a_codes, w_codes, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, s) \
-      : launch_qlinear_lds<W_, MT_, false>(a_codes, w_codes, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, s))
+  (u8 ? launch_qlinear_lds<W_, MT_, true>(a_codes, w_codes, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, zp, s) \
+      : launch_qlinear_lds<W_, MT_, false>(a_codes, w_codes, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, zp, s))
 #define MCTQ_QG(BM_, BN_, BK_)                                                                                    \
-  (u8 ? launch_glds<BM_, BN_, BK_, true>(a_codes, w_codes, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, s)  \
-      : launch_glds<BM_, BN_, BK_, false>(a_codes, w_codes, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, s))
+  (u8 ? launch_glds<BM_, BN_, BK_, true>(a_codes, w_codes, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, zp, s)  \
+      : launch_glds<BM_, BN_, BK_, false>(a_codes, w_codes, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, zp, s))
 #define MCTQ_QW(TM_, TN_)                                                                                         \
   (u8 ? launch_wide<TM_, TN_, true>(a_codes, w_codes, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, s)      \
       : launch_wide<TM_, TN_, false>(a_codes, w_codes, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, s))
 #define MCTQ_QG16(BM_, BN_, BK_, ST_)                                                                                      \
-  (u8 ? launch_glds<BM_, BN_, BK_, true, ST_, 4>(a_codes, w_codes, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, s)  \
-      : launch_glds<BM_, BN_, BK_, false, ST_, 4>(a_codes, w_codes, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, s))
+  (u8 ? launch_glds<BM_, BN_, BK_, true, ST_, 4>(a_codes, w_codes, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, zp, s)  \
+      : launch_glds<BM_, BN_, BK_, false, ST_, 4>(a_codes, w_codes, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, zp, s))
 #define MCTQ_QG8(BM_, BN_, BK_, ST_)                                                                                       \
-  (u8 ? launch_glds<BM_, BN_, BK_, true, ST_, 2>(a_codes, w_codes, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, s)  \
-      : launch_glds<BM_, BN_, BK_, false, ST_, 2>(a_codes, w_codes, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, s))
+  (u8 ? launch_glds<BM_, BN_, BK_, true, ST_, 2>(a_codes, w_codes, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, zp, s)  \
+      : launch_glds<BM_, BN_, BK_, false, ST_, 2>(a_codes, w_codes, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, zp, s))
 #define MCTQ_QPP()                                                                                                    \
   (u8 ? launch_pp<true>(a_codes, w_codes, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, s)                      \
       : launch_pp<false>(a_codes, w_codes, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, s))
   // tuning key "ql_variant": force ONE of the kernels the automatic choice below can select (tests run each of them over
   // ragged shapes against the integer oracle); the experiment variants of round 3 are not built any more
+  if (with_zp && (g_ql_variant == 2544 || g_ql_variant == 2548 || g_ql_variant == 2560))
+    return fail_arg("the register-pinned whole-tile kernels (ql_variant 2544 / 2548 / 2560) are not built for zero-point weights");
   switch (g_ql_variant) {
     case 181: return MCTQ_QLL(8, 1);                  // weight streaming, activation codes through per-wave LDS: 16 / 32 / 64 rows per pass
     case 182: return MCTQ_QLL(8, 2);
@@ -1130,7 +1236,8 @@ static int qlinear_dispatch(const void* a_codes, int32_t a_code_dtype, int32_t a
   // tiles; profiles/r02/qgemm_wide_probe.log) or, when there are too few such tiles for the chip, 128 x 256 wave-wide
   // tiles -- weighed by how full their last round of blocks is (one block per CU; the 128 x 128 kernel fits two).
   // Only where the 128 x 128 kernel would fill the chip: smaller problems keep its finer tiles.
-  if (K % 128 == 0 && K >= 256 && N % 256 == 0 && M % 128 == 0 && blocks(128, 128) >= 2 * cus) {
+  // (Zero-point weights: those two kernels and the pinned 128 x 128 candidate below do not take them; the tiled kernels do.)
+  if (!with_zp && K % 128 == 0 && K >= 256 && N % 256 == 0 && M % 128 == 0 && blocks(128, 128) >= 2 * cus) {
     const auto fill = [&](int64_t nb, int64_t slots) { return (double)nb / (double)(((nb + slots - 1) / slots) * slots); };
     const double old_rate = 1.5 * fill(blocks(128, 128), 2 * cus);
     const double pp_rate = M % 256 == 0 ? 2.25 * fill(blocks(256, 256), cus) : 0.0;
@@ -1175,7 +1282,7 @@ static int qlinear_dispatch(const void* a_codes, int32_t a_code_dtype, int32_t a
     consider(kT126X, tiles_cost(128, 64, 1, 48, 0, 0));         // 16 waves, 256-byte K steps: one block per CU
     consider(kT612, tiles_cost(64, 128, 3, 36, 50, 64));
     consider(kT1212, tiles_cost(128, 128, 2, 30, 48, 0));
-    if (K % 128 == 0 && K >= 256 && N % 128 == 0 && M % 128 == 0) consider(kW44, tiles_cost(128, 128, 2, 38, 43, 0));
+    if (!with_zp && K % 128 == 0 && K >= 256 && N % 128 == 0 && M % 128 == 0) consider(kW44, tiles_cost(128, 128, 2, 38, 43, 0));
     switch (pick) {
       case kStream1: return MCTQ_QLL(8, 1);
       case kStream2: return MCTQ_QLL(8, 2);
@@ -1200,26 +1307,34 @@ static int qlinear_dispatch(const void* a_codes, int32_t a_code_dtype, int32_t a
 #undef MCTQ_QLL
 }
 
-// The two entry points that stream half a byte per weight: 4-bit codes (lut == nullptr) or 4-bit indices into *lut.
+// y_code_dtype < 0: float32 output; otherwise the next layer's codes (mctq_qlinear_i8_codes' checks and parameters).
+static int ql_output_form(QlOut& oq, int32_t y_code_dtype, float y_scale, int32_t y_zero_point, int32_t y_quant_min,
+                          int32_t y_quant_max) {
+  oq.mode = 0; oq.inv = oq.zf = oq.lo = oq.hi = 0.0f;
+  if (y_code_dtype < 0) return 0;
+  if (y_code_dtype != MCTQ_CODE_I8 && y_code_dtype != MCTQ_CODE_U8) return fail_arg("bad y_code_dtype");
+  if (y_quant_min > y_quant_max) return fail_arg("quant_min > quant_max");
+  if (y_code_dtype == MCTQ_CODE_I8 ? (y_quant_min < -128 || y_quant_max > 127) : (y_quant_min < 0 || y_quant_max > 255))
+    return fail_arg("clamp domain does not fit the code type");
+  oq.mode = y_code_dtype == MCTQ_CODE_I8 ? 1 : 2;
+  oq.inv = 1.0f / y_scale;                           // host IEEE division == the codes kernel's
+  oq.zf = (float)y_zero_point; oq.lo = (float)y_quant_min; oq.hi = (float)y_quant_max;
+  return 0;
+}
+
+// The entry points that stream half a byte per weight: 4-bit codes (lut == nullptr) or 4-bit indices into *lut.
 static int qlinear_packed4(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
                            const uint8_t* w_codes4, const QlLut* lut, const float* w_scales, const int32_t* w_rowsum,
                            const float* bias, void* y, int32_t y_code_dtype, float y_scale, int32_t y_zero_point,
-                           int32_t y_quant_min, int32_t y_quant_max, int64_t M, int64_t N, int64_t K, void* stream) {
+                           int32_t y_quant_min, int32_t y_quant_max, const QlZp& zp, bool with_zp, int64_t M, int64_t N,
+                           int64_t K, void* stream) {
   if (M < 0 || N < 0 || K < 0) return fail_arg("negative extent");
   if (a_code_dtype != MCTQ_CODE_I8 && a_code_dtype != MCTQ_CODE_U8) return fail_arg("bad a_code_dtype");
   QlOut oq;
-  oq.mode = 0; oq.inv = oq.zf = oq.lo = oq.hi = 0.0f;
-  if (y_code_dtype >= 0) {
-    if (y_code_dtype != MCTQ_CODE_I8 && y_code_dtype != MCTQ_CODE_U8) return fail_arg("bad y_code_dtype");
-    if (y_quant_min > y_quant_max) return fail_arg("quant_min > quant_max");
-    if (y_code_dtype == MCTQ_CODE_I8 ? (y_quant_min < -128 || y_quant_max > 127) : (y_quant_min < 0 || y_quant_max > 255))
-      return fail_arg("clamp domain does not fit the code type");
-    oq.mode = y_code_dtype == MCTQ_CODE_I8 ? 1 : 2;
-    oq.inv = 1.0f / y_scale;
-    oq.zf = (float)y_zero_point; oq.lo = (float)y_quant_min; oq.hi = (float)y_quant_max;
-  }
+  if (int rc = ql_output_form(oq, y_code_dtype, y_scale, y_zero_point, y_quant_min, y_quant_max)) return rc;
   if (M == 0 || N == 0) return 0;
   if (!a_codes || !w_codes4 || !w_scales || !w_rowsum || !y) return fail_arg("NULL pointer");
+  if (with_zp && (!zp.w_zero_points || !zp.a_rowsum)) return fail_arg("w_zero_points and a_rowsum are both required");
   if (K % 16 != 0) return fail_arg("K must be a multiple of 16");
   if ((((uintptr_t)a_codes) & 15u) != 0 || (((uintptr_t)w_codes4) & 7u) != 0)
     return fail_arg("a_codes must be 16-byte and the packed weights (w_codes4 / w_idx4) 8-byte aligned");
@@ -1230,11 +1345,11 @@ static int qlinear_packed4(const void* a_codes, int32_t a_code_dtype, int32_t a_
   const int8_t* w = reinterpret_cast<const int8_t*>(w_codes4);
   const hipStream_t s = (hipStream_t)stream;
 #define MCTQ_QL4(MT_)                                                                                               \
-  (u8 ? launch_qlinear<8, MT_, true, kQlW4>(a_codes, w, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, s)     \
-      : launch_qlinear<8, MT_, false, kQlW4>(a_codes, w, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, s))
+  (u8 ? launch_qlinear<8, MT_, true, kQlW4>(a_codes, w, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, zp, s)     \
+      : launch_qlinear<8, MT_, false, kQlW4>(a_codes, w, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, zp, s))
 #define MCTQ_QLUT4(MT_)                                                                                                    \
-  (u8 ? launch_qlinear<8, MT_, true, kQlLut4>(a_codes, w, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, s, *lut)   \
-      : launch_qlinear<8, MT_, false, kQlLut4>(a_codes, w, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, s, *lut))
+  (u8 ? launch_qlinear<8, MT_, true, kQlLut4>(a_codes, w, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, zp, s, *lut)   \
+      : launch_qlinear<8, MT_, false, kQlLut4>(a_codes, w, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, zp, s, *lut))
   if (lut) {
     if (M <= 16) return MCTQ_QLUT4(1);
     if (M <= 32) return MCTQ_QLUT4(2);
@@ -1254,8 +1369,8 @@ int mctq_qlinear_i8(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_po
                     float* y, int64_t M, int64_t N, int64_t K, void* stream) {
   QlOut oq;
   oq.mode = 0; oq.inv = oq.zf = oq.lo = oq.hi = 0.0f;
-  return qlinear_dispatch(a_codes, a_code_dtype, a_zero_point, a_scale, w_codes, w_scales, w_rowsum, bias, y, oq, M, N, K,
-                          stream);
+  return qlinear_dispatch(a_codes, a_code_dtype, a_zero_point, a_scale, w_codes, w_scales, w_rowsum, bias, y, oq,
+                          QlZp{nullptr, nullptr}, false, M, N, K, stream);
 }
 
 int mctq_qlinear_i8_codes(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
@@ -1270,8 +1385,8 @@ int mctq_qlinear_i8_codes(const void* a_codes, int32_t a_code_dtype, int32_t a_z
   oq.mode = y_code_dtype == MCTQ_CODE_I8 ? 1 : 2;
   oq.inv = 1.0f / y_scale;                           // host IEEE division == the codes kernel's
   oq.zf = (float)y_zero_point; oq.lo = (float)y_quant_min; oq.hi = (float)y_quant_max;
-  return qlinear_dispatch(a_codes, a_code_dtype, a_zero_point, a_scale, w_codes, w_scales, w_rowsum, bias, y_codes, oq, M,
-                          N, K, stream);
+  return qlinear_dispatch(a_codes, a_code_dtype, a_zero_point, a_scale, w_codes, w_scales, w_rowsum, bias, y_codes, oq,
+                          QlZp{nullptr, nullptr}, false, M, N, K, stream);
 }
 
 
@@ -1280,7 +1395,8 @@ int mctq_qlinear_w4a8(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_
                       void* y, int32_t y_code_dtype, float y_scale, int32_t y_zero_point, int32_t y_quant_min,
                       int32_t y_quant_max, int64_t M, int64_t N, int64_t K, void* stream) {
   return qlinear_packed4(a_codes, a_code_dtype, a_zero_point, a_scale, w_codes4, nullptr, w_scales, w_rowsum, bias, y,
-                         y_code_dtype, y_scale, y_zero_point, y_quant_min, y_quant_max, M, N, K, stream);
+                         y_code_dtype, y_scale, y_zero_point, y_quant_min, y_quant_max, QlZp{nullptr, nullptr}, false, M, N, K,
+                         stream);
 }
 
 int mctq_qlinear_lut4a8(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
@@ -1291,7 +1407,54 @@ int mctq_qlinear_lut4a8(const void* a_codes, int32_t a_code_dtype, int32_t a_zer
   QlLut lut;
   memcpy(lut.t, lut16, sizeof(lut.t));                // entry j -> byte j % 4 of dword j / 4 (little endian)
   return qlinear_packed4(a_codes, a_code_dtype, a_zero_point, a_scale, w_idx4, &lut, w_scales, w_rowsum, bias, y,
-                         y_code_dtype, y_scale, y_zero_point, y_quant_min, y_quant_max, M, N, K, stream);
+                         y_code_dtype, y_scale, y_zero_point, y_quant_min, y_quant_max, QlZp{nullptr, nullptr}, false, M, N, K,
+                         stream);
+}
+
+int mctq_codes_rowsum(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, int32_t* a_rowsum, int64_t M,
+                      int64_t K, void* stream) {
+  if (M < 0 || K < 0) return fail_arg("negative extent");
+  if (a_code_dtype != MCTQ_CODE_I8 && a_code_dtype != MCTQ_CODE_U8) return fail_arg("bad a_code_dtype");
+  if (M == 0) return 0;
+  if (!a_codes || !a_rowsum) return fail_arg("NULL pointer");
+  if (K % 16 != 0) return fail_arg("K must be a multiple of 16");
+  if ((((uintptr_t)a_codes) & 15u) != 0) return fail_arg("a_codes must be 16-byte aligned");
+  if (K > (1 << 15)) return fail_arg("K > 32768: outside the consumer's limit");
+  if (M > INT32_MAX / 2) return fail_arg("M too large");
+  const hipStream_t s = (hipStream_t)stream;
+  const bool u8 = a_code_dtype == MCTQ_CODE_U8, block = M <= kRowsumBlockRows;
+  const dim3 grid((unsigned)(block ? M : (M + 3) / 4));
+  const int8_t* a = static_cast<const int8_t*>(a_codes);
+#define MCTQ_ROWSUM(U8_, BLOCK_) \
+  hipLaunchKernelGGL((codes_rowsum_kernel<U8_, BLOCK_>), grid, dim3(kRowsumThreads), 0, s, a, a_rowsum, (int)M, (int)K, (int)a_zero_point)
+  if (u8) { if (block) MCTQ_ROWSUM(true, true); else MCTQ_ROWSUM(true, false); }
+  else { if (block) MCTQ_ROWSUM(false, true); else MCTQ_ROWSUM(false, false); }
+#undef MCTQ_ROWSUM
+  g_note.shape = "codes_rowsum"; g_note.op = block ? (u8 ? "u8 block per row" : "i8 block per row") : (u8 ? "u8 wave per row" : "i8 wave per row");
+  g_note.unroll = 1; g_note.nt = 0; g_note.in_bytes = 1; g_note.out_bytes = 4; ++g_note.count;
+  if (g_launch_log) log_launch();
+  return check_launch("mctq_codes_rowsum");
+}
+
+int mctq_qlinear_i8_zp(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
+                       const int8_t* w_codes, const float* w_scales, const int32_t* w_rowsum, const float* bias,
+                       void* y, int32_t y_code_dtype, float y_scale, int32_t y_zero_point, int32_t y_quant_min,
+                       int32_t y_quant_max, const int32_t* w_zero_points, const int32_t* a_rowsum, int64_t M, int64_t N,
+                       int64_t K, void* stream) {
+  QlOut oq;
+  if (int rc = ql_output_form(oq, y_code_dtype, y_scale, y_zero_point, y_quant_min, y_quant_max)) return rc;
+  return qlinear_dispatch(a_codes, a_code_dtype, a_zero_point, a_scale, w_codes, w_scales, w_rowsum, bias, y, oq,
+                          QlZp{w_zero_points, a_rowsum}, true, M, N, K, stream);
+}
+
+int mctq_qlinear_w4a8_zp(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
+                         const uint8_t* w_codes4, const float* w_scales, const int32_t* w_rowsum, const float* bias,
+                         void* y, int32_t y_code_dtype, float y_scale, int32_t y_zero_point, int32_t y_quant_min,
+                         int32_t y_quant_max, const int32_t* w_zero_points, const int32_t* a_rowsum, int64_t M, int64_t N,
+                         int64_t K, void* stream) {
+  return qlinear_packed4(a_codes, a_code_dtype, a_zero_point, a_scale, w_codes4, nullptr, w_scales, w_rowsum, bias, y,
+                         y_code_dtype, y_scale, y_zero_point, y_quant_min, y_quant_max, QlZp{w_zero_points, a_rowsum}, true,
+                         M, N, K, stream);
 }
 
 #ifdef MCTQ_QL_STAMP

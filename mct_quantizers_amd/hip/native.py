@@ -122,6 +122,16 @@ SIGNATURES = {
                                            ctypes.c_void_p, ctypes.c_void_p, _c_f32p, _c_i32p, _c_f32p, ctypes.c_void_p,
                                            ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                            ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
+    "mctq_codes_rowsum": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, _c_i32p, ctypes.c_int64,
+                                         ctypes.c_int64, ctypes.c_void_p]),
+    "mctq_qlinear_i8_zp": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
+                                          ctypes.c_void_p, _c_f32p, _c_i32p, _c_f32p, ctypes.c_void_p, ctypes.c_int32,
+                                          ctypes.c_float, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _c_i32p, _c_i32p,
+                                          ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
+    "mctq_qlinear_w4a8_zp": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
+                                            ctypes.c_void_p, _c_f32p, _c_i32p, _c_f32p, ctypes.c_void_p, ctypes.c_int32,
+                                            ctypes.c_float, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _c_i32p, _c_i32p,
+                                            ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
     "mctq_fq_codes_nchw_to_nhwc": (ctypes.c_int, [_c_f32p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                                   ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_int32,
                                                   ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
