@@ -51,12 +51,13 @@ def _activation_code_params(q):
 
 def _check_consumer_operands(a_codes, w_scales, w_rowsum, bias, w_zero_points=None):
     """The kernels read w_scales / bias as float32 and w_rowsum / w_zero_points as int32, all on a_codes' device."""
+    device = a_codes.device
     for name, t, dt in (("w_scales", w_scales, torch.float32), ("w_rowsum", w_rowsum, torch.int32), ("bias", bias, torch.float32),
                         ("w_zero_points", w_zero_points, torch.int32)):
         if t is None:
             continue
-        if t.dtype != dt or t.device != a_codes.device or not t.is_contiguous():
-            raise TypeError(f"{name} must be a contiguous {dt} tensor on {a_codes.device}, got {t.dtype} on {t.device}")
+        if t.dtype != dt or t.device != device or not t.is_contiguous():
+            raise TypeError(f"{name} must be a contiguous {dt} tensor on {device}, got {t.dtype} on {t.device}")
     if w_zero_points is not None and w_zero_points.numel() != w_scales.numel():
         raise RuntimeError(f"w_zero_points has {w_zero_points.numel()} entries for {w_scales.numel()} output channels")
 
@@ -67,7 +68,7 @@ def _output_form(out_codes):
         return torch.float32, -1, 1.0, 0, 0, 0
     o_scale, o_zp, o_qmin, o_qmax = out_codes
     tdt, ocode = ops._code_dtype(o_qmin, o_qmax)
-    return tdt, ocode, o_scale, o_zp, o_qmin, o_qmax
+    return tdt, ocode, float(o_scale), int(o_zp), int(o_qmin), int(o_qmax)
 
 
 def codes_rowsum(a_codes: torch.Tensor, a_zero_point: int) -> torch.Tensor:
@@ -83,7 +84,7 @@ def codes_rowsum(a_codes: torch.Tensor, a_zero_point: int) -> torch.Tensor:
         a_codes = a_codes.contiguous()
         code = native.CODE_U8 if a_codes.dtype == torch.uint8 else native.CODE_I8
         with ops._maybe_on_device(a_codes):
-            out = torch.empty((M,), dtype=torch.int32, device=a_codes.device)
+            out = a_codes.new_empty((M,), dtype=torch.int32)
             rc = ops._launch(lib.mctq_codes_rowsum, a_codes.data_ptr(), code, int(a_zero_point), out.data_ptr(), M, K,
                              ops._stream(a_codes))
         if rc:
@@ -91,6 +92,50 @@ def codes_rowsum(a_codes: torch.Tensor, a_zero_point: int) -> torch.Tensor:
         return out
     ops._cpu_route_allowed()
     return (a_codes.to(torch.int32) - int(a_zero_point)).sum(dim=1, dtype=torch.int32)
+
+
+def _k_mismatch(K, w_k, what):
+    return RuntimeError(f"shape mismatch: activations have K={K}, {what} K={w_k}")
+
+
+def _launch_consumer(name, a_codes, a_zero_point, a_scale, w, lut, w_scales, w_rowsum, bias, out_codes, w_zero_points):
+    """One consumer launch on GPU tensors.  ``name`` is the entry point of the weight format: ``mctq_qlinear_i8`` (``w``: int8
+    codes [N, K]), ``mctq_qlinear_w4a8`` (packed 4-bit codes [N, K / 2]) or ``mctq_qlinear_lut4a8`` (packed 4-bit indices
+    [N, K / 2] and ``lut = (the 16 codebook bytes,)``; for the others ``lut = ()``).  ``w_zero_points`` selects the ``_zp``
+    form of the first two, and ``out_codes`` on int8 weights without zero points ``mctq_qlinear_i8_codes``."""
+    M, K = a_codes.shape
+    N, w_k = w.shape
+    packed = name != "mctq_qlinear_i8"
+    if packed:
+        w_k *= 2
+    if w_k != K:
+        raise _k_mismatch(K, w_k, "packed weights" if packed else "weights")
+    if K % 16 or K > _MAX_K:
+        raise NotImplementedError(f"{name} needs K % 16 == 0 and K <= {_MAX_K}, got K={K}")
+    _check_consumer_operands(a_codes, w_scales, w_rowsum, bias, w_zero_points)
+    lib = native.load()
+    a_codes, w = a_codes.contiguous(), w.contiguous()
+    code = native.CODE_U8 if a_codes.dtype == torch.uint8 else native.CODE_I8
+    if w_zero_points is not None:
+        name += "_zp"
+        a_rowsum = codes_rowsum(a_codes, a_zero_point)       # named: it must outlive the launch, or y is allocated over it
+        zp = (w_zero_points.data_ptr(), a_rowsum.data_ptr())
+        fn = getattr(lib, name)
+    else:
+        zp = ()
+        fn = getattr(lib, name if packed or out_codes is None else "mctq_qlinear_i8_codes")
+    if fn is lib.mctq_qlinear_i8:
+        tdt, form = torch.float32, ()                   # the float32-only entry point: no output form among its arguments
+    else:
+        tdt, *form = _output_form(out_codes)
+    with ops._maybe_on_device(a_codes):
+        y = a_codes.new_empty((M, N), dtype=tdt)
+        rc = ops._launch(fn, a_codes.data_ptr(), code, int(a_zero_point), float(a_scale), w.data_ptr(), *lut, w_scales.data_ptr(),
+                         w_rowsum.data_ptr(), None if bias is None else bias.data_ptr(), y.data_ptr(), *form, *zp, M, N, K,
+                         ops._stream(a_codes))
+    if rc:
+        native.check(rc, name)
+    return y
 
 
 def qlinear_i8(a_codes: torch.Tensor, a_zero_point: int, a_scale: float, w_codes: torch.Tensor,
@@ -101,46 +146,11 @@ def qlinear_i8(a_codes: torch.Tensor, a_zero_point: int, a_scale: float, w_codes
     (int8 / uint8 [M, N]), bit-identical to quantizing the float32 result with ``ops.fq_codes``.
     ``w_zero_points`` (int32 [N], each in [-128, 127]): the weights are ``w_codes[n][k] - w_zero_points[n]``; the row sums
     of the activation codes are computed first (``codes_rowsum``) and the product runs on ``mctq_qlinear_i8_zp``."""
-    M, K = a_codes.shape
-    N = w_codes.shape[0]
-    if w_codes.shape[1] != K:
-        raise RuntimeError(f"shape mismatch: activations have K={K}, weights K={w_codes.shape[1]}")
     if a_codes.is_cuda:
-        if K % 16 or K > _MAX_K:
-            raise NotImplementedError(f"mctq_qlinear_i8 needs K % 16 == 0 and K <= {_MAX_K}, got K={K}")
-        _check_consumer_operands(a_codes, w_scales, w_rowsum, bias, w_zero_points)
-        lib = native.load()
-        a_codes, w_codes = a_codes.contiguous(), w_codes.contiguous()
-        code = native.CODE_U8 if a_codes.dtype == torch.uint8 else native.CODE_I8
-        bias_ptr = None if bias is None else bias.data_ptr()
-        if w_zero_points is not None:
-            a_rowsum = codes_rowsum(a_codes, a_zero_point)
-            tdt, ocode, o_scale, o_zp, o_qmin, o_qmax = _output_form(out_codes)
-            with ops._maybe_on_device(a_codes):
-                y = torch.empty((M, N), dtype=tdt, device=a_codes.device)
-                rc = ops._launch(lib.mctq_qlinear_i8_zp, a_codes.data_ptr(), code, int(a_zero_point), float(a_scale),
-                                 w_codes.data_ptr(), w_scales.data_ptr(), w_rowsum.data_ptr(), bias_ptr, y.data_ptr(),
-                                 ocode, float(o_scale), int(o_zp), int(o_qmin), int(o_qmax), w_zero_points.data_ptr(),
-                                 a_rowsum.data_ptr(), M, N, K, ops._stream(a_codes))
-            if rc:
-                native.check(rc, "mctq_qlinear_i8_zp")
-            return y
-        with ops._maybe_on_device(a_codes):
-            if out_codes is None:
-                y = torch.empty((M, N), dtype=torch.float32, device=a_codes.device)
-                rc = ops._launch(lib.mctq_qlinear_i8, a_codes.data_ptr(), code, int(a_zero_point), float(a_scale),
-                                 w_codes.data_ptr(), w_scales.data_ptr(), w_rowsum.data_ptr(), bias_ptr, y.data_ptr(),
-                                 M, N, K, ops._stream(a_codes))
-            else:
-                tdt, ocode, o_scale, o_zp, o_qmin, o_qmax = _output_form(out_codes)
-                y = torch.empty((M, N), dtype=tdt, device=a_codes.device)
-                rc = ops._launch(lib.mctq_qlinear_i8_codes, a_codes.data_ptr(), code, int(a_zero_point), float(a_scale),
-                                 w_codes.data_ptr(), w_scales.data_ptr(), w_rowsum.data_ptr(), bias_ptr, y.data_ptr(),
-                                 ocode, float(o_scale), int(o_zp), int(o_qmin), int(o_qmax), M, N, K,
-                                 ops._stream(a_codes))
-        if rc:
-            native.check(rc, "mctq_qlinear_i8")
-        return y
+        return _launch_consumer("mctq_qlinear_i8", a_codes, a_zero_point, a_scale, w_codes, (), w_scales, w_rowsum, bias,
+                                out_codes, w_zero_points)
+    if w_codes.shape[1] != a_codes.shape[1]:
+        raise _k_mismatch(a_codes.shape[1], w_codes.shape[1], "weights")
     ops._cpu_route_allowed()
     w32 = w_codes.to(torch.int32)
     if w_zero_points is not None:
@@ -169,39 +179,8 @@ def qlinear_w4a8(a_codes: torch.Tensor, a_zero_point: int, a_scale: float, w_cod
                  out_codes=None, w_zero_points: Optional[torch.Tensor] = None) -> torch.Tensor:
     """As ``qlinear_i8`` with the weights as packed 4-bit codes (``pack_w4``); GPU tensors only.  ``w_zero_points`` (int32
     [N], in the codes' domain [-8, 7]) as there, on ``mctq_qlinear_w4a8_zp``."""
-    M, K = a_codes.shape
-    N = w_codes4.shape[0]
-    if w_codes4.shape[1] * 2 != K:
-        raise RuntimeError(f"shape mismatch: activations have K={K}, packed weights K={w_codes4.shape[1] * 2}")
-    if K % 16 or K > _MAX_K:
-        raise NotImplementedError(f"mctq_qlinear_w4a8 needs K % 16 == 0 and K <= {_MAX_K}, got K={K}")
-    _check_consumer_operands(a_codes, w_scales, w_rowsum, bias, w_zero_points)
-    lib = native.load()
-    a_codes, w_codes4 = a_codes.contiguous(), w_codes4.contiguous()
-    code = native.CODE_U8 if a_codes.dtype == torch.uint8 else native.CODE_I8
-    if w_zero_points is not None:
-        a_rowsum = codes_rowsum(a_codes, a_zero_point)
-        tdt, ocode, o_scale, o_zp, o_qmin, o_qmax = _output_form(out_codes)
-        with ops._maybe_on_device(a_codes):
-            y = torch.empty((M, N), dtype=tdt, device=a_codes.device)
-            rc = ops._launch(lib.mctq_qlinear_w4a8_zp, a_codes.data_ptr(), code, int(a_zero_point), float(a_scale),
-                             w_codes4.data_ptr(), w_scales.data_ptr(), w_rowsum.data_ptr(),
-                             None if bias is None else bias.data_ptr(), y.data_ptr(), ocode, float(o_scale), int(o_zp),
-                             int(o_qmin), int(o_qmax), w_zero_points.data_ptr(), a_rowsum.data_ptr(), M, N, K,
-                             ops._stream(a_codes))
-        if rc:
-            native.check(rc, "mctq_qlinear_w4a8_zp")
-        return y
-    tdt, ocode, o_scale, o_zp, o_qmin, o_qmax = _output_form(out_codes)
-    y = torch.empty((M, N), dtype=tdt, device=a_codes.device)
-    with ops._maybe_on_device(a_codes):
-        rc = ops._launch(lib.mctq_qlinear_w4a8, a_codes.data_ptr(), code, int(a_zero_point), float(a_scale),
-                         w_codes4.data_ptr(), w_scales.data_ptr(), w_rowsum.data_ptr(),
-                         None if bias is None else bias.data_ptr(), y.data_ptr(), ocode, float(o_scale), int(o_zp),
-                         int(o_qmin), int(o_qmax), M, N, K, ops._stream(a_codes))
-    if rc:
-        native.check(rc, "mctq_qlinear_w4a8")
-    return y
+    return _launch_consumer("mctq_qlinear_w4a8", a_codes, a_zero_point, a_scale, w_codes4, (), w_scales, w_rowsum, bias,
+                            out_codes, w_zero_points)
 
 
 _W4_MAX_ROWS = 32          # measured: beyond this the int8 kernels are faster than streaming half the bytes
@@ -240,29 +219,10 @@ def qlinear_lut4a8(a_codes: torch.Tensor, a_zero_point: int, a_scale: float, w_i
     """As ``qlinear_i8`` with ``w_codes[n][k] = lut16[index[n][k]]``, the weights given as packed 4-bit codebook indices
     (``pack_lut4``) and ``lut16`` as at most 16 int8 codebook values on the host (a sequence, a CPU tensor or 16 bytes);
     ``w_rowsum`` is the row sum of the looked-up values.  GPU tensors only."""
-    M, K = a_codes.shape
-    N = w_idx4.shape[0]
-    if w_idx4.shape[1] * 2 != K:
-        raise RuntimeError(f"shape mismatch: activations have K={K}, packed weights K={w_idx4.shape[1] * 2}")
-    if K % 16 or K > _MAX_K:
-        raise NotImplementedError(f"mctq_qlinear_lut4a8 needs K % 16 == 0 and K <= {_MAX_K}, got K={K}")
     if w_idx4.dtype != torch.uint8 or w_idx4.device != a_codes.device:
         raise TypeError(f"w_idx4 must be a uint8 tensor on {a_codes.device}, got {w_idx4.dtype} on {w_idx4.device}")
-    _check_consumer_operands(a_codes, w_scales, w_rowsum, bias)
-    lut = _lut16_bytes(lut16)
-    lib = native.load()
-    a_codes, w_idx4 = a_codes.contiguous(), w_idx4.contiguous()
-    code = native.CODE_U8 if a_codes.dtype == torch.uint8 else native.CODE_I8
-    tdt, ocode, o_scale, o_zp, o_qmin, o_qmax = _output_form(out_codes)
-    y = torch.empty((M, N), dtype=tdt, device=a_codes.device)
-    with ops._maybe_on_device(a_codes):
-        rc = ops._launch(lib.mctq_qlinear_lut4a8, a_codes.data_ptr(), code, int(a_zero_point), float(a_scale),
-                         w_idx4.data_ptr(), lut, w_scales.data_ptr(), w_rowsum.data_ptr(),
-                         None if bias is None else bias.data_ptr(), y.data_ptr(), ocode, float(o_scale), int(o_zp),
-                         int(o_qmin), int(o_qmax), M, N, K, ops._stream(a_codes))
-    if rc:
-        native.check(rc, "mctq_qlinear_lut4a8")
-    return y
+    return _launch_consumer("mctq_qlinear_lut4a8", a_codes, a_zero_point, a_scale, w_idx4, (_lut16_bytes(lut16),), w_scales,
+                            w_rowsum, bias, out_codes, None)
 
 
 # measured (tools/lut_consumer_probe.py, table in profiles/EXPERIMENTS.md): the largest probed M at which the packed kernel beats
@@ -340,67 +300,64 @@ class QuantizedLinear(nn.Module):
         lin.bias = wrapper.layer.bias
         return cls(lin, quantizers["weight"], activation_quantizer)
 
+    def activation_code_params(self):
+        """(scale, zero_point, qmin, qmax) of this layer's activation codes: what ``emit_codes_for`` of the layer in front takes."""
+        return self._a_scale, self._a_zp, self._a_qmin, self._a_qmax
+
+    def _weight_codes(self, w):
+        """The weight kind's part: (int8 codes, scales, int32 zero points or None, (indices, int8 codebook) or None)."""
+        q = self.weights_quantizer
+        if self._lut_weights:
+            # q(w)[n][k] = (lut[idx] / 2^(B-1)) * thr[n] == float(lut_i8[idx]) * (thr[n] / 2^(B-1)) bit for bit (the divisor is
+            # a power of two, so either side rounds once): int8 codes lut_i8[idx] with scales thr / 2^(B-1).
+            idx, lut, thr = q.quantize_to_codes(w.detach())
+            bits = q.lut_values_bitwidth
+            lut = lut.detach().to(device="cpu", dtype=torch.float32).reshape(-1)
+            if bits > 8 or lut.numel() > 256 or not bool(((lut == lut.round()) & (lut >= -128) & (lut <= 127)).all()):
+                raise RuntimeError("the codebook no longer holds at most 256 int8 values")
+            lut_i8 = lut.to(torch.int8)
+            idx = idx.reshape(self.out_features, self.in_features)       # [O, C, 1, 1] of a pointwise convolution too
+            scales = thr.detach().to(device=w.device, dtype=torch.float32) / float(2 ** (bits - 1))
+            return lut_i8.to(w.device)[idx.long()], scales, None, (idx, lut_i8)
+        codes, scales, zps = q.quantize_to_codes(w.detach())
+        if not self._uniform_weights:
+            if codes.dtype != torch.int8:
+                raise RuntimeError("symmetric weight codes are expected to be int8")
+            return codes, scales, None, None
+        # unsigned codes c in 0 .. 2^bits - 1 with zero point z: both re-biased by half the domain, so that the codes are
+        # int8 (at most 4 bits: [-8, 7], the packed layout's nibbles) and c - z is unchanged
+        half = 2 ** (q.num_bits - 1)
+        if codes.dtype != torch.uint8:
+            raise RuntimeError("uniform weight codes are expected to be uint8")
+        zps = zps.to(device=w.device, dtype=torch.int32).reshape(-1) - half
+        if zps.numel() and (int(zps.min()) < -128 or int(zps.max()) > 127):     # (a host read, once per weight change)
+            raise NotImplementedError("a weight zero point lies outside the codes' domain")
+        return (codes.to(torch.int16) - half).to(torch.int8), scales, zps, None
+
     def _refresh_weight_codes(self):
         w = self.weight
         key = (w.data_ptr(), w._version, w.device)
         if key == self._w_key:
             return
-        if self._lut_weights:
-            self._refresh_lut_weight_codes(w)
-            self._w_key = key
-            return
-        codes, scales, zps = self.weights_quantizer.quantize_to_codes(w.detach())
-        if self._uniform_weights:
-            # unsigned codes c in 0 .. 2^bits - 1 with zero point z: both re-biased by half the domain, so that the codes are
-            # int8 (at most 4 bits: [-8, 7], the packed layout's nibbles) and c - z is unchanged
-            half = 2 ** (self.weights_quantizer.num_bits - 1)
-            if codes.dtype != torch.uint8:
-                raise RuntimeError("uniform weight codes are expected to be uint8")
-            codes = (codes.to(torch.int16) - half).to(torch.int8)
-            zps = zps.to(device=w.device, dtype=torch.int32).reshape(-1) - half
-            if zps.numel() and (int(zps.min()) < -128 or int(zps.max()) > 127):     # (a host read, once per weight change)
-                raise NotImplementedError("a weight zero point lies outside the codes' domain")
-            if zps.numel() == 1:
-                zps = zps.expand(self.out_features)
-            self._w_zps = zps.contiguous()
-        elif codes.dtype != torch.int8:
-            raise RuntimeError("symmetric weight codes are expected to be int8")
-        codes = codes.reshape(self.out_features, self.in_features)       # [O, C, 1, 1] of a pointwise convolution too
-        scales = scales.to(device=w.device, dtype=torch.float32).reshape(-1)
-        if scales.numel() == 1:
-            scales = scales.expand(self.out_features)
-        self._w_codes = codes.contiguous()
-        self._w_scales = scales.contiguous()
-        self._w_rowsum = codes.sum(dim=1, dtype=torch.int32).contiguous()
-        # weights of at most 4 bits: also keep them packed, to stream half the bytes when there are few rows
-        self._w_codes4 = pack_w4(self._w_codes) if (self.weights_quantizer.num_bits <= 4 and w.is_cuda
-                                                     and self.in_features % 16 == 0) else None
-        self._w_key = key
+        codes, scales, zps, packed = self._weight_codes(w)
 
-    def _refresh_lut_weight_codes(self, w):
-        """LUT weights: q(w)[n][k] = (lut[idx] / 2^(B-1)) * thr[n] == float(lut_i8[idx]) * (thr[n] / 2^(B-1)) bit for bit (the
-        divisor is a power of two, so either side rounds once): int8 codes lut_i8[idx] with scales thr / 2^(B-1)."""
-        q = self.weights_quantizer
-        idx, lut, thr = q.quantize_to_codes(w.detach())
-        bits = q.lut_values_bitwidth
-        lut = lut.detach().to(device="cpu", dtype=torch.float32).reshape(-1)
-        if bits > 8 or lut.numel() > 256 or not bool(((lut == lut.round()) & (lut >= -128) & (lut <= 127)).all()):
-            raise RuntimeError("the codebook no longer holds at most 256 int8 values")
-        lut_i8 = lut.to(torch.int8)
-        idx = idx.reshape(self.out_features, self.in_features)           # [O, C, 1, 1] of a pointwise convolution too
-        codes = lut_i8.to(w.device)[idx.long()]
-        scales = thr.detach().to(device=w.device, dtype=torch.float32).reshape(-1) / float(2 ** (bits - 1))
-        if scales.numel() == 1:
-            scales = scales.expand(self.out_features)
+        def per_channel(t):
+            return (t.expand(self.out_features) if t.numel() == 1 else t).contiguous()
+
+        codes = codes.reshape(self.out_features, self.in_features)       # [O, C, 1, 1] of a pointwise convolution too
         self._w_codes = codes.contiguous()
-        self._w_scales = scales.contiguous()
+        self._w_scales = per_channel(scales.to(device=w.device, dtype=torch.float32).reshape(-1))
         self._w_rowsum = codes.sum(dim=1, dtype=torch.int32).contiguous()
-        self._w_codes4 = None
-        # a codebook of at most 16 entries is 4 bits per weight: also keep the indices packed, for few rows
-        if lut.numel() <= 16 and w.is_cuda and self.in_features % 16 == 0:
-            self._w_idx4, self._lut16 = pack_lut4(idx), _lut16_bytes(lut_i8)
-        else:
-            self._w_idx4 = self._lut16 = None
+        if zps is not None:
+            self._w_zps = per_channel(zps)
+        # at most 4 bits per weight -- codes, or the indices of a codebook of at most 16 entries: also keep them packed, to
+        # stream half the bytes when there are few rows
+        can_pack = w.is_cuda and self.in_features % 16 == 0
+        self._w_codes4 = pack_w4(self._w_codes) if packed is None and self.weights_quantizer.num_bits <= 4 and can_pack else None
+        self._w_idx4 = self._lut16 = None
+        if packed is not None and packed[1].numel() <= 16 and can_pack:
+            self._w_idx4, self._lut16 = pack_lut4(packed[0]), _lut16_bytes(packed[1])
+        self._w_key = key
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         self._refresh_weight_codes()
@@ -540,7 +497,7 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
             for i in range(len(seq) - 2):
                 first, gap, second = seq[i], seq[i + 1], seq[i + 2]
                 if isinstance(first, QuantizedLinear) and isinstance(gap, _FusedAway) and isinstance(second, QuantizedLinear):
-                    first.emit_codes_for = (second._a_scale, second._a_zp, second._a_qmin, second._a_qmax)
+                    first.emit_codes_for = second.activation_code_params()
     return replaced
 
 
@@ -590,7 +547,7 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
                 user = next(iter(node.users))
                 nxt = mods.get(user.target) if user.op == "call_module" else None
                 if isinstance(nxt, QuantizedLinear) and user.args == (node,):
-                    mods[node.target].emit_codes_for = (nxt._a_scale, nxt._a_zp, nxt._a_qmin, nxt._a_qmax)
+                    mods[node.target].emit_codes_for = nxt.activation_code_params()
     gm.graph.lint()
     gm.recompile()
     return gm, replaced

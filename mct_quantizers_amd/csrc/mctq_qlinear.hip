@@ -441,36 +441,52 @@ __global__ __launch_bounds__(kQlWaves * 64) void qlinear_i8_lds_kernel(
   }
 }
 
+// One checked consumer call, as every launcher receives it (host side; the kernels keep their scalar arguments).
+// za is the zero point in the domain the kernels multiply in (uint8 codes are re-biased by 128), zp is {nullptr, nullptr}
+// unless the call brings weight zero points; the whole-tile kernels (launch_wide, launch_pp) do not read it.
+struct QlCall {
+  const void* a;
+  const int8_t* w;          // int8 codes, or the packed 4-bit codes / indices of launch_qlinear<..., kQlW4 / kQlLut4>
+  const float* w_scales;
+  const int32_t* w_rowsum;
+  const float* bias;
+  void* y;
+  int64_t M, N, K;
+  int za;
+  float sa;
+  QlOut oq;
+  QlZp zp;
+  hipStream_t stream;
+};
+// the kernels' leading arguments, common to all of them
+#define MCTQ_QL_ARGS(c) (const int8_t*)(c).a, (c).w, (c).w_scales, (c).w_rowsum, (c).bias, (c).y, (int)(c).M, (int)(c).N, (c).K, (c).za, (c).sa
+
 template <int WAVES, int MT, bool A_U8>
-static int launch_qlinear_lds(const void* a, const int8_t* w, const float* w_scales, const int32_t* w_rowsum,
-                              const float* bias, void* y, int64_t M, int64_t N, int64_t K, int za, float sa,
-                              const QlOut& oq, const QlZp& zp, hipStream_t stream) {
-  const dim3 grid((unsigned)((N + 15) / 16));
-  const bool one_pass = M <= 16 * MT;
+static int launch_qlinear_lds(const QlCall& c) {
+  const dim3 grid((unsigned)((c.N + 15) / 16));
+  const bool one_pass = c.M <= 16 * MT;
 #define MCTQ_QL_LDS(NT_, ZP_) \
-  hipLaunchKernelGGL((qlinear_i8_lds_kernel<WAVES, MT, A_U8, NT_, ZP_>), grid, dim3(WAVES * 64), 0, stream, \
-                     (const int8_t*)a, w, w_scales, w_rowsum, bias, y, (int)M, (int)N, K, za, sa, oq, zp)
-  if (zp.a_rowsum) { if (one_pass) MCTQ_QL_LDS(true, true); else MCTQ_QL_LDS(false, true); }
+  hipLaunchKernelGGL((qlinear_i8_lds_kernel<WAVES, MT, A_U8, NT_, ZP_>), grid, dim3(WAVES * 64), 0, c.stream, \
+                     MCTQ_QL_ARGS(c), c.oq, c.zp)
+  if (c.zp.a_rowsum) { if (one_pass) MCTQ_QL_LDS(true, true); else MCTQ_QL_LDS(false, true); }
   else { if (one_pass) MCTQ_QL_LDS(true, false); else MCTQ_QL_LDS(false, false); }
 #undef MCTQ_QL_LDS
-  note_ql<A_U8>(WAVES == 8 ? "qlinear_stream_lds_8waves" : "qlinear_stream_lds_4waves", MT, zp.a_rowsum != nullptr);
+  note_ql<A_U8>(WAVES == 8 ? "qlinear_stream_lds_8waves" : "qlinear_stream_lds_4waves", MT, c.zp.a_rowsum != nullptr);
   return check_launch("mctq_qlinear_i8 (LDS-staged activations)");
 }
 
 template <int WAVES, int MT, bool A_U8, int WFMT = kQlW8, class... Lut>
-static int launch_qlinear(const void* a, const int8_t* w, const float* w_scales, const int32_t* w_rowsum,
-                          const float* bias, void* y, int64_t M, int64_t N, int64_t K, int za, float sa,
-                          const QlOut& oq, const QlZp& zp, hipStream_t stream, Lut... lut) {
-  const dim3 grid((unsigned)((N + 15) / 16));
-  const bool one_pass = M <= 16 * MT;             // weights read exactly once: keep them out of the caches
+static int launch_qlinear(const QlCall& c, Lut... lut) {
+  const dim3 grid((unsigned)((c.N + 15) / 16));
+  const bool one_pass = c.M <= 16 * MT;           // weights read exactly once: keep them out of the caches
   if (one_pass)
-    hipLaunchKernelGGL((qlinear_i8_kernel<WAVES, MT, A_U8, true, WFMT, Lut...>), grid, dim3(WAVES * 64), 0, stream,
-                       (const int8_t*)a, w, w_scales, w_rowsum, bias, y, (int)M, (int)N, K, za, sa, oq, zp, lut...);
+    hipLaunchKernelGGL((qlinear_i8_kernel<WAVES, MT, A_U8, true, WFMT, Lut...>), grid, dim3(WAVES * 64), 0, c.stream,
+                       MCTQ_QL_ARGS(c), c.oq, c.zp, lut...);
   else
-    hipLaunchKernelGGL((qlinear_i8_kernel<WAVES, MT, A_U8, false, WFMT, Lut...>), grid, dim3(WAVES * 64), 0, stream,
-                       (const int8_t*)a, w, w_scales, w_rowsum, bias, y, (int)M, (int)N, K, za, sa, oq, zp, lut...);
+    hipLaunchKernelGGL((qlinear_i8_kernel<WAVES, MT, A_U8, false, WFMT, Lut...>), grid, dim3(WAVES * 64), 0, c.stream,
+                       MCTQ_QL_ARGS(c), c.oq, c.zp, lut...);
   note_ql<A_U8>(WFMT == kQlLut4 ? "qlinear_stream_lut4" : WFMT == kQlW4 ? "qlinear_stream_w4" : WAVES == 8 ? "qlinear_stream_8waves" : "qlinear_stream_4waves", MT,
-                zp.a_rowsum != nullptr);
+                c.zp.a_rowsum != nullptr);
   return check_launch("mctq_qlinear_i8");
 }
 
@@ -706,10 +722,8 @@ __global__ __launch_bounds__(256 * KG) void qgemm_i8_glds_kernel(
 }
 
 template <int BM, int BN, int BK, bool A_U8, int ST = 2, int KG = 1>
-static int launch_glds(const void* a, const int8_t* w, const float* w_scales, const int32_t* w_rowsum,
-                       const float* bias, void* y, int64_t M, int64_t N, int64_t K, int za, float sa,
-                       const QlOut& oq, const QlZp& zp, hipStream_t stream) {
-  const int mbl = (int)((M + BM - 1) / BM), nbl = (int)((N + BN - 1) / BN);
+static int launch_glds(const QlCall& c) {
+  const int mbl = (int)((c.M + BM - 1) / BM), nbl = (int)((c.N + BN - 1) / BN);
   // tile rows per band: an XCD's chunk of total / 8 consecutive tiles as a gm x (chunk / gm) rectangle with the least
   // gm * BM + (chunk / gm) * BN, i.e. gm ~ sqrt(chunk * BN / BM)   (tuning key "ql_band" overrides)
   int gm = g_ql_band;
@@ -720,15 +734,15 @@ static int launch_glds(const void* a, const int8_t* w, const float* w_scales, co
   gm = gm < 1 ? 1 : gm > mbl ? mbl : gm;
   const int flags = (g_ql_rot && gm > 1 ? 1 : 0) | (g_ql_stagger ? 2 : 0);
 #define MCTQ_QL_GLDS(ZP_) \
-  hipLaunchKernelGGL((qgemm_i8_glds_kernel<BM, BN, BK, A_U8, ST, KG, ZP_>), dim3((unsigned)(mbl * nbl)), dim3(256 * KG), 0, stream, \
-                     (const int8_t*)a, w, w_scales, w_rowsum, bias, y, (int)M, (int)N, K, za, sa, mbl, nbl, gm, flags, oq, zp)
-  if (zp.a_rowsum) MCTQ_QL_GLDS(true); else MCTQ_QL_GLDS(false);
+  hipLaunchKernelGGL((qgemm_i8_glds_kernel<BM, BN, BK, A_U8, ST, KG, ZP_>), dim3((unsigned)(mbl * nbl)), dim3(256 * KG), 0, c.stream, \
+                     MCTQ_QL_ARGS(c), mbl, nbl, gm, flags, c.oq, c.zp)
+  if (c.zp.a_rowsum) MCTQ_QL_GLDS(true); else MCTQ_QL_GLDS(false);
 #undef MCTQ_QL_GLDS
   static char name[48];                              // "qlinear_tiled[_ring]_<BM>x<BN>x<BK>", formatted once per instantiation
   static const bool named = (snprintf(name, sizeof(name), "qlinear_tiled%s%s_%dx%dx%d", ST > 2 || (BM == 128 && BN == 64) ? "_ring" : "",
                                       KG == 2 ? "_8waves" : KG == 4 ? "_16waves" : "", BM, BN, BK), true);
   (void)named;
-  note_ql<A_U8>(name, gm, zp.a_rowsum != nullptr);
+  note_ql<A_U8>(name, gm, c.zp.a_rowsum != nullptr);
   return check_launch("mctq_qlinear_i8 (tiled, direct-to-LDS)");
 }
 
@@ -1089,31 +1103,28 @@ __global__ __launch_bounds__(512, 1) void qgemm_i8_pp_kernel(
 }
 
 template <bool A_U8>
-static int launch_pp(const void* a, const int8_t* w, const float* w_scales, const int32_t* w_rowsum,
-                     const float* bias, void* y, int64_t M, int64_t N, int64_t K, int za, float sa,
-                     const QlOut& oq, hipStream_t stream) {
-  if (M % 256 != 0 || N % 256 != 0 || K % 64 != 0 || K < 256) return fail_arg("ping-pong tiled kernel needs whole 256 x 256 tiles, K % 64 == 0 and K >= 256");
-  const int mbl = (int)(M / 256), nbl = (int)(N / 256);
-  hipLaunchKernelGGL((qgemm_i8_pp_kernel<A_U8>), dim3((unsigned)(mbl * nbl)), dim3(512), 0, stream,
-                     (const int8_t*)a, w, w_scales, w_rowsum, bias, y, (int)M, (int)N, K, za, sa, mbl, nbl, oq);
+static int launch_pp(const QlCall& c) {
+  if (c.M % 256 != 0 || c.N % 256 != 0 || c.K % 64 != 0 || c.K < 256) return fail_arg("ping-pong tiled kernel needs whole 256 x 256 tiles, K % 64 == 0 and K >= 256");
+  const int mbl = (int)(c.M / 256), nbl = (int)(c.N / 256);
+  hipLaunchKernelGGL((qgemm_i8_pp_kernel<A_U8>), dim3((unsigned)(mbl * nbl)), dim3(512), 0, c.stream,
+                     MCTQ_QL_ARGS(c), mbl, nbl, c.oq);
   note_ql<A_U8>("qlinear_pingpong_256x256");
   return check_launch("mctq_qlinear_i8 (ping-pong tiles)");
 }
 
 template <int TM, int TN, bool A_U8, int S = 4, int OCC = 1>
-static int launch_wide(const void* a, const int8_t* w, const float* w_scales, const int32_t* w_rowsum,
-                       const float* bias, void* y, int64_t M, int64_t N, int64_t K, int za, float sa,
-                       const QlOut& oq, hipStream_t stream) {
+static int launch_wide(const QlCall& c) {
   constexpr int BM = 32 * TM, BN = 32 * TN;
-  if (M % BM != 0 || N % BN != 0 || K % 128 != 0 || K < 256) return fail_arg("wide tiled kernel needs whole tiles, K % 128 == 0 and K >= 256");
-  const int mbl = (int)(M / BM), nbl = (int)(N / BN);
-  hipLaunchKernelGGL((qgemm_i8_wide_kernel<TM, TN, A_U8, S, OCC>), dim3((unsigned)(mbl * nbl)), dim3(256), 0, stream,
-                     (const int8_t*)a, w, w_scales, w_rowsum, bias, y, (int)M, (int)N, K, za, sa, mbl, nbl, oq);
+  if (c.M % BM != 0 || c.N % BN != 0 || c.K % 128 != 0 || c.K < 256) return fail_arg("wide tiled kernel needs whole tiles, K % 128 == 0 and K >= 256");
+  const int mbl = (int)(c.M / BM), nbl = (int)(c.N / BN);
+  hipLaunchKernelGGL((qgemm_i8_wide_kernel<TM, TN, A_U8, S, OCC>), dim3((unsigned)(mbl * nbl)), dim3(256), 0, c.stream,
+                     MCTQ_QL_ARGS(c), mbl, nbl, c.oq);
   static const char* const kName = TM == 8 && TN == 8 ? "qlinear_wide_256x256" : TM == 4 && TN == 8 ? "qlinear_wide_128x256"
       : TM == 8 ? "qlinear_wide_256x128" : "qlinear_wide_128x128";
   note_ql<A_U8>(kName, S);
   return check_launch("mctq_qlinear_i8 (wide tiles)");
 }
+#undef MCTQ_QL_ARGS
 
 // ------------------------------------------------------------------------------------------------
 // Row sums of activation codes, a_rowsum[m] = sum_k (a[m][k] - za): the per-row factor of the weight zero point term
@@ -1172,139 +1183,144 @@ constexpr int64_t kRowsumBlockRows = MCTQ_ROWSUM_BLOCK_ROWS;
 
 using namespace mctq;
 
-static int qlinear_dispatch(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
-                            const int8_t* w_codes, const float* w_scales, const int32_t* w_rowsum, const float* bias,
-                            void* y, const QlOut& oq, const QlZp& zp, bool with_zp, int64_t M, int64_t N, int64_t K,
-                            void* stream) {
-  if (M < 0 || N < 0 || K < 0) return fail_arg("negative extent");
-  if (a_code_dtype != MCTQ_CODE_I8 && a_code_dtype != MCTQ_CODE_U8) return fail_arg("bad a_code_dtype");
-  if (M == 0 || N == 0) return 0;
-  if (!a_codes || !w_codes || !w_scales || !w_rowsum || !y) return fail_arg("NULL pointer");
-  if (with_zp && (!zp.w_zero_points || !zp.a_rowsum)) return fail_arg("w_zero_points and a_rowsum are both required");
-  if (K % 16 != 0) return fail_arg("K must be a multiple of 16");
-  if ((((uintptr_t)a_codes | (uintptr_t)w_codes) & 15u) != 0) return fail_arg("code matrices must be 16-byte aligned");
-  if (K > (1 << 15)) return fail_arg("K > 32768 could overflow the int32 accumulator");
-  if (M > INT32_MAX / 2 || N > INT32_MAX / 2) return fail_arg("M or N too large");
-  const bool u8 = a_code_dtype == MCTQ_CODE_U8;
-  const int za = u8 ? a_zero_point - 128 : a_zero_point;
-  const hipStream_t s = (hipStream_t)stream;
-#define MCTQ_QLL(W_, MT_)                                                                                          \
-  (u8 ? launch_qlinear_lds<W_, MT_, true>(a_codes, w_codes, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, zp, s) \
-      : launch_qlinear_lds<W_, MT_, false>(a_codes, w_codes, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, zp, s))
-#define MCTQ_QG(BM_, BN_, BK_)                                                                                    \
-  (u8 ? launch_glds<BM_, BN_, BK_, true>(a_codes, w_codes, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, zp, s)  \
-      : launch_glds<BM_, BN_, BK_, false>(a_codes, w_codes, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, zp, s))
-#define MCTQ_QW(TM_, TN_)                                                                                         \
-  (u8 ? launch_wide<TM_, TN_, true>(a_codes, w_codes, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, s)      \
-      : launch_wide<TM_, TN_, false>(a_codes, w_codes, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, s))
-#define MCTQ_QG16(BM_, BN_, BK_, ST_)                                                                                      \
-  (u8 ? launch_glds<BM_, BN_, BK_, true, ST_, 4>(a_codes, w_codes, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, zp, s)  \
-      : launch_glds<BM_, BN_, BK_, false, ST_, 4>(a_codes, w_codes, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, zp, s))
-#define MCTQ_QG8(BM_, BN_, BK_, ST_)                                                                                       \
-  (u8 ? launch_glds<BM_, BN_, BK_, true, ST_, 2>(a_codes, w_codes, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, zp, s)  \
-      : launch_glds<BM_, BN_, BK_, false, ST_, 2>(a_codes, w_codes, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, zp, s))
-#define MCTQ_QPP()                                                                                                    \
-  (u8 ? launch_pp<true>(a_codes, w_codes, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, s)                      \
-      : launch_pp<false>(a_codes, w_codes, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, s))
+// ------------------------------------------------------------------------------------------------
+// The kernels of mctq_qlinear_i8 / _codes / _zp: one row per variant, and a variant is declared nowhere else.
+// The rows stand in the order in which the kernels stand in the code object (the compiler instantiates and emits them as
+// the rows name their launchers, uint8 activations first): moving a row moves its kernels.  The order in which the
+// automatic choice considers them is the column `turn`; a tie goes to the earlier turn (smaller tiles first).
+// ------------------------------------------------------------------------------------------------
+typedef int (*QlLaunch)(const QlCall&);
+enum QlModel {
+  kQlStreaming,           // a block = 16 columns x all rows, bm rows per pass: candidate of the cost model for m_lo <= M <= m_hi
+  kQlTiles,               // a block = one bm x bn tile: candidate of the cost model
+  kQlByFill               // whole-tile kernel weighed in front of the cost model, by how full its last round of blocks is
+};
+enum { kQlWholeTiles = 1,      // only M % bm == N % bn == K % 128 == 0 and K >= 256
+       kQlNoZeroPoints = 2 };  // not built for calls that bring weight zero points
+struct QlKernel {
+  int variant;            // tuning key "ql_variant"
+  QlLaunch launch[2];     // uint8 / int8 activation codes
+  QlModel model;
+  int turn;               // place in the order the automatic choice considers the variants in: the earlier turn wins a tie
+  int bm, bn, occ;        // block tile, resident blocks per CU
+  double rate[3];         // fitted: KiB/us a CU takes in with 1 / 2 / 3 resident blocks; kQlByFill: POP/s of full rounds
+  unsigned rules;         // admission: 0 = any shape, any call
+  int m_lo, m_hi;         // kQlStreaming: the row counts it is a candidate for
+};
+// Few rows: the weight-streaming kernels (activation codes staged through per-wave LDS: full-line copies instead of
+// fragment-shaped L2 reads; profiles/r02/qlinear_probe.log) are candidates of the cost model.
+// Between the two regimes every kernel runs at the CU's intake of direct-to-LDS copies, an issue rate: about 36 KiB/us
+// with one resident block per CU, 48-58 with two, 64 with three (profiles/r03/qlinear_tile_sweep.log,
+// qlinear_small_tiles.log, EXPERIMENTS.md).  So the time of a launch is (operand bytes of a block) x (blocks the busiest
+// CU takes) / rate, and the choice is the kernel that makes that least: the weight-streaming kernel (a block = 16
+// columns x all rows, 64 rows per pass), 32 x 32 ... 128 x 128 tiles with two or three LDS buffers and four or eight
+// waves (eight / sixteen: two / four wave groups that all copy and each multiply a share of a K tile -- more waves
+// issuing copies raise the rate by 10-30 %), and the asm-pinned 128 x 128 kernel where the problem is whole tiles.  Earlier candidates win ties (smaller tiles first).
+// Many rows and columns, whole tiles: the 256 x 256 ping-pong kernel (2.2-2.3 POP/s against 1.5 for the 128 x 128
+// tiles; profiles/r02/qgemm_wide_probe.log) or, when there are too few such tiles for the chip, 128 x 256 wave-wide
+// tiles -- weighed by how full their last round of blocks is (one block per CU; the 128 x 128 kernel fits two).
+// (Zero-point weights: those two kernels and the pinned 128 x 128 candidate do not take them; the tiled kernels do.)
+static const QlKernel kQlKernels[] = {
+    // variant, {launcher for uint8, for int8 codes}, model, turn, bm, bn, occ, {rates}[, rules[, m_lo, m_hi]]
+    // weight streaming, activation codes through per-wave LDS: 16 / 32 / 64 rows per pass.  A block = 16 weight rows + 16 MT
+    // activation rows per pass; MT = 1 fits two blocks per CU.  Rates fitted on profiles/r03/qlinear_small_m.log (16 / 32 rows)
+    // and qlinear_small_tiles.log (64 ... 128 rows).
+    {181, {launch_qlinear_lds<8, 1, true>, launch_qlinear_lds<8, 1, false>}, kQlStreaming, 0, 16, 16, 2, {29.0, 36.5}, 0, 1, 16},
+    {182, {launch_qlinear_lds<8, 2, true>, launch_qlinear_lds<8, 2, false>}, kQlStreaming, 1, 32, 16, 1, {38.0}, 0, 17, 32},
+    {184, {launch_qlinear_lds<8, 4, true>, launch_qlinear_lds<8, 4, false>}, kQlStreaming, 2, 64, 16, 1, {47.0}, 0, 33, 128},
+    // 8-wave blocks (two wave groups), ring of three LDS buffers: rates fitted on profiles/r03/qlinear_8waves.log
+    {83233, {launch_glds<32, 32, 256, true, 3, 2>, launch_glds<32, 32, 256, false, 3, 2>}, kQlTiles, 3, 32, 32, 3, {42, 63, 65}},
+    {86433, {launch_glds<64, 32, 256, true, 3, 2>, launch_glds<64, 32, 256, false, 3, 2>}, kQlTiles, 4, 64, 32, 2, {50, 61}},
+    {86633, {launch_glds<64, 64, 128, true, 3, 2>, launch_glds<64, 64, 128, false, 3, 2>}, kQlTiles, 7, 64, 64, 3, {36, 56, 59}},   // 128-byte K steps, three blocks per CU
+    {812613, {launch_glds<128, 64, 128, true, 3, 2>, launch_glds<128, 64, 128, false, 3, 2>}, kQlTiles, 8, 128, 64, 2, {44, 54}},
+    // 16-wave blocks (four wave groups; qlinear_16waves.log): one block per CU
+    {166623, {launch_glds<64, 64, 256, true, 3, 4>, launch_glds<64, 64, 256, false, 3, 4>}, kQlTiles, 5, 64, 64, 1, {48}},
+    {1612623, {launch_glds<128, 64, 256, true, 3, 4>, launch_glds<128, 64, 256, false, 3, 4>}, kQlTiles, 9, 128, 64, 1, {48}},   // 256-byte K steps
+    // 4-wave blocks, two LDS buffers
+    {612, {launch_glds<64, 128, 128, true>, launch_glds<64, 128, 128, false>}, kQlTiles, 10, 64, 128, 3, {36, 50, 64}},
+    {1212, {launch_glds<128, 128, 128, true>, launch_glds<128, 128, 128, false>}, kQlTiles, 11, 128, 128, 2, {30, 48}},
+    {662, {launch_glds<64, 64, 256, true>, launch_glds<64, 64, 256, false>}, kQlTiles, 6, 64, 64, 2, {36, 54}},   // two blocks per CU
+    // wave-wide 128 x 128 / 128 x 256 tiles
+    {2544, {launch_wide<4, 4, true>, launch_wide<4, 4, false>}, kQlTiles, 12, 128, 128, 2, {38, 43}, kQlWholeTiles | kQlNoZeroPoints},
+    {2548, {launch_wide<4, 8, true>, launch_wide<4, 8, false>}, kQlByFill, 14, 128, 256, 1, {2.0}, kQlWholeTiles | kQlNoZeroPoints},
+    // 256 x 256 ping-pong tiles
+    {2560, {launch_pp<true>, launch_pp<false>}, kQlByFill, 13, 256, 256, 1, {2.25}, kQlWholeTiles | kQlNoZeroPoints},
+};
+
+static bool ql_admits(const QlKernel& k, int64_t M, int64_t N, int64_t K, bool with_zp) {
+  if (with_zp && (k.rules & kQlNoZeroPoints)) return false;
+  if ((k.rules & kQlWholeTiles) && (M % k.bm != 0 || N % k.bn != 0 || K % 128 != 0 || K < 256)) return false;
+  return k.model != kQlStreaming || (M >= k.m_lo && M <= k.m_hi);
+}
+
+// The automatic choice for a checked call (M, N >= 1) on a chip of `cus` compute units.  The loops over the table are
+// unrolled: a row's model, tile and occupancy then fold into constants, and the divisions by them cost what they cost when
+// every candidate was spelled out (a third of the time of the rolled loops, measured on the host alone).
+static const QlKernel* ql_choose(int64_t M, int64_t N, int64_t K, bool with_zp, int64_t cus) {
+  const auto blocks = [&](int64_t bm, int64_t bn) { return ((M + bm - 1) / bm) * ((N + bn - 1) / bn); };
+  // Only where the 128 x 128 kernel would fill the chip: smaller problems keep its finer tiles.
+  if (blocks(128, 128) >= 2 * cus) {
+    const auto fill = [&](int64_t nb, int64_t slots) { return (double)nb / (double)(((nb + slots - 1) / slots) * slots); };
+    double best = 1.5 * fill(blocks(128, 128), 2 * cus);        // the 128 x 128 tiles these kernels have to beat
+    const QlKernel* pick = nullptr;
+#pragma unroll
+    for (const QlKernel& k : kQlKernels) {
+      if (k.model != kQlByFill || !ql_admits(k, M, N, K, with_zp)) continue;
+      const double rate = k.rate[0] * fill(blocks(k.bm, k.bn), cus);
+      if (rate > best || (pick && rate == best && k.turn < pick->turn)) { best = rate; pick = &k; }
+    }
+    if (pick) return pick;
+  }
+  double best = 0.0;
+  const QlKernel* pick = nullptr;
+#pragma unroll
+  for (const QlKernel& k : kQlKernels) {
+    if (k.model == kQlByFill || !ql_admits(k, M, N, K, with_zp)) continue;
+    // us, up to a common constant: a streaming block takes all row passes of its 16 columns
+    const int64_t passes = (M + k.bm - 1) / k.bm, across = (N + k.bn - 1) / k.bn;
+    const bool stream = k.model == kQlStreaming;
+    const double kib = (double)((stream ? passes : 1) * (k.bm + k.bn)) * (double)K / 1024.0;
+    const int64_t per_cu = ((stream ? across : passes * across) + cus - 1) / cus, full = per_cu / k.occ, rem = per_cu % k.occ;
+    const double cost = (double)(full * k.occ) * kib / k.rate[k.occ - 1] + (rem ? (double)rem * kib / k.rate[rem - 1] : 0.0);
+    if (!pick || cost < best || (cost == best && k.turn < pick->turn)) { best = cost; pick = &k; }
+  }
+  return pick;
+}
+
+// What every consumer entry point checks, in one place; on success c.za becomes the zero point in the kernels' domain.
+// false: the entry point returns rc -- an argument error, or 0 for an empty problem (decided before any pointer is looked at).
+static bool ql_check_call(QlCall& c, int32_t a_code_dtype, bool with_zp, bool packed, int& rc) {
+  rc = 0;
+  if (c.M < 0 || c.N < 0 || c.K < 0) rc = fail_arg("negative extent");
+  else if (a_code_dtype != MCTQ_CODE_I8 && a_code_dtype != MCTQ_CODE_U8) rc = fail_arg("bad a_code_dtype");
+  else if (c.M == 0 || c.N == 0) return false;
+  else if (!c.a || !c.w || !c.w_scales || !c.w_rowsum || !c.y) rc = fail_arg("NULL pointer");
+  else if (with_zp && (!c.zp.w_zero_points || !c.zp.a_rowsum)) rc = fail_arg("w_zero_points and a_rowsum are both required");
+  else if (c.K % 16 != 0) rc = fail_arg("K must be a multiple of 16");
+  else if (!packed && (((uintptr_t)c.a | (uintptr_t)c.w) & 15u) != 0) rc = fail_arg("code matrices must be 16-byte aligned");
+  else if (packed && ((((uintptr_t)c.a) & 15u) != 0 || (((uintptr_t)c.w) & 7u) != 0))
+    rc = fail_arg("a_codes must be 16-byte and the packed weights (w_codes4 / w_idx4) 8-byte aligned");
+  else if (c.K > (1 << 15)) rc = fail_arg("K > 32768 could overflow the int32 accumulator");
+  else if (c.M > INT32_MAX / 2 || c.N > INT32_MAX / 2) rc = fail_arg("M or N too large");
+  if (rc) return false;
+  if (a_code_dtype == MCTQ_CODE_U8) c.za -= 128;
+  return true;
+}
+
+static int qlinear_dispatch(QlCall c, int32_t a_code_dtype, bool with_zp) {
+  int rc;
+  if (!ql_check_call(c, a_code_dtype, with_zp, false, rc)) return rc;
+  const int which = a_code_dtype == MCTQ_CODE_U8 ? 0 : 1;
   // tuning key "ql_variant": force ONE of the kernels the automatic choice below can select (tests run each of them over
   // ragged shapes against the integer oracle); the experiment variants of round 3 are not built any more
-  if (with_zp && (g_ql_variant == 2544 || g_ql_variant == 2548 || g_ql_variant == 2560))
-    return fail_arg("the register-pinned whole-tile kernels (ql_variant 2544 / 2548 / 2560) are not built for zero-point weights");
-  switch (g_ql_variant) {
-    case 181: return MCTQ_QLL(8, 1);                  // weight streaming, activation codes through per-wave LDS: 16 / 32 / 64 rows per pass
-    case 182: return MCTQ_QLL(8, 2);
-    case 184: return MCTQ_QLL(8, 4);
-    case 83233: return MCTQ_QG8(32, 32, 256, 3);      // 8-wave blocks (two wave groups), ring of three LDS buffers
-    case 86433: return MCTQ_QG8(64, 32, 256, 3);
-    case 86633: return MCTQ_QG8(64, 64, 128, 3);
-    case 812613: return MCTQ_QG8(128, 64, 128, 3);
-    case 166623: return MCTQ_QG16(64, 64, 256, 3);    // 16-wave blocks (four wave groups)
-    case 1612623: return MCTQ_QG16(128, 64, 256, 3);
-    case 612: return MCTQ_QG(64, 128, 128);           // 4-wave blocks, two LDS buffers
-    case 1212: return MCTQ_QG(128, 128, 128);
-    case 662: return MCTQ_QG(64, 64, 256);
-    case 2544: return MCTQ_QW(4, 4);                  // wave-wide 128 x 128 / 128 x 256 tiles
-    case 2548: return MCTQ_QW(4, 8);
-    case 2560: return MCTQ_QPP();                     // 256 x 256 ping-pong tiles
-    default: break;
-  }
-  const int64_t cus = cu_count();
-  const auto blocks = [&](int64_t bm, int64_t bn) { return ((M + bm - 1) / bm) * ((N + bn - 1) / bn); };
-  // Few rows: the weight-streaming kernels (activation codes staged through per-wave LDS: full-line copies instead of
-  // fragment-shaped L2 reads; profiles/r02/qlinear_probe.log) are candidates of the cost model below.
-  // Many rows and columns, whole tiles: the 256 x 256 ping-pong kernel (2.2-2.3 POP/s against 1.5 for the 128 x 128
-  // tiles; profiles/r02/qgemm_wide_probe.log) or, when there are too few such tiles for the chip, 128 x 256 wave-wide
-  // tiles -- weighed by how full their last round of blocks is (one block per CU; the 128 x 128 kernel fits two).
-  // Only where the 128 x 128 kernel would fill the chip: smaller problems keep its finer tiles.
-  // (Zero-point weights: those two kernels and the pinned 128 x 128 candidate below do not take them; the tiled kernels do.)
-  if (!with_zp && K % 128 == 0 && K >= 256 && N % 256 == 0 && M % 128 == 0 && blocks(128, 128) >= 2 * cus) {
-    const auto fill = [&](int64_t nb, int64_t slots) { return (double)nb / (double)(((nb + slots - 1) / slots) * slots); };
-    const double old_rate = 1.5 * fill(blocks(128, 128), 2 * cus);
-    const double pp_rate = M % 256 == 0 ? 2.25 * fill(blocks(256, 256), cus) : 0.0;
-    const double w48_rate = 2.0 * fill(blocks(128, 256), cus);
-    if (pp_rate >= w48_rate && pp_rate > old_rate) return MCTQ_QPP();
-    if (w48_rate > old_rate) return MCTQ_QW(4, 8);
-  }
-  // Between the two regimes every kernel runs at the CU's intake of direct-to-LDS copies, an issue rate: about 36 KiB/us
-  // with one resident block per CU, 48-58 with two, 64 with three (profiles/r03/qlinear_tile_sweep.log,
-  // qlinear_small_tiles.log, EXPERIMENTS.md).  So the time of a launch is (operand bytes of a block) x (blocks the busiest
-  // CU takes) / rate, and the choice is the kernel that makes that least: the weight-streaming kernel (a block = 16
-  // columns x all rows, 64 rows per pass), 32 x 32 ... 128 x 128 tiles with two or three LDS buffers and four or eight
-  // waves (eight / sixteen: two / four wave groups that all copy and each multiply a share of a K tile -- more waves
-  // issuing copies raise the rate by 10-30 %), and the asm-pinned 128 x 128 kernel where the problem is whole tiles.  Earlier candidates win ties (smaller tiles first).
-  {
-    const auto tiles_cost = [&](int bm, int bn, int occ, double r1, double r2, double r3) {   // us, up to a common constant
-      const double kib = (double)(bm + bn) * (double)K / 1024.0, rate[4] = {1.0, r1, r2, r3};
-      const int64_t per_cu = (blocks(bm, bn) + cus - 1) / cus, full = per_cu / occ, rem = per_cu % occ;
-      return (double)(full * occ) * kib / rate[occ] + (rem ? (double)rem * kib / rate[rem] : 0.0);
-    };
-    enum { kStream1, kStream2, kStream, kT33, kT63, kT66R, kT66, kT66S, kT126, kT126X, kT612, kT1212, kW44 };
-    double best = 1e300;
-    int pick = kT66;
-    const auto consider = [&](int id, double c) { if (c < best) { best = c; pick = id; } };
-    // weight streaming: a block = 16 weight rows + 16 MT activation rows per pass; MT = 1 fits two blocks per CU.  Rates
-    // fitted on profiles/r03/qlinear_small_m.log (16 / 32 rows) and qlinear_small_tiles.log (64 ... 128 rows).
-    const int64_t s_per_cu = ((N + 15) / 16 + cus - 1) / cus;
-    const double k_kib = (double)K / 1024.0;
-    if (M <= 16)
-      consider(kStream1, (double)(s_per_cu / 2 * 2) * 32.0 * k_kib / 36.5 + (double)(s_per_cu % 2) * 32.0 * k_kib / 29.0);
-    else if (M <= 32)
-      consider(kStream2, (double)s_per_cu * 48.0 * k_kib / 38.0);
-    else if (M <= 128)
-      consider(kStream, (double)s_per_cu * (double)((M + 63) / 64) * 80.0 * k_kib / 47.0);
-    // 8-wave blocks (two wave groups, 3-buffer ring): rates fitted on profiles/r03/qlinear_8waves.log
-    consider(kT33, tiles_cost(32, 32, 3, 42, 63, 65));
-    consider(kT63, tiles_cost(64, 32, 2, 50, 61, 0));
-    consider(kT66R, tiles_cost(64, 64, 1, 48, 0, 0));           // 16 waves (qlinear_16waves.log): one block per CU
-    consider(kT66, tiles_cost(64, 64, 2, 36, 54, 0));           // 4 waves, two buffers, two blocks per CU
-    consider(kT66S, tiles_cost(64, 64, 3, 36, 56, 59));         // 8 waves, 128-byte K steps, three blocks per CU
-    consider(kT126, tiles_cost(128, 64, 2, 44, 54, 0));
-    consider(kT126X, tiles_cost(128, 64, 1, 48, 0, 0));         // 16 waves, 256-byte K steps: one block per CU
-    consider(kT612, tiles_cost(64, 128, 3, 36, 50, 64));
-    consider(kT1212, tiles_cost(128, 128, 2, 30, 48, 0));
-    if (!with_zp && K % 128 == 0 && K >= 256 && N % 128 == 0 && M % 128 == 0) consider(kW44, tiles_cost(128, 128, 2, 38, 43, 0));
-    switch (pick) {
-      case kStream1: return MCTQ_QLL(8, 1);
-      case kStream2: return MCTQ_QLL(8, 2);
-      case kStream: return MCTQ_QLL(8, 4);
-      case kT33: return MCTQ_QG8(32, 32, 256, 3);
-      case kT63: return MCTQ_QG8(64, 32, 256, 3);
-      case kT66R: return MCTQ_QG16(64, 64, 256, 3);
-      case kT66S: return MCTQ_QG8(64, 64, 128, 3);
-      case kT126: return MCTQ_QG8(128, 64, 128, 3);
-      case kT126X: return MCTQ_QG16(128, 64, 256, 3);
-      case kT612: return MCTQ_QG(64, 128, 128);
-      case kT1212: return MCTQ_QG(128, 128, 128);
-      case kW44: return MCTQ_QW(4, 4);
-      default: return MCTQ_QG(64, 64, 256);
+  if (g_ql_variant != 0)
+    for (const QlKernel& k : kQlKernels) {
+      if (k.variant != g_ql_variant) continue;
+      if (with_zp && (k.rules & kQlNoZeroPoints))
+        return fail_arg("the register-pinned whole-tile kernels (ql_variant 2544 / 2548 / 2560) are not built for zero-point weights");
+      return k.launch[which](c);
     }
-  }
-#undef MCTQ_QG
-#undef MCTQ_QG8
-#undef MCTQ_QG16
-#undef MCTQ_QW
-#undef MCTQ_QPP
-#undef MCTQ_QLL
+  return ql_choose(c.M, c.N, c.K, with_zp, cu_count())->launch[which](c);
 }
 
 // y_code_dtype < 0: float32 output; otherwise the next layer's codes (mctq_qlinear_i8_codes' checks and parameters).
@@ -1323,80 +1339,50 @@ static int ql_output_form(QlOut& oq, int32_t y_code_dtype, float y_scale, int32_
 }
 
 // The entry points that stream half a byte per weight: 4-bit codes (lut == nullptr) or 4-bit indices into *lut.
-static int qlinear_packed4(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
-                           const uint8_t* w_codes4, const QlLut* lut, const float* w_scales, const int32_t* w_rowsum,
-                           const float* bias, void* y, int32_t y_code_dtype, float y_scale, int32_t y_zero_point,
-                           int32_t y_quant_min, int32_t y_quant_max, const QlZp& zp, bool with_zp, int64_t M, int64_t N,
-                           int64_t K, void* stream) {
-  if (M < 0 || N < 0 || K < 0) return fail_arg("negative extent");
-  if (a_code_dtype != MCTQ_CODE_I8 && a_code_dtype != MCTQ_CODE_U8) return fail_arg("bad a_code_dtype");
-  QlOut oq;
-  if (int rc = ql_output_form(oq, y_code_dtype, y_scale, y_zero_point, y_quant_min, y_quant_max)) return rc;
-  if (M == 0 || N == 0) return 0;
-  if (!a_codes || !w_codes4 || !w_scales || !w_rowsum || !y) return fail_arg("NULL pointer");
-  if (with_zp && (!zp.w_zero_points || !zp.a_rowsum)) return fail_arg("w_zero_points and a_rowsum are both required");
-  if (K % 16 != 0) return fail_arg("K must be a multiple of 16");
-  if ((((uintptr_t)a_codes) & 15u) != 0 || (((uintptr_t)w_codes4) & 7u) != 0)
-    return fail_arg("a_codes must be 16-byte and the packed weights (w_codes4 / w_idx4) 8-byte aligned");
-  if (K > (1 << 15)) return fail_arg("K > 32768 could overflow the int32 accumulator");
-  if (M > INT32_MAX / 2 || N > INT32_MAX / 2) return fail_arg("M or N too large");
-  const bool u8 = a_code_dtype == MCTQ_CODE_U8;
-  const int za = u8 ? a_zero_point - 128 : a_zero_point;
-  const int8_t* w = reinterpret_cast<const int8_t*>(w_codes4);
-  const hipStream_t s = (hipStream_t)stream;
-#define MCTQ_QL4(MT_)                                                                                               \
-  (u8 ? launch_qlinear<8, MT_, true, kQlW4>(a_codes, w, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, zp, s)     \
-      : launch_qlinear<8, MT_, false, kQlW4>(a_codes, w, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, zp, s))
-#define MCTQ_QLUT4(MT_)                                                                                                    \
-  (u8 ? launch_qlinear<8, MT_, true, kQlLut4>(a_codes, w, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, zp, s, *lut)   \
-      : launch_qlinear<8, MT_, false, kQlLut4>(a_codes, w, w_scales, w_rowsum, bias, y, M, N, K, za, a_scale, oq, zp, s, *lut))
-  if (lut) {
-    if (M <= 16) return MCTQ_QLUT4(1);
-    if (M <= 32) return MCTQ_QLUT4(2);
-    return MCTQ_QLUT4(4);
-  }
-  if (M <= 16) return MCTQ_QL4(1);
-  if (M <= 32) return MCTQ_QL4(2);
-  return MCTQ_QL4(4);
-#undef MCTQ_QL4
-#undef MCTQ_QLUT4
+template <int WFMT, class... Lut>
+static int launch_packed4(const QlCall& c, bool u8, Lut... lut) {
+  if (c.M <= 16) return u8 ? launch_qlinear<8, 1, true, WFMT>(c, lut...) : launch_qlinear<8, 1, false, WFMT>(c, lut...);
+  if (c.M <= 32) return u8 ? launch_qlinear<8, 2, true, WFMT>(c, lut...) : launch_qlinear<8, 2, false, WFMT>(c, lut...);
+  return u8 ? launch_qlinear<8, 4, true, WFMT>(c, lut...) : launch_qlinear<8, 4, false, WFMT>(c, lut...);
 }
+static int qlinear_packed4(QlCall c, int32_t a_code_dtype, bool with_zp, const QlLut* lut) {
+  int rc;
+  if (!ql_check_call(c, a_code_dtype, with_zp, true, rc)) return rc;
+  const bool u8 = a_code_dtype == MCTQ_CODE_U8;
+  return lut ? launch_packed4<kQlLut4>(c, u8, *lut) : launch_packed4<kQlW4>(c, u8);
+}
+
+// The entry points' arguments as a call record that is not checked yet: a_zero_point as given, float32 output.
+#define MCTQ_QL_CALL(w_, zw_, ar_)                                                                                      \
+  QlCall c{a_codes, reinterpret_cast<const int8_t*>(w_), w_scales, w_rowsum, bias, y, M, N, K, a_zero_point, a_scale, \
+           QlOut{}, QlZp{zw_, ar_}, (hipStream_t)stream}
 
 extern "C" {
 
 int mctq_qlinear_i8(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
                     const int8_t* w_codes, const float* w_scales, const int32_t* w_rowsum, const float* bias,
                     float* y, int64_t M, int64_t N, int64_t K, void* stream) {
-  QlOut oq;
-  oq.mode = 0; oq.inv = oq.zf = oq.lo = oq.hi = 0.0f;
-  return qlinear_dispatch(a_codes, a_code_dtype, a_zero_point, a_scale, w_codes, w_scales, w_rowsum, bias, y, oq,
-                          QlZp{nullptr, nullptr}, false, M, N, K, stream);
+  MCTQ_QL_CALL(w_codes, nullptr, nullptr);
+  return qlinear_dispatch(c, a_code_dtype, false);
 }
 
 int mctq_qlinear_i8_codes(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
                           const int8_t* w_codes, const float* w_scales, const int32_t* w_rowsum, const float* bias,
-                          void* y_codes, int32_t y_code_dtype, float y_scale, int32_t y_zero_point, int32_t y_quant_min,
+                          void* y, int32_t y_code_dtype, float y_scale, int32_t y_zero_point, int32_t y_quant_min,
                           int32_t y_quant_max, int64_t M, int64_t N, int64_t K, void* stream) {
-  if (y_code_dtype != MCTQ_CODE_I8 && y_code_dtype != MCTQ_CODE_U8) return fail_arg("bad y_code_dtype");
-  if (y_quant_min > y_quant_max) return fail_arg("quant_min > quant_max");
-  if (y_code_dtype == MCTQ_CODE_I8 ? (y_quant_min < -128 || y_quant_max > 127) : (y_quant_min < 0 || y_quant_max > 255))
-    return fail_arg("clamp domain does not fit the code type");
-  QlOut oq;
-  oq.mode = y_code_dtype == MCTQ_CODE_I8 ? 1 : 2;
-  oq.inv = 1.0f / y_scale;                           // host IEEE division == the codes kernel's
-  oq.zf = (float)y_zero_point; oq.lo = (float)y_quant_min; oq.hi = (float)y_quant_max;
-  return qlinear_dispatch(a_codes, a_code_dtype, a_zero_point, a_scale, w_codes, w_scales, w_rowsum, bias, y_codes, oq,
-                          QlZp{nullptr, nullptr}, false, M, N, K, stream);
+  if (y_code_dtype < 0) return fail_arg("bad y_code_dtype");      // this entry point has no float32 form
+  MCTQ_QL_CALL(w_codes, nullptr, nullptr);
+  if (int rc = ql_output_form(c.oq, y_code_dtype, y_scale, y_zero_point, y_quant_min, y_quant_max)) return rc;
+  return qlinear_dispatch(c, a_code_dtype, false);
 }
-
 
 int mctq_qlinear_w4a8(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
                       const uint8_t* w_codes4, const float* w_scales, const int32_t* w_rowsum, const float* bias,
                       void* y, int32_t y_code_dtype, float y_scale, int32_t y_zero_point, int32_t y_quant_min,
                       int32_t y_quant_max, int64_t M, int64_t N, int64_t K, void* stream) {
-  return qlinear_packed4(a_codes, a_code_dtype, a_zero_point, a_scale, w_codes4, nullptr, w_scales, w_rowsum, bias, y,
-                         y_code_dtype, y_scale, y_zero_point, y_quant_min, y_quant_max, QlZp{nullptr, nullptr}, false, M, N, K,
-                         stream);
+  MCTQ_QL_CALL(w_codes4, nullptr, nullptr);
+  if (int rc = ql_output_form(c.oq, y_code_dtype, y_scale, y_zero_point, y_quant_min, y_quant_max)) return rc;
+  return qlinear_packed4(c, a_code_dtype, false, nullptr);
 }
 
 int mctq_qlinear_lut4a8(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
@@ -1406,9 +1392,9 @@ int mctq_qlinear_lut4a8(const void* a_codes, int32_t a_code_dtype, int32_t a_zer
   if (!lut16) return fail_arg("lut16 is NULL (a HOST pointer to 16 int8 codebook values)");
   QlLut lut;
   memcpy(lut.t, lut16, sizeof(lut.t));                // entry j -> byte j % 4 of dword j / 4 (little endian)
-  return qlinear_packed4(a_codes, a_code_dtype, a_zero_point, a_scale, w_idx4, &lut, w_scales, w_rowsum, bias, y,
-                         y_code_dtype, y_scale, y_zero_point, y_quant_min, y_quant_max, QlZp{nullptr, nullptr}, false, M, N, K,
-                         stream);
+  MCTQ_QL_CALL(w_idx4, nullptr, nullptr);
+  if (int rc = ql_output_form(c.oq, y_code_dtype, y_scale, y_zero_point, y_quant_min, y_quant_max)) return rc;
+  return qlinear_packed4(c, a_code_dtype, false, &lut);
 }
 
 int mctq_codes_rowsum(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, int32_t* a_rowsum, int64_t M,
@@ -1441,10 +1427,9 @@ int mctq_qlinear_i8_zp(const void* a_codes, int32_t a_code_dtype, int32_t a_zero
                        void* y, int32_t y_code_dtype, float y_scale, int32_t y_zero_point, int32_t y_quant_min,
                        int32_t y_quant_max, const int32_t* w_zero_points, const int32_t* a_rowsum, int64_t M, int64_t N,
                        int64_t K, void* stream) {
-  QlOut oq;
-  if (int rc = ql_output_form(oq, y_code_dtype, y_scale, y_zero_point, y_quant_min, y_quant_max)) return rc;
-  return qlinear_dispatch(a_codes, a_code_dtype, a_zero_point, a_scale, w_codes, w_scales, w_rowsum, bias, y, oq,
-                          QlZp{w_zero_points, a_rowsum}, true, M, N, K, stream);
+  MCTQ_QL_CALL(w_codes, w_zero_points, a_rowsum);
+  if (int rc = ql_output_form(c.oq, y_code_dtype, y_scale, y_zero_point, y_quant_min, y_quant_max)) return rc;
+  return qlinear_dispatch(c, a_code_dtype, true);
 }
 
 int mctq_qlinear_w4a8_zp(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
@@ -1452,10 +1437,11 @@ int mctq_qlinear_w4a8_zp(const void* a_codes, int32_t a_code_dtype, int32_t a_ze
                          void* y, int32_t y_code_dtype, float y_scale, int32_t y_zero_point, int32_t y_quant_min,
                          int32_t y_quant_max, const int32_t* w_zero_points, const int32_t* a_rowsum, int64_t M, int64_t N,
                          int64_t K, void* stream) {
-  return qlinear_packed4(a_codes, a_code_dtype, a_zero_point, a_scale, w_codes4, nullptr, w_scales, w_rowsum, bias, y,
-                         y_code_dtype, y_scale, y_zero_point, y_quant_min, y_quant_max, QlZp{w_zero_points, a_rowsum}, true,
-                         M, N, K, stream);
+  MCTQ_QL_CALL(w_codes4, w_zero_points, a_rowsum);
+  if (int rc = ql_output_form(c.oq, y_code_dtype, y_scale, y_zero_point, y_quant_min, y_quant_max)) return rc;
+  return qlinear_packed4(c, a_code_dtype, true, nullptr);
 }
+#undef MCTQ_QL_CALL
 
 #ifdef MCTQ_QL_STAMP
 int mctq_debug_ql_stamps(unsigned long long* out16x8) {      // diagnostic build only
