@@ -19,7 +19,8 @@
  *   mctq_grid_per_*_f32       the export-time functions quantize_*_torch behind `_use_custom_impl and
  *                             torch.jit.is_tracing()` (file:line at the declarations below)
  *   (dtype-generic forms, the decision-table LUT entry points and the extensions -- integer codes, the integer
- *    consumer mctq_qlinear_* -- are documented at their declarations; extensions have no reference call site)
+ *    consumer mctq_qlinear_* and the patch matrix mctq_codes_im2col_nhwc that feeds it convolutions -- are documented
+ *    at their declarations; extensions have no reference call site)
  *
  * Conventions
  *   - x, y, scales, zero_points, thresholds and lut are DEVICE pointers owned by the caller
@@ -59,6 +60,8 @@ extern "C" {
  * changed; results are bit-identical). */
 /* v10: + codebook-index codes of the LUT quantizers and their decode (mctq_lut_build_index_table, mctq_lut_codes_per_tensor /
  * _per_channel, mctq_lut_decode_per_tensor / _per_channel); no existing signature or result changed. */
+/* v10 (additive, the version number stays): + mctq_codes_im2col_nhwc, the patch matrix of NHWC activation codes that lets k x k,
+ * strided, padded and dilated convolutions run on the integer consumer; no existing signature or result changed. */
 #define MCTQ_ABI_VERSION 10
 #define MCTQ_E_ARG (-10001)
 
@@ -478,6 +481,28 @@ int mctq_grid_per_channel_f32(const float* x, float* y,
 int mctq_fq_codes_nchw_to_nhwc(const void* x, void* codes, int64_t batch, int64_t channels, int64_t pixels, int32_t dtype,
                                int32_t code_dtype, float scale, int32_t zero_point, int32_t quant_min, int32_t quant_max,
                                void* stream);
+
+/*
+ * Patch matrix of activation codes (im2col), what a k x k / strided / padded / dilated convolution feeds the integer
+ * consumer with: codes [batch][height][width][channels] (NHWC, int8 or uint8 -- a pure byte gather, the code type does
+ * not matter) -> patches [batch * Ho * Wo][kh * kw * channels], both DEVICE, 16-byte aligned, with
+ *     Ho = (height + 2 pad_h - dil_h (kh - 1) - 1) / stride_h + 1,   Wo likewise,
+ * row m = (b * Ho + oy) * Wo + ox, column k = (ky * kw + kx) * channels + c holding
+ * codes[b][oy * stride_h - pad_h + ky * dil_h][ox * stride_w - pad_w + kx * dil_w][c], or the byte pad_code & 0xFF where
+ * that tap lies outside the image.  With pad_code = the activation's zero point a padded tap contributes
+ * (a_zero_point - a_zero_point) * w = 0 to mctq_qlinear_*'s sum: the kernels' - a_zero_point * w_rowsum[n] correction
+ * makes zero padding exact.  The weights of the product are the convolution's [O][kh][kw][C] (channels innermost).
+ * channels % 16 == 0 and kh * kw * channels <= 32768 (the consumer's K limit): every 16-byte chunk of an output row is
+ * one aligned 16-byte chunk of the input or 16 pad bytes -- one 16-byte load and one 16-byte store per lane, consecutive
+ * lanes on consecutive chunks of a row; the input is re-read up to kh * kw times out of cache, the output written once.
+ * MCTQ_E_ARG with a mctq_last_error text for: negative extents; a kernel size, stride or dilation below 1; negative
+ * padding; pad_code outside [-128, 255]; channels % 16 != 0; kh * kw * channels > 32768; a padded extent above 2^31 - 1;
+ * Ho <= 0 or Wo <= 0; more than 2^31 - 1 output rows; NULL or misaligned pointers of a non-empty problem.  batch == 0
+ * returns 0 without a launch.  mctq_last_launch names the launch "codes_im2col".
+ */
+int mctq_codes_im2col_nhwc(const void* codes, void* patches, int64_t batch, int64_t height, int64_t width, int64_t channels,
+                           int32_t kh, int32_t kw, int32_t stride_h, int32_t stride_w, int32_t pad_h, int32_t pad_w,
+                           int32_t dil_h, int32_t dil_w, int32_t pad_code, void* stream);
 
 /*
  * Integer consumer of the codes (extension; the reference has no counterpart): the product a wrapped

@@ -27,6 +27,10 @@ and one per output channel in the epilogue (``mctq_qlinear_i8_zp`` / ``mctq_qlin
 whole-tile kernels do not take zero points: large whole-tile products with uniform weights run on the ~1.5 POP/s tiled
 kernels, not the 2.2 POP/s ones.
 
+Convolutions are the same product over a patch matrix (``QuantizedConv2d``: ``ops.codes_im2col`` gathers the NHWC activation
+codes into ``[B * Ho * Wo, kh * kw * C]`` rows, the weight codes are kept as ``[O, kh, kw, C]``); a padded tap holds the zero-point
+code ``za`` and so adds ``(za - za) * qw = 0``.  A pointwise stride-1 convolution needs no patch matrix (``QuantizedConv1x1``).
+
 CPU tensors run the same integer arithmetic with torch ops (host logic for tests, bit-identical to the kernel).
 """
 from typing import Optional
@@ -304,6 +308,10 @@ class QuantizedLinear(nn.Module):
         """(scale, zero_point, qmin, qmax) of this layer's activation codes: what ``emit_codes_for`` of the layer in front takes."""
         return self._a_scale, self._a_zp, self._a_qmin, self._a_qmax
 
+    def _as_rows(self, t):
+        """Codes or codebook indices shaped like the weight -> [O, K] in the order of the activation rows."""
+        return t.reshape(self.out_features, self.in_features)            # [O, C, 1, 1] of a pointwise convolution too
+
     def _weight_codes(self, w):
         """The weight kind's part: (int8 codes, scales, int32 zero points or None, (indices, int8 codebook) or None)."""
         q = self.weights_quantizer
@@ -316,9 +324,8 @@ class QuantizedLinear(nn.Module):
             if bits > 8 or lut.numel() > 256 or not bool(((lut == lut.round()) & (lut >= -128) & (lut <= 127)).all()):
                 raise RuntimeError("the codebook no longer holds at most 256 int8 values")
             lut_i8 = lut.to(torch.int8)
-            idx = idx.reshape(self.out_features, self.in_features)       # [O, C, 1, 1] of a pointwise convolution too
             scales = thr.detach().to(device=w.device, dtype=torch.float32) / float(2 ** (bits - 1))
-            return lut_i8.to(w.device)[idx.long()], scales, None, (idx, lut_i8)
+            return lut_i8.to(w.device)[idx.long()], scales, None, (self._as_rows(idx), lut_i8)
         codes, scales, zps = q.quantize_to_codes(w.detach())
         if not self._uniform_weights:
             if codes.dtype != torch.int8:
@@ -344,7 +351,7 @@ class QuantizedLinear(nn.Module):
         def per_channel(t):
             return (t.expand(self.out_features) if t.numel() == 1 else t).contiguous()
 
-        codes = codes.reshape(self.out_features, self.in_features)       # [O, C, 1, 1] of a pointwise convolution too
+        codes = self._as_rows(codes)
         self._w_codes = codes.contiguous()
         self._w_scales = per_channel(scales.to(device=w.device, dtype=torch.float32).reshape(-1))
         self._w_rowsum = codes.sum(dim=1, dtype=torch.int32).contiguous()
@@ -433,9 +440,90 @@ class QuantizedConv1x1(QuantizedLinear):
         return y.reshape(b, h, w_, self.out_features).permute(0, 3, 1, 2)
 
 
-def _consumer_for(wrapper, activation_quantizer, uniform_weights=False):
+class QuantizedConv2d(QuantizedLinear):
+    """``activation quantizer -> PytorchQuantizationWrapper(nn.Conv2d)`` on integer codes for any kernel size, stride,
+    dilation and symmetric zero padding (``groups == 1``): the convolution is the same product over a patch matrix.  The
+    activation codes, NHWC, are gathered into ``[B * Ho * Wo, kh * kw * C]`` rows (``ops.codes_im2col``, one
+    data-movement launch; the matrix is materialised: kh * kw bytes per input element at stride 1) and the weight codes
+    are kept as ``[O, kh, kw, C]`` rows; everything behind that is QuantizedLinear's.  Padded taps hold the activation's
+    zero-point code, so they add ``(za - za) * qw = 0`` to the sum: zero padding is exact.  That needs the zero point
+    inside the clamp domain, ``in_channels % 16 == 0`` and ``kh * kw * in_channels <= 32768``.  ``padding="same"`` only
+    where every ``dilation * (k - 1)`` is even (PyTorch pads one side more otherwise).  The result has the NCHW shape
+    with channels-last strides."""
+
+    def __init__(self, conv: nn.Conv2d, weights_quantizer, activation_quantizer):
+        if not self.eligible(conv):
+            raise TypeError("QuantizedConv2d takes ungrouped, zero-padded (symmetric) nn.Conv2d layers with in_channels % 16 == 0 "
+                            f"and kh * kw * in_channels <= {_MAX_K}")
+        if conv.weight.dtype != torch.float32 or (conv.bias is not None and conv.bias.dtype != torch.float32):
+            raise TypeError(f"QuantizedConv2d takes float32 layers, got weight {conv.weight.dtype}"
+                            + ("" if conv.bias is None else f" / bias {conv.bias.dtype}"))
+        if conv.bias is not None and conv.bias.device != conv.weight.device:
+            raise TypeError("weight and bias live on different devices")
+        kh, kw = conv.kernel_size
+        # (a shape holder for QuantizedLinear's checks: no [O, K] float tensor is ever allocated)
+        lin = nn.Linear(kh * kw * conv.in_channels, conv.out_channels, bias=False, device="meta", dtype=conv.weight.dtype)
+        super().__init__(lin, weights_quantizer, activation_quantizer)
+        if not self._a_qmin <= self._a_zp <= self._a_qmax:
+            raise NotImplementedError("the activation zero point lies outside the codes' domain: it cannot be the pad byte")
+        self.weight = conv.weight                         # [O, C, kh, kw]; the codes are taken from it as [O, kh, kw, C]
+        self.bias = conv.bias
+        self.in_channels = conv.in_channels
+        self.kernel_size, self.stride, self.dilation = tuple(conv.kernel_size), tuple(conv.stride), tuple(conv.dilation)
+        self.padding = self._padding(conv)
+
+    @staticmethod
+    def _padding(conv):
+        """(pad_h, pad_w) of a symmetrically zero-padded convolution, or None."""
+        if conv.padding == "valid":
+            return 0, 0
+        if conv.padding == "same":
+            spans = [d * (k - 1) for d, k in zip(conv.dilation, conv.kernel_size)]
+            return None if any(s % 2 for s in spans) else tuple(s // 2 for s in spans)
+        if isinstance(conv.padding, tuple) and len(conv.padding) == 2 and all(isinstance(p, int) and p >= 0 for p in conv.padding):
+            return conv.padding
+        return None
+
+    @classmethod
+    def eligible(cls, conv) -> bool:
+        return (isinstance(conv, nn.Conv2d) and conv.groups == 1 and conv.padding_mode == "zeros"
+                and cls._padding(conv) is not None and conv.in_channels % 16 == 0
+                and conv.kernel_size[0] * conv.kernel_size[1] * conv.in_channels <= _MAX_K)
+
+    @classmethod
+    def from_wrapper(cls, wrapper: PytorchQuantizationWrapper, activation_quantizer) -> "QuantizedConv2d":
+        quantizers = wrapper.weights_quantizers
+        layer = wrapper.layer
+        if list(quantizers) != ["weight"] or not cls.eligible(layer):
+            raise TypeError("expected a wrapped nn.Conv2d the integer consumer can take, with one quantizer on 'weight'")
+        conv = nn.Conv2d(layer.in_channels, layer.out_channels, layer.kernel_size, layer.stride, layer.padding, layer.dilation,
+                         bias=False, device="meta", dtype=wrapper.weight.dtype)
+        conv.weight = wrapper.weight                     # the wrapper owns the float weight as its parameter
+        conv.bias = layer.bias
+        return cls(conv, quantizers["weight"], activation_quantizer)
+
+    def _as_rows(self, t):
+        kh, kw = self.kernel_size
+        return t.reshape(self.out_features, self.in_channels, kh, kw).permute(0, 2, 3, 1).reshape(self.out_features, self.in_features)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if x.dim() != 4 or x.shape[1] != self.in_channels:
+            raise RuntimeError(f"expected [N, {self.in_channels}, H, W], got {tuple(x.shape)}")
+        if x.dtype in (torch.uint8, torch.int8):          # codes from the previous layer: NCHW-shaped, NHWC-stored
+            codes = x.permute(0, 2, 3, 1)
+        else:
+            codes = ops.fq_codes_nhwc(x, self._a_qmin, self._a_qmax, self._a_scale, self._a_zp)
+        rows = ops.codes_im2col(codes, self.kernel_size, self.stride, self.padding, self.dilation, self._a_zp)
+        y = super().forward(rows)
+        b, _, h, w_ = x.shape
+        ho, wo = ((n + 2 * p - d * (k - 1) - 1) // s + 1
+                  for n, k, s, p, d in zip((h, w_), self.kernel_size, self.stride, self.padding, self.dilation))
+        return y.reshape(b, ho, wo, self.out_features).permute(0, 3, 1, 2)
+
+
+def _consumer_for(wrapper, activation_quantizer, uniform_weights=False, convolutions=False):
     """The integer consumer that can stand in for ``wrapper`` fed by ``activation_quantizer``, or None.  Uniform weights
-    only with ``uniform_weights``."""
+    only with ``uniform_weights``; convolutions that need a patch matrix (QuantizedConv2d) only with ``convolutions``."""
     layer = getattr(wrapper, "layer", None)
     if list(getattr(wrapper, "weights_quantizers", {})) != ["weight"]:
         return None
@@ -452,6 +540,8 @@ def _consumer_for(wrapper, activation_quantizer, uniform_weights=False):
             return QuantizedLinear.from_wrapper(wrapper, activation_quantizer)
         if QuantizedConv1x1.eligible(layer) and layer.in_channels % 16 == 0 and layer.in_channels <= _MAX_K:
             return QuantizedConv1x1.from_wrapper(wrapper, activation_quantizer)
+        if convolutions and QuantizedConv2d.eligible(layer):
+            return QuantizedConv2d.from_wrapper(wrapper, activation_quantizer)
     except (TypeError, NotImplementedError):
         return None
     return None
@@ -466,7 +556,8 @@ def _plain_holder(m) -> bool:
     return isinstance(m, PytorchActivationQuantizationHolder) and not getattr(m, "quantization_bypass", False)
 
 
-def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights: bool = False) -> int:
+def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights: bool = False,
+                          convolutions: bool = False) -> int:
     """In every ``nn.Sequential`` of ``model``: an activation holder directly followed by a wrapped ``nn.Linear`` with
     a symmetric, power-of-two or LUT weights quantizer (int8 codebook values, at most 256 entries) becomes (Identity,
     QuantizedLinear); a wrapped pointwise ``nn.Conv2d`` likewise becomes a QuantizedConv1x1.  Returns the number of pairs
@@ -478,6 +569,11 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
     of the activation codes), and large whole-tile products run on the tiled kernels rather than the faster whole-tile
     ones.  By default such pairs are left alone.
 
+    ``convolutions=True`` also fuses the other wrapped ``nn.Conv2d`` layers -- k x k, strided, padded, dilated -- into a
+    QuantizedConv2d (``groups == 1``, symmetric zero padding, ``in_channels % 16 == 0``, ``kh * kw * in_channels`` <= 32768,
+    the activation zero point inside its clamp domain).  Each of them materialises a patch matrix of ``kh * kw`` bytes per
+    output pixel and input channel per forward, so by default such pairs are left alone.
+
     ``chain=True``: where one QuantizedLinear feeds the next directly, the float32 tensor between them is never
     materialised -- the first emits the second's activation codes from its epilogue (same codes, bit for bit, as
     quantizing the float32 output).  Modules or hooks that look at that intermediate tensor then see uint8/int8 codes."""
@@ -487,7 +583,7 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
             holder, wrapper = seq[i], seq[i + 1]
             if not _plain_holder(holder) or not isinstance(wrapper, PytorchQuantizationWrapper):
                 continue
-            fused = _consumer_for(wrapper, holder.activation_holder_quantizer, uniform_weights)
+            fused = _consumer_for(wrapper, holder.activation_holder_quantizer, uniform_weights, convolutions)
             if fused is None:
                 continue
             seq[i] = _FusedAway()
@@ -501,12 +597,14 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
     return replaced
 
 
-def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weights: bool = False):
+def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weights: bool = False,
+                             convolutions: bool = False):
     """The same rewrite on an arbitrary module graph (MCT-exported models are not ``nn.Sequential``): traces ``model``
     with torch.fx keeping wrappers and holders as leaves, and wherever an activation holder's ONLY consumer is a
     wrapped ``nn.Linear`` the integer consumer can take (symmetric, power-of-two or LUT weights, and with
     ``uniform_weights=True`` uniform weights, as for ``fuse_linear_consumers``), replaces the pair by one
-    ``QuantizedLinear`` node.
+    ``QuantizedLinear`` node; wrapped pointwise convolutions likewise, and with ``convolutions=True`` the other
+    convolutions a QuantizedConv2d can take.
     Returns ``(graph_module, pairs_replaced)``.  Holders with several consumers (residual branches) stay."""
     import torch.fx as fx
 
@@ -531,7 +629,7 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
         holder = mods.get(src.target)
         if not _plain_holder(holder):
             continue
-        fused = _consumer_for(wrapper, holder.activation_holder_quantizer, uniform_weights)
+        fused = _consumer_for(wrapper, holder.activation_holder_quantizer, uniform_weights, convolutions)
         if fused is None:
             continue
         name = node.target.replace(".", "_") + "_qlinear"

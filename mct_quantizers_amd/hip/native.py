@@ -130,6 +130,8 @@ SIGNATURES = {
     "mctq_fq_codes_nchw_to_nhwc": (ctypes.c_int, [_c_f32p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                                   ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_int32,
                                                   ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
+    "mctq_codes_im2col_nhwc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                              ctypes.c_int64] + [ctypes.c_int32] * 9 + [ctypes.c_void_p]),
     "mctq_lut_table_entries": (ctypes.c_int32, [ctypes.c_float, ctypes.c_float]),
     "mctq_lut_build_table": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_float,
                                             ctypes.c_float, ctypes.c_void_p]),

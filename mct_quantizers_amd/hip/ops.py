@@ -580,6 +580,56 @@ def fq_codes_nhwc(x, qmin: int, qmax: int, scale: float, zero_point: int):
     return codes.permute(0, 2, 3, 1).contiguous()          # a no-op view + check for channels-last storage
 
 
+def _pair(v, what: str):
+    """An int or a pair of ints (torch.nn.Conv2d's kernel_size / stride / padding / dilation) -> (h, w)."""
+    if isinstance(v, int):
+        return v, v
+    v = tuple(v)
+    if len(v) != 2 or not all(isinstance(e, int) for e in v):
+        raise ValueError(f"codes_im2col: {what} must be an int or a pair of ints, got {v!r}")
+    return v
+
+
+def codes_im2col(codes_nhwc, kernel_size, stride=1, padding=0, dilation=1, pad_code: int = 0):
+    """The patch matrix of a convolution over activation codes: contiguous int8 / uint8 codes [B, H, W, C] (what
+    ``fq_codes_nhwc`` returns) -> [B * Ho * Wo, kh * kw * C], row (b, oy, ox), column (ky * kw + kx) * C + c; taps
+    outside the image hold ``pad_code`` (the activation's zero point: such a tap then adds nothing to the integer
+    consumer's sum).  GPU tensors run mctq_codes_im2col_nhwc (C % 16 == 0, kh * kw * C <= 32768); CPU tensors the same
+    gather with torch ops, byte for byte."""
+    if not isinstance(codes_nhwc, torch.Tensor) or codes_nhwc.dim() != 4:
+        raise ValueError("codes_im2col takes [N, H, W, C] tensors")
+    if codes_nhwc.dtype not in (torch.int8, torch.uint8):
+        raise NotImplementedError(f"codes_im2col: int8 / uint8 codes only, got {codes_nhwc.dtype}")
+    (kh, kw), (sh, sw) = _pair(kernel_size, "kernel_size"), _pair(stride, "stride")
+    (ph, pw), (dh, dw) = _pair(padding, "padding"), _pair(dilation, "dilation")
+    pad_code = int(pad_code)
+    lo, hi = (0, 255) if codes_nhwc.dtype == torch.uint8 else (-128, 127)
+    if not lo <= pad_code <= hi:
+        raise ValueError(f"codes_im2col: pad_code {pad_code} is no {codes_nhwc.dtype} code")
+    if min(kh, kw, sh, sw, dh, dw) < 1 or min(ph, pw) < 0:
+        raise ValueError("codes_im2col: kernel_size, stride and dilation must be at least 1 and padding at least 0")
+    b, h, w, c = codes_nhwc.shape
+    ho = (h + 2 * ph - dh * (kh - 1) - 1) // sh + 1
+    wo = (w + 2 * pw - dw * (kw - 1) - 1) // sw + 1
+    if ho <= 0 or wo <= 0:
+        raise ValueError(f"codes_im2col: a {kh}x{kw} kernel (dilation {dh}x{dw}) does not fit the padded {h}x{w} image")
+    x = codes_nhwc if codes_nhwc.is_contiguous() else codes_nhwc.contiguous()
+    if x.is_cuda:
+        lib = native.load()
+        with _maybe_on_device(x):
+            y = torch.empty((b * ho * wo, kh * kw * c), dtype=x.dtype, device=x.device)
+            rc = _launch(lib.mctq_codes_im2col_nhwc, x.data_ptr(), y.data_ptr(), b, h, w, c, kh, kw, sh, sw, ph, pw, dh, dw,
+                         pad_code, _stream(x))
+        if rc:
+            native.check(rc, "mctq_codes_im2col_nhwc")
+        return y
+    _cpu_route_allowed()
+    xp = torch.nn.functional.pad(x, (0, 0, pw, pw, ph, ph), value=pad_code)              # [B, H + 2 ph, W + 2 pw, C]
+    sb, sy, sx, sc = xp.stride()
+    taps = xp.as_strided((b, ho, wo, kh, kw, c), (sb, sy * sh, sx * sw, sy * dh, sx * dw, sc))
+    return taps.reshape(b * ho * wo, kh * kw * c)
+
+
 def make_lut_table(lut_values, mult: float, cmin: float, cmax: float, device):
     """Device copy of the codebook's decision table (see include/mctq_hip.h), or None.
 
