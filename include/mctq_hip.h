@@ -62,6 +62,8 @@ extern "C" {
  * _per_channel, mctq_lut_decode_per_tensor / _per_channel); no existing signature or result changed. */
 /* v10 (additive, the version number stays): + mctq_codes_im2col_nhwc, the patch matrix of NHWC activation codes that lets k x k,
  * strided, padded and dilated convolutions run on the integer consumer; no existing signature or result changed. */
+/* v10 (additive, the version number stays): + mctq_qconv_dw_i8, the depthwise convolution on NHWC activation codes (the layer between
+ * the two pointwise convolutions of a MobileNet-style block); no existing signature or result changed. */
 #define MCTQ_ABI_VERSION 10
 #define MCTQ_E_ARG (-10001)
 
@@ -503,6 +505,42 @@ int mctq_fq_codes_nchw_to_nhwc(const void* x, void* codes, int64_t batch, int64_
 int mctq_codes_im2col_nhwc(const void* codes, void* patches, int64_t batch, int64_t height, int64_t width, int64_t channels,
                            int32_t kh, int32_t kw, int32_t stride_h, int32_t stride_w, int32_t pad_h, int32_t pad_w,
                            int32_t dil_h, int32_t dil_w, int32_t pad_code, void* stream);
+
+/*
+ * Depthwise convolution on activation codes (groups == channels, channel multiplier 1; extension, the reference has no
+ * counterpart): what a wrapped depthwise torch.nn.Conv2d computes on fake-quantized operands, evaluated on the codes.
+ *     acc[b][oy][ox][c] = sum over the taps (ky, kx) inside the image of
+ *                         (a[b][oy * stride_h - pad_h + ky * dil_h][ox * stride_w - pad_w + kx * dil_w][c] - a_zero_point)
+ *                         * (w[ky][kx][c] - zw[c])
+ *     y[b][oy][ox][c]   = float(acc) * (a_scale * w_scales[c]) + bias[c]
+ * zw = 0 when w_zero_points is NULL.  Taps outside the image add nothing: zero padding, exact for the reason given at
+ * mctq_codes_im2col_nhwc (the kernel gives such a tap the zero-point byte).  The int32 sum is exact (at most 256 taps of
+ * |a - za| <= 255 times |w - zw| <= 255: below 2^24 * 2^8); then one float32 multiply of the two scales, one float32
+ * multiply and one float32 add, each rounded once -- the arithmetic of mctq_qlinear_i8.  Output forms as for
+ * mctq_qlinear_w4a8: y_code_dtype < 0 -> y is float32 [batch][Ho][Wo][channels]; MCTQ_CODE_I8 / _U8 -> y holds the next
+ * layer's codes, clamp(rint(y * (1.0f / y_scale)) + y_zero_point, y_quant_min, y_quant_max), NaN -> y_quant_min.
+ *     Ho = (height + 2 pad_h - dil_h (kh - 1) - 1) / stride_h + 1,   Wo likewise.
+ * a_codes [batch][height][width][channels] (NHWC) int8 or uint8 (a_code_dtype); w_codes [kh][kw][channels] int8, channel
+ * innermost, in the int8-ranged domain of mctq_qlinear_i8_zp's weights (uniform codes and zero points re-biased by half
+ * the domain, codebook weights as their int8 codebook values); w_scales float32[channels]; w_zero_points int32[channels],
+ * each in [-128, 127], or NULL; bias float32[channels] or NULL.  All DEVICE pointers, 16-byte aligned (the per-channel
+ * tables are read 16 bytes at a time too).
+ * A lane owns one 16-channel chunk of one output pixel (consecutive lanes: consecutive chunks, then consecutive pixels):
+ * per tap one 16-byte activation load and one 16-byte weight load, 16 int32 accumulators, 16-byte stores.
+ * MCTQ_E_ARG with a mctq_last_error text, before any pointer is read or anything is launched, for: negative extents; a
+ * kernel size, stride or dilation below 1; negative padding; channels % 16 != 0; kh * kw > 256; a bad a_code_dtype;
+ * a_zero_point outside the code type's range ([-128, 127] / [0, 255]: it is the byte a padded tap is given); a bad output
+ * form (mctq_qlinear_i8_codes' checks); a padded extent above 2^31 - 1; Ho <= 0 or Wo <= 0; a non-empty batch of images
+ * without pixels; more than 2^31 - 1 output pixels, or more than 2^32 - 1 16-channel chunks of output (split the batch);
+ * NULL or misaligned pointers of a non-empty problem.  batch == 0 or channels == 0 returns 0 without a launch.
+ * mctq_last_launch names the launch "qconv_dw", op "u8 x i8" / "i8 x i8", with " zp" appended when w_zero_points was given.
+ */
+int mctq_qconv_dw_i8(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
+                     const int8_t* w_codes, const float* w_scales, const int32_t* w_zero_points, const float* bias,
+                     void* y, int32_t y_code_dtype, float y_scale, int32_t y_zero_point, int32_t y_quant_min, int32_t y_quant_max,
+                     int64_t batch, int64_t height, int64_t width, int64_t channels,
+                     int32_t kh, int32_t kw, int32_t stride_h, int32_t stride_w, int32_t pad_h, int32_t pad_w,
+                     int32_t dil_h, int32_t dil_w, void* stream);
 
 /*
  * Integer consumer of the codes (extension; the reference has no counterpart): the product a wrapped

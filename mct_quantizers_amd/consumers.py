@@ -31,6 +31,12 @@ Convolutions are the same product over a patch matrix (``QuantizedConv2d``: ``op
 codes into ``[B * Ho * Wo, kh * kw * C]`` rows, the weight codes are kept as ``[O, kh, kw, C]``); a padded tap holds the zero-point
 code ``za`` and so adds ``(za - za) * qw = 0``.  A pointwise stride-1 convolution needs no patch matrix (``QuantizedConv1x1``).
 
+Depthwise convolutions (``groups == in_channels == out_channels``: the 3x3 layer between the two pointwise convolutions of a
+MobileNet-style block) have no reduction over channels and so no patch matrix worth building: ``QuantizedDepthwiseConv2d`` runs
+``mctq_qconv_dw_i8``, a direct convolution on the NHWC codes with the weight codes kept as ``[kh, kw, C]`` -- 1 byte read per
+input element, ``kh * kw`` integer multiply-accumulates per output element, the same epilogue and output forms.  With it the
+expand -> depthwise -> project layers of such a block can be chained on codes.
+
 CPU tensors run the same integer arithmetic with torch ops (host logic for tests, bit-identical to the kernel).
 """
 from typing import Optional
@@ -161,6 +167,74 @@ def qlinear_i8(a_codes: torch.Tensor, a_zero_point: int, a_scale: float, w_codes
         _check_consumer_operands(a_codes, w_scales, None, None, w_zero_points)     # dtype, device, one per output channel
         w32 = w32 - w_zero_points.to(torch.int32).reshape(-1, 1)
     acc = (a_codes.to(torch.int32) - int(a_zero_point)) @ w32.t()
+    y = acc.to(torch.float32) * (torch.tensor(a_scale, dtype=torch.float64).to(torch.float32) * w_scales)
+    if bias is not None:
+        y = y + bias
+    if out_codes is None:
+        return y
+    o_scale, o_zp, o_qmin, o_qmax = out_codes
+    return ops.fq_codes(y, None, None, None, o_qmin, o_qmax, o_scale, o_zp)
+
+
+def qconv_dw_i8(a_codes_nhwc: torch.Tensor, a_zero_point: int, a_scale: float, w_codes: torch.Tensor, w_scales: torch.Tensor,
+                bias: Optional[torch.Tensor], kernel_size, stride=1, padding=0, dilation=1, out_codes=None,
+                w_zero_points: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Depthwise convolution on codes: a_codes_nhwc [B, H, W, C] int8/uint8, w_codes [kh, kw, C] int8 (zero point 0 unless
+    ``w_zero_points``, int32 [C] each in [-128, 127], is given), w_scales / bias float32 [C] -> float32 [B, Ho, Wo, C],
+
+        y[b][oy][ox][c] = float(sum over taps inside the image of (a - a_zero_point) * (w[ky][kx][c] - zw[c])) * (a_scale * w_scales[c]) + bias[c]
+
+    or with ``out_codes = (scale, zero_point, qmin, qmax)`` the codes of that activation quantizer, bit-identical to
+    ``ops.fq_codes`` of the float32 result.  ``kernel_size``, ``stride``, ``padding`` and ``dilation`` are ints or pairs.
+    GPU tensors run ``mctq_qconv_dw_i8`` (C % 16 == 0, kh * kw <= 256); CPU tensors the same arithmetic with torch ops."""
+    if not isinstance(a_codes_nhwc, torch.Tensor) or a_codes_nhwc.dim() != 4 or a_codes_nhwc.dtype not in (torch.int8, torch.uint8):
+        raise TypeError("qconv_dw_i8 takes int8 / uint8 codes [B, H, W, C]")
+    (kh, kw), (sh, sw) = ops._pair(kernel_size, "kernel_size"), ops._pair(stride, "stride")
+    (ph, pw), (dh, dw) = ops._pair(padding, "padding"), ops._pair(dilation, "dilation")
+    if min(kh, kw, sh, sw, dh, dw) < 1 or min(ph, pw) < 0:
+        raise ValueError("qconv_dw_i8: kernel_size, stride and dilation must be at least 1 and padding at least 0")
+    b, h, w_, c = a_codes_nhwc.shape
+    if w_codes.dtype != torch.int8 or w_codes.device != a_codes_nhwc.device or tuple(w_codes.shape) != (kh, kw, c):
+        raise TypeError(f"w_codes must be an int8 tensor [{kh}, {kw}, {c}] on {a_codes_nhwc.device}, got {w_codes.dtype} "
+                        f"{tuple(w_codes.shape)} on {w_codes.device}")
+    _check_consumer_operands(a_codes_nhwc, w_scales, None, bias, w_zero_points)
+    if w_scales.numel() != c or (bias is not None and bias.numel() != c):
+        raise RuntimeError(f"w_scales and bias must have one entry per channel ({c})")
+    a_zero_point = int(a_zero_point)
+    lo, hi = (0, 255) if a_codes_nhwc.dtype == torch.uint8 else (-128, 127)
+    if not lo <= a_zero_point <= hi:
+        raise ValueError(f"qconv_dw_i8: a_zero_point {a_zero_point} is no {a_codes_nhwc.dtype} code")
+    ho = (h + 2 * ph - dh * (kh - 1) - 1) // sh + 1
+    wo = (w_ + 2 * pw - dw * (kw - 1) - 1) // sw + 1
+    if ho <= 0 or wo <= 0:
+        raise ValueError(f"qconv_dw_i8: a {kh}x{kw} kernel (dilation {dh}x{dw}) does not fit the padded {h}x{w_} image")
+    if a_codes_nhwc.is_cuda:
+        if c % 16 or kh * kw > 256:
+            raise NotImplementedError(f"mctq_qconv_dw_i8 needs C % 16 == 0 and kh * kw <= 256, got C={c}, {kh}x{kw}")
+        lib = native.load()
+        x, w_codes = a_codes_nhwc.contiguous(), w_codes.contiguous()
+        code = native.CODE_U8 if x.dtype == torch.uint8 else native.CODE_I8
+        tdt, *form = _output_form(out_codes)
+        with ops._maybe_on_device(x):
+            y = x.new_empty((b, ho, wo, c), dtype=tdt)
+            rc = ops._launch(lib.mctq_qconv_dw_i8, x.data_ptr(), code, a_zero_point, float(a_scale), w_codes.data_ptr(),
+                             w_scales.data_ptr(), None if w_zero_points is None else w_zero_points.data_ptr(),
+                             None if bias is None else bias.data_ptr(), y.data_ptr(), *form, b, h, w_, c, kh, kw, sh, sw, ph, pw,
+                             dh, dw, ops._stream(x))
+        if rc:
+            native.check(rc, "mctq_qconv_dw_i8")
+        return y
+    ops._cpu_route_allowed()
+    w32 = w_codes.to(torch.int32)
+    if w_zero_points is not None:
+        w32 = w32 - w_zero_points.to(torch.int32).reshape(1, 1, c)
+    # a padded tap holds a - za = 0: it adds nothing
+    xp = torch.nn.functional.pad(a_codes_nhwc.to(torch.int32) - a_zero_point, (0, 0, pw, pw, ph, ph))
+    acc = torch.zeros((b, ho, wo, c), dtype=torch.int32)
+    for ky in range(kh):
+        for kx in range(kw):
+            taps = xp[:, ky * dh:ky * dh + (ho - 1) * sh + 1:sh, kx * dw:kx * dw + (wo - 1) * sw + 1:sw, :]
+            acc += taps * w32[ky, kx]
     y = acc.to(torch.float32) * (torch.tensor(a_scale, dtype=torch.float64).to(torch.float32) * w_scales)
     if bias is not None:
         y = y + bias
@@ -521,9 +595,97 @@ class QuantizedConv2d(QuantizedLinear):
         return y.reshape(b, ho, wo, self.out_features).permute(0, 3, 1, 2)
 
 
-def _consumer_for(wrapper, activation_quantizer, uniform_weights=False, convolutions=False):
+class QuantizedDepthwiseConv2d(QuantizedLinear):
+    """``activation quantizer -> PytorchQuantizationWrapper(depthwise nn.Conv2d)`` on integer codes: ``groups == in_channels ==
+    out_channels`` (channel multiplier 1), any kernel size with ``kh * kw <= 256``, stride, dilation and symmetric zero
+    padding, ``in_channels % 16 == 0``.  There is no reduction over channels, so no patch matrix: ``qconv_dw_i8`` convolves
+    the NHWC activation codes directly with the weight codes kept as ``[kh, kw, C]`` (a few KiB: no packed 4-bit copies).  A
+    tap outside the image adds nothing, which the kernel gets by giving it the activation's zero-point code: that needs the
+    zero point inside the clamp domain.  All four weight families of QuantizedLinear (a per-channel axis is the output-channel
+    axis 0 of the ``[C, 1, kh, kw]`` weight); chaining and ``emit_codes_for`` as for the other consumers.  The result has the
+    NCHW shape with channels-last strides."""
+
+    def __init__(self, conv: nn.Conv2d, weights_quantizer, activation_quantizer):
+        if not self.eligible(conv):
+            raise TypeError("QuantizedDepthwiseConv2d takes zero-padded (symmetric) nn.Conv2d layers with groups == in_channels == "
+                            "out_channels, in_channels % 16 == 0 and kh * kw <= 256")
+        if conv.weight.dtype != torch.float32 or (conv.bias is not None and conv.bias.dtype != torch.float32):
+            raise TypeError(f"QuantizedDepthwiseConv2d takes float32 layers, got weight {conv.weight.dtype}"
+                            + ("" if conv.bias is None else f" / bias {conv.bias.dtype}"))
+        if conv.bias is not None and conv.bias.device != conv.weight.device:
+            raise TypeError("weight and bias live on different devices")
+        kh, kw = conv.kernel_size
+        # (a shape holder for QuantizedLinear's checks: a channel's kh * kw taps are its "row")
+        lin = nn.Linear(kh * kw, conv.out_channels, bias=False, device="meta", dtype=conv.weight.dtype)
+        super().__init__(lin, weights_quantizer, activation_quantizer)
+        if not self._a_qmin <= self._a_zp <= self._a_qmax:
+            raise NotImplementedError("the activation zero point lies outside the codes' domain: it cannot be the pad byte")
+        self.weight = conv.weight                         # [C, 1, kh, kw]; the codes are taken from it as [kh, kw, C]
+        self.bias = conv.bias
+        self.in_channels = conv.in_channels
+        self.kernel_size, self.stride, self.dilation = tuple(conv.kernel_size), tuple(conv.stride), tuple(conv.dilation)
+        self.padding = QuantizedConv2d._padding(conv)
+
+    @staticmethod
+    def eligible(conv) -> bool:
+        return (isinstance(conv, nn.Conv2d) and conv.groups == conv.in_channels == conv.out_channels
+                and conv.padding_mode == "zeros" and QuantizedConv2d._padding(conv) is not None and conv.in_channels % 16 == 0
+                and conv.kernel_size[0] * conv.kernel_size[1] <= 256)
+
+    @classmethod
+    def from_wrapper(cls, wrapper: PytorchQuantizationWrapper, activation_quantizer) -> "QuantizedDepthwiseConv2d":
+        quantizers = wrapper.weights_quantizers
+        layer = wrapper.layer
+        if list(quantizers) != ["weight"] or not cls.eligible(layer):
+            raise TypeError("expected a wrapped depthwise nn.Conv2d the integer consumer can take, with one quantizer on 'weight'")
+        conv = nn.Conv2d(layer.in_channels, layer.out_channels, layer.kernel_size, layer.stride, layer.padding, layer.dilation,
+                         groups=layer.groups, bias=False, device="meta", dtype=wrapper.weight.dtype)
+        conv.weight = wrapper.weight                     # the wrapper owns the float weight as its parameter
+        conv.bias = layer.bias
+        return cls(conv, quantizers["weight"], activation_quantizer)
+
+    def _refresh_weight_codes(self):
+        w = self.weight
+        key = (w.data_ptr(), w._version, w.device)
+        if key == self._w_key:
+            return
+        codes, scales, zps, _ = self._weight_codes(w)
+
+        def per_channel(t):
+            return (t.expand(self.in_channels) if t.numel() == 1 else t).contiguous()
+
+        kh, kw = self.kernel_size
+        self._w_codes = codes.reshape(self.in_channels, kh, kw).permute(1, 2, 0).contiguous()
+        self._w_scales = per_channel(scales.to(device=w.device, dtype=torch.float32).reshape(-1))
+        if zps is not None:
+            self._w_zps = per_channel(zps)
+        self._w_key = key
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if x.dim() != 4 or x.shape[1] != self.in_channels:
+            raise RuntimeError(f"expected [N, {self.in_channels}, H, W], got {tuple(x.shape)}")
+        self._refresh_weight_codes()
+        if x.dtype in (torch.uint8, torch.int8):          # codes from the previous layer: NCHW-shaped, NHWC-stored
+            if x.dtype != ops._code_dtype(self._a_qmin, self._a_qmax)[0]:
+                raise TypeError(f"activation codes of type {x.dtype} do not match this layer's quantizer")
+            codes = x.permute(0, 2, 3, 1)
+            codes = codes if codes.is_contiguous() else codes.contiguous()
+        else:
+            codes = ops.fq_codes_nhwc(x, self._a_qmin, self._a_qmax, self._a_scale, self._a_zp)
+        bias = None
+        if self.bias is not None:
+            bias = self.bias.detach()
+            if bias.dtype != torch.float32 or bias.device != codes.device or not bias.is_contiguous():
+                bias = bias.to(device=codes.device, dtype=torch.float32).contiguous()
+        y = qconv_dw_i8(codes, self._a_zp, self._a_scale, self._w_codes, self._w_scales, bias, self.kernel_size, self.stride,
+                        self.padding, self.dilation, self.emit_codes_for, self._w_zps)
+        return y.permute(0, 3, 1, 2)
+
+
+def _consumer_for(wrapper, activation_quantizer, uniform_weights=False, convolutions=False, depthwise=False):
     """The integer consumer that can stand in for ``wrapper`` fed by ``activation_quantizer``, or None.  Uniform weights
-    only with ``uniform_weights``; convolutions that need a patch matrix (QuantizedConv2d) only with ``convolutions``."""
+    only with ``uniform_weights``; convolutions that need a patch matrix (QuantizedConv2d) only with ``convolutions``;
+    depthwise convolutions (QuantizedDepthwiseConv2d) only with ``depthwise``."""
     layer = getattr(wrapper, "layer", None)
     if list(getattr(wrapper, "weights_quantizers", {})) != ["weight"]:
         return None
@@ -542,6 +704,8 @@ def _consumer_for(wrapper, activation_quantizer, uniform_weights=False, convolut
             return QuantizedConv1x1.from_wrapper(wrapper, activation_quantizer)
         if convolutions and QuantizedConv2d.eligible(layer):
             return QuantizedConv2d.from_wrapper(wrapper, activation_quantizer)
+        if depthwise and QuantizedDepthwiseConv2d.eligible(layer):
+            return QuantizedDepthwiseConv2d.from_wrapper(wrapper, activation_quantizer)
     except (TypeError, NotImplementedError):
         return None
     return None
@@ -557,7 +721,7 @@ def _plain_holder(m) -> bool:
 
 
 def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights: bool = False,
-                          convolutions: bool = False) -> int:
+                          convolutions: bool = False, depthwise: bool = False) -> int:
     """In every ``nn.Sequential`` of ``model``: an activation holder directly followed by a wrapped ``nn.Linear`` with
     a symmetric, power-of-two or LUT weights quantizer (int8 codebook values, at most 256 entries) becomes (Identity,
     QuantizedLinear); a wrapped pointwise ``nn.Conv2d`` likewise becomes a QuantizedConv1x1.  Returns the number of pairs
@@ -574,6 +738,11 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
     the activation zero point inside its clamp domain).  Each of them materialises a patch matrix of ``kh * kw`` bytes per
     output pixel and input channel per forward, so by default such pairs are left alone.
 
+    ``depthwise=True`` also fuses wrapped depthwise ``nn.Conv2d`` layers (``groups == in_channels == out_channels``, symmetric
+    zero padding, ``in_channels % 16 == 0``, ``kh * kw`` <= 256, the activation zero point inside its clamp domain) into a
+    QuantizedDepthwiseConv2d, a direct convolution on the codes without a patch matrix.  It is independent of
+    ``convolutions``: neither switch implies the other, and other grouped convolutions are always left alone.
+
     ``chain=True``: where one QuantizedLinear feeds the next directly, the float32 tensor between them is never
     materialised -- the first emits the second's activation codes from its epilogue (same codes, bit for bit, as
     quantizing the float32 output).  Modules or hooks that look at that intermediate tensor then see uint8/int8 codes."""
@@ -583,7 +752,7 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
             holder, wrapper = seq[i], seq[i + 1]
             if not _plain_holder(holder) or not isinstance(wrapper, PytorchQuantizationWrapper):
                 continue
-            fused = _consumer_for(wrapper, holder.activation_holder_quantizer, uniform_weights, convolutions)
+            fused = _consumer_for(wrapper, holder.activation_holder_quantizer, uniform_weights, convolutions, depthwise)
             if fused is None:
                 continue
             seq[i] = _FusedAway()
@@ -598,13 +767,14 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
 
 
 def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weights: bool = False,
-                             convolutions: bool = False):
+                             convolutions: bool = False, depthwise: bool = False):
     """The same rewrite on an arbitrary module graph (MCT-exported models are not ``nn.Sequential``): traces ``model``
     with torch.fx keeping wrappers and holders as leaves, and wherever an activation holder's ONLY consumer is a
     wrapped ``nn.Linear`` the integer consumer can take (symmetric, power-of-two or LUT weights, and with
     ``uniform_weights=True`` uniform weights, as for ``fuse_linear_consumers``), replaces the pair by one
     ``QuantizedLinear`` node; wrapped pointwise convolutions likewise, and with ``convolutions=True`` the other
-    convolutions a QuantizedConv2d can take.
+    convolutions a QuantizedConv2d can take, and with ``depthwise=True`` the depthwise convolutions a QuantizedDepthwiseConv2d
+    can take.
     Returns ``(graph_module, pairs_replaced)``.  Holders with several consumers (residual branches) stay."""
     import torch.fx as fx
 
@@ -629,7 +799,7 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
         holder = mods.get(src.target)
         if not _plain_holder(holder):
             continue
-        fused = _consumer_for(wrapper, holder.activation_holder_quantizer, uniform_weights, convolutions)
+        fused = _consumer_for(wrapper, holder.activation_holder_quantizer, uniform_weights, convolutions, depthwise)
         if fused is None:
             continue
         name = node.target.replace(".", "_") + "_qlinear"

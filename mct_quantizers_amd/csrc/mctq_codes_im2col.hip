@@ -10,7 +10,7 @@
 //
 // Index arithmetic per CHUNK, never per byte: five divisions by launch constants (chunks per row, chunks per tap, kw,
 // Wo, Ho), each a multiply-high by a host-computed reciprocal and one correction step.
-#include "mctq_kernels.hpp"
+#include "mctq_consumer.hpp"               // FastDiv, u32x4
 
 // timing experiment (tools/conv_consumer_probe.py --im2col-only): 1 = non-temporal stores of the patch matrix
 #ifndef MCTQ_IM2COL_NT
@@ -24,18 +24,6 @@
 
 namespace mctq {
 
-// n / d for 32-bit n by magic = floor(2^32 / d) (d = 1: 2^32 - 1): umulhi gives the quotient or one less.
-struct FastDiv {
-  uint32_t d, magic;
-  __host__ static FastDiv make(uint32_t d) { return {d, d == 1 ? 0xffffffffu : (uint32_t)((1ull << 32) / d)}; }
-  __device__ __forceinline__ uint32_t divmod(uint32_t n, uint32_t& rem) const {
-    uint32_t q = __umulhi(n, magic);
-    rem = n - q * d;
-    if (rem >= d) { ++q; rem -= d; }
-    return q;
-  }
-};
-
 struct Im2colArgs {
   const uint8_t* x;
   uint8_t* y;
@@ -44,8 +32,6 @@ struct Im2colArgs {
   int32_t H, W, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w;
   uint32_t pad4;                                   // the pad byte in all four bytes
 };
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 __global__ __launch_bounds__(kThreads) void codes_im2col_kernel(Im2colArgs a) {
   const uint32_t m0 = blockIdx.x * a.rows_per_block;

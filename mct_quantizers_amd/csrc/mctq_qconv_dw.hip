@@ -1,0 +1,220 @@
+// mctq_qconv_dw.hip -- part of libmctq_hip.so (C ABI: include/mctq_hip.h).
+//
+// Depthwise convolution on the quantizers' codes (groups == channels, channel multiplier 1): the layer between the two
+// pointwise convolutions of a MobileNet-style block.  There is no reduction over channels, so nothing for the matrix
+// cores; per output element it is kh * kw multiply-accumulates on bytes:
+//     acc[b][oy][ox][c] = sum over taps inside the image of (a[b][iy][ix][c] - za) * (w[ky][kx][c] - zw[c])
+//     y = float(acc) * (sa * sw[c]) + bias[c]
+// with the epilogue of mctq_qlinear_i8 (one rounding per float32 operation; -ffp-contract=off) and its output forms
+// (QlOut: float32, or the next layer's codes).
+//
+// Layout: activations NHWC, weights [kh][kw][C], so that 16 consecutive channels are one aligned 16-byte chunk of either.
+// A lane owns one chunk of one output pixel: consecutive lanes take consecutive chunks of a pixel, then consecutive
+// pixels (a pixel may straddle two blocks) -- the loads of a tap and the stores are coalesced over the wave.  Per tap one
+// 16-byte activation load and one 16-byte weight load (the weights are kh * kw * C bytes in all and stay in cache; the
+// input is re-read up to kh * kw times out of cache), 16 int32 accumulators, and at the end four 16-byte stores of
+// float32 or one of codes.  Index arithmetic per chunk: three divisions by launch constants (FastDiv).
+//
+// Padding: a tap outside the image is loaded from a clamped (valid) address and then replaced by 16 zero-point bytes, so
+// that it adds (za - za) * (w - zw) = 0: the loads do not depend on a branch and the compiler can issue all of a 3 x 3
+// kernel's loads before the first multiply.  This is why a_zero_point must be a code of the activations' type.
+//
+// The sum is exact: |a - za| <= 255, |w - zw| <= 255, at most 256 taps: 256 * 255 * 255 < 2^24 * 2^8 < 2^31; each product
+// fits the 24-bit multiplier (v_mad_i32_i24).
+#include "mctq_consumer.hpp"
+
+// 1 (shipped): 3 x 3 kernels run an instance whose tap loops are unrolled at compile time (all 18 loads of a lane in flight
+// at once); 0: every kernel size runs the run-time loops (tools/dw_consumer_probe.py times the two builds against each other)
+#ifndef MCTQ_DW_UNROLL3
+#define MCTQ_DW_UNROLL3 1
+#endif
+
+namespace mctq {
+
+struct DwArgs {
+  const uint8_t* x;
+  const int8_t* w;
+  const float* w_scales;
+  const int32_t* w_zero_points;
+  const float* bias;
+  void* y;
+  FastDiv c16, wo, ho;                             // chunks per pixel (C / 16), Wo, Ho
+  uint32_t chunks;                                 // B * Ho * Wo * C / 16
+  int32_t H, W, kh, kw, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w;
+  int32_t za;
+  float sa;
+  QlOut oq;
+};
+
+typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
+
+// byte j of a dword as an integer: zero-extended (uint8 codes) or sign-extended (int8 codes, weights)
+template <bool U8>
+__device__ __forceinline__ int dw_byte(uint32_t v, int j) {
+  if constexpr (U8) return (int)((v >> (8 * j)) & 0xffu);
+  else return (int)(v << (24 - 8 * j)) >> 24;
+}
+
+// KK > 0: a KK x KK kernel known at compile time (a.kh == a.kw == KK); KK == 0: a.kh x a.kw
+template <bool A_U8, bool ZP, int KK>
+__global__ __launch_bounds__(kThreads) void qconv_dw_kernel(DwArgs a) {
+  const uint32_t g = blockIdx.x * (uint32_t)kThreads + threadIdx.x;          // < 2^32: the launcher checks the chunk count
+  if (g >= a.chunks) return;
+  uint32_t cc, ox, oy;
+  const uint32_t m = a.c16.divmod(g, cc);
+  const uint32_t b = a.ho.divmod(a.wo.divmod(m, ox), oy);
+  const int64_t c16 = a.c16.d;
+  const u32x4* __restrict__ src = reinterpret_cast<const u32x4*>(a.x) + (int64_t)b * a.H * a.W * c16 + cc;
+  const u32x4* __restrict__ wsrc = reinterpret_cast<const u32x4*>(a.w) + cc;
+  const int iy0 = (int)oy * a.stride_h - a.pad_h, ix0 = (int)ox * a.stride_w - a.pad_w;
+  const uint32_t pad = (uint32_t)(a.za & 0xff) * 0x01010101u;
+  const int za = a.za;
+
+  int zw[16];
+  if constexpr (ZP) {
+    const i32x4* __restrict__ zsrc = reinterpret_cast<const i32x4*>(a.w_zero_points) + (int64_t)cc * 4;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const i32x4 z = zsrc[q];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) zw[4 * q + j] = z[j];
+    }
+  }
+  int acc[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) acc[i] = 0;
+
+  auto tap = [&](int ky, int kx, int kw) {
+    const int iy = iy0 + ky * a.dil_h, ix = ix0 + kx * a.dil_w;
+    const bool inside = (uint32_t)iy < (uint32_t)a.H && (uint32_t)ix < (uint32_t)a.W;
+    const int cy = min(max(iy, 0), a.H - 1), cx = min(max(ix, 0), a.W - 1);         // a valid address whatever the tap
+    u32x4 av = src[((int64_t)cy * a.W + cx) * c16];
+    const u32x4 wv = wsrc[(int64_t)(ky * kw + kx) * c16];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const uint32_t aq = inside ? av[q] : pad;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int ae = dw_byte<A_U8>(aq, j) - za;
+        int we = dw_byte<false>(wv[q], j);
+        if constexpr (ZP) we -= zw[4 * q + j];
+        acc[4 * q + j] += __mul24(ae, we);
+      }
+    }
+  };
+  if constexpr (KK > 0) {
+#pragma unroll
+    for (int ky = 0; ky < KK; ++ky) {
+#pragma unroll
+      for (int kx = 0; kx < KK; ++kx) tap(ky, kx, KK);
+    }
+  } else {
+    for (int ky = 0; ky < a.kh; ++ky)
+      for (int kx = 0; kx < a.kw; ++kx) tap(ky, kx, a.kw);
+  }
+
+  // epilogue: float(acc) * (sa * sw[c]) (+ bias[c]), one rounding each, as mctq_qlinear_i8
+  const f32x4* __restrict__ ssrc = reinterpret_cast<const f32x4*>(a.w_scales) + (int64_t)cc * 4;
+  const f32x4* __restrict__ bsrc = reinterpret_cast<const f32x4*>(a.bias) + (int64_t)cc * 4;
+  float out[16];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const f32x4 s = ssrc[q];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) out[4 * q + j] = (float)acc[4 * q + j] * (a.sa * s[j]);
+    if (a.bias) {
+      const f32x4 bv = bsrc[q];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) out[4 * q + j] = out[4 * q + j] + bv[j];
+    }
+  }
+  if (a.oq.mode == 0) {
+    f32x4* __restrict__ dst = reinterpret_cast<f32x4*>(a.y) + (int64_t)g * 4;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) dst[q] = f32x4{out[4 * q], out[4 * q + 1], out[4 * q + 2], out[4 * q + 3]};
+  } else {
+    u32x4 codes;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      uint32_t v = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v |= ((uint32_t)ql_code(out[4 * q + j], a.oq) & 0xffu) << (8 * j);
+      codes[q] = v;
+    }
+    reinterpret_cast<u32x4*>(a.y)[g] = codes;
+  }
+}
+
+template <bool A_U8, bool ZP>
+static void launch_qconv_dw(const DwArgs& a, unsigned blocks, hipStream_t stream) {
+  if (MCTQ_DW_UNROLL3 && a.kh == 3 && a.kw == 3)
+    hipLaunchKernelGGL((qconv_dw_kernel<A_U8, ZP, 3>), dim3(blocks), dim3(kThreads), 0, stream, a);
+  else
+    hipLaunchKernelGGL((qconv_dw_kernel<A_U8, ZP, 0>), dim3(blocks), dim3(kThreads), 0, stream, a);
+}
+
+}  // namespace mctq
+
+using namespace mctq;
+
+extern "C" {
+
+int mctq_qconv_dw_i8(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
+                     const int8_t* w_codes, const float* w_scales, const int32_t* w_zero_points, const float* bias,
+                     void* y, int32_t y_code_dtype, float y_scale, int32_t y_zero_point, int32_t y_quant_min, int32_t y_quant_max,
+                     int64_t batch, int64_t height, int64_t width, int64_t channels,
+                     int32_t kh, int32_t kw, int32_t stride_h, int32_t stride_w, int32_t pad_h, int32_t pad_w,
+                     int32_t dil_h, int32_t dil_w, void* stream) {
+  if (batch < 0 || height < 0 || width < 0 || channels < 0) return fail_arg("negative extent");
+  if (kh < 1 || kw < 1) return fail_arg("kernel size below 1");
+  if (stride_h < 1 || stride_w < 1) return fail_arg("stride below 1");
+  if (dil_h < 1 || dil_w < 1) return fail_arg("dilation below 1");
+  if (pad_h < 0 || pad_w < 0) return fail_arg("negative padding");
+  if (channels % 16 != 0) return fail_arg("channels must be a multiple of 16");
+  if (kh > 256 || kw > 256 || kh * kw > 256) return fail_arg("kh * kw > 256: outside the depthwise consumer's limit");
+  if (a_code_dtype != MCTQ_CODE_I8 && a_code_dtype != MCTQ_CODE_U8) return fail_arg("bad a_code_dtype");
+  const bool u8 = a_code_dtype == MCTQ_CODE_U8;
+  // the zero point is the byte a padded tap is given (it then adds (za - za) * w = 0): it has to be a code
+  if (u8 ? (a_zero_point < 0 || a_zero_point > 255) : (a_zero_point < -128 || a_zero_point > 127))
+    return fail_arg("a_zero_point is no code of a_code_dtype");
+  DwArgs a;
+  if (int rc = ql_output_form(a.oq, y_code_dtype, y_scale, y_zero_point, y_quant_min, y_quant_max)) return rc;
+  // padded extents within int32: the kernel's input coordinates oy * stride + ky * dilation never exceed them
+  const int64_t hp = height + 2 * (int64_t)pad_h, wp = width + 2 * (int64_t)pad_w;
+  if (hp > INT32_MAX || wp > INT32_MAX) return fail_arg("padded image extent exceeds 2^31 - 1");
+  const int64_t span_h = (int64_t)dil_h * (kh - 1) + 1, span_w = (int64_t)dil_w * (kw - 1) + 1;
+  if (hp < span_h || wp < span_w) return fail_arg("the kernel does not fit the padded image (Ho <= 0 or Wo <= 0)");
+  const int64_t ho = (hp - span_h) / stride_h + 1, wo = (wp - span_w) / stride_w + 1;
+  if (batch == 0 || channels == 0) return 0;
+  // (padding alone could make room for a kernel on an image without pixels; the clamped loads need one)
+  if (height == 0 || width == 0) return fail_arg("an image of a non-empty batch needs at least one pixel");
+  if (batch > INT32_MAX / (ho * wo)) return fail_arg("too many output pixels for one launch");       // ho * wo < 2^62
+  const int64_t pixels = batch * ho * wo, c16 = channels / 16;
+  // a lane's index, pixel * (channels / 16) + chunk, is a 32-bit number (beyond it: split the batch)
+  if (c16 > UINT32_MAX / pixels) return fail_arg("more than 2^32 - 1 16-channel chunks of output in one launch");
+  if (!a_codes || !w_codes || !w_scales || !y) return fail_arg("NULL pointer");
+  if ((((uintptr_t)a_codes | (uintptr_t)w_codes | (uintptr_t)y | (uintptr_t)w_scales | (uintptr_t)w_zero_points |
+        (uintptr_t)bias) & 15u) != 0)
+    return fail_arg("codes, weights, per-channel tables and output must be 16-byte aligned");
+  a.x = static_cast<const uint8_t*>(a_codes);
+  a.w = w_codes; a.w_scales = w_scales; a.w_zero_points = w_zero_points; a.bias = bias; a.y = y;
+  a.c16 = FastDiv::make((uint32_t)c16);
+  a.wo = FastDiv::make((uint32_t)wo);
+  a.ho = FastDiv::make((uint32_t)ho);
+  a.chunks = (uint32_t)(pixels * c16);
+  a.H = (int32_t)height; a.W = (int32_t)width; a.kh = kh; a.kw = kw;
+  a.stride_h = stride_h; a.stride_w = stride_w; a.pad_h = pad_h; a.pad_w = pad_w; a.dil_h = dil_h; a.dil_w = dil_w;
+  a.za = a_zero_point; a.sa = a_scale;
+  const unsigned blocks = (unsigned)(((int64_t)a.chunks + kThreads - 1) / kThreads);                  // <= 2^24
+  const hipStream_t s = (hipStream_t)stream;
+  const bool zp = w_zero_points != nullptr;
+  if (u8) { if (zp) launch_qconv_dw<true, true>(a, blocks, s); else launch_qconv_dw<true, false>(a, blocks, s); }
+  else { if (zp) launch_qconv_dw<false, true>(a, blocks, s); else launch_qconv_dw<false, false>(a, blocks, s); }
+  g_note.shape = "qconv_dw"; g_note.op = zp ? (u8 ? "u8 x i8 zp" : "i8 x i8 zp") : (u8 ? "u8 x i8" : "i8 x i8");
+  g_note.unroll = MCTQ_DW_UNROLL3 && kh == 3 && kw == 3 ? 9 : 1; g_note.nt = 0;
+  g_note.in_bytes = 1; g_note.out_bytes = a.oq.mode == 0 ? 4 : 1; ++g_note.count;
+  if (g_launch_log) log_launch();
+  return check_launch("mctq_qconv_dw_i8");
+}
+
+}  // extern "C"

@@ -11,7 +11,7 @@
 // pieces feed four MFMA steps; A and B use the same k assignment, which is all an exact integer sum needs), the 8 waves of a block interleave K blocks so that a row is read in 2 KiB
 // runs, and the partial sums meet in LDS.  One block = 16 output columns x all rows x all of K; no split-K
 // atomics, so the result does not depend on scheduling.
-#include "mctq_kernels.hpp"
+#include "mctq_consumer.hpp"
 
 namespace mctq {
 
@@ -31,22 +31,8 @@ extern int g_ql_stagger;                // tuning hook "ql_stagger": half of the
 extern int g_ql_rot;                    // tuning hook "ql_rot": K rotation between the blocks that share a weight tile (default off)
 extern int g_ql_band;                   // tuning hook "ql_band": tile rows per band of the tiled kernel, 0 = automatic
 
-// Output form: float32 values, or the next layer's activation codes (the fake-quant arithmetic of
-// mctq_fq_codes_per_tensor applied to the float32 value in registers: clamp(rint(v * inv) + zp, lo, hi)).
-struct QlOut {
-  int mode;                 // 0 float32, 1 int8 codes, 2 uint8 codes
-  float inv, zf, lo, hi;
-};
-__device__ __forceinline__ void ql_store(void* __restrict__ y, int64_t idx, float v, const QlOut& o) {
-  if (o.mode == 0) {
-    static_cast<float*>(y)[idx] = v;
-  } else {
-    float q = __builtin_rintf(v * o.inv) + o.zf;
-    q = fminf(fmaxf(q, o.lo), o.hi);                  // NaN -> lo, as the codes kernel
-    if (o.mode == 1) static_cast<int8_t*>(y)[idx] = (int8_t)(int)q;
-    else static_cast<uint8_t*>(y)[idx] = (uint8_t)(int)q;
-  }
-}
+// (QlOut, ql_store and ql_output_form -- the output form of a consumer launch -- live in mctq_consumer.hpp, shared with
+// mctq_qconv_dw.hip.)
 
 // Weight zero points (uniform weights, mctq_qlinear_*_zp): per output channel zw[n] in the domain of the int8 codes, and
 // per activation row a_rowsum[m] = sum_k (a[m][k] - za) (mctq_codes_rowsum).  Then
@@ -1321,21 +1307,6 @@ static int qlinear_dispatch(QlCall c, int32_t a_code_dtype, bool with_zp) {
       return k.launch[which](c);
     }
   return ql_choose(c.M, c.N, c.K, with_zp, cu_count())->launch[which](c);
-}
-
-// y_code_dtype < 0: float32 output; otherwise the next layer's codes (mctq_qlinear_i8_codes' checks and parameters).
-static int ql_output_form(QlOut& oq, int32_t y_code_dtype, float y_scale, int32_t y_zero_point, int32_t y_quant_min,
-                          int32_t y_quant_max) {
-  oq.mode = 0; oq.inv = oq.zf = oq.lo = oq.hi = 0.0f;
-  if (y_code_dtype < 0) return 0;
-  if (y_code_dtype != MCTQ_CODE_I8 && y_code_dtype != MCTQ_CODE_U8) return fail_arg("bad y_code_dtype");
-  if (y_quant_min > y_quant_max) return fail_arg("quant_min > quant_max");
-  if (y_code_dtype == MCTQ_CODE_I8 ? (y_quant_min < -128 || y_quant_max > 127) : (y_quant_min < 0 || y_quant_max > 255))
-    return fail_arg("clamp domain does not fit the code type");
-  oq.mode = y_code_dtype == MCTQ_CODE_I8 ? 1 : 2;
-  oq.inv = 1.0f / y_scale;                           // host IEEE division == the codes kernel's
-  oq.zf = (float)y_zero_point; oq.lo = (float)y_quant_min; oq.hi = (float)y_quant_max;
-  return 0;
 }
 
 // The entry points that stream half a byte per weight: 4-bit codes (lut == nullptr) or 4-bit indices into *lut.

@@ -132,6 +132,11 @@ SIGNATURES = {
                                                   ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
     "mctq_codes_im2col_nhwc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                               ctypes.c_int64] + [ctypes.c_int32] * 9 + [ctypes.c_void_p]),
+    "mctq_qconv_dw_i8": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,   # a_codes, type, zero point, scale
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,  # w_codes, w_scales, w_zero_points, bias
+                                        ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_int32,
+                                        ctypes.c_int32]                                                      # y and its output form
+                         + [ctypes.c_int64] * 4 + [ctypes.c_int32] * 8 + [ctypes.c_void_p]),                # B, H, W, C; geometry; stream
     "mctq_lut_table_entries": (ctypes.c_int32, [ctypes.c_float, ctypes.c_float]),
     "mctq_lut_build_table": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_float,
                                             ctypes.c_float, ctypes.c_void_p]),
