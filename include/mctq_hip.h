@@ -64,6 +64,8 @@ extern "C" {
  * strided, padded and dilated convolutions run on the integer consumer; no existing signature or result changed. */
 /* v10 (additive, the version number stays): + mctq_qconv_dw_i8, the depthwise convolution on NHWC activation codes (the layer between
  * the two pointwise convolutions of a MobileNet-style block); no existing signature or result changed. */
+/* v10 (additive, the version number stays): + mctq_fq_join_f32, the residual add, the ReLU and both outputs of a shared activation
+ * holder (fake-quantized float32 and integer codes) in one pass; no existing signature or result changed. */
 #define MCTQ_ABI_VERSION 10
 #define MCTQ_E_ARG (-10001)
 
@@ -541,6 +543,30 @@ int mctq_qconv_dw_i8(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_p
                      int64_t batch, int64_t height, int64_t width, int64_t channels,
                      int32_t kh, int32_t kw, int32_t stride_h, int32_t stride_w, int32_t pad_h, int32_t pad_w,
                      int32_t dil_h, int32_t dil_w, void* stream);
+
+/*
+ * The join in front of an activation holder that several layers share (extension; the reference runs an ATen add, an ATen
+ * ReLU and the holder as three passes): per element i of n float32 elements in storage order
+ *     v        = x[i]                                   residual == NULL
+ *     v        = x[i] + residual[i]                     otherwise: one float32 rounding, as ATen's add
+ *     v        = v < 0 ? 0 : v                          relu != 0; a NaN stays a NaN, as torch.relu
+ *     y[i]     = (clamp(rint(v * (1.0f / scale)) + zero_point, quant_min, quant_max) - zero_point) * scale
+ *     codes[i] =  clamp(rint(v * (1.0f / scale)) + zero_point, quant_min, quant_max)
+ * y is what mctq_fq_per_tensor_f32 writes for v (its arithmetic contract, NaN, +-inf and -0 included), codes what
+ * mctq_fq_codes_per_tensor writes for it (NaN -> quant_min), as int8 (code_dtype MCTQ_CODE_I8, domain within [-128, 127]) or
+ * uint8 (MCTQ_CODE_U8, within [0, 255]): (codes[i] - zero_point) * scale == y[i] bit for bit.  Either output may be NULL (not
+ * both): it is then not computed, and code_dtype is ignored without codes.  All four buffers share one dense layout of n
+ * elements; DEVICE pointers, 16-byte aligned.  A lane owns 16 consecutive elements (four 16-byte loads per input, four
+ * 16-byte stores of y, one of codes); the last n % 16 elements go through a scalar loop.  Cached loads and stores.
+ * MCTQ_E_ARG with a mctq_last_error text, before any pointer is read or anything is launched, for: n < 0; x NULL; y and codes
+ * both NULL; codes with a code_dtype other than MCTQ_CODE_I8 / _U8; a clamp domain that does not fit the code type;
+ * quant_min > quant_max; a clamp domain beyond 2^24 when y is wanted (the kernel's bounds are float32); a pointer that is not
+ * 16-byte aligned; more than 2^31 - 1 blocks.  n == 0 returns 0 without a launch.  mctq_last_launch names the launch
+ * "fq_join", op e.g. "add relu -> f32 + u8".
+ */
+int mctq_fq_join_f32(const float* x, const float* residual /* NULL: none */, int32_t relu,
+                     float* y /* NULL: no float32 output */, void* codes /* NULL: no codes */, int32_t code_dtype,
+                     int64_t n, float scale, int32_t zero_point, int32_t quant_min, int32_t quant_max, void* stream);
 
 /*
  * Integer consumer of the codes (extension; the reference has no counterpart): the product a wrapped

@@ -37,6 +37,13 @@ MobileNet-style block) have no reduction over channels and so no patch matrix wo
 input element, ``kh * kw`` integer multiply-accumulates per output element, the same epilogue and output forms.  With it the
 expand -> depthwise -> project layers of such a block can be chained on codes.
 
+Holders with several users (the end of a residual block: the next block's first convolution, and its identity add or its
+downsample convolution) are ``fuse_linear_consumers_fx(..., shared_holders=True)``'s: such a holder becomes a ``QuantizedJoin``,
+which folds the residual add and the ReLU in front of it and returns both the fake-quantized float32 tensor, for the users that
+stay in float32, and the codes, for the consumers that replace the wrapped layers -- ``mctq_fq_join_f32``, one launch that reads
+both operands once (13 bytes per element against 28 for add, ReLU, holder and codes as four passes); both outputs are bit for
+bit what the separate launches give.
+
 CPU tensors run the same integer arithmetic with torch ops (host logic for tests, bit-identical to the kernel).
 """
 from typing import Optional
@@ -720,6 +727,134 @@ def _plain_holder(m) -> bool:
     return isinstance(m, PytorchActivationQuantizationHolder) and not getattr(m, "quantization_bypass", False)
 
 
+class QuantizedJoin(nn.Module):
+    """An activation holder with several consumers (the end of a residual block), its elementwise prologue folded in:
+    ``forward(x, residual=None) -> (float32 or None, codes)`` with ``v = relu(x + residual)`` (each part as switched on),
+    the float32 tensor what the holder returns for v -- for the users that stay in float32, None with ``want_float=False``
+    -- and the codes what the integer consumers behind the holder would make of it themselves.  Dense GPU tensors take one
+    launch of ``mctq_fq_join_f32`` (``ops.fq_join``): x and residual are read once.  The codes are NCHW-shaped and
+    NHWC-stored, as a consumer's ``emit_codes_for`` output.
+
+    A 4-D input that is NCHW-contiguous and not channels-last (a network's first holder: every consumer emits channels-last)
+    takes the routes that were there before: the prologue by torch ops, the holder's own call, ``ops.fq_codes_nhwc``.
+
+    The holder stays a submodule: its quantizer is the one in use, whose parameters are read when the join is built."""
+
+    def __init__(self, holder, relu: bool = False, has_residual: bool = False, want_float: bool = True):
+        super().__init__()
+        if not _plain_holder(holder):
+            raise TypeError("QuantizedJoin takes a PytorchActivationQuantizationHolder that quantizes")
+        self.holder = holder
+        self.relu, self.has_residual, self.want_float = bool(relu), bool(has_residual), bool(want_float)
+        self._a_scale, self._a_zp, self._a_qmin, self._a_qmax = _activation_code_params(holder.activation_holder_quantizer)
+        ops._code_dtype(self._a_qmin, self._a_qmax)            # (raises for a domain that is no 8-bit code)
+
+    def forward(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None):
+        if (residual is not None) != self.has_residual:
+            raise RuntimeError(f"this join was built {'with' if self.has_residual else 'without'} a residual operand")
+        form = (self._a_scale, self._a_zp, self._a_qmin, self._a_qmax)
+        if x.dim() == 4 and x.is_contiguous() and not x.is_contiguous(memory_format=torch.channels_last):
+            v = x if residual is None else x + residual
+            if self.relu:
+                v = torch.relu(v)
+            y = self.holder(v) if self.want_float else None
+            codes = ops.fq_codes_nhwc(v, self._a_qmin, self._a_qmax, self._a_scale, self._a_zp)
+            return y, codes.permute(0, 3, 1, 2)
+        return ops.fq_join(x, *form, residual=residual, relu=self.relu, want_float=self.want_float, want_codes=True)
+
+
+def _relu_input(node, mods):
+    """The input node of ``node`` if it is a ReLU of one tensor (``nn.ReLU``, ``F.relu``, ``torch.relu``, ``Tensor.relu``), else None."""
+    from torch.fx import Node
+    if len(node.args) != 1 or not isinstance(node.args[0], Node):
+        return None
+    if node.op == "call_module":
+        ok = type(mods.get(node.target)) is nn.ReLU and not node.kwargs
+    elif node.op == "call_function":
+        ok = (node.target is torch.relu and not node.kwargs) or \
+            (node.target is torch.nn.functional.relu and not set(node.kwargs) - {"inplace"})
+    else:
+        ok = node.op == "call_method" and node.target == "relu" and not node.kwargs
+    # (an in-place ReLU the join no longer performs: nobody else may be looking at its input)
+    inplace = getattr(mods.get(node.target), "inplace", False) if node.op == "call_module" else node.kwargs.get("inplace", False)
+    if inplace and len(node.args[0].users) != 1:
+        ok = False
+    return node.args[0] if ok else None
+
+
+def _add_operands(node):
+    """The two operand nodes of ``node`` if it is a plain add of two tensors (``+``, ``+=``, ``torch.add``, ``Tensor.add``:
+    no ``alpha``, no scalar operand), else None."""
+    import operator
+    from torch.fx import Node
+    if node.kwargs or len(node.args) != 2 or not all(isinstance(a, Node) for a in node.args):
+        return None
+    if node.op == "call_function":
+        ok = node.target in (operator.add, operator.iadd, torch.add)
+        # (an in-place add the join no longer performs: nobody else may be looking at its first operand)
+        if node.target is operator.iadd and len(node.args[0].users) != 1:
+            ok = False
+    else:
+        ok = node.op == "call_method" and node.target == "add"
+    return tuple(node.args) if ok else None
+
+
+def _join_shared_holders(gm, mods, consumer_for) -> int:
+    """``fuse_linear_consumers_fx(shared_holders=True)``: every plain holder with wrapped layers among its users that
+    ``consumer_for(wrapper, quantizer)`` can take becomes a QuantizedJoin, unless it is a lone holder -> layer pair with
+    nothing in front to absorb (the pair rewrite's).  Returns the number of wrapped layers replaced."""
+    import operator
+    from torch.fx import Node
+    replaced = 0
+    for node in list(gm.graph.nodes):
+        if node.op != "call_module" or node.kwargs or len(node.args) != 1 or not isinstance(node.args[0], Node):
+            continue
+        holder = mods.get(node.target)
+        if not _plain_holder(holder):
+            continue
+        taken = []                                           # F: (user node, its consumer)
+        for user in node.users:
+            wrapper = mods.get(user.target) if user.op == "call_module" else None
+            if isinstance(wrapper, PytorchQuantizationWrapper) and not user.kwargs and user.args == (node,):
+                fused = consumer_for(wrapper, holder.activation_holder_quantizer)
+                if fused is not None:
+                    taken.append((user, fused))
+        if not taken:
+            continue
+        rest = [u for u in node.users if all(u is not t for t, _ in taken)]           # R: they keep the float32 tensor
+        src, relu_node, add_node = node.args[0], None, None
+        if len(src.users) == 1 and _relu_input(src, mods) is not None:
+            relu_node, src = src, _relu_input(src, mods)
+        if len(src.users) == 1 and _add_operands(src) is not None:
+            add_node = src
+        if len(node.users) == 1 and relu_node is None and add_node is None:
+            continue                                         # a plain pair
+        try:
+            join = QuantizedJoin(holder, relu=relu_node is not None, has_residual=add_node is not None, want_float=bool(rest))
+        except (TypeError, ValueError):
+            continue
+        name = node.target.replace(".", "_") + "_join"
+        gm.add_submodule(name, join)
+        mods[name] = join
+        with gm.graph.inserting_before(node):
+            jn = gm.graph.call_module(name, _add_operands(add_node) if add_node is not None else (src,))
+            as_float = gm.graph.call_function(operator.getitem, (jn, 0)) if rest else None
+            as_codes = gm.graph.call_function(operator.getitem, (jn, 1))
+        for user, fused in taken:
+            cname = user.target.replace(".", "_") + "_qlinear"
+            gm.add_submodule(cname, fused)
+            mods[cname] = fused
+            user.target = cname
+            user.args = (as_codes,)
+            replaced += 1
+        if rest:
+            node.replace_all_uses_with(as_float)
+        for gone in (node, relu_node, add_node):
+            if gone is not None:
+                gm.graph.erase_node(gone)
+    return replaced
+
+
 def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights: bool = False,
                           convolutions: bool = False, depthwise: bool = False) -> int:
     """In every ``nn.Sequential`` of ``model``: an activation holder directly followed by a wrapped ``nn.Linear`` with
@@ -767,7 +902,7 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
 
 
 def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weights: bool = False,
-                             convolutions: bool = False, depthwise: bool = False):
+                             convolutions: bool = False, depthwise: bool = False, shared_holders: bool = False):
     """The same rewrite on an arbitrary module graph (MCT-exported models are not ``nn.Sequential``): traces ``model``
     with torch.fx keeping wrappers and holders as leaves, and wherever an activation holder's ONLY consumer is a
     wrapped ``nn.Linear`` the integer consumer can take (symmetric, power-of-two or LUT weights, and with
@@ -775,18 +910,30 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
     ``QuantizedLinear`` node; wrapped pointwise convolutions likewise, and with ``convolutions=True`` the other
     convolutions a QuantizedConv2d can take, and with ``depthwise=True`` the depthwise convolutions a QuantizedDepthwiseConv2d
     can take.
-    Returns ``(graph_module, pairs_replaced)``.  Holders with several consumers (residual branches) stay."""
+    Returns ``(graph_module, wrapped_layers_replaced)``.  Holders with several consumers (residual branches) stay, unless
+    ``shared_holders=True``:
+
+    every plain holder then counts whose users include wrapped layers the consumer can take (under the other switches as
+    given) that are fed by the holder alone.  A ``ReLU`` in front of the holder (``nn.ReLU``, ``F.relu``, ``torch.relu``,
+    ``Tensor.relu``) that feeds nothing else is absorbed, and behind it an add of two tensors (``+``, ``+=``, ``torch.add``,
+    ``Tensor.add`` without ``alpha``) that feeds nothing else.  A holder with one user and nothing to absorb is the pair
+    above; every other one becomes a QuantizedJoin node -- one launch for add, ReLU, the holder and the codes -- whose
+    float32 output replaces the holder for the users that stay (it is not computed when there are none) and whose codes feed
+    the consumers that replace the wrapped layers.  With residual networks this is what lets the first convolution of a block
+    and its downsample branch run on codes.  Nothing chains across a join."""
     import torch.fx as fx
 
     class _Tracer(fx.Tracer):
         def is_leaf_module(self, m, qualname):
-            return isinstance(m, (PytorchQuantizationWrapper, PytorchActivationQuantizationHolder, QuantizedLinear)) \
+            return isinstance(m, (PytorchQuantizationWrapper, PytorchActivationQuantizationHolder, QuantizedLinear, QuantizedJoin)) \
                 or super().is_leaf_module(m, qualname)
 
     graph = _Tracer().trace(model)
     gm = fx.GraphModule(model, graph)
     mods = dict(gm.named_modules())
     replaced = 0
+    if shared_holders:
+        replaced = _join_shared_holders(gm, mods, lambda wrapper, q: _consumer_for(wrapper, q, uniform_weights, convolutions, depthwise))
     for node in list(gm.graph.nodes):
         if node.op != "call_module" or node.kwargs or len(node.args) != 1:
             continue

@@ -580,6 +580,54 @@ def fq_codes_nhwc(x, qmin: int, qmax: int, scale: float, zero_point: int):
     return codes.permute(0, 2, 3, 1).contiguous()          # a no-op view + check for channels-last storage
 
 
+def fq_join(x, scale: float, zero_point: int, qmin: int, qmax: int, residual=None, relu: bool = False,
+            want_float: bool = True, want_codes: bool = True):
+    """The prologue and both outputs of an activation holder that several layers share (extension, not in the reference):
+    with ``v = x`` (``+ residual``; then ``relu(v)``), returns ``(y, codes)`` where ``y = fq_per_tensor(v, ...)`` is the
+    fake-quantized float32 tensor and ``codes = fq_codes(v, ...)`` its int8 / uint8 codes, ``(codes - zero_point) * scale ==
+    y`` bit for bit; an output that is not wanted is None.  Both have x's shape and strides (a channels-last x gives
+    "NCHW-shaped, NHWC-stored" codes, which the integer consumers take as they are).
+
+    Dense float32 GPU tensors (``residual`` with x's shape, strides and dtype) run ``mctq_fq_join_f32``: one launch that
+    reads x and residual once and writes both outputs.  Everything else -- CPU tensors, other dtypes, a broadcasting or
+    differently strided residual, a non-dense or misaligned x, clamp domains beyond 2^24 -- composes the same result from
+    torch's add and relu, ``fq_per_tensor`` and ``fq_codes``.  No backward, no ``torch.compile`` op."""
+    if not want_float and not want_codes:
+        raise ValueError("fq_join: at least one of want_float / want_codes")
+    tdt = code = None
+    if want_codes:
+        tdt, code = _code_dtype(qmin, qmax)
+    direct = (_is_real(x) and x.is_cuda and x.dtype == torch.float32 and not _wide(qmin, qmax) and not _tracing()
+              and not _compiling() and _is_dense(x) and x.data_ptr() % 16 == 0)
+    if direct and residual is not None:
+        direct = (_is_real(residual) and residual.device == x.device and residual.dtype == x.dtype
+                  and residual.shape == x.shape and residual.stride() == x.stride() and residual.data_ptr() % 16 == 0)
+    if not direct:
+        if _is_real(x) and x.device.type == "cpu":
+            _cpu_route_allowed()
+        with torch.no_grad():
+            v = x if residual is None else x + residual
+            if relu:
+                v = torch.relu(v)
+            y = fq_per_tensor(v, scale, zero_point, qmin, qmax) if want_float else None
+            codes = fq_codes(v, None, None, None, qmin, qmax, scale, zero_point) if want_codes else None
+        return y, codes
+    if want_float and not qmin <= zero_point <= qmax:       # ATen's checks and messages, as fq_per_tensor
+        if qmin > qmax:
+            raise RuntimeError("`quant_min` should be less than or         equal to `quant_max`.")
+        raise RuntimeError("`zero_point` must be between `quant_min` and `quant_max`.")
+    lib = native.load()
+    y = torch.empty_like(x) if want_float else None          # preserve_format: a dense x keeps its strides
+    codes = torch.empty_like(x, dtype=tdt) if want_codes else None
+    with _maybe_on_device(x):
+        rc = _launch(lib.mctq_fq_join_f32, x.data_ptr(), None if residual is None else residual.data_ptr(), int(bool(relu)),
+                     None if y is None else y.data_ptr(), None if codes is None else codes.data_ptr(), code or 0, x.numel(),
+                     float(scale), int(zero_point), int(qmin), int(qmax), _stream(x))
+    if rc:
+        native.check(rc, "mctq_fq_join_f32")
+    return y, codes
+
+
 def _pair(v, what: str):
     """An int or a pair of ints (torch.nn.Conv2d's kernel_size / stride / padding / dilation) -> (h, w)."""
     if isinstance(v, int):

@@ -1,0 +1,499 @@
+"""Activation codes behind holders that several layers share: host logic and the CPU route (include/mctq_hip.h:
+mctq_fq_join_f32; hip/ops.py: fq_join; consumers.QuantizedJoin and the ``shared_holders`` switch of
+fuse_linear_consumers_fx).
+
+What the join computes is a composition of things the suite already pins down: ATen's add, ``torch.relu``, the holder's
+fake-quant and ``ops.fq_codes``.  So every check here is bit equality against that composition -- on the CPU route by
+construction, and through ``check_fq_join`` on whatever device tests/test_gpu_join_consumer.py hands in.
+
+The rewrite is checked against a twin model: ``ResidualStack(private_holders=True)`` gives every wrapped layer behind a
+shared holder its own duplicate of that holder, which the existing pair rewrite folds.  The duplicate re-quantizes a value
+that is already fake-quantized; that this returns the same code is checked exhaustively below
+(test_requantizing_a_fake_quantized_value_returns_its_code), so the twin must give the same bits as the joins.
+"""
+import functools
+import operator
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import bits_equal, first_mismatch
+from test_conv_consumer import activation_quantizer, conv_pair
+
+F32 = np.float32
+FORMS = {"u8": (0.37, 114, 0, 255), "i8": (0.41, -5, -128, 127)}
+PROLOGUES = [(False, False), (False, True), (True, False), (True, True)]          # (residual, relu)
+
+
+# ---- the re-quantization claim ------------------------------------------------------------------------------------------
+
+def test_requantizing_a_fake_quantized_value_returns_its_code():
+    """rint(fl(k * s) * fl(1 / s)) == k for every integer k a pair of 8-bit codes and zero points can make (|k| <= 255; checked
+    to 383) and 200 000 float32 scales spread over 2^-20 .. 2^20: quantizing a fake-quantized tensor with the same quantizer
+    gives the codes it was made from."""
+    rng = np.random.default_rng(20)
+    s = np.exp2(rng.uniform(-20, 20, 200_000)).astype(F32)
+    s[:41] = np.exp2(np.arange(-20, 21)).astype(F32)
+    s[41:45] = (F32(0.37), F32(0.41), F32(5.4 / 255), F32(5.6 / 255))
+    inv = (F32(1.0) / s).astype(F32)
+    for k in range(-383, 384):
+        y = (F32(k) * s).astype(F32)                     # what the fake-quant writes for clamp index k + zp
+        back = np.rint((y * inv).astype(F32))
+        assert np.array_equal(back, np.full_like(back, k)), (k, s[np.flatnonzero(back != k)[:4]])
+    # ... and through the library: the codes of a join's float32 output are the join's codes, its fake-quant a fixed point
+    from mct_quantizers_amd.hip import ops
+    for form in FORMS.values():
+        x = torch.from_numpy(np.linspace(-1.2, 1.2, 40001, dtype=F32) * F32(form[0] * 256))
+        y, codes = ops.fq_join(x, *form)
+        y2, codes2 = ops.fq_join(y, *form)
+        assert torch.equal(codes2, codes) and bits_equal(y2.numpy(), y.numpy()) and len(torch.unique(codes)) == 256
+
+
+# ---- ops.fq_join ----------------------------------------------------------------------------------------------------------
+
+def ties(scale, n=12):
+    """float32 values x with fl(x * fl(1 / scale)) == k + 0.5 exactly, for several k of both signs."""
+    inv = F32(1.0) / F32(scale)
+    out = []
+    for k in (-140, -7, -1, 0, 1, 2, 3, 40, 99, 100, 141, 254, 255, 300):
+        x = F32(F32(k + 0.5) / inv)
+        for _ in range(8):                               # walk to a neighbour that hits the tie, if there is one
+            p = F32(x * inv)
+            if p == F32(k + 0.5):
+                out.append(x)
+                break
+            x = np.nextafter(x, F32(np.inf) if p < k + 0.5 else F32(-np.inf), dtype=F32)
+    assert len(out) >= 6, (scale, out)
+    return out[:n]
+
+
+@functools.lru_cache(maxsize=None)
+def join_case(n, form, seed=0):
+    """(x, r) float32 [n], read-only: random values that spread over the clamp domain and past both ends, with the edge pairs
+    at the front (the vector path) and again at the back (the scalar tail, where n % 16 != 0)."""
+    scale, zp, qmin, qmax = FORMS[form]
+    rng = np.random.default_rng(1000 * n + seed + (7 if form == "i8" else 0))
+    span = scale * (qmax - qmin)
+    x = rng.uniform(-0.8 * span, 0.8 * span, n).astype(F32)
+    r = rng.uniform(-0.5 * span, 0.5 * span, n).astype(F32)
+    inf, nan, den = F32(np.inf), F32(np.nan), F32(1e-40)
+    pairs = [(nan, 1), (1, nan), (inf, 1), (-inf, 1), (inf, -inf), (-inf, inf), (inf, inf), (-0.0, -0.0), (-0.0, 0.0),
+             (0.0, -0.0), (den, 0), (den, -2 * den), (-den, 0), (1e-45, 1e-45), (1e30, 1e30), (-1e30, -1e30), (3e38, 3e38),
+             (-3e38, -3e38), (1000, 0), (-1000, 0), (0, 1000), (-3.0, 1.0), (2.0, -2.5), (-1e-3, 0)]
+    for t in ties(scale):
+        pairs += [(t, 0), (F32(t / 2), F32(t / 2))]      # the tie as x alone, and as an exact sum
+    e = np.array(pairs, dtype=F32)
+    k = min(n, len(e))
+    x[:k], r[:k] = e[:k, 0], e[:k, 1]
+    if n >= 2 * len(e):
+        x[-len(e):], r[-len(e):] = e[:, 0], e[:, 1]
+    x.setflags(write=False)
+    r.setflags(write=False)
+    return x, r
+
+
+def composed(x, r, relu, form):
+    """The chain the join replaces, on x's device: ATen add, torch.relu, ATen's fake-quant (what a holder's quantizer calls),
+    ops.fq_codes."""
+    from mct_quantizers_amd.hip import ops
+    scale, zp, qmin, qmax = form
+    v = x if r is None else x + r
+    if relu:
+        v = torch.relu(v)
+    return ops.fq_per_tensor(v, scale, zp, qmin, qmax), ops.fq_codes(v, None, None, None, qmin, qmax, scale, zp)
+
+
+def check_fq_join(x, r, relu, form, want_float=True, want_codes=True, want=None, strides=True):
+    """ops.fq_join on (x, r) against ``want`` (default: the composition on the same device), bit for bit; the two outputs
+    against each other.  Returns (y, codes) as CPU tensors."""
+    from mct_quantizers_amd.hip import ops
+    scale, zp, qmin, qmax = form
+    y, codes = ops.fq_join(x, scale, zp, qmin, qmax, residual=r, relu=relu, want_float=want_float, want_codes=want_codes)
+    wy, wc = composed(x, r, relu, form) if want is None else want
+    assert (y is None) == (not want_float) and (codes is None) == (not want_codes)
+    if want_float:
+        assert y.dtype == torch.float32 and y.shape == x.shape and y.device == x.device and (y.stride() == x.stride() or not strides)
+        assert bits_equal(y.cpu().numpy(), wy.cpu().numpy()), first_mismatch(y.cpu().numpy(), wy.cpu().numpy(), x.cpu().numpy())
+    if want_codes:
+        assert codes.dtype == (torch.uint8 if qmin >= 0 else torch.int8) and codes.shape == x.shape
+        assert codes.device == x.device and (codes.stride() == x.stride() or not strides)
+        assert torch.equal(codes.cpu(), wc.cpu()), int((codes.cpu() != wc.cpu()).sum())
+    if want_float and want_codes:                        # (codes - zp) * scale IS the fake-quantized tensor
+        deq = (codes.cpu().to(torch.float32) - zp) * torch.tensor(scale, dtype=torch.float64).to(torch.float32)
+        assert bits_equal(deq.numpy(), y.cpu().numpy()), first_mismatch(deq.numpy(), y.cpu().numpy(), x.cpu().numpy())
+    return (None if y is None else y.cpu()), (None if codes is None else codes.cpu())
+
+
+def edge_values_are_exercised(x, r, relu, form, y, codes):
+    """The case really holds what it claims: NaN sums, both clamp ends, ties, negative sums under ReLU."""
+    scale, zp, qmin, qmax = form
+    v = x + r if r is not None else x
+    assert bool(torch.isnan(v).any()) and bool(torch.isinf(v).any())
+    assert int(codes.min()) == qmin and int(codes.max()) == qmax and len(torch.unique(codes)) > 100
+    if relu:
+        assert bool((v < 0).any()) and int(codes[v < 0].to(torch.int32).sub(zp).abs().max()) == 0
+    assert bool((codes[torch.isnan(v)] == qmin).all())
+    p = v * (torch.tensor(1.0) / torch.tensor(scale, dtype=torch.float32))
+    assert int((p - torch.floor(p) == 0.5).sum()) >= 6
+
+
+@pytest.mark.parametrize("form", ["u8", "i8"])
+@pytest.mark.parametrize("residual,relu", PROLOGUES)
+def test_fq_join_equals_its_composition_on_cpu(form, residual, relu):
+    x, r = (torch.from_numpy(a.copy()) for a in join_case(4096 * 3 + 16 * 5 + 7, form))
+    r = r if residual else None
+    f = FORMS[form]
+    y, codes = check_fq_join(x, r, relu, f)
+    edge_values_are_exercised(x, r, relu, f, y, codes)
+    # the holder's arithmetic written out: ATen's operator itself
+    v = x if r is None else x + r
+    v = torch.relu(v) if relu else v
+    assert bits_equal(y.numpy(), torch.fake_quantize_per_tensor_affine(v, f[0], f[1], f[2], f[3]).numpy())
+    # each output switched off leaves the other unchanged
+    y1, none = check_fq_join(x, r, relu, f, want_codes=False)
+    none2, c1 = check_fq_join(x, r, relu, f, want_float=False)
+    assert none is None and none2 is None and bits_equal(y1.numpy(), y.numpy()) and torch.equal(c1, codes)
+
+
+def test_fq_join_equals_real_holders_and_takes_every_layout_on_cpu():
+    from mct_quantizers_amd import consumers
+    from mct_quantizers_amd.hip import ops
+    import mct_quantizers_amd as mq
+    g = torch.Generator().manual_seed(3)
+    x, r = torch.randn(2, 16, 5, 7, generator=g) * 2, torch.randn(2, 16, 5, 7, generator=g)
+    for kind in ("uniform", "relu", "signed"):
+        holder = mq.PytorchActivationQuantizationHolder(activation_quantizer(kind))
+        form = consumers._activation_code_params(holder.activation_holder_quantizer)
+        for xx, rr in ((x, r), (x.contiguous(memory_format=torch.channels_last), r.contiguous(memory_format=torch.channels_last)),
+                       (x, r[:, :, :1, :1]), (x[:, :, ::2], r[:, :, ::2]), (x.reshape(20, 56).t(), None)):
+            y, codes = ops.fq_join(xx, *form, residual=rr, relu=True)
+            v = torch.relu(xx + rr) if rr is not None else torch.relu(xx)
+            assert bits_equal(y.numpy(), holder(v).numpy()) and y.shape == v.shape
+            assert torch.equal(codes, holder.activation_holder_quantizer.quantize_to_codes(v)[0])
+    with pytest.raises(ValueError):
+        ops.fq_join(x, 0.1, 0, 0, 255, want_float=False, want_codes=False)
+    with pytest.raises(ValueError):
+        ops.fq_join(x, 0.1, 0, 0, 1023)                                     # no 8-bit code
+    y, none = ops.fq_join(x, 0.1, 0, 0, 1023, want_codes=False)            # ... but a float32 output
+    assert none is None and torch.equal(y, torch.fake_quantize_per_tensor_affine(x, 0.1, 0, 0, 1023))
+
+
+# ---- the test model -------------------------------------------------------------------------------------------------------
+
+def _holder(kind):
+    import mct_quantizers_amd as mq
+    return mq.PytorchActivationQuantizationHolder(activation_quantizer(kind))
+
+
+def _act():
+    return torch.nn.Sequential(torch.nn.ReLU(), _holder("relu"))
+
+
+class _Block(torch.nn.Module):
+    """workloads._Bottleneck over conv_pair's wrapped convolutions; ``private``: the kind of the (shared) holder in front of
+    this block, of which c1 and down then get a duplicate each."""
+
+    def __init__(self, cin, width, cout, stride, down, seed, private=None):
+        super().__init__()
+        self.c1 = conv_pair(C=cin, O=width, k=1, padding=0, seed=seed)[1]
+        self.a1 = _act()
+        self.c2 = conv_pair(C=width, O=width, k=3, stride=stride, padding=1, seed=seed + 1)[1]
+        self.a2 = _act()
+        self.c3 = conv_pair(C=width, O=cout, k=1, padding=0, seed=seed + 2)[1]
+        self.down = conv_pair(C=cin, O=cout, k=1, stride=stride, padding=0, seed=seed + 3)[1] if down else None
+        self.a3 = _act()
+        self.h_c1 = _holder(private) if private else None
+        self.h_down = _holder(private) if private and down else None
+
+    def forward(self, x):
+        y = self.c3(self.a2(self.c2(self.a1(self.c1(x if self.h_c1 is None else self.h_c1(x))))))
+        return self.a3(y + (x if self.down is None else self.down(x if self.h_down is None else self.h_down(x))))
+
+
+class ResidualStack(torch.nn.Module):
+    """An input holder and two bottleneck blocks (the first strided, with a downsample branch): ``h0`` feeds A.c1 and
+    A.down, A.a3 feeds B.c1 and B's identity add.  Input [2, 16, 9, 7]."""
+
+    def __init__(self, private_holders=False):
+        super().__init__()
+        self.h0 = _holder("uniform")
+        self.A = _Block(16, 16, 32, 2, True, 10, "uniform" if private_holders else None)
+        self.B = _Block(32, 16, 32, 1, False, 20, "relu" if private_holders else None)
+
+    def forward(self, x):
+        return self.B(self.A(self.h0(x)))
+
+
+def stack_input(device="cpu", channels_last=False):
+    x = (torch.randn(2, 16, 9, 7, generator=torch.Generator().manual_seed(5)) * 1.5).to(device)
+    return x.contiguous(memory_format=torch.channels_last) if channels_last else x
+
+
+def _targets(gm, op="call_module"):
+    return [node.target for node in gm.graph.nodes if node.op == op]
+
+
+def rewritten_stack(device="cpu"):
+    """(the joined model, its private-holders twin under the plain rewrite), both checked for what they replaced."""
+    from mct_quantizers_amd import consumers
+    gm, n = consumers.fuse_linear_consumers_fx(ResidualStack().to(device), convolutions=True, shared_holders=True)
+    twin, n_twin = consumers.fuse_linear_consumers_fx(ResidualStack(private_holders=True).to(device), convolutions=True)
+    assert n == 7 and n_twin == 7
+    assert not [m for m in twin.modules() if isinstance(m, consumers.QuantizedJoin)]
+    return gm, twin
+
+
+def test_rewrite_with_shared_holders_takes_every_convolution_and_without_is_unchanged():
+    from mct_quantizers_amd import consumers
+    gm0, n0 = consumers.fuse_linear_consumers_fx(ResidualStack(), convolutions=True)
+    assert n0 == 4
+    assert _targets(gm0) == ["h0", "A.c1", "A.a1.0", "A_c2_qlinear", "A.a2.0", "A_c3_qlinear", "A.down", "A.a3.0", "A.a3.1",
+                             "B.c1", "B.a1.0", "B_c2_qlinear", "B.a2.0", "B_c3_qlinear", "B.a3.0", "B.a3.1"]
+    assert not [m for m in gm0.modules() if isinstance(m, consumers.QuantizedJoin)]
+    gm00, n00 = consumers.fuse_linear_consumers_fx(ResidualStack(), convolutions=True, shared_holders=False)
+    assert n00 == 4 and str(gm00.graph) == str(gm0.graph) and gm00.code == gm0.code
+    gm, _ = rewritten_stack()
+    kinds = {name: type(m) for name, m in gm.named_modules() if isinstance(m, consumers.QuantizedLinear)}
+    assert kinds == {"A_c1_qlinear": consumers.QuantizedConv1x1, "A_c2_qlinear": consumers.QuantizedConv2d,
+                     "A_c3_qlinear": consumers.QuantizedConv1x1, "A_down_qlinear": consumers.QuantizedConv2d,
+                     "B_c1_qlinear": consumers.QuantizedConv1x1, "B_c2_qlinear": consumers.QuantizedConv2d,
+                     "B_c3_qlinear": consumers.QuantizedConv1x1}
+    # chain=True keeps its meaning: a join between two consumers is no direct feed
+    gmc, nc = consumers.fuse_linear_consumers_fx(ResidualStack(), convolutions=True, shared_holders=True, chain=True)
+    assert nc == 7 and all(m.emit_codes_for is None for m in gmc.modules() if isinstance(m, consumers.QuantizedLinear))
+
+
+def test_joins_in_the_rewritten_graph():
+    from mct_quantizers_amd import consumers
+    import mct_quantizers_amd as mq
+    gm, _ = rewritten_stack()
+    joins = {name: (m.relu, m.has_residual, m.want_float) for name, m in gm.named_modules() if isinstance(m, consumers.QuantizedJoin)}
+    assert joins == {"h0_join": (False, False, False),
+                     "A_a1_1_join": (True, False, False), "A_a2_1_join": (True, False, False),
+                     "B_a1_1_join": (True, False, False), "B_a2_1_join": (True, False, False),
+                     "A_a3_1_join": (True, True, True)}
+    assert _targets(gm) == ["h0_join", "A_c1_qlinear", "A_a1_1_join", "A_c2_qlinear", "A_a2_1_join", "A_c3_qlinear",
+                            "A_down_qlinear", "A_a3_1_join", "B_c1_qlinear", "B_a1_1_join", "B_c2_qlinear", "B_a2_1_join",
+                            "B_c3_qlinear", "B.a3.0", "B.a3.1"]
+    # the only add left is block B's (in front of the plain holder B.a3), the only ReLU its a3.0; nothing else computes in float
+    funcs = [node for node in gm.graph.nodes if node.op == "call_function"]
+    assert [f.target for f in funcs if f.target is not operator.getitem] == [operator.add]
+    assert not [node for node in gm.graph.nodes if node.op == "call_method"]
+    nodes = {node.name: node for node in gm.graph.nodes}
+    join = next(n for n in gm.graph.nodes if n.target == "A_a3_1_join")
+    assert [a.target for a in join.args] == ["A_c3_qlinear", "A_down_qlinear"]
+    picks = {u.args[1]: u for u in join.users}
+    assert set(picks) == {0, 1}
+    assert [u.target for u in picks[1].users] == ["B_c1_qlinear"] and [u.target for u in picks[0].users] == [operator.add]
+    for name in ("h0_join", "A_a1_1_join"):                                # codes only: no float32 pick
+        j = next(n for n in gm.graph.nodes if n.target == name)
+        assert [u.args[1] for u in j.users] == [1]
+    assert isinstance(gm.get_submodule("B.a3.1"), mq.PytorchActivationQuantizationHolder) and nodes
+    # the holder stays inside its join, with the quantizer in use
+    j = gm.get_submodule("A_a3_1_join")
+    assert isinstance(j.holder, mq.PytorchActivationQuantizationHolder)
+    assert (j._a_scale, j._a_zp, j._a_qmin, j._a_qmax) == consumers._activation_code_params(j.holder.activation_holder_quantizer)
+    # a rewritten graph can be traced again (joins are leaves): nothing is left to replace
+    again, n = consumers.fuse_linear_consumers_fx(gm, convolutions=True, shared_holders=True)
+    assert n == 0 and _targets(again) == _targets(gm)
+
+
+def check_stack_output_bits(device, channels_last, against_unrewritten=True):
+    """The joined model against its private-holders twin (bit for bit) and against the unrewritten model (the bound of
+    check_inverted_residual / check_bottleneck for fused against unfused; on the CPU, where the float32 convolutions of the
+    unrewritten model are the same on every machine)."""
+    gm, twin = rewritten_stack(device)
+    x = stack_input(device, channels_last)
+    ref = ResidualStack().to(device)(x)
+    y, y_twin = gm(x), twin(x)
+    assert y.shape == ref.shape == (2, 32, 5, 4) and y.dtype == torch.float32
+    assert bits_equal(y.cpu().numpy(), y_twin.cpu().numpy()), first_mismatch(y.cpu().numpy(), y_twin.cpu().numpy())
+    if against_unrewritten:
+        assert torch.allclose(y, ref, rtol=1e-4, atol=1e-5 * float(ref.detach().abs().max())), float((y - ref).abs().max())
+    assert len(torch.unique(y)) > 50                                        # not a saturated handful
+    return y
+
+
+@pytest.mark.parametrize("channels_last", [False, True])
+def test_rewritten_stack_gives_the_twins_bits_on_cpu(channels_last):
+    y = check_stack_output_bits("cpu", channels_last)
+    assert y.is_contiguous(memory_format=torch.channels_last)
+    if channels_last:
+        assert bits_equal(y.numpy(), check_stack_output_bits("cpu", False).numpy())
+
+
+# ---- what the rewrite leaves alone ---------------------------------------------------------------------------------------
+
+class _Variant(torch.nn.Module):
+    """x -> c0 -> (+ what ``how`` says) -> ReLU -> holder -> one or two wrapped convolutions."""
+
+    def __init__(self, how, shared=True, taken=True):
+        super().__init__()
+        self.how = how
+        self.c0 = conv_pair(C=16, O=16, k=1, padding=0, seed=1)[1]
+        self.h = _holder("relu")
+        k = dict(k=1, padding=0) if taken else dict(k=3, padding=1, padding_mode="reflect")       # reflect: no consumer takes it
+        self.c1 = conv_pair(C=16, O=16, seed=2, **k)[1]
+        self.c2 = conv_pair(C=16, O=16, seed=3, **k)[1] if shared else None
+
+    def forward(self, x):
+        y = self.c0(x)
+        if self.how == "alpha":
+            v = torch.relu(torch.add(y, x, alpha=2))
+        elif self.how == "scalar":
+            v = torch.relu(y + 1.5)
+        elif self.how == "relu twice":
+            v = torch.relu(y + x)
+            a = self.h(v)
+            return self.c1(a) + (self.c2(a) if self.c2 is not None else 0) + v
+        elif self.how == "inplace twice":
+            v = torch.nn.functional.relu(y, inplace=True)          # rewrites y, which the last add reads as well
+            a = self.h(v)
+            return self.c1(a) + (self.c2(a) if self.c2 is not None else 0) + y
+        elif self.how == "method":
+            v = y.add(x).relu()
+        elif self.how == "functional":
+            v = torch.nn.functional.relu(torch.add(y, x), inplace=False)
+        elif self.how == "iadd":
+            y += x
+            v = torch.relu(y)
+        else:
+            v = torch.relu(y + x)
+        a = self.h(v)
+        return self.c1(a) + (self.c2(a) if self.c2 is not None else 0)
+
+
+def _rewrite_variant(how, **kw):
+    from mct_quantizers_amd import consumers
+    torch.manual_seed(0)
+    model = _Variant(how, **kw)
+    x = torch.randn(2, 16, 5, 7, generator=torch.Generator().manual_seed(9))
+    ref = model(x.clone())
+    gm, n = consumers.fuse_linear_consumers_fx(model, shared_holders=True)
+    joins = [m for m in gm.modules() if isinstance(m, consumers.QuantizedJoin)]
+    y = gm(x.clone())
+    assert torch.allclose(y, ref, rtol=1e-4, atol=1e-5 * float(ref.detach().abs().max())), how
+    return gm, n, joins
+
+
+def test_every_spelling_of_add_and_relu_is_absorbed():
+    for how in ("operator", "method", "functional", "iadd"):
+        gm, n, joins = _rewrite_variant(how)
+        assert n == 2 and len(joins) == 1 and (joins[0].relu, joins[0].has_residual, joins[0].want_float) == (True, True, False), how
+        assert _targets(gm) == ["c0", "h_join", "c1_qlinear", "c2_qlinear"], how
+        assert [t for t in _targets(gm, "call_function") if t is not operator.getitem] == [operator.add], how      # c1 + c2
+        assert not _targets(gm, "call_method"), how
+        # a single consumer behind the absorbed prologue is a join as well
+        gm, n, joins = _rewrite_variant(how, shared=False)
+        assert n == 1 and len(joins) == 1 and _targets(gm) == ["c0", "h_join", "c1_qlinear"], how
+
+
+def test_what_the_shared_holder_rewrite_leaves_alone():
+    from mct_quantizers_amd import consumers
+    # an add with alpha, an add of a tensor and a Python scalar: the ReLU is absorbed, the add stays where it is
+    for how, target in (("alpha", torch.add), ("scalar", operator.add)):
+        gm, n, joins = _rewrite_variant(how)
+        assert n == 2 and (joins[0].relu, joins[0].has_residual) == (True, False), how
+        assert target in _targets(gm, "call_function") and torch.relu not in _targets(gm, "call_function"), how
+    # a ReLU with a second user stays, and with it the add behind it
+    gm, n, joins = _rewrite_variant("relu twice")
+    assert n == 2 and (joins[0].relu, joins[0].has_residual) == (False, False)
+    assert torch.relu in _targets(gm, "call_function")
+    # an in-place ReLU whose input somebody else reads as well stays: absorbed, it would no longer rewrite that input
+    gm, n, joins = _rewrite_variant("inplace twice")
+    assert n == 2 and (joins[0].relu, joins[0].has_residual) == (False, False)
+    assert torch.nn.functional.relu in _targets(gm, "call_function")
+    gm, n, joins = _rewrite_variant("relu twice", shared=False)             # ... and a lone pair behind it is the pair rewrite's
+    assert n == 1 and not joins and _targets(gm) == ["c0", "c1_qlinear"]
+    # a shared holder none of whose users the consumer can take: the graph is what it was
+    torch.manual_seed(0)
+    model = _Variant("operator", taken=False)
+    before = consumers.fuse_linear_consumers_fx(model)[0]
+    gm, n = consumers.fuse_linear_consumers_fx(model, shared_holders=True, convolutions=True, depthwise=True, uniform_weights=True)
+    assert n == 0 and str(gm.graph) == str(before.graph) and _targets(gm) == ["c0", "h", "c1", "c2"]
+    # a holder switched to pass-through
+    model = _Variant("operator")
+    model.h.quantization_bypass = True
+    gm, n = consumers.fuse_linear_consumers_fx(model, shared_holders=True)
+    assert n == 0 and _targets(gm) == ["c0", "h", "c1", "c2"] and torch.relu in _targets(gm, "call_function")
+    with pytest.raises(TypeError):
+        consumers.QuantizedJoin(model.h)
+    with pytest.raises(TypeError):
+        consumers.QuantizedJoin(torch.nn.Identity())
+    # a join refuses a call that does not match how it was built
+    j = consumers.QuantizedJoin(_holder("relu"), has_residual=True)
+    with pytest.raises(RuntimeError):
+        j(torch.zeros(1, 16, 2, 2))
+    # the Sequential rewrite has no such switch
+    with pytest.raises(TypeError):
+        consumers.fuse_linear_consumers(torch.nn.Sequential(), shared_holders=True)
+
+
+def test_quantized_join_module_routes_on_cpu():
+    from mct_quantizers_amd import consumers
+    holder = _holder("relu")
+    form = consumers._activation_code_params(holder.activation_holder_quantizer)
+    g = torch.Generator().manual_seed(4)
+    x, r = torch.randn(2, 16, 5, 7, generator=g) * 3, torch.randn(2, 16, 5, 7, generator=g)
+    j = consumers.QuantizedJoin(holder, relu=True, has_residual=True)
+    want_y, want_c = composed(x, r, True, form)
+    for xx, rr in ((x, r), (x.contiguous(memory_format=torch.channels_last), r.contiguous(memory_format=torch.channels_last))):
+        y, codes = j(xx, rr)
+        assert bits_equal(y.numpy(), want_y.numpy()) and torch.equal(codes, want_c)
+        assert codes.shape == x.shape and codes.permute(0, 2, 3, 1).is_contiguous()      # NCHW-shaped, NHWC-stored
+    y, codes = consumers.QuantizedJoin(holder, relu=True, has_residual=True, want_float=False)(x, r)
+    assert y is None and torch.equal(codes, want_c)
+    x2 = torch.randn(3, 48, generator=g)
+    y, codes = consumers.QuantizedJoin(holder)(x2)
+    w = composed(x2, None, False, form)
+    assert bits_equal(y.numpy(), w[0].numpy()) and torch.equal(codes, w[1]) and codes.is_contiguous()
+    assert list(j.children()) == [holder]
+
+
+# ---- the C ABI without a GPU -----------------------------------------------------------------------------------------------
+
+def test_fq_join_argument_validation_needs_no_gpu():
+    import os
+    import re
+    from conftest import REPO
+    from mct_quantizers_amd.hip import build, native
+    build.build()                               # hipcc cross-compiles for gfx950 without a GPU
+    assert os.path.join(build.CSRC, "mctq_fq_join.hip") in build.SOURCES
+    lib = native.load()
+    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "mctq_hip.h")).read(), flags=re.S)
+    assert re.search(r"\bmctq_fq_join_f32\s*\(", header) and "mctq_fq_join_f32" in native.SIGNATURES
+    assert lib.mctq_abi_version() == 10 == native.ABI_VERSION
+    E, P, I8, U8 = native.MCTQ_E_ARG, 4096, native.CODE_I8, native.CODE_U8      # P: an aligned address that is never dereferenced
+    count = lib.mctq_launch_count()
+    valid = dict(x=P, r=P, relu=1, y=P, codes=P, cdt=U8, n=100, scale=0.5, zp=3, qmin=0, qmax=255)
+
+    def call(**over):
+        v = dict(valid, **over)
+        return lib.mctq_fq_join_f32(v["x"], v["r"], v["relu"], v["y"], v["codes"], v["cdt"], v["n"], v["scale"], v["zp"], v["qmin"],
+                                    v["qmax"], None)
+
+    def refused(message, **fault):
+        assert call(**fault) == E, fault
+        assert lib.mctq_last_error() == message, (fault, lib.mctq_last_error())
+
+    refused(b"n < 0", n=-1)
+    refused(b"x is NULL", x=None)
+    refused(b"neither y nor codes is given", y=None, codes=None)
+    for cdt in (-1, 2, 3, 77):                                             # the 4-bit code types among them
+        refused(b"bad code_dtype", cdt=cdt)
+    refused(b"clamp domain does not fit the code type", cdt=U8, qmax=256)
+    refused(b"clamp domain does not fit the code type", cdt=U8, qmin=-1)
+    refused(b"clamp domain does not fit the code type", cdt=I8, qmin=-129, qmax=127)
+    refused(b"clamp domain does not fit the code type", cdt=I8, qmin=-128, qmax=128)
+    refused(b"quant_min > quant_max", qmin=200, qmax=100)
+    refused(b"quant_min > quant_max", codes=None, qmin=200, qmax=100)
+    refused(b"clamp domain beyond 2^24 with a float32 output", codes=None, qmax=2 ** 24 + 1)
+    refused(b"clamp domain beyond 2^24 with a float32 output", codes=None, qmin=-2 ** 24 - 1)
+    for pointer, off in (("x", 4), ("r", 8), ("y", 4), ("codes", 1)):
+        refused(b"x, residual, y and codes must be 16-byte aligned", **{pointer: P + off})
+    refused(b"tensor too large for one launch", n=(2 ** 31) * 4096)
+    # an empty tensor: no launch, and nothing else is looked at
+    assert call(n=0) == 0 and call(n=0, x=None, r=None, y=None, codes=None) == 0
+    assert call(n=0, cdt=77) == 0 and call(n=0, qmin=5, qmax=1) == 0 and call(n=0, x=P + 4) == 0
+    assert lib.mctq_launch_count() == count                                # refused and empty calls launch nothing
