@@ -66,6 +66,8 @@ extern "C" {
  * the two pointwise convolutions of a MobileNet-style block); no existing signature or result changed. */
 /* v10 (additive, the version number stays): + mctq_fq_join_f32, the residual add, the ReLU and both outputs of a shared activation
  * holder (fake-quantized float32 and integer codes) in one pass; no existing signature or result changed. */
+/* v10 (additive, the version number stays): + mctq_fq_join_rc_f32, the join with its residual operand given as the int8 / uint8 codes
+ * of another join (identity branches that stay on codes); no existing signature or result changed. */
 #define MCTQ_ABI_VERSION 10
 #define MCTQ_E_ARG (-10001)
 
@@ -567,6 +569,22 @@ int mctq_qconv_dw_i8(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_p
 int mctq_fq_join_f32(const float* x, const float* residual /* NULL: none */, int32_t relu,
                      float* y /* NULL: no float32 output */, void* codes /* NULL: no codes */, int32_t code_dtype,
                      int64_t n, float scale, int32_t zero_point, int32_t quant_min, int32_t quant_max, void* stream);
+
+/*
+ * The same join with the residual given as integer codes (an identity branch that stays on codes: the codes another join wrote,
+ * with that join's scale and zero point):
+ *     r        = float(r_codes[i] - r_zero_point) * r_scale      one float32 rounding: the float32 value those codes stand for
+ *     v        = x[i] + r                                         a second rounding, as ATen's add of that float32 tensor
+ * and everything behind v as mctq_fq_join_f32.  r is bit for bit what mctq_fq_join_f32 (or mctq_fq_per_tensor_f32) writes as y
+ * next to those codes, so the result equals mctq_fq_join_f32 on that y.  r_codes: int8 (r_code_dtype MCTQ_CODE_I8) or uint8
+ * (MCTQ_CODE_U8), n of them in x's layout, a DEVICE pointer, 16-byte aligned: one 16-byte load per lane in place of four.
+ * MCTQ_E_ARG as mctq_fq_join_f32, and for: r_codes NULL; an r_code_dtype other than MCTQ_CODE_I8 / _U8; an r_zero_point that is
+ * no code of that type; an r_scale that is not finite and positive; r_codes not 16-byte aligned.  n == 0 returns 0 without a
+ * launch.  mctq_last_launch names the launch "fq_join", op e.g. "addc(u8) relu -> u8" (the float32 form says "add").
+ */
+int mctq_fq_join_rc_f32(const float* x, const void* r_codes, int32_t r_code_dtype, float r_scale, int32_t r_zero_point,
+                        int32_t relu, float* y /* NULL: no float32 output */, void* codes /* NULL: no codes */, int32_t code_dtype,
+                        int64_t n, float scale, int32_t zero_point, int32_t quant_min, int32_t quant_max, void* stream);
 
 /*
  * Integer consumer of the codes (extension; the reference has no counterpart): the product a wrapped

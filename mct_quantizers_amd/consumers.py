@@ -44,6 +44,12 @@ stay in float32, and the codes, for the consumers that replace the wrapped layer
 both operands once (13 bytes per element against 28 for add, ReLU, holder and codes as four passes); both outputs are bit for
 bit what the separate launches give.
 
+``fuse_linear_consumers_fx(..., shared_holders=True, stay_on_codes=True)`` then keeps the activations between those layers on
+codes: a ReLU, ReLU6 or Hardtanh between a consumer and a holder that only consumers read is a narrower clamp of the codes the
+consumer emits itself (``folded_clamp``: the code function is monotone, so clamping the value is clamping the code), and a
+residual join reads its identity operand as the codes of the join in front (``mctq_fq_join_rc_f32``: ``(code - zp) * scale`` is
+that join's float32 output bit for bit), which then no longer writes float32 -- 6 bytes per element instead of 13.
+
 CPU tensors run the same integer arithmetic with torch ops (host logic for tests, bit-identical to the kernel).
 """
 from typing import Optional
@@ -83,9 +89,46 @@ def _output_form(out_codes):
     """(tensor dtype, y_code_dtype, scale, zero_point, qmin, qmax) of the entry points whose ``y_code_dtype < 0`` means float32."""
     if out_codes is None:
         return torch.float32, -1, 1.0, 0, 0, 0
-    o_scale, o_zp, o_qmin, o_qmax = out_codes
+    o_scale, o_zp, o_qmin, o_qmax, lo, hi = _with_clamp(out_codes)
     tdt, ocode = ops._code_dtype(o_qmin, o_qmax)
-    return tdt, ocode, float(o_scale), int(o_zp), int(o_qmin), int(o_qmax)
+    return tdt, ocode, float(o_scale), int(o_zp), lo, hi
+
+
+def _with_clamp(out_codes):
+    """``out_codes`` as (scale, zero_point, qmin, qmax, lo, hi): the quantizer's own domain [qmin, qmax] decides the code TYPE
+    (a signed domain stays int8 whatever is folded into it), [lo, hi] within it is what the codes are clamped to -- the domain
+    itself for the four-tuple, narrower where a clamp activation was folded in (``folded_clamp``)."""
+    if len(out_codes) == 4:
+        return (*out_codes, int(out_codes[2]), int(out_codes[3]))
+    o_scale, o_zp, o_qmin, o_qmax, lo, hi = out_codes
+    if not o_qmin <= lo <= hi <= o_qmax:
+        raise ValueError(f"the narrowed clamp [{lo}, {hi}] does not lie inside the domain [{o_qmin}, {o_qmax}]")
+    return o_scale, o_zp, o_qmin, o_qmax, int(lo), int(hi)
+
+
+def _cpu_out_codes(y, out_codes):
+    """The CPU routes' output form: ``ops.fq_codes`` of the float32 result, clamped to [lo, hi], in the domain's code type."""
+    o_scale, o_zp, o_qmin, o_qmax, lo, hi = _with_clamp(out_codes)
+    return ops.fq_codes(y, None, None, None, lo, hi, o_scale, o_zp).to(ops._code_dtype(o_qmin, o_qmax)[0])
+
+
+def folded_clamp(form, a: float, b: float):
+    """[lo, hi]: the clamp of the codes of ``form = (scale, zero_point, qmin, qmax)`` that stands for ``clamp(v, a, b)`` in front
+    of the quantizer.  The code function c(v) = clamp(rint(v * inv) + zp, qmin, qmax) is monotone non-decreasing in v, so
+    c(min(max(v, a), b)) = min(max(c(v), c(a)), c(b)): lo = c(a), hi = c(b), computed here in the kernels' float32 arithmetic
+    (float32 ``1.0f / scale``, a float32 multiply, round-half-even, a float32 add of the zero point).  ``a = -inf`` / ``b = inf``
+    leave that side at the domain's end.  The one difference: a NaN stays a NaN through torch's clamp and then codes to qmin,
+    while the narrowed clamp gives lo -- a consumer's output is an exact integer sum times finite scales plus a bias, so it is
+    NaN only if a scale or a bias is."""
+    import numpy as np
+    scale, zp, qmin, qmax = form
+    if not a <= b:
+        raise ValueError(f"clamp range [{a}, {b}] is empty")
+    f32 = np.float32
+    with np.errstate(all="ignore"):
+        inv = f32(1.0) / f32(scale)
+        lo, hi = (np.minimum(np.maximum(np.rint(f32(v) * inv) + f32(zp), f32(qmin)), f32(qmax)) for v in (a, b))
+    return int(lo), int(hi)
 
 
 def codes_rowsum(a_codes: torch.Tensor, a_zero_point: int) -> torch.Tensor:
@@ -160,7 +203,9 @@ def qlinear_i8(a_codes: torch.Tensor, a_zero_point: int, a_scale: float, w_codes
                out_codes=None, w_zero_points: Optional[torch.Tensor] = None) -> torch.Tensor:
     """a_codes [M, K] int8/uint8, w_codes [N, K] int8 (zero point 0 unless ``w_zero_points`` is given) -> float32
     [M, N]; with ``out_codes = (scale, zero_point, qmin, qmax)`` the result leaves as the codes of that activation quantizer
-    (int8 / uint8 [M, N]), bit-identical to quantizing the float32 result with ``ops.fq_codes``.
+    (int8 / uint8 [M, N]), bit-identical to quantizing the float32 result with ``ops.fq_codes``.  Two more entries,
+    ``(..., lo, hi)`` with qmin <= lo <= hi <= qmax, clamp the codes to [lo, hi] instead (a clamp activation folded into the
+    codes, ``folded_clamp``); the code type stays that of [qmin, qmax].
     ``w_zero_points`` (int32 [N], each in [-128, 127]): the weights are ``w_codes[n][k] - w_zero_points[n]``; the row sums
     of the activation codes are computed first (``codes_rowsum``) and the product runs on ``mctq_qlinear_i8_zp``."""
     if a_codes.is_cuda:
@@ -177,10 +222,7 @@ def qlinear_i8(a_codes: torch.Tensor, a_zero_point: int, a_scale: float, w_codes
     y = acc.to(torch.float32) * (torch.tensor(a_scale, dtype=torch.float64).to(torch.float32) * w_scales)
     if bias is not None:
         y = y + bias
-    if out_codes is None:
-        return y
-    o_scale, o_zp, o_qmin, o_qmax = out_codes
-    return ops.fq_codes(y, None, None, None, o_qmin, o_qmax, o_scale, o_zp)
+    return y if out_codes is None else _cpu_out_codes(y, out_codes)
 
 
 def qconv_dw_i8(a_codes_nhwc: torch.Tensor, a_zero_point: int, a_scale: float, w_codes: torch.Tensor, w_scales: torch.Tensor,
@@ -245,10 +287,7 @@ def qconv_dw_i8(a_codes_nhwc: torch.Tensor, a_zero_point: int, a_scale: float, w
     y = acc.to(torch.float32) * (torch.tensor(a_scale, dtype=torch.float64).to(torch.float32) * w_scales)
     if bias is not None:
         y = y + bias
-    if out_codes is None:
-        return y
-    o_scale, o_zp, o_qmin, o_qmax = out_codes
-    return ops.fq_codes(y, None, None, None, o_qmin, o_qmax, o_scale, o_zp)
+    return y if out_codes is None else _cpu_out_codes(y, out_codes)
 
 
 def pack_w4(codes: torch.Tensor) -> torch.Tensor:
@@ -373,6 +412,10 @@ class QuantizedLinear(nn.Module):
         # chaining (fuse_linear_consumers(chain=True)): parameters of the activation quantizer that would quantize
         # this layer's output next; the output then leaves as that quantizer's codes
         self.emit_codes_for = None
+        # fuse_linear_consumers_fx(stay_on_codes=True): (lo, hi) inside emit_codes_for's domain, the clamp that stands for a
+        # ReLU / ReLU6 / Hardtanh between this layer and that quantizer (folded_clamp).  Kept apart from emit_codes_for: the
+        # code type is the domain's, not the narrowed clamp's.
+        self.emit_clamp = None
 
     @classmethod
     def from_wrapper(cls, wrapper: PytorchQuantizationWrapper, activation_quantizer) -> "QuantizedLinear":
@@ -388,6 +431,12 @@ class QuantizedLinear(nn.Module):
     def activation_code_params(self):
         """(scale, zero_point, qmin, qmax) of this layer's activation codes: what ``emit_codes_for`` of the layer in front takes."""
         return self._a_scale, self._a_zp, self._a_qmin, self._a_qmax
+
+    def _out_codes(self):
+        """``out_codes`` of the launch: None, ``emit_codes_for``, or that with ``emit_clamp`` behind it."""
+        if self.emit_codes_for is None or self.emit_clamp is None:
+            return self.emit_codes_for
+        return (*self.emit_codes_for, *self.emit_clamp)
 
     def _as_rows(self, t):
         """Codes or codebook indices shaped like the weight -> [O, K] in the order of the activation rows."""
@@ -465,13 +514,13 @@ class QuantizedLinear(nn.Module):
                 bias = bias.to(device=a_codes.device, dtype=torch.float32).contiguous()
         if self._w_codes4 is not None and a_codes.is_cuda and a_codes.shape[0] <= _W4_MAX_ROWS:
             y = qlinear_w4a8(a_codes, self._a_zp, self._a_scale, self._w_codes4, self._w_scales, self._w_rowsum, bias,
-                             self.emit_codes_for, self._w_zps)
+                             self._out_codes(), self._w_zps)
         elif self._w_idx4 is not None and a_codes.is_cuda and a_codes.shape[0] <= _LUT4_MAX_ROWS:
             y = qlinear_lut4a8(a_codes, self._a_zp, self._a_scale, self._w_idx4, self._lut16, self._w_scales,
-                               self._w_rowsum, bias, self.emit_codes_for)
+                               self._w_rowsum, bias, self._out_codes())
         else:
             y = qlinear_i8(a_codes, self._a_zp, self._a_scale, self._w_codes, self._w_scales, self._w_rowsum, bias,
-                           self.emit_codes_for, self._w_zps)
+                           self._out_codes(), self._w_zps)
         return y.reshape(*lead, self.out_features)
 
 
@@ -685,7 +734,7 @@ class QuantizedDepthwiseConv2d(QuantizedLinear):
             if bias.dtype != torch.float32 or bias.device != codes.device or not bias.is_contiguous():
                 bias = bias.to(device=codes.device, dtype=torch.float32).contiguous()
         y = qconv_dw_i8(codes, self._a_zp, self._a_scale, self._w_codes, self._w_scales, bias, self.kernel_size, self.stride,
-                        self.padding, self.dilation, self.emit_codes_for, self._w_zps)
+                        self.padding, self.dilation, self._out_codes(), self._w_zps)
         return y.permute(0, 3, 1, 2)
 
 
@@ -738,9 +787,13 @@ class QuantizedJoin(nn.Module):
     A 4-D input that is NCHW-contiguous and not channels-last (a network's first holder: every consumer emits channels-last)
     takes the routes that were there before: the prologue by torch ops, the holder's own call, ``ops.fq_codes_nhwc``.
 
-    The holder stays a submodule: its quantizer is the one in use, whose parameters are read when the join is built."""
+    The holder stays a submodule: its quantizer is the one in use, whose parameters are read when the join is built.
 
-    def __init__(self, holder, relu: bool = False, has_residual: bool = False, want_float: bool = True):
+    ``residual_codes=(scale, zero_point)`` (with ``has_residual``): the second operand of ``forward`` is then an int8 / uint8
+    tensor, the codes of another join with that scale and zero point (an identity branch that stays on codes), standing for
+    the float32 tensor ``(codes - zero_point) * scale`` that join would have written: ``mctq_fq_join_rc_f32``, the same bits."""
+
+    def __init__(self, holder, relu: bool = False, has_residual: bool = False, want_float: bool = True, residual_codes=None):
         super().__init__()
         if not _plain_holder(holder):
             raise TypeError("QuantizedJoin takes a PytorchActivationQuantizationHolder that quantizes")
@@ -748,19 +801,34 @@ class QuantizedJoin(nn.Module):
         self.relu, self.has_residual, self.want_float = bool(relu), bool(has_residual), bool(want_float)
         self._a_scale, self._a_zp, self._a_qmin, self._a_qmax = _activation_code_params(holder.activation_holder_quantizer)
         ops._code_dtype(self._a_qmin, self._a_qmax)            # (raises for a domain that is no 8-bit code)
+        self.residual_codes = None
+        if residual_codes is not None:
+            if not self.has_residual:
+                raise ValueError("residual_codes describes the residual operand: it needs has_residual=True")
+            r_scale, r_zp = residual_codes
+            self.residual_codes = (float(r_scale), int(r_zp))
 
     def forward(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None):
         if (residual is not None) != self.has_residual:
             raise RuntimeError(f"this join was built {'with' if self.has_residual else 'without'} a residual operand")
         form = (self._a_scale, self._a_zp, self._a_qmin, self._a_qmax)
+        r_codes = None
+        if residual is not None and (residual.dtype in (torch.int8, torch.uint8)) != (self.residual_codes is not None):
+            raise TypeError(f"this join was built for a residual operand {'as codes' if self.residual_codes else 'in float32'}, "
+                            f"got {residual.dtype}")
+        if self.residual_codes is not None:
+            r_codes, residual = (residual, *self.residual_codes), None
         if x.dim() == 4 and x.is_contiguous() and not x.is_contiguous(memory_format=torch.channels_last):
+            if r_codes is not None:
+                residual = ops.dequantize_codes(*r_codes)
             v = x if residual is None else x + residual
             if self.relu:
                 v = torch.relu(v)
             y = self.holder(v) if self.want_float else None
             codes = ops.fq_codes_nhwc(v, self._a_qmin, self._a_qmax, self._a_scale, self._a_zp)
             return y, codes.permute(0, 3, 1, 2)
-        return ops.fq_join(x, *form, residual=residual, relu=self.relu, want_float=self.want_float, want_codes=True)
+        return ops.fq_join(x, *form, residual=residual, relu=self.relu, want_float=self.want_float, want_codes=True,
+                           residual_codes=r_codes)
 
 
 def _relu_input(node, mods):
@@ -855,6 +923,138 @@ def _join_shared_holders(gm, mods, consumer_for) -> int:
     return replaced
 
 
+def _clamp_range(node, mods):
+    """(a, b) if ``node`` is a clamp activation of one tensor that ``folded_clamp`` can fold -- a ReLU (as ``_relu_input``),
+    ``nn.ReLU6`` / ``F.relu6``, ``nn.Hardtanh`` / ``F.hardtanh`` with finite ``min_val <= max_val`` -- else None.  In-place forms
+    only where nobody else looks at the input."""
+    import math
+    from torch.fx import Node
+    F = torch.nn.functional
+    if _relu_input(node, mods) is not None:
+        return 0.0, math.inf
+    if not node.args or not isinstance(node.args[0], Node):
+        return None
+    rng, inplace = None, False
+    if node.op == "call_module" and len(node.args) == 1 and not node.kwargs:
+        m = mods.get(node.target)
+        if type(m) is nn.ReLU6:
+            rng, inplace = (0.0, 6.0), m.inplace
+        elif type(m) is nn.Hardtanh:
+            rng, inplace = (m.min_val, m.max_val), m.inplace
+    elif node.op == "call_function" and node.target is F.relu6:
+        if len(node.args) == 1 and not set(node.kwargs) - {"inplace"}:
+            rng, inplace = (0.0, 6.0), node.kwargs.get("inplace", False)
+    elif node.op == "call_function" and node.target is F.hardtanh:
+        names = ("min_val", "max_val", "inplace")
+        if len(node.args) <= 4 and not set(node.kwargs) - set(names[len(node.args) - 1:]):
+            given = dict(zip(names, node.args[1:]), **node.kwargs)
+            rng, inplace = (given.get("min_val", -1.0), given.get("max_val", 1.0)), given.get("inplace", False)
+    if rng is None or not all(isinstance(v, (int, float)) and math.isfinite(v) for v in rng) or not rng[0] <= rng[1]:
+        return None
+    if not isinstance(inplace, bool) or (inplace and len(node.args[0].users) != 1):
+        return None
+    return float(rng[0]), float(rng[1])
+
+
+def _identities_as_codes(gm, mods) -> int:
+    """``fuse_linear_consumers_fx(stay_on_codes=True)``, the identity branches: a join with a residual one of whose add operands
+    is the float32 output of another join takes that join's codes in its place (``QuantizedJoin(residual_codes=...)``; IEEE
+    addition is commutative, so either operand may move to the second place; where both qualify, one is converted), and a join
+    whose float32 output then has no users stops writing it.  Returns the number of joins converted."""
+    import operator
+
+    def pick(node, index):
+        """(the join node, its module) if ``node`` is ``join(...)[index]``."""
+        if node.op == "call_function" and node.target is operator.getitem and len(node.args) == 2 and node.args[1] == index:
+            src = node.args[0]
+            m = mods.get(src.target) if src.op == "call_module" else None
+            if isinstance(m, QuantizedJoin):
+                return src, m
+        return None
+
+    converted = 0
+    for node in list(gm.graph.nodes):
+        join = mods.get(node.target) if node.op == "call_module" else None
+        if not isinstance(join, QuantizedJoin) or not join.has_residual or join.residual_codes is not None or len(node.args) != 2:
+            continue
+        for i in (1, 0):
+            as_float = node.args[i]
+            up = pick(as_float, 0)
+            if up is None:
+                continue
+            up_node, up_join = up
+            as_codes = next((u for u in up_node.users if pick(u, 1) is not None), None)
+            if as_codes is None:
+                with gm.graph.inserting_after(up_node):
+                    as_codes = gm.graph.call_function(operator.getitem, (up_node, 1))
+            new = QuantizedJoin(join.holder, relu=join.relu, has_residual=True, want_float=join.want_float,
+                                residual_codes=(up_join._a_scale, up_join._a_zp))
+            setattr(gm, node.target, new)                # (a join's name has no dots: _join_shared_holders made it)
+            mods[node.target] = new
+            node.args = (node.args[1 - i], as_codes)
+            if not as_float.users:
+                gm.graph.erase_node(as_float)
+                up_join.want_float = False
+            converted += 1
+            break
+    return converted
+
+
+def _fold_clamps_into_producers(gm, mods) -> int:
+    """``fuse_linear_consumers_fx(stay_on_codes=True)``, the activations between consumers: where a consumer's only user leads
+    -- through at most one clamp activation that feeds nothing else (``_clamp_range``; the ReLU a join absorbed counts) -- to a
+    holder all of whose users are integer consumers, the consumer emits that holder's codes itself, the activation folded into
+    their clamp (``folded_clamp``), and the consumers behind take them directly.  The holder is either already inside the one
+    consumer behind it (the pair rewrite) or a residual-free QuantizedJoin that writes no float32 output.  Returns the number of
+    producers that now emit codes."""
+    import math
+    import operator
+    folded = 0
+    for node in list(gm.graph.nodes):
+        producer = mods.get(node.target) if node.op == "call_module" else None
+        if not isinstance(producer, QuantizedLinear) or producer.emit_codes_for is not None or len(node.users) != 1:
+            continue
+        nxt, act, rng = next(iter(node.users)), None, (-math.inf, math.inf)
+        if _clamp_range(nxt, mods) is not None and len(nxt.users) == 1:
+            act, rng = nxt, _clamp_range(nxt, mods)
+            nxt = next(iter(nxt.users))
+        if nxt.op != "call_module" or nxt.kwargs or nxt.args != (act or node,):
+            continue
+        behind, gone = mods.get(nxt.target), [nxt]
+        if isinstance(behind, QuantizedLinear):
+            form, readers, gone = behind.activation_code_params(), [nxt], []
+        elif isinstance(behind, QuantizedJoin) and not behind.has_residual and not behind.want_float:
+            if behind.relu:
+                if act is not None:
+                    continue                             # two activations in a row: left alone
+                rng = (0.0, math.inf)
+            picks = list(nxt.users)
+            if len(picks) != 1 or picks[0].target is not operator.getitem or picks[0].args != (nxt, 1):
+                continue
+            form, readers = (behind._a_scale, behind._a_zp, behind._a_qmin, behind._a_qmax), list(picks[0].users)
+            if not readers or not all(r.op == "call_module" and isinstance(mods.get(r.target), QuantizedLinear)
+                                      and r.args == (picks[0],) and not r.kwargs for r in readers):
+                continue
+            gone = [picks[0], nxt]
+        else:
+            continue
+        try:
+            ops._code_dtype(form[2], form[3])
+            clamp = folded_clamp(form, *rng)
+        except ValueError:
+            continue
+        producer.emit_codes_for, producer.emit_clamp = form, (None if clamp == (form[2], form[3]) else clamp)
+        for r in readers:
+            r.args = (node,)
+        for g in gone + ([act] if act is not None else []):
+            gm.graph.erase_node(g)
+        if gone:
+            gm.delete_submodule(nxt.target)
+            mods.pop(nxt.target, None)
+        folded += 1
+    return folded
+
+
 def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights: bool = False,
                           convolutions: bool = False, depthwise: bool = False) -> int:
     """In every ``nn.Sequential`` of ``model``: an activation holder directly followed by a wrapped ``nn.Linear`` with
@@ -902,7 +1102,8 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
 
 
 def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weights: bool = False,
-                             convolutions: bool = False, depthwise: bool = False, shared_holders: bool = False):
+                             convolutions: bool = False, depthwise: bool = False, shared_holders: bool = False,
+                             stay_on_codes: bool = False):
     """The same rewrite on an arbitrary module graph (MCT-exported models are not ``nn.Sequential``): traces ``model``
     with torch.fx keeping wrappers and holders as leaves, and wherever an activation holder's ONLY consumer is a
     wrapped ``nn.Linear`` the integer consumer can take (symmetric, power-of-two or LUT weights, and with
@@ -920,8 +1121,18 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
     above; every other one becomes a QuantizedJoin node -- one launch for add, ReLU, the holder and the codes -- whose
     float32 output replaces the holder for the users that stay (it is not computed when there are none) and whose codes feed
     the consumers that replace the wrapped layers.  With residual networks this is what lets the first convolution of a block
-    and its downsample branch run on codes.  Nothing chains across a join."""
+    and its downsample branch run on codes.  Nothing chains across a join.
+
+    ``stay_on_codes=True`` (needs ``shared_holders=True``; ValueError otherwise) keeps the activations between those layers on
+    codes, in two exact steps.  A ReLU, ReLU6 or Hardtanh between a consumer and a holder that only consumers read is folded into
+    the clamp of the codes the consumer then emits itself (``folded_clamp``; the activation and the holder or its ReLU-only
+    join leave the graph).  And a residual join whose identity operand is another join's float32 output reads that join's codes
+    instead (``mctq_fq_join_rc_f32``), so that the float32 tensor between two blocks is neither written nor read.  The result
+    is bit for bit that of ``shared_holders=True`` alone, except that a NaN in a consumer's output (only from a NaN scale or
+    bias) codes to the folded clamp's lower end, not the domain's."""
     import torch.fx as fx
+    if stay_on_codes and not shared_holders:
+        raise ValueError("stay_on_codes=True needs shared_holders=True")
 
     class _Tracer(fx.Tracer):
         def is_leaf_module(self, m, qualname):
@@ -963,6 +1174,9 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
                 nxt = mods.get(user.target) if user.op == "call_module" else None
                 if isinstance(nxt, QuantizedLinear) and user.args == (node,):
                     mods[node.target].emit_codes_for = nxt.activation_code_params()
+    if stay_on_codes:
+        _identities_as_codes(gm, mods)
+        _fold_clamps_into_producers(gm, mods)
     gm.graph.lint()
     gm.recompile()
     return gm, replaced

@@ -13,6 +13,11 @@
 // A lane owns 16 consecutive elements: four 16-byte loads per input, all issued before the arithmetic, four 16-byte stores
 // of float32 and one 16-byte store of codes.  The last n % 16 elements are one more lane's scalar loop.  Plain (cached)
 // loads and stores: a product reads the outputs next.
+//
+// The residual may also arrive as the int8 / uint8 codes of another join (mctq_fq_join_rc_f32: an identity branch that stays on
+// codes), with that join's scale and zero point: r = fma(float(code - r_zero_point), r_scale, +0) is the float32 value that
+// join would have written (AffineOp::apply's last step), then v = x + r as above.  One 16-byte load of codes per lane stands for
+// the four of float32: 6 bytes per element with codes out alone, against 13.
 #include "mctq_consumer.hpp"
 
 namespace mctq {
@@ -26,7 +31,21 @@ struct JoinArgs {
   AffineOp op;                                     // the float32 output's clamp domain (scales / zps unused: per tensor)
   AffineOp::Param p;
   int32_t relu;
+  // the residual as codes (RES == 2): the bytes are read as unsigned after ``^ rc_flip`` (0x80 per byte for int8 codes, which
+  // maps code c to c + 128), and rc_zb is the zero point with the same bias -- float(byte) - rc_zb == float(code - r_zero_point)
+  const uint8_t* rcodes;
+  uint32_t rc_flip;
+  float rc_zb, rc_scale;
 };
+
+// the float32 value of one residual code (b: the flipped byte as a float, exact).  The product is a float32 VALUE before the
+// add: without the opaque asm the compiler contracts q * s + x into one v_fma_f32 with a single rounding, where the float32
+// tensor this stands for was rounded once as a product and the add rounds again.
+__device__ __forceinline__ float join_residual(float b, const JoinArgs& a) {
+  float r = __builtin_fmaf(b - a.rc_zb, a.rc_scale, 0.0f);
+  asm("" : "+v"(r));
+  return r;
+}
 
 // the code of v in the form of the float32 output's own parameters (one reciprocal, one set of bounds for both outputs)
 __device__ __forceinline__ int join_code(float v, const JoinArgs& a) {
@@ -35,7 +54,8 @@ __device__ __forceinline__ int join_code(float v, const JoinArgs& a) {
   return ql_code(v, o);
 }
 
-template <bool RES, bool WY, bool WC>
+// RES: 0 no residual, 1 a float32 residual, 2 a residual as codes
+template <int RES, bool WY, bool WC>
 __global__ __launch_bounds__(kThreads) void fq_join_kernel(JoinArgs a) {
   const int64_t g = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   const NoBook book;
@@ -43,19 +63,22 @@ __global__ __launch_bounds__(kThreads) void fq_join_kernel(JoinArgs a) {
     const f32x4* __restrict__ xs = reinterpret_cast<const f32x4*>(a.x) + g * 4;
     const f32x4* __restrict__ rs = reinterpret_cast<const f32x4*>(a.residual) + g * 4;
     f32x4 xv[4], rv[4];
+    u32x4 rc;
 #pragma unroll
     for (int q = 0; q < 4; ++q) xv[q] = xs[q];
-    if constexpr (RES) {
+    if constexpr (RES == 1) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) rv[q] = rs[q];
     }
+    if constexpr (RES == 2) rc = reinterpret_cast<const u32x4*>(a.rcodes)[g];
     float v[16];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         float e = xv[q][j];
-        if constexpr (RES) e = e + rv[q][j];
+        if constexpr (RES == 1) e = e + rv[q][j];
+        if constexpr (RES == 2) e = e + join_residual((float)(((rc[q] ^ a.rc_flip) >> (8 * j)) & 0xffu), a);
         if (a.relu) e = e < 0.0f ? 0.0f : e;
         v[4 * q + j] = e;
       }
@@ -84,7 +107,8 @@ __global__ __launch_bounds__(kThreads) void fq_join_kernel(JoinArgs a) {
   } else if (g == a.chunks) {                      // the tail, n % 16 elements (the launcher adds this lane only when there is one)
     for (int64_t i = a.chunks * 16; i < a.n; ++i) {
       float e = a.x[i];
-      if constexpr (RES) e = e + a.residual[i];
+      if constexpr (RES == 1) e = e + a.residual[i];
+      if constexpr (RES == 2) e = e + join_residual((float)((a.rcodes[i] ^ a.rc_flip) & 0xffu), a);
       if (a.relu) e = e < 0.0f ? 0.0f : e;
       if constexpr (WY) a.y[i] = a.op.apply(e, a.p, book);
       if constexpr (WC) a.codes[i] = (uint8_t)join_code(e, a);
@@ -92,7 +116,7 @@ __global__ __launch_bounds__(kThreads) void fq_join_kernel(JoinArgs a) {
   }
 }
 
-template <bool RES>
+template <int RES>
 static void launch_fq_join(const JoinArgs& a, unsigned blocks, hipStream_t stream) {
   if (a.y && a.codes) hipLaunchKernelGGL((fq_join_kernel<RES, true, true>), dim3(blocks), dim3(kThreads), 0, stream, a);
   else if (a.y) hipLaunchKernelGGL((fq_join_kernel<RES, true, false>), dim3(blocks), dim3(kThreads), 0, stream, a);
@@ -103,10 +127,10 @@ static void launch_fq_join(const JoinArgs& a, unsigned blocks, hipStream_t strea
 
 using namespace mctq;
 
-extern "C" {
-
-int mctq_fq_join_f32(const float* x, const float* residual, int32_t relu, float* y, void* codes, int32_t code_dtype,
-                     int64_t n, float scale, int32_t zero_point, int32_t quant_min, int32_t quant_max, void* stream) {
+// Both entry points: ``residual`` (float32) or ``r_codes`` (with its type, scale and zero point, checked by the caller), or neither.
+static int fq_join_entry(const char* entry, const float* x, const float* residual, const void* r_codes, int32_t r_code_dtype,
+                         float r_scale, int32_t r_zero_point, int32_t relu, float* y, void* codes, int32_t code_dtype, int64_t n,
+                         float scale, int32_t zero_point, int32_t quant_min, int32_t quant_max, void* stream) {
   if (n < 0) return fail_arg("n < 0");
   if (n == 0) return 0;
   if (!x) return fail_arg("x is NULL");
@@ -119,6 +143,7 @@ int mctq_fq_join_f32(const float* x, const float* residual, int32_t relu, float*
   if (y && (quant_min < -(1 << 24) || quant_max > (1 << 24))) return fail_arg("clamp domain beyond 2^24 with a float32 output");
   if ((((uintptr_t)x | (uintptr_t)residual | (uintptr_t)y | (uintptr_t)codes) & 15u) != 0)
     return fail_arg("x, residual, y and codes must be 16-byte aligned");
+  if (((uintptr_t)r_codes & 15u) != 0) return fail_arg("r_codes must be 16-byte aligned");
   JoinArgs a;
   a.chunks = n / 16;
   const int64_t lanes = a.chunks + (n % 16 != 0 ? 1 : 0);
@@ -129,16 +154,45 @@ int mctq_fq_join_f32(const float* x, const float* residual, int32_t relu, float*
   a.op.lo = (float)quant_min; a.op.hi = (float)quant_max;
   a.p = AffineOp::make(scale, zero_point);          // inv = 1.0f / scale on the host, as both launches this one stands for
   a.relu = relu != 0;
+  const bool r_signed = r_code_dtype == MCTQ_CODE_I8;
+  a.rcodes = static_cast<const uint8_t*>(r_codes);
+  a.rc_flip = r_signed ? 0x80808080u : 0u;
+  a.rc_zb = (float)(r_zero_point + (r_signed ? 128 : 0));
+  a.rc_scale = r_scale;
   const hipStream_t s = (hipStream_t)stream;
-  if (residual) launch_fq_join<true>(a, (unsigned)blocks, s); else launch_fq_join<false>(a, (unsigned)blocks, s);
-  static thread_local char op_text[40];
-  snprintf(op_text, sizeof(op_text), "%s%s-> %s%s%s", residual ? "add " : "", a.relu ? "relu " : "", y ? "f32" : "",
-           y && codes ? " + " : "", !codes ? "" : (code_dtype == MCTQ_CODE_I8 ? "i8" : "u8"));
+  if (r_codes) launch_fq_join<2>(a, (unsigned)blocks, s);
+  else if (residual) launch_fq_join<1>(a, (unsigned)blocks, s);
+  else launch_fq_join<0>(a, (unsigned)blocks, s);
+  static thread_local char op_text[48];
+  snprintf(op_text, sizeof(op_text), "%s%s-> %s%s%s", r_codes ? (r_signed ? "addc(i8) " : "addc(u8) ") : residual ? "add " : "",
+           a.relu ? "relu " : "", y ? "f32" : "", y && codes ? " + " : "", !codes ? "" : (code_dtype == MCTQ_CODE_I8 ? "i8" : "u8"));
   g_note.shape = "fq_join"; g_note.op = op_text;
   g_note.unroll = 4; g_note.nt = 0;
-  g_note.in_bytes = 4; g_note.out_bytes = (y ? 4 : 0) + (codes ? 1 : 0); ++g_note.count;
+  g_note.in_bytes = r_codes ? 5 : 4; g_note.out_bytes = (y ? 4 : 0) + (codes ? 1 : 0); ++g_note.count;
   if (g_launch_log) log_launch();
-  return check_launch("mctq_fq_join_f32");
+  return check_launch(entry);
+}
+
+extern "C" {
+
+int mctq_fq_join_f32(const float* x, const float* residual, int32_t relu, float* y, void* codes, int32_t code_dtype,
+                     int64_t n, float scale, int32_t zero_point, int32_t quant_min, int32_t quant_max, void* stream) {
+  return fq_join_entry("mctq_fq_join_f32", x, residual, nullptr, 0, 0.0f, 0, relu, y, codes, code_dtype, n, scale, zero_point,
+                       quant_min, quant_max, stream);
+}
+
+int mctq_fq_join_rc_f32(const float* x, const void* r_codes, int32_t r_code_dtype, float r_scale, int32_t r_zero_point,
+                        int32_t relu, float* y, void* codes, int32_t code_dtype, int64_t n, float scale, int32_t zero_point,
+                        int32_t quant_min, int32_t quant_max, void* stream) {
+  if (n < 0) return fail_arg("n < 0");
+  if (n == 0) return 0;
+  if (!r_codes) return fail_arg("r_codes is NULL");
+  if (r_code_dtype != MCTQ_CODE_I8 && r_code_dtype != MCTQ_CODE_U8) return fail_arg("bad r_code_dtype");
+  if (r_code_dtype == MCTQ_CODE_I8 ? (r_zero_point < -128 || r_zero_point > 127) : (r_zero_point < 0 || r_zero_point > 255))
+    return fail_arg("r_zero_point is no code of the residual's type");
+  if (!(r_scale > 0.0f) || !__builtin_isfinite(r_scale)) return fail_arg("r_scale must be finite and positive");
+  return fq_join_entry("mctq_fq_join_rc_f32", x, nullptr, r_codes, r_code_dtype, r_scale, r_zero_point, relu, y, codes,
+                       code_dtype, n, scale, zero_point, quant_min, quant_max, stream);
 }
 
 }  // extern "C"

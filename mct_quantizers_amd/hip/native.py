@@ -140,6 +140,10 @@ SIGNATURES = {
     "mctq_fq_join_f32": (ctypes.c_int, [_c_f32p, _c_f32p, ctypes.c_int32, _c_f32p, ctypes.c_void_p, ctypes.c_int32,   # x, residual, relu, y, codes, code_dtype
                                         ctypes.c_int64, ctypes.c_float, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                         ctypes.c_void_p]),                                                            # n, scale, zero_point, qmin, qmax, stream
+    "mctq_fq_join_rc_f32": (ctypes.c_int, [_c_f32p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_int32,             # x, r_codes, r_code_dtype, r_scale, r_zero_point
+                                           ctypes.c_int32, _c_f32p, ctypes.c_void_p, ctypes.c_int32,                              # relu, y, codes, code_dtype
+                                           ctypes.c_int64, ctypes.c_float, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                           ctypes.c_void_p]),                                                                     # n, scale, zero_point, qmin, qmax, stream
     "mctq_lut_table_entries": (ctypes.c_int32, [ctypes.c_float, ctypes.c_float]),
     "mctq_lut_build_table": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_float,
                                             ctypes.c_float, ctypes.c_void_p]),

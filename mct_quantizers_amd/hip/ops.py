@@ -580,8 +580,16 @@ def fq_codes_nhwc(x, qmin: int, qmax: int, scale: float, zero_point: int):
     return codes.permute(0, 2, 3, 1).contiguous()          # a no-op view + check for channels-last storage
 
 
+def dequantize_codes(codes, scale: float, zero_point: int):
+    """``(codes - zero_point) * scale`` in float32 with one rounding: bit for bit the fake-quantized tensor the int8 / uint8
+    ``codes`` were written next to (``fq_join``, ``fq_codes``); torch ops on the codes' device."""
+    if codes.dtype not in (torch.int8, torch.uint8):
+        raise TypeError(f"dequantize_codes takes int8 / uint8 codes, got {codes.dtype}")
+    return (codes.to(torch.int32) - int(zero_point)).to(torch.float32) * torch.tensor(scale, dtype=torch.float64).to(torch.float32)
+
+
 def fq_join(x, scale: float, zero_point: int, qmin: int, qmax: int, residual=None, relu: bool = False,
-            want_float: bool = True, want_codes: bool = True):
+            want_float: bool = True, want_codes: bool = True, residual_codes=None):
     """The prologue and both outputs of an activation holder that several layers share (extension, not in the reference):
     with ``v = x`` (``+ residual``; then ``relu(v)``), returns ``(y, codes)`` where ``y = fq_per_tensor(v, ...)`` is the
     fake-quantized float32 tensor and ``codes = fq_codes(v, ...)`` its int8 / uint8 codes, ``(codes - zero_point) * scale ==
@@ -591,9 +599,28 @@ def fq_join(x, scale: float, zero_point: int, qmin: int, qmax: int, residual=Non
     Dense float32 GPU tensors (``residual`` with x's shape, strides and dtype) run ``mctq_fq_join_f32``: one launch that
     reads x and residual once and writes both outputs.  Everything else -- CPU tensors, other dtypes, a broadcasting or
     differently strided residual, a non-dense or misaligned x, clamp domains beyond 2^24 -- composes the same result from
-    torch's add and relu, ``fq_per_tensor`` and ``fq_codes``.  No backward, no ``torch.compile`` op."""
+    torch's add and relu, ``fq_per_tensor`` and ``fq_codes``.  No backward, no ``torch.compile`` op.
+
+    ``residual_codes = (codes, scale, zero_point)`` instead of ``residual``: the residual operand as the int8 / uint8 codes of
+    another quantizer (an identity branch that stays on codes), standing for ``dequantize_codes(codes, scale, zero_point)`` --
+    bit for bit the float32 tensor a join writes next to those codes, so the result is that of ``residual=`` that tensor.
+    Dense float32 GPU x with codes of x's shape and strides, both 16-byte aligned, run ``mctq_fq_join_rc_f32``: one launch that
+    reads 1 byte per residual element instead of 4.  Everything else dequantizes the codes with torch ops and goes on as above."""
     if not want_float and not want_codes:
         raise ValueError("fq_join: at least one of want_float / want_codes")
+    r_codes = None
+    if residual_codes is not None:
+        if residual is not None:
+            raise ValueError("fq_join: residual and residual_codes exclude each other")
+        r_codes, r_scale, r_zp = residual_codes
+        if not isinstance(r_codes, torch.Tensor) or r_codes.dtype not in (torch.int8, torch.uint8):
+            raise TypeError("fq_join: residual_codes takes an int8 / uint8 tensor")
+        r_scale, r_zp = float(r_scale), int(r_zp)
+        r_lo, r_hi = (0, 255) if r_codes.dtype == torch.uint8 else (-128, 127)
+        if not r_lo <= r_zp <= r_hi:
+            raise ValueError(f"fq_join: the residual's zero point {r_zp} is no {r_codes.dtype} code")
+        if not 0.0 < r_scale < float("inf"):
+            raise ValueError("fq_join: the residual's scale must be finite and positive")
     tdt = code = None
     if want_codes:
         tdt, code = _code_dtype(qmin, qmax)
@@ -602,6 +629,12 @@ def fq_join(x, scale: float, zero_point: int, qmin: int, qmax: int, residual=Non
     if direct and residual is not None:
         direct = (_is_real(residual) and residual.device == x.device and residual.dtype == x.dtype
                   and residual.shape == x.shape and residual.stride() == x.stride() and residual.data_ptr() % 16 == 0)
+    if direct and r_codes is not None:
+        direct = (_is_real(r_codes) and r_codes.device == x.device and r_codes.shape == x.shape
+                  and r_codes.stride() == x.stride() and r_codes.data_ptr() % 16 == 0)
+    if not direct and r_codes is not None:
+        with torch.no_grad():
+            residual = dequantize_codes(r_codes, r_scale, r_zp)
     if not direct:
         if _is_real(x) and x.device.type == "cpu":
             _cpu_route_allowed()
@@ -619,12 +652,20 @@ def fq_join(x, scale: float, zero_point: int, qmin: int, qmax: int, residual=Non
     lib = native.load()
     y = torch.empty_like(x) if want_float else None          # preserve_format: a dense x keeps its strides
     codes = torch.empty_like(x, dtype=tdt) if want_codes else None
+    outputs = (None if y is None else y.data_ptr(), None if codes is None else codes.data_ptr(), code or 0, x.numel(),
+               float(scale), int(zero_point), int(qmin), int(qmax))
     with _maybe_on_device(x):
-        rc = _launch(lib.mctq_fq_join_f32, x.data_ptr(), None if residual is None else residual.data_ptr(), int(bool(relu)),
-                     None if y is None else y.data_ptr(), None if codes is None else codes.data_ptr(), code or 0, x.numel(),
-                     float(scale), int(zero_point), int(qmin), int(qmax), _stream(x))
+        if r_codes is not None:
+            name = "mctq_fq_join_rc_f32"
+            rc = _launch(lib.mctq_fq_join_rc_f32, x.data_ptr(), r_codes.data_ptr(),
+                         native.CODE_U8 if r_codes.dtype == torch.uint8 else native.CODE_I8, r_scale, r_zp, int(bool(relu)),
+                         *outputs, _stream(x))
+        else:
+            name = "mctq_fq_join_f32"
+            rc = _launch(lib.mctq_fq_join_f32, x.data_ptr(), None if residual is None else residual.data_ptr(), int(bool(relu)),
+                         *outputs, _stream(x))
     if rc:
-        native.check(rc, "mctq_fq_join_f32")
+        native.check(rc, name)
     return y, codes
 
 
