@@ -50,8 +50,15 @@ consumer emits itself (``folded_clamp``: the code function is monotone, so clamp
 residual join reads its identity operand as the codes of the join in front (``mctq_fq_join_rc_f32``: ``(code - zp) * scale`` is
 that join's float32 output bit for bit), which then no longer writes float32 -- 6 bytes per element instead of 13.
 
+The four modules derive from ``IntegerConsumer``, which owns what they share: the checks of the quantizers and of the float32
+weight and bias, the cache of the weight's codes, the step from ``forward``'s input to activation codes, ``from_wrapper`` and
+the ``emit_codes_for`` / ``emit_clamp`` output form.  ``QuantizedLinear`` is the product over ``[O, K]`` rows; ``QuantizedConv1x1``
+and ``QuantizedConv2d`` are that product and derive from it; ``QuantizedDepthwiseConv2d`` is not and derives from
+``IntegerConsumer`` directly.  "Any integer consumer" in the graph rewrites is ``isinstance(m, IntegerConsumer)``.
+
 CPU tensors run the same integer arithmetic with torch ops (host logic for tests, bit-identical to the kernel).
 """
+import math
 from typing import Optional
 
 import torch
@@ -112,6 +119,15 @@ def _cpu_out_codes(y, out_codes):
     return ops.fq_codes(y, None, None, None, lo, hi, o_scale, o_zp).to(ops._code_dtype(o_qmin, o_qmax)[0])
 
 
+def _cpu_epilogue(acc, a_scale, w_scales, bias, out_codes):
+    """The CPU routes' epilogue, the kernels' own: the int32 sums ``acc`` (output channels last) times ``a_scale`` (rounded to
+    float32 first) times the channel's weight scale, plus the bias; float32, or the codes of ``out_codes``."""
+    y = acc.to(torch.float32) * (torch.tensor(a_scale, dtype=torch.float64).to(torch.float32) * w_scales)
+    if bias is not None:
+        y = y + bias
+    return y if out_codes is None else _cpu_out_codes(y, out_codes)
+
+
 def folded_clamp(form, a: float, b: float):
     """[lo, hi]: the clamp of the codes of ``form = (scale, zero_point, qmin, qmax)`` that stands for ``clamp(v, a, b)`` in front
     of the quantizer.  The code function c(v) = clamp(rint(v * inv) + zp, qmin, qmax) is monotone non-decreasing in v, so
@@ -142,11 +158,10 @@ def codes_rowsum(a_codes: torch.Tensor, a_zero_point: int) -> torch.Tensor:
             raise NotImplementedError(f"mctq_codes_rowsum needs K % 16 == 0 and K <= {_MAX_K}, got K={K}")
         lib = native.load()
         a_codes = a_codes.contiguous()
-        code = native.CODE_U8 if a_codes.dtype == torch.uint8 else native.CODE_I8
         with ops._maybe_on_device(a_codes):
             out = a_codes.new_empty((M,), dtype=torch.int32)
-            rc = ops._launch(lib.mctq_codes_rowsum, a_codes.data_ptr(), code, int(a_zero_point), out.data_ptr(), M, K,
-                             ops._stream(a_codes))
+            rc = ops._launch(lib.mctq_codes_rowsum, a_codes.data_ptr(), ops._code_of(a_codes), int(a_zero_point), out.data_ptr(),
+                             M, K, ops._stream(a_codes))
         if rc:
             native.check(rc, "mctq_codes_rowsum")
         return out
@@ -175,7 +190,6 @@ def _launch_consumer(name, a_codes, a_zero_point, a_scale, w, lut, w_scales, w_r
     _check_consumer_operands(a_codes, w_scales, w_rowsum, bias, w_zero_points)
     lib = native.load()
     a_codes, w = a_codes.contiguous(), w.contiguous()
-    code = native.CODE_U8 if a_codes.dtype == torch.uint8 else native.CODE_I8
     if w_zero_points is not None:
         name += "_zp"
         a_rowsum = codes_rowsum(a_codes, a_zero_point)       # named: it must outlive the launch, or y is allocated over it
@@ -190,9 +204,9 @@ def _launch_consumer(name, a_codes, a_zero_point, a_scale, w, lut, w_scales, w_r
         tdt, *form = _output_form(out_codes)
     with ops._maybe_on_device(a_codes):
         y = a_codes.new_empty((M, N), dtype=tdt)
-        rc = ops._launch(fn, a_codes.data_ptr(), code, int(a_zero_point), float(a_scale), w.data_ptr(), *lut, w_scales.data_ptr(),
-                         w_rowsum.data_ptr(), None if bias is None else bias.data_ptr(), y.data_ptr(), *form, *zp, M, N, K,
-                         ops._stream(a_codes))
+        rc = ops._launch(fn, a_codes.data_ptr(), ops._code_of(a_codes), int(a_zero_point), float(a_scale), w.data_ptr(), *lut,
+                         w_scales.data_ptr(), w_rowsum.data_ptr(), None if bias is None else bias.data_ptr(), y.data_ptr(), *form,
+                         *zp, M, N, K, ops._stream(a_codes))
     if rc:
         native.check(rc, name)
     return y
@@ -219,10 +233,7 @@ def qlinear_i8(a_codes: torch.Tensor, a_zero_point: int, a_scale: float, w_codes
         _check_consumer_operands(a_codes, w_scales, None, None, w_zero_points)     # dtype, device, one per output channel
         w32 = w32 - w_zero_points.to(torch.int32).reshape(-1, 1)
     acc = (a_codes.to(torch.int32) - int(a_zero_point)) @ w32.t()
-    y = acc.to(torch.float32) * (torch.tensor(a_scale, dtype=torch.float64).to(torch.float32) * w_scales)
-    if bias is not None:
-        y = y + bias
-    return y if out_codes is None else _cpu_out_codes(y, out_codes)
+    return _cpu_epilogue(acc, a_scale, w_scales, bias, out_codes)
 
 
 def qconv_dw_i8(a_codes_nhwc: torch.Tensor, a_zero_point: int, a_scale: float, w_codes: torch.Tensor, w_scales: torch.Tensor,
@@ -238,11 +249,8 @@ def qconv_dw_i8(a_codes_nhwc: torch.Tensor, a_zero_point: int, a_scale: float, w
     GPU tensors run ``mctq_qconv_dw_i8`` (C % 16 == 0, kh * kw <= 256); CPU tensors the same arithmetic with torch ops."""
     if not isinstance(a_codes_nhwc, torch.Tensor) or a_codes_nhwc.dim() != 4 or a_codes_nhwc.dtype not in (torch.int8, torch.uint8):
         raise TypeError("qconv_dw_i8 takes int8 / uint8 codes [B, H, W, C]")
-    (kh, kw), (sh, sw) = ops._pair(kernel_size, "kernel_size"), ops._pair(stride, "stride")
-    (ph, pw), (dh, dw) = ops._pair(padding, "padding"), ops._pair(dilation, "dilation")
-    if min(kh, kw, sh, sw, dh, dw) < 1 or min(ph, pw) < 0:
-        raise ValueError("qconv_dw_i8: kernel_size, stride and dilation must be at least 1 and padding at least 0")
     b, h, w_, c = a_codes_nhwc.shape
+    (kh, kw), (sh, sw), (ph, pw), (dh, dw), (ho, wo) = ops._conv_geometry(h, w_, kernel_size, stride, padding, dilation, "qconv_dw_i8")
     if w_codes.dtype != torch.int8 or w_codes.device != a_codes_nhwc.device or tuple(w_codes.shape) != (kh, kw, c):
         raise TypeError(f"w_codes must be an int8 tensor [{kh}, {kw}, {c}] on {a_codes_nhwc.device}, got {w_codes.dtype} "
                         f"{tuple(w_codes.shape)} on {w_codes.device}")
@@ -253,20 +261,15 @@ def qconv_dw_i8(a_codes_nhwc: torch.Tensor, a_zero_point: int, a_scale: float, w
     lo, hi = (0, 255) if a_codes_nhwc.dtype == torch.uint8 else (-128, 127)
     if not lo <= a_zero_point <= hi:
         raise ValueError(f"qconv_dw_i8: a_zero_point {a_zero_point} is no {a_codes_nhwc.dtype} code")
-    ho = (h + 2 * ph - dh * (kh - 1) - 1) // sh + 1
-    wo = (w_ + 2 * pw - dw * (kw - 1) - 1) // sw + 1
-    if ho <= 0 or wo <= 0:
-        raise ValueError(f"qconv_dw_i8: a {kh}x{kw} kernel (dilation {dh}x{dw}) does not fit the padded {h}x{w_} image")
     if a_codes_nhwc.is_cuda:
         if c % 16 or kh * kw > 256:
             raise NotImplementedError(f"mctq_qconv_dw_i8 needs C % 16 == 0 and kh * kw <= 256, got C={c}, {kh}x{kw}")
         lib = native.load()
         x, w_codes = a_codes_nhwc.contiguous(), w_codes.contiguous()
-        code = native.CODE_U8 if x.dtype == torch.uint8 else native.CODE_I8
         tdt, *form = _output_form(out_codes)
         with ops._maybe_on_device(x):
             y = x.new_empty((b, ho, wo, c), dtype=tdt)
-            rc = ops._launch(lib.mctq_qconv_dw_i8, x.data_ptr(), code, a_zero_point, float(a_scale), w_codes.data_ptr(),
+            rc = ops._launch(lib.mctq_qconv_dw_i8, x.data_ptr(), ops._code_of(x), a_zero_point, float(a_scale), w_codes.data_ptr(),
                              w_scales.data_ptr(), None if w_zero_points is None else w_zero_points.data_ptr(),
                              None if bias is None else bias.data_ptr(), y.data_ptr(), *form, b, h, w_, c, kh, kw, sh, sw, ph, pw,
                              dh, dw, ops._stream(x))
@@ -284,10 +287,7 @@ def qconv_dw_i8(a_codes_nhwc: torch.Tensor, a_zero_point: int, a_scale: float, w
         for kx in range(kw):
             taps = xp[:, ky * dh:ky * dh + (ho - 1) * sh + 1:sh, kx * dw:kx * dw + (wo - 1) * sw + 1:sw, :]
             acc += taps * w32[ky, kx]
-    y = acc.to(torch.float32) * (torch.tensor(a_scale, dtype=torch.float64).to(torch.float32) * w_scales)
-    if bias is not None:
-        y = y + bias
-    return y if out_codes is None else _cpu_out_codes(y, out_codes)
+    return _cpu_epilogue(acc, a_scale, w_scales, bias, out_codes)
 
 
 def pack_w4(codes: torch.Tensor) -> torch.Tensor:
@@ -364,20 +364,26 @@ def _is_uniform_weights(q) -> bool:
     return isinstance(q, WeightsUniformInferableQuantizer)
 
 
-class QuantizedLinear(nn.Module):
-    """``activation quantizer -> PytorchQuantizationWrapper(nn.Linear)`` evaluated on integer codes.
+class IntegerConsumer(nn.Module):
+    """``activation quantizer -> PytorchQuantizationWrapper(layer)`` evaluated on integer codes: what the four consumers share.
 
     ``weights_quantizer``: WeightsSymmetric / WeightsPOT (zero point 0), per tensor or per output channel
     (``channel_axis`` 0), at most 8 bits; or WeightsUniform (a zero point per tensor or per output channel, at most 8 bits:
     unsigned codes c and zero points z are kept as c - 2^(num_bits - 1) and z - 2^(num_bits - 1), both int8-ranged); or
-    WeightsLUTSymmetric / WeightsLUTPOT with ``lut_values_bitwidth`` <= 8 (int8
-    codebook values) and at most 256 codebook entries, per tensor or per output channel.  ``activation_quantizer``: ActivationSymmetric / POT / Uniform, at most
-    8 bits.  The float weight stays the module's parameter; its codes are rebuilt when it changes."""
+    WeightsLUTSymmetric / WeightsLUTPOT with ``lut_values_bitwidth`` <= 8 (int8 codebook values) and at most 256 codebook
+    entries, per tensor or per output channel.  ``activation_quantizer``: ActivationSymmetric / POT / Uniform, at most 8 bits.
+    ``weight``: the float weight to own in place of ``layer.weight`` (a wrapper has replaced that by a plain tensor and owns the
+    parameter itself).  The float weight stays the module's parameter; its codes are rebuilt when it changes.
 
-    def __init__(self, linear: nn.Linear, weights_quantizer, activation_quantizer):
+    A subclass says which layers it takes (``eligible``, ``_takes`` for the messages), in which layout it keeps the weight
+    codes (``_store_weight_codes``) and runs the product (``forward``)."""
+
+    _takes = None
+
+    def __init__(self, layer, weights_quantizer, activation_quantizer, weight=None):
         super().__init__()
-        if not isinstance(linear, nn.Linear):
-            raise TypeError("QuantizedLinear wraps torch.nn.Linear")
+        if not self.eligible(layer):
+            raise TypeError(f"{type(self).__name__} takes {self._takes}")
         self._lut_weights = _is_lut_weights(weights_quantizer)
         self._uniform_weights = _is_uniform_weights(weights_quantizer)
         if self._lut_weights:
@@ -392,22 +398,21 @@ class QuantizedLinear(nn.Module):
             raise NotImplementedError("per-channel weight scales must run along the output channels (axis 0)")
         if weights_quantizer.num_bits > 8 or activation_quantizer.num_bits > 8:
             raise NotImplementedError("codes wider than 8 bits")
+        weight, bias = layer.weight if weight is None else weight, layer.bias
         # The kernels read the bias as float32 and return float32: a half-precision layer stays on the fake-quant
         # path (its wrapper returns the layer's own type), it is never reinterpreted.
-        if linear.weight.dtype != torch.float32 or (linear.bias is not None and linear.bias.dtype != torch.float32):
-            raise TypeError(f"QuantizedLinear takes float32 layers, got weight {linear.weight.dtype}"
-                            + ("" if linear.bias is None else f" / bias {linear.bias.dtype}"))
-        if linear.bias is not None and linear.bias.device != linear.weight.device:
+        if not isinstance(weight, torch.Tensor) or weight.dtype != torch.float32 or (bias is not None and bias.dtype != torch.float32):
+            raise TypeError(f"{type(self).__name__} takes float32 layers, got weight {getattr(weight, 'dtype', type(weight).__name__)}"
+                            + ("" if bias is None else f" / bias {bias.dtype}"))
+        if bias is not None and bias.device != weight.device:
             raise TypeError("weight and bias live on different devices")
-        self.weight = linear.weight
-        self.bias = linear.bias
-        self.in_features, self.out_features = linear.in_features, linear.out_features
+        self.weight = weight                             # of the layer's own shape: the codes are taken from it in the class's layout
+        self.bias = bias
         self.weights_quantizer = weights_quantizer
         self.activation_quantizer = activation_quantizer
         self._a_scale, self._a_zp, self._a_qmin, self._a_qmax = _activation_code_params(activation_quantizer)
         self._w_key = None
-        self._w_codes = self._w_scales = self._w_rowsum = self._w_codes4 = None
-        self._w_idx4 = self._lut16 = None                # LUT weights of at most 16 entries: packed indices + host codebook
+        self._w_codes = self._w_scales = None
         self._w_zps = None                               # uniform weights: int32 zero points in the stored codes' domain
         # chaining (fuse_linear_consumers(chain=True)): parameters of the activation quantizer that would quantize
         # this layer's output next; the output then leaves as that quantizer's codes
@@ -418,15 +423,12 @@ class QuantizedLinear(nn.Module):
         self.emit_clamp = None
 
     @classmethod
-    def from_wrapper(cls, wrapper: PytorchQuantizationWrapper, activation_quantizer) -> "QuantizedLinear":
+    def from_wrapper(cls, wrapper: PytorchQuantizationWrapper, activation_quantizer):
         quantizers = wrapper.weights_quantizers
-        if list(quantizers) != ["weight"] or not isinstance(wrapper.layer, nn.Linear):
-            raise TypeError("expected a wrapped torch.nn.Linear with one quantizer on 'weight'")
-        lin = nn.Linear(wrapper.layer.in_features, wrapper.layer.out_features, bias=wrapper.layer.bias is not None,
-                        device=wrapper.weight.device, dtype=wrapper.weight.dtype)
-        lin.weight = wrapper.weight                     # the wrapper owns the float weight as its parameter
-        lin.bias = wrapper.layer.bias
-        return cls(lin, quantizers["weight"], activation_quantizer)
+        if list(quantizers) != ["weight"] or not cls.eligible(wrapper.layer):
+            raise TypeError(f"expected wrapped {cls._takes} with one quantizer on 'weight'")
+        # (the wrapper owns the float weight as its parameter)
+        return cls(wrapper.layer, quantizers["weight"], activation_quantizer, weight=wrapper.weight)
 
     def activation_code_params(self):
         """(scale, zero_point, qmin, qmax) of this layer's activation codes: what ``emit_codes_for`` of the layer in front takes."""
@@ -438,12 +440,9 @@ class QuantizedLinear(nn.Module):
             return self.emit_codes_for
         return (*self.emit_codes_for, *self.emit_clamp)
 
-    def _as_rows(self, t):
-        """Codes or codebook indices shaped like the weight -> [O, K] in the order of the activation rows."""
-        return t.reshape(self.out_features, self.in_features)            # [O, C, 1, 1] of a pointwise convolution too
-
     def _weight_codes(self, w):
-        """The weight kind's part: (int8 codes, scales, int32 zero points or None, (indices, int8 codebook) or None)."""
+        """The weight kind's part: (int8 codes, scales, int32 zero points or None, (indices, int8 codebook) or None); codes
+        and indices shaped like the weight."""
         q = self.weights_quantizer
         if self._lut_weights:
             # q(w)[n][k] = (lut[idx] / 2^(B-1)) * thr[n] == float(lut_i8[idx]) * (thr[n] / 2^(B-1)) bit for bit (the divisor is
@@ -455,7 +454,7 @@ class QuantizedLinear(nn.Module):
                 raise RuntimeError("the codebook no longer holds at most 256 int8 values")
             lut_i8 = lut.to(torch.int8)
             scales = thr.detach().to(device=w.device, dtype=torch.float32) / float(2 ** (bits - 1))
-            return lut_i8.to(w.device)[idx.long()], scales, None, (self._as_rows(idx), lut_i8)
+            return lut_i8.to(w.device)[idx.long()], scales, None, (idx, lut_i8)
         codes, scales, zps = q.quantize_to_codes(w.detach())
         if not self._uniform_weights:
             if codes.dtype != torch.int8:
@@ -472,56 +471,126 @@ class QuantizedLinear(nn.Module):
         return (codes.to(torch.int16) - half).to(torch.int8), scales, zps, None
 
     def _refresh_weight_codes(self):
+        """Rebuilds the weight's codes, and its scales and zero points as one value per output channel, when the weight tensor
+        changed; the subclass keeps the codes in its own layout (``_store_weight_codes(codes, lut)``)."""
         w = self.weight
         key = (w.data_ptr(), w._version, w.device)
         if key == self._w_key:
             return
-        codes, scales, zps, packed = self._weight_codes(w)
+        codes, scales, zps, lut = self._weight_codes(w)
 
         def per_channel(t):
-            return (t.expand(self.out_features) if t.numel() == 1 else t).contiguous()
+            return (t.expand(w.shape[0]) if t.numel() == 1 else t).contiguous()
 
-        codes = self._as_rows(codes)
-        self._w_codes = codes.contiguous()
         self._w_scales = per_channel(scales.to(device=w.device, dtype=torch.float32).reshape(-1))
-        self._w_rowsum = codes.sum(dim=1, dtype=torch.int32).contiguous()
         if zps is not None:
             self._w_zps = per_channel(zps)
-        # at most 4 bits per weight -- codes, or the indices of a codebook of at most 16 entries: also keep them packed, to
-        # stream half the bytes when there are few rows
-        can_pack = w.is_cuda and self.in_features % 16 == 0
-        self._w_codes4 = pack_w4(self._w_codes) if packed is None and self.weights_quantizer.num_bits <= 4 and can_pack else None
-        self._w_idx4 = self._lut16 = None
-        if packed is not None and packed[1].numel() <= 16 and can_pack:
-            self._w_idx4, self._lut16 = pack_lut4(packed[0]), _lut16_bytes(packed[1])
+        self._store_weight_codes(codes, lut)
         self._w_key = key
 
+    def _activation_codes(self, x):
+        """``forward``'s input as this layer's activation codes.  int8 / uint8 tensors already are codes (chained layers) and
+        must be of the quantizer's type; anything else is quantized.  2-D rows stay rows; an [N, C, H, W] tensor (codes:
+        NCHW-shaped, NHWC-stored) gives contiguous [N, H, W, C] codes."""
+        if x.dtype in (torch.uint8, torch.int8):
+            if x.dtype != ops._code_dtype(self._a_qmin, self._a_qmax)[0]:
+                raise TypeError(f"activation codes of type {x.dtype} do not match this layer's quantizer")
+            if x.dim() != 4:
+                return x
+            codes = x.permute(0, 2, 3, 1)
+            return codes if codes.is_contiguous() else codes.contiguous()
+        if x.dim() == 4:
+            return ops.fq_codes_nhwc(x, self._a_qmin, self._a_qmax, self._a_scale, self._a_zp)
+        return ops.fq_codes(x, None, None, None, self._a_qmin, self._a_qmax, self._a_scale, self._a_zp)
+
+    def _bias_for(self, codes):
+        """The bias as the kernels read it, a contiguous float32 tensor on the codes' device, or None."""
+        if self.bias is None:
+            return None
+        bias = self.bias.detach()
+        if bias.dtype != torch.float32 or bias.device != codes.device or not bias.is_contiguous():
+            # (.to() after construction, e.g. model.half(): convert instead of letting the kernel misread it)
+            bias = bias.to(device=codes.device, dtype=torch.float32).contiguous()
+        return bias
+
+
+def _padding(conv):
+    """(pad_h, pad_w) of a symmetrically zero-padded convolution, or None."""
+    if conv.padding == "valid":
+        return 0, 0
+    if conv.padding == "same":
+        spans = [d * (k - 1) for d, k in zip(conv.dilation, conv.kernel_size)]
+        return None if any(s % 2 for s in spans) else tuple(s // 2 for s in spans)
+    if isinstance(conv.padding, tuple) and len(conv.padding) == 2 and all(isinstance(p, int) and p >= 0 for p in conv.padding):
+        return conv.padding
+    return None
+
+
+def _take_conv_geometry(consumer, conv):
+    """The geometry a convolution consumer reads on ``forward``.  A tap outside the image adds nothing because it holds the
+    activation's zero-point code, which therefore has to be a code."""
+    if not consumer._a_qmin <= consumer._a_zp <= consumer._a_qmax:
+        raise NotImplementedError("the activation zero point lies outside the codes' domain: it cannot be the pad byte")
+    consumer.in_channels = conv.in_channels
+    consumer.kernel_size, consumer.stride, consumer.dilation = tuple(conv.kernel_size), tuple(conv.stride), tuple(conv.dilation)
+    consumer.padding = _padding(conv)
+
+
+def _check_nchw(x, channels):
+    if x.dim() != 4 or x.shape[1] != channels:
+        raise RuntimeError(f"expected [N, {channels}, H, W], got {tuple(x.shape)}")
+
+
+class QuantizedLinear(IntegerConsumer):
+    """``activation quantizer -> PytorchQuantizationWrapper(nn.Linear)`` on integer codes (``IntegerConsumer`` for the
+    quantizers it takes): the product over rows.  The weight codes are kept as ``[O, K]`` rows with their row sums; at most 4
+    bits per weight -- codes, or the indices of a codebook of at most 16 entries -- are also kept packed, to stream half the
+    bytes when there are few activation rows."""
+
+    _takes = "torch.nn.Linear layers"
+
+    def __init__(self, linear, weights_quantizer, activation_quantizer, weight=None):
+        super().__init__(linear, weights_quantizer, activation_quantizer, weight)
+        # [O, K] of a Linear, [O, C, 1, 1] of a pointwise and [O, C, kh, kw] of a k x k convolution
+        self.out_features, self.in_features = self.weight.shape[0], math.prod(self.weight.shape[1:])
+        self._w_rowsum = self._w_codes4 = None
+        self._w_idx4 = self._lut16 = None                # LUT weights of at most 16 entries: packed indices + host codebook
+
+    @staticmethod
+    def eligible(layer) -> bool:
+        return isinstance(layer, nn.Linear)
+
+    def _as_rows(self, t):
+        """Codes or codebook indices shaped like the weight -> [O, K] in the order of the activation rows."""
+        return t.reshape(self.out_features, self.in_features)            # [O, C, 1, 1] of a pointwise convolution too
+
+    def _store_weight_codes(self, codes, lut):
+        codes = self._as_rows(codes)
+        self._w_codes = codes.contiguous()
+        self._w_rowsum = codes.sum(dim=1, dtype=torch.int32).contiguous()
+        can_pack = self.weight.is_cuda and self.in_features % 16 == 0
+        self._w_codes4 = pack_w4(self._w_codes) if lut is None and self.weights_quantizer.num_bits <= 4 and can_pack else None
+        self._w_idx4 = self._lut16 = None
+        if lut is not None and lut[1].numel() <= 16 and can_pack:
+            self._w_idx4, self._lut16 = pack_lut4(self._as_rows(lut[0])), _lut16_bytes(lut[1])
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        self._refresh_weight_codes()
         lead = x.shape[:-1]
-        x2 = x.reshape(-1, self.in_features)
-        if x2.dtype in (torch.uint8, torch.int8):          # already this layer's activation codes (chained layers)
-            if x2.dtype != ops._code_dtype(self._a_qmin, self._a_qmax)[0]:
-                raise TypeError(f"activation codes of type {x2.dtype} do not match this layer's quantizer")
-            a_codes = x2
-        else:
-            a_codes = ops.fq_codes(x2, None, None, None, self._a_qmin, self._a_qmax, self._a_scale, self._a_zp)
-        bias = None
-        if self.bias is not None:
-            bias = self.bias.detach()
-            if bias.dtype != torch.float32 or bias.device != a_codes.device or not bias.is_contiguous():
-                # (.to() after construction, e.g. model.half(): convert instead of letting the kernel misread it)
-                bias = bias.to(device=a_codes.device, dtype=torch.float32).contiguous()
+        return self._rows_product(self._activation_codes(x.reshape(-1, self.in_features))).reshape(*lead, self.out_features)
+
+    def _rows_product(self, a_codes):
+        """This layer's activation codes [M, K] -> [M, O], float32 or the codes of ``emit_codes_for``: what the convolutions
+        that are this product call with their pixels or patches as rows (their codes are checked once, not again here)."""
+        self._refresh_weight_codes()
+        bias = self._bias_for(a_codes)
         if self._w_codes4 is not None and a_codes.is_cuda and a_codes.shape[0] <= _W4_MAX_ROWS:
-            y = qlinear_w4a8(a_codes, self._a_zp, self._a_scale, self._w_codes4, self._w_scales, self._w_rowsum, bias,
-                             self._out_codes(), self._w_zps)
-        elif self._w_idx4 is not None and a_codes.is_cuda and a_codes.shape[0] <= _LUT4_MAX_ROWS:
-            y = qlinear_lut4a8(a_codes, self._a_zp, self._a_scale, self._w_idx4, self._lut16, self._w_scales,
-                               self._w_rowsum, bias, self._out_codes())
-        else:
-            y = qlinear_i8(a_codes, self._a_zp, self._a_scale, self._w_codes, self._w_scales, self._w_rowsum, bias,
-                           self._out_codes(), self._w_zps)
-        return y.reshape(*lead, self.out_features)
+            return qlinear_w4a8(a_codes, self._a_zp, self._a_scale, self._w_codes4, self._w_scales, self._w_rowsum, bias,
+                                self._out_codes(), self._w_zps)
+        if self._w_idx4 is not None and a_codes.is_cuda and a_codes.shape[0] <= _LUT4_MAX_ROWS:
+            return qlinear_lut4a8(a_codes, self._a_zp, self._a_scale, self._w_idx4, self._lut16, self._w_scales,
+                                  self._w_rowsum, bias, self._out_codes())
+        return qlinear_i8(a_codes, self._a_zp, self._a_scale, self._w_codes, self._w_scales, self._w_rowsum, bias,
+                          self._out_codes(), self._w_zps)
 
 
 class QuantizedConv1x1(QuantizedLinear):
@@ -531,14 +600,7 @@ class QuantizedConv1x1(QuantizedLinear):
     M = batch x height x width rows.  Channels-last inputs are quantized in place; NCHW inputs take one fused
     quantize-and-transpose pass (``mctq_fq_codes_nchw_to_nhwc``).  The result has the NCHW shape with channels-last strides."""
 
-    def __init__(self, conv: nn.Conv2d, weights_quantizer, activation_quantizer):
-        if not self.eligible(conv):
-            raise TypeError("QuantizedConv1x1 takes 1x1, stride-1, unpadded, undilated, ungrouped nn.Conv2d layers")
-        lin = nn.Linear(conv.in_channels, conv.out_channels, bias=conv.bias is not None, device=conv.weight.device,
-                        dtype=conv.weight.dtype)
-        lin.bias = conv.bias
-        super().__init__(lin, weights_quantizer, activation_quantizer)
-        self.weight = conv.weight                         # [O, C, 1, 1]; the codes are taken from it as [O, C]
+    _takes = "1x1, stride-1, unpadded, undilated, ungrouped nn.Conv2d layers"
 
     @staticmethod
     def eligible(conv) -> bool:
@@ -546,27 +608,10 @@ class QuantizedConv1x1(QuantizedLinear):
                 and conv.padding in ((0, 0), 0, "valid") and conv.dilation == (1, 1) and conv.groups == 1
                 and conv.padding_mode == "zeros")
 
-    @classmethod
-    def from_wrapper(cls, wrapper: PytorchQuantizationWrapper, activation_quantizer) -> "QuantizedConv1x1":
-        quantizers = wrapper.weights_quantizers
-        if list(quantizers) != ["weight"] or not cls.eligible(wrapper.layer):
-            raise TypeError("expected a wrapped pointwise nn.Conv2d with one quantizer on 'weight'")
-        conv = nn.Conv2d(wrapper.layer.in_channels, wrapper.layer.out_channels, 1, bias=wrapper.layer.bias is not None,
-                         device=wrapper.weight.device, dtype=wrapper.weight.dtype)
-        conv.weight = wrapper.weight
-        conv.bias = wrapper.layer.bias
-        return cls(conv, quantizers["weight"], activation_quantizer)
-
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        if x.dim() != 4 or x.shape[1] != self.in_features:
-            raise RuntimeError(f"expected [N, {self.in_features}, H, W], got {tuple(x.shape)}")
+        _check_nchw(x, self.in_features)
         b, _, h, w_ = x.shape
-        if x.dtype in (torch.uint8, torch.int8):          # codes from the previous layer: NCHW-shaped, NHWC-stored
-            rows = x.permute(0, 2, 3, 1)
-            rows = rows if rows.is_contiguous() else rows.contiguous()
-        else:
-            rows = ops.fq_codes_nhwc(x, self._a_qmin, self._a_qmax, self._a_scale, self._a_zp)
-        y = super().forward(rows.reshape(b * h * w_, self.in_features))
+        y = self._rows_product(self._activation_codes(x).reshape(b * h * w_, self.in_features))
         return y.reshape(b, h, w_, self.out_features).permute(0, 3, 1, 2)
 
 
@@ -581,194 +626,112 @@ class QuantizedConv2d(QuantizedLinear):
     where every ``dilation * (k - 1)`` is even (PyTorch pads one side more otherwise).  The result has the NCHW shape
     with channels-last strides."""
 
-    def __init__(self, conv: nn.Conv2d, weights_quantizer, activation_quantizer):
-        if not self.eligible(conv):
-            raise TypeError("QuantizedConv2d takes ungrouped, zero-padded (symmetric) nn.Conv2d layers with in_channels % 16 == 0 "
-                            f"and kh * kw * in_channels <= {_MAX_K}")
-        if conv.weight.dtype != torch.float32 or (conv.bias is not None and conv.bias.dtype != torch.float32):
-            raise TypeError(f"QuantizedConv2d takes float32 layers, got weight {conv.weight.dtype}"
-                            + ("" if conv.bias is None else f" / bias {conv.bias.dtype}"))
-        if conv.bias is not None and conv.bias.device != conv.weight.device:
-            raise TypeError("weight and bias live on different devices")
-        kh, kw = conv.kernel_size
-        # (a shape holder for QuantizedLinear's checks: no [O, K] float tensor is ever allocated)
-        lin = nn.Linear(kh * kw * conv.in_channels, conv.out_channels, bias=False, device="meta", dtype=conv.weight.dtype)
-        super().__init__(lin, weights_quantizer, activation_quantizer)
-        if not self._a_qmin <= self._a_zp <= self._a_qmax:
-            raise NotImplementedError("the activation zero point lies outside the codes' domain: it cannot be the pad byte")
-        self.weight = conv.weight                         # [O, C, kh, kw]; the codes are taken from it as [O, kh, kw, C]
-        self.bias = conv.bias
-        self.in_channels = conv.in_channels
-        self.kernel_size, self.stride, self.dilation = tuple(conv.kernel_size), tuple(conv.stride), tuple(conv.dilation)
-        self.padding = self._padding(conv)
+    _takes = f"ungrouped, zero-padded (symmetric) nn.Conv2d layers with in_channels % 16 == 0 and kh * kw * in_channels <= {_MAX_K}"
+
+    def __init__(self, conv, weights_quantizer, activation_quantizer, weight=None):
+        super().__init__(conv, weights_quantizer, activation_quantizer, weight)
+        _take_conv_geometry(self, conv)
 
     @staticmethod
-    def _padding(conv):
-        """(pad_h, pad_w) of a symmetrically zero-padded convolution, or None."""
-        if conv.padding == "valid":
-            return 0, 0
-        if conv.padding == "same":
-            spans = [d * (k - 1) for d, k in zip(conv.dilation, conv.kernel_size)]
-            return None if any(s % 2 for s in spans) else tuple(s // 2 for s in spans)
-        if isinstance(conv.padding, tuple) and len(conv.padding) == 2 and all(isinstance(p, int) and p >= 0 for p in conv.padding):
-            return conv.padding
-        return None
-
-    @classmethod
-    def eligible(cls, conv) -> bool:
+    def eligible(conv) -> bool:
         return (isinstance(conv, nn.Conv2d) and conv.groups == 1 and conv.padding_mode == "zeros"
-                and cls._padding(conv) is not None and conv.in_channels % 16 == 0
+                and _padding(conv) is not None and conv.in_channels % 16 == 0
                 and conv.kernel_size[0] * conv.kernel_size[1] * conv.in_channels <= _MAX_K)
-
-    @classmethod
-    def from_wrapper(cls, wrapper: PytorchQuantizationWrapper, activation_quantizer) -> "QuantizedConv2d":
-        quantizers = wrapper.weights_quantizers
-        layer = wrapper.layer
-        if list(quantizers) != ["weight"] or not cls.eligible(layer):
-            raise TypeError("expected a wrapped nn.Conv2d the integer consumer can take, with one quantizer on 'weight'")
-        conv = nn.Conv2d(layer.in_channels, layer.out_channels, layer.kernel_size, layer.stride, layer.padding, layer.dilation,
-                         bias=False, device="meta", dtype=wrapper.weight.dtype)
-        conv.weight = wrapper.weight                     # the wrapper owns the float weight as its parameter
-        conv.bias = layer.bias
-        return cls(conv, quantizers["weight"], activation_quantizer)
 
     def _as_rows(self, t):
         kh, kw = self.kernel_size
         return t.reshape(self.out_features, self.in_channels, kh, kw).permute(0, 2, 3, 1).reshape(self.out_features, self.in_features)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        if x.dim() != 4 or x.shape[1] != self.in_channels:
-            raise RuntimeError(f"expected [N, {self.in_channels}, H, W], got {tuple(x.shape)}")
-        if x.dtype in (torch.uint8, torch.int8):          # codes from the previous layer: NCHW-shaped, NHWC-stored
-            codes = x.permute(0, 2, 3, 1)
-        else:
-            codes = ops.fq_codes_nhwc(x, self._a_qmin, self._a_qmax, self._a_scale, self._a_zp)
-        rows = ops.codes_im2col(codes, self.kernel_size, self.stride, self.padding, self.dilation, self._a_zp)
-        y = super().forward(rows)
+        _check_nchw(x, self.in_channels)
         b, _, h, w_ = x.shape
-        ho, wo = ((n + 2 * p - d * (k - 1) - 1) // s + 1
-                  for n, k, s, p, d in zip((h, w_), self.kernel_size, self.stride, self.padding, self.dilation))
+        rows = ops.codes_im2col(self._activation_codes(x), self.kernel_size, self.stride, self.padding, self.dilation, self._a_zp)
+        y = self._rows_product(rows)
+        ho, wo = map(ops._conv_out_size, (h, w_), self.kernel_size, self.stride, self.padding, self.dilation)
         return y.reshape(b, ho, wo, self.out_features).permute(0, 3, 1, 2)
 
 
-class QuantizedDepthwiseConv2d(QuantizedLinear):
+class QuantizedDepthwiseConv2d(IntegerConsumer):
     """``activation quantizer -> PytorchQuantizationWrapper(depthwise nn.Conv2d)`` on integer codes: ``groups == in_channels ==
     out_channels`` (channel multiplier 1), any kernel size with ``kh * kw <= 256``, stride, dilation and symmetric zero
-    padding, ``in_channels % 16 == 0``.  There is no reduction over channels, so no patch matrix: ``qconv_dw_i8`` convolves
-    the NHWC activation codes directly with the weight codes kept as ``[kh, kw, C]`` (a few KiB: no packed 4-bit copies).  A
-    tap outside the image adds nothing, which the kernel gets by giving it the activation's zero-point code: that needs the
-    zero point inside the clamp domain.  All four weight families of QuantizedLinear (a per-channel axis is the output-channel
-    axis 0 of the ``[C, 1, kh, kw]`` weight); chaining and ``emit_codes_for`` as for the other consumers.  The result has the
-    NCHW shape with channels-last strides."""
+    padding, ``in_channels % 16 == 0``.  There is no reduction over channels, so no patch matrix and no product over rows:
+    ``qconv_dw_i8`` convolves the NHWC activation codes directly with the weight codes kept as ``[kh, kw, C]`` (a few KiB: no
+    row sums, no packed 4-bit copies).  A tap outside the image adds nothing, which the kernel gets by giving it the
+    activation's zero-point code: that needs the zero point inside the clamp domain.  All four weight families of
+    IntegerConsumer (a per-channel axis is the output-channel axis 0 of the ``[C, 1, kh, kw]`` weight); chaining and
+    ``emit_codes_for`` as for the other consumers.  The result has the NCHW shape with channels-last strides."""
 
-    def __init__(self, conv: nn.Conv2d, weights_quantizer, activation_quantizer):
-        if not self.eligible(conv):
-            raise TypeError("QuantizedDepthwiseConv2d takes zero-padded (symmetric) nn.Conv2d layers with groups == in_channels == "
-                            "out_channels, in_channels % 16 == 0 and kh * kw <= 256")
-        if conv.weight.dtype != torch.float32 or (conv.bias is not None and conv.bias.dtype != torch.float32):
-            raise TypeError(f"QuantizedDepthwiseConv2d takes float32 layers, got weight {conv.weight.dtype}"
-                            + ("" if conv.bias is None else f" / bias {conv.bias.dtype}"))
-        if conv.bias is not None and conv.bias.device != conv.weight.device:
-            raise TypeError("weight and bias live on different devices")
-        kh, kw = conv.kernel_size
-        # (a shape holder for QuantizedLinear's checks: a channel's kh * kw taps are its "row")
-        lin = nn.Linear(kh * kw, conv.out_channels, bias=False, device="meta", dtype=conv.weight.dtype)
-        super().__init__(lin, weights_quantizer, activation_quantizer)
-        if not self._a_qmin <= self._a_zp <= self._a_qmax:
-            raise NotImplementedError("the activation zero point lies outside the codes' domain: it cannot be the pad byte")
-        self.weight = conv.weight                         # [C, 1, kh, kw]; the codes are taken from it as [kh, kw, C]
-        self.bias = conv.bias
-        self.in_channels = conv.in_channels
-        self.kernel_size, self.stride, self.dilation = tuple(conv.kernel_size), tuple(conv.stride), tuple(conv.dilation)
-        self.padding = QuantizedConv2d._padding(conv)
+    _takes = ("zero-padded (symmetric) nn.Conv2d layers with groups == in_channels == out_channels, in_channels % 16 == 0 "
+              "and kh * kw <= 256")
+
+    def __init__(self, conv, weights_quantizer, activation_quantizer, weight=None):
+        super().__init__(conv, weights_quantizer, activation_quantizer, weight)
+        _take_conv_geometry(self, conv)
 
     @staticmethod
     def eligible(conv) -> bool:
         return (isinstance(conv, nn.Conv2d) and conv.groups == conv.in_channels == conv.out_channels
-                and conv.padding_mode == "zeros" and QuantizedConv2d._padding(conv) is not None and conv.in_channels % 16 == 0
+                and conv.padding_mode == "zeros" and _padding(conv) is not None and conv.in_channels % 16 == 0
                 and conv.kernel_size[0] * conv.kernel_size[1] <= 256)
 
-    @classmethod
-    def from_wrapper(cls, wrapper: PytorchQuantizationWrapper, activation_quantizer) -> "QuantizedDepthwiseConv2d":
-        quantizers = wrapper.weights_quantizers
-        layer = wrapper.layer
-        if list(quantizers) != ["weight"] or not cls.eligible(layer):
-            raise TypeError("expected a wrapped depthwise nn.Conv2d the integer consumer can take, with one quantizer on 'weight'")
-        conv = nn.Conv2d(layer.in_channels, layer.out_channels, layer.kernel_size, layer.stride, layer.padding, layer.dilation,
-                         groups=layer.groups, bias=False, device="meta", dtype=wrapper.weight.dtype)
-        conv.weight = wrapper.weight                     # the wrapper owns the float weight as its parameter
-        conv.bias = layer.bias
-        return cls(conv, quantizers["weight"], activation_quantizer)
-
-    def _refresh_weight_codes(self):
-        w = self.weight
-        key = (w.data_ptr(), w._version, w.device)
-        if key == self._w_key:
-            return
-        codes, scales, zps, _ = self._weight_codes(w)
-
-        def per_channel(t):
-            return (t.expand(self.in_channels) if t.numel() == 1 else t).contiguous()
-
+    def _store_weight_codes(self, codes, lut):
         kh, kw = self.kernel_size
         self._w_codes = codes.reshape(self.in_channels, kh, kw).permute(1, 2, 0).contiguous()
-        self._w_scales = per_channel(scales.to(device=w.device, dtype=torch.float32).reshape(-1))
-        if zps is not None:
-            self._w_zps = per_channel(zps)
-        self._w_key = key
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        if x.dim() != 4 or x.shape[1] != self.in_channels:
-            raise RuntimeError(f"expected [N, {self.in_channels}, H, W], got {tuple(x.shape)}")
+        _check_nchw(x, self.in_channels)
         self._refresh_weight_codes()
-        if x.dtype in (torch.uint8, torch.int8):          # codes from the previous layer: NCHW-shaped, NHWC-stored
-            if x.dtype != ops._code_dtype(self._a_qmin, self._a_qmax)[0]:
-                raise TypeError(f"activation codes of type {x.dtype} do not match this layer's quantizer")
-            codes = x.permute(0, 2, 3, 1)
-            codes = codes if codes.is_contiguous() else codes.contiguous()
-        else:
-            codes = ops.fq_codes_nhwc(x, self._a_qmin, self._a_qmax, self._a_scale, self._a_zp)
-        bias = None
-        if self.bias is not None:
-            bias = self.bias.detach()
-            if bias.dtype != torch.float32 or bias.device != codes.device or not bias.is_contiguous():
-                bias = bias.to(device=codes.device, dtype=torch.float32).contiguous()
-        y = qconv_dw_i8(codes, self._a_zp, self._a_scale, self._w_codes, self._w_scales, bias, self.kernel_size, self.stride,
-                        self.padding, self.dilation, self._out_codes(), self._w_zps)
+        codes = self._activation_codes(x)
+        y = qconv_dw_i8(codes, self._a_zp, self._a_scale, self._w_codes, self._w_scales, self._bias_for(codes), self.kernel_size,
+                        self.stride, self.padding, self.dilation, self._out_codes(), self._w_zps)
         return y.permute(0, 3, 1, 2)
+
+
+# In the order they are tried: (class, the switch of the rewrites that enables it or None, what fusing asks of the layer beyond
+# ``eligible``).  The rows kernels need K % 16 == 0 and K <= _MAX_K, which QuantizedConv2d's ``eligible`` holds itself.
+_CONSUMERS = (
+    (QuantizedLinear, None, lambda layer: layer.in_features % 16 == 0 and layer.in_features <= _MAX_K),
+    (QuantizedConv1x1, None, lambda layer: layer.in_channels % 16 == 0 and layer.in_channels <= _MAX_K),
+    (QuantizedConv2d, "convolutions", None),
+    (QuantizedDepthwiseConv2d, "depthwise", None),
+)
 
 
 def _consumer_for(wrapper, activation_quantizer, uniform_weights=False, convolutions=False, depthwise=False):
     """The integer consumer that can stand in for ``wrapper`` fed by ``activation_quantizer``, or None.  Uniform weights
     only with ``uniform_weights``; convolutions that need a patch matrix (QuantizedConv2d) only with ``convolutions``;
-    depthwise convolutions (QuantizedDepthwiseConv2d) only with ``depthwise``."""
+    depthwise convolutions (QuantizedDepthwiseConv2d) only with ``depthwise``.  Half-precision layers are refused by the
+    classes: the integer consumer would change the output type."""
     layer = getattr(wrapper, "layer", None)
     if list(getattr(wrapper, "weights_quantizers", {})) != ["weight"]:
         return None
     if _is_uniform_weights(wrapper.weights_quantizers["weight"]) and not uniform_weights:
         return None
-    weight = getattr(wrapper, "weight", None)
-    bias = getattr(layer, "bias", None)
-    if not isinstance(weight, torch.Tensor) or weight.dtype != torch.float32:
-        return None                     # half-precision layers: the integer consumer would change the output type
-    if isinstance(bias, torch.Tensor) and (bias.dtype != torch.float32 or bias.device != weight.device):
-        return None
-    try:
-        if isinstance(layer, nn.Linear) and layer.in_features % 16 == 0 and layer.in_features <= _MAX_K:
-            return QuantizedLinear.from_wrapper(wrapper, activation_quantizer)
-        if QuantizedConv1x1.eligible(layer) and layer.in_channels % 16 == 0 and layer.in_channels <= _MAX_K:
-            return QuantizedConv1x1.from_wrapper(wrapper, activation_quantizer)
-        if convolutions and QuantizedConv2d.eligible(layer):
-            return QuantizedConv2d.from_wrapper(wrapper, activation_quantizer)
-        if depthwise and QuantizedDepthwiseConv2d.eligible(layer):
-            return QuantizedDepthwiseConv2d.from_wrapper(wrapper, activation_quantizer)
-    except (TypeError, NotImplementedError):
-        return None
+    enabled = {None: True, "convolutions": convolutions, "depthwise": depthwise}
+    for cls, switch, fits in _CONSUMERS:
+        if enabled[switch] and cls.eligible(layer) and (fits is None or fits(layer)):
+            try:
+                return cls.from_wrapper(wrapper, activation_quantizer)
+            except (TypeError, NotImplementedError):
+                return None
     return None
 
 
 class _FusedAway(nn.Identity):
     """Placeholder left where an activation holder was folded into the QuantizedLinear after it."""
+
+
+def _module_of(node, mods):
+    """The module a ``call_module`` node calls; None for every other node."""
+    return mods.get(node.target) if node.op == "call_module" else None
+
+
+def _install_consumer(gm, mods, node, fused):
+    """Registers ``fused`` as ``<the wrapper's name>_qlinear`` and makes ``node``, the wrapper's call, call it."""
+    name = node.target.replace(".", "_") + "_qlinear"
+    gm.add_submodule(name, fused)
+    mods[name] = fused
+    node.target = name
 
 
 def _plain_holder(m) -> bool:
@@ -844,7 +807,7 @@ def _relu_input(node, mods):
     else:
         ok = node.op == "call_method" and node.target == "relu" and not node.kwargs
     # (an in-place ReLU the join no longer performs: nobody else may be looking at its input)
-    inplace = getattr(mods.get(node.target), "inplace", False) if node.op == "call_module" else node.kwargs.get("inplace", False)
+    inplace = getattr(_module_of(node, mods), "inplace", False) if node.op == "call_module" else node.kwargs.get("inplace", False)
     if inplace and len(node.args[0].users) != 1:
         ok = False
     return node.args[0] if ok else None
@@ -882,7 +845,7 @@ def _join_shared_holders(gm, mods, consumer_for) -> int:
             continue
         taken = []                                           # F: (user node, its consumer)
         for user in node.users:
-            wrapper = mods.get(user.target) if user.op == "call_module" else None
+            wrapper = _module_of(user, mods)
             if isinstance(wrapper, PytorchQuantizationWrapper) and not user.kwargs and user.args == (node,):
                 fused = consumer_for(wrapper, holder.activation_holder_quantizer)
                 if fused is not None:
@@ -909,10 +872,7 @@ def _join_shared_holders(gm, mods, consumer_for) -> int:
             as_float = gm.graph.call_function(operator.getitem, (jn, 0)) if rest else None
             as_codes = gm.graph.call_function(operator.getitem, (jn, 1))
         for user, fused in taken:
-            cname = user.target.replace(".", "_") + "_qlinear"
-            gm.add_submodule(cname, fused)
-            mods[cname] = fused
-            user.target = cname
+            _install_consumer(gm, mods, user, fused)
             user.args = (as_codes,)
             replaced += 1
         if rest:
@@ -927,7 +887,6 @@ def _clamp_range(node, mods):
     """(a, b) if ``node`` is a clamp activation of one tensor that ``folded_clamp`` can fold -- a ReLU (as ``_relu_input``),
     ``nn.ReLU6`` / ``F.relu6``, ``nn.Hardtanh`` / ``F.hardtanh`` with finite ``min_val <= max_val`` -- else None.  In-place forms
     only where nobody else looks at the input."""
-    import math
     from torch.fx import Node
     F = torch.nn.functional
     if _relu_input(node, mods) is not None:
@@ -966,15 +925,14 @@ def _identities_as_codes(gm, mods) -> int:
     def pick(node, index):
         """(the join node, its module) if ``node`` is ``join(...)[index]``."""
         if node.op == "call_function" and node.target is operator.getitem and len(node.args) == 2 and node.args[1] == index:
-            src = node.args[0]
-            m = mods.get(src.target) if src.op == "call_module" else None
+            m = _module_of(node.args[0], mods)
             if isinstance(m, QuantizedJoin):
-                return src, m
+                return node.args[0], m
         return None
 
     converted = 0
     for node in list(gm.graph.nodes):
-        join = mods.get(node.target) if node.op == "call_module" else None
+        join = _module_of(node, mods)
         if not isinstance(join, QuantizedJoin) or not join.has_residual or join.residual_codes is not None or len(node.args) != 2:
             continue
         for i in (1, 0):
@@ -1007,12 +965,11 @@ def _fold_clamps_into_producers(gm, mods) -> int:
     their clamp (``folded_clamp``), and the consumers behind take them directly.  The holder is either already inside the one
     consumer behind it (the pair rewrite) or a residual-free QuantizedJoin that writes no float32 output.  Returns the number of
     producers that now emit codes."""
-    import math
     import operator
     folded = 0
     for node in list(gm.graph.nodes):
-        producer = mods.get(node.target) if node.op == "call_module" else None
-        if not isinstance(producer, QuantizedLinear) or producer.emit_codes_for is not None or len(node.users) != 1:
+        producer = _module_of(node, mods)
+        if not isinstance(producer, IntegerConsumer) or producer.emit_codes_for is not None or len(node.users) != 1:
             continue
         nxt, act, rng = next(iter(node.users)), None, (-math.inf, math.inf)
         if _clamp_range(nxt, mods) is not None and len(nxt.users) == 1:
@@ -1021,7 +978,7 @@ def _fold_clamps_into_producers(gm, mods) -> int:
         if nxt.op != "call_module" or nxt.kwargs or nxt.args != (act or node,):
             continue
         behind, gone = mods.get(nxt.target), [nxt]
-        if isinstance(behind, QuantizedLinear):
+        if isinstance(behind, IntegerConsumer):
             form, readers, gone = behind.activation_code_params(), [nxt], []
         elif isinstance(behind, QuantizedJoin) and not behind.has_residual and not behind.want_float:
             if behind.relu:
@@ -1032,8 +989,8 @@ def _fold_clamps_into_producers(gm, mods) -> int:
             if len(picks) != 1 or picks[0].target is not operator.getitem or picks[0].args != (nxt, 1):
                 continue
             form, readers = (behind._a_scale, behind._a_zp, behind._a_qmin, behind._a_qmax), list(picks[0].users)
-            if not readers or not all(r.op == "call_module" and isinstance(mods.get(r.target), QuantizedLinear)
-                                      and r.args == (picks[0],) and not r.kwargs for r in readers):
+            if not readers or not all(isinstance(_module_of(r, mods), IntegerConsumer) and r.args == (picks[0],) and not r.kwargs
+                                      for r in readers):
                 continue
             gone = [picks[0], nxt]
         else:
@@ -1096,7 +1053,7 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
         if chain:
             for i in range(len(seq) - 2):
                 first, gap, second = seq[i], seq[i + 1], seq[i + 2]
-                if isinstance(first, QuantizedLinear) and isinstance(gap, _FusedAway) and isinstance(second, QuantizedLinear):
+                if isinstance(first, IntegerConsumer) and isinstance(gap, _FusedAway) and isinstance(second, IntegerConsumer):
                     first.emit_codes_for = second.activation_code_params()
     return replaced
 
@@ -1136,7 +1093,7 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
 
     class _Tracer(fx.Tracer):
         def is_leaf_module(self, m, qualname):
-            return isinstance(m, (PytorchQuantizationWrapper, PytorchActivationQuantizationHolder, QuantizedLinear, QuantizedJoin)) \
+            return isinstance(m, (PytorchQuantizationWrapper, PytorchActivationQuantizationHolder, IntegerConsumer, QuantizedJoin)) \
                 or super().is_leaf_module(m, qualname)
 
     graph = _Tracer().trace(model)
@@ -1160,19 +1117,16 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
         fused = _consumer_for(wrapper, holder.activation_holder_quantizer, uniform_weights, convolutions, depthwise)
         if fused is None:
             continue
-        name = node.target.replace(".", "_") + "_qlinear"
-        gm.add_submodule(name, fused)
-        mods[name] = fused
-        node.target = name
+        _install_consumer(gm, mods, node, fused)
         node.args = (src.args[0],)
         gm.graph.erase_node(src)
         replaced += 1
     if chain:
         for node in gm.graph.nodes:
-            if node.op == "call_module" and isinstance(mods.get(node.target), QuantizedLinear) and len(node.users) == 1:
+            if isinstance(_module_of(node, mods), IntegerConsumer) and len(node.users) == 1:
                 user = next(iter(node.users))
-                nxt = mods.get(user.target) if user.op == "call_module" else None
-                if isinstance(nxt, QuantizedLinear) and user.args == (node,):
+                nxt = _module_of(user, mods)
+                if isinstance(nxt, IntegerConsumer) and user.args == (node,):
                     mods[node.target].emit_codes_for = nxt.activation_code_params()
     if stay_on_codes:
         _identities_as_codes(gm, mods)

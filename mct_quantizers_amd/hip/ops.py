@@ -471,6 +471,11 @@ def _code_dtype(qmin: int, qmax: int):
     raise ValueError(f"clamp domain [{qmin}, {qmax}] does not fit an 8-bit code")
 
 
+def _code_of(codes: torch.Tensor) -> int:
+    """The C ABI's code type of an int8 / uint8 tensor of codes."""
+    return native.CODE_U8 if codes.dtype == torch.uint8 else native.CODE_I8
+
+
 def _packed_shape(x):
     return tuple(x.shape[:-1]) + (x.shape[-1] // 2,) if x.dim() and x.shape[-1] % 2 == 0 and x.is_contiguous() \
         else (x.numel() // 2,)
@@ -657,9 +662,8 @@ def fq_join(x, scale: float, zero_point: int, qmin: int, qmax: int, residual=Non
     with _maybe_on_device(x):
         if r_codes is not None:
             name = "mctq_fq_join_rc_f32"
-            rc = _launch(lib.mctq_fq_join_rc_f32, x.data_ptr(), r_codes.data_ptr(),
-                         native.CODE_U8 if r_codes.dtype == torch.uint8 else native.CODE_I8, r_scale, r_zp, int(bool(relu)),
-                         *outputs, _stream(x))
+            rc = _launch(lib.mctq_fq_join_rc_f32, x.data_ptr(), r_codes.data_ptr(), _code_of(r_codes), r_scale, r_zp,
+                         int(bool(relu)), *outputs, _stream(x))
         else:
             name = "mctq_fq_join_f32"
             rc = _launch(lib.mctq_fq_join_f32, x.data_ptr(), None if residual is None else residual.data_ptr(), int(bool(relu)),
@@ -669,14 +673,32 @@ def fq_join(x, scale: float, zero_point: int, qmin: int, qmax: int, residual=Non
     return y, codes
 
 
-def _pair(v, what: str):
+def _pair(v, what: str, caller: str = "codes_im2col"):
     """An int or a pair of ints (torch.nn.Conv2d's kernel_size / stride / padding / dilation) -> (h, w)."""
     if isinstance(v, int):
         return v, v
     v = tuple(v)
     if len(v) != 2 or not all(isinstance(e, int) for e in v):
-        raise ValueError(f"codes_im2col: {what} must be an int or a pair of ints, got {v!r}")
+        raise ValueError(f"{caller}: {what} must be an int or a pair of ints, got {v!r}")
     return v
+
+
+def _conv_out_size(n: int, k: int, s: int, p: int, d: int) -> int:
+    """Outputs along one axis of a convolution: ``n`` inputs, kernel ``k``, stride ``s``, padding ``p``, dilation ``d``."""
+    return (n + 2 * p - d * (k - 1) - 1) // s + 1
+
+
+def _conv_geometry(h: int, w: int, kernel_size, stride, padding, dilation, caller: str):
+    """A convolution of an ``h`` x ``w`` image, its arguments ints or pairs -> the pairs ``(kh, kw), (sh, sw), (ph, pw), (dh, dw)``
+    and the output size ``(ho, wo)``; ValueError, in ``caller``'s name, for arguments that describe no convolution of it."""
+    (kh, kw), (sh, sw) = _pair(kernel_size, "kernel_size", caller), _pair(stride, "stride", caller)
+    (ph, pw), (dh, dw) = _pair(padding, "padding", caller), _pair(dilation, "dilation", caller)
+    if min(kh, kw, sh, sw, dh, dw) < 1 or min(ph, pw) < 0:
+        raise ValueError(f"{caller}: kernel_size, stride and dilation must be at least 1 and padding at least 0")
+    ho, wo = _conv_out_size(h, kh, sh, ph, dh), _conv_out_size(w, kw, sw, pw, dw)
+    if ho <= 0 or wo <= 0:
+        raise ValueError(f"{caller}: a {kh}x{kw} kernel (dilation {dh}x{dw}) does not fit the padded {h}x{w} image")
+    return (kh, kw), (sh, sw), (ph, pw), (dh, dw), (ho, wo)
 
 
 def codes_im2col(codes_nhwc, kernel_size, stride=1, padding=0, dilation=1, pad_code: int = 0):
@@ -689,19 +711,12 @@ def codes_im2col(codes_nhwc, kernel_size, stride=1, padding=0, dilation=1, pad_c
         raise ValueError("codes_im2col takes [N, H, W, C] tensors")
     if codes_nhwc.dtype not in (torch.int8, torch.uint8):
         raise NotImplementedError(f"codes_im2col: int8 / uint8 codes only, got {codes_nhwc.dtype}")
-    (kh, kw), (sh, sw) = _pair(kernel_size, "kernel_size"), _pair(stride, "stride")
-    (ph, pw), (dh, dw) = _pair(padding, "padding"), _pair(dilation, "dilation")
     pad_code = int(pad_code)
     lo, hi = (0, 255) if codes_nhwc.dtype == torch.uint8 else (-128, 127)
     if not lo <= pad_code <= hi:
         raise ValueError(f"codes_im2col: pad_code {pad_code} is no {codes_nhwc.dtype} code")
-    if min(kh, kw, sh, sw, dh, dw) < 1 or min(ph, pw) < 0:
-        raise ValueError("codes_im2col: kernel_size, stride and dilation must be at least 1 and padding at least 0")
     b, h, w, c = codes_nhwc.shape
-    ho = (h + 2 * ph - dh * (kh - 1) - 1) // sh + 1
-    wo = (w + 2 * pw - dw * (kw - 1) - 1) // sw + 1
-    if ho <= 0 or wo <= 0:
-        raise ValueError(f"codes_im2col: a {kh}x{kw} kernel (dilation {dh}x{dw}) does not fit the padded {h}x{w} image")
+    (kh, kw), (sh, sw), (ph, pw), (dh, dw), (ho, wo) = _conv_geometry(h, w, kernel_size, stride, padding, dilation, "codes_im2col")
     x = codes_nhwc if codes_nhwc.is_contiguous() else codes_nhwc.contiguous()
     if x.is_cuda:
         lib = native.load()

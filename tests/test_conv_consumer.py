@@ -264,7 +264,7 @@ def test_fusion_of_convolutions_is_opt_in():
         x = torch.randn(2, 32, 5, 7) * 1.5
         ref = model(x)
         assert consumers.fuse_linear_consumers(model) == 0              # default: left alone, exactly as before
-        assert not isinstance(model[1], consumers.QuantizedLinear) and torch.equal(model(x), ref)
+        assert not isinstance(model[1], consumers.IntegerConsumer) and torch.equal(model(x), ref)
         assert consumers.fuse_linear_consumers(model, convolutions=True) == 1
         assert isinstance(model[0], torch.nn.Identity) and type(model[1]) is consumers.QuantizedConv2d
         y = model(x)
@@ -375,7 +375,7 @@ def check_bottleneck(device):
     assert n0 == 1 and type(gm0.get_submodule("c3_qlinear")) is consumers.QuantizedConv1x1
     gm, n = consumers.fuse_linear_consumers_fx(model, convolutions=True)
     assert n == 2
-    fused = {name: m for name, m in gm.named_modules() if isinstance(m, consumers.QuantizedLinear)}
+    fused = {name: m for name, m in gm.named_modules() if isinstance(m, consumers.IntegerConsumer)}
     assert {name: type(m) for name, m in fused.items()} == {"c2_qlinear": consumers.QuantizedConv2d,
                                                              "c3_qlinear": consumers.QuantizedConv1x1}
     called = [node.target for node in gm.graph.nodes if node.op == "call_module"]

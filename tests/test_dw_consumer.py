@@ -189,6 +189,8 @@ def test_qconv_dw_i8_refuses_bad_operands():
         consumers.qconv_dw_i8(a, 256, 0.1, w, ws, b, 3, 1, 1)                                      # no uint8 code
     with pytest.raises(ValueError):
         consumers.qconv_dw_i8(a, 114, 0.1, w, ws, b, 3, 0, 1)
+    with pytest.raises(ValueError, match="qconv_dw_i8: stride"):                                   # refused in this function's own name
+        consumers.qconv_dw_i8(a, 114, 0.1, w, ws, b, 3, (1, 1, 1), 1)
     with pytest.raises(ValueError):
         consumers.qconv_dw_i8(a, 114, 0.1, torch.zeros(9, 9, 16, dtype=torch.int8), ws, b, 9, 1, 1)  # 9 > 5 + 2
 
@@ -396,7 +398,7 @@ def check_inverted_residual(device):
     assert n0 == 2 and [node.target for node in gm0.graph.nodes if node.op == "call_module"] == ["c1_qlinear", "h2", "c2", "c3_qlinear"]
     gm, n = consumers.fuse_linear_consumers_fx(model, depthwise=True)
     assert n == 3
-    fused = {name: type(m) for name, m in gm.named_modules() if isinstance(m, consumers.QuantizedLinear)}
+    fused = {name: type(m) for name, m in gm.named_modules() if isinstance(m, consumers.IntegerConsumer)}
     assert fused == {"c1_qlinear": consumers.QuantizedConv1x1, "c2_qlinear": consumers.QuantizedDepthwiseConv2d,
                      "c3_qlinear": consumers.QuantizedConv1x1}
     assert [node.target for node in gm.graph.nodes if node.op == "call_module"] == ["c1_qlinear", "c2_qlinear", "c3_qlinear"]
@@ -412,6 +414,62 @@ def check_inverted_residual(device):
 
 def test_fx_rewrite_of_an_inverted_residual_cpu():
     check_inverted_residual("cpu")
+
+
+# ---- what the four consumer classes share -----------------------------------------------------------------------------------
+
+CLASSES = ["QuantizedLinear", "QuantizedConv1x1", "QuantizedConv2d", "QuantizedDepthwiseConv2d"]
+
+
+def consumer_pairs(act="signed"):
+    """class name -> ([activation holder, wrapped layer], the shape of its input): a Linear with 16 inputs, 16-channel
+    convolutions on a 4 x 4 image."""
+    import mct_quantizers_amd as mq
+    from test_conv_consumer import activation_quantizer, weights_quantizer
+    torch.manual_seed(0)
+    lin = torch.nn.Linear(16, 24)
+    linear = [mq.PytorchActivationQuantizationHolder(activation_quantizer(act)),
+              mq.PytorchQuantizationWrapper(lin, {"weight": weights_quantizer(lin.weight, "sym", True)})]
+    image = (2, 16, 4, 4)
+    return {"QuantizedLinear": (linear, (3, 16)), "QuantizedConv1x1": (conv_pair(k=1, padding=0, act=act), image),
+            "QuantizedConv2d": (conv_pair(act=act), image), "QuantizedDepthwiseConv2d": (conv_pair(O=16, groups=16, act=act), image)}
+
+
+@pytest.mark.parametrize("name", CLASSES)
+def test_activation_codes_of_the_wrong_type_are_refused(name):
+    from mct_quantizers_amd import consumers
+    (holder, wrapper), shape = consumer_pairs("signed")[name]
+    qc = getattr(consumers, name).from_wrapper(wrapper, holder.activation_holder_quantizer)
+    assert qc(torch.zeros(shape, dtype=torch.int8)).dtype == torch.float32           # the quantizer's own code type is taken
+    with pytest.raises(TypeError, match="do not match this layer's quantizer"):
+        qc(torch.zeros(shape, dtype=torch.uint8))
+
+
+def test_consumer_class_hierarchy():
+    from mct_quantizers_amd import consumers
+    assert all(issubclass(getattr(consumers, name), consumers.IntegerConsumer) for name in CLASSES)
+    assert issubclass(consumers.QuantizedConv1x1, consumers.QuantizedLinear)          # products over rows: they call its forward
+    assert issubclass(consumers.QuantizedConv2d, consumers.QuantizedLinear)
+    assert not issubclass(consumers.QuantizedDepthwiseConv2d, consumers.QuantizedLinear)
+
+
+def test_consumers_construct_no_stand_in_layers(monkeypatch):
+    """A consumer reads geometry and bias from the wrapped layer and owns the wrapper's weight: it builds no nn.Linear or
+    nn.Conv2d of its own, at construction or on forward."""
+    from mct_quantizers_amd import consumers
+    pairs = consumer_pairs("uniform")                      # the wrapped models first: they need the real constructors
+
+    def refuse(self, *args, **kwargs):
+        raise AssertionError(f"a consumer constructed a {type(self).__name__}")
+
+    monkeypatch.setattr(torch.nn.Linear, "__init__", refuse)
+    monkeypatch.setattr(torch.nn.Conv2d, "__init__", refuse)
+    with pytest.raises(AssertionError):
+        torch.nn.Linear(16, 16)                            # (the patch is in place)
+    for name, ((holder, wrapper), shape) in pairs.items():
+        qc = getattr(consumers, name).from_wrapper(wrapper, holder.activation_holder_quantizer)
+        assert type(qc) is getattr(consumers, name) and qc.weight is wrapper.weight and qc.bias is wrapper.layer.bias
+        assert qc(torch.randn(shape)).dtype == torch.float32
 
 
 # ---- the C ABI without a GPU -----------------------------------------------------------------------------------------------

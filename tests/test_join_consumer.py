@@ -254,14 +254,14 @@ def test_rewrite_with_shared_holders_takes_every_convolution_and_without_is_unch
     gm00, n00 = consumers.fuse_linear_consumers_fx(ResidualStack(), convolutions=True, shared_holders=False)
     assert n00 == 4 and str(gm00.graph) == str(gm0.graph) and gm00.code == gm0.code
     gm, _ = rewritten_stack()
-    kinds = {name: type(m) for name, m in gm.named_modules() if isinstance(m, consumers.QuantizedLinear)}
+    kinds = {name: type(m) for name, m in gm.named_modules() if isinstance(m, consumers.IntegerConsumer)}
     assert kinds == {"A_c1_qlinear": consumers.QuantizedConv1x1, "A_c2_qlinear": consumers.QuantizedConv2d,
                      "A_c3_qlinear": consumers.QuantizedConv1x1, "A_down_qlinear": consumers.QuantizedConv2d,
                      "B_c1_qlinear": consumers.QuantizedConv1x1, "B_c2_qlinear": consumers.QuantizedConv2d,
                      "B_c3_qlinear": consumers.QuantizedConv1x1}
     # chain=True keeps its meaning: a join between two consumers is no direct feed
     gmc, nc = consumers.fuse_linear_consumers_fx(ResidualStack(), convolutions=True, shared_holders=True, chain=True)
-    assert nc == 7 and all(m.emit_codes_for is None for m in gmc.modules() if isinstance(m, consumers.QuantizedLinear))
+    assert nc == 7 and all(m.emit_codes_for is None for m in gmc.modules() if isinstance(m, consumers.IntegerConsumer))
 
 
 def test_joins_in_the_rewritten_graph():

@@ -343,7 +343,7 @@ def test_four_block_stack_graph():
     # the input holder (nothing in front to emit its codes) and the three block ends; the eight ReLU-only joins are gone
     assert joins == {"h0_join": (False, False, False, False), "A_a3_1_join": (True, True, False, False),
                      "B_a3_1_join": (True, True, False, True), "C_a3_1_join": (True, True, True, True)}
-    consumers_ = {name: m for name, m in gm.named_modules() if isinstance(m, consumers.QuantizedLinear)}
+    consumers_ = {name: m for name, m in gm.named_modules() if isinstance(m, consumers.IntegerConsumer)}
     assert len(consumers_) == 13
     emitting = sorted(name for name, m in consumers_.items() if m.emit_codes_for is not None)
     assert emitting == sorted(f"{b}_{c}_qlinear" for b in "ABCD" for c in ("c1", "c2"))
@@ -426,7 +426,7 @@ def test_without_the_keyword_nothing_changes():
         gm, n = consumers.fuse_linear_consumers_fx(ResidualStack(), **switches)
         gm_off, n_off = consumers.fuse_linear_consumers_fx(ResidualStack(), stay_on_codes=False, **switches)
         assert n == n_off and str(gm.graph) == str(gm_off.graph) and gm.code == gm_off.code
-        assert all(m.emit_clamp is None for m in gm.modules() if isinstance(m, consumers.QuantizedLinear))
+        assert all(m.emit_clamp is None for m in gm.modules() if isinstance(m, consumers.IntegerConsumer))
     gm, _ = consumers.fuse_linear_consumers_fx(ResidualStack(), convolutions=True, shared_holders=True)
     assert _targets(gm) == ["h0_join", "A_c1_qlinear", "A_a1_1_join", "A_c2_qlinear", "A_a2_1_join", "A_c3_qlinear",
                             "A_down_qlinear", "A_a3_1_join", "B_c1_qlinear", "B_a1_1_join", "B_c2_qlinear", "B_a2_1_join",
@@ -509,8 +509,8 @@ def test_wrapped_resnet50_structure():
     assert (joins["3_a1_1_join"].relu, joins["3_a1_1_join"].want_float) == (True, False)
     assert sum(joins[t].residual_codes is not None for t in residual) == 11
     assert [t for t in names if joins[t].want_float] == [residual[-1]] == ["17_a3_1_join"]
-    emitting = [m for m in gm.modules() if isinstance(m, consumers.QuantizedLinear) and m.emit_codes_for is not None]
-    assert len(emitting) == 31 and len([m for m in gm.modules() if isinstance(m, consumers.QuantizedLinear)]) == 50
+    emitting = [m for m in gm.modules() if isinstance(m, consumers.IntegerConsumer) and m.emit_codes_for is not None]
+    assert len(emitting) == 31 and len([m for m in gm.modules() if isinstance(m, consumers.IntegerConsumer)]) == 50
     # an unsigned domain with zero point 0: the ReLU's code is the domain's lower end, nothing is left to narrow
     assert all(m.emit_clamp is None and m.emit_codes_for[1:] == (0, 0, 255) for m in emitting)
     relus = [t for t in _targets(gm) if isinstance(gm.get_submodule(t), torch.nn.ReLU)]

@@ -169,7 +169,7 @@ def test_fusion_of_uniform_weights_is_opt_in():
     x = torch.randn(7, 64) * 1.5
     ref = model(x)
     assert consumers.fuse_linear_consumers(model) == 0               # default: left alone, exactly as before
-    assert not isinstance(model[1], consumers.QuantizedLinear) and torch.equal(model(x), ref)
+    assert not isinstance(model[1], consumers.IntegerConsumer) and torch.equal(model(x), ref)
     assert consumers.fuse_linear_consumers(model, uniform_weights=True) == 1
     assert isinstance(model[0], torch.nn.Identity) and isinstance(model[1], consumers.QuantizedLinear)
     y = model(x)
