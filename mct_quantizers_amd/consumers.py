@@ -64,7 +64,7 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
-from mct_quantizers_amd.hip import native, ops
+from mct_quantizers_amd.hip import ops
 from mct_quantizers_amd.pytorch.containers import PytorchActivationQuantizationHolder, PytorchQuantizationWrapper
 
 _MAX_K = 32768
@@ -156,14 +156,10 @@ def codes_rowsum(a_codes: torch.Tensor, a_zero_point: int) -> torch.Tensor:
     if a_codes.is_cuda:
         if K % 16 or K > _MAX_K:
             raise NotImplementedError(f"mctq_codes_rowsum needs K % 16 == 0 and K <= {_MAX_K}, got K={K}")
-        lib = native.load()
         a_codes = a_codes.contiguous()
-        with ops._maybe_on_device(a_codes):
-            out = a_codes.new_empty((M,), dtype=torch.int32)
-            rc = ops._launch(lib.mctq_codes_rowsum, a_codes.data_ptr(), ops._code_of(a_codes), int(a_zero_point), out.data_ptr(),
-                             M, K, ops._stream(a_codes))
-        if rc:
-            native.check(rc, "mctq_codes_rowsum")
+        out = a_codes.new_empty((M,), dtype=torch.int32)
+        ops._gpu_call("mctq_codes_rowsum", a_codes, a_codes.data_ptr(), ops._code_of(a_codes), int(a_zero_point), out.data_ptr(),
+                      M, K)
         return out
     ops._cpu_route_allowed()
     return (a_codes.to(torch.int32) - int(a_zero_point)).sum(dim=1, dtype=torch.int32)
@@ -188,27 +184,23 @@ def _launch_consumer(name, a_codes, a_zero_point, a_scale, w, lut, w_scales, w_r
     if K % 16 or K > _MAX_K:
         raise NotImplementedError(f"{name} needs K % 16 == 0 and K <= {_MAX_K}, got K={K}")
     _check_consumer_operands(a_codes, w_scales, w_rowsum, bias, w_zero_points)
-    lib = native.load()
     a_codes, w = a_codes.contiguous(), w.contiguous()
     if w_zero_points is not None:
         name += "_zp"
         a_rowsum = codes_rowsum(a_codes, a_zero_point)       # named: it must outlive the launch, or y is allocated over it
         zp = (w_zero_points.data_ptr(), a_rowsum.data_ptr())
-        fn = getattr(lib, name)
     else:
         zp = ()
-        fn = getattr(lib, name if packed or out_codes is None else "mctq_qlinear_i8_codes")
-    if fn is lib.mctq_qlinear_i8:
+        if not packed and out_codes is not None:
+            name = "mctq_qlinear_i8_codes"
+    if name == "mctq_qlinear_i8":
         tdt, form = torch.float32, ()                   # the float32-only entry point: no output form among its arguments
     else:
         tdt, *form = _output_form(out_codes)
-    with ops._maybe_on_device(a_codes):
-        y = a_codes.new_empty((M, N), dtype=tdt)
-        rc = ops._launch(fn, a_codes.data_ptr(), ops._code_of(a_codes), int(a_zero_point), float(a_scale), w.data_ptr(), *lut,
-                         w_scales.data_ptr(), w_rowsum.data_ptr(), None if bias is None else bias.data_ptr(), y.data_ptr(), *form,
-                         *zp, M, N, K, ops._stream(a_codes))
-    if rc:
-        native.check(rc, name)
+    y = a_codes.new_empty((M, N), dtype=tdt)
+    ops._gpu_call(name, a_codes, a_codes.data_ptr(), ops._code_of(a_codes), int(a_zero_point), float(a_scale), w.data_ptr(), *lut,
+                  w_scales.data_ptr(), w_rowsum.data_ptr(), None if bias is None else bias.data_ptr(), y.data_ptr(), *form, *zp,
+                  M, N, K)
     return y
 
 
@@ -264,17 +256,12 @@ def qconv_dw_i8(a_codes_nhwc: torch.Tensor, a_zero_point: int, a_scale: float, w
     if a_codes_nhwc.is_cuda:
         if c % 16 or kh * kw > 256:
             raise NotImplementedError(f"mctq_qconv_dw_i8 needs C % 16 == 0 and kh * kw <= 256, got C={c}, {kh}x{kw}")
-        lib = native.load()
         x, w_codes = a_codes_nhwc.contiguous(), w_codes.contiguous()
         tdt, *form = _output_form(out_codes)
-        with ops._maybe_on_device(x):
-            y = x.new_empty((b, ho, wo, c), dtype=tdt)
-            rc = ops._launch(lib.mctq_qconv_dw_i8, x.data_ptr(), ops._code_of(x), a_zero_point, float(a_scale), w_codes.data_ptr(),
-                             w_scales.data_ptr(), None if w_zero_points is None else w_zero_points.data_ptr(),
-                             None if bias is None else bias.data_ptr(), y.data_ptr(), *form, b, h, w_, c, kh, kw, sh, sw, ph, pw,
-                             dh, dw, ops._stream(x))
-        if rc:
-            native.check(rc, "mctq_qconv_dw_i8")
+        y = x.new_empty((b, ho, wo, c), dtype=tdt)
+        ops._gpu_call("mctq_qconv_dw_i8", x, x.data_ptr(), ops._code_of(x), a_zero_point, float(a_scale), w_codes.data_ptr(),
+                      w_scales.data_ptr(), None if w_zero_points is None else w_zero_points.data_ptr(),
+                      None if bias is None else bias.data_ptr(), y.data_ptr(), *form, b, h, w_, c, kh, kw, sh, sw, ph, pw, dh, dw)
         return y
     ops._cpu_route_allowed()
     w32 = w_codes.to(torch.int32)

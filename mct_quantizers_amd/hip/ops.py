@@ -11,7 +11,11 @@ Routing:
   * GPU (HIP) float32 / float16 / bfloat16 / float64 tensor -> the gfx950 kernels through the C ABI, on torch's
     current stream.  No fallback: a missing library raises.  Two interchangeable bindings of the SAME extern "C"
     entry points: the compiled one (csrc/binding/mctq_torch.cpp: checks, allocation, stream lookup and launch in
-    one CPython call -- small activations are launch-bound) and ctypes (hip/native.py).
+    one CPython call -- small activations are launch-bound) and ctypes (hip/native.py).  Every launch of the ctypes
+    binding, here and in consumers.py, is one ``_gpu_call(symbol, tensor, *args)``: it looks the symbol up, makes the
+    tensor's device current if it is not, appends torch's current stream of that device (the last argument of every
+    launching entry point), and raises in the symbol's name when the library refuses; the callers keep their checks
+    and allocations.
   * CPU tensor                -> the very ATen ops the reference runs on a CPU tensor
     (BASELINE config 1, "torch-cpu plumbing"); not a substitute for the GPU path.
   * torch.jit tracing (TorchScript / ONNX export without enable_custom_impl) -> the ATen operators / torch op
@@ -112,51 +116,26 @@ _raw_stream = torch._C._cuda_getCurrentRawStream      # (device index) -> hipStr
 _current_device = torch._C._cuda_getDevice
 
 
-def _stream(x: torch.Tensor) -> int:
-    return _raw_stream(x.get_device())
-
-
-class _on_device:
-    """Make x's device current for the launch (only entered when it is not already current)."""
-    __slots__ = ("idx", "prev")
-
-    def __init__(self, idx):
-        self.idx = idx
-        self.prev = -1
-
-    def __enter__(self):
-        self.prev = _current_device()
-        torch.cuda.set_device(self.idx)
-
-    def __exit__(self, *exc):
-        torch.cuda.set_device(self.prev)
-        return False
-
-
-def _launch(fn, *args):
-    """Call a C-ABI launch function; with MCTQ_ROCTX=1 the launch is wrapped in a roctx range named after it."""
-    if native.TRACE:
-        with native.trace_range(fn.__name__):
-            return fn(*args)
-    return fn(*args)
-
-
-class _noop:
-    __slots__ = ()
-
-    def __enter__(self):
-        return None
-
-    def __exit__(self, *exc):
-        return False
-
-
-_NOOP = _noop()
-
-
-def _maybe_on_device(x):
-    idx = x.get_device()
-    return _NOOP if idx == _current_device() else _on_device(idx)
+def _gpu_call(name: str, on: torch.Tensor, *args) -> None:
+    """THE launch of the ctypes route: the C-ABI entry point ``name(*args, stream)`` on torch's current stream of ``on``'s
+    device, that device made current for the call when it is not already (and the previous one restored).  With
+    MCTQ_ROCTX=1 the call is wrapped in a roctx range named after the symbol; a refusal raises in the symbol's name."""
+    fn = getattr(native.load(), name)
+    idx = on.get_device()
+    prev = _current_device()
+    if prev != idx:
+        torch.cuda.set_device(idx)
+    try:
+        if native.TRACE:
+            with native.trace_range(name):
+                rc = fn(*args, _raw_stream(idx))
+        else:
+            rc = fn(*args, _raw_stream(idx))
+    finally:
+        if prev != idx:
+            torch.cuda.set_device(prev)
+    if rc:
+        native.check(rc, name)
 
 
 _DTYPES = {torch.float32: native.DT_F32, torch.float16: native.DT_F16, torch.bfloat16: native.DT_BF16,
@@ -199,29 +178,25 @@ def _fast_mod():
 # GPU launches
 # ------------------------------------------------------------------------------------------
 
+def _check_aten_range(zero_point: int, qmin: int, qmax: int):
+    """ATen's check of a per-tensor zero point against the clamp domain, with its messages."""
+    if not qmin <= zero_point <= qmax:
+        if qmin > qmax:
+            raise RuntimeError("`quant_min` should be less than or         equal to `quant_max`.")
+        raise RuntimeError("`zero_point` must be between `quant_min` and `quant_max`.")
+
+
 def _hip_fq_per_tensor(x, scale: float, zero_point: int, qmin: int, qmax: int):
     # hot for small activations (launch-bound): keep the Python between the caller and the launch short
     dt = _DTYPES.get(x.dtype)
     if dt is None:
         _dtype_code(x, "fq_per_tensor")
-    if not qmin <= zero_point <= qmax:                  # ATen's checks and messages
-        if qmin > qmax:
-            raise RuntimeError("`quant_min` should be less than or         equal to `quant_max`.")
-        raise RuntimeError("`zero_point` must be between `quant_min` and `quant_max`.")
-    lib = native.load()
+    if not qmin <= zero_point <= qmax:
+        _check_aten_range(zero_point, qmin, qmax)
     if not x.is_contiguous():
         x = _dense_input(x)
     y = torch.empty_like(x)
-    idx = x.get_device()
-    if idx == _current_device():
-        rc = _launch(lib.mctq_fq_per_tensor, x.data_ptr(), y.data_ptr(), x.numel(), dt, scale, zero_point, qmin, qmax,
-                                    _raw_stream(idx))
-    else:
-        with _on_device(idx):
-            rc = _launch(lib.mctq_fq_per_tensor, x.data_ptr(), y.data_ptr(), x.numel(), dt, scale, zero_point, qmin, qmax,
-                                        _raw_stream(idx))
-    if rc:
-        native.check(rc, "mctq_fq_per_tensor")
+    _gpu_call("mctq_fq_per_tensor", x, x.data_ptr(), y.data_ptr(), x.numel(), dt, scale, zero_point, qmin, qmax)
     return y
 
 
@@ -244,17 +219,12 @@ def _hip_fq_per_channel(x, scales, zero_points, axis: int, qmin: int, qmax: int,
         _check_axis(x, scales.numel(), axis)
     scales = _param_on(x, scales, "scales", torch.float32)
     zero_points = _param_on(x, zero_points, "zero_points", torch.int32)
-    lib = native.load()
     if not x.is_contiguous():
         x = _dense_input(x)
     y = torch.empty_like(x)
     outer, c, inner = _channel_view(x, axis)
-    idx = x.get_device()
-    with (_NOOP if idx == _current_device() else _on_device(idx)):
-        rc = _launch(lib.mctq_fq_per_channel, x.data_ptr(), y.data_ptr(), outer, c, inner, dt, scales.data_ptr(),
-                                     None if zero_zps else zero_points.data_ptr(), qmin, qmax, _raw_stream(idx))
-    if rc:
-        native.check(rc, "mctq_fq_per_channel")
+    _gpu_call("mctq_fq_per_channel", x, x.data_ptr(), y.data_ptr(), outer, c, inner, dt, scales.data_ptr(),
+              None if zero_zps else zero_points.data_ptr(), qmin, qmax)
     return y
 
 
@@ -266,21 +236,16 @@ def _hip_fq_per_tensor_tqp(x, scale, zero_point, qmin: int, qmax: int):
     scale, zero_point = scale.reshape(-1)[:1], zero_point.reshape(-1)[:1]
     scale = _param_on(x, scale, "scale", torch.float32)
     zero_point = _param_on(x, zero_point, "zero_point", torch.int32)
-    lib = native.load()
     if not x.is_contiguous():
         x = _dense_input(x)
     y = torch.empty_like(x)
-    with _maybe_on_device(x):
-        rc = _launch(lib.mctq_fq_per_tensor_tqp, x.data_ptr(), y.data_ptr(), x.numel(), dt, scale.data_ptr(),
-                     zero_point.data_ptr(), qmin, qmax, _stream(x))
-    if rc:
-        native.check(rc, "mctq_fq_per_tensor_tqp")
+    _gpu_call("mctq_fq_per_tensor_tqp", x, x.data_ptr(), y.data_ptr(), x.numel(), dt, scale.data_ptr(), zero_point.data_ptr(),
+              qmin, qmax)
     return y
 
 
 def _hip_fq_batched(items):
     """ctypes route of fq_batched (see below): items = [(x, scales, zero_points | None, axis | None, qmin, qmax)]."""
-    lib = native.load()
     n = len(items)
     arr = (native.FqItem * n)()
     outs, keep = [], []
@@ -316,10 +281,7 @@ def _hip_fq_batched(items):
         outs.append(y)
         keep.append((x, scales, zps))
     if n:
-        with _maybe_on_device(outs[0]):
-            rc = _launch(lib.mctq_fq_batched, arr, n, _stream(outs[0]))
-        if rc:
-            native.check(rc, "mctq_fq_batched")
+        _gpu_call("mctq_fq_batched", outs[0], arr, n)
     return outs
 
 
@@ -329,6 +291,25 @@ def _lut_result(x, y):
     The kernels work in storage order (same strides as the input); a permuted input pays one layout copy here to hand
     back what the reference hands back."""
     return y if x.is_contiguous() else y.contiguous()
+
+
+def _lut_family(x, dt: int, lut, table, steps, mult: float, cmin: float, cmax: float):
+    """Which LUT kernels run on ``x`` -> ``(stem, suffix, book, entries)``: the entry points are
+    ``mctq_<stem>_per_{tensor,channel}<suffix>`` and take ``book``'s pointer and ``entries`` as their codebook arguments.
+    float64 tensors: the DOUBLE threshold list of an integer codebook ("luts", "_f64"), otherwise the literal scan; other
+    storage types: the decision ``table`` ("lutt"), the sorted threshold list ``steps`` of an integer codebook too wide for the
+    table (binary search in LDS; "luts"), or the literal first-minimum scan (non-integer codebooks, wide bit widths; "lut")."""
+    if dt == native.DT_F64:
+        s64 = _op_steps64(lut, mult, cmin, cmax)
+        if s64 is not None:
+            return "luts", "_f64", s64[0], s64[1]
+    elif table is not None:
+        table = _param_on(x, table, "table", torch.float32)
+        return "lutt", "", table, table.shape[0] - 1
+    elif steps is not None:
+        steps = _param_on(x, steps, "steps", torch.float32)
+        return "luts", "", steps, steps.numel()
+    return "lut", "", lut, lut.numel()
 
 
 def _hip_lut_per_tensor(x, lut, thr_div: float, thr_mul: float, mult: float, cmin: float, cmax: float, table=None,
@@ -345,42 +326,20 @@ def _hip_lut_per_tensor(x, lut, thr_div: float, thr_mul: float, mult: float, cmi
             y = f.lutt_per_tensor(x, table, step_round, thr_div, thr_mul, mult, cmin, cmax)
             if y is not NotImplemented:
                 return y if x.is_contiguous() else y.contiguous()      # see _lut_result
-    lib = native.load()
     x_in = x
     x = _dense_input(x)
     y = torch.empty_like(x, dtype=torch.float32)
     lut = _param_on(x, lut, "lut_values", torch.float32)
-    with _maybe_on_device(x):
-        s64 = _op_steps64(lut, mult, cmin, cmax) if dt == native.DT_F64 else None
-        if s64 is not None:
-            # float64 tensor, integer codebook: the threshold list evaluated in double (the divisor is the activation
-            # quantizer's double, or a weights quantizer's float32 sum widened -- the same number either way)
-            rc = _launch(lib.mctq_luts_per_tensor_f64, x.data_ptr(), y.data_ptr(), x.numel(),
-                         thr_div64 if thr_div64 is not None else thr_div, thr_mul, s64[0].data_ptr(), s64[1], mult, cmin,
-                         cmax, _stream(x))
-        elif dt == native.DT_F64:
-            if thr_div64 is not None:
-                rc = _launch(lib.mctq_lut_per_tensor_f64, x.data_ptr(), y.data_ptr(), x.numel(), thr_div64, thr_mul,
-                             lut.data_ptr(), lut.numel(), mult, cmin, cmax, _stream(x))
-            else:
-                rc = _launch(lib.mctq_lut_per_tensor, x.data_ptr(), y.data_ptr(), x.numel(), dt, 0, thr_div, thr_mul,
-                             lut.data_ptr(), lut.numel(), mult, cmin, cmax, _stream(x))
-        elif table is not None:
-            table = _param_on(x, table, "table", torch.float32)
-            rc = _launch(lib.mctq_lutt_per_tensor, x.data_ptr(), y.data_ptr(), x.numel(), dt, step_round, thr_div, thr_mul,
-                                          table.data_ptr(), table.shape[0] - 1, mult, cmin, cmax, _stream(x))
-        elif steps is not None:
-            # integer codebook too wide for the table: sorted threshold list, binary search in LDS
-            steps = _param_on(x, steps, "steps", torch.float32)
-            rc = _launch(lib.mctq_luts_per_tensor, x.data_ptr(), y.data_ptr(), x.numel(), dt, step_round, thr_div, thr_mul,
-                         steps.data_ptr(), steps.numel(), mult, cmin, cmax, _stream(x))
-        else:
-            # literal first-minimum scan (non-integer codebooks, wide bit widths): every storage type, incl. the
-            # per-step half-precision roundings of a half activation (step_round)
-            rc = _launch(lib.mctq_lut_per_tensor, x.data_ptr(), y.data_ptr(), x.numel(), dt, step_round, thr_div, thr_mul,
-                                         lut.data_ptr(), lut.numel(), mult, cmin, cmax, _stream(x))
-    if rc:
-        native.check(rc, "mctq_lut_per_tensor")
+    stem, suffix, book, n_book = _lut_family(x, dt, lut, table, steps, mult, cmin, cmax)
+    if suffix or (dt == native.DT_F64 and thr_div64 is not None):
+        # the divisor stays a double: the activation quantizer's, or a weights quantizer's float32 sum widened -- the same
+        # number either way
+        _gpu_call(f"mctq_{stem}_per_tensor_f64", x, x.data_ptr(), y.data_ptr(), x.numel(),
+                  thr_div if thr_div64 is None else thr_div64, thr_mul, book.data_ptr(), n_book, mult, cmin, cmax)
+    else:
+        # every storage type, incl. the per-step half-precision roundings of a half activation (step_round)
+        _gpu_call(f"mctq_{stem}_per_tensor", x, x.data_ptr(), y.data_ptr(), x.numel(), dt,
+                  0 if dt == native.DT_F64 else step_round, thr_div, thr_mul, book.data_ptr(), n_book, mult, cmin, cmax)
     return _lut_result(x_in, y)
 
 
@@ -400,31 +359,15 @@ def _hip_lut_per_channel(x, lut, thresholds, eps: float, axis: int, mult: float,
             y = f.lutt_per_channel(x, thresholds, eps, table, axis, mult, cmin, cmax)
             if y is not NotImplemented:
                 return y if x.is_contiguous() else y.contiguous()      # see _lut_result
-    lib = native.load()
     x_in = x
     x = _dense_input(x)
     y = torch.empty_like(x, dtype=torch.float32)
     outer, c, inner = _channel_view(x, axis)
     thresholds = _param_on(x, thresholds, "thresholds", torch.float32)
     lut = _param_on(x, lut, "lut_values", torch.float32)
-    with _maybe_on_device(x):
-        s64 = _op_steps64(lut, mult, cmin, cmax) if dt == native.DT_F64 else None
-        if s64 is not None:
-            rc = _launch(lib.mctq_luts_per_channel_f64, x.data_ptr(), y.data_ptr(), outer, c, inner, thresholds.data_ptr(),
-                         eps, s64[0].data_ptr(), s64[1], mult, cmin, cmax, _stream(x))
-        elif table is not None and dt != native.DT_F64:
-            table = _param_on(x, table, "table", torch.float32)
-            rc = _launch(lib.mctq_lutt_per_channel, x.data_ptr(), y.data_ptr(), outer, c, inner, dt, thresholds.data_ptr(),
-                                           eps, table.data_ptr(), table.shape[0] - 1, mult, cmin, cmax, _stream(x))
-        elif steps is not None and dt != native.DT_F64:
-            steps = _param_on(x, steps, "steps", torch.float32)
-            rc = _launch(lib.mctq_luts_per_channel, x.data_ptr(), y.data_ptr(), outer, c, inner, dt, thresholds.data_ptr(),
-                         eps, steps.data_ptr(), steps.numel(), mult, cmin, cmax, _stream(x))
-        else:
-            rc = _launch(lib.mctq_lut_per_channel, x.data_ptr(), y.data_ptr(), outer, c, inner, dt, thresholds.data_ptr(),
-                                          eps, lut.data_ptr(), lut.numel(), mult, cmin, cmax, _stream(x))
-    if rc:
-        native.check(rc, "mctq_lut_per_channel")
+    stem, suffix, book, n_book = _lut_family(x, dt, lut, table, steps, mult, cmin, cmax)
+    _gpu_call(f"mctq_{stem}_per_channel{suffix}", x, x.data_ptr(), y.data_ptr(), outer, c, inner, *(() if suffix else (dt,)),
+              thresholds.data_ptr(), eps, book.data_ptr(), n_book, mult, cmin, cmax)
     return _lut_result(x_in, y)
 
 
@@ -432,14 +375,9 @@ def _hip_grid_per_tensor(x, lo: float, hi: float, step: float, shifted: bool):
     """Export-time arithmetic (include/mctq_hip.h: mctq_grid_per_tensor_f32), float32 only."""
     if x.dtype != torch.float32:
         raise NotImplementedError(f"export-time quantizer arithmetic on the GPU takes float32 tensors, got {x.dtype}")
-    lib = native.load()
     x = _dense_input(x)
     y = torch.empty_like(x)
-    with _maybe_on_device(x):
-        rc = _launch(lib.mctq_grid_per_tensor_f32, x.data_ptr(), y.data_ptr(), x.numel(), lo, hi, step, int(shifted),
-                     _stream(x))
-    if rc:
-        native.check(rc, "mctq_grid_per_tensor_f32")
+    _gpu_call("mctq_grid_per_tensor_f32", x, x.data_ptr(), y.data_ptr(), x.numel(), lo, hi, step, int(shifted))
     return y
 
 
@@ -447,7 +385,6 @@ def _hip_grid_per_channel(x, los, his, steps, axis: int, shifted: bool):
     if x.dtype != torch.float32:
         raise NotImplementedError(f"export-time quantizer arithmetic on the GPU takes float32 tensors, got {x.dtype}")
     _check_axis(x, steps.numel(), axis)
-    lib = native.load()
     x = _dense_input(x)
     if x.numel() > _SPLIT_ELEMS and steps.numel() > 1:
         return _split_rows(x, axis, (los.reshape(-1), his.reshape(-1), steps.reshape(-1)), torch.float32,
@@ -455,11 +392,8 @@ def _hip_grid_per_channel(x, los, his, steps, axis: int, shifted: bool):
     y = torch.empty_like(x)
     outer, c, inner = _channel_view(x, axis)
     los, his, steps = (t.to(device=x.device, dtype=torch.float32).contiguous() for t in (los, his, steps))
-    with _maybe_on_device(x):
-        rc = _launch(lib.mctq_grid_per_channel_f32, x.data_ptr(), y.data_ptr(), outer, c, inner, los.data_ptr(),
-                     his.data_ptr(), steps.data_ptr(), int(shifted), _stream(x))
-    if rc:
-        native.check(rc, "mctq_grid_per_channel_f32")
+    _gpu_call("mctq_grid_per_channel_f32", x, x.data_ptr(), y.data_ptr(), outer, c, inner, los.data_ptr(), his.data_ptr(),
+              steps.data_ptr(), int(shifted))
     return y
 
 
@@ -479,6 +413,23 @@ def _code_of(codes: torch.Tensor) -> int:
 def _packed_shape(x):
     return tuple(x.shape[:-1]) + (x.shape[-1] // 2,) if x.dim() and x.shape[-1] % 2 == 0 and x.is_contiguous() \
         else (x.numel() // 2,)
+
+
+def _pack4_as_stored(q: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    """CPU routes: the integer codes ``q`` of ``x`` (x's shape), two per byte in x's STORAGE order."""
+    if x.is_contiguous() or not _is_dense(x):
+        return pack4(q.contiguous()).reshape(_packed_shape(x))
+    flat = torch.empty(x.numel(), dtype=torch.int16)          # dense, permuted storage: pack in STORAGE order
+    torch.as_strided(flat, x.shape, x.stride()).copy_(q.to(torch.int16))
+    return pack4(flat).reshape(_packed_shape(x))
+
+
+def _codes_output(x: torch.Tensor, packed4: bool, tdt, code: int, code4: int):
+    """GPU routes: ``(output tensor, the C ABI's code type)`` for the codes of ``x`` -- ``packed4``: uint8 of half the elements
+    and ``code4``, otherwise x's sizes and strides in ``tdt`` and ``code``."""
+    if packed4:
+        return torch.empty(_packed_shape(x), dtype=torch.uint8, device=x.device), code4
+    return torch.empty_like(x, dtype=tdt), code
 
 
 def pack4(q: torch.Tensor) -> torch.Tensor:
@@ -523,41 +474,25 @@ def fq_codes(x, scales, zero_points, axis, qmin: int, qmax: int, scale0: float =
             q = torch.round(xf * (1.0 / scales.float().to(x.device)).reshape(shape)) + \
                 zero_points.to(x.device).reshape(shape).float()
         q = torch.clamp(torch.nan_to_num(q, nan=float(qmin)), qmin, qmax)
-        if packed4:
-            if x.is_contiguous() or not _is_dense(x):
-                return pack4(q.contiguous()).reshape(_packed_shape(x))
-            flat = torch.empty(x.numel(), dtype=torch.int16)          # dense, permuted storage: pack in STORAGE order
-            torch.as_strided(flat, x.shape, x.stride()).copy_(q.to(torch.int16))
-            return pack4(flat).reshape(_packed_shape(x))
-        return q.to(tdt)
+        return _pack4_as_stored(q, x) if packed4 else q.to(tdt)
     dt = _dtype_code(x, "fq_codes")
     if dt == native.DT_F64:
         raise NotImplementedError("fq_codes: integer codes are produced from float32 / float16 / bfloat16 tensors")
-    lib = native.load()
     if not x.is_contiguous():
         x = _dense_input(x)
     if axis is not None and not packed4 and x.numel() > _SPLIT_ELEMS and scales.numel() > 1:
         return _split_rows(x, axis, (scales.reshape(-1), zero_points.reshape(-1)), tdt,
                            lambda xp, ps, ax: fq_codes(xp, ps[0], ps[1], ax, qmin, qmax))
-    if packed4:
-        code = native.CODE_I4 if qmin < 0 else native.CODE_U4
-        y = torch.empty(_packed_shape(x), dtype=torch.uint8, device=x.device)
+    y, code = _codes_output(x, packed4, tdt, code, native.CODE_I4 if qmin < 0 else native.CODE_U4)
+    if axis is None:
+        _gpu_call("mctq_fq_codes_per_tensor", x, x.data_ptr(), y.data_ptr(), x.numel(), dt, code, scale0, zp0, qmin, qmax)
     else:
-        y = torch.empty_like(x, dtype=tdt)
-    idx = x.get_device()
-    with (_NOOP if idx == _current_device() else _on_device(idx)):
-        if axis is None:
-            rc = _launch(lib.mctq_fq_codes_per_tensor, x.data_ptr(), y.data_ptr(), x.numel(), dt, code, scale0, zp0, qmin, qmax,
-                                              _raw_stream(idx))
-        else:
-            _check_axis(x, scales.numel(), axis)
-            scales = _param_on(x, scales, "scales", torch.float32)
-            zero_points = _param_on(x, zero_points, "zero_points", torch.int32)
-            outer, c, inner = _channel_view(x, axis)
-            rc = _launch(lib.mctq_fq_codes_per_channel, x.data_ptr(), y.data_ptr(), outer, c, inner, dt, code,
-                                               scales.data_ptr(), zero_points.data_ptr(), qmin, qmax, _raw_stream(idx))
-    if rc:
-        native.check(rc, "mctq_fq_codes")
+        _check_axis(x, scales.numel(), axis)
+        scales = _param_on(x, scales, "scales", torch.float32)
+        zero_points = _param_on(x, zero_points, "zero_points", torch.int32)
+        outer, c, inner = _channel_view(x, axis)
+        _gpu_call("mctq_fq_codes_per_channel", x, x.data_ptr(), y.data_ptr(), outer, c, inner, dt, code, scales.data_ptr(),
+                  zero_points.data_ptr(), qmin, qmax)
     return y
 
 
@@ -573,13 +508,9 @@ def fq_codes_nhwc(x, qmin: int, qmax: int, scale: float, zero_point: int):
         dt = _dtype_code(x, "fq_codes_nhwc")
         if dt == native.DT_F64:
             raise NotImplementedError("fq_codes_nhwc: float32 / float16 / bfloat16 tensors only")
-        lib = native.load()
         y = torch.empty((b, h, w, c), dtype=tdt, device=x.device)
-        with _maybe_on_device(x):
-            rc = _launch(lib.mctq_fq_codes_nchw_to_nhwc, x.data_ptr(), y.data_ptr(), b, c, h * w, dt, code, float(scale),
-                         int(zero_point), qmin, qmax, _stream(x))
-        if rc:
-            native.check(rc, "mctq_fq_codes_nchw_to_nhwc")
+        _gpu_call("mctq_fq_codes_nchw_to_nhwc", x, x.data_ptr(), y.data_ptr(), b, c, h * w, dt, code, float(scale),
+                  int(zero_point), qmin, qmax)
         return y
     codes = fq_codes(x, None, None, None, qmin, qmax, scale, zero_point)
     return codes.permute(0, 2, 3, 1).contiguous()          # a no-op view + check for channels-last storage
@@ -650,26 +581,18 @@ def fq_join(x, scale: float, zero_point: int, qmin: int, qmax: int, residual=Non
             y = fq_per_tensor(v, scale, zero_point, qmin, qmax) if want_float else None
             codes = fq_codes(v, None, None, None, qmin, qmax, scale, zero_point) if want_codes else None
         return y, codes
-    if want_float and not qmin <= zero_point <= qmax:       # ATen's checks and messages, as fq_per_tensor
-        if qmin > qmax:
-            raise RuntimeError("`quant_min` should be less than or         equal to `quant_max`.")
-        raise RuntimeError("`zero_point` must be between `quant_min` and `quant_max`.")
-    lib = native.load()
+    if want_float:
+        _check_aten_range(zero_point, qmin, qmax)           # as fq_per_tensor
     y = torch.empty_like(x) if want_float else None          # preserve_format: a dense x keeps its strides
     codes = torch.empty_like(x, dtype=tdt) if want_codes else None
     outputs = (None if y is None else y.data_ptr(), None if codes is None else codes.data_ptr(), code or 0, x.numel(),
                float(scale), int(zero_point), int(qmin), int(qmax))
-    with _maybe_on_device(x):
-        if r_codes is not None:
-            name = "mctq_fq_join_rc_f32"
-            rc = _launch(lib.mctq_fq_join_rc_f32, x.data_ptr(), r_codes.data_ptr(), _code_of(r_codes), r_scale, r_zp,
-                         int(bool(relu)), *outputs, _stream(x))
-        else:
-            name = "mctq_fq_join_f32"
-            rc = _launch(lib.mctq_fq_join_f32, x.data_ptr(), None if residual is None else residual.data_ptr(), int(bool(relu)),
-                         *outputs, _stream(x))
-    if rc:
-        native.check(rc, name)
+    if r_codes is not None:
+        _gpu_call("mctq_fq_join_rc_f32", x, x.data_ptr(), r_codes.data_ptr(), _code_of(r_codes), r_scale, r_zp, int(bool(relu)),
+                  *outputs)
+    else:
+        _gpu_call("mctq_fq_join_f32", x, x.data_ptr(), None if residual is None else residual.data_ptr(), int(bool(relu)),
+                  *outputs)
     return y, codes
 
 
@@ -719,13 +642,8 @@ def codes_im2col(codes_nhwc, kernel_size, stride=1, padding=0, dilation=1, pad_c
     (kh, kw), (sh, sw), (ph, pw), (dh, dw), (ho, wo) = _conv_geometry(h, w, kernel_size, stride, padding, dilation, "codes_im2col")
     x = codes_nhwc if codes_nhwc.is_contiguous() else codes_nhwc.contiguous()
     if x.is_cuda:
-        lib = native.load()
-        with _maybe_on_device(x):
-            y = torch.empty((b * ho * wo, kh * kw * c), dtype=x.dtype, device=x.device)
-            rc = _launch(lib.mctq_codes_im2col_nhwc, x.data_ptr(), y.data_ptr(), b, h, w, c, kh, kw, sh, sw, ph, pw, dh, dw,
-                         pad_code, _stream(x))
-        if rc:
-            native.check(rc, "mctq_codes_im2col_nhwc")
+        y = torch.empty((b * ho * wo, kh * kw * c), dtype=x.dtype, device=x.device)
+        _gpu_call("mctq_codes_im2col_nhwc", x, x.data_ptr(), y.data_ptr(), b, h, w, c, kh, kw, sh, sw, ph, pw, dh, dw, pad_code)
         return y
     _cpu_route_allowed()
     xp = torch.nn.functional.pad(x, (0, 0, pw, pw, ph, ph), value=pad_code)              # [B, H + 2 ph, W + 2 pw, C]
@@ -827,44 +745,27 @@ def lut_codes(x, lut, thresholds, axis, eps: float, thr_div: float, mult: float,
             thr = thresholds.detach().to(x.device).float().reshape(shape)
             t = torch.clip((xf / (thr + eps)) * mult, min=cmin, max=cmax)
         q = torch.argmin(torch.abs(t.unsqueeze(-1) - lut_c), dim=-1).to(torch.uint8)
-        if packed4:
-            if x.is_contiguous() or not _is_dense(x):
-                return pack4(q.contiguous()).reshape(_packed_shape(x))
-            flat = torch.empty(x.numel(), dtype=torch.int16)          # dense, permuted storage: pack in STORAGE order
-            torch.as_strided(flat, x.shape, x.stride()).copy_(q.to(torch.int16))
-            return pack4(flat).reshape(_packed_shape(x))
-        return q
+        return _pack4_as_stored(q, x) if packed4 else q
     dt = _dtype_code(x, "lut_codes")
-    lib = native.load()
     if not x.is_contiguous():
         x = _dense_input(x)
     if axis is not None and not packed4 and x.numel() > _SPLIT_ELEMS and thresholds.numel() > 1:
         return _split_rows(x, axis, (thresholds.reshape(-1),), torch.uint8,
                            lambda xp, ps, ax: lut_codes(xp, lut, ps[0], ax, eps, thr_div, mult, cmin, cmax, index_table))
-    if packed4:
-        code = native.CODE_U4
-        y = torch.empty(_packed_shape(x), dtype=torch.uint8, device=x.device)
-    else:
-        code = native.CODE_U8
-        y = torch.empty_like(x, dtype=torch.uint8)
+    y, code = _codes_output(x, packed4, torch.uint8, native.CODE_U8, native.CODE_U4)
     lut = _param_on(x, lut, "lut_values", torch.float32)
     tab_ptr, entries = 0, 0
     if index_table is not None:
         index_table = _param_on(x, index_table, "index_table", torch.float32)
         tab_ptr, entries = index_table.data_ptr(), index_table.shape[0] - 1
-    idx = x.get_device()
-    with (_NOOP if idx == _current_device() else _on_device(idx)):
-        if axis is None:
-            rc = _launch(lib.mctq_lut_codes_per_tensor, x.data_ptr(), y.data_ptr(), x.numel(), dt, code, step_round, thr_div,
-                         lut.data_ptr(), n_lut, tab_ptr, entries, mult, cmin, cmax, _raw_stream(idx))
-        else:
-            thresholds = _param_on(x, thresholds, "thresholds", torch.float32)
-            outer, c, inner = _channel_view(x, axis)
-            rc = _launch(lib.mctq_lut_codes_per_channel, x.data_ptr(), y.data_ptr(), outer, c, inner, dt, code,
-                         thresholds.data_ptr(), eps, lut.data_ptr(), n_lut, tab_ptr, entries, mult, cmin, cmax,
-                         _raw_stream(idx))
-    if rc:
-        native.check(rc, "mctq_lut_codes")
+    if axis is None:
+        _gpu_call("mctq_lut_codes_per_tensor", x, x.data_ptr(), y.data_ptr(), x.numel(), dt, code, step_round, thr_div,
+                  lut.data_ptr(), n_lut, tab_ptr, entries, mult, cmin, cmax)
+    else:
+        thresholds = _param_on(x, thresholds, "thresholds", torch.float32)
+        outer, c, inner = _channel_view(x, axis)
+        _gpu_call("mctq_lut_codes_per_channel", x, x.data_ptr(), y.data_ptr(), outer, c, inner, dt, code, thresholds.data_ptr(),
+                  eps, lut.data_ptr(), n_lut, tab_ptr, entries, mult, cmin, cmax)
     return y
 
 
@@ -906,7 +807,6 @@ def lut_decode(codes, lut, thresholds, axis, thr_mul: float, mult: float, packed
         bshape = [1] * c8.dim()
         bshape[axis] = -1
         return q * thresholds.detach().to(codes.device).float().reshape(bshape)
-    lib = native.load()
     lut = _param_on(codes, lut, "lut_values", torch.float32)
     if packed4:
         src = codes if codes.is_contiguous() else codes.contiguous()
@@ -928,18 +828,14 @@ def lut_decode(codes, lut, thresholds, axis, thr_mul: float, mult: float, packed
         y = torch.empty_like(src, dtype=torch.float32)
         geom = src
         code = native.CODE_U8
-    idx = codes.get_device()
-    with (_NOOP if idx == _current_device() else _on_device(idx)):
-        if axis is None:
-            rc = _launch(lib.mctq_lut_decode_per_tensor, src.data_ptr(), y.data_ptr(), y.numel(), code, lut.data_ptr(), n_lut,
-                         mult, thr_mul, _raw_stream(idx))
-        else:
-            thresholds = _param_on(codes, thresholds, "thresholds", torch.float32)
-            outer, c, inner = _channel_view(geom, axis)
-            rc = _launch(lib.mctq_lut_decode_per_channel, src.data_ptr(), y.data_ptr(), outer, c, inner, code, lut.data_ptr(),
-                         n_lut, mult, thresholds.data_ptr(), _raw_stream(idx))
-    if rc:
-        native.check(rc, "mctq_lut_decode")
+    if axis is None:
+        _gpu_call("mctq_lut_decode_per_tensor", codes, src.data_ptr(), y.data_ptr(), y.numel(), code, lut.data_ptr(), n_lut, mult,
+                  thr_mul)
+    else:
+        thresholds = _param_on(codes, thresholds, "thresholds", torch.float32)
+        outer, c, inner = _channel_view(geom, axis)
+        _gpu_call("mctq_lut_decode_per_channel", codes, src.data_ptr(), y.data_ptr(), outer, c, inner, code, lut.data_ptr(), n_lut,
+                  mult, thresholds.data_ptr())
     return y
 
 
@@ -1016,49 +912,46 @@ _lib_def.define("lut_per_channel(Tensor x, Tensor lut, Tensor thresholds, float 
 
 # decision tables for codebooks that reach the ops without their quantizer (fx graphs): built once per codebook TENSOR
 # OBJECT (weak reference + version counter: an address can be reused by another tensor, an object cannot)
-_op_tables = {}
+_op_books = {}
+
+
+def _per_codebook(build, lut, mult, cmin, cmax):
+    """``build(lut, mult, cmin, cmax)``, once per codebook tensor object and version."""
+    import weakref
+    key = (build, id(lut), mult, cmin, cmax)
+    hit = _op_books.get(key)
+    if hit is not None and hit[0]() is lut and hit[1] == lut._version:
+        return hit[2]
+    if len(_op_books) > 256:
+        _op_books.clear()
+    val = build(lut, mult, cmin, cmax)
+    try:
+        _op_books[key] = (weakref.ref(lut), lut._version, val)
+    except TypeError:                                   # not weak-referenceable: do not cache
+        pass
+    return val
+
+
+def _build_op_table(lut, mult, cmin, cmax):
+    lut_np = lut.detach().cpu().numpy()
+    table = make_lut_table(lut_np, mult, cmin, cmax, lut.device)
+    return table, None if table is not None else make_lut_steps(lut_np, mult, cmin, cmax, lut.device)
+
+
+def _build_op_steps64(lut, mult, cmin, cmax):
+    built = native.build_lut_steps_f64(lut.detach().cpu().numpy(), mult, cmin, cmax)
+    return None if built is None else (torch.from_numpy(built[0]).to(lut.device), built[1])
 
 
 def _op_table(lut, mult, cmin, cmax):
     """(decision table | None, threshold list | None) of a codebook tensor."""
-    import weakref
-    key = (id(lut), mult, cmin, cmax)
-    hit = _op_tables.get(key)
-    if hit is not None and hit[0]() is lut and hit[1] == lut._version:
-        return hit[2]
-    if len(_op_tables) > 256:
-        _op_tables.clear()
-    lut_np = lut.detach().cpu().numpy()
-    table = make_lut_table(lut_np, mult, cmin, cmax, lut.device)
-    books = (table, None if table is not None else make_lut_steps(lut_np, mult, cmin, cmax, lut.device))
-    try:
-        _op_tables[key] = (weakref.ref(lut), lut._version, books)
-    except TypeError:                                   # not weak-referenceable: do not cache
-        pass
-    return books
-
-
-_op_steps64_cache = {}
+    return _per_codebook(_build_op_table, lut, mult, cmin, cmax)
 
 
 def _op_steps64(lut, mult, cmin, cmax):
     """(device blob, P) of the DOUBLE threshold list of a codebook tensor for float64 inputs, or None (literal double
-    scan).  Built once per codebook TENSOR OBJECT and version, like ``_op_table`` (one device -> host read at the first
-    float64 call: not inside hipGraph capture)."""
-    import weakref
-    key = (id(lut), mult, cmin, cmax)
-    hit = _op_steps64_cache.get(key)
-    if hit is not None and hit[0]() is lut and hit[1] == lut._version:
-        return hit[2]
-    if len(_op_steps64_cache) > 256:
-        _op_steps64_cache.clear()
-    built = native.build_lut_steps_f64(lut.detach().cpu().numpy(), mult, cmin, cmax)
-    val = None if built is None else (torch.from_numpy(built[0]).to(lut.device), built[1])
-    try:
-        _op_steps64_cache[key] = (weakref.ref(lut), lut._version, val)
-    except TypeError:
-        pass
-    return val
+    scan).  One device -> host read at the first float64 call: not inside hipGraph capture."""
+    return _per_codebook(_build_op_steps64, lut, mult, cmin, cmax)
 
 
 def _op_hip_lut_per_tensor(x, lut, thr_div, thr_mul, mult, cmin, cmax, step_round=0):
