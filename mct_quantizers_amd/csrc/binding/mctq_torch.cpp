@@ -269,10 +269,44 @@ PyObject* py_lutt_per_channel(PyObject*, PyObject* const* args, Py_ssize_t nargs
   END_HANDLE_TH_ERRORS
 }
 
+// ---- one item of an affine list: x, then (scales, zero_points | None, axis | None, quant_min, quant_max); axis None = per
+//      tensor (scales / zero_points are 1-element device tensors).  Fills everything of the item but y.  fq_batched answers
+//      NotImplemented for every reason but a Python error; BatchPlan raises TypeError with the reason's text. -----------
+enum ItemReason { kItemOk, kItemPyError, kItemNotTensor, kItemAxis, kItemZeroPoints, kItemScales, kItemF64PerTensor };
+const char* const kItemReasonText[] = {
+    nullptr, nullptr, "x and y must be plain dense HIP tensors of a supported dtype", "axis out of range",
+    "zero_points must be a contiguous int32 tensor on x's device with one entry per channel",
+    "scales must be a contiguous float32 tensor on x's device with one entry per channel",
+    "a float64 per-tensor item needs zero_points"};                    // (fq_batched: the general route supplies zeros)
+
+ItemReason parse_affine_item(PyObject* xo, PyObject* const* a, mctq_fq_item* d, const at::Tensor** xt, int64_t* axis_out) {
+  int dt;
+  const at::Tensor* xp = eligible(xo, &dt);
+  const bool per_tensor = a[2] == Py_None;
+  int64_t qmin, qmax, axis = -1;
+  if (!as_i64(a[3], &qmin) || !as_i64(a[4], &qmax) || (!per_tensor && !as_i64(a[2], &axis))) return kItemPyError;
+  if (!xp) return kItemNotTensor;
+  *xt = xp; d->dtype = dt; *axis_out = axis;                            // (valid from here on, whatever the reason)
+  if (!per_tensor && (axis < 0 || axis >= xp->dim())) return kItemAxis;
+  const int64_t want = per_tensor ? 1 : xp->size(axis);
+  const at::Tensor* sp = param_tensor(a[0], *xp, c10::ScalarType::Float, want);
+  const at::Tensor* zp = nullptr;
+  if (a[1] != Py_None && !(zp = param_tensor(a[1], *xp, c10::ScalarType::Int, want))) return kItemZeroPoints;
+  if (!sp) return kItemScales;
+  if (dt == MCTQ_DT_F64 && per_tensor && !zp) return kItemF64PerTensor;
+  d->x = xp->const_data_ptr(); d->y = nullptr;
+  if (per_tensor) { d->outer = 1; d->channels = 1; d->inner = xp->numel(); }
+  else channel_view(*xp, axis, &d->outer, &d->channels, &d->inner);
+  d->scales = sp->const_data_ptr<float>();
+  d->zero_points = zp ? zp->const_data_ptr<int32_t>() : nullptr;
+  d->quant_min = (int32_t)qmin; d->quant_max = (int32_t)qmax;
+  d->flags = per_tensor ? MCTQ_FQ_ITEM_PER_TENSOR : 0;
+  return kItemOk;
+}
+
 // ---- a list of weights in ONE launch ------------------------------------------------------------------
-// fq_batched(items) with items = sequence of (x, scales, zero_points | None, axis | None, quant_min, quant_max);
-// axis None = per tensor (scales / zero_points are 1-element device tensors).  Returns a list of new tensors,
-// or NotImplemented if any item is not eligible (the caller then quantizes them one by one).
+// fq_batched(items) with items = sequence of (x, scales, zero_points | None, axis | None, quant_min, quant_max).
+// Returns a list of new tensors, or NotImplemented if any item is not eligible (the caller then quantizes them one by one).
 PyObject* py_fq_batched(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
   HANDLE_TH_ERRORS
   if (nargs != 1) { PyErr_SetString(PyExc_TypeError, "fq_batched(items)"); return nullptr; }
@@ -290,36 +324,14 @@ PyObject* py_fq_batched(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
       PyErr_SetString(PyExc_TypeError, "fq_batched item: (x, scales, zero_points, axis, quant_min, quant_max)");
       return nullptr;
     }
-    int dt;
-    const at::Tensor* xp = eligible(PyTuple_GET_ITEM(it, 0), &dt);
-    int64_t qmin, qmax, axis = -1;
-    PyObject* axis_o = PyTuple_GET_ITEM(it, 3);
-    if (!as_i64(PyTuple_GET_ITEM(it, 4), &qmin) || !as_i64(PyTuple_GET_ITEM(it, 5), &qmax) ||
-        (axis_o != Py_None && !as_i64(axis_o, &axis))) { Py_DECREF(seq); return nullptr; }
-    bool ok = xp != nullptr && (axis_o == Py_None || (axis >= 0 && axis < xp->dim()));
-    const at::Tensor *sp = nullptr, *zp = nullptr;
-    if (ok) {
-      if (idx < 0) idx = xp->device().index();
-      ok = xp->device().index() == idx;
-      const int64_t want = axis_o == Py_None ? 1 : xp->size(axis);
-      sp = param_tensor(PyTuple_GET_ITEM(it, 1), *xp, c10::ScalarType::Float, want);
-      ok = ok && sp != nullptr;
-      if (PyTuple_GET_ITEM(it, 2) != Py_None) {
-        zp = param_tensor(PyTuple_GET_ITEM(it, 2), *xp, c10::ScalarType::Int, want);
-        ok = ok && zp != nullptr;
-      }
-    }
-    if (!ok) { Py_DECREF(seq); return not_implemented(); }
+    const at::Tensor* xp;
+    int64_t axis;
+    const ItemReason why = parse_affine_item(PyTuple_GET_ITEM(it, 0), PySequence_Fast_ITEMS(it) + 1, &items[(size_t)i], &xp, &axis);
+    if (why == kItemPyError) { Py_DECREF(seq); return nullptr; }
+    if (why == kItemOk && idx < 0) idx = xp->device().index();
+    if (why != kItemOk || xp->device().index() != idx) { Py_DECREF(seq); return not_implemented(); }
     outs.push_back(like(*xp, xp->scalar_type()));
-    mctq_fq_item& d = items[(size_t)i];
-    d.x = xp->const_data_ptr(); d.y = outs.back().mutable_data_ptr();
-    if (axis_o == Py_None) { d.outer = 1; d.channels = 1; d.inner = xp->numel(); }
-    else channel_view(*xp, axis, &d.outer, &d.channels, &d.inner);
-    d.scales = sp->const_data_ptr<float>();
-    d.zero_points = zp ? zp->const_data_ptr<int32_t>() : nullptr;
-    d.quant_min = (int32_t)qmin; d.quant_max = (int32_t)qmax; d.dtype = dt;
-    d.flags = axis_o == Py_None ? MCTQ_FQ_ITEM_PER_TENSOR : 0;
-    if (dt == MCTQ_DT_F64 && axis_o == Py_None && !zp) { Py_DECREF(seq); return not_implemented(); }   // general route supplies zeros
+    items[(size_t)i].y = outs.back().mutable_data_ptr();
   }
   Py_DECREF(seq);
   if (n > 0) {
@@ -579,37 +591,124 @@ inline uint64_t dict_tag(PyObject* d) { return ((PyDictObject*)d)->ma_version_ta
 inline uint64_t dict_tag(PyObject*) { return 0; }
 #endif
 
-struct BatchPlan {
-  PyObject_HEAD
-  vectorcallfunc vectorcall;
-  std::vector<mctq_fq_item>* items;
-  std::vector<PyObject*>* refs;          // 4 per item: x, y, scales, zero_points (or Py_None)
-  std::vector<std::vector<int64_t>>* sizes;
-  std::vector<std::vector<int64_t>>* strides;   // x's strides when the item was packed: same sizes AND strides = same (outer, channels, inner)
-  std::vector<int64_t>* axes;            // -1: per tensor
-  std::vector<BatchWatch>* watch;
-  std::vector<WatchGroup>* groups;
-  std::vector<uint8_t>* host_table;
-  at::Tensor* dev_table;
-  // LUT items (decision-table quantizers): ("lut", x, y, thresholds | None, table, axis | None, eps, thr_div, thr_mul,
-  // mult, clip_min, clip_max, step_round[, watch]); y float32, contiguous like x
-  std::vector<mctq_lut_item>* lut_items;
-  std::vector<PyObject*>* lut_refs;      // 4 per item: x, y, thresholds (or Py_None), table
-  std::vector<std::vector<int64_t>>* lut_sizes;
-  std::vector<int64_t>* lut_axes;
-  std::vector<uint8_t>* lut_host_table;
-  at::Tensor* lut_dev_table;
-  bool uploaded;
-  c10::DeviceIndex device;
-  bool versioned;                          // skip the launch when nothing changed since the last one
-  bool fresh;                              // the outputs hold the quantization of the inputs as recorded below
-  std::vector<uint32_t>* seen;             // per item (affine items first, then LUT items): x version, y version after the launch
+// Structure: the Python object holds ONE pointer to a PlanState (made with new, destroyed with delete: its members are
+// ordinary values).  PlanState = two PlanSide<Kind> -- the affine items and the LUT items, each with its own packed table
+// -- plus what the two share (watches, version records, counters).  A kind (AffineSide / LutSide) names the item type
+// and the library's pack / run entry points, tells whether an item's tensors are still what it was packed for, and
+// hands out / re-points the item's four device pointers; upload(), refresh(), launch() and record() are written once.
+template <class Kind>
+struct PlanSide {
+  std::vector<typename Kind::Item> items;
+  std::vector<PyObject*> refs;             // 4 per item -- affine: x, y, scales, zero_points (or Py_None); LUT: x, y, thresholds (or Py_None), table
+  std::vector<std::vector<int64_t>> sizes;
+  std::vector<std::vector<int64_t>> strides;    // affine only: x's strides when the item was packed: same sizes AND strides = same (outer, channels, inner)
+  std::vector<int64_t> axes;               // affine only; -1: per tensor
+  std::vector<uint8_t> host_table;
+  at::Tensor dev_table;
+  ~PlanSide() { for (PyObject* o : refs) Py_XDECREF(o); }
+};
+
+struct AffineSide {
+  typedef mctq_fq_item Item;
+  static constexpr const char* kPack = "mctq_fq_batch_pack";
+  static constexpr const char* kRun = "mctq_fq_batch_run";
+  static int64_t pack(const Item* items, int32_t n, void* table, int64_t capacity) { return mctq_fq_batch_pack(items, n, table, capacity); }
+  static int run(const void* host, const void* dev, void* stream) { return mctq_fq_batch_run(host, dev, stream); }
+  // are x / y / the parameters still what item i was packed for?  then ptr = its device pointers as they are now
+  static bool current(const PlanSide<AffineSide>& s, size_t i, const at::Tensor& x, const at::Tensor& y, c10::DeviceIndex device,
+                      const void* (&ptr)[4]) {
+    const at::Tensor& sc = THPVariable_Unpack(s.refs[4 * i + 2]);
+    const mctq_fq_item& d = s.items[i];
+    if (x.sizes() != c10::IntArrayRef(s.sizes[i]) || y.sizes() != x.sizes() || !x.is_cuda() || !y.is_cuda() ||
+        x.device().index() != device || y.device().index() != device ||
+        !x.unsafeGetTensorImpl()->is_non_overlapping_and_dense() || x.strides() != y.strides() ||
+        dtype_code(x.scalar_type()) != d.dtype || y.scalar_type() != x.scalar_type())
+      return false;
+    const int64_t axis = s.axes[i];
+    if (x.strides() != c10::IntArrayRef(s.strides[i])) {             // same sizes, other strides: is the channel view the same?
+      int64_t outer, c, inner;
+      if (axis < 0) { outer = 1; c = 1; inner = x.numel(); }
+      else channel_view(x, axis, &outer, &c, &inner);
+      if (outer != d.outer || c != d.channels || inner != d.inner) return false;
+    }
+    const int64_t want = axis < 0 ? 1 : d.channels;
+    if (sc.scalar_type() != c10::ScalarType::Float || !sc.is_contiguous() || sc.device() != x.device() || sc.numel() != want)
+      return false;
+    ptr[3] = nullptr;
+    if (s.refs[4 * i + 3] != Py_None) {
+      const at::Tensor& z = THPVariable_Unpack(s.refs[4 * i + 3]);
+      if (z.scalar_type() != c10::ScalarType::Int || !z.is_contiguous() || z.device() != x.device() || z.numel() != want)
+        return false;
+      ptr[3] = z.const_data_ptr();
+    }
+    ptr[0] = x.const_data_ptr(); ptr[1] = y.mutable_data_ptr(); ptr[2] = sc.const_data_ptr();
+    return true;
+  }
+  static bool repoint(Item& d, const void* const (&ptr)[4]) {          // true: a pointer moved
+    if (ptr[0] == d.x && ptr[1] == d.y && ptr[2] == (const void*)d.scales && ptr[3] == (const void*)d.zero_points) return false;
+    d.x = ptr[0]; d.y = const_cast<void*>(ptr[1]); d.scales = (const float*)ptr[2]; d.zero_points = (const int32_t*)ptr[3];
+    return true;
+  }
+};
+
+// LUT items (decision-table quantizers): ("lut", x, y, thresholds | None, table, axis | None, eps, thr_div, thr_mul,
+// mult, clip_min, clip_max, step_round[, watch]); y float32, contiguous like x
+struct LutSide {
+  typedef mctq_lut_item Item;
+  static constexpr const char* kPack = "mctq_lutt_batch_pack";
+  static constexpr const char* kRun = "mctq_lutt_batch_run";
+  static int64_t pack(const Item* items, int32_t n, void* table, int64_t capacity) { return mctq_lutt_batch_pack(items, n, table, capacity); }
+  static int run(const void* host, const void* dev, void* stream) { return mctq_lutt_batch_run(host, dev, stream); }
+  static bool current(const PlanSide<LutSide>& s, size_t i, const at::Tensor& x, const at::Tensor& y, c10::DeviceIndex device,
+                      const void* (&ptr)[4]) {
+    const at::Tensor& tb = THPVariable_Unpack(s.refs[4 * i + 3]);
+    const mctq_lut_item& d = s.items[i];
+    if (x.sizes() != c10::IntArrayRef(s.sizes[i]) || y.sizes() != x.sizes() || !x.is_cuda() || !y.is_cuda() ||
+        x.device().index() != device || y.device().index() != device || !x.is_contiguous() || !y.is_contiguous() ||
+        dtype_code(x.scalar_type()) != d.dtype || y.scalar_type() != c10::ScalarType::Float ||
+        tb.scalar_type() != c10::ScalarType::Float || !tb.is_contiguous() || tb.device() != x.device() ||
+        tb.numel() != 2 * ((int64_t)d.entries + 1))
+      return false;
+    ptr[2] = nullptr;
+    if (s.refs[4 * i + 2] != Py_None) {
+      const at::Tensor& t = THPVariable_Unpack(s.refs[4 * i + 2]);
+      if (t.scalar_type() != c10::ScalarType::Float || !t.is_contiguous() || t.device() != x.device() || t.numel() != d.channels)
+        return false;
+      ptr[2] = t.const_data_ptr();
+    }
+    ptr[0] = x.const_data_ptr(); ptr[1] = y.mutable_data_ptr(); ptr[3] = tb.const_data_ptr();
+    return true;
+  }
+  static bool repoint(Item& d, const void* const (&ptr)[4]) {
+    if (ptr[0] == d.x && ptr[1] == (const void*)d.y && ptr[2] == (const void*)d.thresholds && ptr[3] == (const void*)d.table) return false;
+    d.x = ptr[0]; d.y = (float*)const_cast<void*>(ptr[1]); d.thresholds = (const float*)ptr[2]; d.table = (const float*)ptr[3];
+    return true;
+  }
+};
+
+struct PlanState {
+  PlanSide<AffineSide> affine;
+  PlanSide<LutSide> lut;
+  std::vector<BatchWatch> watch;
+  std::vector<WatchGroup> groups;
+  bool uploaded = false;
+  c10::DeviceIndex device = -1;
+  bool versioned = false;                  // skip the launch when nothing changed since the last one
+  bool fresh = false;                      // the outputs hold the quantization of the inputs as recorded below
+  std::vector<uint32_t> seen;              // per item (affine items first, then LUT items): x version, y version after the launch
   // versioned reuse: the storages the last launch READ stay referenced until the next launch, so that the caching allocator
   // cannot hand their device pointers to a tensor that later becomes a planned weight (`w.data = tmp; w.data = fresh` with no
   // forward in between: same sizes, dtype and version counter; without the reference `fresh` could sit where the launch read)
-  std::vector<c10::Storage>* held;
-  hipStream_t last_stream;                 // the stream of the last launch: a skip is only valid for work queued behind it
-  int64_t launches, skips;
+  std::vector<c10::Storage> held;
+  hipStream_t last_stream = nullptr;       // the stream of the last launch: a skip is only valid for work queued behind it
+  int64_t launches = 0, skips = 0;
+  ~PlanState() { for (BatchWatch& w : watch) { Py_XDECREF(w.dict); Py_XDECREF(w.name); Py_XDECREF(w.obj); } }
+};
+
+struct BatchPlan {
+  PyObject_HEAD
+  vectorcallfunc vectorcall;
+  PlanState* state;
 };
 
 // in-place version counter of a tensor; inference tensors have none (they are never skipped over: see `trackable`)
@@ -621,42 +720,70 @@ inline bool stream_is_capturing(hipStream_t st) {
   return status != hipStreamCaptureStatusNone;
 }
 
-bool batchplan_upload_lut(BatchPlan* p) {
-  const int64_t need = mctq_lutt_batch_pack(p->lut_items->data(), (int32_t)p->lut_items->size(), nullptr, 0);
-  if (need < 0) { raise_rc((int)need, "mctq_lutt_batch_pack"); return false; }
-  p->lut_host_table->resize((size_t)need);
-  const int64_t got = mctq_lutt_batch_pack(p->lut_items->data(), (int32_t)p->lut_items->size(), p->lut_host_table->data(), need);
-  if (got != need) { raise_rc((int)got, "mctq_lutt_batch_pack"); return false; }
-  if (!p->lut_dev_table->defined() || p->lut_dev_table->numel() < need)
-    *p->lut_dev_table = at::Tensor(at::detail::empty_cuda({need}, c10::ScalarType::Byte, c10::Device(c10::kCUDA, p->device), std::nullopt));
-  const auto stream = c10::hip::getCurrentHIPStream(p->device);
-  c10::hip::memcpy_and_sync(p->lut_dev_table->mutable_data_ptr(), p->lut_host_table->data(), need, hipMemcpyHostToDevice, stream.stream());
+// pack the side's items again and refresh the device copy (one small synchronous copy: not legal under stream capture)
+template <class Kind>
+bool upload(PlanSide<Kind>& s, c10::DeviceIndex device) {
+  const int64_t need = Kind::pack(s.items.data(), (int32_t)s.items.size(), nullptr, 0);
+  if (need < 0) { raise_rc((int)need, Kind::kPack); return false; }
+  s.host_table.resize((size_t)need);
+  const int64_t got = Kind::pack(s.items.data(), (int32_t)s.items.size(), s.host_table.data(), need);
+  if (got != need) { raise_rc((int)got, Kind::kPack); return false; }
+  if (!s.dev_table.defined() || s.dev_table.numel() < need)
+    s.dev_table = at::Tensor(at::detail::empty_cuda({need}, c10::ScalarType::Byte, c10::Device(c10::kCUDA, device), std::nullopt));
+  const auto stream = c10::hip::getCurrentHIPStream(device);
+  c10::hip::memcpy_and_sync(s.dev_table.mutable_data_ptr(), s.host_table.data(), need, hipMemcpyHostToDevice, stream.stream());
   return true;
 }
 
-bool batchplan_upload(BatchPlan* p) {
-  const int64_t need = mctq_fq_batch_pack(p->items->data(), (int32_t)p->items->size(), nullptr, 0);
-  if (need < 0) { raise_rc((int)need, "mctq_fq_batch_pack"); return false; }
-  p->host_table->resize((size_t)need);
-  const int64_t got = mctq_fq_batch_pack(p->items->data(), (int32_t)p->items->size(), p->host_table->data(), need);
-  if (got != need) { raise_rc((int)got, "mctq_fq_batch_pack"); return false; }
-  if (!p->dev_table->defined() || p->dev_table->numel() < need)
-    *p->dev_table = at::Tensor(at::detail::empty_cuda({need}, c10::ScalarType::Byte, c10::Device(c10::kCUDA, p->device), std::nullopt));
-  const auto stream = c10::hip::getCurrentHIPStream(p->device);
-  c10::hip::memcpy_and_sync(p->dev_table->mutable_data_ptr(), p->host_table->data(), need, hipMemcpyHostToDevice, stream.stream());
+// Every call re-reads the side's tensors.  false: some item is no longer what it was packed for (NotImplemented);
+// `changed`: a version counter moved since the last launch; `dirty`: a device pointer moved (the item is re-pointed).
+template <class Kind>
+bool refresh(PlanSide<Kind>& s, c10::DeviceIndex device, const uint32_t* seen, bool& changed, bool& dirty) {
+  const size_t n = s.items.size();
+  for (size_t i = 0; i < n; ++i) {
+    const at::Tensor& x = THPVariable_Unpack(s.refs[4 * i]);
+    const at::Tensor& y = THPVariable_Unpack(s.refs[4 * i + 1]);
+    if (!changed && (x.is_inference() || version_of(x) != seen[2 * i] || version_of(y) != seen[2 * i + 1])) changed = true;
+    const void* ptr[4];
+    if (!Kind::current(s, i, x, y, device, ptr)) return false;
+    if (Kind::repoint(s.items[i], ptr)) dirty = true;
+  }
   return true;
+}
+
+template <class Kind>
+bool launch(PlanSide<Kind>& s, bool dirty, c10::DeviceIndex device, void* stream) {
+  if (s.items.empty()) return true;
+  if (dirty && !upload(s, device)) return false;
+  const int rc = Kind::run(s.host_table.data(), s.dev_table.const_data_ptr(), stream);
+  if (rc) raise_rc(rc, Kind::kRun);
+  return rc == 0;
+}
+
+// the kernels rewrote every output in place: say so to autograd, and remember what this launch read and wrote
+template <class Kind>
+void record(const PlanSide<Kind>& s, uint32_t* seen, std::vector<c10::Storage>* held) {
+  const size_t n = s.items.size();
+  for (size_t i = 0; i < n; ++i) {
+    const at::Tensor& x = THPVariable_Unpack(s.refs[4 * i]);
+    const at::Tensor& y = THPVariable_Unpack(s.refs[4 * i + 1]);
+    if (!y.is_inference()) y.unsafeGetTensorImpl()->bump_version();
+    seen[2 * i] = version_of(x);
+    seen[2 * i + 1] = version_of(y);
+    if (held) held->push_back(x.storage());
+  }
 }
 
 PyObject* batchplan_vectorcall(PyObject* self, PyObject* const*, size_t nargsf, PyObject* kwnames) {
   HANDLE_TH_ERRORS
-  BatchPlan* p = (BatchPlan*)self;
+  PlanState* p = ((BatchPlan*)self)->state;
   if (PyVectorcall_NARGS(nargsf) != 0 || (kwnames && PyTuple_GET_SIZE(kwnames))) {
     PyErr_SetString(PyExc_TypeError, "BatchPlan.__call__()");
     return nullptr;
   }
   if (torch::jit::tracer::isTracing()) return not_implemented();
-  for (WatchGroup& g : *p->groups) {
-    const BatchWatch* w0 = p->watch->data() + g.first;
+  for (WatchGroup& g : p->groups) {
+    const BatchWatch* w0 = p->watch.data() + g.first;
     const uint64_t tag = dict_tag(w0->dict);
     const bool same_dict = g.tag != 0 && tag == g.tag;               // untouched since the last full check: identities hold
     for (size_t k = 0; k < g.count; ++k) {
@@ -672,76 +799,12 @@ PyObject* batchplan_vectorcall(PyObject* self, PyObject* const*, size_t nargsf, 
     }
     g.tag = tag;
   }
-  const size_t n = p->items->size();
-  bool dirty = !p->uploaded;
+  const size_t n = p->affine.items.size(), nl = p->lut.items.size();
+  bool dirty = !p->uploaded, lut_dirty = !p->uploaded;
   bool changed = !p->versioned || !p->fresh;        // versioned reuse: did anything the last launch read or wrote move on?
-  uint32_t* seen = p->seen->data();
-  for (size_t i = 0; i < n; ++i) {
-    const at::Tensor& x = THPVariable_Unpack((*p->refs)[4 * i]);
-    const at::Tensor& y = THPVariable_Unpack((*p->refs)[4 * i + 1]);
-    const at::Tensor& sc = THPVariable_Unpack((*p->refs)[4 * i + 2]);
-    mctq_fq_item& d = (*p->items)[i];
-    if (!changed && (x.is_inference() || version_of(x) != seen[2 * i] || version_of(y) != seen[2 * i + 1])) changed = true;
-    const std::vector<int64_t>& sz = (*p->sizes)[i];
-    if (x.sizes() != c10::IntArrayRef(sz) || y.sizes() != x.sizes() || !x.is_cuda() || !y.is_cuda() ||
-        x.device().index() != p->device || y.device().index() != p->device ||
-        !x.unsafeGetTensorImpl()->is_non_overlapping_and_dense() || x.strides() != y.strides() ||
-        dtype_code(x.scalar_type()) != d.dtype || y.scalar_type() != x.scalar_type())
-      return not_implemented();
-    const int64_t axis = (*p->axes)[i];
-    if (x.strides() != c10::IntArrayRef((*p->strides)[i])) {         // same sizes, other strides: is the channel view the same?
-      int64_t outer, c, inner;
-      if (axis < 0) { outer = 1; c = 1; inner = x.numel(); }
-      else channel_view(x, axis, &outer, &c, &inner);
-      if (outer != d.outer || c != d.channels || inner != d.inner) return not_implemented();
-    }
-    const int64_t want = axis < 0 ? 1 : d.channels;
-    if (sc.scalar_type() != c10::ScalarType::Float || !sc.is_contiguous() || sc.device() != x.device() || sc.numel() != want)
-      return not_implemented();
-    const void* zp = nullptr;
-    if ((*p->refs)[4 * i + 3] != Py_None) {
-      const at::Tensor& z = THPVariable_Unpack((*p->refs)[4 * i + 3]);
-      if (z.scalar_type() != c10::ScalarType::Int || !z.is_contiguous() || z.device() != x.device() || z.numel() != want)
-        return not_implemented();
-      zp = z.const_data_ptr();
-    }
-    const void* xp = x.const_data_ptr();
-    void* yp = y.mutable_data_ptr();
-    const void* sp = sc.const_data_ptr();
-    if (xp != d.x || yp != d.y || sp != (const void*)d.scales || zp != (const void*)d.zero_points) {
-      d.x = xp; d.y = yp; d.scales = (const float*)sp; d.zero_points = (const int32_t*)zp;
-      dirty = true;
-    }
-  }
-  const size_t nl = p->lut_items->size();
-  bool lut_dirty = !p->uploaded;
-  for (size_t i = 0; i < nl; ++i) {
-    const at::Tensor& x = THPVariable_Unpack((*p->lut_refs)[4 * i]);
-    const at::Tensor& y = THPVariable_Unpack((*p->lut_refs)[4 * i + 1]);
-    const at::Tensor& tb = THPVariable_Unpack((*p->lut_refs)[4 * i + 3]);
-    mctq_lut_item& d = (*p->lut_items)[i];
-    if (!changed && (x.is_inference() || version_of(x) != seen[2 * (n + i)] || version_of(y) != seen[2 * (n + i) + 1])) changed = true;
-    if (x.sizes() != c10::IntArrayRef((*p->lut_sizes)[i]) || y.sizes() != x.sizes() || !x.is_cuda() || !y.is_cuda() ||
-        x.device().index() != p->device || y.device().index() != p->device || !x.is_contiguous() || !y.is_contiguous() ||
-        dtype_code(x.scalar_type()) != d.dtype || y.scalar_type() != c10::ScalarType::Float ||
-        tb.scalar_type() != c10::ScalarType::Float || !tb.is_contiguous() || tb.device() != x.device() ||
-        tb.numel() != 2 * ((int64_t)d.entries + 1))
-      return not_implemented();
-    const void* tp = nullptr;
-    if ((*p->lut_refs)[4 * i + 2] != Py_None) {
-      const at::Tensor& t = THPVariable_Unpack((*p->lut_refs)[4 * i + 2]);
-      if (t.scalar_type() != c10::ScalarType::Float || !t.is_contiguous() || t.device() != x.device() || t.numel() != d.channels)
-        return not_implemented();
-      tp = t.const_data_ptr();
-    }
-    const void* xp = x.const_data_ptr();
-    void* yp = y.mutable_data_ptr();
-    const void* bp = tb.const_data_ptr();
-    if (xp != d.x || yp != (void*)d.y || tp != (const void*)d.thresholds || bp != (const void*)d.table) {
-      d.x = xp; d.y = (float*)yp; d.thresholds = (const float*)tp; d.table = (const float*)bp;
-      lut_dirty = true;
-    }
-  }
+  uint32_t* seen = p->seen.data();
+  if (!refresh(p->affine, p->device, seen, changed, dirty)) return not_implemented();         // the affine items first
+  if (!refresh(p->lut, p->device, seen + 2 * n, changed, lut_dirty)) return not_implemented();
   if (n > 0 || nl > 0) {
     DeviceScope scope(p->device);
     hipStream_t st = c10::hip::getCurrentHIPStream(p->device).stream();
@@ -750,32 +813,14 @@ PyObject* batchplan_vectorcall(PyObject* self, PyObject* const*, size_t nargsf, 
       ++p->skips;                                    // the outputs ARE the quantization of these inputs: nothing to launch
       Py_RETURN_NONE;
     }
-    void* stream = (void*)st;
     p->fresh = false;
-    if (n > 0) {
-      if (dirty && !batchplan_upload(p)) return nullptr;
-      const int rc = mctq_fq_batch_run(p->host_table->data(), p->dev_table->const_data_ptr(), stream);
-      if (rc) return raise_rc(rc, "mctq_fq_batch_run");
-    }
-    if (nl > 0) {
-      if (lut_dirty && !batchplan_upload_lut(p)) return nullptr;
-      const int rc = mctq_lutt_batch_run(p->lut_host_table->data(), p->lut_dev_table->const_data_ptr(), stream);
-      if (rc) return raise_rc(rc, "mctq_lutt_batch_run");
-    }
+    if (!launch(p->affine, dirty, p->device, (void*)st) || !launch(p->lut, lut_dirty, p->device, (void*)st)) return nullptr;
     p->uploaded = true;
     p->last_stream = st;
     ++p->launches;
-    // the kernels rewrote every output in place: say so to autograd, and remember what this launch read and wrote
-    if (p->versioned) p->held->clear();
-    for (size_t i = 0; i < n + nl; ++i) {
-      PyObject* const* r = i < n ? &(*p->refs)[4 * i] : &(*p->lut_refs)[4 * (i - n)];
-      const at::Tensor& x = THPVariable_Unpack(r[0]);
-      const at::Tensor& y = THPVariable_Unpack(r[1]);
-      if (!y.is_inference()) y.unsafeGetTensorImpl()->bump_version();
-      seen[2 * i] = version_of(x);
-      seen[2 * i + 1] = version_of(y);
-      if (p->versioned) p->held->push_back(x.storage());
-    }
+    if (p->versioned) p->held.clear();
+    record(p->affine, seen, p->versioned ? &p->held : nullptr);
+    record(p->lut, seen + 2 * n, p->versioned ? &p->held : nullptr);
     p->fresh = true;
   }
   Py_RETURN_NONE;
@@ -783,25 +828,18 @@ PyObject* batchplan_vectorcall(PyObject* self, PyObject* const*, size_t nargsf, 
 }
 
 void batchplan_dealloc(PyObject* self) {
-  BatchPlan* p = (BatchPlan*)self;
-  if (p->refs) for (PyObject* o : *p->refs) Py_XDECREF(o);
-  if (p->watch) for (BatchWatch& w : *p->watch) { Py_XDECREF(w.dict); Py_XDECREF(w.name); Py_XDECREF(w.obj); }
-  if (p->lut_refs) for (PyObject* o : *p->lut_refs) Py_XDECREF(o);
-  delete p->items; delete p->refs; delete p->sizes; delete p->strides; delete p->axes; delete p->watch; delete p->groups; delete p->host_table; delete p->dev_table;
-  delete p->lut_items; delete p->lut_refs; delete p->lut_sizes; delete p->lut_axes; delete p->lut_host_table; delete p->lut_dev_table;
-  delete p->seen;
-  delete p->held;
+  delete ((BatchPlan*)self)->state;
   Py_TYPE(self)->tp_free(self);
 }
 
 // plan.invalidate(): the next call launches whatever the version counters say (after a write the counters cannot see)
 PyObject* batchplan_invalidate(PyObject* self, PyObject*) {
-  ((BatchPlan*)self)->fresh = false;
+  ((BatchPlan*)self)->state->fresh = false;
   Py_RETURN_NONE;
 }
 // plan.stats() -> (launches, skipped calls)
 PyObject* batchplan_stats(PyObject* self, PyObject*) {
-  BatchPlan* p = (BatchPlan*)self;
+  const PlanState* p = ((BatchPlan*)self)->state;
   return Py_BuildValue("(LL)", (long long)p->launches, (long long)p->skips);
 }
 PyMethodDef batchplan_methods[] = {
@@ -810,7 +848,7 @@ PyMethodDef batchplan_methods[] = {
     {nullptr, nullptr, 0, nullptr}};
 
 // watch = (dict, ((name, object, version), ...)); returns an error text or nullptr
-const char* batchplan_add_watch(BatchPlan* p, PyObject* w) {
+const char* batchplan_add_watch(PlanState* p, PyObject* w) {
   if (w == Py_None) return nullptr;
   if (!PyTuple_Check(w) || PyTuple_GET_SIZE(w) != 2 || !PyDict_Check(PyTuple_GET_ITEM(w, 0)) || !PyTuple_Check(PyTuple_GET_ITEM(w, 1)))
     return "watch: (dict, ((name, object, version), ...))";
@@ -824,9 +862,15 @@ const char* batchplan_add_watch(BatchPlan* p, PyObject* w) {
     bw.dict = dict; bw.name = PyTuple_GET_ITEM(e, 0); bw.obj = PyTuple_GET_ITEM(e, 1);
     bw.version = PyLong_AsLongLong(PyTuple_GET_ITEM(e, 2));
     Py_INCREF(bw.dict); Py_INCREF(bw.name); Py_INCREF(bw.obj);
-    p->watch->push_back(bw);
+    p->watch.push_back(bw);
   }
   return nullptr;
+}
+
+// the item's four tensors (tuple positions first .. first + 3) stay referenced as long as the plan lives
+template <class Kind>
+void keep_refs(PlanSide<Kind>& s, PyObject* item, int first) {
+  for (int k = first; k < first + 4; ++k) { PyObject* o = PyTuple_GET_ITEM(item, k); Py_INCREF(o); s.refs.push_back(o); }
 }
 
 PyObject* batchplan_new(PyTypeObject* type, PyObject* args, PyObject*) {
@@ -836,23 +880,11 @@ PyObject* batchplan_new(PyTypeObject* type, PyObject* args, PyObject*) {
   if (PyTuple_GET_SIZE(args) == 2 && (versioned = PyObject_IsTrue(PyTuple_GET_ITEM(args, 1))) < 0) return nullptr;
   PyObject* seq = PySequence_Fast(PyTuple_GET_ITEM(args, 0), "BatchPlan expects a sequence of tuples");
   if (!seq) return nullptr;
-  BatchPlan* p = (BatchPlan*)type->tp_alloc(type, 0);
-  if (!p) { Py_DECREF(seq); return nullptr; }
-  p->vectorcall = batchplan_vectorcall;
-  p->items = new std::vector<mctq_fq_item>(); p->refs = new std::vector<PyObject*>();
-  p->sizes = new std::vector<std::vector<int64_t>>(); p->strides = new std::vector<std::vector<int64_t>>();
-  p->axes = new std::vector<int64_t>();
-  p->watch = new std::vector<BatchWatch>(); p->groups = new std::vector<WatchGroup>();
-  p->host_table = new std::vector<uint8_t>(); p->dev_table = new at::Tensor();
-  p->lut_items = new std::vector<mctq_lut_item>(); p->lut_refs = new std::vector<PyObject*>();
-  p->lut_sizes = new std::vector<std::vector<int64_t>>(); p->lut_axes = new std::vector<int64_t>();
-  p->lut_host_table = new std::vector<uint8_t>(); p->lut_dev_table = new at::Tensor();
-  p->uploaded = false;
-  p->device = -1;
-  p->versioned = versioned != 0; p->fresh = false; p->launches = 0; p->skips = 0;
-  p->seen = new std::vector<uint32_t>();
-  p->held = new std::vector<c10::Storage>();
-  p->last_stream = nullptr;
+  BatchPlan* self = (BatchPlan*)type->tp_alloc(type, 0);
+  if (!self) { Py_DECREF(seq); return nullptr; }
+  self->vectorcall = batchplan_vectorcall;
+  PlanState* p = self->state = new PlanState();
+  p->versioned = versioned != 0;
   const Py_ssize_t n = PySequence_Fast_GET_SIZE(seq);
   const char* err = nullptr;
   for (Py_ssize_t i = 0; i < n && !err; ++i) {
@@ -875,7 +907,7 @@ PyObject* batchplan_new(PyTypeObject* type, PyObject* args, PyObject*) {
       int64_t sr, axis = -1;
       PyObject* axis_o = PyTuple_GET_ITEM(it, 5);
       if (!okv || !as_i64(PyTuple_GET_ITEM(it, 12), &sr) || (axis_o != Py_None && !as_i64(axis_o, &axis))) {
-        Py_DECREF(seq); Py_DECREF(p); return nullptr;
+        Py_DECREF(seq); Py_DECREF(self); return nullptr;
       }
       if (axis_o != Py_None && (axis < 0 || axis >= xp->dim())) { err = "axis out of range"; break; }
       if (p->device < 0) p->device = xp->device().index();
@@ -896,65 +928,51 @@ PyObject* batchplan_new(PyTypeObject* type, PyObject* args, PyObject*) {
       d.entries = (int32_t)(tb->numel() / 2 - 1);
       d.eps = (float)v[0]; d.thr_div = (float)v[1]; d.thr_mul = (float)v[2]; d.mult = (float)v[3]; d.clip_min = (float)v[4]; d.clip_max = (float)v[5];
       d.dtype = dt; d.step_round = (int32_t)sr;
-      p->lut_items->push_back(d);
-      p->lut_sizes->push_back(xp->sizes().vec());
-      p->lut_axes->push_back(axis_o == Py_None ? -1 : axis);
-      for (int k = 1; k <= 4; ++k) { PyObject* o = PyTuple_GET_ITEM(it, k); Py_INCREF(o); p->lut_refs->push_back(o); }
+      p->lut.items.push_back(d);
+      p->lut.sizes.push_back(xp->sizes().vec());
+      keep_refs(p->lut, it, 1);
       if (PyTuple_GET_SIZE(it) == 14) err = batchplan_add_watch(p, PyTuple_GET_ITEM(it, 13));
       continue;
     }
     if (!PyTuple_Check(it) || (PyTuple_GET_SIZE(it) != 7 && PyTuple_GET_SIZE(it) != 8)) {
       err = "item: (x, y, scales, zero_points, axis, quant_min, quant_max[, watch])"; break;
     }
-    int dt, dty;
-    const at::Tensor* xp = eligible(PyTuple_GET_ITEM(it, 0), &dt);
+    int dty;
     const at::Tensor* yp = eligible(PyTuple_GET_ITEM(it, 1), &dty);
-    int64_t qmin, qmax, axis = -1;
-    PyObject* axis_o = PyTuple_GET_ITEM(it, 4);
-    if (!as_i64(PyTuple_GET_ITEM(it, 5), &qmin) || !as_i64(PyTuple_GET_ITEM(it, 6), &qmax) || (axis_o != Py_None && !as_i64(axis_o, &axis))) {
-      Py_DECREF(seq); Py_DECREF(p); return nullptr;
-    }
-    if (!xp || !yp) { err = "x and y must be plain dense HIP tensors of a supported dtype"; break; }
-    if (dt != dty || xp->sizes() != yp->sizes() || xp->strides() != yp->strides() || xp->device() != yp->device()) {
-      err = "y must have x's dtype, shape, strides and device"; break;
-    }
-    if (axis_o != Py_None && (axis < 0 || axis >= xp->dim())) { err = "axis out of range"; break; }
-    if (p->device < 0) p->device = xp->device().index();
-    if (xp->device().index() != p->device) { err = "all tensors of one plan must be on the same device"; break; }
-    const int64_t want = axis_o == Py_None ? 1 : xp->size(axis);
-    const at::Tensor* sp = param_tensor(PyTuple_GET_ITEM(it, 2), *xp, c10::ScalarType::Float, want);
-    const at::Tensor* zp = nullptr;
-    if (PyTuple_GET_ITEM(it, 3) != Py_None) {
-      zp = param_tensor(PyTuple_GET_ITEM(it, 3), *xp, c10::ScalarType::Int, want);
-      if (!zp) { err = "zero_points must be a contiguous int32 tensor on x's device with one entry per channel"; break; }
-    }
-    if (!sp) { err = "scales must be a contiguous float32 tensor on x's device with one entry per channel"; break; }
-    if (dt == MCTQ_DT_F64 && axis_o == Py_None && !zp) { err = "a float64 per-tensor item needs zero_points"; break; }
+    const at::Tensor* xp;
     mctq_fq_item d;
-    d.x = xp->const_data_ptr(); d.y = yp->mutable_data_ptr();
-    if (axis_o == Py_None) { d.outer = 1; d.channels = 1; d.inner = xp->numel(); }
-    else channel_view(*xp, axis, &d.outer, &d.channels, &d.inner);
-    d.scales = sp->const_data_ptr<float>();
-    d.zero_points = zp ? zp->const_data_ptr<int32_t>() : nullptr;
-    d.quant_min = (int32_t)qmin; d.quant_max = (int32_t)qmax; d.dtype = dt;
-    d.flags = axis_o == Py_None ? MCTQ_FQ_ITEM_PER_TENSOR : 0;
-    p->items->push_back(d);
-    p->sizes->push_back(xp->sizes().vec());
-    p->strides->push_back(xp->strides().vec());
-    p->axes->push_back(axis_o == Py_None ? -1 : axis);
-    for (int k = 0; k < 4; ++k) { PyObject* o = PyTuple_GET_ITEM(it, k); Py_INCREF(o); p->refs->push_back(o); }
+    int64_t axis;
+    const ItemReason why = parse_affine_item(PyTuple_GET_ITEM(it, 0), PySequence_Fast_ITEMS(it) + 2, &d, &xp, &axis);
+    if (why == kItemPyError) { Py_DECREF(seq); Py_DECREF(self); return nullptr; }
+    // (the reasons in the order they have always been reported in: y's behind x's and ahead of the axis', the device's behind that)
+    if (why == kItemNotTensor || !yp) err = kItemReasonText[kItemNotTensor];
+    else if (d.dtype != dty || xp->sizes() != yp->sizes() || xp->strides() != yp->strides() || xp->device() != yp->device())
+      err = "y must have x's dtype, shape, strides and device";
+    else if (why == kItemAxis) err = kItemReasonText[why];
+    else {
+      if (p->device < 0) p->device = xp->device().index();
+      if (xp->device().index() != p->device) err = "all tensors of one plan must be on the same device";
+      else if (why != kItemOk) err = kItemReasonText[why];
+    }
+    if (err) break;
+    d.y = yp->mutable_data_ptr();
+    p->affine.items.push_back(d);
+    p->affine.sizes.push_back(xp->sizes().vec());
+    p->affine.strides.push_back(xp->strides().vec());
+    p->affine.axes.push_back(axis);
+    keep_refs(p->affine, it, 0);
     if (PyTuple_GET_SIZE(it) == 8) err = batchplan_add_watch(p, PyTuple_GET_ITEM(it, 7));
   }
   Py_DECREF(seq);
-  if (err) { Py_DECREF(p); PyErr_Format(PyExc_TypeError, "BatchPlan: %s", err); return nullptr; }
-  p->seen->assign(2 * (p->items->size() + p->lut_items->size()), 0u);
-  for (size_t i = 0; i < p->watch->size();) {                       // runs of entries that watch the same dictionary
+  if (err) { Py_DECREF(self); PyErr_Format(PyExc_TypeError, "BatchPlan: %s", err); return nullptr; }
+  p->seen.assign(2 * (p->affine.items.size() + p->lut.items.size()), 0u);
+  for (size_t i = 0; i < p->watch.size();) {                        // runs of entries that watch the same dictionary
     size_t j = i;
-    while (j < p->watch->size() && (*p->watch)[j].dict == (*p->watch)[i].dict) ++j;
-    p->groups->push_back(WatchGroup{i, j - i, 0});
+    while (j < p->watch.size() && p->watch[j].dict == p->watch[i].dict) ++j;
+    p->groups.push_back(WatchGroup{i, j - i, 0});
     i = j;
   }
-  return (PyObject*)p;
+  return (PyObject*)self;
   END_HANDLE_TH_ERRORS
 }
 

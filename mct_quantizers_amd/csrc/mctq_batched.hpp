@@ -3,6 +3,11 @@
 // mctq_batched_lut.hip (MCTQ_BATCHED_PART 2: the decision-table LUT lists, mctq_lutt_batch_*).  The tile code and the
 // policies are shared; each part instantiates only the kernels its entry points launch.
 //
+// The host side is written once, too: validate_items / pack_table / run_table (and the helpers under them: fits_grid,
+// fill_head, chunk_shift, place_chunks) are templates over a KIND -- AffineKind in part 1, LutKind in part 2 -- that
+// names the item and descriptor types, the table's group record and magic word, the tile size and the few rules that
+// differ (its own argument checks, what is one row, the descriptor's tail, the group's LDS bytes, the launches).  The
+// four extern "C" table entry points are one-line calls; the two table layouts are fixed by their Group structs.
 //
 // A LIST of affine fake-quantizations in one launch.  The reference re-quantizes every wrapped layer's weights
 // on every forward (pytorch/quantize_wrapper.py:228-240: one quantizer call per weight attribute), i.e. tens of
@@ -478,10 +483,188 @@ __global__ __launch_bounds__(kThreads) void batched_lut_table_kernel(const LutBa
   else batched_tile<false, LutPol<TI>, U, NT>(it, pol, smem, e0, left);
 }
 
+// ---- host: which tensors one grid can take, how the grid is cut, and the packed table -----------------------------
+// Everything below is written ONCE for both kinds of list.  A KIND (AffineKind in part 1, LutKind in part 2) names
+//   Item / Desc          the public list element (mctq_fq_item / mctq_lut_item) and its device descriptor
+//   Group, kMagic        the per-storage-type record of the packed table's header and the table's magic word
+//   kNotPacked           what mctq_*_batch_run answers for a buffer its packer did not write
+//   tile(dtype)          elements per block
+//   check_range / check  the kind's own argument checks, ahead of / behind the shared pointer check
+//   params / one_row / batchable / fill / add_to_group / launch_group / launch_single
+// and validate_items / pack_table / run_table do the rest.
 template <class TI, class TO>
 static constexpr uint32_t batch_tile_elems() { return kThreads * kBatchU * IO<TI, TO>::N; }
-static uint32_t tile_elems_of(int dtype) {
-  return dtype == MCTQ_DT_F32 ? batch_tile_elems<float, float>() : batch_tile_elems<_Float16, _Float16>();
+
+template <class Item>
+static int64_t elems(const Item& d) { return d.outer * d.channels * d.inner; }
+
+static BatchItem& head(BatchItem& b) { return b; }
+static BatchItem& head(LutBatchItem& l) { return l.b; }
+
+// All items are validated before anything is launched or written: a bad descriptor must not leave a list half done.
+// (Item by item, every check in the order it has always had: which message a bad item gets is part of the interface.)
+template <class Kind>
+static int validate_items(const typename Kind::Item* items, int32_t n_items) {
+  if (n_items < 0) return fail_arg("n_items < 0");
+  if (n_items > 0 && !items) return fail_arg("items is NULL");
+  for (int32_t k = 0; k < n_items; ++k) {
+    const typename Kind::Item& d = items[k];
+    if (d.outer < 0 || d.channels < 0 || d.inner < 0) return fail_arg("negative extent");
+    if (int rc = Kind::check_range(d)) return rc;
+    if (elems(d) > 0 && (!d.x || !d.y || !Kind::params(d))) return fail_arg("NULL pointer");
+    if (int rc = Kind::check(d)) return rc;
+  }
+  return 0;
+}
+
+// One grid takes: tensors whose x and y are aligned to a lane-vector (`x_mask`; y: 16 bytes), with fewer than 2^31
+// elements, and rows of at least 32 elements (or one parameter set for the whole tensor: `one_row`) -- or any rows when
+// the tensor is small (<= 2^20 elements: depthwise 3x3 weights, [C, 1, 3, 3], are tiny and many; one more launch each
+// would cost more than the element-by-element path of their row-straddling vectors).  LARGE channel-last layouts keep
+// their own kernels (lastaxis / window): launched one by one on the same stream.
+template <class Item>
+static bool fits_grid(const Item& d, uintptr_t x_mask, uint32_t tile, bool one_row) {
+  const int64_t n = elems(d);
+  if (((uintptr_t)d.x & x_mask) || ((uintptr_t)d.y & 15u)) return false;
+  if (n >= (1ll << 31) - (int64_t)tile || d.channels > 0x7fffffffLL || d.inner > 0x7fffffffLL) return false;
+  return one_row || d.inner >= 32 || n <= (1ll << 20);
+}
+
+// The 64 bytes every descriptor starts with, but for the parameter pointers and lo / hi (the kind's fill() sets those).
+template <class Item>
+static void fill_head(BatchItem& b, const Item& d, bool one_row, uint32_t tiles) {
+  const int64_t n = elems(d);
+  b.x = d.x; b.y = d.y;
+  b.n = (uint32_t)n;
+  b.inner = one_row ? (uint32_t)n : (uint32_t)d.inner;
+  b.channels = one_row ? 1u : (uint32_t)d.channels;
+  b.tile_begin = 0; b.tiles = tiles; b.reserved = 0;
+}
+
+static uint32_t ceil_shift(uint32_t tiles, uint32_t shift) { return (tiles + (1u << shift) - 1) >> shift; }
+
+// Smallest chunk shift with sum over tensors of ceil(tiles / 2^shift) <= max_chunks.
+static uint32_t chunk_shift(const uint32_t* tiles, int n, uint32_t max_chunks) {
+  for (uint32_t s = 0;; ++s) {
+    uint64_t chunks = 0;
+    for (int k = 0; k < n; ++k) chunks += ((uint64_t)tiles[k] + (1u << s) - 1) >> s;
+    if (chunks <= max_chunks) return s;
+  }
+}
+
+// Tensor `index` of a launch takes the next ceil(tiles / 2^shift) chunks: its first block is theirs, their map entries name it.
+template <class MapT>
+static void place_chunks(BatchItem& b, uint32_t index, MapT* map, uint32_t& chunk, uint32_t shift) {
+  b.tile_begin = chunk << shift;
+  const uint32_t c = ceil_shift(b.tiles, shift);
+  for (uint32_t j = 0; j < c; ++j) map[chunk + j] = (MapT)index;
+  chunk += c;
+}
+
+// ---- packed table (mctq_*_batch_pack / mctq_*_batch_run): header, then per storage type the descriptors and the
+//      half-word chunk map, then the items that are launched one by one (copied as they came) -----------------------
+template <class Group>
+struct TableHeader {
+  uint32_t magic, version, total_bytes, n_groups, n_singles, singles_off, pad0, pad1;
+  Group g[3];
+};
+
+template <class Kind>
+static int64_t pack_table(const typename Kind::Item* items, int32_t n_items, void* host_table, int64_t capacity) {
+  typedef typename Kind::Item Item;
+  typedef typename Kind::Desc Desc;
+  typedef TableHeader<typename Kind::Group> Header;
+  if (int rc = validate_items<Kind>(items, n_items)) return rc;
+  // where each item goes: the grid of its storage type (0..2), a launch of its own, or (empty) nowhere
+  enum : int8_t { kNowhere = -1, kAlone = 3 };
+  std::vector<int8_t> where;
+  std::vector<uint32_t> tl;
+  try {
+    where.resize((size_t)n_items);
+    tl.resize((size_t)n_items);
+  } catch (const std::bad_alloc&) {
+    return fail_arg("out of host memory");
+  }
+  uint32_t count[4] = {0, 0, 0, 0};
+  for (int32_t k = 0; k < n_items; ++k) {
+    const Item& d = items[k];
+    where[k] = elems(d) == 0 ? kNowhere : Kind::batchable(d) ? (int8_t)(d.dtype - MCTQ_DT_F32) : kAlone;
+    if (where[k] != kNowhere) ++count[where[k]];
+  }
+  for (int g = 0; g < 3; ++g)
+    if (count[g] > 0xffffu) return fail_arg("more than 65535 tensors of one storage type");
+  uint32_t shift[3] = {0, 0, 0}, chunks[3] = {0, 0, 0};
+  for (int g = 0; g < 3; ++g) {
+    if (!count[g]) continue;
+    const uint32_t tile_e = Kind::tile(MCTQ_DT_F32 + g);
+    int m = 0;
+    uint64_t total = 0;
+    for (int32_t k = 0; k < n_items; ++k) {
+      if (where[k] != g) continue;
+      tl[m] = (uint32_t)((elems(items[k]) + tile_e - 1) / tile_e);
+      total += tl[m++];
+    }
+    shift[g] = chunk_shift(tl.data(), m, kMaxChunksT);
+    for (int j = 0; j < m; ++j) chunks[g] += ceil_shift(tl[j], shift[g]);
+    if (total + ((uint64_t)m << shift[g]) > 0x7fffffffull) return fail_arg("too many tiles for one launch");
+  }
+  auto align16 = [](uint64_t v) { return (v + 15u) & ~(uint64_t)15u; };
+  uint64_t off = align16(sizeof(Header));
+  uint64_t items_off[3], map_off[3];
+  for (int g = 0; g < 3; ++g) {
+    items_off[g] = off; off += (uint64_t)count[g] * sizeof(Desc);
+    map_off[g] = off; off = align16(off + (uint64_t)chunks[g] * 2u + 2u);
+  }
+  const uint64_t singles_off = off;
+  off = align16(off + (uint64_t)count[kAlone] * sizeof(Item));
+  if (off > 0x7fffffffull) return fail_arg("table too large");
+  if (!host_table || capacity < (int64_t)off) return (int64_t)off;     // size query
+
+  uint8_t* base = static_cast<uint8_t*>(host_table);
+  memset(base, 0, (size_t)off);
+  Header* h = reinterpret_cast<Header*>(base);
+  h->magic = Kind::kMagic; h->version = MCTQ_ABI_VERSION; h->total_bytes = (uint32_t)off;
+  h->n_singles = count[kAlone]; h->singles_off = (uint32_t)singles_off;
+  for (int g = 0; g < 3; ++g) {
+    if (!count[g]) continue;
+    typename Kind::Group& tg = h->g[h->n_groups++];
+    tg.dtype = MCTQ_DT_F32 + g; tg.items_off = (uint32_t)items_off[g]; tg.map_off = (uint32_t)map_off[g];
+    tg.n_items = count[g]; tg.shift = shift[g];
+    const uint32_t tile_e = Kind::tile(tg.dtype);
+    Desc* bi = reinterpret_cast<Desc*>(base + items_off[g]);
+    uint16_t* map = reinterpret_cast<uint16_t*>(base + map_off[g]);
+    uint32_t chunk = 0, m = 0;
+    for (int32_t k = 0; k < n_items; ++k) {
+      if (where[k] != g) continue;
+      const Item& d = items[k];
+      Kind::fill(bi[m], d, (uint32_t)((elems(d) + tile_e - 1) / tile_e));
+      place_chunks(head(bi[m]), m, map, chunk, tg.shift);
+      Kind::add_to_group(tg, d);
+      ++m;
+    }
+    tg.grid = chunk << tg.shift;
+  }
+  Item* sg = reinterpret_cast<Item*>(base + singles_off);
+  for (int32_t k = 0; k < n_items; ++k)
+    if (where[k] == kAlone) *sg++ = items[k];
+  return (int64_t)off;
+}
+
+template <class Kind>
+static int run_table(const void* host_table, const void* device_table, void* stream) {
+  typedef TableHeader<typename Kind::Group> Header;
+  if (!host_table) return fail_arg("host_table is NULL");
+  const uint8_t* base = static_cast<const uint8_t*>(host_table);
+  const Header* h = reinterpret_cast<const Header*>(base);
+  if (h->magic != Kind::kMagic || h->version != (uint32_t)MCTQ_ABI_VERSION || h->n_groups > 3) return fail_arg(Kind::kNotPacked);
+  if (h->n_groups && (!device_table || ((uintptr_t)device_table & 15u))) return fail_arg("device_table is NULL or not 16-byte aligned");
+  const uint8_t* dev = static_cast<const uint8_t*>(device_table);
+  for (uint32_t g = 0; g < h->n_groups; ++g)
+    if (int rc = Kind::launch_group(h->g[g], dev, (hipStream_t)stream)) return rc;
+  const typename Kind::Item* sg = reinterpret_cast<const typename Kind::Item*>(base + h->singles_off);
+  for (uint32_t s = 0; s < h->n_singles; ++s)          // what one grid cannot take: one launch each, same stream
+    if (int rc = Kind::launch_single(sg[s], stream)) return rc;
+  return 0;
 }
 
 #if MCTQ_BATCHED_PART == 1
@@ -508,20 +691,6 @@ static int launch_batch_dt(int dt, const Src& src, uint32_t grid, int64_t out_by
   return launch_batch<__bf16, __bf16>(src, grid, out_bytes, st);
 }
 
-#endif
-#if MCTQ_BATCHED_PART == 2
-template <class TI>
-static int launch_lut_batch(const LutTableSrc& src, uint32_t grid, size_t lds, int64_t out_bytes, hipStream_t st) {
-  MCTQ_WITH_MODE(nt_mode(out_bytes), {
-    hipLaunchKernelGGL((batched_lut_table_kernel<TI, kBatchU, NT>), dim3(grid), dim3(kThreads), lds, st, src.it, src.map, src.shift);
-    note<LutTableOp, TI, float>("batched_lut_kernel<table>", kBatchU, NT);
-  });
-  return check_launch("batched LUT launch");
-}
-
-#endif
-
-#if MCTQ_BATCHED_PART == 1
 // float32 [rows][inner] with per-channel parameters, x / y 16-byte aligned, n < 2^31 - tile (checked by the caller)
 int fq_gather_one_f32(const void* x, void* y, int64_t outer, int64_t channels, int64_t inner, const float* scales,
                       const int32_t* zps, int32_t qmin, int32_t qmax, hipStream_t st) {
@@ -538,404 +707,191 @@ int fq_gather_one_f32(const void* x, void* y, int64_t outer, int64_t channels, i
   return check_launch("gather launch");
 }
 
-// ---- host: which tensors one grid can take, and how the grid is cut ---------------------------------------
-static int validate_items(const mctq_fq_item* items, int32_t n_items) {
-  if (n_items < 0) return fail_arg("n_items < 0");
-  if (n_items > 0 && !items) return fail_arg("items is NULL");
-  for (int32_t k = 0; k < n_items; ++k) {
-    const mctq_fq_item& d = items[k];
-    if (d.outer < 0 || d.channels < 0 || d.inner < 0) return fail_arg("negative extent");
-    if (d.quant_min > d.quant_max) return fail_arg("quant_min > quant_max");
-    if (d.outer * d.channels * d.inner > 0 && (!d.x || !d.y || !d.scales)) return fail_arg("NULL pointer");
+// Affine lists: float32 / float16 / bfloat16 tensors ride the grid of their storage type; float64 has its own path.
+struct AffineKind {
+  typedef mctq_fq_item Item;
+  typedef BatchItem Desc;
+  struct Group { uint32_t dtype, items_off, map_off, n_items, grid, shift; int64_t out_bytes; };
+  static constexpr uint32_t kMagic = 0x4d435451u;   // "MCTQ"
+  static constexpr const char* kNotPacked = "not a table packed by this library version (mctq_fq_batch_pack)";
+  static uint32_t tile(int dtype) {
+    return dtype == MCTQ_DT_F32 ? batch_tile_elems<float, float>() : batch_tile_elems<_Float16, _Float16>();
+  }
+  static int check_range(const Item& d) { return d.quant_min > d.quant_max ? fail_arg("quant_min > quant_max") : 0; }
+  static const void* params(const Item& d) { return d.scales; }
+  static int check(const Item& d) {
     if (d.dtype != MCTQ_DT_F32 && d.dtype != MCTQ_DT_F16 && d.dtype != MCTQ_DT_BF16 && d.dtype != MCTQ_DT_F64)
       return fail_arg("unknown dtype");
     if (d.dtype == MCTQ_DT_F64 && (d.flags & MCTQ_FQ_ITEM_PER_TENSOR) && !d.zero_points)
       return fail_arg("a float64 per-tensor item needs a zero_points pointer");
+    return 0;
   }
-  return 0;
-}
-
-// One grid takes: float32 / float16 / bfloat16 tensors with 16-byte aligned x and y, fewer than 2^31 elements, and
-// rows of at least 32 elements (or one parameter set for the whole tensor) -- or any rows when the tensor is small
-// (<= 2^20 elements: depthwise 3x3 weights, [C, 1, 3, 3], are tiny and many; one more launch each would cost more
-// than the element-by-element path of their row-straddling vectors).  LARGE channel-last layouts keep their own
-// kernels (lastaxis / window), float64 its own path: launched one by one on the same stream.
-static bool batchable(const mctq_fq_item& d) {
-  if (d.dtype == MCTQ_DT_F64) return false;
-  const int64_t n = d.outer * d.channels * d.inner;
-  const bool aligned = (((uintptr_t)d.x | (uintptr_t)d.y) & 15u) == 0;
-  if (!aligned || n >= (1ll << 31) - (int64_t)tile_elems_of(d.dtype)) return false;
-  if (d.channels > 0x7fffffffLL || d.inner > 0x7fffffffLL) return false;
-  return d.outer * d.channels == 1 || d.inner >= 32 || n <= (1ll << 20);
-}
-
-static int launch_single(const mctq_fq_item& d, void* stream) {
-  const int64_t n = d.outer * d.channels * d.inner;
-  if (n == 0) return 0;
-  if ((d.flags & MCTQ_FQ_ITEM_PER_TENSOR) && d.zero_points)
-    return mctq_fq_per_tensor_tqp(d.x, d.y, n, d.dtype, d.scales, d.zero_points, d.quant_min, d.quant_max, stream);
-  if ((d.flags & MCTQ_FQ_ITEM_PER_TENSOR) && d.dtype == MCTQ_DT_F64)
-    return fail_arg("a float64 per-tensor item needs a zero_points pointer");
-  return mctq_fq_per_channel(d.x, d.y, d.outer, d.channels, d.inner, d.dtype, d.scales, d.zero_points, d.quant_min,
-                             d.quant_max, stream);
-}
-
-static void fill_item(BatchItem& b, const mctq_fq_item& d, uint32_t tiles) {
-  const int64_t n = d.outer * d.channels * d.inner;
-  b.x = d.x; b.y = d.y; b.scales = d.scales; b.zps = d.zero_points;
-  b.n = (uint32_t)n;
-  const bool one_row = d.outer * d.channels == 1;
-  b.inner = one_row ? (uint32_t)n : (uint32_t)d.inner;
-  b.channels = one_row ? 1u : (uint32_t)d.channels;
-  b.tile_begin = 0; b.tiles = tiles; b.reserved = 0;
-  b.lo = (float)d.quant_min; b.hi = (float)d.quant_max;
-}
-
-#endif
-// Smallest chunk shift with sum over tensors of ceil(tiles / 2^shift) <= max_chunks.
-static uint32_t chunk_shift(const uint32_t* tiles, int n, uint32_t max_chunks) {
-  for (uint32_t s = 0;; ++s) {
-    uint64_t chunks = 0;
-    for (int k = 0; k < n; ++k) chunks += ((uint64_t)tiles[k] + (1u << s) - 1) >> s;
-    if (chunks <= max_chunks) return s;
+  static bool one_row(const Item& d) { return d.outer * d.channels == 1; }
+  static bool batchable(const Item& d) { return d.dtype != MCTQ_DT_F64 && fits_grid(d, 15u, tile(d.dtype), one_row(d)); }
+  static void fill(Desc& b, const Item& d, uint32_t tiles) {
+    fill_head(b, d, one_row(d), tiles);
+    b.scales = d.scales; b.zps = d.zero_points;
+    b.lo = (float)d.quant_min; b.hi = (float)d.quant_max;
   }
-}
-#if MCTQ_BATCHED_PART == 1
-
-// ---- packed table (mctq_fq_batch_pack / mctq_fq_batch_run) -------------------------------------------------
-constexpr uint32_t kTableMagic = 0x4d435451u;   // "MCTQ"
-struct TableGroup { uint32_t dtype, items_off, map_off, n_items, grid, shift; int64_t out_bytes; };
-struct TableHeader {
-  uint32_t magic, version, total_bytes, n_groups, n_singles, singles_off, pad0, pad1;
-  TableGroup g[3];
+  static void add_to_group(Group& tg, const Item& d) { tg.out_bytes += elems(d) * (tg.dtype == MCTQ_DT_F32 ? 4 : 2); }
+  // mctq_fq_batched: descriptors and chunk map in the kernel arguments, up to kMaxBatch tensors per launch.  (Ahead of
+  // launch_group so that the kernels keep their order in the code object.)
+  static int run_kernarg(const Item* items, int32_t n_items, void* stream) {
+    if (int rc = validate_items<AffineKind>(items, n_items)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    bool singles = false;
+    for (int dt = MCTQ_DT_F32; dt <= MCTQ_DT_BF16; ++dt) {
+      const uint32_t tile_e = tile(dt);
+      const int64_t esz = dt == MCTQ_DT_F32 ? 4 : 2;
+      int32_t k = 0;
+      while (k < n_items) {
+        // next group: up to kMaxBatch batchable tensors of this storage type whose chunk map fits the kernel arguments
+        KernargSrc a;
+        uint32_t tiles[kMaxBatch];
+        int m = 0;
+        int64_t out_bytes = 0;
+        uint64_t total_tiles = 0;
+        for (; k < n_items && m < kMaxBatch; ++k) {
+          const Item& d = items[k];
+          if (d.dtype != dt) { if (d.dtype == MCTQ_DT_F64 && dt == MCTQ_DT_F32) singles = true; continue; }
+          const int64_t n = elems(d);
+          if (n == 0) continue;
+          if (!batchable(d)) { singles = true; continue; }
+          const uint32_t t = (uint32_t)((n + tile_e - 1) / tile_e);
+          if (total_tiles + t + ((uint64_t)kMaxBatch << 21) > 0x7fffffffull) break;    // grid limit (incl. chunk padding)
+          fill(a.it[m], d, t);
+          tiles[m++] = t;
+          total_tiles += t;
+          out_bytes += n * esz;
+        }
+        if (m == 0) continue;
+        a.shift = chunk_shift(tiles, m, kMaxChunksK);
+        memset(a.map, 0, sizeof(a.map));
+        uint32_t chunk = 0;
+        for (int j = 0; j < m; ++j) place_chunks(a.it[j], (uint32_t)j, reinterpret_cast<uint8_t*>(a.map), chunk, a.shift);
+        if (int rc = launch_batch_dt(dt, a, chunk << a.shift, out_bytes, st)) return rc;
+      }
+    }
+    if (singles)
+      for (int32_t k = 0; k < n_items; ++k)                     // what one grid cannot take: one launch each, same stream
+        if (!batchable(items[k]))
+          if (int rc = launch_single(items[k], stream)) return rc;
+    return 0;
+  }
+  static int launch_group(const Group& tg, const uint8_t* dev, hipStream_t st) {
+    TableSrc src;
+    src.it = reinterpret_cast<const BatchItem*>(dev + tg.items_off);
+    src.map = reinterpret_cast<const uint32_t*>(dev + tg.map_off);
+    src.shift = tg.shift;
+    return launch_batch_dt((int)tg.dtype, src, tg.grid, tg.out_bytes, st);
+  }
+  static int launch_single(const Item& d, void* stream) {
+    const int64_t n = elems(d);
+    if (n == 0) return 0;
+    if ((d.flags & MCTQ_FQ_ITEM_PER_TENSOR) && d.zero_points)
+      return mctq_fq_per_tensor_tqp(d.x, d.y, n, d.dtype, d.scales, d.zero_points, d.quant_min, d.quant_max, stream);
+    if ((d.flags & MCTQ_FQ_ITEM_PER_TENSOR) && d.dtype == MCTQ_DT_F64)
+      return fail_arg("a float64 per-tensor item needs a zero_points pointer");
+    return mctq_fq_per_channel(d.x, d.y, d.outer, d.channels, d.inner, d.dtype, d.scales, d.zero_points, d.quant_min,
+                               d.quant_max, stream);
+  }
 };
-static_assert(sizeof(TableHeader) == 128, "table header layout");
+static_assert(sizeof(TableHeader<AffineKind::Group>) == 32 + 3 * 32, "table header layout");
 
 }  // namespace mctq
 
 extern "C" {
 
 int mctq_fq_batched(const mctq_fq_item* items, int32_t n_items, void* stream) {
-  // validate everything before the first launch: a bad descriptor must not leave the list half done
-  if (int rc = validate_items(items, n_items)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  bool singles = false;
-  for (int dt = MCTQ_DT_F32; dt <= MCTQ_DT_BF16; ++dt) {
-    const uint32_t tile_e = tile_elems_of(dt);
-    const int64_t esz = dt == MCTQ_DT_F32 ? 4 : 2;
-    int32_t k = 0;
-    while (k < n_items) {
-      // next group: up to kMaxBatch batchable tensors of this storage type whose chunk map fits the kernel arguments
-      KernargSrc a;
-      uint32_t tiles[kMaxBatch];
-      int m = 0;
-      int64_t out_bytes = 0;
-      uint64_t total_tiles = 0;
-      for (; k < n_items && m < kMaxBatch; ++k) {
-        const mctq_fq_item& d = items[k];
-        if (d.dtype != dt) { if (d.dtype == MCTQ_DT_F64 && dt == MCTQ_DT_F32) singles = true; continue; }
-        const int64_t n = d.outer * d.channels * d.inner;
-        if (n == 0) continue;
-        if (!batchable(d)) { singles = true; continue; }
-        const uint32_t t = (uint32_t)((n + tile_e - 1) / tile_e);
-        if (total_tiles + t + ((uint64_t)kMaxBatch << 21) > 0x7fffffffull) break;    // grid limit (incl. chunk padding)
-        fill_item(a.it[m], d, t);
-        tiles[m++] = t;
-        total_tiles += t;
-        out_bytes += n * esz;
-      }
-      if (m == 0) continue;
-      a.shift = chunk_shift(tiles, m, kMaxChunksK);
-      memset(a.map, 0, sizeof(a.map));
-      uint32_t chunk = 0;
-      uint8_t* map = reinterpret_cast<uint8_t*>(a.map);
-      for (int j = 0; j < m; ++j) {
-        a.it[j].tile_begin = chunk << a.shift;
-        const uint32_t c = (tiles[j] + (1u << a.shift) - 1) >> a.shift;
-        memset(map + chunk, j, c);
-        chunk += c;
-      }
-      if (int rc = launch_batch_dt(dt, a, chunk << a.shift, out_bytes, st)) return rc;
-    }
-  }
-  if (singles)
-    for (int32_t k = 0; k < n_items; ++k)                     // what one grid cannot take: one launch each, same stream
-      if (!batchable(items[k]))
-        if (int rc = launch_single(items[k], stream)) return rc;
-  return 0;
+  return AffineKind::run_kernarg(items, n_items, stream);
 }
 
 int64_t mctq_fq_batch_pack(const mctq_fq_item* items, int32_t n_items, void* host_table, int64_t capacity) {
-  if (int rc = validate_items(items, n_items)) return rc;
-  // sizes first
-  uint32_t count[3] = {0, 0, 0}, n_singles = 0;
-  for (int32_t k = 0; k < n_items; ++k) {
-    const mctq_fq_item& d = items[k];
-    if (d.outer * d.channels * d.inner == 0) continue;
-    if (batchable(d)) ++count[d.dtype - MCTQ_DT_F32]; else ++n_singles;
-  }
-  for (int g = 0; g < 3; ++g)
-    if (count[g] > 0xffffu) return fail_arg("more than 65535 tensors of one storage type");
-  uint32_t shift[3] = {0, 0, 0}, chunks[3] = {0, 0, 0};
-  uint32_t* tl = n_items ? (uint32_t*)malloc(sizeof(uint32_t) * (size_t)n_items) : nullptr;
-  if (n_items && !tl) return fail_arg("out of host memory");
-  for (int g = 0; g < 3; ++g) {
-    if (!count[g]) continue;
-    const uint32_t tile_e = tile_elems_of(MCTQ_DT_F32 + g);
-    int m = 0;
-    uint64_t total = 0;
-    for (int32_t k = 0; k < n_items; ++k) {
-      const mctq_fq_item& d = items[k];
-      const int64_t n = d.outer * d.channels * d.inner;
-      if (d.dtype != MCTQ_DT_F32 + g || n == 0 || !batchable(d)) continue;
-      tl[m] = (uint32_t)((n + tile_e - 1) / tile_e);
-      total += tl[m++];
-    }
-    shift[g] = chunk_shift(tl, m, kMaxChunksT);
-    for (int j = 0; j < m; ++j) chunks[g] += (tl[j] + (1u << shift[g]) - 1) >> shift[g];
-    if (total + ((uint64_t)m << shift[g]) > 0x7fffffffull) { free(tl); return fail_arg("too many tiles for one launch"); }
-  }
-  auto align16 = [](uint64_t v) { return (v + 15u) & ~(uint64_t)15u; };
-  uint64_t off = sizeof(TableHeader);
-  uint64_t items_off[3], map_off[3];
-  for (int g = 0; g < 3; ++g) {
-    items_off[g] = off; off += (uint64_t)count[g] * sizeof(BatchItem);
-    map_off[g] = off; off = align16(off + (uint64_t)chunks[g] * 2u + 2u);
-  }
-  const uint64_t singles_off = off;
-  off = align16(off + (uint64_t)n_singles * sizeof(mctq_fq_item));
-  if (off > 0x7fffffffull) { free(tl); return fail_arg("table too large"); }
-  if (!host_table || capacity < (int64_t)off) { free(tl); return (int64_t)off; }     // size query
-
-  uint8_t* base = static_cast<uint8_t*>(host_table);
-  memset(base, 0, (size_t)off);
-  TableHeader* h = reinterpret_cast<TableHeader*>(base);
-  h->magic = kTableMagic; h->version = MCTQ_ABI_VERSION; h->total_bytes = (uint32_t)off;
-  h->n_singles = n_singles; h->singles_off = (uint32_t)singles_off;
-  for (int g = 0; g < 3; ++g) {
-    if (!count[g]) continue;
-    TableGroup& tg = h->g[h->n_groups++];
-    tg.dtype = MCTQ_DT_F32 + g; tg.items_off = (uint32_t)items_off[g]; tg.map_off = (uint32_t)map_off[g];
-    tg.n_items = count[g]; tg.shift = shift[g]; tg.out_bytes = 0;
-    const uint32_t tile_e = tile_elems_of(tg.dtype);
-    BatchItem* bi = reinterpret_cast<BatchItem*>(base + items_off[g]);
-    uint16_t* map = reinterpret_cast<uint16_t*>(base + map_off[g]);
-    uint32_t chunk = 0;
-    int m = 0;
-    for (int32_t k = 0; k < n_items; ++k) {
-      const mctq_fq_item& d = items[k];
-      const int64_t n = d.outer * d.channels * d.inner;
-      if (d.dtype != (int32_t)tg.dtype || n == 0 || !batchable(d)) continue;
-      const uint32_t t = (uint32_t)((n + tile_e - 1) / tile_e);
-      fill_item(bi[m], d, t);
-      bi[m].tile_begin = chunk << tg.shift;
-      const uint32_t c = (t + (1u << tg.shift) - 1) >> tg.shift;
-      for (uint32_t j = 0; j < c; ++j) map[chunk + j] = (uint16_t)m;
-      chunk += c;
-      tg.out_bytes += n * (tg.dtype == MCTQ_DT_F32 ? 4 : 2);
-      ++m;
-    }
-    tg.grid = chunk << tg.shift;
-  }
-  mctq_fq_item* sg = reinterpret_cast<mctq_fq_item*>(base + singles_off);
-  uint32_t s = 0;
-  for (int32_t k = 0; k < n_items; ++k)
-    if (items[k].outer * items[k].channels * items[k].inner != 0 && !batchable(items[k])) sg[s++] = items[k];
-  free(tl);
-  return (int64_t)off;
+  return pack_table<AffineKind>(items, n_items, host_table, capacity);
 }
 
 int mctq_fq_batch_run(const void* host_table, const void* device_table, void* stream) {
-  if (!host_table) return fail_arg("host_table is NULL");
-  const uint8_t* base = static_cast<const uint8_t*>(host_table);
-  const TableHeader* h = reinterpret_cast<const TableHeader*>(base);
-  if (h->magic != kTableMagic || h->version != (uint32_t)MCTQ_ABI_VERSION || h->n_groups > 3)
-    return fail_arg("not a table packed by this library version (mctq_fq_batch_pack)");
-  if (h->n_groups && (!device_table || ((uintptr_t)device_table & 15u))) return fail_arg("device_table is NULL or not 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  const uint8_t* dev = static_cast<const uint8_t*>(device_table);
-  for (uint32_t g = 0; g < h->n_groups; ++g) {
-    const TableGroup& tg = h->g[g];
-    TableSrc src;
-    src.it = reinterpret_cast<const BatchItem*>(dev + tg.items_off);
-    src.map = reinterpret_cast<const uint32_t*>(dev + tg.map_off);
-    src.shift = tg.shift;
-    if (int rc = launch_batch_dt((int)tg.dtype, src, tg.grid, tg.out_bytes, st)) return rc;
-  }
-  const mctq_fq_item* sg = reinterpret_cast<const mctq_fq_item*>(base + h->singles_off);
-  for (uint32_t s = 0; s < h->n_singles; ++s)
-    if (int rc = launch_single(sg[s], stream)) return rc;
-  return 0;
+  return run_table<AffineKind>(host_table, device_table, stream);
 }
 
 }  // extern "C"
 #endif  // affine part
 
 #if MCTQ_BATCHED_PART == 2
-}  // namespace mctq
+template <class TI>
+static int launch_lut_batch(const LutTableSrc& src, uint32_t grid, size_t lds, int64_t out_bytes, hipStream_t st) {
+  MCTQ_WITH_MODE(nt_mode(out_bytes), {
+    hipLaunchKernelGGL((batched_lut_table_kernel<TI, kBatchU, NT>), dim3(grid), dim3(kThreads), lds, st, src.it, src.map, src.shift);
+    note<LutTableOp, TI, float>("batched_lut_kernel<table>", kBatchU, NT);
+  });
+  return check_launch("batched LUT launch");
+}
 
-extern "C" {
-
-// ---- LUT quantizers with a decision table: the same table-driven grid -------------------------------------------
-namespace {
-
-int validate_lut_items(const mctq_lut_item* items, int32_t n_items) {
-  if (n_items < 0) return fail_arg("n_items < 0");
-  if (n_items > 0 && !items) return fail_arg("items is NULL");
-  for (int32_t k = 0; k < n_items; ++k) {
-    const mctq_lut_item& d = items[k];
-    if (d.outer < 0 || d.channels < 0 || d.inner < 0) return fail_arg("negative extent");
-    if (d.outer * d.channels * d.inner > 0 && (!d.x || !d.y || !d.table)) return fail_arg("NULL pointer");
+// LUT quantizers with a decision table: the same table-driven grid.  The float32 output decides the lane-vector (4
+// elements), so the tile is the same for every storage type; a per-tensor item (thresholds NULL) is one row.
+struct LutKind {
+  typedef mctq_lut_item Item;
+  typedef LutBatchItem Desc;
+  struct Group { uint32_t dtype, items_off, map_off, n_items, grid, shift, lds_bytes, pad; int64_t out_bytes; };
+  static constexpr uint32_t kMagic = 0x4d43544cu;   // "MCTL"
+  static constexpr const char* kNotPacked = "not a table packed by this library version (mctq_lutt_batch_pack)";
+  static constexpr uint32_t kTile = kThreads * kBatchU * 4;
+  static uint32_t tile(int) { return kTile; }
+  static int check_range(const Item&) { return 0; }
+  static const void* params(const Item& d) { return d.table; }
+  static int check(const Item& d) {
     if (d.dtype != MCTQ_DT_F32 && d.dtype != MCTQ_DT_F16 && d.dtype != MCTQ_DT_BF16) return fail_arg("unknown dtype");
     if (d.step_round != 0 && d.step_round != MCTQ_DT_F16 && d.step_round != MCTQ_DT_BF16) return fail_arg("bad step_round");
     if (d.step_round != 0 && d.thresholds) return fail_arg("step_round is a per-tensor option");
     if (check_pow2(d.mult)) return MCTQ_E_ARG;
     if (d.entries != table_entries(d.clip_min, d.clip_max)) return fail_arg("entries does not match the clip range");
+    return 0;
   }
-  return 0;
-}
-
-uint32_t lut_tile_elems(int dtype) {      // 256 lanes x 4 vectors x N, N = 16 B / 4 B (the float32 output decides)
-  (void)dtype;
-  return kThreads * kBatchU * 4;
-}
-
-bool lut_batchable(const mctq_lut_item& d) {
-  const int64_t n = d.outer * d.channels * d.inner;
-  const uintptr_t xa = d.dtype == MCTQ_DT_F32 ? 15u : 7u;    // a lane-vector: 4 elements in, 4 float32 out
-  if (((uintptr_t)d.x & xa) || ((uintptr_t)d.y & 15u)) return false;
-  if (n >= (1ll << 31) - (int64_t)lut_tile_elems(d.dtype) || d.channels > 0x7fffffffLL || d.inner > 0x7fffffffLL) return false;
-  return !d.thresholds || d.outer * d.channels == 1 || d.inner >= 32 || n <= (1ll << 20);
-}
-
-int launch_lut_single(const mctq_lut_item& d, void* stream) {
-  const int64_t n = d.outer * d.channels * d.inner;
-  if (n == 0) return 0;
-  if (!d.thresholds)
-    return mctq_lutt_per_tensor(d.x, d.y, n, d.dtype, d.step_round, d.thr_div, d.thr_mul, d.table, d.entries, d.mult,
-                                d.clip_min, d.clip_max, stream);
-  return mctq_lutt_per_channel(d.x, d.y, d.outer, d.channels, d.inner, d.dtype, d.thresholds, d.eps, d.table, d.entries,
-                               d.mult, d.clip_min, d.clip_max, stream);
-}
-
-constexpr uint32_t kLutTableMagic = 0x4d43544cu;   // "MCTL"
-struct LutTableGroup { uint32_t dtype, items_off, map_off, n_items, grid, shift, lds_bytes, pad; int64_t out_bytes; };
-struct LutTableHeader {
-  uint32_t magic, version, total_bytes, n_groups, n_singles, singles_off, pad0, pad1;
-  LutTableGroup g[3];
-};
-static_assert(sizeof(LutTableHeader) == 32 + 3 * 40, "LUT table header layout");
-
-}  // namespace
-
-int64_t mctq_lutt_batch_pack(const mctq_lut_item* items, int32_t n_items, void* host_table, int64_t capacity) {
-  if (int rc = validate_lut_items(items, n_items)) return rc;
-  uint32_t count[3] = {0, 0, 0}, n_singles = 0, shift[3] = {0, 0, 0}, chunks[3] = {0, 0, 0};
-  for (int32_t k = 0; k < n_items; ++k) {
-    const mctq_lut_item& d = items[k];
-    if (d.outer * d.channels * d.inner == 0) continue;
-    if (lut_batchable(d)) ++count[d.dtype - MCTQ_DT_F32]; else ++n_singles;
+  static bool one_row(const Item& d) { return !d.thresholds || d.outer * d.channels == 1; }
+  static bool batchable(const Item& d) { return fits_grid(d, d.dtype == MCTQ_DT_F32 ? 15u : 7u, kTile, one_row(d)); }
+  static void fill(Desc& b, const Item& d, uint32_t tiles) {
+    fill_head(b.b, d, one_row(d), tiles);
+    b.b.scales = d.thresholds; b.b.zps = reinterpret_cast<const int32_t*>(d.table);
+    b.b.lo = 0.f; b.b.hi = 0.f;
+    b.mult = d.mult; b.cmin = d.clip_min; b.cmax = d.clip_max; b.eps = d.eps; b.thr_div = d.thr_div; b.thr_mul = d.thr_mul;
+    b.entries = d.entries; b.step_round = d.step_round;
   }
-  for (int g = 0; g < 3; ++g)
-    if (count[g] > 0xffffu) return fail_arg("more than 65535 tensors of one storage type");
-  std::vector<uint32_t> tl((size_t)(n_items > 0 ? n_items : 1));
-  for (int g = 0; g < 3; ++g) {
-    if (!count[g]) continue;
-    const uint32_t tile_e = lut_tile_elems(MCTQ_DT_F32 + g);
-    int m = 0;
-    uint64_t total = 0;
-    for (int32_t k = 0; k < n_items; ++k) {
-      const mctq_lut_item& d = items[k];
-      const int64_t n = d.outer * d.channels * d.inner;
-      if (d.dtype != MCTQ_DT_F32 + g || n == 0 || !lut_batchable(d)) continue;
-      tl[m] = (uint32_t)((n + tile_e - 1) / tile_e);
-      total += tl[m++];
-    }
-    shift[g] = chunk_shift(tl.data(), m, kMaxChunksT);
-    for (int j = 0; j < m; ++j) chunks[g] += (tl[j] + (1u << shift[g]) - 1) >> shift[g];
-    if (total + ((uint64_t)m << shift[g]) > 0x7fffffffull) return fail_arg("too many tiles for one launch");
+  static void add_to_group(Group& tg, const Item& d) {      // the launch's dynamic LDS holds the largest item's table
+    tg.out_bytes += elems(d) * 4;
+    const uint32_t lds = (uint32_t)table_bytes(d.entries);
+    if (lds > tg.lds_bytes) tg.lds_bytes = lds;
   }
-  auto align16 = [](uint64_t v) { return (v + 15u) & ~(uint64_t)15u; };
-  uint64_t off = align16(sizeof(LutTableHeader));
-  uint64_t items_off[3], map_off[3];
-  for (int g = 0; g < 3; ++g) {
-    items_off[g] = off; off += (uint64_t)count[g] * sizeof(LutBatchItem);
-    map_off[g] = off; off = align16(off + (uint64_t)chunks[g] * 2u + 2u);
-  }
-  const uint64_t singles_off = off;
-  off = align16(off + (uint64_t)n_singles * sizeof(mctq_lut_item));
-  if (off > 0x7fffffffull) return fail_arg("table too large");
-  if (!host_table || capacity < (int64_t)off) return (int64_t)off;     // size query
-
-  uint8_t* base = static_cast<uint8_t*>(host_table);
-  memset(base, 0, (size_t)off);
-  LutTableHeader* h = reinterpret_cast<LutTableHeader*>(base);
-  h->magic = kLutTableMagic; h->version = MCTQ_ABI_VERSION; h->total_bytes = (uint32_t)off;
-  h->n_singles = n_singles; h->singles_off = (uint32_t)singles_off;
-  for (int g = 0; g < 3; ++g) {
-    if (!count[g]) continue;
-    LutTableGroup& tg = h->g[h->n_groups++];
-    tg.dtype = MCTQ_DT_F32 + g; tg.items_off = (uint32_t)items_off[g]; tg.map_off = (uint32_t)map_off[g];
-    tg.n_items = count[g]; tg.shift = shift[g]; tg.out_bytes = 0; tg.lds_bytes = 0;
-    const uint32_t tile_e = lut_tile_elems(tg.dtype);
-    LutBatchItem* bi = reinterpret_cast<LutBatchItem*>(base + items_off[g]);
-    uint16_t* map = reinterpret_cast<uint16_t*>(base + map_off[g]);
-    uint32_t chunk = 0;
-    int m = 0;
-    for (int32_t k = 0; k < n_items; ++k) {
-      const mctq_lut_item& d = items[k];
-      const int64_t n = d.outer * d.channels * d.inner;
-      if (d.dtype != (int32_t)tg.dtype || n == 0 || !lut_batchable(d)) continue;
-      const uint32_t t = (uint32_t)((n + tile_e - 1) / tile_e);
-      LutBatchItem& b = bi[m];
-      const bool one_row = !d.thresholds || d.outer * d.channels == 1;
-      b.b.x = d.x; b.b.y = d.y; b.b.scales = d.thresholds; b.b.zps = reinterpret_cast<const int32_t*>(d.table);
-      b.b.n = (uint32_t)n; b.b.inner = one_row ? (uint32_t)n : (uint32_t)d.inner; b.b.channels = one_row ? 1u : (uint32_t)d.channels;
-      b.b.tile_begin = chunk << tg.shift; b.b.tiles = t; b.b.reserved = 0; b.b.lo = 0.f; b.b.hi = 0.f;
-      b.mult = d.mult; b.cmin = d.clip_min; b.cmax = d.clip_max; b.eps = d.eps; b.thr_div = d.thr_div; b.thr_mul = d.thr_mul;
-      b.entries = d.entries; b.step_round = d.step_round;
-      const uint32_t c = (t + (1u << tg.shift) - 1) >> tg.shift;
-      for (uint32_t j = 0; j < c; ++j) map[chunk + j] = (uint16_t)m;
-      chunk += c;
-      tg.out_bytes += n * 4;
-      const uint32_t lds = (uint32_t)table_bytes(d.entries);
-      if (lds > tg.lds_bytes) tg.lds_bytes = lds;
-      ++m;
-    }
-    tg.grid = chunk << tg.shift;
-  }
-  mctq_lut_item* sg = reinterpret_cast<mctq_lut_item*>(base + singles_off);
-  uint32_t sidx = 0;
-  for (int32_t k = 0; k < n_items; ++k)
-    if (items[k].outer * items[k].channels * items[k].inner != 0 && !lut_batchable(items[k])) sg[sidx++] = items[k];
-  return (int64_t)off;
-}
-
-int mctq_lutt_batch_run(const void* host_table, const void* device_table, void* stream) {
-  if (!host_table) return fail_arg("host_table is NULL");
-  const uint8_t* base = static_cast<const uint8_t*>(host_table);
-  const LutTableHeader* h = reinterpret_cast<const LutTableHeader*>(base);
-  if (h->magic != kLutTableMagic || h->version != (uint32_t)MCTQ_ABI_VERSION || h->n_groups > 3)
-    return fail_arg("not a table packed by this library version (mctq_lutt_batch_pack)");
-  if (h->n_groups && (!device_table || ((uintptr_t)device_table & 15u))) return fail_arg("device_table is NULL or not 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  const uint8_t* dev = static_cast<const uint8_t*>(device_table);
-  for (uint32_t g = 0; g < h->n_groups; ++g) {
-    const LutTableGroup& tg = h->g[g];
+  static int launch_group(const Group& tg, const uint8_t* dev, hipStream_t st) {
     LutTableSrc src;
     src.it = reinterpret_cast<const LutBatchItem*>(dev + tg.items_off);
     src.map = reinterpret_cast<const uint32_t*>(dev + tg.map_off);
     src.shift = tg.shift;
-    int rc;
-    if (tg.dtype == MCTQ_DT_F32) rc = launch_lut_batch<float>(src, tg.grid, tg.lds_bytes, tg.out_bytes, st);
-    else if (tg.dtype == MCTQ_DT_F16) rc = launch_lut_batch<_Float16>(src, tg.grid, tg.lds_bytes, tg.out_bytes, st);
-    else rc = launch_lut_batch<__bf16>(src, tg.grid, tg.lds_bytes, tg.out_bytes, st);
-    if (rc) return rc;
+    if (tg.dtype == MCTQ_DT_F32) return launch_lut_batch<float>(src, tg.grid, tg.lds_bytes, tg.out_bytes, st);
+    if (tg.dtype == MCTQ_DT_F16) return launch_lut_batch<_Float16>(src, tg.grid, tg.lds_bytes, tg.out_bytes, st);
+    return launch_lut_batch<__bf16>(src, tg.grid, tg.lds_bytes, tg.out_bytes, st);
   }
-  const mctq_lut_item* sg = reinterpret_cast<const mctq_lut_item*>(base + h->singles_off);
-  for (uint32_t k = 0; k < h->n_singles; ++k)
-    if (int rc = launch_lut_single(sg[k], stream)) return rc;
-  return 0;
+  static int launch_single(const Item& d, void* stream) {
+    const int64_t n = elems(d);
+    if (n == 0) return 0;
+    if (!d.thresholds)
+      return mctq_lutt_per_tensor(d.x, d.y, n, d.dtype, d.step_round, d.thr_div, d.thr_mul, d.table, d.entries, d.mult,
+                                  d.clip_min, d.clip_max, stream);
+    return mctq_lutt_per_channel(d.x, d.y, d.outer, d.channels, d.inner, d.dtype, d.thresholds, d.eps, d.table, d.entries,
+                                 d.mult, d.clip_min, d.clip_max, stream);
+  }
+};
+static_assert(sizeof(TableHeader<LutKind::Group>) == 32 + 3 * 40, "LUT table header layout");
+
+}  // namespace mctq
+
+extern "C" {
+
+int64_t mctq_lutt_batch_pack(const mctq_lut_item* items, int32_t n_items, void* host_table, int64_t capacity) {
+  return pack_table<LutKind>(items, n_items, host_table, capacity);
+}
+
+int mctq_lutt_batch_run(const void* host_table, const void* device_table, void* stream) {
+  return run_table<LutKind>(host_table, device_table, stream);
 }
 
 }  // extern "C"

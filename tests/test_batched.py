@@ -103,6 +103,120 @@ def test_batch_pack_is_host_code_and_maps_every_block_to_its_tensor():
     assert lib.mctq_fq_batch_run(hdr, None, None) == 0
 
 
+LUT_TILE = 4096                      # the float32 output decides the lane-vector: 256 lanes x 4 vectors x 4 elements, whatever x's type
+
+
+def _lut_table_bytes(entries):
+    return (((entries + 1) * 2 + 3) & ~3) * 4
+
+
+def _parse_lut_table(buf: bytes):
+    magic, version, total, n_groups, n_singles, singles_off, _, _ = struct.unpack_from("<8I", buf, 0)
+    groups = []
+    for g in range(n_groups):
+        dtype, items_off, map_off, n_items, grid, shift, lds_bytes, _pad, out_bytes = struct.unpack_from("<8Iq", buf, 32 + 40 * g)
+        items = []
+        for k in range(n_items):
+            f = struct.unpack_from("<4Q6I2f6f2i", buf, items_off + 96 * k)
+            items.append(dict(zip(("x", "y", "thresholds", "table", "n", "inner", "channels", "tile_begin", "tiles", "reserved", "lo", "hi",
+                                   "mult", "cmin", "cmax", "eps", "thr_div", "thr_mul", "entries", "step_round"), f)))
+        cmap = struct.unpack_from(f"<{grid >> shift}H", buf, map_off)
+        groups.append(dict(dtype=dtype, items=items, grid=grid, shift=shift, lds_bytes=lds_bytes, out_bytes=out_bytes, map=cmap))
+    return dict(magic=magic, version=version, total=total, n_singles=n_singles, singles_off=singles_off, groups=groups)
+
+
+def test_lut_batch_pack_is_host_code_and_maps_every_block_to_its_tensor():
+    """mctq_lutt_batch_pack, the decision-table flavour of the packed table: 40-byte groups, 96-byte descriptors."""
+    from mct_quantizers_amd.hip import native
+    lib = native.load()
+    rng = np.random.default_rng(9)
+    widths = [1, 2, 7, 64, 127, 255, 1023]                         # clip_max - clip_min: 3 ... 2047 table entries (the largest)
+    specs = []                                                   # (outer, channels, inner, dtype, per_tensor, width)
+    for k in range(54):
+        dt = (native.DT_F32, native.DT_F16, native.DT_BF16)[k % 3]
+        if k % 4 == 0:
+            specs.append((1, 1, int(rng.choice([1, 37, 4095, 4096, 4097, 70000])), dt, True, widths[k % 7]))
+        else:
+            specs.append((int(rng.choice([1, 1, 3])), int(rng.integers(1, 300)), int(rng.choice([1, 9, 32, 64, 147, 1000, 4608])), dt,
+                          False, widths[k % 7]))
+    specs += [(1, 1, 100_000_003, native.DT_F32, True, 127),      # more tiles than the map has entries: chunks of two blocks
+              (1, 1, 0, native.DT_F32, True, 127),                # empty
+              (1, 1 << 19, 3, native.DT_F32, False, 127),         # a LARGE tensor of short rows: its own launch ...
+              (1, 1, (1 << 19) * 3, native.DT_BF16, True, 127),   # ... unless it is per tensor
+              (1, 40, 64, native.DT_F32, False, 127), (1, 40, 64, native.DT_F16, False, 127), (1, 40, 64, native.DT_BF16, False, 127)]
+    n = len(specs)
+    X_OFF = {n - 3: 4, n - 2: 8}                                 # float32 x off by 4 bytes: alone; 16-bit x on 8 bytes: a lane-vector, rides along
+    Y_OFF = {n - 1: 4}                                           # y off by 4 bytes: alone
+    arr = (native.LutItem * n)()
+    base = 0x10000000
+    for k, (outer, c, inner, dt, per_tensor, w) in enumerate(specs):
+        it = arr[k]
+        it.x, it.y = base + 0x40000000 * k + X_OFF.get(k, 0), base + 0x40000000 * k + 0x20000000 + Y_OFF.get(k, 0)
+        it.outer, it.channels, it.inner = outer, c, inner
+        it.thresholds, it.table, it.entries = (None if per_tensor else 0x5000 + 16 * k), 0x9000 + 16 * k, 2 * w + 1
+        it.eps, it.thr_div, it.thr_mul = (0.0, 1.5, 1.25) if per_tensor else (1e-8, 0.0, 0.0)
+        it.mult, it.clip_min, it.clip_max, it.dtype = 128.0, float(-(w // 2)), float(-(w // 2) + w), dt
+        it.step_round = native.DT_F16 if per_tensor and k % 8 == 0 else 0
+    need = lib.mctq_lutt_batch_pack(arr, n, None, 0)             # a size query ...
+    assert need > 152
+    buf = ctypes.create_string_buffer(need)
+    assert lib.mctq_lutt_batch_pack(arr, n, buf, need - 1) == need and buf.raw == b"\0" * need     # ... and a too-small capacity write nothing
+    assert lib.mctq_lutt_batch_pack(arr, n, buf, need) == need
+    t = _parse_lut_table(buf.raw)
+    assert t["magic"] == 0x4d43544c and t["version"] == native.ABI_VERSION and t["total"] == need
+    assert sorted(g["dtype"] for g in t["groups"]) == [native.DT_F32, native.DT_F16, native.DT_BF16]
+
+    def rides(k):
+        outer, c, inner, dt, per_tensor, _ = specs[k]
+        aligned = (arr[k].x % (16 if dt == native.DT_F32 else 8) == 0) and arr[k].y % 16 == 0
+        return aligned and (per_tensor or outer * c == 1 or inner >= 32 or outer * c * inner <= (1 << 20))
+
+    nonempty = [k for k in range(n) if specs[k][0] * specs[k][1] * specs[k][2] > 0]
+    alone = [k for k in nonempty if not rides(k)]
+    assert alone == [n - 5, n - 3, n - 1] and t["n_singles"] == 3        # singles are counted, and copied as they came
+    item_bytes = ctypes.sizeof(native.LutItem)
+    for j, k in enumerate(alone):
+        assert buf.raw[t["singles_off"] + item_bytes * j:t["singles_off"] + item_bytes * (j + 1)] == bytes(arr[k])
+    packed = 0
+    for g in t["groups"]:
+        want = [k for k in nonempty if specs[k][3] == g["dtype"] and rides(k)]
+        assert len(g["items"]) == len(want)
+        work = 0
+        for k, it in zip(want, g["items"]):
+            outer, c, inner, _, per_tensor, w = specs[k]
+            nel = outer * c * inner
+            assert it["n"] == nel and it["tiles"] == -(-nel // LUT_TILE) and it["x"] == arr[k].x and it["y"] == arr[k].y
+            assert (it["inner"], it["channels"]) == ((nel, 1) if per_tensor or outer * c == 1 else (inner, c))
+            assert it["thresholds"] == (arr[k].thresholds or 0) and it["table"] == arr[k].table and (it["lo"], it["hi"]) == (0.0, 0.0)
+            assert (it["mult"], it["cmin"], it["cmax"], it["entries"], it["step_round"]) == \
+                (128.0, arr[k].clip_min, arr[k].clip_max, 2 * w + 1, arr[k].step_round)
+            assert (it["eps"], it["thr_div"], it["thr_mul"]) == (arr[k].eps, arr[k].thr_div, arr[k].thr_mul)
+            assert it["tile_begin"] % (1 << g["shift"]) == 0 and it["reserved"] == 0
+            work += it["tiles"]
+        assert g["grid"] == len(g["map"]) << g["shift"] and len(g["map"]) <= 16384
+        assert g["shift"] == (1 if g["dtype"] == native.DT_F32 else 0)
+        assert g["lds_bytes"] == max(_lut_table_bytes(2 * specs[k][5] + 1) for k in want)      # the largest item's table
+        assert g["out_bytes"] == 4 * sum(it["n"] for it in g["items"])
+        # every block of the grid: the map names the tensor whose [tile_begin, tile_begin + chunk-padded tiles) holds it
+        seen = 0
+        for b in range(g["grid"]):
+            it = g["items"][g["map"][b >> g["shift"]]]
+            assert it["tile_begin"] <= b
+            seen += b - it["tile_begin"] < it["tiles"]
+        assert seen == work
+        packed += len(g["items"])
+    assert packed + t["n_singles"] == n - 1                     # the empty tensor is nowhere
+    # errors: nothing is launched or written
+    arr[0].entries = 4
+    assert lib.mctq_lutt_batch_pack(arr, n, None, 0) == native.MCTQ_E_ARG and b"entries" in lib.mctq_last_error()
+    assert lib.mctq_lutt_batch_run(None, None, None) == native.MCTQ_E_ARG
+    assert lib.mctq_lutt_batch_run(b"\0" * 256, None, None) == native.MCTQ_E_ARG and b"mctq_lutt_batch_pack" in lib.mctq_last_error()
+    bare = lib.mctq_lutt_batch_pack(None, 0, None, 0)           # an empty list packs to a bare header: nothing to launch
+    hdr = ctypes.create_string_buffer(bare)
+    assert 152 <= bare <= 256 and lib.mctq_lutt_batch_pack(None, 0, hdr, bare) == bare
+    assert lib.mctq_lutt_batch_run(hdr, None, None) == 0
+
+
 def test_wrapper_state_drops_the_prepared_tensors_and_handle_pickles_on_cpu():
     """torch.save / deepcopy of a model with the batching handle installed: the handle's launch state and
     the tensors prepared for one forward stay behind; the copy quantizes on its own."""
@@ -688,3 +802,57 @@ def test_a_recorded_forward_is_told_apart_from_an_inference_forward():
     y = model(x)                                                     # and the CPU forward is what it was
     assert y.shape == (2, 3)
     h.remove()
+
+
+@pytest.mark.gpu
+def test_batch_plan_sides_follow_their_own_inputs():
+    """One plan with three affine and three LUT items (the three storage types; a tile inside one row, over several rows, and
+    lane-vectors that straddle rows).  The two sides keep their own packed table: re-pointing a LUT input re-packs the LUT
+    side, re-pointing an affine input the affine side, and after every call every output equals the single-tensor entry
+    point's bit for bit.  Three calls are three launches; with versioned reuse a fourth call with nothing changed is a skip."""
+    from mct_quantizers_amd.hip import native, ops
+    fast = native.fast()
+    if fast is None:
+        pytest.skip("needs the compiled binding (BatchPlan)")
+    torch.manual_seed(21)
+    dev = "cuda"
+    table = ops.make_lut_table(np.float32(LUT16), 128.0, -128.0, 127.0, dev)
+    lut_args = (128.0, -128.0, 127.0)
+    zero1 = torch.zeros(1, dtype=torch.int32, device=dev)
+    affine = []                                                   # (x, scales, zero_points | None, axis | None)
+    for shape, dt, axis in (((8, 64), torch.float32, 0), ((3, 3, 1, 5), torch.bfloat16, 0), ((1000,), torch.float16, None)):
+        c = 1 if axis is None else shape[axis]
+        affine.append((torch.randn(shape, device=dev).to(dt), torch.rand(c, device=dev) * 0.05 + 0.01,
+                       zero1 if axis is None else (torch.randint(-3, 4, (c,), dtype=torch.int32, device=dev) if dt == torch.float32 else None), axis))
+    luts = []                                                     # (x, thresholds | None, axis | None)
+    for shape, dt, axis in (((8, 64), torch.float32, 0), ((37,), torch.float16, None), ((4, 33), torch.bfloat16, 0)):
+        luts.append((torch.randn(shape, device=dev).to(dt), None if axis is None else torch.rand(shape[axis], device=dev) + 1.0, axis))
+    outs_a = [torch.empty_like(x) for x, _, _, _ in affine]
+    outs_l = [torch.empty(x.shape, dtype=torch.float32, device=dev) for x, _, _ in luts]
+    thr_div, thr_mul = float(np.float32(1.75) + np.float32(1e-8)), 1.75
+    items = [(x, y, s, z, axis, -128, 127) for (x, s, z, axis), y in zip(affine, outs_a)]
+    items += [("lut", x, y, thr, table, axis, 1e-8 if axis is not None else 0.0, 0.0 if axis is not None else thr_div,
+               0.0 if axis is not None else thr_mul) + lut_args + (0,) for (x, thr, axis), y in zip(luts, outs_l)]
+    plan = fast.BatchPlan(items, True)
+
+    def check(what):
+        assert plan() is None
+        for (x, s, z, axis), y in zip(affine, outs_a):
+            want = fast.fq_per_tensor_tqp(x, s, z, -128, 127) if axis is None else fast.fq_per_channel(x, s, z, axis, -128, 127)
+            assert want is not NotImplemented and torch.equal(y.view(torch.int16 if y.element_size() == 2 else torch.int32),
+                                                              want.view(torch.int16 if y.element_size() == 2 else torch.int32)), (what, tuple(x.shape))
+        for (x, thr, axis), y in zip(luts, outs_l):
+            want = fast.lutt_per_tensor(x, table, 0, thr_div, thr_mul, *lut_args) if axis is None else \
+                fast.lutt_per_channel(x, thr, 1e-8, table, axis, *lut_args)
+            assert want is not NotImplemented and torch.equal(y.view(torch.int32), want.view(torch.int32)), (what, tuple(x.shape))
+
+    check("first call")
+    w = luts[2][0]
+    w.data = w.data.clone().mul_(0.75)                            # a LUT input in new storage (and with new values)
+    check("LUT input re-pointed")
+    w = affine[1][0]
+    w.data = w.data.clone().mul_(0.75)                            # then an affine one
+    check("affine input re-pointed")
+    assert plan.stats() == (3, 0)
+    check("nothing changed")
+    assert plan.stats() == (3, 1)
