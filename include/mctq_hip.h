@@ -68,6 +68,8 @@ extern "C" {
  * holder (fake-quantized float32 and integer codes) in one pass; no existing signature or result changed. */
 /* v10 (additive, the version number stays): + mctq_fq_join_rc_f32, the join with its residual operand given as the int8 / uint8 codes
  * of another join (identity branches that stay on codes); no existing signature or result changed. */
+/* v10 (additive, the version number stays): + mctq_codes_maxpool_nhwc, torch.nn.MaxPool2d on NHWC activation codes (a max pool between
+ * an activation holder and the integer consumers behind it stays on codes); no existing signature or result changed. */
 #define MCTQ_ABI_VERSION 10
 #define MCTQ_E_ARG (-10001)
 
@@ -509,6 +511,38 @@ int mctq_fq_codes_nchw_to_nhwc(const void* x, void* codes, int64_t batch, int64_
 int mctq_codes_im2col_nhwc(const void* codes, void* patches, int64_t batch, int64_t height, int64_t width, int64_t channels,
                            int32_t kh, int32_t kw, int32_t stride_h, int32_t stride_w, int32_t pad_h, int32_t pad_w,
                            int32_t dil_h, int32_t dil_w, int32_t pad_code, void* stream);
+
+/*
+ * Max pooling on activation codes (extension; the reference runs ATen's float32 max pool on the holder's output):
+ * codes [batch][height][width][channels] (NHWC, int8 -- code_dtype MCTQ_CODE_I8 -- or uint8, MCTQ_CODE_U8) -> pooled
+ * [batch][Ho][Wo][channels] of the same type, both DEVICE, 16-byte aligned, with torch.nn.MaxPool2d's semantics:
+ *     pooled[b][oy][ox][c] = max over the taps (ky, kx) inside the image of
+ *                            codes[b][oy * stride_h - pad_h + ky * dil_h][ox * stride_w - pad_w + kx * dil_w][c]
+ * in the order of the code type (signed for int8, unsigned for uint8).  A tap outside the image is ignored: it stands for
+ * -inf, not for the zero-point code.  A holder's float32 output is float(code - zero_point) * scale with scale > 0, monotone
+ * non-decreasing in the code and never NaN, so dequantizing `pooled` gives ATen's max pool of the dequantized `codes` bit
+ * for bit.  pad_h <= kh / 2 and pad_w <= kw / 2, as PyTorch requires.  Output extent, PyTorch's rule:
+ *     Ho = floor_or_ceil((height + 2 pad_h - dil_h (kh - 1) - 1) / stride_h) + 1   (ceil with ceil_mode != 0),
+ *     less one with ceil_mode if (Ho - 1) * stride_h >= height + pad_h (a last window that would start beyond the image
+ *     plus its left padding is dropped);   Wo likewise.
+ * The caller passes the out_height / out_width it allocated `pooled` for, and the call is refused unless they equal the
+ * library's own Ho / Wo: a disagreement about the extent can then never become an out-of-bounds write.
+ * A window without any tap inside the image (possible only where the image is narrower than the dilation) gives the least
+ * code of the type, 0 / -128, as ATen's integer max pool does.
+ * channels % 16 == 0.  A lane owns one 16-channel chunk of one output pixel (consecutive lanes: consecutive chunks, then
+ * consecutive pixels): one 16-byte load per tap, one 16-byte store; the input is re-read about kh * kw / (stride_h *
+ * stride_w) times out of cache.
+ * MCTQ_E_ARG with a mctq_last_error text, before any pointer is read or anything is launched, for: negative extents; a
+ * kernel size, stride or dilation below 1; negative padding; padding above half the kernel size; channels % 16 != 0; a bad
+ * code_dtype; a padded extent plus kernel span above 2^31 - 1; Ho <= 0 or Wo <= 0; out_height / out_width other than Ho /
+ * Wo; a non-empty batch of images without pixels; more than 2^31 - 1 output pixels, or more than 2^32 - 1 16-channel chunks
+ * of output (split the batch); NULL or misaligned pointers of a non-empty problem.  batch == 0 or channels == 0 returns 0
+ * without a launch.  mctq_last_launch names the launch "codes_maxpool", op "u8 max" / "i8 max".
+ */
+int mctq_codes_maxpool_nhwc(const void* codes, void* pooled, int32_t code_dtype, int64_t batch, int64_t height, int64_t width,
+                            int64_t channels, int32_t kh, int32_t kw, int32_t stride_h, int32_t stride_w, int32_t pad_h,
+                            int32_t pad_w, int32_t dil_h, int32_t dil_w, int32_t ceil_mode, int64_t out_height, int64_t out_width,
+                            void* stream);
 
 /*
  * Depthwise convolution on activation codes (groups == channels, channel multiplier 1; extension, the reference has no

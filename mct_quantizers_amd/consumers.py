@@ -50,6 +50,11 @@ consumer emits itself (``folded_clamp``: the code function is monotone, so clamp
 residual join reads its identity operand as the codes of the join in front (``mctq_fq_join_rc_f32``: ``(code - zp) * scale`` is
 that join's float32 output bit for bit), which then no longer writes float32 -- 6 bytes per element instead of 13.
 
+A max pool between a holder and wrapped layers stays on codes with ``pools=True`` (both rewrites): the holder's float32 output
+is ``float(code - zp) * scale`` with ``scale > 0``, monotone in the code and never NaN, so the pool of that output is the
+dequantized pool of the codes bit for bit.  ``QuantizedMaxPool2d`` (``mctq_codes_maxpool_nhwc``) pools the codes -- a padded tap
+is ignored, it stands for -inf and not for the zero point -- and the convolutions behind it become consumers of the pooled codes.
+
 The four modules derive from ``IntegerConsumer``, which owns what they share: the checks of the quantizers and of the float32
 weight and bias, the cache of the weight's codes, the step from ``forward``'s input to activation codes, ``from_wrapper`` and
 the ``emit_codes_for`` / ``emit_clamp`` output form.  ``QuantizedLinear`` is the product over ``[O, K]`` rows; ``QuantizedConv1x1``
@@ -674,6 +679,75 @@ class QuantizedDepthwiseConv2d(IntegerConsumer):
         return y.permute(0, 3, 1, 2)
 
 
+def _ints_or_pair(v) -> bool:
+    one = lambda e: isinstance(e, int) and not isinstance(e, bool)                     # noqa: E731
+    return one(v) or (isinstance(v, (tuple, list)) and len(v) == 2 and all(one(e) for e in v))
+
+
+class QuantizedMaxPool2d(nn.Module):
+    """``activation holder -> nn.MaxPool2d`` on integer codes, for the integer consumers behind the pool.  The holder's float32
+    output is ``float(code - zp) * scale`` with ``scale > 0``: monotone non-decreasing in the code and never NaN, so the pool of
+    the holder's output is the dequantized pool of the codes bit for bit, and the layers behind see a tensor whose codes are the
+    pooled codes -- ``ops.codes_maxpool`` (``mctq_codes_maxpool_nhwc``), 1 byte read and a quarter of one written per element
+    of a stride-2 pool, where ATen's pool reads 4 and writes 1 and the layers behind quantize that again.
+
+    ``forward`` takes the codes of ``activation_quantizer`` (int8 / uint8 of its code type, NCHW-shaped and NHWC-stored, as the
+    consumers and joins emit them) or a float32 [N, C, H, W] tensor, which it quantizes with the holder's parameters
+    (``ops.fq_codes_nhwc``); it returns the pooled codes, NCHW-shaped and NHWC-stored, which an ``IntegerConsumer`` of the same
+    quantizer takes as they are.  It has no weights and is no ``IntegerConsumer``; ``activation_code_params`` is theirs, so the
+    modules in front and behind agree on the form.  GPU tensors need ``C % 16 == 0``."""
+
+    def __init__(self, pool, activation_quantizer):
+        super().__init__()
+        if not self.eligible(pool):
+            raise TypeError("QuantizedMaxPool2d takes torch.nn.MaxPool2d layers without return_indices, their kernel_size, stride, "
+                            "padding and dilation ints or pairs, padding at most half the kernel size")
+        if activation_quantizer.num_bits > 8:
+            raise NotImplementedError("codes wider than 8 bits")
+        self.activation_quantizer = activation_quantizer
+        self._a_scale, self._a_zp, self._a_qmin, self._a_qmax = _activation_code_params(activation_quantizer)
+        ops._code_dtype(self._a_qmin, self._a_qmax)            # (raises for a domain that is no 8-bit code)
+        self.kernel_size = ops._pair(pool.kernel_size, "kernel_size", "QuantizedMaxPool2d")
+        self.stride = self.kernel_size if pool.stride is None else ops._pair(pool.stride, "stride", "QuantizedMaxPool2d")
+        self.padding = ops._pair(pool.padding, "padding", "QuantizedMaxPool2d")
+        self.dilation = ops._pair(pool.dilation, "dilation", "QuantizedMaxPool2d")
+        self.ceil_mode = bool(pool.ceil_mode)
+
+    @staticmethod
+    def eligible(pool) -> bool:
+        if type(pool) is not nn.MaxPool2d or pool.return_indices or not isinstance(pool.ceil_mode, bool):
+            return False
+        stride = pool.kernel_size if pool.stride is None else pool.stride
+        if not all(_ints_or_pair(v) for v in (pool.kernel_size, stride, pool.padding, pool.dilation)):
+            return False
+        k, s, p, d = (ops._pair(v, "", "QuantizedMaxPool2d") for v in (pool.kernel_size, stride, pool.padding, pool.dilation))
+        return min(*k, *s, *d) >= 1 and min(p) >= 0 and p[0] <= k[0] // 2 and p[1] <= k[1] // 2
+
+    def activation_code_params(self):
+        """(scale, zero_point, qmin, qmax) of the codes this pool reads and returns: what ``emit_codes_for`` of the layer in
+        front takes."""
+        return self._a_scale, self._a_zp, self._a_qmin, self._a_qmax
+
+    def extra_repr(self) -> str:
+        return (f"kernel_size={self.kernel_size}, stride={self.stride}, padding={self.padding}, dilation={self.dilation}, "
+                f"ceil_mode={self.ceil_mode}")
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if x.dim() != 4:
+            raise RuntimeError(f"expected [N, C, H, W], got {tuple(x.shape)}")
+        if x.dtype in (torch.uint8, torch.int8):
+            if x.dtype != ops._code_dtype(self._a_qmin, self._a_qmax)[0]:
+                raise TypeError(f"activation codes of type {x.dtype} do not match this pool's quantizer")
+            codes = x.permute(0, 2, 3, 1)
+            codes = codes if codes.is_contiguous() else codes.contiguous()
+        elif x.dtype == torch.float32:
+            codes = ops.fq_codes_nhwc(x, self._a_qmin, self._a_qmax, self._a_scale, self._a_zp)
+        else:
+            raise TypeError(f"QuantizedMaxPool2d takes float32 tensors or activation codes, got {x.dtype}")
+        y = ops.codes_maxpool(codes, self.kernel_size, self.stride, self.padding, self.dilation, self.ceil_mode)
+        return y.permute(0, 3, 1, 2)
+
+
 # In the order they are tried: (class, the switch of the rewrites that enables it or None, what fusing asks of the layer beyond
 # ``eligible``).  The rows kernels need K % 16 == 0 and K <= _MAX_K, which QuantizedConv2d's ``eligible`` holds itself.
 _CONSUMERS = (
@@ -704,6 +778,10 @@ def _consumer_for(wrapper, activation_quantizer, uniform_weights=False, convolut
     return None
 
 
+# what reads the activation codes of the module in front as they are
+_CODE_READERS = (IntegerConsumer, QuantizedMaxPool2d)
+
+
 class _FusedAway(nn.Identity):
     """Placeholder left where an activation holder was folded into the QuantizedLinear after it."""
 
@@ -724,6 +802,66 @@ def _install_consumer(gm, mods, node, fused):
 def _plain_holder(m) -> bool:
     """An activation holder that really quantizes (the FLN / preserving variants can be switched to pass-through)."""
     return isinstance(m, PytorchActivationQuantizationHolder) and not getattr(m, "quantization_bypass", False)
+
+
+def _pool_of(node, mods):
+    """The ``nn.MaxPool2d`` that ``node`` applies to its one tensor operand -- a call of such a module, or ``F.max_pool2d`` with
+    constant arguments, for which one is built -- if QuantizedMaxPool2d can take it, else None."""
+    from torch.fx import Node
+    if not node.args or not isinstance(node.args[0], Node):
+        return None
+    pool = None
+    if node.op == "call_module" and len(node.args) == 1 and not node.kwargs:
+        pool = mods.get(node.target)
+    elif node.op == "call_function" and node.target is torch.nn.functional.max_pool2d:
+        names = ("kernel_size", "stride", "padding", "dilation", "ceil_mode", "return_indices")
+        if len(node.args) > 7 or set(node.kwargs) - set(names[len(node.args) - 1:]):
+            return None
+        given = dict(zip(names, node.args[1:]), **node.kwargs)
+        if "kernel_size" not in given or any(isinstance(v, Node) for v in given.values()):
+            return None
+        if not all(isinstance(given.get(k, False), bool) for k in ("ceil_mode", "return_indices")):
+            return None
+        try:
+            pool = nn.MaxPool2d(**given)
+        except (TypeError, ValueError):
+            return None
+    return pool if QuantizedMaxPool2d.eligible(pool) else None
+
+
+def _pool_plan(node, mods, quantizer, consumer_for):
+    """``node`` a user of a plain holder with ``quantizer``: (QuantizedMaxPool2d, [(user, its consumer)]) if it is a max pool of
+    the holder's output that can run on codes -- every user a wrapped convolution ``consumer_for`` can take, fed by the pool
+    alone -- else None.  (A pool that also feeds a float32 user, an identity add for instance, is left alone.)"""
+    pool = _pool_of(node, mods)
+    if pool is None or not node.users:
+        return None
+    taken = []
+    for user in node.users:
+        wrapper = _module_of(user, mods)
+        if not isinstance(wrapper, PytorchQuantizationWrapper) or user.kwargs or user.args != (node,):
+            return None
+        fused = consumer_for(wrapper, quantizer)
+        if fused is None or type(fused) is QuantizedLinear:      # (a Linear behind a pool runs along the width, not the channels)
+            return None
+        taken.append((user, fused))
+    try:
+        return QuantizedMaxPool2d(pool, quantizer), taken
+    except (TypeError, ValueError, NotImplementedError):
+        return None
+
+
+def _install_pool(gm, mods, node, plan, source) -> int:
+    """Makes ``node``, the pool's call, a call of ``plan``'s QuantizedMaxPool2d on ``source`` (codes, or the float32 tensor the
+    holder read) and its users the consumers of the plan; returns their number."""
+    qpool, taken = plan
+    name = (node.target.replace(".", "_") if node.op == "call_module" else node.name) + "_qpool"
+    gm.add_submodule(name, qpool)
+    mods[name] = qpool
+    node.op, node.target, node.args, node.kwargs = "call_module", name, (source,), {}
+    for user, fused in taken:
+        _install_consumer(gm, mods, user, fused)
+    return len(taken)
 
 
 class QuantizedJoin(nn.Module):
@@ -817,10 +955,12 @@ def _add_operands(node):
     return tuple(node.args) if ok else None
 
 
-def _join_shared_holders(gm, mods, consumer_for) -> int:
+def _join_shared_holders(gm, mods, consumer_for, pools: bool = False) -> int:
     """``fuse_linear_consumers_fx(shared_holders=True)``: every plain holder with wrapped layers among its users that
     ``consumer_for(wrapper, quantizer)`` can take becomes a QuantizedJoin, unless it is a lone holder -> layer pair with
-    nothing in front to absorb (the pair rewrite's).  Returns the number of wrapped layers replaced."""
+    nothing in front to absorb (the pair rewrite's).  With ``pools`` a max pool among the users that can run on codes
+    (``_pool_plan``) reads the join's codes as well, as a QuantizedMaxPool2d in front of its own consumers; a lone holder ->
+    pool pair with nothing to absorb is left to ``_pool_lone_holders``.  Returns the number of wrapped layers replaced."""
     import operator
     from torch.fx import Node
     replaced = 0
@@ -837,9 +977,14 @@ def _join_shared_holders(gm, mods, consumer_for) -> int:
                 fused = consumer_for(wrapper, holder.activation_holder_quantizer)
                 if fused is not None:
                     taken.append((user, fused))
-        if not taken:
+        pooled = []                                          # P: (pool node, its plan)
+        if pools:
+            plans = ((user, _pool_plan(user, mods, holder.activation_holder_quantizer, consumer_for)) for user in node.users)
+            pooled = [(user, plan) for user, plan in plans if plan is not None]
+        if not taken and not pooled:
             continue
-        rest = [u for u in node.users if all(u is not t for t, _ in taken)]           # R: they keep the float32 tensor
+        on_codes = [t for t, _ in taken] + [t for t, _ in pooled]
+        rest = [u for u in node.users if all(u is not t for t in on_codes)]           # R: they keep the float32 tensor
         src, relu_node, add_node = node.args[0], None, None
         if len(src.users) == 1 and _relu_input(src, mods) is not None:
             relu_node, src = src, _relu_input(src, mods)
@@ -862,11 +1007,34 @@ def _join_shared_holders(gm, mods, consumer_for) -> int:
             _install_consumer(gm, mods, user, fused)
             user.args = (as_codes,)
             replaced += 1
+        for user, plan in pooled:
+            replaced += _install_pool(gm, mods, user, plan, as_codes)
         if rest:
             node.replace_all_uses_with(as_float)
         for gone in (node, relu_node, add_node):
             if gone is not None:
                 gm.graph.erase_node(gone)
+    return replaced
+
+
+def _pool_lone_holders(gm, mods, consumer_for) -> int:
+    """``fuse_linear_consumers_fx(pools=True)``, the pair: a plain holder whose only user is a max pool that can run on codes
+    (``_pool_plan``) leaves the graph, the QuantizedMaxPool2d that replaces the pool quantizes the holder's input itself.
+    Returns the number of wrapped layers replaced."""
+    from torch.fx import Node
+    replaced = 0
+    for node in list(gm.graph.nodes):
+        if node.op != "call_module" or node.kwargs or len(node.args) != 1 or not isinstance(node.args[0], Node) or len(node.users) != 1:
+            continue
+        holder = mods.get(node.target)
+        if not _plain_holder(holder):
+            continue
+        user = next(iter(node.users))
+        plan = _pool_plan(user, mods, holder.activation_holder_quantizer, consumer_for)
+        if plan is None:
+            continue
+        replaced += _install_pool(gm, mods, user, plan, node.args[0])
+        gm.graph.erase_node(node)
     return replaced
 
 
@@ -948,8 +1116,9 @@ def _identities_as_codes(gm, mods) -> int:
 def _fold_clamps_into_producers(gm, mods) -> int:
     """``fuse_linear_consumers_fx(stay_on_codes=True)``, the activations between consumers: where a consumer's only user leads
     -- through at most one clamp activation that feeds nothing else (``_clamp_range``; the ReLU a join absorbed counts) -- to a
-    holder all of whose users are integer consumers, the consumer emits that holder's codes itself, the activation folded into
-    their clamp (``folded_clamp``), and the consumers behind take them directly.  The holder is either already inside the one
+    holder all of whose users are integer consumers (or, with ``pools=True``, QuantizedMaxPool2d modules in front of such), the
+    consumer emits that holder's codes itself, the activation folded into their clamp (``folded_clamp``), and the modules behind
+    take them directly.  The holder is either already inside the one
     consumer behind it (the pair rewrite) or a residual-free QuantizedJoin that writes no float32 output.  Returns the number of
     producers that now emit codes."""
     import operator
@@ -965,7 +1134,7 @@ def _fold_clamps_into_producers(gm, mods) -> int:
         if nxt.op != "call_module" or nxt.kwargs or nxt.args != (act or node,):
             continue
         behind, gone = mods.get(nxt.target), [nxt]
-        if isinstance(behind, IntegerConsumer):
+        if isinstance(behind, _CODE_READERS):
             form, readers, gone = behind.activation_code_params(), [nxt], []
         elif isinstance(behind, QuantizedJoin) and not behind.has_residual and not behind.want_float:
             if behind.relu:
@@ -976,7 +1145,7 @@ def _fold_clamps_into_producers(gm, mods) -> int:
             if len(picks) != 1 or picks[0].target is not operator.getitem or picks[0].args != (nxt, 1):
                 continue
             form, readers = (behind._a_scale, behind._a_zp, behind._a_qmin, behind._a_qmax), list(picks[0].users)
-            if not readers or not all(isinstance(_module_of(r, mods), IntegerConsumer) and r.args == (picks[0],) and not r.kwargs
+            if not readers or not all(isinstance(_module_of(r, mods), _CODE_READERS) and r.args == (picks[0],) and not r.kwargs
                                       for r in readers):
                 continue
             gone = [picks[0], nxt]
@@ -1000,7 +1169,7 @@ def _fold_clamps_into_producers(gm, mods) -> int:
 
 
 def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights: bool = False,
-                          convolutions: bool = False, depthwise: bool = False) -> int:
+                          convolutions: bool = False, depthwise: bool = False, pools: bool = False) -> int:
     """In every ``nn.Sequential`` of ``model``: an activation holder directly followed by a wrapped ``nn.Linear`` with
     a symmetric, power-of-two or LUT weights quantizer (int8 codebook values, at most 256 entries) becomes (Identity,
     QuantizedLinear); a wrapped pointwise ``nn.Conv2d`` likewise becomes a QuantizedConv1x1.  Returns the number of pairs
@@ -1024,9 +1193,31 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
 
     ``chain=True``: where one QuantizedLinear feeds the next directly, the float32 tensor between them is never
     materialised -- the first emits the second's activation codes from its epilogue (same codes, bit for bit, as
-    quantizing the float32 output).  Modules or hooks that look at that intermediate tensor then see uint8/int8 codes."""
+    quantizing the float32 output).  Modules or hooks that look at that intermediate tensor then see uint8/int8 codes.
+
+    ``pools=True`` also takes (activation holder, ``nn.MaxPool2d``, wrapped convolution the consumer can take under the other
+    switches): it becomes (Identity, QuantizedMaxPool2d, consumer), the pool running on the holder's codes
+    (``mctq_codes_maxpool_nhwc``; no ``return_indices``, padding at most half the kernel size) and the consumer taking the pooled
+    codes; with ``chain=True`` a consumer in front of the triple emits the pool's codes.  Counted as one pair.  The codes are
+    monotone in the value, so the pooled codes are bit for bit the codes of the float32 pool of the holder's output, and the model
+    rewritten with ``pools=True`` returns, bit for bit, what the same rewrite without it returns wherever the float32 products of
+    the layers behind the pools are exact; otherwise it differs by the accumulation rounding of those products, like every pair
+    that becomes a consumer."""
     replaced = 0
     for seq in [m for m in model.modules() if isinstance(m, nn.Sequential)]:
+        for i in range(len(seq) - 2 if pools else 0):
+            holder, pool, wrapper = seq[i], seq[i + 1], seq[i + 2]
+            if not _plain_holder(holder) or not QuantizedMaxPool2d.eligible(pool) or not isinstance(wrapper, PytorchQuantizationWrapper):
+                continue
+            fused = _consumer_for(wrapper, holder.activation_holder_quantizer, uniform_weights, convolutions, depthwise)
+            if fused is None or type(fused) is QuantizedLinear:
+                continue
+            try:
+                qpool = QuantizedMaxPool2d(pool, holder.activation_holder_quantizer)
+            except (TypeError, ValueError, NotImplementedError):
+                continue
+            seq[i], seq[i + 1], seq[i + 2] = _FusedAway(), qpool, fused
+            replaced += 1
         for i in range(len(seq) - 1):
             holder, wrapper = seq[i], seq[i + 1]
             if not _plain_holder(holder) or not isinstance(wrapper, PytorchQuantizationWrapper):
@@ -1040,14 +1231,14 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
         if chain:
             for i in range(len(seq) - 2):
                 first, gap, second = seq[i], seq[i + 1], seq[i + 2]
-                if isinstance(first, IntegerConsumer) and isinstance(gap, _FusedAway) and isinstance(second, IntegerConsumer):
+                if isinstance(first, IntegerConsumer) and isinstance(gap, _FusedAway) and isinstance(second, _CODE_READERS):
                     first.emit_codes_for = second.activation_code_params()
     return replaced
 
 
 def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weights: bool = False,
                              convolutions: bool = False, depthwise: bool = False, shared_holders: bool = False,
-                             stay_on_codes: bool = False):
+                             stay_on_codes: bool = False, pools: bool = False):
     """The same rewrite on an arbitrary module graph (MCT-exported models are not ``nn.Sequential``): traces ``model``
     with torch.fx keeping wrappers and holders as leaves, and wherever an activation holder's ONLY consumer is a
     wrapped ``nn.Linear`` the integer consumer can take (symmetric, power-of-two or LUT weights, and with
@@ -1073,22 +1264,42 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
     join leave the graph).  And a residual join whose identity operand is another join's float32 output reads that join's codes
     instead (``mctq_fq_join_rc_f32``), so that the float32 tensor between two blocks is neither written nor read.  The result
     is bit for bit that of ``shared_holders=True`` alone, except that a NaN in a consumer's output (only from a NaN scale or
-    bias) codes to the folded clamp's lower end, not the domain's."""
+    bias) codes to the folded clamp's lower end, not the domain's.
+
+    ``pools=True`` (needs no other switch) keeps a max pool between a holder and wrapped layers on codes.  The candidate is a
+    plain holder one of whose users is a max pool -- an ``nn.MaxPool2d`` module or ``F.max_pool2d`` with constant arguments, no
+    ``return_indices``, padding at most half the kernel size -- every user of which is a wrapped convolution the consumer can
+    take under the other switches, fed by the pool alone.  The pool becomes a QuantizedMaxPool2d on the holder's codes
+    (``mctq_codes_maxpool_nhwc``) and those layers consumers of its output.  A holder whose only user is the pool, with nothing
+    in front to absorb, leaves the graph: the pool module quantizes.  With ``shared_holders=True`` a ReLU and / or an add in
+    front is absorbed into a QuantizedJoin as above, which writes no float32 output when the pool was the holder's only user;
+    the holder's other users keep what they get without ``pools``.  Without ``shared_holders`` a holder with other users
+    besides the pool is left alone, and so is every pool with another kind of user (an identity add: a residual join does
+    not read pooled codes).  With ``stay_on_codes=True`` a QuantizedMaxPool2d counts as a reader of the holder's codes, so that
+    consumer -> ReLU / ReLU6 / Hardtanh -> holder -> pool -> consumers runs codes to codes (the VGG pattern).  The codes are
+    monotone in the value and a padded tap is ignored, so the pooled codes are bit for bit the codes of the float32 pool of the
+    holder's output, and the model rewritten with ``pools=True`` returns, bit for bit, what the same rewrite without it returns
+    wherever the float32 products of the layers behind the pools are exact; otherwise it differs by the accumulation rounding of
+    those products, like every wrapped layer that becomes a consumer."""
     import torch.fx as fx
     if stay_on_codes and not shared_holders:
         raise ValueError("stay_on_codes=True needs shared_holders=True")
 
     class _Tracer(fx.Tracer):
         def is_leaf_module(self, m, qualname):
-            return isinstance(m, (PytorchQuantizationWrapper, PytorchActivationQuantizationHolder, IntegerConsumer, QuantizedJoin)) \
+            return isinstance(m, (PytorchQuantizationWrapper, PytorchActivationQuantizationHolder, IntegerConsumer, QuantizedJoin,
+                                  QuantizedMaxPool2d)) \
                 or super().is_leaf_module(m, qualname)
 
     graph = _Tracer().trace(model)
     gm = fx.GraphModule(model, graph)
     mods = dict(gm.named_modules())
     replaced = 0
+    consumer_for = lambda wrapper, q: _consumer_for(wrapper, q, uniform_weights, convolutions, depthwise)      # noqa: E731
     if shared_holders:
-        replaced = _join_shared_holders(gm, mods, lambda wrapper, q: _consumer_for(wrapper, q, uniform_weights, convolutions, depthwise))
+        replaced = _join_shared_holders(gm, mods, consumer_for, pools)
+    if pools:
+        replaced += _pool_lone_holders(gm, mods, consumer_for)
     for node in list(gm.graph.nodes):
         if node.op != "call_module" or node.kwargs or len(node.args) != 1:
             continue
@@ -1113,7 +1324,7 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
             if isinstance(_module_of(node, mods), IntegerConsumer) and len(node.users) == 1:
                 user = next(iter(node.users))
                 nxt = _module_of(user, mods)
-                if isinstance(nxt, IntegerConsumer) and user.args == (node,):
+                if isinstance(nxt, _CODE_READERS) and user.args == (node,):
                     mods[node.target].emit_codes_for = nxt.activation_code_params()
     if stay_on_codes:
         _identities_as_codes(gm, mods)

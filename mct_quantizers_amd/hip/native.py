@@ -132,6 +132,8 @@ SIGNATURES = {
                                                   ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
     "mctq_codes_im2col_nhwc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                               ctypes.c_int64] + [ctypes.c_int32] * 9 + [ctypes.c_void_p]),
+    "mctq_codes_maxpool_nhwc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32] + [ctypes.c_int64] * 4    # codes, pooled, type; B, H, W, C
+                                + [ctypes.c_int32] * 9 + [ctypes.c_int64] * 2 + [ctypes.c_void_p]),                # geometry, ceil_mode; Ho, Wo; stream
     "mctq_qconv_dw_i8": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,   # a_codes, type, zero point, scale
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,  # w_codes, w_scales, w_zero_points, bias
                                         ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_int32,

@@ -652,6 +652,54 @@ def codes_im2col(codes_nhwc, kernel_size, stride=1, padding=0, dilation=1, pad_c
     return taps.reshape(b * ho * wo, kh * kw * c)
 
 
+def _pool_out_size(n: int, k: int, s: int, p: int, d: int, ceil_mode: bool) -> int:
+    """Outputs along one axis of ``torch.nn.MaxPool2d``: as ``_conv_out_size``, the division rounded up with ``ceil_mode``, less
+    the last window where it would start beyond the image plus its left padding."""
+    span = n + 2 * p - d * (k - 1) - 1
+    out = (-(-span // s) if ceil_mode else span // s) + 1
+    if ceil_mode and (out - 1) * s >= n + p:
+        out -= 1
+    return out
+
+
+def codes_maxpool(codes_nhwc, kernel_size, stride=None, padding=0, dilation=1, ceil_mode: bool = False):
+    """``torch.nn.MaxPool2d`` on activation codes: int8 / uint8 codes [B, H, W, C] (what ``fq_codes_nhwc`` returns) -> contiguous
+    [B, Ho, Wo, C] of the same type; ``stride=None`` means ``kernel_size``, padded taps are ignored (they stand for -inf, not for
+    the zero point), ``padding`` is at most half the kernel size.  The codes of a quantizer are monotone in the value, so
+    ``dequantize_codes(codes_maxpool(c), s, z) == F.max_pool2d(dequantize_codes(c, s, z))`` bit for bit (NCHW views of both).
+    GPU tensors run mctq_codes_maxpool_nhwc (C % 16 == 0), which is given the output extent allocated here and refuses one
+    that is not its own; CPU tensors run ``F.max_pool2d`` on the codes themselves."""
+    if not isinstance(codes_nhwc, torch.Tensor) or codes_nhwc.dim() != 4:
+        raise ValueError("codes_maxpool takes [N, H, W, C] tensors")
+    if codes_nhwc.dtype not in (torch.int8, torch.uint8):
+        raise NotImplementedError(f"codes_maxpool: int8 / uint8 codes only, got {codes_nhwc.dtype}")
+    b, h, w, c = codes_nhwc.shape
+    (kh, kw), (sh, sw) = _pair(kernel_size, "kernel_size", "codes_maxpool"), _pair(kernel_size if stride is None else stride, "stride", "codes_maxpool")
+    (ph, pw), (dh, dw) = _pair(padding, "padding", "codes_maxpool"), _pair(dilation, "dilation", "codes_maxpool")
+    if min(kh, kw, sh, sw, dh, dw) < 1 or min(ph, pw) < 0:
+        raise ValueError("codes_maxpool: kernel_size, stride and dilation must be at least 1 and padding at least 0")
+    if ph > kh // 2 or pw > kw // 2:
+        raise ValueError(f"codes_maxpool: padding {ph}x{pw} is larger than half the {kh}x{kw} kernel")
+    ceil_mode = bool(ceil_mode)
+    ho, wo = _pool_out_size(h, kh, sh, ph, dh, ceil_mode), _pool_out_size(w, kw, sw, pw, dw, ceil_mode)
+    if ho <= 0 or wo <= 0:
+        raise ValueError(f"codes_maxpool: a {kh}x{kw} kernel (dilation {dh}x{dw}) does not fit the padded {h}x{w} image")
+    x = codes_nhwc if codes_nhwc.is_contiguous() else codes_nhwc.contiguous()
+    if x.is_cuda:
+        if c % 16:
+            raise NotImplementedError(f"mctq_codes_maxpool_nhwc needs C % 16 == 0, got C={c}")
+        y = torch.empty((b, ho, wo, c), dtype=x.dtype, device=x.device)
+        _gpu_call("mctq_codes_maxpool_nhwc", x, x.data_ptr(), y.data_ptr(), _code_of(x), b, h, w, c, kh, kw, sh, sw, ph, pw, dh, dw,
+                  int(ceil_mode), ho, wo)
+        return y
+    _cpu_route_allowed()
+    if 0 in (b, c):
+        return x.new_empty((b, ho, wo, c))
+    # (NCHW-contiguous: ATen's channels-last kernel keeps its indices in the tensor's own integer type and refuses larger images)
+    y = torch.nn.functional.max_pool2d(x.permute(0, 3, 1, 2).contiguous(), (kh, kw), (sh, sw), (ph, pw), (dh, dw), ceil_mode)
+    return y.permute(0, 2, 3, 1).contiguous()
+
+
 def make_lut_table(lut_values, mult: float, cmin: float, cmax: float, device):
     """Device copy of the codebook's decision table (see include/mctq_hip.h), or None.
 
