@@ -237,7 +237,9 @@ int mctq_lutt_batch_run(const void* host_table, const void* device_table, void* 
  * MCTQ_CODE_I4 (domain within [-8, 7], two's-complement nibbles) / MCTQ_CODE_U4 (within [0, 15]): two codes per
  * byte in storage order, element 2j in the low nibble and 2j + 1 in the high nibble; `codes` then holds n / 2
  * bytes (4-byte aligned).  Supported layouts: per tensor with n % 8 == 0; per channel with inner % 8 == 0, or
- * inner == 1 with channels % 8 == 0; anything else returns MCTQ_E_ARG.
+ * inner == 1 with channels % 8 == 0; anything else returns MCTQ_E_ARG.  mctq_last_launch names these launches
+ * "codes4_flat_kernel", "codes4_rows_kernel" (U = the 4 or 8 lane vectors per lane chosen for the row length) and
+ * "codes4_lastaxis_kernel", op "AffineCodesOp", out1B; each counts once in mctq_launch_count.
  */
 int mctq_fq_codes_per_tensor(const void* x, void* codes, int64_t n, int32_t dtype, int32_t code_dtype,
                              float scale, int32_t zero_point, int32_t quant_min, int32_t quant_max,

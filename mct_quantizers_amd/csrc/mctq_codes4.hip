@@ -171,6 +171,7 @@ int codes4_per_tensor(const void* x, void* codes, int64_t n, int dtype, float sc
     if (blocks > 0x7fffffffLL) return fail_arg("tensor too large for one launch");
     hipLaunchKernelGGL((codes4_flat_kernel<TI>), dim3((unsigned)blocks), dim3(kThreads), 0, st, static_cast<const TI*>(x),
                        static_cast<typename V::Out*>(codes), nv, p, (float)qmin, (float)qmax);
+    note<AffineCodesOp, TI, uint8_t>("codes4_flat_kernel", kC4U, 1);
     return check_launch("codes4 flat launch");
   });
 }
@@ -199,6 +200,7 @@ int codes4_per_channel(const void* x, void* codes, int64_t outer, int64_t channe
         hipLaunchKernelGGL((codes4_rows_kernel<TI, 8>), dim3((unsigned)(rows * tiles)), dim3(kThreads), 0, st,
                            static_cast<const TI*>(x), static_cast<typename V::Out*>(codes), (uint32_t)tiles, (uint32_t)innerv,
                            (uint32_t)channels, scales, zps, (float)qmin, (float)qmax);
+      note<AffineCodesOp, TI, uint8_t>("codes4_rows_kernel", u_sel, 1);
       return check_launch("codes4 rows launch");
     });
   }
@@ -218,6 +220,7 @@ int codes4_per_channel(const void* x, void* codes, int64_t outer, int64_t channe
       hipLaunchKernelGGL((codes4_lastaxis_kernel<TI>), dim3((unsigned)blocks), dim3(kThreads), 0, st,
                          static_cast<const TI*>(x), static_cast<typename V::Out*>(codes), (uint64_t)outer, (uint32_t)vc,
                          (uint32_t)k, (uint32_t)bps, scales, zps, (float)qmin, (float)qmax);
+      note<AffineCodesOp, TI, uint8_t>("codes4_lastaxis_kernel", kC4U, 1);
       return check_launch("codes4 lastaxis launch");
     });
   }
