@@ -486,7 +486,14 @@ int mctq_grid_per_channel_f32(const float* x, float* y,
  * Per-tensor codes with a layout change: x [batch][channels][pixels] (NCHW, pixels = H * W) -> codes
  * [batch][pixels][channels] (NHWC), int8 / uint8, same arithmetic as mctq_fq_codes_per_tensor.  What a pointwise
  * (1x1) convolution consumer feeds mctq_qlinear_i8 with (rows = pixels, K = channels) when the activation arrives
- * in PyTorch's default layout.
+ * in PyTorch's default layout.  NaN -> quant_min, +-inf saturate, as there.
+ * One block moves a 128 (channels) x 32 (pixels) tile.  Four pixels per lane arrive by one 8- / 16-byte load when
+ * pixels % 4 == 0 and x is aligned to four elements, element by element otherwise; 16 channels per lane leave by one
+ * 16-byte store when channels % 16 == 0 and codes is 16-byte aligned, byte by byte otherwise: any x aligned to its
+ * element and any codes pointer are accepted.  MCTQ_E_ARG for negative extents, quant_min > quant_max, a code type other
+ * than MCTQ_CODE_I8 / MCTQ_CODE_U8 or a clamp domain outside it, NULL pointers, more than 2^31 - 1 channels or tiles and an
+ * unknown dtype; an empty extent returns 0 without a launch.  mctq_last_launch names the launch "codes_nchw_to_nhwc" with
+ * the form it took ("vector loads" / "scalar loads" + "16-byte stores" / "byte stores") and the input's byte width.
  */
 int mctq_fq_codes_nchw_to_nhwc(const void* x, void* codes, int64_t batch, int64_t channels, int64_t pixels, int32_t dtype,
                                int32_t code_dtype, float scale, int32_t zero_point, int32_t quant_min, int32_t quant_max,

@@ -5,17 +5,19 @@
 // algorithmic bytes per element instead of a codes pass plus a byte transposition.  Same arithmetic as the codes
 // kernels (AffineOp::make; q = clamp(rint(x * (1/s)) + z)).  A block moves a 128 (channels) x 32 (pixels) tile:
 // 128-byte row pieces in (four consecutive pixels per lane), quantized bytes transposed through LDS, 128-byte row
-// pieces out (16 consecutive channels per lane).
+// pieces out (16 consecutive channels per lane).  Both vector forms are chosen on the host (shape AND pointer alignment) and
+// arrive in `forms`; without them the same tile moves element by element / byte by byte.
 #include "mctq_kernels.hpp"
 
 namespace mctq {
 
 constexpr int kTC = 128, kTP = 32;            // tile: channels x pixels
+constexpr int kVecLoads = 1, kVecStores = 2;  // `forms`: four pixels per 8- / 16-byte load; 16 channels per 16-byte store
 
 template <class TI>
 __global__ __launch_bounds__(kThreads) void codes_nchw_to_nhwc_kernel(const TI* __restrict__ x, uint8_t* __restrict__ y,
                                                                       int C, int64_t P, int c_tiles, int64_t p_tiles,
-                                                                      AffineOp::Param prm, float lo, float hi, int vec_ok) {
+                                                                      AffineOp::Param prm, float lo, float hi, int forms) {
   __shared__ uint8_t tile[kTP][kTC + 16];                 // [pixel][channel]; padded rows: 16-byte chunks stay aligned
   int64_t id = blockIdx.x;
   const int64_t pt = id % p_tiles; id /= p_tiles;
@@ -33,7 +35,7 @@ __global__ __launch_bounds__(kThreads) void codes_nchw_to_nhwc_kernel(const TI* 
     float f[4] = {0.f, 0.f, 0.f, 0.f};
     if (c < C) {
       const TI* src = xb + (int64_t)c * P + p0 + pr;
-      if (vec_ok && p0 + pr + 4 <= P) {
+      if ((forms & kVecLoads) && p0 + pr + 4 <= P) {
         typedef typename VecT<TI, 4>::type V4;
         const V4 v = __builtin_nontemporal_load(reinterpret_cast<const V4*>(src));
 #pragma unroll
@@ -56,7 +58,7 @@ __global__ __launch_bounds__(kThreads) void codes_nchw_to_nhwc_kernel(const TI* 
   const int op = threadIdx.x >> 3, oc = (threadIdx.x & 7) * 16;
   if (p0 + op < P && c0 + oc < C) {
     uint8_t* dst = y + ((b * P + p0 + op) * C) + c0 + oc;
-    if (c0 + oc + 16 <= C && (C & 15) == 0) {
+    if (forms & kVecStores) {                               // C % 16 == 0: the 16 channels exist; y is 16-byte aligned
       typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
       __builtin_nontemporal_store(*reinterpret_cast<const u32x4*>(&tile[op][oc]), reinterpret_cast<u32x4*>(dst));
     } else {
@@ -89,10 +91,18 @@ int mctq_fq_codes_nchw_to_nhwc(const void* x, void* codes, int64_t batch, int64_
   const hipStream_t st = (hipStream_t)stream;
   const auto launch = [&](auto ti) {
     typedef decltype(ti) TI;
-    const int vec_ok = (pixels % 4 == 0) && ((uintptr_t)x % (4 * sizeof(TI)) == 0);
+    // the vector forms need every access aligned: rows of whole vectors from an aligned base (as vec_aligned for the shared launchers)
+    const bool vload = pixels % 4 == 0 && (uintptr_t)x % (4 * sizeof(TI)) == 0;
+    const bool vstore = channels % 16 == 0 && (uintptr_t)codes % 16 == 0;
+    const int forms = (vload ? kVecLoads : 0) | (vstore ? kVecStores : 0);
     hipLaunchKernelGGL((codes_nchw_to_nhwc_kernel<TI>), dim3((unsigned)blocks), dim3(kThreads), 0, st,
                        static_cast<const TI*>(x), static_cast<uint8_t*>(codes), (int)channels, pixels, (int)c_tiles, p_tiles, p,
-                       (float)quant_min, (float)quant_max, vec_ok);
+                       (float)quant_min, (float)quant_max, forms);
+    g_note.shape = "codes_nchw_to_nhwc";
+    g_note.op = vload ? (vstore ? "vector loads + 16-byte stores" : "vector loads + byte stores")
+                      : (vstore ? "scalar loads + 16-byte stores" : "scalar loads + byte stores");
+    g_note.unroll = 4; g_note.nt = 1; g_note.in_bytes = (int)sizeof(TI); g_note.out_bytes = 1; ++g_note.count;
+    if (g_launch_log) log_launch();
     return check_launch("codes nchw->nhwc launch");
   };
   switch (dtype) {
