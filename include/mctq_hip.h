@@ -70,6 +70,8 @@ extern "C" {
  * of another join (identity branches that stay on codes); no existing signature or result changed. */
 /* v10 (additive, the version number stays): + mctq_codes_maxpool_nhwc, torch.nn.MaxPool2d on NHWC activation codes (a max pool between
  * an activation holder and the integer consumers behind it stays on codes); no existing signature or result changed. */
+/* v10 (additive, the version number stays): + mctq_qlinear_i8_res, the integer product with the residual add and the ReLU of a residual
+ * join in its epilogue (the block's last convolution emits the next block's codes itself); no existing signature or result changed. */
 #define MCTQ_ABI_VERSION 10
 #define MCTQ_E_ARG (-10001)
 
@@ -735,6 +737,33 @@ int mctq_qlinear_w4a8_zp(const void* a_codes, int32_t a_code_dtype, int32_t a_ze
                          void* y, int32_t y_code_dtype, float y_scale, int32_t y_zero_point, int32_t y_quant_min,
                          int32_t y_quant_max, const int32_t* w_zero_points, const int32_t* a_rowsum, int64_t M, int64_t N,
                          int64_t K, void* stream);
+
+/*
+ * The integer consumer with the residual add and the ReLU of a residual join in its epilogue (the last 1x1 convolution of a
+ * residual block, which then emits the next block's codes itself instead of writing float32 for a mctq_fq_join_* launch):
+ *     v       = float( sum_k (a[m][k] - a_zero_point) * w[n][k] ) * (a_scale * w_scales[n])     as mctq_qlinear_i8
+ *     v       = v + bias[n]                     if bias
+ *     v       = v + r[m][n]                     one float32 add, not contracted
+ *     v       = v < 0 ? 0 : v                   if relu: a NaN stays a NaN and -0.0 stays -0.0, the join's expression
+ *     y[m][n] = v (y_code_dtype < 0: float32), or the code of v in the output form, as mctq_qlinear_i8_codes
+ * residual is [M][N] row-major like y, DEVICE.  r_code_dtype < 0: const float*, 4-byte aligned, r = residual[m * N + n] (r_scale
+ * and r_zero_point unused).  r_code_dtype MCTQ_CODE_I8 / MCTQ_CODE_U8: int8 / uint8 codes of another quantizer,
+ * r = fma(float(code - r_zero_point), r_scale, +0) -- the value mctq_fq_join_rc_f32 reads its residual as, i.e. bit for bit the
+ * float32 tensor written next to those codes; r_zero_point must be a code of that type and r_scale finite and positive.
+ * The register of v holds exactly the float32 value mctq_qlinear_i8 would have stored, and the add, the ReLU and the code are
+ * the join's own operations on it: the result is bit for bit that of mctq_qlinear_i8 followed by mctq_fq_join_f32 /
+ * mctq_fq_join_rc_f32 (codes) or by a float32 add and ReLU (float32 output).  MCTQ_E_ARG for residual == NULL, a misaligned
+ * float32 residual and a y whose bytes overlap the residual's; an empty problem (M == 0 or N == 0) returns 0 without a launch.
+ * Everything else as for mctq_qlinear_i8.  No weight zero points.  Launch shapes: the weight-streaming and LDS-tiled kernels
+ * under the same cost model and "ql_variant" key; the register-pinned whole-tile kernels are not built for a residual, so large
+ * whole-tile products run on the ~1.5 POP/s tiled kernels, and ql_variant 2544 / 2548 / 2560 returns MCTQ_E_ARG here.
+ * mctq_last_launch marks the form that ran: "...<u8 x i8 res(u8) relu,...>" (res(i8), res(f32); "relu" only when set).
+ */
+int mctq_qlinear_i8_res(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
+                        const int8_t* w_codes, const float* w_scales, const int32_t* w_rowsum, const float* bias,
+                        const void* residual, int32_t r_code_dtype, float r_scale, int32_t r_zero_point, int32_t relu,
+                        void* y, int32_t y_code_dtype, float y_scale, int32_t y_zero_point, int32_t y_quant_min,
+                        int32_t y_quant_max, int64_t M, int64_t N, int64_t K, void* stream);
 
 /*
  * Tuning hook (benchmarks only): selects the launch variant used by later calls on any thread.

@@ -50,6 +50,11 @@ consumer emits itself (``folded_clamp``: the code function is monotone, so clamp
 residual join reads its identity operand as the codes of the join in front (``mctq_fq_join_rc_f32``: ``(code - zp) * scale`` is
 that join's float32 output bit for bit), which then no longer writes float32 -- 6 bytes per element instead of 13.
 
+``fuse_linear_consumers_fx(..., stay_on_codes=True, fused_residuals=True)`` folds the residual joins that are left into the
+product in front of them: the block's last convolution reads the identity branch -- the codes of the join in front, or the
+downsample branch's float32 output -- in its own epilogue, adds it, applies the ReLU and emits the next block's codes
+(``mctq_qlinear_i8_res``): about 2 bytes per element where the product and the join moved 10, and one launch less per block.
+
 A max pool between a holder and wrapped layers stays on codes with ``pools=True`` (both rewrites): the holder's float32 output
 is ``float(code - zp) * scale`` with ``scale > 0``, monotone in the code and never NaN, so the pool of that output is the
 dequantized pool of the codes bit for bit.  ``QuantizedMaxPool2d`` (``mctq_codes_maxpool_nhwc``) pools the codes -- a padded tap
@@ -124,13 +129,49 @@ def _cpu_out_codes(y, out_codes):
     return ops.fq_codes(y, None, None, None, lo, hi, o_scale, o_zp).to(ops._code_dtype(o_qmin, o_qmax)[0])
 
 
-def _cpu_epilogue(acc, a_scale, w_scales, bias, out_codes):
+def _cpu_epilogue(acc, a_scale, w_scales, bias, out_codes, residual=None, residual_codes=None, relu=False):
     """The CPU routes' epilogue, the kernels' own: the int32 sums ``acc`` (output channels last) times ``a_scale`` (rounded to
-    float32 first) times the channel's weight scale, plus the bias; float32, or the codes of ``out_codes``."""
+    float32 first) times the channel's weight scale, plus the bias; with ``residual`` (float32, or codes with
+    ``residual_codes = (scale, zero_point)``, dequantized) one float32 add and, with ``relu``, ``v < 0 ? 0 : v`` -- a NaN stays a
+    NaN and -0.0 stays -0.0, as in the kernel; float32, or the codes of ``out_codes``."""
     y = acc.to(torch.float32) * (torch.tensor(a_scale, dtype=torch.float64).to(torch.float32) * w_scales)
     if bias is not None:
         y = y + bias
+    if residual is not None:
+        y = y + (residual if residual_codes is None else ops.dequantize_codes(residual, *residual_codes))
+        if relu:
+            y = torch.where(y < 0, torch.zeros((), dtype=torch.float32, device=y.device), y)
     return y if out_codes is None else _cpu_out_codes(y, out_codes)
+
+
+def _check_residual(a_codes, n, residual, residual_codes, relu, w_zero_points):
+    """The residual operand of ``qlinear_i8`` as ``(residual, (scale, zero_point) or None)``, or ``(None, None)``."""
+    if residual is None:
+        if residual_codes is not None:
+            raise ValueError("residual_codes describes the residual: it needs one")
+        if relu:
+            raise ValueError("relu=True needs a residual: the ReLU behind a product alone is a clamp of its codes (folded_clamp)")
+        return None, None
+    if w_zero_points is not None:
+        raise NotImplementedError("a residual together with weight zero points")
+    if not isinstance(residual, torch.Tensor) or residual.dtype not in (torch.float32, torch.int8, torch.uint8):
+        raise TypeError(f"the residual must be a float32 tensor or int8 / uint8 codes, got {getattr(residual, 'dtype', type(residual).__name__)}")
+    if residual.device != a_codes.device or tuple(residual.shape) != (a_codes.shape[0], n):
+        raise RuntimeError(f"the residual must be [{a_codes.shape[0]}, {n}] on {a_codes.device}, got {tuple(residual.shape)} on "
+                           f"{residual.device}")
+    if residual.dtype == torch.float32:
+        if residual_codes is not None:
+            raise ValueError("residual_codes given with a float32 residual")
+        return residual, None
+    if residual_codes is None:
+        raise ValueError("a residual given as codes needs residual_codes=(scale, zero_point)")
+    r_scale, r_zp = float(residual_codes[0]), int(residual_codes[1])
+    lo, hi = (0, 255) if residual.dtype == torch.uint8 else (-128, 127)
+    if not lo <= r_zp <= hi:
+        raise ValueError(f"the residual's zero point {r_zp} is no {residual.dtype} code")
+    if not 0.0 < r_scale < float("inf"):
+        raise ValueError("the residual's scale must be finite and positive")
+    return residual, (r_scale, r_zp)
 
 
 def folded_clamp(form, a: float, b: float):
@@ -174,11 +215,13 @@ def _k_mismatch(K, w_k, what):
     return RuntimeError(f"shape mismatch: activations have K={K}, {what} K={w_k}")
 
 
-def _launch_consumer(name, a_codes, a_zero_point, a_scale, w, lut, w_scales, w_rowsum, bias, out_codes, w_zero_points):
+def _launch_consumer(name, a_codes, a_zero_point, a_scale, w, lut, w_scales, w_rowsum, bias, out_codes, w_zero_points,
+                     residual=None, residual_codes=None, relu=False):
     """One consumer launch on GPU tensors.  ``name`` is the entry point of the weight format: ``mctq_qlinear_i8`` (``w``: int8
     codes [N, K]), ``mctq_qlinear_w4a8`` (packed 4-bit codes [N, K / 2]) or ``mctq_qlinear_lut4a8`` (packed 4-bit indices
     [N, K / 2] and ``lut = (the 16 codebook bytes,)``; for the others ``lut = ()``).  ``w_zero_points`` selects the ``_zp``
-    form of the first two, and ``out_codes`` on int8 weights without zero points ``mctq_qlinear_i8_codes``."""
+    form of the first two, and ``out_codes`` on int8 weights without zero points ``mctq_qlinear_i8_codes``.  ``residual``
+    (checked by ``_check_residual``; int8 weights without zero points only) selects ``mctq_qlinear_i8_res``."""
     M, K = a_codes.shape
     N, w_k = w.shape
     packed = name != "mctq_qlinear_i8"
@@ -196,32 +239,46 @@ def _launch_consumer(name, a_codes, a_zero_point, a_scale, w, lut, w_scales, w_r
         zp = (w_zero_points.data_ptr(), a_rowsum.data_ptr())
     else:
         zp = ()
-        if not packed and out_codes is not None:
+        if residual is not None:
+            name = "mctq_qlinear_i8_res"
+        elif not packed and out_codes is not None:
             name = "mctq_qlinear_i8_codes"
+    res = ()
+    if residual is not None:
+        residual = residual.contiguous()
+        r_scale, r_zp = residual_codes or (0.0, 0)
+        res = (residual.data_ptr(), -1 if residual_codes is None else ops._code_of(residual), r_scale, r_zp, int(bool(relu)))
     if name == "mctq_qlinear_i8":
         tdt, form = torch.float32, ()                   # the float32-only entry point: no output form among its arguments
     else:
         tdt, *form = _output_form(out_codes)
     y = a_codes.new_empty((M, N), dtype=tdt)
     ops._gpu_call(name, a_codes, a_codes.data_ptr(), ops._code_of(a_codes), int(a_zero_point), float(a_scale), w.data_ptr(), *lut,
-                  w_scales.data_ptr(), w_rowsum.data_ptr(), None if bias is None else bias.data_ptr(), y.data_ptr(), *form, *zp,
+                  w_scales.data_ptr(), w_rowsum.data_ptr(), None if bias is None else bias.data_ptr(), *res, y.data_ptr(), *form, *zp,
                   M, N, K)
     return y
 
 
 def qlinear_i8(a_codes: torch.Tensor, a_zero_point: int, a_scale: float, w_codes: torch.Tensor,
                w_scales: torch.Tensor, w_rowsum: torch.Tensor, bias: Optional[torch.Tensor],
-               out_codes=None, w_zero_points: Optional[torch.Tensor] = None) -> torch.Tensor:
+               out_codes=None, w_zero_points: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
+               residual_codes=None, relu: bool = False) -> torch.Tensor:
     """a_codes [M, K] int8/uint8, w_codes [N, K] int8 (zero point 0 unless ``w_zero_points`` is given) -> float32
     [M, N]; with ``out_codes = (scale, zero_point, qmin, qmax)`` the result leaves as the codes of that activation quantizer
     (int8 / uint8 [M, N]), bit-identical to quantizing the float32 result with ``ops.fq_codes``.  Two more entries,
     ``(..., lo, hi)`` with qmin <= lo <= hi <= qmax, clamp the codes to [lo, hi] instead (a clamp activation folded into the
     codes, ``folded_clamp``); the code type stays that of [qmin, qmax].
     ``w_zero_points`` (int32 [N], each in [-128, 127]): the weights are ``w_codes[n][k] - w_zero_points[n]``; the row sums
-    of the activation codes are computed first (``codes_rowsum``) and the product runs on ``mctq_qlinear_i8_zp``."""
+    of the activation codes are computed first (``codes_rowsum``) and the product runs on ``mctq_qlinear_i8_zp``.
+    ``residual`` [M, N]: the second operand of a residual join, added to the result in the product's epilogue with one float32
+    add -- a float32 tensor, or int8 / uint8 codes with ``residual_codes = (scale, zero_point)`` that stand for
+    ``ops.dequantize_codes(residual, scale, zero_point)`` -- and with ``relu=True`` the join's ReLU behind the add, before the
+    output form: bit for bit ``ops.fq_join(qlinear_i8(...), ..., residual=..., relu=...)`` of the float32 product, without that
+    tensor (``mctq_qlinear_i8_res``).  Not together with ``w_zero_points`` (NotImplementedError); ``relu`` needs a residual."""
+    residual, residual_codes = _check_residual(a_codes, w_codes.shape[0], residual, residual_codes, relu, w_zero_points)
     if a_codes.is_cuda:
         return _launch_consumer("mctq_qlinear_i8", a_codes, a_zero_point, a_scale, w_codes, (), w_scales, w_rowsum, bias,
-                                out_codes, w_zero_points)
+                                out_codes, w_zero_points, residual, residual_codes, relu)
     if w_codes.shape[1] != a_codes.shape[1]:
         raise _k_mismatch(a_codes.shape[1], w_codes.shape[1], "weights")
     ops._cpu_route_allowed()
@@ -230,7 +287,7 @@ def qlinear_i8(a_codes: torch.Tensor, a_zero_point: int, a_scale: float, w_codes
         _check_consumer_operands(a_codes, w_scales, None, None, w_zero_points)     # dtype, device, one per output channel
         w32 = w32 - w_zero_points.to(torch.int32).reshape(-1, 1)
     acc = (a_codes.to(torch.int32) - int(a_zero_point)) @ w32.t()
-    return _cpu_epilogue(acc, a_scale, w_scales, bias, out_codes)
+    return _cpu_epilogue(acc, a_scale, w_scales, bias, out_codes, residual, residual_codes, relu)
 
 
 def qconv_dw_i8(a_codes_nhwc: torch.Tensor, a_zero_point: int, a_scale: float, w_codes: torch.Tensor, w_scales: torch.Tensor,
@@ -413,6 +470,12 @@ class IntegerConsumer(nn.Module):
         # ReLU / ReLU6 / Hardtanh between this layer and that quantizer (folded_clamp).  Kept apart from emit_codes_for: the
         # code type is the domain's, not the narrowed clamp's.
         self.emit_clamp = None
+        # fuse_linear_consumers_fx(fused_residuals=True): the residual join behind this layer folded into its epilogue.
+        # emit_residual: None, "float" (forward's second operand is a float32 tensor) or (scale, zero_point) (it is the int8 /
+        # uint8 codes of that quantizer); emit_relu: the join's ReLU behind the add.  QuantizedLinear and the convolutions
+        # that are its product only.
+        self.emit_residual = None
+        self.emit_relu = False
 
     @classmethod
     def from_wrapper(cls, wrapper: PytorchQuantizationWrapper, activation_quantizer):
@@ -566,15 +629,38 @@ class QuantizedLinear(IntegerConsumer):
         if lut is not None and lut[1].numel() <= 16 and can_pack:
             self._w_idx4, self._lut16 = pack_lut4(self._as_rows(lut[0])), _lut16_bytes(lut[1])
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
         lead = x.shape[:-1]
-        return self._rows_product(self._activation_codes(x.reshape(-1, self.in_features))).reshape(*lead, self.out_features)
+        if residual is not None:
+            residual = residual.reshape(-1, self.out_features)
+        return self._rows_product(self._activation_codes(x.reshape(-1, self.in_features)), residual).reshape(*lead, self.out_features)
 
-    def _rows_product(self, a_codes):
+    def _residual_rows(self, residual):
+        """A convolution's residual -- [B, O, Ho, Wo], NCHW-shaped and NHWC-stored as consumers and joins emit it -- as
+        [B * Ho * Wo, O] rows: a view of channels-last storage, a copy of anything else."""
+        if residual is None:
+            return None
+        if residual.dim() != 4 or residual.shape[1] != self.out_features:
+            raise RuntimeError(f"expected a residual [N, {self.out_features}, H, W], got {tuple(residual.shape)}")
+        rows = residual.permute(0, 2, 3, 1)
+        return (rows if rows.is_contiguous() else rows.contiguous()).reshape(-1, self.out_features)
+
+    def _rows_product(self, a_codes, residual=None):
         """This layer's activation codes [M, K] -> [M, O], float32 or the codes of ``emit_codes_for``: what the convolutions
-        that are this product call with their pixels or patches as rows (their codes are checked once, not again here)."""
+        that are this product call with their pixels or patches as rows (their codes are checked once, not again here).
+        ``residual`` [M, O], as ``emit_residual`` says: added (and ``emit_relu``) in the epilogue of ``qlinear_i8``, the one
+        route that takes one."""
         self._refresh_weight_codes()
         bias = self._bias_for(a_codes)
+        if (residual is not None) != (self.emit_residual is not None):
+            raise RuntimeError(f"this layer was built {'with' if self.emit_residual is not None else 'without'} a residual operand")
+        if residual is not None:
+            as_codes = self.emit_residual != "float"
+            if (residual.dtype in (torch.int8, torch.uint8)) != as_codes or (not as_codes and residual.dtype != torch.float32):
+                raise TypeError(f"this layer was built for a residual operand {'as codes' if as_codes else 'in float32'}, "
+                                f"got {residual.dtype}")
+            return qlinear_i8(a_codes, self._a_zp, self._a_scale, self._w_codes, self._w_scales, self._w_rowsum, bias,
+                              self._out_codes(), self._w_zps, residual, self.emit_residual if as_codes else None, self.emit_relu)
         if self._w_codes4 is not None and a_codes.is_cuda and a_codes.shape[0] <= _W4_MAX_ROWS:
             return qlinear_w4a8(a_codes, self._a_zp, self._a_scale, self._w_codes4, self._w_scales, self._w_rowsum, bias,
                                 self._out_codes(), self._w_zps)
@@ -600,10 +686,10 @@ class QuantizedConv1x1(QuantizedLinear):
                 and conv.padding in ((0, 0), 0, "valid") and conv.dilation == (1, 1) and conv.groups == 1
                 and conv.padding_mode == "zeros")
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
         _check_nchw(x, self.in_features)
         b, _, h, w_ = x.shape
-        y = self._rows_product(self._activation_codes(x).reshape(b * h * w_, self.in_features))
+        y = self._rows_product(self._activation_codes(x).reshape(b * h * w_, self.in_features), self._residual_rows(residual))
         return y.reshape(b, h, w_, self.out_features).permute(0, 3, 1, 2)
 
 
@@ -634,11 +720,11 @@ class QuantizedConv2d(QuantizedLinear):
         kh, kw = self.kernel_size
         return t.reshape(self.out_features, self.in_channels, kh, kw).permute(0, 2, 3, 1).reshape(self.out_features, self.in_features)
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
         _check_nchw(x, self.in_channels)
         b, _, h, w_ = x.shape
         rows = ops.codes_im2col(self._activation_codes(x), self.kernel_size, self.stride, self.padding, self.dilation, self._a_zp)
-        y = self._rows_product(rows)
+        y = self._rows_product(rows, self._residual_rows(residual))
         ho, wo = map(ops._conv_out_size, (h, w_), self.kernel_size, self.stride, self.padding, self.dilation)
         return y.reshape(b, ho, wo, self.out_features).permute(0, 3, 1, 2)
 
@@ -1168,6 +1254,46 @@ def _fold_clamps_into_producers(gm, mods) -> int:
     return folded
 
 
+def _fuse_residuals_into_producers(gm, mods) -> int:
+    """``fuse_linear_consumers_fx(fused_residuals=True)``: a residual join that writes codes only, one of whose operands is the
+    output of a QuantizedLinear-derived consumer (weights without zero points) that feeds nothing else, emits nothing yet and
+    is evaluated after the other operand, leaves the graph: that consumer takes the other operand as its residual, adds it
+    and applies the join's ReLU in its own epilogue and emits the join's codes (``mctq_qlinear_i8_res``).  IEEE addition is
+    commutative, so either operand may be the product; the one evaluated last is, as the other has to exist when it runs.
+    Returns the number of joins removed."""
+    import operator
+    order = {n: i for i, n in enumerate(gm.graph.nodes)}
+    fused = 0
+    for node in list(gm.graph.nodes):
+        join = _module_of(node, mods)
+        if not isinstance(join, QuantizedJoin) or not join.has_residual or join.want_float or len(node.args) != 2 or node.kwargs:
+            continue
+        picks = list(node.users)
+        if not picks or not all(p.op == "call_function" and p.target is operator.getitem and p.args == (node, 1) for p in picks):
+            continue
+        for i in ((0,) if join.residual_codes is not None else (0, 1)):       # (codes are the join's second operand)
+            prod, other = node.args[i], node.args[1 - i]
+            consumer = _module_of(prod, mods)
+            if (isinstance(consumer, QuantizedLinear) and not consumer._uniform_weights and consumer.emit_codes_for is None
+                    and consumer.emit_residual is None and len(prod.users) == 1 and len(prod.args) == 1 and not prod.kwargs
+                    and order[prod] > order[other]):
+                break
+        else:
+            continue
+        consumer.emit_codes_for = (join._a_scale, join._a_zp, join._a_qmin, join._a_qmax)
+        consumer.emit_residual = join.residual_codes if join.residual_codes is not None else "float"
+        consumer.emit_relu = join.relu
+        prod.args = (prod.args[0], other)
+        for p in picks:
+            p.replace_all_uses_with(prod)
+            gm.graph.erase_node(p)
+        gm.graph.erase_node(node)
+        gm.delete_submodule(node.target)
+        mods.pop(node.target, None)
+        fused += 1
+    return fused
+
+
 def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights: bool = False,
                           convolutions: bool = False, depthwise: bool = False, pools: bool = False) -> int:
     """In every ``nn.Sequential`` of ``model``: an activation holder directly followed by a wrapped ``nn.Linear`` with
@@ -1238,7 +1364,7 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
 
 def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weights: bool = False,
                              convolutions: bool = False, depthwise: bool = False, shared_holders: bool = False,
-                             stay_on_codes: bool = False, pools: bool = False):
+                             stay_on_codes: bool = False, pools: bool = False, fused_residuals: bool = False):
     """The same rewrite on an arbitrary module graph (MCT-exported models are not ``nn.Sequential``): traces ``model``
     with torch.fx keeping wrappers and holders as leaves, and wherever an activation holder's ONLY consumer is a
     wrapped ``nn.Linear`` the integer consumer can take (symmetric, power-of-two or LUT weights, and with
@@ -1280,10 +1406,25 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
     monotone in the value and a padded tap is ignored, so the pooled codes are bit for bit the codes of the float32 pool of the
     holder's output, and the model rewritten with ``pools=True`` returns, bit for bit, what the same rewrite without it returns
     wherever the float32 products of the layers behind the pools are exact; otherwise it differs by the accumulation rounding of
-    those products, like every wrapped layer that becomes a consumer."""
+    those products, like every wrapped layer that becomes a consumer.
+
+    ``fused_residuals=True`` (needs ``stay_on_codes=True``; ValueError otherwise -- without it every residual join also writes
+    float32 for the next identity add) folds the residual joins that write codes only into the product in front of them, after
+    the two steps of ``stay_on_codes``.  Such a join goes when one of its two operands is the output of a QuantizedLinear,
+    QuantizedConv1x1 or QuantizedConv2d with weights without zero points that feeds nothing else, emits nothing yet and is
+    evaluated after the other operand: that consumer then takes the other operand -- the codes of the join in front in an
+    identity block, the other branch's float32 output in a downsample block -- as its second argument, adds it and applies the
+    join's ReLU in its own epilogue and emits the join's codes (``mctq_qlinear_i8_res``; ``emit_residual``, ``emit_relu``).  The
+    float32 tensor between the block's last convolution and its join is then neither written nor read, and the join's launch
+    goes.  Joins that must write float32, joins without a residual and joins behind a depthwise, uniform-weights or
+    non-consumer node stay.  The ReLU stays an operation (it is not folded into the clamp), so the result is bit for bit that
+    of the same rewrite without the switch, NaNs included.  Large whole-tile products with a residual run on the tiled kernels,
+    not the faster register-pinned ones (as with weight zero points): the rewrite has no cost model and fuses them all the same."""
     import torch.fx as fx
     if stay_on_codes and not shared_holders:
         raise ValueError("stay_on_codes=True needs shared_holders=True")
+    if fused_residuals and not stay_on_codes:
+        raise ValueError("fused_residuals=True needs stay_on_codes=True")
 
     class _Tracer(fx.Tracer):
         def is_leaf_module(self, m, qualname):
@@ -1329,6 +1470,8 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
     if stay_on_codes:
         _identities_as_codes(gm, mods)
         _fold_clamps_into_producers(gm, mods)
+    if fused_residuals:
+        _fuse_residuals_into_producers(gm, mods)
     gm.graph.lint()
     gm.recompile()
     return gm, replaced

@@ -44,6 +44,60 @@ static int ql_output_form(QlOut& oq, int32_t y_code_dtype, float y_scale, int32_
   return 0;
 }
 
+// The float32 value of one residual code, d = float(code - zero_point) (exact): fma(d, scale, +0), the last step of
+// AffineOp::apply and so the value the join that wrote the code would have written in float32.  The product is a float32
+// VALUE before the add that follows: without the opaque asm the compiler contracts d * s + x into one v_fma_f32 with a single
+// rounding, where the float32 tensor this stands for was rounded once as a product and the add rounds again.  Shared by the
+// join (mctq_fq_join.hip) and the residual form of the integer product (mctq_qlinear.hip).
+__device__ __forceinline__ float join_residual(float d, float scale) {
+  float r = __builtin_fmaf(d, scale, 0.0f);
+  asm("" : "+v"(r));
+  return r;
+}
+
+// The residual operand of a consumer launch (mctq_qlinear_i8_res): [M][N] row-major like y, float32 values or the int8 /
+// uint8 codes of another quantizer with its scale and zero point; relu: v < 0 ? 0 : v behind the add (the join's expression).
+struct QlRes {
+  const void* r;
+  int mode;                 // 0 none, 1 float32, 2 int8 codes, 3 uint8 codes
+  int zp;
+  float scale;
+  int relu;
+};
+// out (+ residual at idx) (then the ReLU): one float32 add, not contracted (-ffp-contract=off; the code's value is opaque).
+// The branches are uniform over the launch.
+__device__ __forceinline__ float ql_residual_at(const QlRes& rs, int64_t idx) {
+  if (rs.mode == 1) return static_cast<const float*>(rs.r)[idx];
+  const int c = rs.mode == 2 ? (int)static_cast<const int8_t*>(rs.r)[idx] : (int)static_cast<const uint8_t*>(rs.r)[idx];
+  return join_residual((float)(c - rs.zp), rs.scale);
+}
+// CNT residuals at once, at idx[0 .. CNT) (valid indices all: the caller clamps rows it will not store): one straight line of
+// loads of the residual's type, issued before any is used -- a branch on the type around every single load would make each
+// wait for the one before it.
+template <class T, int CNT>
+__device__ __forceinline__ void ql_residuals_as(const QlRes& rs, const int64_t (&idx)[CNT], float (&out)[CNT]) {
+  const T* __restrict__ rp = static_cast<const T*>(rs.r);
+  T raw[CNT];
+#pragma unroll
+  for (int j = 0; j < CNT; ++j) raw[j] = rp[idx[j]];
+#pragma unroll
+  for (int j = 0; j < CNT; ++j) {
+    if constexpr (std::is_same<T, float>::value) out[j] = raw[j];
+    else out[j] = join_residual((float)((int)raw[j] - rs.zp), rs.scale);
+  }
+}
+template <int CNT>
+__device__ __forceinline__ void ql_residuals(const QlRes& rs, const int64_t (&idx)[CNT], float (&out)[CNT]) {
+  if (rs.mode == 1) ql_residuals_as<float, CNT>(rs, idx, out);
+  else if (rs.mode == 2) ql_residuals_as<int8_t, CNT>(rs, idx, out);
+  else ql_residuals_as<uint8_t, CNT>(rs, idx, out);
+}
+__device__ __forceinline__ float ql_join(float out, float r, const QlRes& rs) {
+  out = out + r;
+  if (rs.relu) out = out < 0.0f ? 0.0f : out;
+  return out;
+}
+
 // n / d for 32-bit n by magic = floor(2^32 / d) (d = 1: 2^32 - 1): umulhi gives the quotient or one less.
 struct FastDiv {
   uint32_t d, magic;

@@ -38,14 +38,9 @@ struct JoinArgs {
   float rc_zb, rc_scale;
 };
 
-// the float32 value of one residual code (b: the flipped byte as a float, exact).  The product is a float32 VALUE before the
-// add: without the opaque asm the compiler contracts q * s + x into one v_fma_f32 with a single rounding, where the float32
-// tensor this stands for was rounded once as a product and the add rounds again.
-__device__ __forceinline__ float join_residual(float b, const JoinArgs& a) {
-  float r = __builtin_fmaf(b - a.rc_zb, a.rc_scale, 0.0f);
-  asm("" : "+v"(r));
-  return r;
-}
+// the float32 value of one residual code (b: the flipped byte as a float, exact; b - rc_zb == float(code - r_zero_point), exact
+// too): mctq_consumer.hpp's join_residual, which the residual form of the integer product shares
+__device__ __forceinline__ float join_residual(float b, const JoinArgs& a) { return join_residual(b - a.rc_zb, a.rc_scale); }
 
 // the code of v in the form of the float32 output's own parameters (one reciprocal, one set of bounds for both outputs)
 __device__ __forceinline__ int join_code(float v, const JoinArgs& a) {

@@ -21,8 +21,14 @@ constexpr int kQlKBlock = 256;          // bytes of K per wave step: 4 lane grou
 extern int g_ql_variant;                // tuning hook "ql_variant": 0 = automatic
 // what the calling thread launched last (mctq_last_launch): "qlinear_<kernel>_<tile>" with the code widths
 template <bool A_U8>
-static void note_ql(const char* shape, int u = 0, bool zp = false) {       // zp: the form with weight zero points ran
+static void note_ql(const char* shape, int u = 0, bool zp = false, const QlRes* res = nullptr) {   // zp: the form with weight zero points ran
   g_note.shape = shape; g_note.op = zp ? (A_U8 ? "u8 x i8 zp" : "i8 x i8 zp") : (A_U8 ? "u8 x i8" : "i8 x i8");
+  if (res && res->mode) {                 // the residual form ran: "u8 x i8 res(u8) relu"
+    static thread_local char op_text[40];
+    snprintf(op_text, sizeof(op_text), "%s res(%s)%s", g_note.op, res->mode == 1 ? "f32" : res->mode == 2 ? "i8" : "u8",
+             res->relu ? " relu" : "");
+    g_note.op = op_text;
+  }
   g_note.unroll = u; g_note.nt = 0;
   g_note.in_bytes = 1; g_note.out_bytes = 4; ++g_note.count;
   if (g_launch_log) log_launch();
@@ -136,6 +142,8 @@ __device__ __forceinline__ i32x4 ql_unpack_lut4(i32x2 x, const QlLut& c) {
 }
 __device__ __forceinline__ QlLut ql_lut_arg() { return QlLut{{0, 0, 0, 0}}; }
 __device__ __forceinline__ QlLut ql_lut_arg(const QlLut& c) { return c; }
+__device__ __forceinline__ QlRes ql_res_arg() { return QlRes{nullptr, 0, 0, 0.0f, 0}; }
+__device__ __forceinline__ const QlRes& ql_res_arg(const QlRes& r) { return r; }
 enum { kQlW8 = 0, kQlW4 = 1, kQlLut4 = 2 };      // weight formats of the streaming kernel
 
 // MT: 16-row tiles of A per pass (1..4).  A_U8: activation codes are uint8 (re-biased to int8 by ^0x80).
@@ -291,11 +299,15 @@ __global__ __launch_bounds__(kQlWaves * 64) void qlinear_i8_kernel(
 typedef __attribute__((address_space(3))) void ql_lds_void_;
 typedef const __attribute__((address_space(1))) void ql_glb_void_;
 
-template <int kQlWaves, int MT, bool A_U8, bool W_NT, bool ZP = false>
+// Res: empty, or one QlRes -- the residual form (mctq_qlinear_i8_res), a trailing kernel argument that the other
+// instantiations do not have; it is read in the epilogue only.
+template <int kQlWaves, int MT, bool A_U8, bool W_NT, bool ZP = false, class... Res>
 __global__ __launch_bounds__(kQlWaves * 64) void qlinear_i8_lds_kernel(
     const int8_t* __restrict__ a, const int8_t* __restrict__ w, const float* __restrict__ w_scales,
     const int32_t* __restrict__ w_rowsum, const float* __restrict__ bias, void* __restrict__ y,
-    int M, int N, int64_t K, int za, float sa, QlOut oq, QlZp zp) {
+    int M, int N, int64_t K, int za, float sa, QlOut oq, QlZp zp, Res... res) {
+  static_assert(sizeof...(Res) <= 1 && !(ZP && sizeof...(Res)), "the residual form is built without weight zero points");
+  constexpr bool RES = sizeof...(Res) == 1;
   constexpr int kQlThreads = kQlWaves * 64;
   constexpr int NBUF = kQlWaves * 2 * MT * 4096 <= 128 * 1024 ? 2 : 1;      // double-buffer when it fits 128 KiB
   constexpr int kSlots = MT * 256;                       // 16-byte slots of one A buffer: MT*16 rows x 16 chunks
@@ -420,6 +432,7 @@ __global__ __launch_bounds__(kQlWaves * 64) void qlinear_i8_lds_kernel(
       if (m < M && n < N) {
         float out = (float)ql_corrected<ZP>(v, e_corr, e_zw, zp, m) * e_scale;
         if (bias) out = out + e_bias;
+        if constexpr (RES) out = ql_join(out, ql_residual_at(ql_res_arg(res...), (int64_t)m * N + n), ql_res_arg(res...));
         ql_store(y, (int64_t)m * N + n, out, oq);
       }
     }
@@ -443,6 +456,7 @@ struct QlCall {
   QlOut oq;
   QlZp zp;
   hipStream_t stream;
+  QlRes res;                // mode 0 unless the call brings a residual (mctq_qlinear_i8_res); never together with zp
 };
 // the kernels' leading arguments, common to all of them
 #define MCTQ_QL_ARGS(c) (const int8_t*)(c).a, (c).w, (c).w_scales, (c).w_rowsum, (c).bias, (c).y, (int)(c).M, (int)(c).N, (c).K, (c).za, (c).sa
@@ -454,10 +468,16 @@ static int launch_qlinear_lds(const QlCall& c) {
 #define MCTQ_QL_LDS(NT_, ZP_) \
   hipLaunchKernelGGL((qlinear_i8_lds_kernel<WAVES, MT, A_U8, NT_, ZP_>), grid, dim3(WAVES * 64), 0, c.stream, \
                      MCTQ_QL_ARGS(c), c.oq, c.zp)
+#define MCTQ_QL_LDS_RES(NT_) \
+  hipLaunchKernelGGL((qlinear_i8_lds_kernel<WAVES, MT, A_U8, NT_, false, QlRes>), grid, dim3(WAVES * 64), 0, c.stream, \
+                     MCTQ_QL_ARGS(c), c.oq, c.zp, c.res)
+  // (the residual form last: the kernels are emitted in the order in which they are named here)
   if (c.zp.a_rowsum) { if (one_pass) MCTQ_QL_LDS(true, true); else MCTQ_QL_LDS(false, true); }
-  else { if (one_pass) MCTQ_QL_LDS(true, false); else MCTQ_QL_LDS(false, false); }
+  else if (!c.res.mode) { if (one_pass) MCTQ_QL_LDS(true, false); else MCTQ_QL_LDS(false, false); }
+  else { if (one_pass) MCTQ_QL_LDS_RES(true); else MCTQ_QL_LDS_RES(false); }
+#undef MCTQ_QL_LDS_RES
 #undef MCTQ_QL_LDS
-  note_ql<A_U8>(WAVES == 8 ? "qlinear_stream_lds_8waves" : "qlinear_stream_lds_4waves", MT, c.zp.a_rowsum != nullptr);
+  note_ql<A_U8>(WAVES == 8 ? "qlinear_stream_lds_8waves" : "qlinear_stream_lds_4waves", MT, c.zp.a_rowsum != nullptr, &c.res);
   return check_launch("mctq_qlinear_i8 (LDS-staged activations)");
 }
 
@@ -509,11 +529,14 @@ __device__ unsigned long long g_ql_stamp[16 * 8];      // per wave of ONE block:
 // tiles run at the copy issue rate, which grows with the waves that issue), group g multiplies the g-th half of the
 // 64-byte sub-steps of every K tile into its own accumulators, and the two partial sums meet in LDS at the end (exact
 // integer sums: the order does not matter).
-template <int BM, int BN, int kTileBK, bool A_U8, int ST = 2, int KG = 1, bool ZP = false>
+// Res: empty, or one QlRes (the residual form, as in qlinear_i8_lds_kernel): read in the epilogue only.
+template <int BM, int BN, int kTileBK, bool A_U8, int ST = 2, int KG = 1, bool ZP = false, class... Res>
 __global__ __launch_bounds__(256 * KG) void qgemm_i8_glds_kernel(
     const int8_t* __restrict__ a, const int8_t* __restrict__ w, const float* __restrict__ w_scales,
     const int32_t* __restrict__ w_rowsum, const float* __restrict__ bias, void* __restrict__ y,
-    int M, int N, int64_t K, int za, float sa, int m_blocks, int n_blocks, int gm, int flags, QlOut oq, QlZp zp) {
+    int M, int N, int64_t K, int za, float sa, int m_blocks, int n_blocks, int gm, int flags, QlOut oq, QlZp zp, Res... res) {
+  static_assert(sizeof...(Res) <= 1 && !(ZP && sizeof...(Res)), "the residual form is built without weight zero points");
+  constexpr bool RES = sizeof...(Res) == 1;
   const bool rotate = (flags & 1) != 0;              // K rotation (below)
   const bool stagger = (flags & 2) != 0;             // half of the waves request the later tile AFTER multiplying (below)
   constexpr int TM = BM / 32, TN = BN / 32;
@@ -692,6 +715,17 @@ __global__ __launch_bounds__(256 * KG) void qgemm_i8_glds_kernel(
     if (n >= N) continue;
     int e_zw = 0;
     if constexpr (ZP) e_zw = zp.w_zero_points[n];                // here, not with e_corr: nothing more stays live across the K loop
+    float e_res[RES ? TM * 4 : 1];                               // this column's residuals, all requested before the first is used
+    (void)e_res;
+    if constexpr (RES) {
+      int64_t at[TM * 4];                                        // (rows beyond M are clamped: loaded, never stored)
+#pragma unroll
+      for (int t = 0; t < TM; ++t) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) at[4 * t + i] = (int64_t)min(m0 + wm * (BM / 2) + 16 * t + 4 * g + i, M - 1) * N + n;
+      }
+      ql_residuals<TM * 4>(ql_res_arg(res...), at, e_res);
+    }
 #pragma unroll
     for (int t = 0; t < TM; ++t) {
 #pragma unroll
@@ -700,6 +734,7 @@ __global__ __launch_bounds__(256 * KG) void qgemm_i8_glds_kernel(
         if (m < M) {
           float out = (float)ql_corrected<ZP>(acc[t][u][i], e_corr[u], e_zw, zp, m) * e_scale[u];
           if (bias) out = out + e_bias[u];
+          if constexpr (RES) out = ql_join(out, e_res[4 * t + i], ql_res_arg(res...));
           ql_store(y, (int64_t)m * N + n, out, oq);
         }
       }
@@ -722,13 +757,17 @@ static int launch_glds(const QlCall& c) {
 #define MCTQ_QL_GLDS(ZP_) \
   hipLaunchKernelGGL((qgemm_i8_glds_kernel<BM, BN, BK, A_U8, ST, KG, ZP_>), dim3((unsigned)(mbl * nbl)), dim3(256 * KG), 0, c.stream, \
                      MCTQ_QL_ARGS(c), mbl, nbl, gm, flags, c.oq, c.zp)
-  if (c.zp.a_rowsum) MCTQ_QL_GLDS(true); else MCTQ_QL_GLDS(false);
+  if (c.zp.a_rowsum) MCTQ_QL_GLDS(true);
+  else if (!c.res.mode) MCTQ_QL_GLDS(false);
+  else          // the residual form (last: the kernels are emitted in the order in which they are named here)
+    hipLaunchKernelGGL((qgemm_i8_glds_kernel<BM, BN, BK, A_U8, ST, KG, false, QlRes>), dim3((unsigned)(mbl * nbl)), dim3(256 * KG), 0,
+                       c.stream, MCTQ_QL_ARGS(c), mbl, nbl, gm, flags, c.oq, c.zp, c.res);
 #undef MCTQ_QL_GLDS
   static char name[48];                              // "qlinear_tiled[_ring]_<BM>x<BN>x<BK>", formatted once per instantiation
   static const bool named = (snprintf(name, sizeof(name), "qlinear_tiled%s%s_%dx%dx%d", ST > 2 || (BM == 128 && BN == 64) ? "_ring" : "",
                                       KG == 2 ? "_8waves" : KG == 4 ? "_16waves" : "", BM, BN, BK), true);
   (void)named;
-  note_ql<A_U8>(name, gm, c.zp.a_rowsum != nullptr);
+  note_ql<A_U8>(name, gm, c.zp.a_rowsum != nullptr, &c.res);
   return check_launch("mctq_qlinear_i8 (tiled, direct-to-LDS)");
 }
 
@@ -1182,7 +1221,10 @@ enum QlModel {
   kQlByFill               // whole-tile kernel weighed in front of the cost model, by how full its last round of blocks is
 };
 enum { kQlWholeTiles = 1,      // only M % bm == N % bn == K % 128 == 0 and K >= 256
-       kQlNoZeroPoints = 2 };  // not built for calls that bring weight zero points
+       kQlNoZeroPoints = 2,    // not built for calls that bring weight zero points
+       kQlNoResidual = 4 };    // not built for calls that bring a residual (mctq_qlinear_i8_res)
+// what a call needs, as the mask of the rule bits that exclude a kernel from it
+constexpr unsigned kQlNeeds = kQlNoZeroPoints | kQlNoResidual;
 struct QlKernel {
   int variant;            // tuning key "ql_variant"
   QlLaunch launch[2];     // uint8 / int8 activation codes
@@ -1205,7 +1247,8 @@ struct QlKernel {
 // Many rows and columns, whole tiles: the 256 x 256 ping-pong kernel (2.2-2.3 POP/s against 1.5 for the 128 x 128
 // tiles; profiles/r02/qgemm_wide_probe.log) or, when there are too few such tiles for the chip, 128 x 256 wave-wide
 // tiles -- weighed by how full their last round of blocks is (one block per CU; the 128 x 128 kernel fits two).
-// (Zero-point weights: those two kernels and the pinned 128 x 128 candidate do not take them; the tiled kernels do.)
+// (Zero-point weights and residuals: those two kernels and the pinned 128 x 128 candidate do not take them; the tiled
+// kernels do.)
 static const QlKernel kQlKernels[] = {
     // variant, {launcher for uint8, for int8 codes}, model, turn, bm, bn, occ, {rates}[, rules[, m_lo, m_hi]]
     // weight streaming, activation codes through per-wave LDS: 16 / 32 / 64 rows per pass.  A block = 16 weight rows + 16 MT
@@ -1227,14 +1270,14 @@ static const QlKernel kQlKernels[] = {
     {1212, {launch_glds<128, 128, 128, true>, launch_glds<128, 128, 128, false>}, kQlTiles, 11, 128, 128, 2, {30, 48}},
     {662, {launch_glds<64, 64, 256, true>, launch_glds<64, 64, 256, false>}, kQlTiles, 6, 64, 64, 2, {36, 54}},   // two blocks per CU
     // wave-wide 128 x 128 / 128 x 256 tiles
-    {2544, {launch_wide<4, 4, true>, launch_wide<4, 4, false>}, kQlTiles, 12, 128, 128, 2, {38, 43}, kQlWholeTiles | kQlNoZeroPoints},
-    {2548, {launch_wide<4, 8, true>, launch_wide<4, 8, false>}, kQlByFill, 14, 128, 256, 1, {2.0}, kQlWholeTiles | kQlNoZeroPoints},
+    {2544, {launch_wide<4, 4, true>, launch_wide<4, 4, false>}, kQlTiles, 12, 128, 128, 2, {38, 43}, kQlWholeTiles | kQlNoZeroPoints | kQlNoResidual},
+    {2548, {launch_wide<4, 8, true>, launch_wide<4, 8, false>}, kQlByFill, 14, 128, 256, 1, {2.0}, kQlWholeTiles | kQlNoZeroPoints | kQlNoResidual},
     // 256 x 256 ping-pong tiles
-    {2560, {launch_pp<true>, launch_pp<false>}, kQlByFill, 13, 256, 256, 1, {2.25}, kQlWholeTiles | kQlNoZeroPoints},
+    {2560, {launch_pp<true>, launch_pp<false>}, kQlByFill, 13, 256, 256, 1, {2.25}, kQlWholeTiles | kQlNoZeroPoints | kQlNoResidual},
 };
 
-static bool ql_admits(const QlKernel& k, int64_t M, int64_t N, int64_t K, bool with_zp) {
-  if (with_zp && (k.rules & kQlNoZeroPoints)) return false;
+static bool ql_admits(const QlKernel& k, int64_t M, int64_t N, int64_t K, unsigned needs) {
+  if (k.rules & needs & kQlNeeds) return false;
   if ((k.rules & kQlWholeTiles) && (M % k.bm != 0 || N % k.bn != 0 || K % 128 != 0 || K < 256)) return false;
   return k.model != kQlStreaming || (M >= k.m_lo && M <= k.m_hi);
 }
@@ -1242,7 +1285,7 @@ static bool ql_admits(const QlKernel& k, int64_t M, int64_t N, int64_t K, bool w
 // The automatic choice for a checked call (M, N >= 1) on a chip of `cus` compute units.  The loops over the table are
 // unrolled: a row's model, tile and occupancy then fold into constants, and the divisions by them cost what they cost when
 // every candidate was spelled out (a third of the time of the rolled loops, measured on the host alone).
-static const QlKernel* ql_choose(int64_t M, int64_t N, int64_t K, bool with_zp, int64_t cus) {
+static const QlKernel* ql_choose(int64_t M, int64_t N, int64_t K, unsigned needs, int64_t cus) {
   const auto blocks = [&](int64_t bm, int64_t bn) { return ((M + bm - 1) / bm) * ((N + bn - 1) / bn); };
   // Only where the 128 x 128 kernel would fill the chip: smaller problems keep its finer tiles.
   if (blocks(128, 128) >= 2 * cus) {
@@ -1251,7 +1294,7 @@ static const QlKernel* ql_choose(int64_t M, int64_t N, int64_t K, bool with_zp, 
     const QlKernel* pick = nullptr;
 #pragma unroll
     for (const QlKernel& k : kQlKernels) {
-      if (k.model != kQlByFill || !ql_admits(k, M, N, K, with_zp)) continue;
+      if (k.model != kQlByFill || !ql_admits(k, M, N, K, needs)) continue;
       const double rate = k.rate[0] * fill(blocks(k.bm, k.bn), cus);
       if (rate > best || (pick && rate == best && k.turn < pick->turn)) { best = rate; pick = &k; }
     }
@@ -1261,7 +1304,7 @@ static const QlKernel* ql_choose(int64_t M, int64_t N, int64_t K, bool with_zp, 
   const QlKernel* pick = nullptr;
 #pragma unroll
   for (const QlKernel& k : kQlKernels) {
-    if (k.model == kQlByFill || !ql_admits(k, M, N, K, with_zp)) continue;
+    if (k.model == kQlByFill || !ql_admits(k, M, N, K, needs)) continue;
     // us, up to a common constant: a streaming block takes all row passes of its 16 columns
     const int64_t passes = (M + k.bm - 1) / k.bm, across = (N + k.bn - 1) / k.bn;
     const bool stream = k.model == kQlStreaming;
@@ -1293,20 +1336,23 @@ static bool ql_check_call(QlCall& c, int32_t a_code_dtype, bool with_zp, bool pa
   return true;
 }
 
-static int qlinear_dispatch(QlCall c, int32_t a_code_dtype, bool with_zp) {
+// needs: kQlNoZeroPoints for a call with weight zero points, kQlNoResidual for one with a residual (checked by its entry point)
+static int qlinear_dispatch(QlCall c, int32_t a_code_dtype, unsigned needs) {
   int rc;
-  if (!ql_check_call(c, a_code_dtype, with_zp, false, rc)) return rc;
+  if (!ql_check_call(c, a_code_dtype, (needs & kQlNoZeroPoints) != 0, false, rc)) return rc;
   const int which = a_code_dtype == MCTQ_CODE_U8 ? 0 : 1;
   // tuning key "ql_variant": force ONE of the kernels the automatic choice below can select (tests run each of them over
   // ragged shapes against the integer oracle); the experiment variants of round 3 are not built any more
   if (g_ql_variant != 0)
     for (const QlKernel& k : kQlKernels) {
       if (k.variant != g_ql_variant) continue;
-      if (with_zp && (k.rules & kQlNoZeroPoints))
+      if (k.rules & needs & kQlNoZeroPoints)
         return fail_arg("the register-pinned whole-tile kernels (ql_variant 2544 / 2548 / 2560) are not built for zero-point weights");
+      if (k.rules & needs & kQlNoResidual)
+        return fail_arg("the register-pinned whole-tile kernels (ql_variant 2544 / 2548 / 2560) are not built for a residual");
       return k.launch[which](c);
     }
-  return ql_choose(c.M, c.N, c.K, with_zp, cu_count())->launch[which](c);
+  return ql_choose(c.M, c.N, c.K, needs, cu_count())->launch[which](c);
 }
 
 // The entry points that stream half a byte per weight: 4-bit codes (lut == nullptr) or 4-bit indices into *lut.
@@ -1326,7 +1372,7 @@ static int qlinear_packed4(QlCall c, int32_t a_code_dtype, bool with_zp, const Q
 // The entry points' arguments as a call record that is not checked yet: a_zero_point as given, float32 output.
 #define MCTQ_QL_CALL(w_, zw_, ar_)                                                                                      \
   QlCall c{a_codes, reinterpret_cast<const int8_t*>(w_), w_scales, w_rowsum, bias, y, M, N, K, a_zero_point, a_scale, \
-           QlOut{}, QlZp{zw_, ar_}, (hipStream_t)stream}
+           QlOut{}, QlZp{zw_, ar_}, (hipStream_t)stream, QlRes{nullptr, 0, 0, 0.0f, 0}}
 
 extern "C" {
 
@@ -1334,7 +1380,7 @@ int mctq_qlinear_i8(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_po
                     const int8_t* w_codes, const float* w_scales, const int32_t* w_rowsum, const float* bias,
                     float* y, int64_t M, int64_t N, int64_t K, void* stream) {
   MCTQ_QL_CALL(w_codes, nullptr, nullptr);
-  return qlinear_dispatch(c, a_code_dtype, false);
+  return qlinear_dispatch(c, a_code_dtype, 0u);
 }
 
 int mctq_qlinear_i8_codes(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
@@ -1344,7 +1390,7 @@ int mctq_qlinear_i8_codes(const void* a_codes, int32_t a_code_dtype, int32_t a_z
   if (y_code_dtype < 0) return fail_arg("bad y_code_dtype");      // this entry point has no float32 form
   MCTQ_QL_CALL(w_codes, nullptr, nullptr);
   if (int rc = ql_output_form(c.oq, y_code_dtype, y_scale, y_zero_point, y_quant_min, y_quant_max)) return rc;
-  return qlinear_dispatch(c, a_code_dtype, false);
+  return qlinear_dispatch(c, a_code_dtype, 0u);
 }
 
 int mctq_qlinear_w4a8(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
@@ -1400,7 +1446,7 @@ int mctq_qlinear_i8_zp(const void* a_codes, int32_t a_code_dtype, int32_t a_zero
                        int64_t K, void* stream) {
   MCTQ_QL_CALL(w_codes, w_zero_points, a_rowsum);
   if (int rc = ql_output_form(c.oq, y_code_dtype, y_scale, y_zero_point, y_quant_min, y_quant_max)) return rc;
-  return qlinear_dispatch(c, a_code_dtype, true);
+  return qlinear_dispatch(c, a_code_dtype, kQlNoZeroPoints);
 }
 
 int mctq_qlinear_w4a8_zp(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
@@ -1411,6 +1457,34 @@ int mctq_qlinear_w4a8_zp(const void* a_codes, int32_t a_code_dtype, int32_t a_ze
   MCTQ_QL_CALL(w_codes4, w_zero_points, a_rowsum);
   if (int rc = ql_output_form(c.oq, y_code_dtype, y_scale, y_zero_point, y_quant_min, y_quant_max)) return rc;
   return qlinear_packed4(c, a_code_dtype, true, nullptr);
+}
+
+int mctq_qlinear_i8_res(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
+                        const int8_t* w_codes, const float* w_scales, const int32_t* w_rowsum, const float* bias,
+                        const void* residual, int32_t r_code_dtype, float r_scale, int32_t r_zero_point, int32_t relu,
+                        void* y, int32_t y_code_dtype, float y_scale, int32_t y_zero_point, int32_t y_quant_min,
+                        int32_t y_quant_max, int64_t M, int64_t N, int64_t K, void* stream) {
+  MCTQ_QL_CALL(w_codes, nullptr, nullptr);
+  if (int rc = ql_output_form(c.oq, y_code_dtype, y_scale, y_zero_point, y_quant_min, y_quant_max)) return rc;
+  // the residual's own checks, for a problem that is not empty and whose extents ql_check_call will not refuse
+  if (M > 0 && N > 0 && M <= INT32_MAX / 2 && N <= INT32_MAX / 2) {
+    if (!residual) return fail_arg("residual is NULL");
+    if (r_code_dtype >= 0) {                   // the residual as codes: mctq_fq_join_rc_f32's checks
+      if (r_code_dtype != MCTQ_CODE_I8 && r_code_dtype != MCTQ_CODE_U8) return fail_arg("bad r_code_dtype");
+      if (r_code_dtype == MCTQ_CODE_I8 ? (r_zero_point < -128 || r_zero_point > 127) : (r_zero_point < 0 || r_zero_point > 255))
+        return fail_arg("r_zero_point is no code of the residual's type");
+      if (!(r_scale > 0.0f) || !__builtin_isfinite(r_scale)) return fail_arg("r_scale must be finite and positive");
+    } else if (((uintptr_t)residual & 3u) != 0) {
+      return fail_arg("a float32 residual must be 4-byte aligned");
+    }
+    if (y) {                                   // the two byte ranges: a block would read residuals another has overwritten
+      const uintptr_t yb = (uintptr_t)y, rb = (uintptr_t)residual, elems = (uintptr_t)M * (uintptr_t)N;
+      const uintptr_t ye = yb + elems * (y_code_dtype < 0 ? 4u : 1u), re = rb + elems * (r_code_dtype < 0 ? 4u : 1u);
+      if (yb < re && rb < ye) return fail_arg("y overlaps the residual");
+    }
+  }
+  c.res = QlRes{residual, r_code_dtype < 0 ? 1 : r_code_dtype == MCTQ_CODE_I8 ? 2 : 3, (int)r_zero_point, r_scale, relu != 0};
+  return qlinear_dispatch(c, a_code_dtype, kQlNoResidual);
 }
 #undef MCTQ_QL_CALL
 

@@ -50,13 +50,15 @@ class LutItem(ctypes.Structure):
                 ("dtype", ctypes.c_int32), ("step_round", ctypes.c_int32)]
 
 
-def _ql_signature(lut=False, form=True, zp=False):
-    """The integer consumer's entry points (mctq_qlinear_*) share their argument list up to three optional groups."""
+def _ql_signature(lut=False, form=True, zp=False, res=False):
+    """The integer consumer's entry points (mctq_qlinear_*) share their argument list up to four optional groups."""
     return ctypes.c_int, (
         [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,      # a_codes, a_code_dtype, a_zero_point, a_scale
          ctypes.c_void_p]                                                       # w_codes / w_codes4 / w_idx4
         + ([ctypes.c_void_p] if lut else [])                                    # lut16 (a host pointer)
-        + [_c_f32p, _c_i32p, _c_f32p, ctypes.c_void_p]                          # w_scales, w_rowsum, bias, y
+        + [_c_f32p, _c_i32p, _c_f32p]                                           # w_scales, w_rowsum, bias
+        + ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_int32] if res else [])   # residual, r_code_dtype, r_scale, r_zero_point, relu
+        + [ctypes.c_void_p]                                                     # y
         + ([ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32] if form else [])   # y_code_dtype, y_scale, y_zero_point, y_quant_min, y_quant_max
         + ([_c_i32p, _c_i32p] if zp else [])                                    # w_zero_points, a_rowsum
         + [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p])    # M, N, K, stream
@@ -127,6 +129,7 @@ SIGNATURES = {
                                          ctypes.c_int64, ctypes.c_void_p]),
     "mctq_qlinear_i8_zp": _ql_signature(zp=True),
     "mctq_qlinear_w4a8_zp": _ql_signature(zp=True),
+    "mctq_qlinear_i8_res": _ql_signature(res=True),
     "mctq_fq_codes_nchw_to_nhwc": (ctypes.c_int, [_c_f32p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                                   ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_int32,
                                                   ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
