@@ -393,7 +393,9 @@ int mctq_lutt_per_channel(const void* x, float* y,
  *                            step_round as mctq_lutt_per_tensor.  5 algorithmic bytes per float32 element (4.5 packed).
  *   mctq_lut_decode_per_tensor / _per_channel : codes in, y float32 out; every block stages lut[j] / mult once and each
  *                            element costs one table read and one multiplication by its threshold.  A code >= n_lut
- *                            (never produced by the encoders) reads as code 0 ... 255 of a zero-padded table.
+ *                            (never produced by the encoders) decodes to 0.0 * thr: the staged table is zero-padded to
+ *                            the 256 (4-bit: 16) values a code can take.  uint8 codes that are not 4-byte or a y that is
+ *                            not 16-byte aligned take a one-element-per-lane kernel; 4-bit codes are refused then.
  * Conventions of every entry point (caller-owned device pointers, stream order, legal under graph capture, no allocation,
  * mctq_last_launch / mctq_launch_count, MCTQ_E_ARG without a GPU, empty tensors launch nothing) hold; the size limit above
  * (2^32 - 8192 elements in short rows) applies to the per-channel encode, and the decode takes at most 2^32 - 8192 elements
