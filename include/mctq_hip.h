@@ -72,6 +72,9 @@ extern "C" {
  * an activation holder and the integer consumers behind it stays on codes); no existing signature or result changed. */
 /* v10 (additive, the version number stays): + mctq_qlinear_i8_res, the integer product with the residual add and the ReLU of a residual
  * join in its epilogue (the block's last convolution emits the next block's codes itself); no existing signature or result changed. */
+/* v10 (additive, the version number stays): + mctq_codes_concat_nhwc, torch.cat along the channels on NHWC activation codes in the
+ * form of the holder behind it (Inception / Fire / skip-connection blocks stay on codes), + tuning key "concat_copy"; no existing
+ * signature or result changed. */
 #define MCTQ_ABI_VERSION 10
 #define MCTQ_E_ARG (-10001)
 
@@ -558,6 +561,40 @@ int mctq_codes_maxpool_nhwc(const void* codes, void* pooled, int32_t code_dtype,
                             void* stream);
 
 /*
+ * Channel concatenation on activation codes (extension; the reference runs torch.cat on the float32 outputs of the operand
+ * holders and the holder behind it on the result): operand k is codes [pixels][channels_k] (NHWC with the leading extents
+ * folded; int8 -- MCTQ_CODE_I8 -- or uint8, MCTQ_CODE_U8) with its own scale and zero point, out is
+ * [pixels][sum of channels_k] in the form (out_code_dtype, scale, zero_point, quant_min, quant_max); all DEVICE pointers,
+ * 16-byte aligned; `items` is a HOST array of `count` operands, 1 .. 8, read before the call returns:
+ *     v                          = fma(float(code_k[p][c] - zero_point_k), scale_k, +0)     the operand holder's float32 output
+ *     out[p][start_k + c]        = clamp(rint(v * (1.0f / scale)) + zero_point, quant_min, quant_max)
+ * -- bit for bit the code the holder behind the concatenation gives that float32 tensor (mctq_fq_codes_per_tensor's
+ * arithmetic, the reciprocal computed on the host as there).  count == 1 is a requantization of codes.
+ * Every channels_k is a positive multiple of 16: a 16-byte chunk of an output row is one aligned chunk of one operand, and a
+ * lane owns one such chunk -- one 16-byte load, one 16-byte store, 1 byte read and 1 written per element.
+ * An operand whose form is the output's (the same float32 scale bits, zero point and code type, [quant_min, quant_max] the
+ * whole range of the type, scale in [2^-100, 2^100]) is copied: for such a form the arithmetic above returns the code it
+ * was given, for every code.  Tuning key "concat_copy" = 0 sends such operands through the arithmetic as well.
+ * A lane reads only chunks below pixels * channels_k / 16 of its operand and writes only chunks below
+ * pixels * sum(channels_k) / 16.
+ * MCTQ_E_ARG with a mctq_last_error text, before anything is launched, for: count outside 1 .. 8; items NULL; pixels < 0; a
+ * bad code type; a zero point that is no code of its type (operands and output); a scale that is not finite and positive
+ * (operands and output); quant_min > quant_max or a domain outside the output type; channels_k not a positive multiple of
+ * 16; more than 2^31 - 1 16-byte chunks of output (split the pixels); NULL or misaligned pointers of a non-empty problem;
+ * an `out` whose bytes overlap an operand's.  pixels == 0 returns 0 without a launch.  mctq_last_launch names the launch
+ * "codes_concat", op "<count> -> u8" / "<count> -> i8".
+ */
+typedef struct mctq_concat_item {
+  const void* codes;      /* device, [pixels][channels], 16-byte aligned */
+  int64_t channels;
+  int32_t code_dtype;     /* MCTQ_CODE_I8 / MCTQ_CODE_U8 */
+  int32_t zero_point;
+  float scale;
+} mctq_concat_item;
+int mctq_codes_concat_nhwc(const mctq_concat_item* items, int32_t count, void* out, int32_t out_code_dtype, int64_t pixels,
+                           float scale, int32_t zero_point, int32_t quant_min, int32_t quant_max, void* stream);
+
+/*
  * Depthwise convolution on activation codes (groups == channels, channel multiplier 1; extension, the reference has no
  * counterpart): what a wrapped depthwise torch.nn.Conv2d computes on fake-quantized operands, evaluated on the codes.
  *     acc[b][oy][ox][c] = sum over the taps (ky, kx) inside the image of
@@ -801,6 +838,8 @@ int mctq_qlinear_i8_res(const void* a_codes, int32_t a_code_dtype, int32_t a_zer
  *                  measured faster (4096 x 4096 22.2 -> 21.55 us; 1-4 % up to four rounds, 0.2-0.8 % at six and eight), 2 = every
  *                  eligible launch that reaches the rows shape (those inside the "paced" window go to that kernel first).
  *                  Launches with a zero-point table and 16-bit storage are never eligible.
+ *   key "concat_copy" : mctq_codes_concat_nhwc, operands in the output's own form: 1 (default) = their lanes store what they loaded,
+ *                  0 = they run the requantization arithmetic like every other operand (the bytes are the same: the tests' proof)
  * Only variants a default dispatcher can select are instantiated; every value of every key is exercised by the GPU tests.
  * Returns 0, or MCTQ_E_ARG for an unknown key/value.  Numerical results never depend on it.
  */

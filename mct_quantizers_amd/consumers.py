@@ -60,6 +60,12 @@ is ``float(code - zp) * scale`` with ``scale > 0``, monotone in the code and nev
 dequantized pool of the codes bit for bit.  ``QuantizedMaxPool2d`` (``mctq_codes_maxpool_nhwc``) pools the codes -- a padded tap
 is ignored, it stands for -inf and not for the zero point -- and the convolutions behind it become consumers of the pooled codes.
 
+A channel concatenation between holders stays on codes with ``fuse_linear_consumers_fx(..., concats=True)``: every operand
+holder's float32 output is ``float(code - zp_i) * scale_i`` bit for bit and ``torch.cat`` only moves data, so the codes the holder
+behind the concatenation gives are the operands' codes requantized one by one into its form.  ``QuantizedConcat``
+(``mctq_codes_concat_nhwc``) does that in one launch, 1 byte read and 1 written per element, and the layers and pools behind
+the holder become consumers of its codes; with ``stay_on_codes=True`` the branch convolutions emit the operands' codes.
+
 The four modules derive from ``IntegerConsumer``, which owns what they share: the checks of the quantizers and of the float32
 weight and bias, the cache of the weight's codes, the step from ``forward``'s input to activation codes, ``from_wrapper`` and
 the ``emit_codes_for`` / ``emit_clamp`` output form.  ``QuantizedLinear`` is the product over ``[O, K]`` rows; ``QuantizedConv1x1``
@@ -834,6 +840,88 @@ class QuantizedMaxPool2d(nn.Module):
         return y.permute(0, 3, 1, 2)
 
 
+class QuantizedConcat(nn.Module):
+    """``activation holders -> torch.cat(..., dim=1) -> activation holder`` on integer codes, for the integer consumers and
+    pools behind that holder.  An operand holder's float32 output is ``float(code - zp_i) * scale_i`` bit for bit
+    (``ops.dequantize_codes``), ``torch.cat`` only moves data, and the holder behind it codes every element by itself, so the
+    codes of the concatenated tensor are the operands' codes requantized one by one into the output form --
+    ``ops.codes_concat`` (``mctq_codes_concat_nhwc``): 1 byte read and 1 written per element in one launch, where every
+    operand holder, ``torch.cat`` and the holder behind it each read and write 4.
+
+    ``operand_quantizers`` (1 to any number; more than 8, or channel counts that are no multiple of 16, take the torch route of
+    ``ops.codes_concat``) and ``activation_quantizer``, the output holder's: per-tensor affine activation quantizers of at most 8
+    bits.  ``forward(*xs)`` takes each operand as the codes of its quantizer (int8 / uint8 of its code type, NCHW-shaped and
+    NHWC-stored as the consumers and joins emit them, or ``[M, C]`` rows) or as a float32 tensor, which it quantizes with that
+    operand's parameters -- the holder's input and its output give the same codes, since a quantizer's codes of its own
+    output are the codes that output was made from.  It returns the output holder's codes, NCHW-shaped and NHWC-stored for
+    4-D operands and ``[M, sum C]`` for rows, which an ``IntegerConsumer`` or a ``QuantizedMaxPool2d`` of that quantizer takes as
+    they are.  ``activation_code_params`` is the OUTPUT form, what the modules behind agree on; ``operand_code_params(i)`` is
+    what ``emit_codes_for`` of the layer in front of operand ``i`` takes."""
+
+    def __init__(self, operand_quantizers, activation_quantizer):
+        super().__init__()
+        operand_quantizers = tuple(operand_quantizers)
+        if not operand_quantizers:
+            raise ValueError("QuantizedConcat needs at least one operand")
+        for q in (*operand_quantizers, activation_quantizer):
+            if getattr(q, "num_bits", 9) > 8:
+                raise NotImplementedError("codes wider than 8 bits")
+        self.operand_quantizers = operand_quantizers
+        self.activation_quantizer = activation_quantizer
+        self._forms = tuple(self._form_of(q) for q in operand_quantizers)
+        self._out_form = self._form_of(activation_quantizer)
+
+    @staticmethod
+    def _form_of(q):
+        """(scale, zero_point, qmin, qmax) of a quantizer whose codes and zero point are 8-bit codes of one type."""
+        scale, zp, qmin, qmax = _activation_code_params(q)
+        tdt, _ = ops._code_dtype(qmin, qmax)                   # (raises for a domain that is no 8-bit code)
+        lo, hi = (0, 255) if tdt == torch.uint8 else (-128, 127)
+        if not lo <= zp <= hi:
+            raise NotImplementedError(f"the zero point {zp} is no {tdt} code")
+        if not 0.0 < scale < math.inf:
+            raise ValueError("the scale must be finite and positive")
+        return scale, zp, qmin, qmax
+
+    def operand_code_params(self, i: int):
+        """(scale, zero_point, qmin, qmax) of the codes operand ``i`` is read as."""
+        return self._forms[i]
+
+    def activation_code_params(self):
+        """(scale, zero_point, qmin, qmax) of the codes ``forward`` returns: what the consumers and pools behind read."""
+        return self._out_form
+
+    def extra_repr(self) -> str:
+        return f"operands={len(self._forms)}"
+
+    def forward(self, *xs) -> torch.Tensor:
+        if len(xs) != len(self._forms):
+            raise RuntimeError(f"this concatenation was built for {len(self._forms)} operands, got {len(xs)}")
+        first = xs[0]
+        if first.dim() not in (2, 4):
+            raise RuntimeError(f"expected [N, C, H, W] or [M, C] operands, got {tuple(first.shape)}")
+        parts = []
+        for i, (x, (scale, zp, qmin, qmax)) in enumerate(zip(xs, self._forms)):
+            if x.dim() != first.dim() or x.shape[0] != first.shape[0] or x.shape[2:] != first.shape[2:]:
+                raise RuntimeError(f"operand {i} is {tuple(x.shape)} next to {tuple(first.shape)}: the operands of a concatenation "
+                                   f"along dimension 1 differ in that dimension only")
+            if x.dtype in (torch.uint8, torch.int8):
+                if x.dtype != ops._code_dtype(qmin, qmax)[0]:
+                    raise TypeError(f"operand {i}: activation codes of type {x.dtype} do not match its quantizer")
+                codes = x
+                if x.dim() == 4:
+                    codes = x.permute(0, 2, 3, 1)
+                    codes = codes if codes.is_contiguous() else codes.contiguous()
+            elif x.dtype == torch.float32:
+                codes = ops.fq_codes_nhwc(x, qmin, qmax, scale, zp) if x.dim() == 4 else \
+                    ops.fq_codes(x, None, None, None, qmin, qmax, scale, zp)
+            else:
+                raise TypeError(f"QuantizedConcat takes float32 tensors or activation codes, got {x.dtype}")
+            parts.append((codes, scale, zp))
+        y = ops.codes_concat(parts, self._out_form)
+        return y.permute(0, 3, 1, 2) if first.dim() == 4 else y
+
+
 # In the order they are tried: (class, the switch of the rewrites that enables it or None, what fusing asks of the layer beyond
 # ``eligible``).  The rows kernels need K % 16 == 0 and K <= _MAX_K, which QuantizedConv2d's ``eligible`` holds itself.
 _CONSUMERS = (
@@ -1124,6 +1212,82 @@ def _pool_lone_holders(gm, mods, consumer_for) -> int:
     return replaced
 
 
+def _cat_operands(node):
+    """The operand nodes of ``node`` if it is ``torch.cat`` / ``torch.concat`` / ``torch.concatenate`` of a list or tuple of 2 to
+    8 nodes along the constant dimension 1 (positional or ``dim=``; no ``out=``), else None."""
+    from torch.fx import Node
+    if node.op != "call_function" or node.target not in (torch.cat, torch.concat, torch.concatenate):
+        return None
+    if not 1 <= len(node.args) <= 2 or set(node.kwargs) - ({"dim"} if len(node.args) == 1 else set()):
+        return None
+    dim = node.args[1] if len(node.args) == 2 else node.kwargs.get("dim", 0)
+    if not isinstance(dim, int) or isinstance(dim, bool) or dim != 1:
+        return None
+    tensors = node.args[0]
+    if not isinstance(tensors, (list, tuple)) or not 2 <= len(tensors) <= 8 or not all(isinstance(t, Node) for t in tensors):
+        return None
+    return list(tensors)
+
+
+def _concat_holders(gm, mods, consumer_for, pools: bool = False) -> int:
+    """``fuse_linear_consumers_fx(concats=True)``: a plain holder whose one argument is a concatenation along the channels
+    (``_cat_operands``) that feeds nothing else, every operand of which is the output of a plain holder, and every user of which
+    is a wrapped layer ``consumer_for`` can take, fed by it alone -- or, with ``pools``, a max pool that can run on codes
+    (``_pool_plan``) -- becomes a QuantizedConcat node together with the concatenation; its users become consumers and pools of
+    its codes.  An operand holder whose only user was the concatenation leaves the graph and the QuantizedConcat quantizes that
+    holder's input; one with other users stays and the QuantizedConcat quantizes its float32 output (the same codes).  Returns
+    the number of wrapped layers replaced."""
+    from torch.fx import Node
+    replaced = 0
+    for node in list(gm.graph.nodes):
+        if node.op != "call_module" or node.kwargs or len(node.args) != 1 or not isinstance(node.args[0], Node) or not node.users:
+            continue
+        holder = mods.get(node.target)
+        if not _plain_holder(holder):
+            continue
+        cat = node.args[0]
+        operands = _cat_operands(cat)
+        if operands is None or len(cat.users) != 1:
+            continue
+        sources = [_module_of(o, mods) for o in operands]
+        if not all(_plain_holder(h) and len(o.args) == 1 and isinstance(o.args[0], Node) and not o.kwargs
+                   for o, h in zip(operands, sources)):
+            continue
+        quantizer = holder.activation_holder_quantizer
+        taken, pooled = [], []
+        for user in node.users:
+            wrapper = _module_of(user, mods)
+            if isinstance(wrapper, PytorchQuantizationWrapper) and not user.kwargs and user.args == (node,):
+                fused = consumer_for(wrapper, quantizer)
+                if fused is not None:
+                    taken.append((user, fused))
+                    continue
+            plan = _pool_plan(user, mods, quantizer, consumer_for) if pools else None
+            if plan is None:
+                break
+            pooled.append((user, plan))
+        else:
+            try:
+                concat = QuantizedConcat([h.activation_holder_quantizer for h in sources], quantizer)
+            except (TypeError, ValueError, NotImplementedError):
+                continue
+            name = node.target.replace(".", "_") + "_concat"
+            gm.add_submodule(name, concat)
+            mods[name] = concat
+            absorbed = [o for o in dict.fromkeys(operands) if len(o.users) == 1]
+            with gm.graph.inserting_before(node):
+                cn = gm.graph.call_module(name, tuple(o.args[0] if o in absorbed else o for o in operands))
+            for user, fused in taken:
+                _install_consumer(gm, mods, user, fused)
+                user.args = (cn,)
+                replaced += 1
+            for user, plan in pooled:
+                replaced += _install_pool(gm, mods, user, plan, cn)
+            for gone in (node, cat, *absorbed):
+                gm.graph.erase_node(gone)
+    return replaced
+
+
 def _clamp_range(node, mods):
     """(a, b) if ``node`` is a clamp activation of one tensor that ``folded_clamp`` can fold -- a ReLU (as ``_relu_input``),
     ``nn.ReLU6`` / ``F.relu6``, ``nn.Hardtanh`` / ``F.hardtanh`` with finite ``min_val <= max_val`` -- else None.  In-place forms
@@ -1205,8 +1369,10 @@ def _fold_clamps_into_producers(gm, mods) -> int:
     holder all of whose users are integer consumers (or, with ``pools=True``, QuantizedMaxPool2d modules in front of such), the
     consumer emits that holder's codes itself, the activation folded into their clamp (``folded_clamp``), and the modules behind
     take them directly.  The holder is either already inside the one
-    consumer behind it (the pair rewrite) or a residual-free QuantizedJoin that writes no float32 output.  Returns the number of
-    producers that now emit codes."""
+    consumer behind it (the pair rewrite) or a residual-free QuantizedJoin that writes no float32 output.  With
+    ``concats=True`` the reader may also be a QuantizedConcat among whose arguments the consumer's output (or its one clamp
+    activation) occurs exactly once, at index i: the consumer then emits the codes of ``operand_code_params(i)``, the clamp
+    folded in, and that one argument becomes the consumer's output.  Returns the number of producers that now emit codes."""
     import operator
     folded = 0
     for node in list(gm.graph.nodes):
@@ -1217,10 +1383,18 @@ def _fold_clamps_into_producers(gm, mods) -> int:
         if _clamp_range(nxt, mods) is not None and len(nxt.users) == 1:
             act, rng = nxt, _clamp_range(nxt, mods)
             nxt = next(iter(nxt.users))
-        if nxt.op != "call_module" or nxt.kwargs or nxt.args != (act or node,):
+        if nxt.op != "call_module" or nxt.kwargs:
             continue
-        behind, gone = mods.get(nxt.target), [nxt]
-        if isinstance(behind, _CODE_READERS):
+        behind, gone, src, concat_args = mods.get(nxt.target), [nxt], act or node, None
+        if isinstance(behind, QuantizedConcat):
+            if sum(a is src for a in nxt.args) != 1:
+                continue                                 # (the same tensor at two places, with two forms: left alone)
+            at = next(i for i, a in enumerate(nxt.args) if a is src)
+            form, readers, gone = behind.operand_code_params(at), [], []
+            concat_args = tuple(node if a is src else a for a in nxt.args)
+        elif nxt.args != (src,):
+            continue
+        elif isinstance(behind, _CODE_READERS):
             form, readers, gone = behind.activation_code_params(), [nxt], []
         elif isinstance(behind, QuantizedJoin) and not behind.has_residual and not behind.want_float:
             if behind.relu:
@@ -1245,6 +1419,8 @@ def _fold_clamps_into_producers(gm, mods) -> int:
         producer.emit_codes_for, producer.emit_clamp = form, (None if clamp == (form[2], form[3]) else clamp)
         for r in readers:
             r.args = (node,)
+        if concat_args is not None:
+            nxt.args = concat_args
         for g in gone + ([act] if act is not None else []):
             gm.graph.erase_node(g)
         if gone:
@@ -1364,7 +1540,8 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
 
 def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weights: bool = False,
                              convolutions: bool = False, depthwise: bool = False, shared_holders: bool = False,
-                             stay_on_codes: bool = False, pools: bool = False, fused_residuals: bool = False):
+                             stay_on_codes: bool = False, pools: bool = False, fused_residuals: bool = False,
+                             concats: bool = False):
     """The same rewrite on an arbitrary module graph (MCT-exported models are not ``nn.Sequential``): traces ``model``
     with torch.fx keeping wrappers and holders as leaves, and wherever an activation holder's ONLY consumer is a
     wrapped ``nn.Linear`` the integer consumer can take (symmetric, power-of-two or LUT weights, and with
@@ -1419,7 +1596,26 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
     goes.  Joins that must write float32, joins without a residual and joins behind a depthwise, uniform-weights or
     non-consumer node stay.  The ReLU stays an operation (it is not folded into the clamp), so the result is bit for bit that
     of the same rewrite without the switch, NaNs included.  Large whole-tile products with a residual run on the tiled kernels,
-    not the faster register-pinned ones (as with weight zero points): the rewrite has no cost model and fuses them all the same."""
+    not the faster register-pinned ones (as with weight zero points): the rewrite has no cost model and fuses them all the same.
+
+    ``concats=True`` (needs no other switch) keeps a channel concatenation between holders on codes: the Inception block, the
+    Fire module, a decoder stage with skip connections.  The candidate is a plain holder whose one argument is ``torch.cat`` /
+    ``torch.concat`` / ``torch.concatenate`` of a list or tuple of 2 to 8 tensors along the constant dimension 1 (no ``out=``)
+    that feeds nothing else, every operand the output of a plain holder, and every user of which is a wrapped layer the consumer
+    can take under the other switches, fed by it alone, or with ``pools=True`` a max pool that can run on codes.  The
+    concatenation and the holder become one QuantizedConcat node (``mctq_codes_concat_nhwc``: the operands' codes requantized
+    into the holder's form, 1 byte read and 1 written per element) and the users consumers and pools of its codes.  An operand
+    holder whose only user was the concatenation leaves the graph, the QuantizedConcat quantizes its input; one with other
+    users (a skip connection) stays, and the QuantizedConcat quantizes its float32 output -- or, where ``shared_holders=True``
+    turns it into a join, that join's float32 output.  Everything else is left alone: a float32 user of the holder, an operand
+    that is no holder's output, a clamp between the concatenation and the holder, another dimension, more than 8 operands.
+    With ``stay_on_codes=True`` a consumer in front of an operand -- through at most one ReLU / ReLU6 / Hardtanh -- emits that
+    operand's codes itself, so that conv -> ReLU -> holder -> cat -> holder -> conv runs codes to codes.  A holder's float32
+    output is ``float(code - zp) * scale`` bit for bit and ``torch.cat`` only moves data, so the codes are bit for bit those of the
+    holder behind the float32 concatenation, for any channel counts (counts that are no multiple of 16 take torch ops), and
+    the model rewritten with ``concats=True`` returns, bit for bit, what the same rewrite without it returns wherever the
+    float32 products of the layers behind the concatenation are exact; otherwise it differs by the accumulation rounding of
+    those products, like every wrapped layer that becomes a consumer."""
     import torch.fx as fx
     if stay_on_codes and not shared_holders:
         raise ValueError("stay_on_codes=True needs shared_holders=True")
@@ -1429,7 +1625,7 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
     class _Tracer(fx.Tracer):
         def is_leaf_module(self, m, qualname):
             return isinstance(m, (PytorchQuantizationWrapper, PytorchActivationQuantizationHolder, IntegerConsumer, QuantizedJoin,
-                                  QuantizedMaxPool2d)) \
+                                  QuantizedMaxPool2d, QuantizedConcat)) \
                 or super().is_leaf_module(m, qualname)
 
     graph = _Tracer().trace(model)
@@ -1437,8 +1633,10 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
     mods = dict(gm.named_modules())
     replaced = 0
     consumer_for = lambda wrapper, q: _consumer_for(wrapper, q, uniform_weights, convolutions, depthwise)      # noqa: E731
+    if concats:
+        replaced = _concat_holders(gm, mods, consumer_for, pools)
     if shared_holders:
-        replaced = _join_shared_holders(gm, mods, consumer_for, pools)
+        replaced += _join_shared_holders(gm, mods, consumer_for, pools)
     if pools:
         replaced += _pool_lone_holders(gm, mods, consumer_for)
     for node in list(gm.graph.nodes):

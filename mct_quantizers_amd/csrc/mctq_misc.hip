@@ -24,6 +24,7 @@ int g_ql_variant = 0;
 int g_ql_band = 0;
 int g_ql_stagger = 0;         // tiled consumer kernel: half of the waves copy after multiplying (experiment: no gain)
 int g_ql_rot = 0;            // tiled consumer kernel: blocks that share a weight tile start at different K offsets (experiment: no gain)
+int g_concat_copy = 1;       // mctq_codes_concat_nhwc: operands in the output's own form are copied, not requantized (0: never; the result is the same)
 
 static const char* launch_log_path() {
   const char* p = getenv("MCTQ_LAUNCH_LOG");
@@ -208,6 +209,11 @@ int mctq_set_tuning(const char* key, int32_t value) {
   if (!strcmp(key, "ql_band")) {
     if (value < 0 || value > 4096) return fail_arg("ql_band must be 0 (automatic) or the number of tile rows per band");
     g_ql_band = value;
+    return 0;
+  }
+  if (!strcmp(key, "concat_copy")) {
+    if (value != 0 && value != 1) return fail_arg("concat_copy must be 0 or 1");
+    g_concat_copy = value;
     return 0;
   }
   return fail_arg("unknown tuning key");

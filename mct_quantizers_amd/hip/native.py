@@ -50,6 +50,12 @@ class LutItem(ctypes.Structure):
                 ("dtype", ctypes.c_int32), ("step_round", ctypes.c_int32)]
 
 
+class ConcatItem(ctypes.Structure):
+    """mctq_concat_item of include/mctq_hip.h (one operand of a concatenation on codes)."""
+    _fields_ = [("codes", ctypes.c_void_p), ("channels", ctypes.c_int64), ("code_dtype", ctypes.c_int32),
+                ("zero_point", ctypes.c_int32), ("scale", ctypes.c_float)]
+
+
 def _ql_signature(lut=False, form=True, zp=False, res=False):
     """The integer consumer's entry points (mctq_qlinear_*) share their argument list up to four optional groups."""
     return ctypes.c_int, (
@@ -137,6 +143,9 @@ SIGNATURES = {
                                               ctypes.c_int64] + [ctypes.c_int32] * 9 + [ctypes.c_void_p]),
     "mctq_codes_maxpool_nhwc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32] + [ctypes.c_int64] * 4    # codes, pooled, type; B, H, W, C
                                 + [ctypes.c_int32] * 9 + [ctypes.c_int64] * 2 + [ctypes.c_void_p]),                # geometry, ceil_mode; Ho, Wo; stream
+    "mctq_codes_concat_nhwc": (ctypes.c_int, [ctypes.POINTER(ConcatItem), ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,    # items, count, out, out type
+                                              ctypes.c_int64, ctypes.c_float, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,  # pixels, scale, zero point, qmin, qmax
+                                              ctypes.c_void_p]),
     "mctq_qconv_dw_i8": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,   # a_codes, type, zero point, scale
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,  # w_codes, w_scales, w_zero_points, bias
                                         ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_int32,

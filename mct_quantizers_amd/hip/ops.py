@@ -27,6 +27,7 @@ from __future__ import annotations
 
 from typing import Tuple
 
+import math
 import os
 
 import torch
@@ -698,6 +699,59 @@ def codes_maxpool(codes_nhwc, kernel_size, stride=None, padding=0, dilation=1, c
     # (NCHW-contiguous: ATen's channels-last kernel keeps its indices in the tensor's own integer type and refuses larger images)
     y = torch.nn.functional.max_pool2d(x.permute(0, 3, 1, 2).contiguous(), (kh, kw), (sh, sw), (ph, pw), (dh, dw), ceil_mode)
     return y.permute(0, 2, 3, 1).contiguous()
+
+
+_CONCAT_MAX = 8           # operands of one mctq_codes_concat_nhwc launch
+
+
+def codes_concat(operands, out_form):
+    """``torch.cat`` along the channels on activation codes, in the form of the holder behind it.  ``operands``: a sequence of
+    ``(codes, scale, zero_point)``, int8 / uint8 codes ``[.., C_k]`` (channels last) with the same leading shape on one device;
+    ``out_form = (scale, zero_point, qmin, qmax)``.  Returns contiguous codes ``[.., sum C_k]`` of ``_code_dtype(qmin, qmax)``:
+
+        torch.cat([fq_codes(dequantize_codes(c_k, s_k, z_k), None, None, None, qmin, qmax, s, z) for k], -1)
+
+    -- a holder's float32 output is ``dequantize_codes`` of its codes bit for bit and ``torch.cat`` only moves data, so these are
+    the codes the holder behind ``torch.cat`` of the operand holders' outputs gives.  GPU tensors with every ``C_k % 16 == 0``
+    and at most 8 operands take one launch of mctq_codes_concat_nhwc (1 byte read, 1 byte written per element; an operand in the
+    output's own form is copied); anything else on the GPU, and every CPU tensor, evaluates the expression above with torch ops,
+    which the kernel matches byte for byte."""
+    operands = [(c, float(s), int(z)) for c, s, z in operands]
+    if not operands:
+        raise ValueError("codes_concat needs at least one operand")
+    o_scale, o_zp, qmin, qmax = float(out_form[0]), int(out_form[1]), int(out_form[2]), int(out_form[3])
+    tdt, ocode = _code_dtype(qmin, qmax)
+    first = operands[0][0]
+    for c, s, z in operands:
+        if not isinstance(c, torch.Tensor) or c.dtype not in (torch.int8, torch.uint8) or c.dim() < 1:
+            raise TypeError("codes_concat takes int8 / uint8 codes [.., C]")
+        if c.device != first.device or c.shape[:-1] != first.shape[:-1]:
+            raise RuntimeError(f"codes_concat: operands must share the device and the leading shape, got {tuple(c.shape)} on "
+                               f"{c.device} next to {tuple(first.shape)} on {first.device}")
+        lo, hi = (0, 255) if c.dtype == torch.uint8 else (-128, 127)
+        if not lo <= z <= hi:
+            raise ValueError(f"codes_concat: the zero point {z} is no {c.dtype} code")
+        if not 0.0 < s < float("inf"):
+            raise ValueError("codes_concat: an operand's scale must be finite and positive")
+    if not 0.0 < o_scale < float("inf"):
+        raise ValueError("codes_concat: the output's scale must be finite and positive")
+    lead, total = tuple(first.shape[:-1]), sum(c.shape[-1] for c, _, _ in operands)
+    o_lo, o_hi = (0, 255) if tdt == torch.uint8 else (-128, 127)
+    if (first.is_cuda and len(operands) <= _CONCAT_MAX and all(c.shape[-1] > 0 and c.shape[-1] % 16 == 0 for c, _, _ in operands)
+            and o_lo <= o_zp <= o_hi):
+        pixels = math.prod(lead)
+        keep = [c if c.is_contiguous() else c.contiguous() for c, _, _ in operands]     # named: they must outlive the launch
+        out = torch.empty(lead + (total,), dtype=tdt, device=first.device)
+        items = (native.ConcatItem * len(keep))()
+        for it, c, (_, s, z) in zip(items, keep, operands):
+            it.codes, it.channels, it.code_dtype, it.zero_point, it.scale = c.data_ptr(), c.shape[-1], _code_of(c), z, s
+        _gpu_call("mctq_codes_concat_nhwc", first, items, len(keep), out.data_ptr(), ocode, pixels, o_scale, o_zp, qmin, qmax)
+        return out
+    if not first.is_cuda:
+        _cpu_route_allowed()
+    with torch.no_grad():
+        parts = [fq_codes(dequantize_codes(c, s, z), None, None, None, qmin, qmax, o_scale, o_zp) for c, s, z in operands]
+        return torch.cat(parts, -1).contiguous()
 
 
 def make_lut_table(lut_values, mult: float, cmin: float, cmax: float, device):
