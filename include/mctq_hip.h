@@ -75,6 +75,9 @@ extern "C" {
 /* v10 (additive, the version number stays): + mctq_codes_concat_nhwc, torch.cat along the channels on NHWC activation codes in the
  * form of the holder behind it (Inception / Fire / skip-connection blocks stay on codes), + tuning key "concat_copy"; no existing
  * signature or result changed. */
+/* v10 (additive, the version number stays): + mctq_codes_avgpool_nhwc, torch.nn.AvgPool2d / global average pooling on NHWC activation
+ * codes in the form of the holder behind the pool (classifier heads and SE squeezes stay on codes), + tuning key "avgpool_form"; no
+ * existing signature or result changed. */
 #define MCTQ_ABI_VERSION 10
 #define MCTQ_E_ARG (-10001)
 
@@ -595,6 +598,40 @@ int mctq_codes_concat_nhwc(const mctq_concat_item* items, int32_t count, void* o
                            float scale, int32_t zero_point, int32_t quant_min, int32_t quant_max, void* stream);
 
 /*
+ * Average pooling on activation codes (extension; the reference runs ATen's float32 average pool on the holder's output and
+ * the holder behind it on the result): codes [batch][height][width][channels] (NHWC; int8 -- MCTQ_CODE_I8 -- or uint8,
+ * MCTQ_CODE_U8) of the form (scale, zero_point) -> pooled [batch][out_height][out_width][channels] in the form
+ * (y_code_dtype, y_scale, y_zero_point, y_quant_min, y_quant_max), DEVICE pointers, 16-byte aligned; torch.nn.AvgPool2d's
+ * kernel, stride, padding, ceil_mode, count_include_pad and divisor_override (0 = none).  Per output element
+ *     S    = sum over the window's taps inside the image of (code - zero_point)                int32, exact
+ *     div  = divisor_override, or with count_include_pad (min(h0 + kh, H + pad_h) - h0) * (min(w0 + kw, W + pad_w) - w0)
+ *            with h0 = oy * stride_h - pad_h (PyTorch's pool_size), or else the number of taps inside the image
+ *     v    = fma(float(S), scale, +0)                                                         one float32 rounding
+ *     m    = v / float(div)                                                                   IEEE float32 division
+ *     out  = clamp(rint(m * (1.0f / y_scale)) + y_zero_point, y_quant_min, y_quant_max)       NaN -> y_quant_min
+ * float(S) is exact: a window has at most 65536 taps and 255 * 65536 < 2^24.  A window without a tap inside the image (no
+ * geometry PyTorch accepts has one) gives m = 0.0.  Where scale and every div are powers of two this is bit for bit the code
+ * the holder behind any float32 average pool of the dequantized codes gives; elsewhere it is the exact mean rounded twice.
+ * Two forms with the same bytes (the sum is an integer): "lane", one lane per 16-channel chunk of an output pixel as in
+ * mctq_codes_maxpool_nhwc, and "split", the taps of a window divided among the lanes of one workgroup with int32 partial
+ * sums meeting in LDS, for few and large windows.  The launcher chooses; tuning key "avgpool_form" forces one.
+ * A lane reads only chunks of images below `batch` and writes only chunks below batch * Ho * Wo * channels / 16.
+ * MCTQ_E_ARG with a mctq_last_error text, before anything is launched, for: a negative extent; kernel size or stride below
+ * 1; negative padding; padding above half the kernel size; kh * kw > 65536; a negative divisor_override; channels % 16 != 0;
+ * a bad code_dtype or y_code_dtype; a zero_point that is no code of the input's type; a scale or y_scale that is not finite
+ * and positive; y_quant_min > y_quant_max or a domain outside the output type; a padded extent plus kernel above 2^31 - 1;
+ * Ho <= 0 or Wo <= 0; out_height / out_width other than Ho / Wo; a non-empty batch of images without pixels; more than
+ * 2^31 - 1 output pixels, or more than 2^32 - 1 16-channel chunks of output (split the batch); NULL or misaligned pointers of
+ * a non-empty problem.  batch == 0 or channels == 0 returns 0 without a launch.  mctq_last_launch names the launch
+ * "codes_avgpool", op "u8 avg lane" / "u8 avg split" / "i8 avg lane" / "i8 avg split".
+ */
+int mctq_codes_avgpool_nhwc(const void* codes, void* pooled, int32_t code_dtype, int32_t zero_point, float scale, int64_t batch,
+                            int64_t height, int64_t width, int64_t channels, int32_t kh, int32_t kw, int32_t stride_h,
+                            int32_t stride_w, int32_t pad_h, int32_t pad_w, int32_t ceil_mode, int32_t count_include_pad,
+                            int32_t divisor_override, int64_t out_height, int64_t out_width, int32_t y_code_dtype, float y_scale,
+                            int32_t y_zero_point, int32_t y_quant_min, int32_t y_quant_max, void* stream);
+
+/*
  * Depthwise convolution on activation codes (groups == channels, channel multiplier 1; extension, the reference has no
  * counterpart): what a wrapped depthwise torch.nn.Conv2d computes on fake-quantized operands, evaluated on the codes.
  *     acc[b][oy][ox][c] = sum over the taps (ky, kx) inside the image of
@@ -840,6 +877,8 @@ int mctq_qlinear_i8_res(const void* a_codes, int32_t a_code_dtype, int32_t a_zer
  *                  Launches with a zero-point table and 16-bit storage are never eligible.
  *   key "concat_copy" : mctq_codes_concat_nhwc, operands in the output's own form: 1 (default) = their lanes store what they loaded,
  *                  0 = they run the requantization arithmetic like every other operand (the bytes are the same: the tests' proof)
+ *   key "avgpool_form" : mctq_codes_avgpool_nhwc: 0 (default) = the launcher chooses between the lane and the split form, 1 = the lane
+ *                  form, 2 = the split form (the bytes are the same: the sums are integers)
  * Only variants a default dispatcher can select are instantiated; every value of every key is exercised by the GPU tests.
  * Returns 0, or MCTQ_E_ARG for an unknown key/value.  Numerical results never depend on it.
  */

@@ -66,6 +66,18 @@ behind the concatenation gives are the operands' codes requantized one by one in
 (``mctq_codes_concat_nhwc``) does that in one launch, 1 byte read and 1 written per element, and the layers and pools behind
 the holder become consumers of its codes; with ``stay_on_codes=True`` the branch convolutions emit the operands' codes.
 
+An average pool between two holders stays on codes with ``avg_pools=True`` (both rewrites): holder A -> average pool -> holder B,
+through at most one flatten behind a global pool, becomes one ``QuantizedAvgPool2d`` (``mctq_codes_avgpool_nhwc``) -- classifier
+heads (``AdaptiveAvgPool2d(1)`` / ``x.mean((2, 3))`` -> holder -> flatten -> Linear), SE squeezes, Inception's 3 x 3 branch.  The
+contract: S, the sum of ``code - zp_a`` over the window's taps inside the image, is an exact integer (at most 65536 taps:
+255 * 65536 < 2^24), and then in float32, each step rounded once, ``v = S * scale_a``, ``m = v / div`` with PyTorch's divisor,
+``code = clamp(rint(m * (1 / scale_b)) + zp_b, qmin, qmax)``.  Exactness: where ``scale_a`` and every divisor are powers of two
+these are bit for bit the codes B gives any float32 average pool of A's output; everywhere else the exact mean rounded twice,
+which can differ from a float32 chain by one code, and only next to a rounding tie (ATen's own average pools do not agree
+with each other in the last bit).  Limits: per-tensor quantizers of at most 8 bits whose zero points are codes of their type;
+the kernel takes C % 16 == 0 and at most 65536 taps, anything else and CPU tensors run the same contract with torch ops.
+Measured / not measured: see the README paragraph and ``profiles/EXPERIMENTS.md``.
+
 The four modules derive from ``IntegerConsumer``, which owns what they share: the checks of the quantizers and of the float32
 weight and bias, the cache of the weight's codes, the step from ``forward``'s input to activation codes, ``from_wrapper`` and
 the ``emit_codes_for`` / ``emit_clamp`` output form.  ``QuantizedLinear`` is the product over ``[O, K]`` rows; ``QuantizedConv1x1``
@@ -840,6 +852,121 @@ class QuantizedMaxPool2d(nn.Module):
         return y.permute(0, 3, 1, 2)
 
 
+def _code_form(q):
+    """(scale, zero_point, qmin, qmax) of a quantizer of at most 8 bits whose codes and zero point are 8-bit codes of one type."""
+    if getattr(q, "num_bits", 9) > 8:
+        raise NotImplementedError("codes wider than 8 bits")
+    scale, zp, qmin, qmax = _activation_code_params(q)
+    tdt, _ = ops._code_dtype(qmin, qmax)                       # (raises for a domain that is no 8-bit code)
+    lo, hi = (0, 255) if tdt == torch.uint8 else (-128, 127)
+    if not lo <= zp <= hi:
+        raise NotImplementedError(f"the zero point {zp} is no {tdt} code")
+    if not 0.0 < scale < math.inf:
+        raise ValueError("the scale must be finite and positive")
+    return scale, zp, qmin, qmax
+
+
+class QuantizedAvgPool2d(nn.Module):
+    """``activation holder A -> average pool -> activation holder B`` on integer codes, for the integer consumers behind B.
+    A's float32 output is ``float(code - zp_a) * scale_a`` bit for bit, so the sum of a window is ``scale_a`` times the exact
+    integer sum S of ``code - zp_a`` over its taps inside the image (a padded tap is 0.0 and adds nothing), and B codes the mean:
+
+        code = clamp(rint((float32(S) * scale_a) / float32(div) * (1 / scale_b)) + zp_b, qmin, qmax)
+
+    with ``div`` PyTorch's divisor (``divisor_override``, ``pool_size`` with ``count_include_pad``, or the taps inside the
+    image) -- ``ops.codes_avgpool`` (``mctq_codes_avgpool_nhwc``): 1 byte read per tap and 1 written per output element in one
+    launch, where A writes 4, ATen's pool reads 4 and writes 4 and B reads 4 again.  Where ``scale_a`` and every ``div`` are
+    powers of two these are bit for bit the codes B gives any float32 average pool of A's output; elsewhere the exact mean
+    rounded twice, which differs from a float32 chain by at most one code next to a rounding tie (ATen's own average pools do
+    not agree with each other in the last bit either).
+
+    ``pool``: an ``nn.AvgPool2d`` (ints or pairs, padding at most half the kernel size), an ``nn.AdaptiveAvgPool2d`` of output
+    size 1 -- the kernel is then the input's H x W at forward -- or ``QuantizedAvgPool2d.GLOBAL``, the same global pool
+    without a module (``x.mean((2, 3))``).  ``forward`` takes A's codes (int8 / uint8 of A's code type, NCHW-shaped and
+    NHWC-stored as the consumers and joins emit them) or a float32 [N, C, H, W] tensor, which it quantizes with A's
+    parameters (``ops.fq_codes_nhwc``); it returns B's codes NCHW-shaped and NHWC-stored, or with ``flatten=True`` (global pools
+    only) as [N, C] rows, which a ``QuantizedLinear`` of B's quantizer takes as they are.  ``activation_code_params`` is the INPUT
+    form, what a producer in front emits (the meaning it has for ``IntegerConsumer`` and ``QuantizedMaxPool2d``);
+    ``output_code_params`` is B's form.  It has no weights and is no ``IntegerConsumer``.  GPU tensors whose C is no multiple
+    of 16, windows of more than 65536 taps and CPU tensors take torch ops with the same bytes."""
+
+    GLOBAL = "global"
+
+    def __init__(self, pool, in_quantizer, out_quantizer, flatten: bool = False):
+        super().__init__()
+        if isinstance(pool, nn.AdaptiveAvgPool2d) and not self.eligible(pool):
+            raise TypeError(f"QuantizedAvgPool2d takes torch.nn.AdaptiveAvgPool2d layers of output size 1 only, got {pool.output_size!r}")
+        if not self.eligible(pool):
+            raise TypeError("QuantizedAvgPool2d takes torch.nn.AvgPool2d layers, their kernel_size, stride and padding ints or pairs, "
+                            "padding at most half the kernel size, divisor_override None or a positive int; "
+                            "torch.nn.AdaptiveAvgPool2d layers of output size 1; or QuantizedAvgPool2d.GLOBAL")
+        self.in_quantizer, self.out_quantizer = in_quantizer, out_quantizer
+        self._a_scale, self._a_zp, self._a_qmin, self._a_qmax = _code_form(in_quantizer)
+        self._out_form = _code_form(out_quantizer)
+        self.global_pool = type(pool) is not nn.AvgPool2d
+        self.flatten = bool(flatten)
+        if self.flatten and not self.global_pool:
+            raise ValueError("flatten=True needs a global pool: a windowed pool's output is not 1 x 1")
+        self.kernel_size = self.stride = None
+        self.padding, self.ceil_mode, self.count_include_pad, self.divisor_override = (0, 0), False, True, None
+        if not self.global_pool:
+            self.kernel_size = ops._pair(pool.kernel_size, "kernel_size", "QuantizedAvgPool2d")
+            self.stride = self.kernel_size if pool.stride is None else ops._pair(pool.stride, "stride", "QuantizedAvgPool2d")
+            self.padding = ops._pair(pool.padding, "padding", "QuantizedAvgPool2d")
+            self.ceil_mode, self.count_include_pad = bool(pool.ceil_mode), bool(pool.count_include_pad)
+            self.divisor_override = pool.divisor_override
+
+    @staticmethod
+    def eligible(pool) -> bool:
+        if isinstance(pool, str):
+            return pool == QuantizedAvgPool2d.GLOBAL
+        if type(pool) is nn.AdaptiveAvgPool2d:
+            size = pool.output_size
+            return (isinstance(size, int) and not isinstance(size, bool) and size == 1) or \
+                (isinstance(size, (tuple, list)) and len(size) == 2 and _ints_or_pair(tuple(size)) and tuple(size) == (1, 1))
+        if type(pool) is not nn.AvgPool2d or not isinstance(pool.ceil_mode, bool) or not isinstance(pool.count_include_pad, bool):
+            return False
+        div = pool.divisor_override
+        if div is not None and (not isinstance(div, int) or isinstance(div, bool) or div < 1):
+            return False
+        stride = pool.kernel_size if pool.stride is None else pool.stride
+        if not all(_ints_or_pair(v) for v in (pool.kernel_size, stride, pool.padding)):
+            return False
+        k, s, p = (ops._pair(v, "", "QuantizedAvgPool2d") for v in (pool.kernel_size, stride, pool.padding))
+        return min(*k, *s) >= 1 and min(p) >= 0 and p[0] <= k[0] // 2 and p[1] <= k[1] // 2
+
+    def activation_code_params(self):
+        """(scale, zero_point, qmin, qmax) of the codes this pool READS (holder A's): what ``emit_codes_for`` of the layer in
+        front takes."""
+        return self._a_scale, self._a_zp, self._a_qmin, self._a_qmax
+
+    def output_code_params(self):
+        """(scale, zero_point, qmin, qmax) of the codes ``forward`` returns (holder B's): what the consumers behind read."""
+        return self._out_form
+
+    def extra_repr(self) -> str:
+        if self.global_pool:
+            return f"global, flatten={self.flatten}"
+        return (f"kernel_size={self.kernel_size}, stride={self.stride}, padding={self.padding}, ceil_mode={self.ceil_mode}, "
+                f"count_include_pad={self.count_include_pad}, divisor_override={self.divisor_override}")
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if x.dim() != 4:
+            raise RuntimeError(f"expected [N, C, H, W], got {tuple(x.shape)}")
+        if x.dtype in (torch.uint8, torch.int8):
+            if x.dtype != ops._code_dtype(self._a_qmin, self._a_qmax)[0]:
+                raise TypeError(f"activation codes of type {x.dtype} do not match this pool's input quantizer")
+            codes = x.permute(0, 2, 3, 1)
+            codes = codes if codes.is_contiguous() else codes.contiguous()
+        elif x.dtype == torch.float32:
+            codes = ops.fq_codes_nhwc(x, self._a_qmin, self._a_qmax, self._a_scale, self._a_zp)
+        else:
+            raise TypeError(f"QuantizedAvgPool2d takes float32 tensors or activation codes, got {x.dtype}")
+        y = ops.codes_avgpool(codes, (self._a_scale, self._a_zp), self._out_form, self.kernel_size, self.stride, self.padding,
+                              self.ceil_mode, self.count_include_pad, self.divisor_override)
+        return y.reshape(y.shape[0], y.shape[3]) if self.flatten else y.permute(0, 3, 1, 2)
+
+
 class QuantizedConcat(nn.Module):
     """``activation holders -> torch.cat(..., dim=1) -> activation holder`` on integer codes, for the integer consumers and
     pools behind that holder.  An operand holder's float32 output is ``float(code - zp_i) * scale_i`` bit for bit
@@ -874,14 +1001,7 @@ class QuantizedConcat(nn.Module):
     @staticmethod
     def _form_of(q):
         """(scale, zero_point, qmin, qmax) of a quantizer whose codes and zero point are 8-bit codes of one type."""
-        scale, zp, qmin, qmax = _activation_code_params(q)
-        tdt, _ = ops._code_dtype(qmin, qmax)                   # (raises for a domain that is no 8-bit code)
-        lo, hi = (0, 255) if tdt == torch.uint8 else (-128, 127)
-        if not lo <= zp <= hi:
-            raise NotImplementedError(f"the zero point {zp} is no {tdt} code")
-        if not 0.0 < scale < math.inf:
-            raise ValueError("the scale must be finite and positive")
-        return scale, zp, qmin, qmax
+        return _code_form(q)
 
     def operand_code_params(self, i: int):
         """(scale, zero_point, qmin, qmax) of the codes operand ``i`` is read as."""
@@ -953,7 +1073,7 @@ def _consumer_for(wrapper, activation_quantizer, uniform_weights=False, convolut
 
 
 # what reads the activation codes of the module in front as they are
-_CODE_READERS = (IntegerConsumer, QuantizedMaxPool2d)
+_CODE_READERS = (IntegerConsumer, QuantizedMaxPool2d, QuantizedAvgPool2d)
 
 
 class _FusedAway(nn.Identity):
@@ -1028,6 +1148,8 @@ def _pool_plan(node, mods, quantizer, consumer_for):
 def _install_pool(gm, mods, node, plan, source) -> int:
     """Makes ``node``, the pool's call, a call of ``plan``'s QuantizedMaxPool2d on ``source`` (codes, or the float32 tensor the
     holder read) and its users the consumers of the plan; returns their number."""
+    if len(plan) == 3:
+        return _install_avg_pool(gm, mods, node, plan, source)
     qpool, taken = plan
     name = (node.target.replace(".", "_") if node.op == "call_module" else node.name) + "_qpool"
     gm.add_submodule(name, qpool)
@@ -1035,6 +1157,151 @@ def _install_pool(gm, mods, node, plan, source) -> int:
     node.op, node.target, node.args, node.kwargs = "call_module", name, (source,), {}
     for user, fused in taken:
         _install_consumer(gm, mods, user, fused)
+    return len(taken)
+
+
+def _const_args(node, names):
+    """The arguments of ``node`` behind its first (tensor) operand by name -- ``names`` in positional order -- if every one of
+    them is a known name given once and a constant, else None."""
+    from torch.fx import Node
+    rest = node.args[1:]
+    if len(rest) > len(names) or set(node.kwargs) - set(names[len(rest):]):
+        return None
+    given = dict(zip(names, rest), **node.kwargs)
+    return None if any(isinstance(v, Node) for v in given.values()) else given
+
+
+def _avg_pool_of(node, mods):
+    """``(pool, flat)`` if ``node`` is an average pool of its one tensor operand that QuantizedAvgPool2d can take: a call of an
+    ``nn.AvgPool2d`` / ``nn.AdaptiveAvgPool2d(1)`` module, ``F.avg_pool2d`` with constant arguments, ``F.adaptive_avg_pool2d(x, 1)``,
+    or ``x.mean(...)`` / ``torch.mean(x, ...)`` over the constant dims (2, 3) / (-2, -1) in either order with a constant
+    ``keepdim`` -- ``pool`` what the class takes, ``flat`` True where the result already is [N, C] (``keepdim=False``).  Else None."""
+    from torch.fx import Node
+    F = torch.nn.functional
+    if not node.args or not isinstance(node.args[0], Node):
+        return None
+    pool, flat = None, False
+    if node.op == "call_module":
+        if len(node.args) == 1 and not node.kwargs and isinstance(mods.get(node.target), (nn.AvgPool2d, nn.AdaptiveAvgPool2d)):
+            pool = mods.get(node.target)
+    elif node.op == "call_function" and node.target is F.avg_pool2d:
+        given = _const_args(node, ("kernel_size", "stride", "padding", "ceil_mode", "count_include_pad", "divisor_override"))
+        if given is None or "kernel_size" not in given:
+            return None
+        if not all(isinstance(given.get(k, False), bool) for k in ("ceil_mode", "count_include_pad")):
+            return None
+        try:
+            pool = nn.AvgPool2d(**given)
+        except (TypeError, ValueError):
+            return None
+    elif node.op == "call_function" and node.target is F.adaptive_avg_pool2d:
+        given = _const_args(node, ("output_size",))
+        if given is None or "output_size" not in given:
+            return None
+        pool = nn.AdaptiveAvgPool2d(given["output_size"])
+    elif (node.op == "call_method" and node.target == "mean") or (node.op == "call_function" and node.target is torch.mean):
+        given = _const_args(node, ("dim", "keepdim"))
+        if given is None or not isinstance(given.get("keepdim", False), bool):
+            return None
+        dim = given.get("dim")
+        if not isinstance(dim, (tuple, list)) or tuple(dim) not in ((2, 3), (3, 2), (-2, -1), (-1, -2)) \
+                or any(isinstance(d, bool) for d in dim):
+            return None
+        pool, flat = QuantizedAvgPool2d.GLOBAL, not given.get("keepdim", False)
+    if pool is None or not QuantizedAvgPool2d.eligible(pool):
+        return None
+    return pool, flat
+
+
+def _is_flatten(node, mods) -> bool:
+    """``node`` flattens its one tensor operand from dimension 1 on: ``nn.Flatten()`` with the defaults, ``torch.flatten(x, 1)`` or
+    ``x.flatten(1)`` (``end_dim`` -1 where given).  ``view`` / ``reshape`` are not recognised: their sizes are not constants."""
+    from torch.fx import Node
+    if not node.args or not isinstance(node.args[0], Node):
+        return False
+    if node.op == "call_module":
+        m = mods.get(node.target)
+        return type(m) is nn.Flatten and m.start_dim == 1 and m.end_dim == -1 and len(node.args) == 1 and not node.kwargs
+    if (node.op == "call_function" and node.target is torch.flatten) or (node.op == "call_method" and node.target == "flatten"):
+        given = _const_args(node, ("start_dim", "end_dim"))
+        if given is None:
+            return False
+        start, end = given.get("start_dim", 0), given.get("end_dim", -1)
+        return all(isinstance(v, int) and not isinstance(v, bool) for v in (start, end)) and start == 1 and end == -1
+    return False
+
+
+def _avg_pool_plan(node, mods, quantizer, consumer_for):
+    """``node`` a user of a plain holder A with ``quantizer``: (QuantizedAvgPool2d, [(user, its consumer)], [nodes that leave]) if
+    it is an average pool of A's output (``_avg_pool_of``) whose one user -- through at most one flatten (``_is_flatten``), and
+    that behind a global pool only, where H = W = 1 is known without shapes -- is a plain holder B, every user of which is a
+    wrapped layer ``consumer_for`` can take, fed by B alone (a 4-D tensor never feeds a QuantizedLinear, rows feed nothing
+    else), or, behind a global pool, a flatten all of whose users are such wrapped ``nn.Linear`` layers.  Else None: a float32
+    user of the pool or of B, an activation between them, no holder B.  B's users all see rows or all see 4-D tensors."""
+    found = _avg_pool_of(node, mods)
+    if found is None or len(node.users) != 1:
+        return None
+    pool, flat = found
+    is_global = type(pool) is not nn.AvgPool2d
+    gone, nxt, last = [], next(iter(node.users)), node
+    if not flat and is_global and _is_flatten(nxt, mods) and len(nxt.users) == 1:
+        gone, flat, last, nxt = [nxt], True, nxt, next(iter(nxt.users))
+    holder = _module_of(nxt, mods)
+    if not _plain_holder(holder) or nxt.kwargs or nxt.args != (last,) or not nxt.users:
+        return None
+    out_quantizer = holder.activation_holder_quantizer
+
+    def consumers_of(src, rows):
+        taken = []
+        for user in src.users:
+            wrapper = _module_of(user, mods)
+            if not isinstance(wrapper, PytorchQuantizationWrapper) or user.kwargs or user.args != (src,):
+                return None
+            fused = consumer_for(wrapper, out_quantizer)
+            if fused is None or (type(fused) is QuantizedLinear) != rows:
+                return None
+            taken.append((user, fused))
+        return taken
+
+    if flat:
+        taken = consumers_of(nxt, True)
+    elif is_global and all(_is_flatten(u, mods) and u.args[0] is nxt and u.users for u in nxt.users):
+        taken, flat = [], True
+        for u in nxt.users:
+            behind = consumers_of(u, True)
+            if behind is None:
+                return None
+            taken += behind
+        gone = gone + list(nxt.users)
+    else:
+        taken = consumers_of(nxt, False)
+    if not taken:
+        return None
+    try:
+        return QuantizedAvgPool2d(pool, quantizer, out_quantizer, flatten=flat), taken, gone + [nxt]
+    except (TypeError, ValueError, NotImplementedError):
+        return None
+
+
+def _install_avg_pool(gm, mods, node, plan, source) -> int:
+    """Makes ``node``, the pool's call, a call of ``plan``'s QuantizedAvgPool2d on ``source`` (holder A's codes, or the float32
+    tensor A read), the wrapped layers of the plan consumers of its output, and erases holder B and the flattens; returns the
+    number of consumers."""
+    qpool, taken, gone = plan
+    name = (node.target.replace(".", "_") if node.op == "call_module" else node.name) + "_qavgpool"
+    gm.add_submodule(name, qpool)
+    mods[name] = qpool
+    node.op, node.target, node.args, node.kwargs = "call_module", name, (source,), {}
+    for user, fused in taken:
+        _install_consumer(gm, mods, user, fused)
+        user.args = (node,)
+    while gone:                                              # users first
+        free = [g for g in gone if not g.users]
+        if not free:
+            raise RuntimeError("a node of the average pool's chain still has users")
+        for g in free:
+            gm.graph.erase_node(g)
+            gone.remove(g)
     return len(taken)
 
 
@@ -1129,12 +1396,13 @@ def _add_operands(node):
     return tuple(node.args) if ok else None
 
 
-def _join_shared_holders(gm, mods, consumer_for, pools: bool = False) -> int:
+def _join_shared_holders(gm, mods, consumer_for, pools: bool = False, avg_pools: bool = False) -> int:
     """``fuse_linear_consumers_fx(shared_holders=True)``: every plain holder with wrapped layers among its users that
     ``consumer_for(wrapper, quantizer)`` can take becomes a QuantizedJoin, unless it is a lone holder -> layer pair with
     nothing in front to absorb (the pair rewrite's).  With ``pools`` a max pool among the users that can run on codes
     (``_pool_plan``) reads the join's codes as well, as a QuantizedMaxPool2d in front of its own consumers; a lone holder ->
-    pool pair with nothing to absorb is left to ``_pool_lone_holders``.  Returns the number of wrapped layers replaced."""
+    pool pair with nothing to absorb is left to ``_pool_lone_holders``.  With ``avg_pools`` the same holds for an average pool
+    in front of a second holder (``_avg_pool_plan``), as a QuantizedAvgPool2d.  Returns the number of wrapped layers replaced."""
     import operator
     from torch.fx import Node
     replaced = 0
@@ -1152,8 +1420,9 @@ def _join_shared_holders(gm, mods, consumer_for, pools: bool = False) -> int:
                 if fused is not None:
                     taken.append((user, fused))
         pooled = []                                          # P: (pool node, its plan)
-        if pools:
-            plans = ((user, _pool_plan(user, mods, holder.activation_holder_quantizer, consumer_for)) for user in node.users)
+        if pools or avg_pools:
+            plans = ((user, _any_pool_plan(user, mods, holder.activation_holder_quantizer, consumer_for, pools, avg_pools))
+                     for user in node.users)
             pooled = [(user, plan) for user, plan in plans if plan is not None]
         if not taken and not pooled:
             continue
@@ -1191,9 +1460,18 @@ def _join_shared_holders(gm, mods, consumer_for, pools: bool = False) -> int:
     return replaced
 
 
-def _pool_lone_holders(gm, mods, consumer_for) -> int:
+def _any_pool_plan(node, mods, quantizer, consumer_for, pools: bool, avg_pools: bool):
+    """``_pool_plan`` (with ``pools``) or else ``_avg_pool_plan`` (with ``avg_pools``) of ``node``, or None."""
+    plan = _pool_plan(node, mods, quantizer, consumer_for) if pools else None
+    if plan is None and avg_pools:
+        plan = _avg_pool_plan(node, mods, quantizer, consumer_for)
+    return plan
+
+
+def _pool_lone_holders(gm, mods, consumer_for, pools: bool = True, avg_pools: bool = False) -> int:
     """``fuse_linear_consumers_fx(pools=True)``, the pair: a plain holder whose only user is a max pool that can run on codes
     (``_pool_plan``) leaves the graph, the QuantizedMaxPool2d that replaces the pool quantizes the holder's input itself.
+    With ``avg_pools`` likewise for an average pool in front of a second holder (``_avg_pool_plan``) and its QuantizedAvgPool2d.
     Returns the number of wrapped layers replaced."""
     from torch.fx import Node
     replaced = 0
@@ -1204,7 +1482,7 @@ def _pool_lone_holders(gm, mods, consumer_for) -> int:
         if not _plain_holder(holder):
             continue
         user = next(iter(node.users))
-        plan = _pool_plan(user, mods, holder.activation_holder_quantizer, consumer_for)
+        plan = _any_pool_plan(user, mods, holder.activation_holder_quantizer, consumer_for, pools, avg_pools)
         if plan is None:
             continue
         replaced += _install_pool(gm, mods, user, plan, node.args[0])
@@ -1471,7 +1749,8 @@ def _fuse_residuals_into_producers(gm, mods) -> int:
 
 
 def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights: bool = False,
-                          convolutions: bool = False, depthwise: bool = False, pools: bool = False) -> int:
+                          convolutions: bool = False, depthwise: bool = False, pools: bool = False,
+                          avg_pools: bool = False) -> int:
     """In every ``nn.Sequential`` of ``model``: an activation holder directly followed by a wrapped ``nn.Linear`` with
     a symmetric, power-of-two or LUT weights quantizer (int8 codebook values, at most 256 entries) becomes (Identity,
     QuantizedLinear); a wrapped pointwise ``nn.Conv2d`` likewise becomes a QuantizedConv1x1.  Returns the number of pairs
@@ -1504,9 +1783,39 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
     monotone in the value, so the pooled codes are bit for bit the codes of the float32 pool of the holder's output, and the model
     rewritten with ``pools=True`` returns, bit for bit, what the same rewrite without it returns wherever the float32 products of
     the layers behind the pools are exact; otherwise it differs by the accumulation rounding of those products, like every pair
-    that becomes a consumer."""
+    that becomes a consumer.
+
+    ``avg_pools=True`` also takes (holder A, average pool, holder B, wrapped convolution the consumer can take) and (holder A,
+    global average pool, holder B, ``nn.Flatten()``, wrapped ``nn.Linear``): they become (Identity, QuantizedAvgPool2d, Identity,
+    [Identity,] consumer), the pool and B running as one launch on A's codes (``mctq_codes_avgpool_nhwc``) and the consumer
+    taking B's codes.  The pool is an ``nn.AvgPool2d`` (padding at most half the kernel size) or an ``nn.AdaptiveAvgPool2d`` of
+    output size 1; the flatten form needs the global pool.  With ``chain=True`` a consumer in front emits A's codes.  Counted
+    as one pair.  Where A's scale and every window's divisor are powers of two the codes are bit for bit those of the float32
+    chain, elsewhere the exact mean rounded twice (``QuantizedAvgPool2d``)."""
     replaced = 0
     for seq in [m for m in model.modules() if isinstance(m, nn.Sequential)]:
+        for i in range(len(seq) - 3 if avg_pools else 0):
+            holder, pool, second = seq[i], seq[i + 1], seq[i + 2]
+            if not _plain_holder(holder) or not _plain_holder(second) or isinstance(pool, str) or not QuantizedAvgPool2d.eligible(pool):
+                continue
+            flat = type(seq[i + 3]) is nn.Flatten and seq[i + 3].start_dim == 1 and seq[i + 3].end_dim == -1
+            if flat and (type(pool) is nn.AvgPool2d or i + 4 >= len(seq)):
+                continue
+            wrapper = seq[i + 4] if flat else seq[i + 3]
+            if not isinstance(wrapper, PytorchQuantizationWrapper):
+                continue
+            fused = _consumer_for(wrapper, second.activation_holder_quantizer, uniform_weights, convolutions, depthwise)
+            if fused is None or (type(fused) is QuantizedLinear) != flat:
+                continue
+            try:
+                qpool = QuantizedAvgPool2d(pool, holder.activation_holder_quantizer, second.activation_holder_quantizer, flatten=flat)
+            except (TypeError, ValueError, NotImplementedError):
+                continue
+            seq[i], seq[i + 1], seq[i + 2] = _FusedAway(), qpool, _FusedAway()
+            if flat:
+                seq[i + 3] = _FusedAway()
+            seq[i + 4 if flat else i + 3] = fused
+            replaced += 1
         for i in range(len(seq) - 2 if pools else 0):
             holder, pool, wrapper = seq[i], seq[i + 1], seq[i + 2]
             if not _plain_holder(holder) or not QuantizedMaxPool2d.eligible(pool) or not isinstance(wrapper, PytorchQuantizationWrapper):
@@ -1541,7 +1850,7 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
 def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weights: bool = False,
                              convolutions: bool = False, depthwise: bool = False, shared_holders: bool = False,
                              stay_on_codes: bool = False, pools: bool = False, fused_residuals: bool = False,
-                             concats: bool = False):
+                             concats: bool = False, avg_pools: bool = False):
     """The same rewrite on an arbitrary module graph (MCT-exported models are not ``nn.Sequential``): traces ``model``
     with torch.fx keeping wrappers and holders as leaves, and wherever an activation holder's ONLY consumer is a
     wrapped ``nn.Linear`` the integer consumer can take (symmetric, power-of-two or LUT weights, and with
@@ -1615,7 +1924,30 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
     holder behind the float32 concatenation, for any channel counts (counts that are no multiple of 16 take torch ops), and
     the model rewritten with ``concats=True`` returns, bit for bit, what the same rewrite without it returns wherever the
     float32 products of the layers behind the concatenation are exact; otherwise it differs by the accumulation rounding of
-    those products, like every wrapped layer that becomes a consumer."""
+    those products, like every wrapped layer that becomes a consumer.
+
+    ``avg_pools=True`` (needs no other switch) keeps an average pool between two holders on codes: classifier heads, SE squeezes,
+    Inception's pooling branch.  The candidate is a plain holder A one of whose users is an average pool of its output -- a call
+    of an ``nn.AvgPool2d`` (padding at most half the kernel size) or ``nn.AdaptiveAvgPool2d`` of output size 1, ``F.avg_pool2d``
+    with constant arguments, ``F.adaptive_avg_pool2d(x, 1 | (1, 1))``, or ``x.mean(...)`` / ``torch.mean(x, ...)`` over the constant
+    dims (2, 3) or (-2, -1) in either order with a constant ``keepdim`` (``keepdim=False`` is a global pool that is already flat).
+    Through at most one flatten -- ``nn.Flatten()`` with the defaults, ``torch.flatten(x, 1)`` or ``x.flatten(1)``, accepted only
+    behind a global pool, where H = W = 1 is known without shapes -- the pool's one user is a plain holder B, and every user of B
+    is a wrapped layer the consumer can take under the other switches, fed by B alone (never a QuantizedLinear on an unflattened
+    4-D tensor), or such a flatten all of whose users are wrapped ``nn.Linear`` layers the consumer can take.  The pool, B and
+    the flatten(s) become one QuantizedAvgPool2d node (``mctq_codes_avgpool_nhwc``) and the layers behind consumers of its codes,
+    counted in the returned total.  Holder A is treated as for ``pools``: if the pool is its only user and nothing in front is to
+    be absorbed it leaves the graph and the pool module quantizes; with ``shared_holders=True`` a ReLU and / or an add in front
+    is absorbed into a QuantizedJoin, which writes no float32 when the pool was A's only user, and A's other users (an SE
+    block's multiply) keep what they get today; without ``shared_holders`` a holder A with other users is left alone.  With
+    ``stay_on_codes=True`` the pool counts as a reader of A's codes, so that consumer -> ReLU6 -> A -> pool -> B -> Linear runs
+    codes to codes, and with ``fused_residuals=True`` ResNet's last join folds into the last convolution's epilogue.  Left alone:
+    a float32 user of B or of the pool; no holder B (``workloads.wrapped_resnet50``'s head as it stands: its Linear reads an
+    unquantized mean; ``pooled_holder=True`` builds the exported form); an activation between pool and B; an adaptive output
+    size other than 1; ``view`` / ``reshape`` forms of flatten; ``AvgPool1d/3d``; users of B that are partly flattened and partly
+    4-D.  Where A's scale and every window's divisor are powers of two the codes are bit for bit those B gives the float32
+    pool, and the model returns what the same rewrite without the switch returns wherever the products behind are exact;
+    elsewhere the codes are the exact mean rounded twice, within one code of a float32 chain next to a rounding tie."""
     import torch.fx as fx
     if stay_on_codes and not shared_holders:
         raise ValueError("stay_on_codes=True needs shared_holders=True")
@@ -1625,7 +1957,7 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
     class _Tracer(fx.Tracer):
         def is_leaf_module(self, m, qualname):
             return isinstance(m, (PytorchQuantizationWrapper, PytorchActivationQuantizationHolder, IntegerConsumer, QuantizedJoin,
-                                  QuantizedMaxPool2d, QuantizedConcat)) \
+                                  QuantizedMaxPool2d, QuantizedAvgPool2d, QuantizedConcat)) \
                 or super().is_leaf_module(m, qualname)
 
     graph = _Tracer().trace(model)
@@ -1636,9 +1968,9 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
     if concats:
         replaced = _concat_holders(gm, mods, consumer_for, pools)
     if shared_holders:
-        replaced += _join_shared_holders(gm, mods, consumer_for, pools)
-    if pools:
-        replaced += _pool_lone_holders(gm, mods, consumer_for)
+        replaced += _join_shared_holders(gm, mods, consumer_for, pools, avg_pools)
+    if pools or avg_pools:
+        replaced += _pool_lone_holders(gm, mods, consumer_for, pools, avg_pools)
     for node in list(gm.graph.nodes):
         if node.op != "call_module" or node.kwargs or len(node.args) != 1:
             continue

@@ -24,6 +24,7 @@ int g_ql_variant = 0;
 int g_ql_band = 0;
 int g_ql_stagger = 0;         // tiled consumer kernel: half of the waves copy after multiplying (experiment: no gain)
 int g_ql_rot = 0;            // tiled consumer kernel: blocks that share a weight tile start at different K offsets (experiment: no gain)
+int g_avgpool_form = 0;      // mctq_codes_avgpool_nhwc: 0 = the launcher chooses, 1 = lane form, 2 = split form (the result is the same)
 int g_concat_copy = 1;       // mctq_codes_concat_nhwc: operands in the output's own form are copied, not requantized (0: never; the result is the same)
 
 static const char* launch_log_path() {
@@ -214,6 +215,11 @@ int mctq_set_tuning(const char* key, int32_t value) {
   if (!strcmp(key, "concat_copy")) {
     if (value != 0 && value != 1) return fail_arg("concat_copy must be 0 or 1");
     g_concat_copy = value;
+    return 0;
+  }
+  if (!strcmp(key, "avgpool_form")) {
+    if (value < 0 || value > 2) return fail_arg("avgpool_form must be 0 (auto), 1 (lane) or 2 (split)");
+    g_avgpool_form = value;
     return 0;
   }
   return fail_arg("unknown tuning key");

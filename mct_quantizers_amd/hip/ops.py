@@ -701,6 +701,88 @@ def codes_maxpool(codes_nhwc, kernel_size, stride=None, padding=0, dilation=1, c
     return y.permute(0, 2, 3, 1).contiguous()
 
 
+_AVGPOOL_MAX_TAPS = 65536    # taps of a window of one mctq_codes_avgpool_nhwc launch: 255 * 65536 < 2^24, float32(S) is exact
+
+
+def codes_avgpool(codes_nhwc, in_form, out_form, kernel_size, stride=None, padding=0, ceil_mode: bool = False,
+                  count_include_pad: bool = True, divisor_override=None):
+    """``torch.nn.AvgPool2d`` on activation codes, in the form of the holder behind the pool: int8 / uint8 codes [B, H, W, C] of
+    the form ``in_form = (scale, zero_point)`` -> contiguous [B, Ho, Wo, C] codes of ``_code_dtype(qmin, qmax)`` in
+    ``out_form = (scale, zero_point, qmin, qmax)``.  ``kernel_size=None`` is the whole image (global pooling), ``stride=None``
+    means ``kernel_size``, ``padding`` is at most half the kernel size.  Per output element, with S the exact integer sum of
+    ``code - zero_point`` over the window's taps inside the image (a padded tap is 0.0 in float32 and adds nothing) and ``div``
+    the divisor -- ``divisor_override``, or PyTorch's ``pool_size`` with ``count_include_pad``, or the taps inside the image --
+
+        code = clamp(rint((float32(S) * scale_in) / float32(div) * (1 / scale_out)) + zp_out, qmin, qmax)
+
+    every operation in float32 and rounded once (a window without a tap gives 0.0).  Where ``scale_in`` and every ``div`` are
+    powers of two this is bit for bit the code the holder behind a float32 average pool of the dequantized codes gives, whichever
+    way that pool sums; elsewhere it is the exact mean rounded twice, within one code of a float32 chain next to a rounding tie.
+    GPU tensors with C % 16 == 0 and at most 65536 taps per window take one launch of mctq_codes_avgpool_nhwc (1 byte read per
+    tap, 1 written per output element), which is given the output extent allocated here and refuses one that is not its own;
+    anything else on the GPU, and every CPU tensor, evaluates the expression above with torch integer and float32 ops, which the
+    kernel matches byte for byte."""
+    if not isinstance(codes_nhwc, torch.Tensor) or codes_nhwc.dim() != 4:
+        raise ValueError("codes_avgpool takes [N, H, W, C] tensors")
+    if codes_nhwc.dtype not in (torch.int8, torch.uint8):
+        raise NotImplementedError(f"codes_avgpool: int8 / uint8 codes only, got {codes_nhwc.dtype}")
+    a_scale, a_zp = float(in_form[0]), int(in_form[1])
+    o_scale, o_zp, qmin, qmax = float(out_form[0]), int(out_form[1]), int(out_form[2]), int(out_form[3])
+    tdt, ocode = _code_dtype(qmin, qmax)
+    lo, hi = (0, 255) if codes_nhwc.dtype == torch.uint8 else (-128, 127)
+    if not lo <= a_zp <= hi:
+        raise ValueError(f"codes_avgpool: the zero point {a_zp} is no {codes_nhwc.dtype} code")
+    if not 0.0 < a_scale < float("inf") or not 0.0 < o_scale < float("inf"):
+        raise ValueError("codes_avgpool: the scales must be finite and positive")
+    if divisor_override is not None and (not isinstance(divisor_override, int) or isinstance(divisor_override, bool)
+                                         or divisor_override < 1):
+        raise ValueError(f"codes_avgpool: divisor_override must be a positive int or None, got {divisor_override!r}")
+    b, h, w, c = codes_nhwc.shape
+    if kernel_size is None:
+        kernel_size = (h, w)
+    (kh, kw), (sh, sw) = _pair(kernel_size, "kernel_size", "codes_avgpool"), _pair(kernel_size if stride is None else stride, "stride", "codes_avgpool")
+    ph, pw = _pair(padding, "padding", "codes_avgpool")
+    if min(kh, kw, sh, sw) < 1 or min(ph, pw) < 0:
+        raise ValueError("codes_avgpool: kernel_size and stride must be at least 1 and padding at least 0")
+    if ph > kh // 2 or pw > kw // 2:
+        raise ValueError(f"codes_avgpool: padding {ph}x{pw} is larger than half the {kh}x{kw} kernel")
+    ceil_mode, count_include_pad = bool(ceil_mode), bool(count_include_pad)
+    ho, wo = _pool_out_size(h, kh, sh, ph, 1, ceil_mode), _pool_out_size(w, kw, sw, pw, 1, ceil_mode)
+    if ho <= 0 or wo <= 0:
+        raise ValueError(f"codes_avgpool: a {kh}x{kw} kernel does not fit the padded {h}x{w} image")
+    x = codes_nhwc if codes_nhwc.is_contiguous() else codes_nhwc.contiguous()
+    if x.is_cuda and c % 16 == 0 and kh * kw <= _AVGPOOL_MAX_TAPS:
+        y = torch.empty((b, ho, wo, c), dtype=tdt, device=x.device)
+        _gpu_call("mctq_codes_avgpool_nhwc", x, x.data_ptr(), y.data_ptr(), _code_of(x), a_zp, a_scale, b, h, w, c, kh, kw, sh, sw,
+                  ph, pw, int(ceil_mode), int(count_include_pad), divisor_override or 0, ho, wo, ocode, o_scale, o_zp, qmin, qmax)
+        return y
+    if not x.is_cuda:
+        _cpu_route_allowed()
+    if 0 in (b, c):
+        return x.new_empty((b, ho, wo, c), dtype=tdt)
+    with torch.no_grad():
+        # S: the codes less the zero point, zeros around them as far as the last window reaches (ceil_mode: beyond the padding)
+        d = x.to(torch.int32) - a_zp
+        d = torch.nn.functional.pad(d, (0, 0, pw, max(0, (wo - 1) * sw + kw - w - pw), ph, max(0, (ho - 1) * sh + kh - h - ph)))
+        sb, sy, sx, sc = d.stride()
+        total = d.as_strided((b, ho, wo, kh, kw, c), (sb, sy * sh, sx * sw, sy, sx, sc)).sum(dim=(3, 4))          # int64, exact
+        h0, w0 = torch.arange(ho, device=x.device) * sh - ph, torch.arange(wo, device=x.device) * sw - pw
+        if divisor_override is not None:
+            div = torch.full((ho, wo), divisor_override, dtype=torch.int64, device=x.device)
+        elif count_include_pad:
+            div = ((h0 + kh).clamp(max=h + ph) - h0)[:, None] * ((w0 + kw).clamp(max=w + pw) - w0)[None, :]
+        else:
+            div = ((h0 + kh).clamp(max=h) - h0.clamp(min=0)).clamp(min=0)[:, None] * \
+                ((w0 + kw).clamp(max=w) - w0.clamp(min=0)).clamp(min=0)[None, :]
+        div = div.to(torch.float32)[None, :, :, None]
+        f32 = lambda v: torch.tensor(v, dtype=torch.float64, device=x.device).to(torch.float32)               # noqa: E731
+        v = total.to(torch.float32) * f32(a_scale)
+        m = torch.where(div > 0, v / div, torch.zeros_like(v))
+        q = torch.round(m * (torch.tensor(1.0, dtype=torch.float32, device=x.device) / f32(o_scale))) + float(o_zp)
+        q = torch.clamp(torch.nan_to_num(q, nan=float(qmin)), qmin, qmax)
+        return q.to(tdt).contiguous()
+
+
 _CONCAT_MAX = 8           # operands of one mctq_codes_concat_nhwc launch
 
 

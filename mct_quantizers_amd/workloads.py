@@ -204,11 +204,13 @@ def _bottleneck_class():
     return Bottleneck
 
 
-def wrapped_resnet50(device="cuda", weights: str = "symmetric", holders: bool = True):
+def wrapped_resnet50(device="cuda", weights: str = "symmetric", holders: bool = True, pooled_holder: bool = False):
     """ResNet-50 as an MCT export looks (batch norms folded into the convolutions): 53 wrapped convolutions + the wrapped
     classifier, their weights from ``make_model_weights("resnet50")`` in forward order, 8-bit per-channel symmetric
     weights quantizers (``weights="lut"``: 16-entry codebook LUT quantizers), an unsigned 8-bit activation holder behind
-    every ReLU.  Pure workload: random weights, no checkpoint."""
+    every ReLU.  ``pooled_holder=True`` puts the same holder behind the global average pool as well, as an MCT export has it
+    (the classifier then reads a quantized mean); the default is the model without it.  Pure workload: random weights, no
+    checkpoint."""
     import torch
     import torch.nn as nn
     import mct_quantizers_amd as mq
@@ -249,5 +251,9 @@ def wrapped_resnet50(device="cuda", weights: str = "symmetric", holders: bool = 
         for b in range(blocks):
             layers.append(block(cin, width, stride if b == 0 else 1, b == 0))
             cin = width * 4
-    layers += [nn.AdaptiveAvgPool2d(1), nn.Flatten(), wrap(nn.Linear(2048, 1000, bias=False))]
+    layers += [nn.AdaptiveAvgPool2d(1)]
+    if pooled_holder:
+        layers += [mq.PytorchActivationQuantizationHolder(
+            Q.ActivationSymmetricInferableQuantizer(num_bits=8, threshold=[8.0], signed=False))]
+    layers += [nn.Flatten(), wrap(nn.Linear(2048, 1000, bias=False))]
     return nn.Sequential(*layers).to(device).eval()
