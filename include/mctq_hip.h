@@ -78,6 +78,9 @@ extern "C" {
 /* v10 (additive, the version number stays): + mctq_codes_avgpool_nhwc, torch.nn.AvgPool2d / global average pooling on NHWC activation
  * codes in the form of the holder behind the pool (classifier heads and SE squeezes stay on codes), + tuning key "avgpool_form"; no
  * existing signature or result changed. */
+/* v10 (additive, the version number stays): + mctq_codes_mul_nhwc, torch.mul of two holder outputs on NHWC activation codes in the
+ * form of the holder behind it, the second operand same-shape codes, row-broadcast codes or row-broadcast float32 values (the
+ * multiply of a squeeze-and-excitation block and gated layers stay on codes); no existing signature or result changed. */
 #define MCTQ_ABI_VERSION 10
 #define MCTQ_E_ARG (-10001)
 
@@ -596,6 +599,41 @@ typedef struct mctq_concat_item {
 } mctq_concat_item;
 int mctq_codes_concat_nhwc(const mctq_concat_item* items, int32_t count, void* out, int32_t out_code_dtype, int64_t pixels,
                            float scale, int32_t zero_point, int32_t quant_min, int32_t quant_max, void* stream);
+
+/*
+ * Elementwise multiply on activation codes (extension; the reference runs torch.mul on the float32 outputs of two holders and
+ * the holder behind it on the result): a is codes [pixels][channels] (NHWC with the leading extents folded; int8 --
+ * MCTQ_CODE_I8 -- or uint8, MCTQ_CODE_U8) of the form (a_scale, a_zero_point), out is [pixels][channels] in the form
+ * (out_code_dtype, scale, zero_point, quant_min, quant_max); all DEVICE pointers, 16-byte aligned.  The second operand g:
+ *     gate_pixels == 0, g_is_f32 == 0   codes [pixels][channels] of (g_code_dtype, g_scale, g_zero_point)          "same"
+ *     gate_pixels == n >= 1, g_is_f32 == 0   codes [pixels / n][channels]: row p / n multiplies pixel p (an SE gate
+ *                                            [B, C, 1, 1] over images of n = H * W pixels)                          "row"
+ *     gate_pixels == n >= 1, g_is_f32 != 0   raw float32 values [pixels / n][channels], coded first in G's form
+ *                                            cg = clamp(rint(g * (1.0f / g_scale)) + g_zero_point, g_quant_min, g_quant_max),
+ *                                            NaN -> g_quant_min (mctq_fq_codes_per_tensor's arithmetic)             "row f32"
+ * g_quant_min / g_quant_max are read for a float32 g only; a float32 g is taken in the row form only.  Per element
+ *     va  = fma(float(ca - a_zero_point), a_scale, +0)        holder A's float32 output
+ *     vg  = fma(float(cg - g_zero_point), g_scale, +0)        holder G's float32 output
+ *     m   = va * vg                                           one IEEE float32 multiplication, torch.mul's
+ *     out = clamp(rint(m * (1.0f / scale)) + zero_point, quant_min, quant_max)        NaN -> quant_min
+ * -- bit for bit the code the holder behind the multiply gives that float32 product (the reciprocal computed on the host as
+ * in mctq_fq_codes_per_tensor); a function of the two codes alone.
+ * channels is a positive multiple of 16.  A lane owns one 16-byte chunk of the output: one 16-byte load of a, one of g (four
+ * for float32), one 16-byte store; consecutive pixels re-read the same row of g from cache.  A lane reads only chunks below
+ * pixels * channels / 16 of a, below that or (pixels / n) * channels / 16 of g, and writes only chunks below
+ * pixels * channels / 16.
+ * MCTQ_E_ARG with a mctq_last_error text, before anything is launched, for: pixels < 0; a bad code type (a, g, out); a zero
+ * point that is no code of its type (a, g, out); a scale that is not finite and positive (a, g, out); quant_min > quant_max
+ * or a domain outside the type (out, and g where it is float32); gate_pixels < 0; a float32 g with gate_pixels == 0;
+ * channels not a positive multiple of 16; pixels % gate_pixels != 0; more than 2^31 - 1 16-byte chunks (split the pixels);
+ * NULL or misaligned pointers of a non-empty problem; an `out` whose bytes overlap a's or g's (a and g may be one buffer:
+ * x * x).  pixels == 0 returns 0 without a launch.  mctq_last_launch names the launch "codes_mul", op
+ * "<a> * <g> -> <out> <form>" with the code types "u8" / "i8" and the form "same" / "row" / "row f32".
+ */
+int mctq_codes_mul_nhwc(const void* a, int32_t a_code_dtype, float a_scale, int32_t a_zero_point, const void* g,
+                        int32_t g_code_dtype, float g_scale, int32_t g_zero_point, int32_t g_is_f32, int32_t g_quant_min,
+                        int32_t g_quant_max, int64_t gate_pixels, void* out, int32_t out_code_dtype, int64_t pixels,
+                        int64_t channels, float scale, int32_t zero_point, int32_t quant_min, int32_t quant_max, void* stream);
 
 /*
  * Average pooling on activation codes (extension; the reference runs ATen's float32 average pool on the holder's output and

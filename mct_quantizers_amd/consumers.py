@@ -78,6 +78,14 @@ with each other in the last bit).  Limits: per-tensor quantizers of at most 8 bi
 the kernel takes C % 16 == 0 and at most 65536 taps, anything else and CPU tensors run the same contract with torch ops.
 Measured / not measured: see the README paragraph and ``profiles/EXPERIMENTS.md``.
 
+An elementwise multiply between holders stays on codes with ``fuse_linear_consumers_fx(..., muls=True)``: holders A, G -> ``torch.mul``
+-> holder M, the multiply of a squeeze-and-excitation block or a gated layer.  Both operands are ``float(code - zp) * scale`` bit for
+bit, ``torch.mul`` is one IEEE float32 multiplication and M codes every element by itself, so M's code is a function of the two operand
+codes and nothing is approximated.  ``QuantizedMul`` (``mctq_codes_mul_nhwc``) does that in one launch, 1 byte read and 1 written per
+element of the large tensor; the gate ``[B, C, 1, 1]`` may arrive as codes or as the float32 values in front of its holder, which the
+kernel codes itself.  With ``shared_holders=True`` and ``avg_pools=True`` the holder in front of an SE block never writes float32.
+Measured / not measured: see the README paragraph and ``profiles/EXPERIMENTS.md``.
+
 The four modules derive from ``IntegerConsumer``, which owns what they share: the checks of the quantizers and of the float32
 weight and bias, the cache of the weight's codes, the step from ``forward``'s input to activation codes, ``from_wrapper`` and
 the ``emit_codes_for`` / ``emit_clamp`` output form.  ``QuantizedLinear`` is the product over ``[O, K]`` rows; ``QuantizedConv1x1``
@@ -1042,6 +1050,83 @@ class QuantizedConcat(nn.Module):
         return y.permute(0, 3, 1, 2) if first.dim() == 4 else y
 
 
+class QuantizedMul(nn.Module):
+    """``activation holders A, G -> torch.mul -> activation holder M`` on integer codes, for the integer consumers and pools
+    behind M: the multiply of a squeeze-and-excitation block, a gated layer.  A holder's float32 output is
+    ``float(code - zp) * scale`` bit for bit (``ops.dequantize_codes``), ``torch.mul`` is one IEEE float32 multiplication and M
+    codes every element by itself, so M's codes are a function of the two operand codes --
+    ``ops.codes_mul`` (``mctq_codes_mul_nhwc``): 1 byte read and 1 written per element of the large tensor in one launch, where
+    the two holders, ``torch.mul`` and M each read and write 4.  Nothing is approximated.
+
+    ``operand_quantizers``: the two operand holders' quantizers, in the order of ``forward``'s operands; ``activation_quantizer``:
+    M's.  Per-tensor affine activation quantizers of at most 8 bits.  ``forward(x0, x1)`` takes each operand as the codes of its
+    quantizer (int8 / uint8 of its code type; 4-D codes NCHW-shaped and NHWC-stored as the consumers and joins emit them, 2-D
+    ones ``[M, C]`` rows) or as a float32 tensor, which stands for the holder's input -- the holder's input and its output
+    give the same codes.  The shapes decide at forward time: equal shapes take the kernel's same-shape form (a float32
+    operand is quantized first, ``ops.fq_codes_nhwc``); ``[B, C, H, W]`` with ``[B, C, 1, 1]``, in either order, the row-broadcast
+    form, where a float32 gate goes to the kernel as it is and is coded there; any other pair of shapes broadcasts as
+    ``torch.mul`` does with torch ops (``ops.codes_mul``'s torch route, as for C % 16 != 0 and CPU tensors -- the same bytes).
+    It returns M's codes, NCHW-shaped and NHWC-stored for a 4-D result, which an ``IntegerConsumer`` or a ``QuantizedMaxPool2d``
+    of that quantizer takes as they are.  ``activation_code_params`` is the OUTPUT form, what the modules behind agree on;
+    ``operand_code_params(i)`` is what ``emit_codes_for`` of the layer in front of operand ``i`` takes."""
+
+    def __init__(self, operand_quantizers, activation_quantizer):
+        super().__init__()
+        operand_quantizers = tuple(operand_quantizers)
+        if len(operand_quantizers) != 2:
+            raise ValueError("QuantizedMul takes the quantizers of two operands")
+        self.operand_quantizers = operand_quantizers
+        self.activation_quantizer = activation_quantizer
+        self._forms = tuple(_code_form(q) for q in operand_quantizers)
+        self._out_form = _code_form(activation_quantizer)
+
+    def operand_code_params(self, i: int):
+        """(scale, zero_point, qmin, qmax) of the codes operand ``i`` is read as."""
+        return self._forms[i]
+
+    def activation_code_params(self):
+        """(scale, zero_point, qmin, qmax) of the codes ``forward`` returns: what the consumers and pools behind read."""
+        return self._out_form
+
+    def _codes_of(self, i: int, x: torch.Tensor, nhwc: bool):
+        """Operand ``i`` as codes: given codes as they are, float32 quantized in its form; ``nhwc``: 4-D ones as [B, H, W, C]."""
+        scale, zp, qmin, qmax = self._forms[i]
+        if x.dtype in (torch.uint8, torch.int8):
+            if x.dtype != ops._code_dtype(qmin, qmax)[0]:
+                raise TypeError(f"operand {i}: activation codes of type {x.dtype} do not match its quantizer")
+            if nhwc and x.dim() == 4:
+                x = x.permute(0, 2, 3, 1)
+                x = x if x.is_contiguous() else x.contiguous()
+            return x
+        if x.dtype != torch.float32:
+            raise TypeError(f"QuantizedMul takes float32 tensors or activation codes, got {x.dtype}")
+        if nhwc and x.dim() == 4:
+            return ops.fq_codes_nhwc(x, qmin, qmax, scale, zp)
+        return ops.fq_codes(x, None, None, None, qmin, qmax, scale, zp)
+
+    def forward(self, x0: torch.Tensor, x1: torch.Tensor) -> torch.Tensor:
+        xs = (x0, x1)
+        (s0, z0, _, _), (s1, z1, _, _) = self._forms
+        is_gate = lambda g, a: (a.dim() == 4 and g.dim() == 4 and g.shape[:2] == a.shape[:2]              # noqa: E731
+                                and tuple(g.shape[2:]) == (1, 1) and g.shape != a.shape)
+        if x0.shape == x1.shape and x0.dim() in (2, 4):
+            y = ops.codes_mul((self._codes_of(0, x0, True), s0, z0), (self._codes_of(1, x1, True), s1, z1), self._out_form)
+        elif is_gate(x1, x0) or is_gate(x0, x1):
+            at = 0 if is_gate(x1, x0) else 1                     # the large operand; the multiplication is commutative
+            gate, (gs, gz, gmin, gmax) = xs[1 - at], self._forms[1 - at]
+            big = (self._codes_of(at, xs[at], True), *self._forms[at][:2])
+            if gate.dtype == torch.float32:
+                y = ops.codes_mul(big, (gate.permute(0, 2, 3, 1), gs, gz), self._out_form, gate_form=(gmin, gmax))
+            else:
+                y = ops.codes_mul(big, (self._codes_of(1 - at, gate, True), gs, gz), self._out_form)
+        elif x0.dim() == x1.dim() == 4:
+            y = ops.codes_mul((self._codes_of(0, x0, True), s0, z0), (self._codes_of(1, x1, True), s1, z1), self._out_form)
+        else:                                                    # operands of different rank: as torch.mul sees them
+            y = ops.codes_mul((self._codes_of(0, x0, False), s0, z0), (self._codes_of(1, x1, False), s1, z1), self._out_form)
+            return y.contiguous(memory_format=torch.channels_last) if y.dim() == 4 else y
+        return y.permute(0, 3, 1, 2) if y.dim() == 4 else y
+
+
 # In the order they are tried: (class, the switch of the rewrites that enables it or None, what fusing asks of the layer beyond
 # ``eligible``).  The rows kernels need K % 16 == 0 and K <= _MAX_K, which QuantizedConv2d's ``eligible`` holds itself.
 _CONSUMERS = (
@@ -1402,7 +1487,9 @@ def _join_shared_holders(gm, mods, consumer_for, pools: bool = False, avg_pools:
     nothing in front to absorb (the pair rewrite's).  With ``pools`` a max pool among the users that can run on codes
     (``_pool_plan``) reads the join's codes as well, as a QuantizedMaxPool2d in front of its own consumers; a lone holder ->
     pool pair with nothing to absorb is left to ``_pool_lone_holders``.  With ``avg_pools`` the same holds for an average pool
-    in front of a second holder (``_avg_pool_plan``), as a QuantizedAvgPool2d.  Returns the number of wrapped layers replaced."""
+    in front of a second holder (``_avg_pool_plan``), as a QuantizedAvgPool2d.  A QuantizedMul among the users (``_mul_holders``,
+    which built it with this holder's quantizer at that operand) reads the join's codes too, at whichever operand position the
+    holder occupies.  Returns the number of wrapped layers replaced."""
     import operator
     from torch.fx import Node
     replaced = 0
@@ -1424,9 +1511,11 @@ def _join_shared_holders(gm, mods, consumer_for, pools: bool = False, avg_pools:
             plans = ((user, _any_pool_plan(user, mods, holder.activation_holder_quantizer, consumer_for, pools, avg_pools))
                      for user in node.users)
             pooled = [(user, plan) for user, plan in plans if plan is not None]
-        if not taken and not pooled:
+        # M: the QuantizedMul nodes of ``_mul_holders`` that read this holder (built with its quantizer at those operands)
+        muls = [user for user in node.users if isinstance(_module_of(user, mods), QuantizedMul) and not user.kwargs]
+        if not taken and not pooled and not muls:
             continue
-        on_codes = [t for t, _ in taken] + [t for t, _ in pooled]
+        on_codes = [t for t, _ in taken] + [t for t, _ in pooled] + muls
         rest = [u for u in node.users if all(u is not t for t in on_codes)]           # R: they keep the float32 tensor
         src, relu_node, add_node = node.args[0], None, None
         if len(src.users) == 1 and _relu_input(src, mods) is not None:
@@ -1452,6 +1541,8 @@ def _join_shared_holders(gm, mods, consumer_for, pools: bool = False, avg_pools:
             replaced += 1
         for user, plan in pooled:
             replaced += _install_pool(gm, mods, user, plan, as_codes)
+        for user in muls:                                    # at whichever operand position(s) the holder occupies
+            user.args = tuple(as_codes if a is node else a for a in user.args)
         if rest:
             node.replace_all_uses_with(as_float)
         for gone in (node, relu_node, add_node):
@@ -1566,6 +1657,82 @@ def _concat_holders(gm, mods, consumer_for, pools: bool = False) -> int:
     return replaced
 
 
+def _mul_operands(node):
+    """The two operand nodes of ``node`` if it is a plain multiply of two tensors (``*``, ``*=``, ``torch.mul`` /
+    ``torch.multiply``, ``Tensor.mul`` / ``Tensor.multiply``: no scalar operand, no ``out=``), else None."""
+    import operator
+    from torch.fx import Node
+    if node.kwargs or len(node.args) != 2 or not all(isinstance(a, Node) for a in node.args):
+        return None
+    if node.op == "call_function":
+        ok = node.target in (operator.mul, operator.imul, torch.mul, torch.multiply)
+        # (an in-place multiply the module no longer performs: nobody else may be looking at its first operand)
+        if node.target is operator.imul and len(node.args[0].users) != 1:
+            ok = False
+    else:
+        ok = node.op == "call_method" and node.target in ("mul", "multiply")
+    return tuple(node.args) if ok else None
+
+
+def _mul_holders(gm, mods, consumer_for, pools: bool = False) -> int:
+    """``fuse_linear_consumers_fx(muls=True)``: a plain holder M whose one argument is a multiply of two tensors
+    (``_mul_operands``) that feeds nothing else, each operand the output of a plain holder, and every user of which is a wrapped
+    layer ``consumer_for`` can take, fed by it alone -- or, with ``pools``, a max pool that can run on codes (``_pool_plan``) --
+    becomes a QuantizedMul node together with the multiply; its users become consumers and pools of its codes.  An operand
+    holder whose only user was the multiply leaves the graph and the QuantizedMul quantizes that holder's input (a
+    ``[B, C, 1, 1]`` gate inside its kernel); one with other users stays and the QuantizedMul quantizes its float32 output (the
+    same codes) until ``_join_shared_holders`` hands it the codes.  Returns the number of wrapped layers replaced."""
+    from torch.fx import Node
+    replaced = 0
+    for node in list(gm.graph.nodes):
+        if node.op != "call_module" or node.kwargs or len(node.args) != 1 or not isinstance(node.args[0], Node) or not node.users:
+            continue
+        holder = mods.get(node.target)
+        if not _plain_holder(holder):
+            continue
+        mul = node.args[0]
+        operands = _mul_operands(mul)
+        if operands is None or len(mul.users) != 1:
+            continue
+        sources = [_module_of(o, mods) for o in operands]
+        if not all(_plain_holder(h) and len(o.args) == 1 and isinstance(o.args[0], Node) and not o.kwargs
+                   for o, h in zip(operands, sources)):
+            continue
+        quantizer = holder.activation_holder_quantizer
+        taken, pooled = [], []
+        for user in node.users:
+            wrapper = _module_of(user, mods)
+            if isinstance(wrapper, PytorchQuantizationWrapper) and not user.kwargs and user.args == (node,):
+                fused = consumer_for(wrapper, quantizer)
+                if fused is not None:
+                    taken.append((user, fused))
+                    continue
+            plan = _pool_plan(user, mods, quantizer, consumer_for) if pools else None
+            if plan is None:
+                break
+            pooled.append((user, plan))
+        else:
+            try:
+                qmul = QuantizedMul([h.activation_holder_quantizer for h in sources], quantizer)
+            except (TypeError, ValueError, NotImplementedError):
+                continue
+            name = node.target.replace(".", "_") + "_mul"
+            gm.add_submodule(name, qmul)
+            mods[name] = qmul
+            absorbed = [o for o in dict.fromkeys(operands) if len(o.users) == 1]
+            with gm.graph.inserting_before(node):
+                mn = gm.graph.call_module(name, tuple(o.args[0] if o in absorbed else o for o in operands))
+            for user, fused in taken:
+                _install_consumer(gm, mods, user, fused)
+                user.args = (mn,)
+                replaced += 1
+            for user, plan in pooled:
+                replaced += _install_pool(gm, mods, user, plan, mn)
+            for gone in (node, mul, *absorbed):
+                gm.graph.erase_node(gone)
+    return replaced
+
+
 def _clamp_range(node, mods):
     """(a, b) if ``node`` is a clamp activation of one tensor that ``folded_clamp`` can fold -- a ReLU (as ``_relu_input``),
     ``nn.ReLU6`` / ``F.relu6``, ``nn.Hardtanh`` / ``F.hardtanh`` with finite ``min_val <= max_val`` -- else None.  In-place forms
@@ -1641,6 +1808,18 @@ def _identities_as_codes(gm, mods) -> int:
     return converted
 
 
+def _reads_codes_once(reader, codes, form, mods) -> bool:
+    """``reader`` takes the node ``codes`` -- activation codes of ``form`` -- at exactly one operand and reads it as that form:
+    a module of ``_CODE_READERS`` whose one argument it is, or a QuantizedMul, which has two operands, at one of them."""
+    m = _module_of(reader, mods)
+    if reader.kwargs or sum(a is codes for a in reader.args) != 1:
+        return False
+    if isinstance(m, _CODE_READERS):
+        return len(reader.args) == 1
+    return isinstance(m, QuantizedMul) and len(reader.args) == 2 and \
+        m.operand_code_params(0 if reader.args[0] is codes else 1) == tuple(form)
+
+
 def _fold_clamps_into_producers(gm, mods) -> int:
     """``fuse_linear_consumers_fx(stay_on_codes=True)``, the activations between consumers: where a consumer's only user leads
     -- through at most one clamp activation that feeds nothing else (``_clamp_range``; the ReLU a join absorbed counts) -- to a
@@ -1650,7 +1829,9 @@ def _fold_clamps_into_producers(gm, mods) -> int:
     consumer behind it (the pair rewrite) or a residual-free QuantizedJoin that writes no float32 output.  With
     ``concats=True`` the reader may also be a QuantizedConcat among whose arguments the consumer's output (or its one clamp
     activation) occurs exactly once, at index i: the consumer then emits the codes of ``operand_code_params(i)``, the clamp
-    folded in, and that one argument becomes the consumer's output.  Returns the number of producers that now emit codes."""
+    folded in, and that one argument becomes the consumer's output.  With ``muls=True`` a QuantizedMul is such a reader too,
+    directly or among the readers of a join's codes, where those codes occur at exactly one of its two operands (``x * x`` is
+    left to the module's float32 quantize path).  Returns the number of producers that now emit codes."""
     import operator
     folded = 0
     for node in list(gm.graph.nodes):
@@ -1664,9 +1845,10 @@ def _fold_clamps_into_producers(gm, mods) -> int:
         if nxt.op != "call_module" or nxt.kwargs:
             continue
         behind, gone, src, concat_args = mods.get(nxt.target), [nxt], act or node, None
-        if isinstance(behind, QuantizedConcat):
+        via = src                                        # what the readers read now
+        if isinstance(behind, (QuantizedConcat, QuantizedMul)):
             if sum(a is src for a in nxt.args) != 1:
-                continue                                 # (the same tensor at two places, with two forms: left alone)
+                continue                                 # (the same tensor at two places -- x * x, two forms of a cat: left alone)
             at = next(i for i, a in enumerate(nxt.args) if a is src)
             form, readers, gone = behind.operand_code_params(at), [], []
             concat_args = tuple(node if a is src else a for a in nxt.args)
@@ -1682,9 +1864,8 @@ def _fold_clamps_into_producers(gm, mods) -> int:
             picks = list(nxt.users)
             if len(picks) != 1 or picks[0].target is not operator.getitem or picks[0].args != (nxt, 1):
                 continue
-            form, readers = (behind._a_scale, behind._a_zp, behind._a_qmin, behind._a_qmax), list(picks[0].users)
-            if not readers or not all(isinstance(_module_of(r, mods), _CODE_READERS) and r.args == (picks[0],) and not r.kwargs
-                                      for r in readers):
+            form, readers, via = (behind._a_scale, behind._a_zp, behind._a_qmin, behind._a_qmax), list(picks[0].users), picks[0]
+            if not readers or not all(_reads_codes_once(r, via, form, mods) for r in readers):
                 continue
             gone = [picks[0], nxt]
         else:
@@ -1696,7 +1877,7 @@ def _fold_clamps_into_producers(gm, mods) -> int:
             continue
         producer.emit_codes_for, producer.emit_clamp = form, (None if clamp == (form[2], form[3]) else clamp)
         for r in readers:
-            r.args = (node,)
+            r.args = tuple(node if a is via else a for a in r.args)
         if concat_args is not None:
             nxt.args = concat_args
         for g in gone + ([act] if act is not None else []):
@@ -1850,7 +2031,7 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
 def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weights: bool = False,
                              convolutions: bool = False, depthwise: bool = False, shared_holders: bool = False,
                              stay_on_codes: bool = False, pools: bool = False, fused_residuals: bool = False,
-                             concats: bool = False, avg_pools: bool = False):
+                             concats: bool = False, avg_pools: bool = False, muls: bool = False):
     """The same rewrite on an arbitrary module graph (MCT-exported models are not ``nn.Sequential``): traces ``model``
     with torch.fx keeping wrappers and holders as leaves, and wherever an activation holder's ONLY consumer is a
     wrapped ``nn.Linear`` the integer consumer can take (symmetric, power-of-two or LUT weights, and with
@@ -1939,7 +2120,7 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
     counted in the returned total.  Holder A is treated as for ``pools``: if the pool is its only user and nothing in front is to
     be absorbed it leaves the graph and the pool module quantizes; with ``shared_holders=True`` a ReLU and / or an add in front
     is absorbed into a QuantizedJoin, which writes no float32 when the pool was A's only user, and A's other users (an SE
-    block's multiply) keep what they get today; without ``shared_holders`` a holder A with other users is left alone.  With
+    block's multiply) keep what they get today (``muls=True``, below, puts that multiply on codes); without ``shared_holders`` a holder A with other users is left alone.  With
     ``stay_on_codes=True`` the pool counts as a reader of A's codes, so that consumer -> ReLU6 -> A -> pool -> B -> Linear runs
     codes to codes, and with ``fused_residuals=True`` ResNet's last join folds into the last convolution's epilogue.  Left alone:
     a float32 user of B or of the pool; no holder B (``workloads.wrapped_resnet50``'s head as it stands: its Linear reads an
@@ -1947,7 +2128,31 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
     size other than 1; ``view`` / ``reshape`` forms of flatten; ``AvgPool1d/3d``; users of B that are partly flattened and partly
     4-D.  Where A's scale and every window's divisor are powers of two the codes are bit for bit those B gives the float32
     pool, and the model returns what the same rewrite without the switch returns wherever the products behind are exact;
-    elsewhere the codes are the exact mean rounded twice, within one code of a float32 chain next to a rounding tie."""
+    elsewhere the codes are the exact mean rounded twice, within one code of a float32 chain next to a rounding tie.
+
+    ``muls=True`` (needs no other switch) keeps an elementwise multiply between holders on codes: the multiply of a
+    squeeze-and-excitation block (RegNetY, MnasNet, MobileNetV3, EfficientNet), a gated layer.  The candidate is a plain holder M
+    whose one argument is a multiply of two graph nodes -- ``*``, ``torch.mul`` / ``torch.multiply``, ``Tensor.mul`` /
+    ``Tensor.multiply``, ``*=`` only where nobody else reads its first operand; no scalar operand, no ``out=`` -- that feeds nothing
+    else, each operand the output of a plain holder, and every user of which is a wrapped layer the consumer can take under the
+    other switches, fed by M alone, or with ``pools=True`` a max pool that can run on codes.  The multiply and M become one
+    QuantizedMul node (``mctq_codes_mul_nhwc``: 1 byte read and 1 written per element of the large tensor) and the users
+    consumers and pools of its codes, counted in the returned total.  An operand holder that the multiply alone reads leaves the
+    graph and the QuantizedMul quantizes its input -- a ``[B, C, 1, 1]`` gate in float32 goes to the kernel as it is; one with
+    other users stays.  With ``shared_holders=True`` a holder that becomes a QuantizedJoin hands the QuantizedMul its codes, at
+    whichever operand position it occupies, and writes no float32 when no float32 user remains: with ``avg_pools=True`` the
+    holder in front of an SE block, read by the squeeze and by the multiply, never writes its float32 tensor.  With
+    ``stay_on_codes=True`` a QuantizedMul counts as a reader of codes, directly or behind such a join next to other readers, so
+    that conv -> ReLU -> A -> {squeeze, multiply} -> M -> conv runs codes to codes; the same tensor at both operands (``x * x``)
+    is left to the module's float32 quantize path.  Left alone: a float32 user of M (SE-ResNet's identity add behind M: a
+    residual join does not read a QuantizedMul's codes yet); an operand that is no holder's output (``x * sigmoid(y)`` without
+    a holder); anything between the multiply and M; ``div``; scalar operands; folding the sigmoid or hardsigmoid in front of
+    the gate's holder into the product in front of it.  A holder's float32 output is ``float(code - zp) * scale`` bit for bit and
+    ``torch.mul`` is one IEEE float32 multiplication, so the codes are bit for bit those M gives the float32 product, for any
+    shapes ``torch.mul`` broadcasts (the kernel takes equal shapes and ``[B, C, H, W]`` with ``[B, C, 1, 1]`` where C % 16 == 0,
+    everything else torch ops), and the model rewritten with ``muls=True`` returns, bit for bit, what the same rewrite without
+    it returns wherever the float32 products of the layers behind M are exact; otherwise it differs by the accumulation
+    rounding of those products, like every wrapped layer that becomes a consumer."""
     import torch.fx as fx
     if stay_on_codes and not shared_holders:
         raise ValueError("stay_on_codes=True needs shared_holders=True")
@@ -1957,7 +2162,7 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
     class _Tracer(fx.Tracer):
         def is_leaf_module(self, m, qualname):
             return isinstance(m, (PytorchQuantizationWrapper, PytorchActivationQuantizationHolder, IntegerConsumer, QuantizedJoin,
-                                  QuantizedMaxPool2d, QuantizedAvgPool2d, QuantizedConcat)) \
+                                  QuantizedMaxPool2d, QuantizedAvgPool2d, QuantizedConcat, QuantizedMul)) \
                 or super().is_leaf_module(m, qualname)
 
     graph = _Tracer().trace(model)
@@ -1967,6 +2172,8 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
     consumer_for = lambda wrapper, q: _consumer_for(wrapper, q, uniform_weights, convolutions, depthwise)      # noqa: E731
     if concats:
         replaced = _concat_holders(gm, mods, consumer_for, pools)
+    if muls:
+        replaced += _mul_holders(gm, mods, consumer_for, pools)
     if shared_holders:
         replaced += _join_shared_holders(gm, mods, consumer_for, pools, avg_pools)
     if pools or avg_pools:

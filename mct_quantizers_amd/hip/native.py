@@ -146,6 +146,11 @@ SIGNATURES = {
     "mctq_codes_concat_nhwc": (ctypes.c_int, [ctypes.POINTER(ConcatItem), ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,    # items, count, out, out type
                                               ctypes.c_int64, ctypes.c_float, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,  # pixels, scale, zero point, qmin, qmax
                                               ctypes.c_void_p]),
+    "mctq_codes_mul_nhwc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_int32,                 # a, its type, scale, zero point
+                                           ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_int32,                 # g, its type, scale, zero point
+                                           ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,                  # g_is_f32, G's qmin, qmax; gate_pixels
+                                           ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64,                 # out, out type, pixels, channels
+                                           ctypes.c_float, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),  # scale, zero point, qmin, qmax; stream
     "mctq_codes_avgpool_nhwc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float]   # codes, pooled, type, zero point, scale
                                 + [ctypes.c_int64] * 4 + [ctypes.c_int32] * 9 + [ctypes.c_int64] * 2     # B, H, W, C; geometry, ceil_mode, count_include_pad, divisor_override; Ho, Wo
                                 + [ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),  # output form; stream

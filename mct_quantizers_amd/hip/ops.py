@@ -836,6 +836,81 @@ def codes_concat(operands, out_form):
         return torch.cat(parts, -1).contiguous()
 
 
+def codes_mul(a, g, out_form, gate_form=None):
+    """``torch.mul`` of two holder outputs on activation codes, in the form of the holder behind it.  ``a = (codes, scale,
+    zero_point)``, int8 / uint8 codes ``[.., C]`` (channels last); ``g = (tensor, scale, zero_point)``, codes likewise or, with
+    ``gate_form = (qmin, qmax)`` (the clamp domain of g's quantizer), raw float32 values; ``out_form = (scale, zero_point, qmin,
+    qmax)``.  Returns contiguous codes of ``_code_dtype(qmin, qmax)`` in the broadcast shape of the two:
+
+        g_codes = g if gate_form is None else fq_codes(g, None, None, None, *gate_form, g_scale, g_zp)
+        fq_codes(dequantize_codes(a, a_scale, a_zp) * dequantize_codes(g_codes, g_scale, g_zp), None, None, None, qmin, qmax, s, z)
+
+    -- a holder's float32 output is ``dequantize_codes`` of its codes bit for bit and ``torch.mul`` is one IEEE float32
+    multiplication, so these are the codes the holder behind the product of the two holder outputs gives.  GPU tensors with
+    ``C % 16 == 0`` take one launch of mctq_codes_mul_nhwc (1 byte read, 1 byte written per element) in three forms: codes of
+    the same shape; codes ``[B, 1, .., 1, C]`` next to ``[B, .., C]`` (the gate of a squeeze-and-excitation block, in either
+    operand order); float32 values of that gate shape, coded inside the kernel.  Anything else on the GPU -- another ``C``,
+    any other broadcast (``[B, H, W, 1]``, ``[1, 1, 1, C]``, operands of different rank), a float32 operand of another shape
+    -- and every CPU tensor evaluates the expression above with torch ops, broadcasting as ``torch.mul`` does, which the kernel
+    matches byte for byte."""
+    (ac, a_scale, a_zp), (gc, g_scale, g_zp) = a, g
+    a_scale, a_zp, g_scale, g_zp = float(a_scale), int(a_zp), float(g_scale), int(g_zp)
+    o_scale, o_zp, qmin, qmax = float(out_form[0]), int(out_form[1]), int(out_form[2]), int(out_form[3])
+    tdt, ocode = _code_dtype(qmin, qmax)
+    if not isinstance(ac, torch.Tensor) or ac.dtype not in (torch.int8, torch.uint8) or ac.dim() < 1:
+        raise TypeError("codes_mul takes int8 / uint8 codes [.., C] as its first operand")
+    if gate_form is None:
+        if not isinstance(gc, torch.Tensor) or gc.dtype not in (torch.int8, torch.uint8) or gc.dim() < 1:
+            raise TypeError("codes_mul takes int8 / uint8 codes [.., C] as its second operand, or float32 values with gate_form")
+        g_tdt, g_qmin, g_qmax = gc.dtype, 0, 0
+    else:
+        if not isinstance(gc, torch.Tensor) or gc.dtype != torch.float32 or gc.dim() < 1:
+            raise TypeError("codes_mul: gate_form describes a float32 second operand")
+        g_qmin, g_qmax = int(gate_form[0]), int(gate_form[1])
+        g_tdt, _ = _code_dtype(g_qmin, g_qmax)
+    if gc.device != ac.device:
+        raise RuntimeError(f"codes_mul: operands must share the device, got {ac.device} and {gc.device}")
+    for dt, z, what in ((ac.dtype, a_zp, "first"), (g_tdt, g_zp, "second"), (tdt, o_zp, "output")):
+        lo, hi = (0, 255) if dt == torch.uint8 else (-128, 127)
+        if not lo <= z <= hi:
+            raise ValueError(f"codes_mul: the zero point {z} of the {what} form is no {dt} code")
+    if not all(0.0 < s < float("inf") for s in (a_scale, g_scale, o_scale)):
+        raise ValueError("codes_mul: the scales must be finite and positive")
+
+    def gate_of(big, small):
+        """small is [B, 1, .., 1, C] next to big [B, .., C]: the pixels per gate row, else None."""
+        if small.dim() != big.dim() or big.dim() < 3 or small.shape[0] != big.shape[0] or small.shape[-1] != big.shape[-1]:
+            return None
+        return math.prod(big.shape[1:-1]) if all(e == 1 for e in small.shape[1:-1]) else None
+
+    n = None                                                     # the kernel's gate_pixels; None: the torch route
+    if ac.is_cuda and ac.shape[-1] > 0 and ac.shape[-1] % 16 == 0:
+        if gc.shape == ac.shape:
+            n = 0 if gate_form is None else 1                    # (float32 values: every pixel its own gate row)
+        elif gate_of(ac, gc) is not None:
+            n = gate_of(ac, gc)
+        elif gate_form is None and gate_of(gc, ac) is not None:   # the gate first: the multiplication is commutative
+            n = gate_of(gc, ac)
+            ac, a_scale, a_zp, gc, g_scale, g_zp, g_tdt = gc, g_scale, g_zp, ac, a_scale, a_zp, ac.dtype
+    if n is not None:
+        out = torch.empty(ac.shape, dtype=tdt, device=ac.device)
+        if out.numel() == 0:
+            return out
+        ak = ac if ac.is_contiguous() else ac.contiguous()      # named: they must outlive the launch
+        gk = gc if gc.is_contiguous() else gc.contiguous()
+        _gpu_call("mctq_codes_mul_nhwc", ak, ak.data_ptr(), _code_of(ak), a_scale, a_zp, gk.data_ptr(),
+                  native.CODE_U8 if g_tdt == torch.uint8 else native.CODE_I8, g_scale, g_zp, int(gate_form is not None), g_qmin,
+                  g_qmax, n, out.data_ptr(), ocode, ak.numel() // ak.shape[-1], ak.shape[-1], o_scale, o_zp, qmin, qmax)
+        return out
+    if not ac.is_cuda:
+        _cpu_route_allowed()
+    with torch.no_grad():
+        if gate_form is not None:
+            gc = fq_codes(gc, None, None, None, g_qmin, g_qmax, g_scale, g_zp)
+        v = dequantize_codes(ac, a_scale, a_zp) * dequantize_codes(gc, g_scale, g_zp)
+        return fq_codes(v.contiguous(), None, None, None, qmin, qmax, o_scale, o_zp).contiguous()
+
+
 def make_lut_table(lut_values, mult: float, cmin: float, cmax: float, device):
     """Device copy of the codebook's decision table (see include/mctq_hip.h), or None.
 
