@@ -81,6 +81,9 @@ extern "C" {
 /* v10 (additive, the version number stays): + mctq_codes_mul_nhwc, torch.mul of two holder outputs on NHWC activation codes in the
  * form of the holder behind it, the second operand same-shape codes, row-broadcast codes or row-broadcast float32 values (the
  * multiply of a squeeze-and-excitation block and gated layers stay on codes); no existing signature or result changed. */
+/* v10 (additive, the version number stays): + mctq_qlinear_i8_act and mctq_qconv_dw_i8_act, the integer product and the depthwise
+ * convolution with a Hardswish / Hardsigmoid in front of the codes they emit (MobileNetV3's layers and the SE gate stay on codes); no
+ * existing signature or result changed. */
 #define MCTQ_ABI_VERSION 10
 #define MCTQ_E_ARG (-10001)
 
@@ -878,6 +881,40 @@ int mctq_qlinear_i8_res(const void* a_codes, int32_t a_code_dtype, int32_t a_zer
                         const void* residual, int32_t r_code_dtype, float r_scale, int32_t r_zero_point, int32_t relu,
                         void* y, int32_t y_code_dtype, float y_scale, int32_t y_zero_point, int32_t y_quant_min,
                         int32_t y_quant_max, int64_t M, int64_t N, int64_t K, void* stream);
+
+/*
+ * The integer consumers with a Hardswish / Hardsigmoid in front of the codes they emit (wrapped layer -> Hardswish -> holder ->
+ * wrapped layer without the float32 tensors in between):
+ *     v       = float( sum ... ) * (a_scale * w_scales[n]) (+ bias[n])                  as mctq_qlinear_i8 / mctq_qconv_dw_i8
+ *     act 1:  v = v * min(max(v + 3, 0), 6) * (1.0f / 6.0f)                             hardswish
+ *     act 2:  v =     min(max(v + 3, 0), 6) * (1.0f / 6.0f)                             hardsigmoid
+ *     y       = the code of v in the output form, as mctq_qlinear_i8_codes
+ * The expression is evaluated left to right with one float32 rounding per operation; max / min are a < b ? b : a and
+ * b < a ? b : a (a NaN stays a NaN and then codes to y_quant_min; hardswish(-inf) = -inf * 0 = NaN).  This is what ATen's GPU
+ * kernels evaluate: F.hardswish / F.hardsigmoid of a float32 GPU tensor give these bits for every one of the 2^32 float32 bit
+ * patterns (tools/hard_act_probe.py).  ATen's CPU kernels divide by 6 instead of multiplying by 1.0f / 6.0f and differ from it in
+ * the last bit for about a quarter (hardswish) / a thirtieth (hardsigmoid) of the patterns.  The register of v holds exactly
+ * the float32 value the plain entry point would have stored, so the codes are bit for bit those of the plain entry point
+ * followed by ATen's GPU activation and mctq_fq_codes_per_tensor.
+ * mctq_qlinear_i8_act: the arguments of mctq_qlinear_i8_codes and act in front of M; int8 weights without zero points, no
+ * residual.  mctq_qconv_dw_i8_act: the arguments of mctq_qconv_dw_i8 and act in front of batch; weights with or without
+ * zero points.  MCTQ_E_ARG for an act other than 1 and 2 and for y_code_dtype < 0 (codes are the only output: the sign of a
+ * zero never shows); everything else as for the plain entry points, an empty problem returns 0 without a launch.
+ * Launch shapes of the product: the weight-streaming and LDS-tiled kernels under the same cost model and "ql_variant" key;
+ * the register-pinned whole-tile kernels are not built for an activation (as for a residual), so large whole-tile products
+ * run on the tiled kernels and ql_variant 2544 / 2548 / 2560 returns MCTQ_E_ARG here.
+ * mctq_last_launch names the activation: "...<u8 x i8 hardswish,...>" / "...<i8 x i8 zp hardsigmoid,...>".
+ */
+int mctq_qlinear_i8_act(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
+                        const int8_t* w_codes, const float* w_scales, const int32_t* w_rowsum, const float* bias,
+                        void* y, int32_t y_code_dtype, float y_scale, int32_t y_zero_point, int32_t y_quant_min,
+                        int32_t y_quant_max, int32_t act, int64_t M, int64_t N, int64_t K, void* stream);
+int mctq_qconv_dw_i8_act(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
+                         const int8_t* w_codes, const float* w_scales, const int32_t* w_zero_points, const float* bias,
+                         void* y, int32_t y_code_dtype, float y_scale, int32_t y_zero_point, int32_t y_quant_min, int32_t y_quant_max,
+                         int32_t act, int64_t batch, int64_t height, int64_t width, int64_t channels,
+                         int32_t kh, int32_t kw, int32_t stride_h, int32_t stride_w, int32_t pad_h, int32_t pad_w,
+                         int32_t dil_h, int32_t dil_w, void* stream);
 
 /*
  * Tuning hook (benchmarks only): selects the launch variant used by later calls on any thread.

@@ -55,6 +55,11 @@ product in front of them: the block's last convolution reads the identity branch
 downsample branch's float32 output -- in its own epilogue, adds it, applies the ReLU and emits the next block's codes
 (``mctq_qlinear_i8_res``): about 2 bytes per element where the product and the join moved 10, and one launch less per block.
 
+``fuse_linear_consumers_fx(..., stay_on_codes=True, hard_activations=True)`` does for Hardswish and Hardsigmoid what
+``stay_on_codes`` does for the clamp activations, except that these two are no clamps of the codes: the consumer in front applies
+them to its float32 value in its own epilogue, with the float32 expression of ATen's GPU kernels, and emits the holder's codes
+(``mctq_qlinear_i8_act``, ``mctq_qconv_dw_i8_act``; ``emit_act``) -- MobileNetV3's layers and the gate of an SE block.
+
 A max pool between a holder and wrapped layers stays on codes with ``pools=True`` (both rewrites): the holder's float32 output
 is ``float(code - zp) * scale`` with ``scale > 0``, monotone in the code and never NaN, so the pool of that output is the
 dequantized pool of the codes bit for bit.  ``QuantizedMaxPool2d`` (``mctq_codes_maxpool_nhwc``) pools the codes -- a padded tap
@@ -155,11 +160,27 @@ def _cpu_out_codes(y, out_codes):
     return ops.fq_codes(y, None, None, None, lo, hi, o_scale, o_zp).to(ops._code_dtype(o_qmin, o_qmax)[0])
 
 
-def _cpu_epilogue(acc, a_scale, w_scales, bias, out_codes, residual=None, residual_codes=None, relu=False):
+_ACTS = {"hardswish": 1, "hardsigmoid": 2}
+
+
+def _check_act(act, out_codes):
+    """``act`` of ``qlinear_i8`` / ``qconv_dw_i8``: None, "hardswish" or "hardsigmoid"; an activation leaves as codes only."""
+    if act is None:
+        return None
+    if act not in _ACTS:
+        raise ValueError(f"act must be None, 'hardswish' or 'hardsigmoid', got {act!r}")
+    if out_codes is None:
+        raise ValueError(f"act={act!r} needs out_codes: the activation is folded in front of the codes, there is no float32 form")
+    return act
+
+
+def _cpu_epilogue(acc, a_scale, w_scales, bias, out_codes, residual=None, residual_codes=None, relu=False, act=None):
     """The CPU routes' epilogue, the kernels' own: the int32 sums ``acc`` (output channels last) times ``a_scale`` (rounded to
     float32 first) times the channel's weight scale, plus the bias; with ``residual`` (float32, or codes with
     ``residual_codes = (scale, zero_point)``, dequantized) one float32 add and, with ``relu``, ``v < 0 ? 0 : v`` -- a NaN stays a
-    NaN and -0.0 stays -0.0, as in the kernel; float32, or the codes of ``out_codes``."""
+    NaN and -0.0 stays -0.0, as in the kernel; with ``act`` ``torch.nn.functional.hardswish`` / ``hardsigmoid`` of that value (ATen's
+    CPU expression, which divides by 6 where the GPU kernels multiply by 1.0f / 6.0f: see ``qlinear_i8``); float32, or the codes
+    of ``out_codes``."""
     y = acc.to(torch.float32) * (torch.tensor(a_scale, dtype=torch.float64).to(torch.float32) * w_scales)
     if bias is not None:
         y = y + bias
@@ -167,6 +188,8 @@ def _cpu_epilogue(acc, a_scale, w_scales, bias, out_codes, residual=None, residu
         y = y + (residual if residual_codes is None else ops.dequantize_codes(residual, *residual_codes))
         if relu:
             y = torch.where(y < 0, torch.zeros((), dtype=torch.float32, device=y.device), y)
+    if act is not None:
+        y = getattr(torch.nn.functional, act)(y)
     return y if out_codes is None else _cpu_out_codes(y, out_codes)
 
 
@@ -242,12 +265,13 @@ def _k_mismatch(K, w_k, what):
 
 
 def _launch_consumer(name, a_codes, a_zero_point, a_scale, w, lut, w_scales, w_rowsum, bias, out_codes, w_zero_points,
-                     residual=None, residual_codes=None, relu=False):
+                     residual=None, residual_codes=None, relu=False, act=None):
     """One consumer launch on GPU tensors.  ``name`` is the entry point of the weight format: ``mctq_qlinear_i8`` (``w``: int8
     codes [N, K]), ``mctq_qlinear_w4a8`` (packed 4-bit codes [N, K / 2]) or ``mctq_qlinear_lut4a8`` (packed 4-bit indices
     [N, K / 2] and ``lut = (the 16 codebook bytes,)``; for the others ``lut = ()``).  ``w_zero_points`` selects the ``_zp``
     form of the first two, and ``out_codes`` on int8 weights without zero points ``mctq_qlinear_i8_codes``.  ``residual``
-    (checked by ``_check_residual``; int8 weights without zero points only) selects ``mctq_qlinear_i8_res``."""
+    (checked by ``_check_residual``; int8 weights without zero points only) selects ``mctq_qlinear_i8_res``, ``act`` (checked by
+    ``qlinear_i8``: codes out, no zero points, no residual) ``mctq_qlinear_i8_act``."""
     M, K = a_codes.shape
     N, w_k = w.shape
     packed = name != "mctq_qlinear_i8"
@@ -267,6 +291,8 @@ def _launch_consumer(name, a_codes, a_zero_point, a_scale, w, lut, w_scales, w_r
         zp = ()
         if residual is not None:
             name = "mctq_qlinear_i8_res"
+        elif act is not None:
+            name = "mctq_qlinear_i8_act"
         elif not packed and out_codes is not None:
             name = "mctq_qlinear_i8_codes"
     res = ()
@@ -281,14 +307,14 @@ def _launch_consumer(name, a_codes, a_zero_point, a_scale, w, lut, w_scales, w_r
     y = a_codes.new_empty((M, N), dtype=tdt)
     ops._gpu_call(name, a_codes, a_codes.data_ptr(), ops._code_of(a_codes), int(a_zero_point), float(a_scale), w.data_ptr(), *lut,
                   w_scales.data_ptr(), w_rowsum.data_ptr(), None if bias is None else bias.data_ptr(), *res, y.data_ptr(), *form, *zp,
-                  M, N, K)
+                  *(() if act is None else (_ACTS[act],)), M, N, K)
     return y
 
 
 def qlinear_i8(a_codes: torch.Tensor, a_zero_point: int, a_scale: float, w_codes: torch.Tensor,
                w_scales: torch.Tensor, w_rowsum: torch.Tensor, bias: Optional[torch.Tensor],
                out_codes=None, w_zero_points: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
-               residual_codes=None, relu: bool = False) -> torch.Tensor:
+               residual_codes=None, relu: bool = False, *, act: Optional[str] = None) -> torch.Tensor:
     """a_codes [M, K] int8/uint8, w_codes [N, K] int8 (zero point 0 unless ``w_zero_points`` is given) -> float32
     [M, N]; with ``out_codes = (scale, zero_point, qmin, qmax)`` the result leaves as the codes of that activation quantizer
     (int8 / uint8 [M, N]), bit-identical to quantizing the float32 result with ``ops.fq_codes``.  Two more entries,
@@ -300,11 +326,21 @@ def qlinear_i8(a_codes: torch.Tensor, a_zero_point: int, a_scale: float, w_codes
     add -- a float32 tensor, or int8 / uint8 codes with ``residual_codes = (scale, zero_point)`` that stand for
     ``ops.dequantize_codes(residual, scale, zero_point)`` -- and with ``relu=True`` the join's ReLU behind the add, before the
     output form: bit for bit ``ops.fq_join(qlinear_i8(...), ..., residual=..., relu=...)`` of the float32 product, without that
-    tensor (``mctq_qlinear_i8_res``).  Not together with ``w_zero_points`` (NotImplementedError); ``relu`` needs a residual."""
+    tensor (``mctq_qlinear_i8_res``).  Not together with ``w_zero_points`` (NotImplementedError); ``relu`` needs a residual.
+    ``act`` ("hardswish" / "hardsigmoid"; needs ``out_codes``, ValueError otherwise): that activation of the float32 result in
+    front of the codes, in the product's epilogue (``mctq_qlinear_i8_act``) -- on the GPU bit for bit
+    ``ops.fq_codes(F.hardswish(qlinear_i8(...)), ...)`` of the float32 product, NaNs and infinities included, without the two
+    float32 tensors.  The kernel evaluates what ATen's GPU kernels evaluate, ``x * min(max(x + 3, 0), 6) * (1.0f / 6.0f)``; CPU
+    tensors take ``F.hardswish`` / ``F.hardsigmoid`` on the CPU, which divide by 6 -- the two float32 values differ in the last
+    bit for about a quarter / a thirtieth of all inputs, so the CPU route's codes may differ from the kernel's by one at a rounding
+    tie, exactly as the float32 chain's do between the two devices.  Not together with ``residual`` or ``w_zero_points``
+    (NotImplementedError).  Whole-tile products with an activation run on the tiled kernels, not the register-pinned ones."""
     residual, residual_codes = _check_residual(a_codes, w_codes.shape[0], residual, residual_codes, relu, w_zero_points)
+    if _check_act(act, out_codes) is not None and (residual is not None or w_zero_points is not None):
+        raise NotImplementedError("an activation together with a residual or with weight zero points")
     if a_codes.is_cuda:
         return _launch_consumer("mctq_qlinear_i8", a_codes, a_zero_point, a_scale, w_codes, (), w_scales, w_rowsum, bias,
-                                out_codes, w_zero_points, residual, residual_codes, relu)
+                                out_codes, w_zero_points, residual, residual_codes, relu, act)
     if w_codes.shape[1] != a_codes.shape[1]:
         raise _k_mismatch(a_codes.shape[1], w_codes.shape[1], "weights")
     ops._cpu_route_allowed()
@@ -313,12 +349,12 @@ def qlinear_i8(a_codes: torch.Tensor, a_zero_point: int, a_scale: float, w_codes
         _check_consumer_operands(a_codes, w_scales, None, None, w_zero_points)     # dtype, device, one per output channel
         w32 = w32 - w_zero_points.to(torch.int32).reshape(-1, 1)
     acc = (a_codes.to(torch.int32) - int(a_zero_point)) @ w32.t()
-    return _cpu_epilogue(acc, a_scale, w_scales, bias, out_codes, residual, residual_codes, relu)
+    return _cpu_epilogue(acc, a_scale, w_scales, bias, out_codes, residual, residual_codes, relu, act)
 
 
 def qconv_dw_i8(a_codes_nhwc: torch.Tensor, a_zero_point: int, a_scale: float, w_codes: torch.Tensor, w_scales: torch.Tensor,
                 bias: Optional[torch.Tensor], kernel_size, stride=1, padding=0, dilation=1, out_codes=None,
-                w_zero_points: Optional[torch.Tensor] = None) -> torch.Tensor:
+                w_zero_points: Optional[torch.Tensor] = None, *, act: Optional[str] = None) -> torch.Tensor:
     """Depthwise convolution on codes: a_codes_nhwc [B, H, W, C] int8/uint8, w_codes [kh, kw, C] int8 (zero point 0 unless
     ``w_zero_points``, int32 [C] each in [-128, 127], is given), w_scales / bias float32 [C] -> float32 [B, Ho, Wo, C],
 
@@ -326,7 +362,10 @@ def qconv_dw_i8(a_codes_nhwc: torch.Tensor, a_zero_point: int, a_scale: float, w
 
     or with ``out_codes = (scale, zero_point, qmin, qmax)`` the codes of that activation quantizer, bit-identical to
     ``ops.fq_codes`` of the float32 result.  ``kernel_size``, ``stride``, ``padding`` and ``dilation`` are ints or pairs.
+    ``act`` ("hardswish" / "hardsigmoid"; needs ``out_codes``): that activation of the float32 value in front of the codes, as for
+    ``qlinear_i8`` (``mctq_qconv_dw_i8_act``; weights with or without zero points; the same note on the CPU route's expression).
     GPU tensors run ``mctq_qconv_dw_i8`` (C % 16 == 0, kh * kw <= 256); CPU tensors the same arithmetic with torch ops."""
+    _check_act(act, out_codes)
     if not isinstance(a_codes_nhwc, torch.Tensor) or a_codes_nhwc.dim() != 4 or a_codes_nhwc.dtype not in (torch.int8, torch.uint8):
         raise TypeError("qconv_dw_i8 takes int8 / uint8 codes [B, H, W, C]")
     b, h, w_, c = a_codes_nhwc.shape
@@ -347,9 +386,10 @@ def qconv_dw_i8(a_codes_nhwc: torch.Tensor, a_zero_point: int, a_scale: float, w
         x, w_codes = a_codes_nhwc.contiguous(), w_codes.contiguous()
         tdt, *form = _output_form(out_codes)
         y = x.new_empty((b, ho, wo, c), dtype=tdt)
-        ops._gpu_call("mctq_qconv_dw_i8", x, x.data_ptr(), ops._code_of(x), a_zero_point, float(a_scale), w_codes.data_ptr(),
-                      w_scales.data_ptr(), None if w_zero_points is None else w_zero_points.data_ptr(),
-                      None if bias is None else bias.data_ptr(), y.data_ptr(), *form, b, h, w_, c, kh, kw, sh, sw, ph, pw, dh, dw)
+        ops._gpu_call("mctq_qconv_dw_i8" if act is None else "mctq_qconv_dw_i8_act", x, x.data_ptr(), ops._code_of(x), a_zero_point,
+                      float(a_scale), w_codes.data_ptr(), w_scales.data_ptr(),
+                      None if w_zero_points is None else w_zero_points.data_ptr(), None if bias is None else bias.data_ptr(),
+                      y.data_ptr(), *form, *(() if act is None else (_ACTS[act],)), b, h, w_, c, kh, kw, sh, sw, ph, pw, dh, dw)
         return y
     ops._cpu_route_allowed()
     w32 = w_codes.to(torch.int32)
@@ -362,7 +402,7 @@ def qconv_dw_i8(a_codes_nhwc: torch.Tensor, a_zero_point: int, a_scale: float, w
         for kx in range(kw):
             taps = xp[:, ky * dh:ky * dh + (ho - 1) * sh + 1:sh, kx * dw:kx * dw + (wo - 1) * sw + 1:sw, :]
             acc += taps * w32[ky, kx]
-    return _cpu_epilogue(acc, a_scale, w_scales, bias, out_codes)
+    return _cpu_epilogue(acc, a_scale, w_scales, bias, out_codes, act=act)
 
 
 def pack_w4(codes: torch.Tensor) -> torch.Tensor:
@@ -502,6 +542,13 @@ class IntegerConsumer(nn.Module):
         # that are its product only.
         self.emit_residual = None
         self.emit_relu = False
+        # fuse_linear_consumers_fx(hard_activations=True): "hardswish" / "hardsigmoid", the activation between this layer and
+        # the quantizer of emit_codes_for, applied to the float32 value in the epilogue (needs emit_codes_for; the product
+        # with int8 weights without zero points and without a residual, and the depthwise convolution).
+        self.emit_act = None
+
+    def extra_repr(self) -> str:
+        return "" if self.emit_act is None else f"emit_act={self.emit_act!r}"
 
     @classmethod
     def from_wrapper(cls, wrapper: PytorchQuantizationWrapper, activation_quantizer):
@@ -686,7 +733,11 @@ class QuantizedLinear(IntegerConsumer):
                 raise TypeError(f"this layer was built for a residual operand {'as codes' if as_codes else 'in float32'}, "
                                 f"got {residual.dtype}")
             return qlinear_i8(a_codes, self._a_zp, self._a_scale, self._w_codes, self._w_scales, self._w_rowsum, bias,
-                              self._out_codes(), self._w_zps, residual, self.emit_residual if as_codes else None, self.emit_relu)
+                              self._out_codes(), self._w_zps, residual, self.emit_residual if as_codes else None, self.emit_relu,
+                              act=self.emit_act)
+        if self.emit_act is not None:                    # (the packed 4-bit routes take no activation: int8 codes)
+            return qlinear_i8(a_codes, self._a_zp, self._a_scale, self._w_codes, self._w_scales, self._w_rowsum, bias,
+                              self._out_codes(), self._w_zps, act=self.emit_act)
         if self._w_codes4 is not None and a_codes.is_cuda and a_codes.shape[0] <= _W4_MAX_ROWS:
             return qlinear_w4a8(a_codes, self._a_zp, self._a_scale, self._w_codes4, self._w_scales, self._w_rowsum, bias,
                                 self._out_codes(), self._w_zps)
@@ -787,7 +838,7 @@ class QuantizedDepthwiseConv2d(IntegerConsumer):
         self._refresh_weight_codes()
         codes = self._activation_codes(x)
         y = qconv_dw_i8(codes, self._a_zp, self._a_scale, self._w_codes, self._w_scales, self._bias_for(codes), self.kernel_size,
-                        self.stride, self.padding, self.dilation, self._out_codes(), self._w_zps)
+                        self.stride, self.padding, self.dilation, self._out_codes(), self._w_zps, act=self.emit_act)
         return y.permute(0, 3, 1, 2)
 
 
@@ -1765,6 +1816,37 @@ def _clamp_range(node, mods):
     return float(rng[0]), float(rng[1])
 
 
+def _hard_activation(node, mods):
+    """"hardswish" / "hardsigmoid" if ``node`` is that activation of one tensor -- ``nn.Hardswish`` / ``nn.Hardsigmoid`` modules,
+    ``F.hardswish`` / ``F.hardsigmoid`` with at most a constant ``inplace`` -- else None.  In-place forms only where nobody else
+    looks at the input (as ``_clamp_range``)."""
+    from torch.fx import Node
+    F = torch.nn.functional
+    if not node.args or not isinstance(node.args[0], Node):
+        return None
+    kind, inplace = None, False
+    if node.op == "call_module" and len(node.args) == 1 and not node.kwargs:
+        m = mods.get(node.target)
+        if type(m) in (nn.Hardswish, nn.Hardsigmoid):
+            kind, inplace = ("hardswish" if type(m) is nn.Hardswish else "hardsigmoid"), m.inplace
+    elif node.op == "call_function" and node.target in (F.hardswish, F.hardsigmoid):
+        if len(node.args) <= 2 and not set(node.kwargs) - ({"inplace"} if len(node.args) == 1 else set()):
+            kind = "hardswish" if node.target is F.hardswish else "hardsigmoid"
+            inplace = node.args[1] if len(node.args) == 2 else node.kwargs.get("inplace", False)
+    if kind is None or not isinstance(inplace, bool) or (inplace and len(node.args[0].users) != 1):
+        return None
+    return kind
+
+
+def _takes_hard_activation(consumer) -> bool:
+    """The entry points with an activation: the depthwise convolution with any weights; the product with int8 weights that
+    have no zero points, no packed 4-bit / codebook form and no residual."""
+    if isinstance(consumer, QuantizedDepthwiseConv2d):
+        return True
+    return (isinstance(consumer, QuantizedLinear) and not consumer._uniform_weights and not consumer._lut_weights
+            and consumer.weights_quantizer.num_bits > 4 and consumer.emit_residual is None)
+
+
 def _identities_as_codes(gm, mods) -> int:
     """``fuse_linear_consumers_fx(stay_on_codes=True)``, the identity branches: a join with a residual one of whose add operands
     is the float32 output of another join takes that join's codes in its place (``QuantizedJoin(residual_codes=...)``; IEEE
@@ -1820,9 +1902,11 @@ def _reads_codes_once(reader, codes, form, mods) -> bool:
         m.operand_code_params(0 if reader.args[0] is codes else 1) == tuple(form)
 
 
-def _fold_clamps_into_producers(gm, mods) -> int:
+def _fold_clamps_into_producers(gm, mods, hard_activations: bool = False) -> int:
     """``fuse_linear_consumers_fx(stay_on_codes=True)``, the activations between consumers: where a consumer's only user leads
-    -- through at most one clamp activation that feeds nothing else (``_clamp_range``; the ReLU a join absorbed counts) -- to a
+    -- through at most one clamp activation that feeds nothing else (``_clamp_range``; the ReLU a join absorbed counts), or with
+    ``hard_activations=True`` one Hardswish / Hardsigmoid (``_hard_activation``) behind a consumer that takes one
+    (``_takes_hard_activation``), which is not folded into the clamp but applied in the consumer's epilogue (``emit_act``) -- to a
     holder all of whose users are integer consumers (or, with ``pools=True``, QuantizedMaxPool2d modules in front of such), the
     consumer emits that holder's codes itself, the activation folded into their clamp (``folded_clamp``), and the modules behind
     take them directly.  The holder is either already inside the one
@@ -1838,9 +1922,13 @@ def _fold_clamps_into_producers(gm, mods) -> int:
         producer = _module_of(node, mods)
         if not isinstance(producer, IntegerConsumer) or producer.emit_codes_for is not None or len(node.users) != 1:
             continue
-        nxt, act, rng = next(iter(node.users)), None, (-math.inf, math.inf)
+        nxt, act, rng, hard = next(iter(node.users)), None, (-math.inf, math.inf), None
         if _clamp_range(nxt, mods) is not None and len(nxt.users) == 1:
             act, rng = nxt, _clamp_range(nxt, mods)
+            nxt = next(iter(nxt.users))
+        elif hard_activations and _hard_activation(nxt, mods) is not None and len(nxt.users) == 1 \
+                and _takes_hard_activation(producer):
+            act, hard = nxt, _hard_activation(nxt, mods)
             nxt = next(iter(nxt.users))
         if nxt.op != "call_module" or nxt.kwargs:
             continue
@@ -1876,6 +1964,7 @@ def _fold_clamps_into_producers(gm, mods) -> int:
         except ValueError:
             continue
         producer.emit_codes_for, producer.emit_clamp = form, (None if clamp == (form[2], form[3]) else clamp)
+        producer.emit_act = hard                         # (then rng is the whole line and emit_clamp None)
         for r in readers:
             r.args = tuple(node if a is via else a for a in r.args)
         if concat_args is not None:
@@ -2031,7 +2120,8 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
 def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weights: bool = False,
                              convolutions: bool = False, depthwise: bool = False, shared_holders: bool = False,
                              stay_on_codes: bool = False, pools: bool = False, fused_residuals: bool = False,
-                             concats: bool = False, avg_pools: bool = False, muls: bool = False):
+                             concats: bool = False, avg_pools: bool = False, muls: bool = False,
+                             hard_activations: bool = False):
     """The same rewrite on an arbitrary module graph (MCT-exported models are not ``nn.Sequential``): traces ``model``
     with torch.fx keeping wrappers and holders as leaves, and wherever an activation holder's ONLY consumer is a
     wrapped ``nn.Linear`` the integer consumer can take (symmetric, power-of-two or LUT weights, and with
@@ -2146,18 +2236,44 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
     that conv -> ReLU -> A -> {squeeze, multiply} -> M -> conv runs codes to codes; the same tensor at both operands (``x * x``)
     is left to the module's float32 quantize path.  Left alone: a float32 user of M (SE-ResNet's identity add behind M: a
     residual join does not read a QuantizedMul's codes yet); an operand that is no holder's output (``x * sigmoid(y)`` without
-    a holder); anything between the multiply and M; ``div``; scalar operands; folding the sigmoid or hardsigmoid in front of
-    the gate's holder into the product in front of it.  A holder's float32 output is ``float(code - zp) * scale`` bit for bit and
+    a holder); anything between the multiply and M; ``div``; scalar operands; folding a sigmoid in front of the gate's holder
+    into the product in front of it (a hardsigmoid: ``hard_activations=True``, below).  A holder's float32 output is ``float(code - zp) * scale`` bit for bit and
     ``torch.mul`` is one IEEE float32 multiplication, so the codes are bit for bit those M gives the float32 product, for any
     shapes ``torch.mul`` broadcasts (the kernel takes equal shapes and ``[B, C, H, W]`` with ``[B, C, 1, 1]`` where C % 16 == 0,
     everything else torch ops), and the model rewritten with ``muls=True`` returns, bit for bit, what the same rewrite without
     it returns wherever the float32 products of the layers behind M are exact; otherwise it differs by the accumulation
-    rounding of those products, like every wrapped layer that becomes a consumer."""
+    rounding of those products, like every wrapped layer that becomes a consumer.
+
+    ``hard_activations=True`` (needs ``stay_on_codes=True``; ValueError otherwise) keeps the activations on codes across a
+    Hardswish or Hardsigmoid: MobileNetV3's ``conv -> Hardswish -> holder -> conv`` layers, depthwise ones included, and the
+    ``fc2 -> Hardsigmoid -> G -> multiply`` gate of its SE blocks.  Where ``stay_on_codes`` accepts one ReLU / ReLU6 / Hardtanh
+    between a consumer and the readers of a holder's codes, one ``nn.Hardswish`` / ``F.hardswish`` / ``nn.Hardsigmoid`` /
+    ``F.hardsigmoid`` of one tensor that feeds nothing else is accepted too (in-place forms only where nobody else reads the
+    input), with every kind of reader: consumers and pools, a residual-free join that writes no float32, and with ``concats`` /
+    ``muls`` an operand of a QuantizedConcat / QuantizedMul -- the SE gate then reaches ``mctq_codes_mul_nhwc`` as codes instead of
+    float32.  These two activations are no clamps of the codes: the consumer applies them to its float32 value in its own
+    epilogue (``emit_act``; ``mctq_qlinear_i8_act``, ``mctq_qconv_dw_i8_act``) and emits the holder's codes, and the activation and
+    the holder or join leave the graph -- per folded activation ATen's launch, the quantize launch and two float32 tensors.  Left
+    alone: producers the entry points do not take (a product with uniform, 4-bit or LUT weights or one that already takes a
+    residual; the depthwise convolution takes every weight kind); a holder with a float32 reader; an activation whose input
+    has other users; two activations in a row (a join that absorbed a ReLU behind the Hardswish); sigmoid, SiLU, GELU, tanh,
+    which no epilogue can reproduce bit for bit.  The kernels evaluate the float32 expression of ATen's GPU kernels,
+    ``x * min(max(x + 3, 0), 6) * (1.0f / 6.0f)``, equal to them for every float32 bit pattern, on the same float32 value the
+    consumer would have written, so on the GPU the result is bit for bit that of the same rewrite without the switch, NaNs
+    and infinities included.  On the CPU the consumers apply ``F.hardswish`` / ``F.hardsigmoid`` (ATen's CPU kernels divide by 6:
+    another rounding for a quarter of the inputs), so there too the result equals the same rewrite without the switch, while
+    CPU and GPU may differ by one code at a rounding tie, with and without the switch.  Large whole-tile products with an
+    activation run on the tiled kernels, not the faster register-pinned ones (as with a residual): the rewrite has no cost
+    model and folds them all the same (measured on 4096 x 4096 x 256: the tiled launch with the activation 31 us, the
+    register-pinned launch 22 us, the three launches it replaces 54 us together; tools/hard_act_probe.py,
+    profiles/EXPERIMENTS.md)."""
     import torch.fx as fx
     if stay_on_codes and not shared_holders:
         raise ValueError("stay_on_codes=True needs shared_holders=True")
     if fused_residuals and not stay_on_codes:
         raise ValueError("fused_residuals=True needs stay_on_codes=True")
+    if hard_activations and not stay_on_codes:
+        raise ValueError("hard_activations=True needs stay_on_codes=True")
 
     class _Tracer(fx.Tracer):
         def is_leaf_module(self, m, qualname):
@@ -2206,7 +2322,7 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
                     mods[node.target].emit_codes_for = nxt.activation_code_params()
     if stay_on_codes:
         _identities_as_codes(gm, mods)
-        _fold_clamps_into_producers(gm, mods)
+        _fold_clamps_into_producers(gm, mods, hard_activations)
     if fused_residuals:
         _fuse_residuals_into_producers(gm, mods)
     gm.graph.lint()

@@ -55,14 +55,34 @@ __device__ __forceinline__ float join_residual(float d, float scale) {
   return r;
 }
 
+// Hardswish / Hardsigmoid of the float32 epilogue value, in front of ql_code / ql_store (mctq_qlinear_i8_act,
+// mctq_qconv_dw_i8_act).  act: 0 none, 1 hardswish, 2 hardsigmoid.  The expression is the one ATen's GPU kernels evaluate,
+//     hardswish(x) = x * min(max(x + 3, 0), 6) * (1.0f / 6.0f)      hardsigmoid(x) = min(max(x + 3, 0), 6) * (1.0f / 6.0f)
+// left to right, one rounding per operation, with std::max / std::min semantics (a < b ? b : a; a NaN stays a NaN, and
+// hardswish(-inf) = -inf * 0 = NaN) -- equal to F.hardswish / F.hardsigmoid on the GPU for all 2^32 float32 bit patterns
+// (docs/KERNEL_NOTES.md; ATen's CPU kernels divide by 6 instead and differ in a quarter / a thirtieth of the patterns).
+// x * ramp is a float32 VALUE before the multiplication by 1/6: the opaque asm keeps the compiler from ever folding the
+// two constants' side of the chain (x * (ramp * c)), which rounds differently.  The branch on act is uniform over a launch.
+__device__ __forceinline__ float ql_act(float v, int act) {
+  if (act == 0) return v;
+  float t = v + 3.0f;
+  t = t < 0.0f ? 0.0f : t;                            // std::max(t, 0.0f)
+  t = 6.0f < t ? 6.0f : t;                            // std::min(t, 6.0f)
+  if (act == 1) t = v * t;
+  asm("" : "+v"(t));
+  return t * (1.0f / 6.0f);
+}
+
 // The residual operand of a consumer launch (mctq_qlinear_i8_res): [M][N] row-major like y, float32 values or the int8 /
 // uint8 codes of another quantizer with its scale and zero point; relu: v < 0 ? 0 : v behind the add (the join's expression).
+// act: ql_act's, applied last (mctq_qlinear_i8_act: mode 0 -- the instantiations that take this record then skip the add).
 struct QlRes {
   const void* r;
   int mode;                 // 0 none, 1 float32, 2 int8 codes, 3 uint8 codes
   int zp;
   float scale;
   int relu;
+  int act;
 };
 // out (+ residual at idx) (then the ReLU): one float32 add, not contracted (-ffp-contract=off; the code's value is opaque).
 // The branches are uniform over the launch.

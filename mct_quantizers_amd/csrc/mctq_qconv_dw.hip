@@ -6,7 +6,8 @@
 //     acc[b][oy][ox][c] = sum over taps inside the image of (a[b][iy][ix][c] - za) * (w[ky][kx][c] - zw[c])
 //     y = float(acc) * (sa * sw[c]) + bias[c]
 // with the epilogue of mctq_qlinear_i8 (one rounding per float32 operation; -ffp-contract=off) and its output forms
-// (QlOut: float32, or the next layer's codes).
+// (QlOut: float32, or the next layer's codes); mctq_qconv_dw_i8_act puts a Hardswish / Hardsigmoid (ql_act) in front of the
+// codes.
 //
 // Layout: activations NHWC, weights [kh][kw][C], so that 16 consecutive channels are one aligned 16-byte chunk of either.
 // A lane owns one chunk of one output pixel: consecutive lanes take consecutive chunks of a pixel, then consecutive
@@ -44,6 +45,7 @@ struct DwArgs {
   int32_t za;
   float sa;
   QlOut oq;
+  int act;                                         // ql_act's, in front of the codes (mctq_qconv_dw_i8_act); 0 otherwise
 };
 
 typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
@@ -138,7 +140,7 @@ __global__ __launch_bounds__(kThreads) void qconv_dw_kernel(DwArgs a) {
     for (int q = 0; q < 4; ++q) {
       uint32_t v = 0;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) v |= ((uint32_t)ql_code(out[4 * q + j], a.oq) & 0xffu) << (8 * j);
+      for (int j = 0; j < 4; ++j) v |= ((uint32_t)ql_code(ql_act(out[4 * q + j], a.act), a.oq) & 0xffu) << (8 * j);
       codes[q] = v;
     }
     reinterpret_cast<u32x4*>(a.y)[g] = codes;
@@ -157,14 +159,13 @@ static void launch_qconv_dw(const DwArgs& a, unsigned blocks, hipStream_t stream
 
 using namespace mctq;
 
-extern "C" {
-
-int mctq_qconv_dw_i8(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
-                     const int8_t* w_codes, const float* w_scales, const int32_t* w_zero_points, const float* bias,
-                     void* y, int32_t y_code_dtype, float y_scale, int32_t y_zero_point, int32_t y_quant_min, int32_t y_quant_max,
-                     int64_t batch, int64_t height, int64_t width, int64_t channels,
-                     int32_t kh, int32_t kw, int32_t stride_h, int32_t stride_w, int32_t pad_h, int32_t pad_w,
-                     int32_t dil_h, int32_t dil_w, void* stream) {
+// The two entry points' checks and launch.  act: 0 (mctq_qconv_dw_i8) or ql_act's 1 / 2, checked by mctq_qconv_dw_i8_act.
+static int qconv_dw_call(const char* entry, const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
+                         const int8_t* w_codes, const float* w_scales, const int32_t* w_zero_points, const float* bias,
+                         void* y, int32_t y_code_dtype, float y_scale, int32_t y_zero_point, int32_t y_quant_min, int32_t y_quant_max,
+                         int32_t act, int64_t batch, int64_t height, int64_t width, int64_t channels,
+                         int32_t kh, int32_t kw, int32_t stride_h, int32_t stride_w, int32_t pad_h, int32_t pad_w,
+                         int32_t dil_h, int32_t dil_w, void* stream) {
   if (batch < 0 || height < 0 || width < 0 || channels < 0) return fail_arg("negative extent");
   if (kh < 1 || kw < 1) return fail_arg("kernel size below 1");
   if (stride_h < 1 || stride_w < 1) return fail_arg("stride below 1");
@@ -204,17 +205,48 @@ int mctq_qconv_dw_i8(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_p
   a.chunks = (uint32_t)(pixels * c16);
   a.H = (int32_t)height; a.W = (int32_t)width; a.kh = kh; a.kw = kw;
   a.stride_h = stride_h; a.stride_w = stride_w; a.pad_h = pad_h; a.pad_w = pad_w; a.dil_h = dil_h; a.dil_w = dil_w;
-  a.za = a_zero_point; a.sa = a_scale;
+  a.za = a_zero_point; a.sa = a_scale; a.act = act;
   const unsigned blocks = (unsigned)(((int64_t)a.chunks + kThreads - 1) / kThreads);                  // <= 2^24
   const hipStream_t s = (hipStream_t)stream;
   const bool zp = w_zero_points != nullptr;
   if (u8) { if (zp) launch_qconv_dw<true, true>(a, blocks, s); else launch_qconv_dw<true, false>(a, blocks, s); }
   else { if (zp) launch_qconv_dw<false, true>(a, blocks, s); else launch_qconv_dw<false, false>(a, blocks, s); }
   g_note.shape = "qconv_dw"; g_note.op = zp ? (u8 ? "u8 x i8 zp" : "i8 x i8 zp") : (u8 ? "u8 x i8" : "i8 x i8");
+  if (act) {                                       // "u8 x i8 zp hardswish"
+    static thread_local char op_text[40];
+    snprintf(op_text, sizeof(op_text), "%s%s", g_note.op, act == 1 ? " hardswish" : " hardsigmoid");
+    g_note.op = op_text;
+  }
   g_note.unroll = MCTQ_DW_UNROLL3 && kh == 3 && kw == 3 ? 9 : 1; g_note.nt = 0;
   g_note.in_bytes = 1; g_note.out_bytes = a.oq.mode == 0 ? 4 : 1; ++g_note.count;
   if (g_launch_log) log_launch();
-  return check_launch("mctq_qconv_dw_i8");
+  return check_launch(entry);
+}
+
+extern "C" {
+
+int mctq_qconv_dw_i8(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
+                     const int8_t* w_codes, const float* w_scales, const int32_t* w_zero_points, const float* bias,
+                     void* y, int32_t y_code_dtype, float y_scale, int32_t y_zero_point, int32_t y_quant_min, int32_t y_quant_max,
+                     int64_t batch, int64_t height, int64_t width, int64_t channels,
+                     int32_t kh, int32_t kw, int32_t stride_h, int32_t stride_w, int32_t pad_h, int32_t pad_w,
+                     int32_t dil_h, int32_t dil_w, void* stream) {
+  return qconv_dw_call("mctq_qconv_dw_i8", a_codes, a_code_dtype, a_zero_point, a_scale, w_codes, w_scales, w_zero_points, bias, y,
+                       y_code_dtype, y_scale, y_zero_point, y_quant_min, y_quant_max, 0, batch, height, width, channels, kh, kw,
+                       stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, stream);
+}
+
+int mctq_qconv_dw_i8_act(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
+                         const int8_t* w_codes, const float* w_scales, const int32_t* w_zero_points, const float* bias,
+                         void* y, int32_t y_code_dtype, float y_scale, int32_t y_zero_point, int32_t y_quant_min, int32_t y_quant_max,
+                         int32_t act, int64_t batch, int64_t height, int64_t width, int64_t channels,
+                         int32_t kh, int32_t kw, int32_t stride_h, int32_t stride_w, int32_t pad_h, int32_t pad_w,
+                         int32_t dil_h, int32_t dil_w, void* stream) {
+  if (act != 1 && act != 2) return fail_arg("act must be 1 (hardswish) or 2 (hardsigmoid)");
+  if (y_code_dtype < 0) return fail_arg("bad y_code_dtype");      // an activation leaves as codes only
+  return qconv_dw_call("mctq_qconv_dw_i8_act", a_codes, a_code_dtype, a_zero_point, a_scale, w_codes, w_scales, w_zero_points, bias,
+                       y, y_code_dtype, y_scale, y_zero_point, y_quant_min, y_quant_max, act, batch, height, width, channels, kh,
+                       kw, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, stream);
 }
 
 }  // extern "C"

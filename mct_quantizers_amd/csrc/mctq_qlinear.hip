@@ -28,6 +28,10 @@ static void note_ql(const char* shape, int u = 0, bool zp = false, const QlRes* 
     snprintf(op_text, sizeof(op_text), "%s res(%s)%s", g_note.op, res->mode == 1 ? "f32" : res->mode == 2 ? "i8" : "u8",
              res->relu ? " relu" : "");
     g_note.op = op_text;
+  } else if (res && res->act) {           // the activation form ran (mctq_qlinear_i8_act): "u8 x i8 hardswish"
+    static thread_local char op_text[40];
+    snprintf(op_text, sizeof(op_text), "%s%s", g_note.op, res->act == 1 ? " hardswish" : " hardsigmoid");
+    g_note.op = op_text;
   }
   g_note.unroll = u; g_note.nt = 0;
   g_note.in_bytes = 1; g_note.out_bytes = 4; ++g_note.count;
@@ -142,7 +146,7 @@ __device__ __forceinline__ i32x4 ql_unpack_lut4(i32x2 x, const QlLut& c) {
 }
 __device__ __forceinline__ QlLut ql_lut_arg() { return QlLut{{0, 0, 0, 0}}; }
 __device__ __forceinline__ QlLut ql_lut_arg(const QlLut& c) { return c; }
-__device__ __forceinline__ QlRes ql_res_arg() { return QlRes{nullptr, 0, 0, 0.0f, 0}; }
+__device__ __forceinline__ QlRes ql_res_arg() { return QlRes{nullptr, 0, 0, 0.0f, 0, 0}; }
 __device__ __forceinline__ const QlRes& ql_res_arg(const QlRes& r) { return r; }
 enum { kQlW8 = 0, kQlW4 = 1, kQlLut4 = 2 };      // weight formats of the streaming kernel
 
@@ -299,8 +303,9 @@ __global__ __launch_bounds__(kQlWaves * 64) void qlinear_i8_kernel(
 typedef __attribute__((address_space(3))) void ql_lds_void_;
 typedef const __attribute__((address_space(1))) void ql_glb_void_;
 
-// Res: empty, or one QlRes -- the residual form (mctq_qlinear_i8_res), a trailing kernel argument that the other
-// instantiations do not have; it is read in the epilogue only.
+// Res: empty, or one QlRes -- the residual form (mctq_qlinear_i8_res) and the activation form (mctq_qlinear_i8_act: the
+// record's mode is 0 and the add is branched out), a trailing kernel argument that the other instantiations do not have; it
+// is read in the epilogue only.
 template <int kQlWaves, int MT, bool A_U8, bool W_NT, bool ZP = false, class... Res>
 __global__ __launch_bounds__(kQlWaves * 64) void qlinear_i8_lds_kernel(
     const int8_t* __restrict__ a, const int8_t* __restrict__ w, const float* __restrict__ w_scales,
@@ -432,7 +437,11 @@ __global__ __launch_bounds__(kQlWaves * 64) void qlinear_i8_lds_kernel(
       if (m < M && n < N) {
         float out = (float)ql_corrected<ZP>(v, e_corr, e_zw, zp, m) * e_scale;
         if (bias) out = out + e_bias;
-        if constexpr (RES) out = ql_join(out, ql_residual_at(ql_res_arg(res...), (int64_t)m * N + n), ql_res_arg(res...));
+        if constexpr (RES) {                   // (+ residual) (ReLU) (activation): branches uniform over the launch
+          if (ql_res_arg(res...).mode)
+            out = ql_join(out, ql_residual_at(ql_res_arg(res...), (int64_t)m * N + n), ql_res_arg(res...));
+          out = ql_act(out, ql_res_arg(res...).act);
+        }
         ql_store(y, (int64_t)m * N + n, out, oq);
       }
     }
@@ -473,7 +482,7 @@ static int launch_qlinear_lds(const QlCall& c) {
                      MCTQ_QL_ARGS(c), c.oq, c.zp, c.res)
   // (the residual form last: the kernels are emitted in the order in which they are named here)
   if (c.zp.a_rowsum) { if (one_pass) MCTQ_QL_LDS(true, true); else MCTQ_QL_LDS(false, true); }
-  else if (!c.res.mode) { if (one_pass) MCTQ_QL_LDS(true, false); else MCTQ_QL_LDS(false, false); }
+  else if (!c.res.mode && !c.res.act) { if (one_pass) MCTQ_QL_LDS(true, false); else MCTQ_QL_LDS(false, false); }
   else { if (one_pass) MCTQ_QL_LDS_RES(true); else MCTQ_QL_LDS_RES(false); }
 #undef MCTQ_QL_LDS_RES
 #undef MCTQ_QL_LDS
@@ -724,7 +733,7 @@ __global__ __launch_bounds__(256 * KG) void qgemm_i8_glds_kernel(
 #pragma unroll
         for (int i = 0; i < 4; ++i) at[4 * t + i] = (int64_t)min(m0 + wm * (BM / 2) + 16 * t + 4 * g + i, M - 1) * N + n;
       }
-      ql_residuals<TM * 4>(ql_res_arg(res...), at, e_res);
+      if (ql_res_arg(res...).mode) ql_residuals<TM * 4>(ql_res_arg(res...), at, e_res);      // (mode 0: the activation form)
     }
 #pragma unroll
     for (int t = 0; t < TM; ++t) {
@@ -734,7 +743,10 @@ __global__ __launch_bounds__(256 * KG) void qgemm_i8_glds_kernel(
         if (m < M) {
           float out = (float)ql_corrected<ZP>(acc[t][u][i], e_corr[u], e_zw, zp, m) * e_scale[u];
           if (bias) out = out + e_bias[u];
-          if constexpr (RES) out = ql_join(out, e_res[4 * t + i], ql_res_arg(res...));
+          if constexpr (RES) {
+            if (ql_res_arg(res...).mode) out = ql_join(out, e_res[4 * t + i], ql_res_arg(res...));
+            out = ql_act(out, ql_res_arg(res...).act);
+          }
           ql_store(y, (int64_t)m * N + n, out, oq);
         }
       }
@@ -758,8 +770,8 @@ static int launch_glds(const QlCall& c) {
   hipLaunchKernelGGL((qgemm_i8_glds_kernel<BM, BN, BK, A_U8, ST, KG, ZP_>), dim3((unsigned)(mbl * nbl)), dim3(256 * KG), 0, c.stream, \
                      MCTQ_QL_ARGS(c), mbl, nbl, gm, flags, c.oq, c.zp)
   if (c.zp.a_rowsum) MCTQ_QL_GLDS(true);
-  else if (!c.res.mode) MCTQ_QL_GLDS(false);
-  else          // the residual form (last: the kernels are emitted in the order in which they are named here)
+  else if (!c.res.mode && !c.res.act) MCTQ_QL_GLDS(false);
+  else          // the residual / activation form (last: the kernels are emitted in the order in which they are named here)
     hipLaunchKernelGGL((qgemm_i8_glds_kernel<BM, BN, BK, A_U8, ST, KG, false, QlRes>), dim3((unsigned)(mbl * nbl)), dim3(256 * KG), 0,
                        c.stream, MCTQ_QL_ARGS(c), mbl, nbl, gm, flags, c.oq, c.zp, c.res);
 #undef MCTQ_QL_GLDS
@@ -1222,9 +1234,10 @@ enum QlModel {
 };
 enum { kQlWholeTiles = 1,      // only M % bm == N % bn == K % 128 == 0 and K >= 256
        kQlNoZeroPoints = 2,    // not built for calls that bring weight zero points
-       kQlNoResidual = 4 };    // not built for calls that bring a residual (mctq_qlinear_i8_res)
+       kQlNoResidual = 4,      // not built for calls that bring a residual (mctq_qlinear_i8_res)
+       kQlNoActivation = 8 };  // not built for calls that bring a Hardswish / Hardsigmoid (mctq_qlinear_i8_act)
 // what a call needs, as the mask of the rule bits that exclude a kernel from it
-constexpr unsigned kQlNeeds = kQlNoZeroPoints | kQlNoResidual;
+constexpr unsigned kQlNeeds = kQlNoZeroPoints | kQlNoResidual | kQlNoActivation;
 struct QlKernel {
   int variant;            // tuning key "ql_variant"
   QlLaunch launch[2];     // uint8 / int8 activation codes
@@ -1247,8 +1260,8 @@ struct QlKernel {
 // Many rows and columns, whole tiles: the 256 x 256 ping-pong kernel (2.2-2.3 POP/s against 1.5 for the 128 x 128
 // tiles; profiles/r02/qgemm_wide_probe.log) or, when there are too few such tiles for the chip, 128 x 256 wave-wide
 // tiles -- weighed by how full their last round of blocks is (one block per CU; the 128 x 128 kernel fits two).
-// (Zero-point weights and residuals: those two kernels and the pinned 128 x 128 candidate do not take them; the tiled
-// kernels do.)
+// (Zero-point weights, residuals and activations: those two kernels and the pinned 128 x 128 candidate do not take them; the
+// tiled kernels do.)
 static const QlKernel kQlKernels[] = {
     // variant, {launcher for uint8, for int8 codes}, model, turn, bm, bn, occ, {rates}[, rules[, m_lo, m_hi]]
     // weight streaming, activation codes through per-wave LDS: 16 / 32 / 64 rows per pass.  A block = 16 weight rows + 16 MT
@@ -1270,10 +1283,10 @@ static const QlKernel kQlKernels[] = {
     {1212, {launch_glds<128, 128, 128, true>, launch_glds<128, 128, 128, false>}, kQlTiles, 11, 128, 128, 2, {30, 48}},
     {662, {launch_glds<64, 64, 256, true>, launch_glds<64, 64, 256, false>}, kQlTiles, 6, 64, 64, 2, {36, 54}},   // two blocks per CU
     // wave-wide 128 x 128 / 128 x 256 tiles
-    {2544, {launch_wide<4, 4, true>, launch_wide<4, 4, false>}, kQlTiles, 12, 128, 128, 2, {38, 43}, kQlWholeTiles | kQlNoZeroPoints | kQlNoResidual},
-    {2548, {launch_wide<4, 8, true>, launch_wide<4, 8, false>}, kQlByFill, 14, 128, 256, 1, {2.0}, kQlWholeTiles | kQlNoZeroPoints | kQlNoResidual},
+    {2544, {launch_wide<4, 4, true>, launch_wide<4, 4, false>}, kQlTiles, 12, 128, 128, 2, {38, 43}, kQlWholeTiles | kQlNoZeroPoints | kQlNoResidual | kQlNoActivation},
+    {2548, {launch_wide<4, 8, true>, launch_wide<4, 8, false>}, kQlByFill, 14, 128, 256, 1, {2.0}, kQlWholeTiles | kQlNoZeroPoints | kQlNoResidual | kQlNoActivation},
     // 256 x 256 ping-pong tiles
-    {2560, {launch_pp<true>, launch_pp<false>}, kQlByFill, 13, 256, 256, 1, {2.25}, kQlWholeTiles | kQlNoZeroPoints | kQlNoResidual},
+    {2560, {launch_pp<true>, launch_pp<false>}, kQlByFill, 13, 256, 256, 1, {2.25}, kQlWholeTiles | kQlNoZeroPoints | kQlNoResidual | kQlNoActivation},
 };
 
 static bool ql_admits(const QlKernel& k, int64_t M, int64_t N, int64_t K, unsigned needs) {
@@ -1336,7 +1349,8 @@ static bool ql_check_call(QlCall& c, int32_t a_code_dtype, bool with_zp, bool pa
   return true;
 }
 
-// needs: kQlNoZeroPoints for a call with weight zero points, kQlNoResidual for one with a residual (checked by its entry point)
+// needs: kQlNoZeroPoints for a call with weight zero points, kQlNoResidual for one with a residual, kQlNoActivation for one
+// with a Hardswish / Hardsigmoid (each checked by its entry point)
 static int qlinear_dispatch(QlCall c, int32_t a_code_dtype, unsigned needs) {
   int rc;
   if (!ql_check_call(c, a_code_dtype, (needs & kQlNoZeroPoints) != 0, false, rc)) return rc;
@@ -1350,6 +1364,8 @@ static int qlinear_dispatch(QlCall c, int32_t a_code_dtype, unsigned needs) {
         return fail_arg("the register-pinned whole-tile kernels (ql_variant 2544 / 2548 / 2560) are not built for zero-point weights");
       if (k.rules & needs & kQlNoResidual)
         return fail_arg("the register-pinned whole-tile kernels (ql_variant 2544 / 2548 / 2560) are not built for a residual");
+      if (k.rules & needs & kQlNoActivation)
+        return fail_arg("the register-pinned whole-tile kernels (ql_variant 2544 / 2548 / 2560) are not built for an activation");
       return k.launch[which](c);
     }
   return ql_choose(c.M, c.N, c.K, needs, cu_count())->launch[which](c);
@@ -1372,7 +1388,7 @@ static int qlinear_packed4(QlCall c, int32_t a_code_dtype, bool with_zp, const Q
 // The entry points' arguments as a call record that is not checked yet: a_zero_point as given, float32 output.
 #define MCTQ_QL_CALL(w_, zw_, ar_)                                                                                      \
   QlCall c{a_codes, reinterpret_cast<const int8_t*>(w_), w_scales, w_rowsum, bias, y, M, N, K, a_zero_point, a_scale, \
-           QlOut{}, QlZp{zw_, ar_}, (hipStream_t)stream, QlRes{nullptr, 0, 0, 0.0f, 0}}
+           QlOut{}, QlZp{zw_, ar_}, (hipStream_t)stream, QlRes{nullptr, 0, 0, 0.0f, 0, 0}}
 
 extern "C" {
 
@@ -1483,8 +1499,20 @@ int mctq_qlinear_i8_res(const void* a_codes, int32_t a_code_dtype, int32_t a_zer
       if (yb < re && rb < ye) return fail_arg("y overlaps the residual");
     }
   }
-  c.res = QlRes{residual, r_code_dtype < 0 ? 1 : r_code_dtype == MCTQ_CODE_I8 ? 2 : 3, (int)r_zero_point, r_scale, relu != 0};
+  c.res = QlRes{residual, r_code_dtype < 0 ? 1 : r_code_dtype == MCTQ_CODE_I8 ? 2 : 3, (int)r_zero_point, r_scale, relu != 0, 0};
   return qlinear_dispatch(c, a_code_dtype, kQlNoResidual);
+}
+
+int mctq_qlinear_i8_act(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
+                        const int8_t* w_codes, const float* w_scales, const int32_t* w_rowsum, const float* bias,
+                        void* y, int32_t y_code_dtype, float y_scale, int32_t y_zero_point, int32_t y_quant_min,
+                        int32_t y_quant_max, int32_t act, int64_t M, int64_t N, int64_t K, void* stream) {
+  if (act != 1 && act != 2) return fail_arg("act must be 1 (hardswish) or 2 (hardsigmoid)");
+  if (y_code_dtype < 0) return fail_arg("bad y_code_dtype");      // an activation leaves as codes only
+  MCTQ_QL_CALL(w_codes, nullptr, nullptr);
+  if (int rc = ql_output_form(c.oq, y_code_dtype, y_scale, y_zero_point, y_quant_min, y_quant_max)) return rc;
+  c.res.act = act;
+  return qlinear_dispatch(c, a_code_dtype, kQlNoActivation);
 }
 #undef MCTQ_QL_CALL
 

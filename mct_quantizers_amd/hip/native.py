@@ -56,8 +56,8 @@ class ConcatItem(ctypes.Structure):
                 ("zero_point", ctypes.c_int32), ("scale", ctypes.c_float)]
 
 
-def _ql_signature(lut=False, form=True, zp=False, res=False):
-    """The integer consumer's entry points (mctq_qlinear_*) share their argument list up to four optional groups."""
+def _ql_signature(lut=False, form=True, zp=False, res=False, act=False):
+    """The integer consumer's entry points (mctq_qlinear_*) share their argument list up to five optional groups."""
     return ctypes.c_int, (
         [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,      # a_codes, a_code_dtype, a_zero_point, a_scale
          ctypes.c_void_p]                                                       # w_codes / w_codes4 / w_idx4
@@ -67,6 +67,7 @@ def _ql_signature(lut=False, form=True, zp=False, res=False):
         + [ctypes.c_void_p]                                                     # y
         + ([ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32] if form else [])   # y_code_dtype, y_scale, y_zero_point, y_quant_min, y_quant_max
         + ([_c_i32p, _c_i32p] if zp else [])                                    # w_zero_points, a_rowsum
+        + ([ctypes.c_int32] if act else [])                                     # act
         + [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p])    # M, N, K, stream
 
 
@@ -136,6 +137,7 @@ SIGNATURES = {
     "mctq_qlinear_i8_zp": _ql_signature(zp=True),
     "mctq_qlinear_w4a8_zp": _ql_signature(zp=True),
     "mctq_qlinear_i8_res": _ql_signature(res=True),
+    "mctq_qlinear_i8_act": _ql_signature(act=True),
     "mctq_fq_codes_nchw_to_nhwc": (ctypes.c_int, [_c_f32p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                                   ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_int32,
                                                   ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
@@ -159,6 +161,11 @@ SIGNATURES = {
                                         ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_int32,
                                         ctypes.c_int32]                                                      # y and its output form
                          + [ctypes.c_int64] * 4 + [ctypes.c_int32] * 8 + [ctypes.c_void_p]),                # B, H, W, C; geometry; stream
+    "mctq_qconv_dw_i8_act": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,   # as mctq_qconv_dw_i8 ...
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_int32,
+                                            ctypes.c_int32, ctypes.c_int32]                                   # ... and act behind the output form
+                             + [ctypes.c_int64] * 4 + [ctypes.c_int32] * 8 + [ctypes.c_void_p]),
     "mctq_fq_join_f32": (ctypes.c_int, [_c_f32p, _c_f32p, ctypes.c_int32, _c_f32p, ctypes.c_void_p, ctypes.c_int32,   # x, residual, relu, y, codes, code_dtype
                                         ctypes.c_int64, ctypes.c_float, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                         ctypes.c_void_p]),                                                            # n, scale, zero_point, qmin, qmax, stream
