@@ -95,12 +95,15 @@ The four modules derive from ``IntegerConsumer``, which owns what they share: th
 weight and bias, the cache of the weight's codes, the step from ``forward``'s input to activation codes, ``from_wrapper`` and
 the ``emit_codes_for`` / ``emit_clamp`` output form.  ``QuantizedLinear`` is the product over ``[O, K]`` rows; ``QuantizedConv1x1``
 and ``QuantizedConv2d`` are that product and derive from it; ``QuantizedDepthwiseConv2d`` is not and derives from
-``IntegerConsumer`` directly.  "Any integer consumer" in the graph rewrites is ``isinstance(m, IntegerConsumer)``.
+``IntegerConsumer`` directly.  "Any integer consumer" in the graph rewrites is ``isinstance(m, IntegerConsumer)``.  The modules
+without weights -- the pools, ``QuantizedConcat``, ``QuantizedMul``, ``QuantizedJoin`` -- derive from ``_OnCodes``;
+``_operand_codes`` is the one step from an operand of ``forward`` to codes, theirs and the consumers' (the join has its own kernel).
 
 CPU tensors run the same integer arithmetic with torch ops (host logic for tests, bit-identical to the kernel).
 """
 import math
-from typing import Optional
+import operator
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -479,6 +482,28 @@ def _is_uniform_weights(q) -> bool:
     return isinstance(q, WeightsUniformInferableQuantizer)
 
 
+def _operand_codes(x, form, who, whose, *, at="", nhwc=True, float32_only=True):
+    """An operand of ``forward`` as contiguous codes of ``form = (scale, zero_point, qmin, qmax)``.  int8 / uint8 tensors already
+    are codes and must be of the form's type (TypeError: "... do not match ``whose``", behind ``at``); anything else is quantized
+    with the form -- with ``float32_only`` only float32, every other dtype is ``who``'s TypeError.  With ``nhwc`` a 4-D operand
+    (codes: NCHW-shaped, NHWC-stored) gives contiguous [N, H, W, C] codes, copied only where they are not; everything else keeps
+    its shape."""
+    scale, zp, qmin, qmax = form
+    nhwc = nhwc and x.dim() == 4
+    if x.dtype in (torch.uint8, torch.int8):
+        if x.dtype != ops._code_dtype(qmin, qmax)[0]:
+            raise TypeError(f"{at}activation codes of type {x.dtype} do not match {whose}")
+        if not nhwc:
+            return x
+        codes = x.permute(0, 2, 3, 1)
+        return codes if codes.is_contiguous() else codes.contiguous()
+    if float32_only and x.dtype != torch.float32:
+        raise TypeError(f"{who} takes float32 tensors or activation codes, got {x.dtype}")
+    if nhwc:
+        return ops.fq_codes_nhwc(x, qmin, qmax, scale, zp)
+    return ops.fq_codes(x, None, None, None, qmin, qmax, scale, zp)
+
+
 class IntegerConsumer(nn.Module):
     """``activation quantizer -> PytorchQuantizationWrapper(layer)`` evaluated on integer codes: what the four consumers share.
 
@@ -620,16 +645,7 @@ class IntegerConsumer(nn.Module):
         """``forward``'s input as this layer's activation codes.  int8 / uint8 tensors already are codes (chained layers) and
         must be of the quantizer's type; anything else is quantized.  2-D rows stay rows; an [N, C, H, W] tensor (codes:
         NCHW-shaped, NHWC-stored) gives contiguous [N, H, W, C] codes."""
-        if x.dtype in (torch.uint8, torch.int8):
-            if x.dtype != ops._code_dtype(self._a_qmin, self._a_qmax)[0]:
-                raise TypeError(f"activation codes of type {x.dtype} do not match this layer's quantizer")
-            if x.dim() != 4:
-                return x
-            codes = x.permute(0, 2, 3, 1)
-            return codes if codes.is_contiguous() else codes.contiguous()
-        if x.dim() == 4:
-            return ops.fq_codes_nhwc(x, self._a_qmin, self._a_qmax, self._a_scale, self._a_zp)
-        return ops.fq_codes(x, None, None, None, self._a_qmin, self._a_qmax, self._a_scale, self._a_zp)
+        return _operand_codes(x, self.activation_code_params(), type(self).__name__, "this layer's quantizer", float32_only=False)
 
     def _bias_for(self, codes):
         """The bias as the kernels read it, a contiguous float32 tensor on the codes' device, or None."""
@@ -847,7 +863,12 @@ def _ints_or_pair(v) -> bool:
     return one(v) or (isinstance(v, (tuple, list)) and len(v) == 2 and all(one(e) for e in v))
 
 
-class QuantizedMaxPool2d(nn.Module):
+class _OnCodes(nn.Module):
+    """Base of the modules without weights that read or write activation codes -- the pools, QuantizedConcat, QuantizedMul and
+    QuantizedJoin: with the wrappers, the holders and the integer consumers, the leaves of the graph rewrite's tracer."""
+
+
+class QuantizedMaxPool2d(_OnCodes):
     """``activation holder -> nn.MaxPool2d`` on integer codes, for the integer consumers behind the pool.  The holder's float32
     output is ``float(code - zp) * scale`` with ``scale > 0``: monotone non-decreasing in the code and never NaN, so the pool of
     the holder's output is the dequantized pool of the codes bit for bit, and the layers behind see a tensor whose codes are the
@@ -898,15 +919,7 @@ class QuantizedMaxPool2d(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if x.dim() != 4:
             raise RuntimeError(f"expected [N, C, H, W], got {tuple(x.shape)}")
-        if x.dtype in (torch.uint8, torch.int8):
-            if x.dtype != ops._code_dtype(self._a_qmin, self._a_qmax)[0]:
-                raise TypeError(f"activation codes of type {x.dtype} do not match this pool's quantizer")
-            codes = x.permute(0, 2, 3, 1)
-            codes = codes if codes.is_contiguous() else codes.contiguous()
-        elif x.dtype == torch.float32:
-            codes = ops.fq_codes_nhwc(x, self._a_qmin, self._a_qmax, self._a_scale, self._a_zp)
-        else:
-            raise TypeError(f"QuantizedMaxPool2d takes float32 tensors or activation codes, got {x.dtype}")
+        codes = _operand_codes(x, self.activation_code_params(), "QuantizedMaxPool2d", "this pool's quantizer")
         y = ops.codes_maxpool(codes, self.kernel_size, self.stride, self.padding, self.dilation, self.ceil_mode)
         return y.permute(0, 3, 1, 2)
 
@@ -925,7 +938,7 @@ def _code_form(q):
     return scale, zp, qmin, qmax
 
 
-class QuantizedAvgPool2d(nn.Module):
+class QuantizedAvgPool2d(_OnCodes):
     """``activation holder A -> average pool -> activation holder B`` on integer codes, for the integer consumers behind B.
     A's float32 output is ``float(code - zp_a) * scale_a`` bit for bit, so the sum of a window is ``scale_a`` times the exact
     integer sum S of ``code - zp_a`` over its taps inside the image (a padded tap is 0.0 and adds nothing), and B codes the mean:
@@ -1012,21 +1025,37 @@ class QuantizedAvgPool2d(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if x.dim() != 4:
             raise RuntimeError(f"expected [N, C, H, W], got {tuple(x.shape)}")
-        if x.dtype in (torch.uint8, torch.int8):
-            if x.dtype != ops._code_dtype(self._a_qmin, self._a_qmax)[0]:
-                raise TypeError(f"activation codes of type {x.dtype} do not match this pool's input quantizer")
-            codes = x.permute(0, 2, 3, 1)
-            codes = codes if codes.is_contiguous() else codes.contiguous()
-        elif x.dtype == torch.float32:
-            codes = ops.fq_codes_nhwc(x, self._a_qmin, self._a_qmax, self._a_scale, self._a_zp)
-        else:
-            raise TypeError(f"QuantizedAvgPool2d takes float32 tensors or activation codes, got {x.dtype}")
+        codes = _operand_codes(x, self.activation_code_params(), "QuantizedAvgPool2d", "this pool's input quantizer")
         y = ops.codes_avgpool(codes, (self._a_scale, self._a_zp), self._out_form, self.kernel_size, self.stride, self.padding,
                               self.ceil_mode, self.count_include_pad, self.divisor_override)
         return y.reshape(y.shape[0], y.shape[3]) if self.flatten else y.permute(0, 3, 1, 2)
 
 
-class QuantizedConcat(nn.Module):
+class _OperandsOnCodes(_OnCodes):
+    """What QuantizedConcat and QuantizedMul share: several operands, each read as the codes of its own holder's quantizer,
+    and one output holder's quantizer, all per-tensor affine of at most 8 bits (``_code_form``)."""
+
+    def __init__(self, operand_quantizers, activation_quantizer):
+        super().__init__()
+        self.operand_quantizers = tuple(operand_quantizers)
+        self.activation_quantizer = activation_quantizer
+        self._forms = tuple(_code_form(q) for q in self.operand_quantizers)
+        self._out_form = _code_form(activation_quantizer)
+
+    def operand_code_params(self, i: int):
+        """(scale, zero_point, qmin, qmax) of the codes operand ``i`` is read as."""
+        return self._forms[i]
+
+    def activation_code_params(self):
+        """(scale, zero_point, qmin, qmax) of the codes ``forward`` returns: what the consumers and pools behind read."""
+        return self._out_form
+
+    def _codes_of(self, i: int, x: torch.Tensor, nhwc: bool = True):
+        """Operand ``i`` as codes: given codes as they are, float32 quantized in its form; ``nhwc``: 4-D ones as [B, H, W, C]."""
+        return _operand_codes(x, self._forms[i], type(self).__name__, "its quantizer", at=f"operand {i}: ", nhwc=nhwc)
+
+
+class QuantizedConcat(_OperandsOnCodes):
     """``activation holders -> torch.cat(..., dim=1) -> activation holder`` on integer codes, for the integer consumers and
     pools behind that holder.  An operand holder's float32 output is ``float(code - zp_i) * scale_i`` bit for bit
     (``ops.dequantize_codes``), ``torch.cat`` only moves data, and the holder behind it codes every element by itself, so the
@@ -1045,30 +1074,13 @@ class QuantizedConcat(nn.Module):
     what ``emit_codes_for`` of the layer in front of operand ``i`` takes."""
 
     def __init__(self, operand_quantizers, activation_quantizer):
-        super().__init__()
         operand_quantizers = tuple(operand_quantizers)
         if not operand_quantizers:
             raise ValueError("QuantizedConcat needs at least one operand")
         for q in (*operand_quantizers, activation_quantizer):
             if getattr(q, "num_bits", 9) > 8:
                 raise NotImplementedError("codes wider than 8 bits")
-        self.operand_quantizers = operand_quantizers
-        self.activation_quantizer = activation_quantizer
-        self._forms = tuple(self._form_of(q) for q in operand_quantizers)
-        self._out_form = self._form_of(activation_quantizer)
-
-    @staticmethod
-    def _form_of(q):
-        """(scale, zero_point, qmin, qmax) of a quantizer whose codes and zero point are 8-bit codes of one type."""
-        return _code_form(q)
-
-    def operand_code_params(self, i: int):
-        """(scale, zero_point, qmin, qmax) of the codes operand ``i`` is read as."""
-        return self._forms[i]
-
-    def activation_code_params(self):
-        """(scale, zero_point, qmin, qmax) of the codes ``forward`` returns: what the consumers and pools behind read."""
-        return self._out_form
+        super().__init__(operand_quantizers, activation_quantizer)
 
     def extra_repr(self) -> str:
         return f"operands={len(self._forms)}"
@@ -1080,28 +1092,16 @@ class QuantizedConcat(nn.Module):
         if first.dim() not in (2, 4):
             raise RuntimeError(f"expected [N, C, H, W] or [M, C] operands, got {tuple(first.shape)}")
         parts = []
-        for i, (x, (scale, zp, qmin, qmax)) in enumerate(zip(xs, self._forms)):
+        for i, (x, (scale, zp, _, _)) in enumerate(zip(xs, self._forms)):
             if x.dim() != first.dim() or x.shape[0] != first.shape[0] or x.shape[2:] != first.shape[2:]:
                 raise RuntimeError(f"operand {i} is {tuple(x.shape)} next to {tuple(first.shape)}: the operands of a concatenation "
                                    f"along dimension 1 differ in that dimension only")
-            if x.dtype in (torch.uint8, torch.int8):
-                if x.dtype != ops._code_dtype(qmin, qmax)[0]:
-                    raise TypeError(f"operand {i}: activation codes of type {x.dtype} do not match its quantizer")
-                codes = x
-                if x.dim() == 4:
-                    codes = x.permute(0, 2, 3, 1)
-                    codes = codes if codes.is_contiguous() else codes.contiguous()
-            elif x.dtype == torch.float32:
-                codes = ops.fq_codes_nhwc(x, qmin, qmax, scale, zp) if x.dim() == 4 else \
-                    ops.fq_codes(x, None, None, None, qmin, qmax, scale, zp)
-            else:
-                raise TypeError(f"QuantizedConcat takes float32 tensors or activation codes, got {x.dtype}")
-            parts.append((codes, scale, zp))
+            parts.append((self._codes_of(i, x), scale, zp))
         y = ops.codes_concat(parts, self._out_form)
         return y.permute(0, 3, 1, 2) if first.dim() == 4 else y
 
 
-class QuantizedMul(nn.Module):
+class QuantizedMul(_OperandsOnCodes):
     """``activation holders A, G -> torch.mul -> activation holder M`` on integer codes, for the integer consumers and pools
     behind M: the multiply of a squeeze-and-excitation block, a gated layer.  A holder's float32 output is
     ``float(code - zp) * scale`` bit for bit (``ops.dequantize_codes``), ``torch.mul`` is one IEEE float32 multiplication and M
@@ -1122,57 +1122,27 @@ class QuantizedMul(nn.Module):
     ``operand_code_params(i)`` is what ``emit_codes_for`` of the layer in front of operand ``i`` takes."""
 
     def __init__(self, operand_quantizers, activation_quantizer):
-        super().__init__()
         operand_quantizers = tuple(operand_quantizers)
         if len(operand_quantizers) != 2:
             raise ValueError("QuantizedMul takes the quantizers of two operands")
-        self.operand_quantizers = operand_quantizers
-        self.activation_quantizer = activation_quantizer
-        self._forms = tuple(_code_form(q) for q in operand_quantizers)
-        self._out_form = _code_form(activation_quantizer)
-
-    def operand_code_params(self, i: int):
-        """(scale, zero_point, qmin, qmax) of the codes operand ``i`` is read as."""
-        return self._forms[i]
-
-    def activation_code_params(self):
-        """(scale, zero_point, qmin, qmax) of the codes ``forward`` returns: what the consumers and pools behind read."""
-        return self._out_form
-
-    def _codes_of(self, i: int, x: torch.Tensor, nhwc: bool):
-        """Operand ``i`` as codes: given codes as they are, float32 quantized in its form; ``nhwc``: 4-D ones as [B, H, W, C]."""
-        scale, zp, qmin, qmax = self._forms[i]
-        if x.dtype in (torch.uint8, torch.int8):
-            if x.dtype != ops._code_dtype(qmin, qmax)[0]:
-                raise TypeError(f"operand {i}: activation codes of type {x.dtype} do not match its quantizer")
-            if nhwc and x.dim() == 4:
-                x = x.permute(0, 2, 3, 1)
-                x = x if x.is_contiguous() else x.contiguous()
-            return x
-        if x.dtype != torch.float32:
-            raise TypeError(f"QuantizedMul takes float32 tensors or activation codes, got {x.dtype}")
-        if nhwc and x.dim() == 4:
-            return ops.fq_codes_nhwc(x, qmin, qmax, scale, zp)
-        return ops.fq_codes(x, None, None, None, qmin, qmax, scale, zp)
+        super().__init__(operand_quantizers, activation_quantizer)
 
     def forward(self, x0: torch.Tensor, x1: torch.Tensor) -> torch.Tensor:
         xs = (x0, x1)
         (s0, z0, _, _), (s1, z1, _, _) = self._forms
         is_gate = lambda g, a: (a.dim() == 4 and g.dim() == 4 and g.shape[:2] == a.shape[:2]              # noqa: E731
                                 and tuple(g.shape[2:]) == (1, 1) and g.shape != a.shape)
-        if x0.shape == x1.shape and x0.dim() in (2, 4):
-            y = ops.codes_mul((self._codes_of(0, x0, True), s0, z0), (self._codes_of(1, x1, True), s1, z1), self._out_form)
-        elif is_gate(x1, x0) or is_gate(x0, x1):
+        if is_gate(x1, x0) or is_gate(x0, x1):
             at = 0 if is_gate(x1, x0) else 1                     # the large operand; the multiplication is commutative
             gate, (gs, gz, gmin, gmax) = xs[1 - at], self._forms[1 - at]
-            big = (self._codes_of(at, xs[at], True), *self._forms[at][:2])
+            big = (self._codes_of(at, xs[at]), *self._forms[at][:2])
             if gate.dtype == torch.float32:
                 y = ops.codes_mul(big, (gate.permute(0, 2, 3, 1), gs, gz), self._out_form, gate_form=(gmin, gmax))
             else:
-                y = ops.codes_mul(big, (self._codes_of(1 - at, gate, True), gs, gz), self._out_form)
+                y = ops.codes_mul(big, (self._codes_of(1 - at, gate), gs, gz), self._out_form)
         elif x0.dim() == x1.dim() == 4:
-            y = ops.codes_mul((self._codes_of(0, x0, True), s0, z0), (self._codes_of(1, x1, True), s1, z1), self._out_form)
-        else:                                                    # operands of different rank: as torch.mul sees them
+            y = ops.codes_mul((self._codes_of(0, x0), s0, z0), (self._codes_of(1, x1), s1, z1), self._out_form)
+        else:                                                    # rows, or operands of different rank: as torch.mul sees them
             y = ops.codes_mul((self._codes_of(0, x0, False), s0, z0), (self._codes_of(1, x1, False), s1, z1), self._out_form)
             return y.contiguous(memory_format=torch.channels_last) if y.dim() == 4 else y
         return y.permute(0, 3, 1, 2) if y.dim() == 4 else y
@@ -1213,7 +1183,8 @@ _CODE_READERS = (IntegerConsumer, QuantizedMaxPool2d, QuantizedAvgPool2d)
 
 
 class _FusedAway(nn.Identity):
-    """Placeholder left where an activation holder was folded into the QuantizedLinear after it."""
+    """Placeholder ``fuse_linear_consumers`` leaves in an ``nn.Sequential`` where a module went into the one behind it: an
+    activation holder in front of a consumer or a pool, an average pool's second holder, a flatten."""
 
 
 def _module_of(node, mods):
@@ -1234,66 +1205,44 @@ def _plain_holder(m) -> bool:
     return isinstance(m, PytorchActivationQuantizationHolder) and not getattr(m, "quantization_bypass", False)
 
 
-def _pool_of(node, mods):
-    """The ``nn.MaxPool2d`` that ``node`` applies to its one tensor operand -- a call of such a module, or ``F.max_pool2d`` with
-    constant arguments, for which one is built -- if QuantizedMaxPool2d can take it, else None."""
+def _holder_of(node, mods):
+    """The plain holder ``node`` calls on one tensor -- a ``call_module`` node without kwargs whose one argument is a node --
+    or None."""
     from torch.fx import Node
-    if not node.args or not isinstance(node.args[0], Node):
+    if node.op != "call_module" or node.kwargs or len(node.args) != 1 or not isinstance(node.args[0], Node):
         return None
-    pool = None
-    if node.op == "call_module" and len(node.args) == 1 and not node.kwargs:
-        pool = mods.get(node.target)
-    elif node.op == "call_function" and node.target is torch.nn.functional.max_pool2d:
-        names = ("kernel_size", "stride", "padding", "dilation", "ceil_mode", "return_indices")
-        if len(node.args) > 7 or set(node.kwargs) - set(names[len(node.args) - 1:]):
-            return None
-        given = dict(zip(names, node.args[1:]), **node.kwargs)
-        if "kernel_size" not in given or any(isinstance(v, Node) for v in given.values()):
-            return None
-        if not all(isinstance(given.get(k, False), bool) for k in ("ceil_mode", "return_indices")):
-            return None
-        try:
-            pool = nn.MaxPool2d(**given)
-        except (TypeError, ValueError):
-            return None
-    return pool if QuantizedMaxPool2d.eligible(pool) else None
+    holder = mods.get(node.target)
+    return holder if _plain_holder(holder) else None
 
 
-def _pool_plan(node, mods, quantizer, consumer_for):
-    """``node`` a user of a plain holder with ``quantizer``: (QuantizedMaxPool2d, [(user, its consumer)]) if it is a max pool of
-    the holder's output that can run on codes -- every user a wrapped convolution ``consumer_for`` can take, fed by the pool
-    alone -- else None.  (A pool that also feeds a float32 user, an identity add for instance, is left alone.)"""
-    pool = _pool_of(node, mods)
-    if pool is None or not node.users:
+def _holder_calls(gm, mods):
+    """``(node, holder)`` for every node of the graph that calls a plain holder on one tensor (``_holder_of``), tested when its
+    turn comes: the loops that use this rewrite the graph as they go."""
+    for node in list(gm.graph.nodes):
+        holder = _holder_of(node, mods)
+        if holder is not None:
+            yield node, holder
+
+
+def _wrapped_consumer(user, src, mods, quantizer, consumer_for):
+    """The consumer ``consumer_for(wrapper, quantizer)`` gives for ``user`` if it calls a wrapped layer on ``src`` alone, else None."""
+    wrapper = _module_of(user, mods)
+    if not isinstance(wrapper, PytorchQuantizationWrapper) or user.kwargs or user.args != (src,):
         return None
+    return consumer_for(wrapper, quantizer)
+
+
+def _wrapped_users(src, mods, quantizer, consumer_for, rows: bool):
+    """[(user, its consumer)] if every user of ``src`` is a wrapped layer ``consumer_for`` can take, fed by ``src`` alone
+    (``_wrapped_consumer``) -- with ``rows`` a QuantizedLinear, without anything else: a 4-D tensor never feeds a QuantizedLinear
+    (it would run along the width, not the channels) and rows feed nothing else -- else None."""
     taken = []
-    for user in node.users:
-        wrapper = _module_of(user, mods)
-        if not isinstance(wrapper, PytorchQuantizationWrapper) or user.kwargs or user.args != (node,):
-            return None
-        fused = consumer_for(wrapper, quantizer)
-        if fused is None or type(fused) is QuantizedLinear:      # (a Linear behind a pool runs along the width, not the channels)
+    for user in src.users:
+        fused = _wrapped_consumer(user, src, mods, quantizer, consumer_for)
+        if fused is None or (type(fused) is QuantizedLinear) != rows:
             return None
         taken.append((user, fused))
-    try:
-        return QuantizedMaxPool2d(pool, quantizer), taken
-    except (TypeError, ValueError, NotImplementedError):
-        return None
-
-
-def _install_pool(gm, mods, node, plan, source) -> int:
-    """Makes ``node``, the pool's call, a call of ``plan``'s QuantizedMaxPool2d on ``source`` (codes, or the float32 tensor the
-    holder read) and its users the consumers of the plan; returns their number."""
-    if len(plan) == 3:
-        return _install_avg_pool(gm, mods, node, plan, source)
-    qpool, taken = plan
-    name = (node.target.replace(".", "_") if node.op == "call_module" else node.name) + "_qpool"
-    gm.add_submodule(name, qpool)
-    mods[name] = qpool
-    node.op, node.target, node.args, node.kwargs = "call_module", name, (source,), {}
-    for user, fused in taken:
-        _install_consumer(gm, mods, user, fused)
-    return len(taken)
+    return taken
 
 
 def _const_args(node, names):
@@ -1305,6 +1254,73 @@ def _const_args(node, names):
         return None
     given = dict(zip(names, rest), **node.kwargs)
     return None if any(isinstance(v, Node) for v in given.values()) else given
+
+
+def _pool_of(node, mods):
+    """The ``nn.MaxPool2d`` that ``node`` applies to its one tensor operand -- a call of such a module, or ``F.max_pool2d`` with
+    constant arguments, for which one is built -- if QuantizedMaxPool2d can take it, else None."""
+    from torch.fx import Node
+    if not node.args or not isinstance(node.args[0], Node):
+        return None
+    pool = None
+    if node.op == "call_module" and len(node.args) == 1 and not node.kwargs:
+        pool = mods.get(node.target)
+    elif node.op == "call_function" and node.target is torch.nn.functional.max_pool2d:
+        given = _const_args(node, ("kernel_size", "stride", "padding", "dilation", "ceil_mode", "return_indices"))
+        if given is None or "kernel_size" not in given:
+            return None
+        if not all(isinstance(given.get(k, False), bool) for k in ("ceil_mode", "return_indices")):
+            return None
+        try:
+            pool = nn.MaxPool2d(**given)
+        except (TypeError, ValueError):
+            return None
+    return pool if QuantizedMaxPool2d.eligible(pool) else None
+
+
+class _PoolPlan(NamedTuple):
+    """A pool that can run on codes: the ``module`` that replaces it, the ``suffix`` of its node's name, ``taken`` [(user, its
+    consumer)], the wrapped layers that read its output, and ``gone``, the nodes between the pool and those that leave the graph."""
+    module: nn.Module
+    suffix: str
+    taken: list
+    gone: list
+
+
+def _pool_plan(node, mods, quantizer, consumer_for):
+    """``node`` a user of a plain holder with ``quantizer``: the plan of a QuantizedMaxPool2d if it is a max pool of the holder's
+    output that can run on codes -- every user a wrapped convolution ``consumer_for`` can take, fed by the pool alone -- else
+    None.  (A pool that also feeds a float32 user, an identity add for instance, is left alone.)"""
+    pool = _pool_of(node, mods)
+    taken = _wrapped_users(node, mods, quantizer, consumer_for, rows=False) if pool is not None else None
+    if not taken:
+        return None
+    try:
+        return _PoolPlan(QuantizedMaxPool2d(pool, quantizer), "_qpool", taken, [])
+    except (TypeError, ValueError, NotImplementedError):
+        return None
+
+
+def _install_pool(gm, mods, node, plan, source) -> int:
+    """Makes ``node``, the pool's call, a call of ``plan``'s module on ``source`` (the holder's codes, or the float32 tensor the
+    holder read), the wrapped layers of the plan consumers of its output, and erases the nodes between them (an average pool's
+    second holder and flattens); returns the number of consumers."""
+    name = (node.target.replace(".", "_") if node.op == "call_module" else node.name) + plan.suffix
+    gm.add_submodule(name, plan.module)
+    mods[name] = plan.module
+    node.op, node.target, node.args, node.kwargs = "call_module", name, (source,), {}
+    for user, fused in plan.taken:
+        _install_consumer(gm, mods, user, fused)
+        user.args = (node,)
+    gone = list(plan.gone)
+    while gone:                                              # users first
+        free = [g for g in gone if not g.users]
+        if not free:
+            raise RuntimeError("a node of the pool's chain still has users")
+        for g in free:
+            gm.graph.erase_node(g)
+            gone.remove(g)
+    return len(plan.taken)
 
 
 def _avg_pool_of(node, mods):
@@ -1368,7 +1384,7 @@ def _is_flatten(node, mods) -> bool:
 
 
 def _avg_pool_plan(node, mods, quantizer, consumer_for):
-    """``node`` a user of a plain holder A with ``quantizer``: (QuantizedAvgPool2d, [(user, its consumer)], [nodes that leave]) if
+    """``node`` a user of a plain holder A with ``quantizer``: the plan of a QuantizedAvgPool2d, B and the flattens in ``gone``, if
     it is an average pool of A's output (``_avg_pool_of``) whose one user -- through at most one flatten (``_is_flatten``), and
     that behind a global pool only, where H = W = 1 is known without shapes -- is a plain holder B, every user of which is a
     wrapped layer ``consumer_for`` can take, fed by B alone (a 4-D tensor never feeds a QuantizedLinear, rows feed nothing
@@ -1382,66 +1398,31 @@ def _avg_pool_plan(node, mods, quantizer, consumer_for):
     gone, nxt, last = [], next(iter(node.users)), node
     if not flat and is_global and _is_flatten(nxt, mods) and len(nxt.users) == 1:
         gone, flat, last, nxt = [nxt], True, nxt, next(iter(nxt.users))
-    holder = _module_of(nxt, mods)
-    if not _plain_holder(holder) or nxt.kwargs or nxt.args != (last,) or not nxt.users:
+    holder = _holder_of(nxt, mods)
+    if holder is None or nxt.args != (last,) or not nxt.users:
         return None
     out_quantizer = holder.activation_holder_quantizer
-
-    def consumers_of(src, rows):
-        taken = []
-        for user in src.users:
-            wrapper = _module_of(user, mods)
-            if not isinstance(wrapper, PytorchQuantizationWrapper) or user.kwargs or user.args != (src,):
-                return None
-            fused = consumer_for(wrapper, out_quantizer)
-            if fused is None or (type(fused) is QuantizedLinear) != rows:
-                return None
-            taken.append((user, fused))
-        return taken
-
     if flat:
-        taken = consumers_of(nxt, True)
+        taken = _wrapped_users(nxt, mods, out_quantizer, consumer_for, rows=True)
     elif is_global and all(_is_flatten(u, mods) and u.args[0] is nxt and u.users for u in nxt.users):
         taken, flat = [], True
         for u in nxt.users:
-            behind = consumers_of(u, True)
+            behind = _wrapped_users(u, mods, out_quantizer, consumer_for, rows=True)
             if behind is None:
                 return None
             taken += behind
         gone = gone + list(nxt.users)
     else:
-        taken = consumers_of(nxt, False)
+        taken = _wrapped_users(nxt, mods, out_quantizer, consumer_for, rows=False)
     if not taken:
         return None
     try:
-        return QuantizedAvgPool2d(pool, quantizer, out_quantizer, flatten=flat), taken, gone + [nxt]
+        return _PoolPlan(QuantizedAvgPool2d(pool, quantizer, out_quantizer, flatten=flat), "_qavgpool", taken, gone + [nxt])
     except (TypeError, ValueError, NotImplementedError):
         return None
 
 
-def _install_avg_pool(gm, mods, node, plan, source) -> int:
-    """Makes ``node``, the pool's call, a call of ``plan``'s QuantizedAvgPool2d on ``source`` (holder A's codes, or the float32
-    tensor A read), the wrapped layers of the plan consumers of its output, and erases holder B and the flattens; returns the
-    number of consumers."""
-    qpool, taken, gone = plan
-    name = (node.target.replace(".", "_") if node.op == "call_module" else node.name) + "_qavgpool"
-    gm.add_submodule(name, qpool)
-    mods[name] = qpool
-    node.op, node.target, node.args, node.kwargs = "call_module", name, (source,), {}
-    for user, fused in taken:
-        _install_consumer(gm, mods, user, fused)
-        user.args = (node,)
-    while gone:                                              # users first
-        free = [g for g in gone if not g.users]
-        if not free:
-            raise RuntimeError("a node of the average pool's chain still has users")
-        for g in free:
-            gm.graph.erase_node(g)
-            gone.remove(g)
-    return len(taken)
-
-
-class QuantizedJoin(nn.Module):
+class QuantizedJoin(_OnCodes):
     """An activation holder with several consumers (the end of a residual block), its elementwise prologue folded in:
     ``forward(x, residual=None) -> (float32 or None, codes)`` with ``v = relu(x + residual)`` (each part as switched on),
     the float32 tensor what the holder returns for v -- for the users that stay in float32, None with ``want_float=False``
@@ -1496,6 +1477,12 @@ class QuantizedJoin(nn.Module):
                            residual_codes=r_codes)
 
 
+def _in_place_ok(node, inplace) -> bool:
+    """The rule for an in-place form (``inplace`` true) of an operation the rewrite folds into a module, which then no longer
+    performs it on its first operand: nobody else may be looking at that operand."""
+    return not inplace or len(node.args[0].users) == 1
+
+
 def _relu_input(node, mods):
     """The input node of ``node`` if it is a ReLU of one tensor (``nn.ReLU``, ``F.relu``, ``torch.relu``, ``Tensor.relu``), else None."""
     from torch.fx import Node
@@ -1508,28 +1495,34 @@ def _relu_input(node, mods):
             (node.target is torch.nn.functional.relu and not set(node.kwargs) - {"inplace"})
     else:
         ok = node.op == "call_method" and node.target == "relu" and not node.kwargs
-    # (an in-place ReLU the join no longer performs: nobody else may be looking at its input)
     inplace = getattr(_module_of(node, mods), "inplace", False) if node.op == "call_module" else node.kwargs.get("inplace", False)
-    if inplace and len(node.args[0].users) != 1:
-        ok = False
-    return node.args[0] if ok else None
+    return node.args[0] if ok and _in_place_ok(node, inplace) else None
+
+
+def _binary_operands(node, functions, methods, in_place):
+    """The two operand nodes of ``node`` if it calls one of ``functions`` or, as a method, one of ``methods`` on two tensors and
+    nothing else (no keyword, no scalar operand); ``in_place``, the in-place operator among ``functions``, under ``_in_place_ok``.
+    Else None."""
+    from torch.fx import Node
+    if node.kwargs or len(node.args) != 2 or not all(isinstance(a, Node) for a in node.args):
+        return None
+    if node.op == "call_function":
+        ok = node.target in functions and _in_place_ok(node, node.target is in_place)
+    else:
+        ok = node.op == "call_method" and node.target in methods
+    return tuple(node.args) if ok else None
 
 
 def _add_operands(node):
     """The two operand nodes of ``node`` if it is a plain add of two tensors (``+``, ``+=``, ``torch.add``, ``Tensor.add``:
     no ``alpha``, no scalar operand), else None."""
-    import operator
-    from torch.fx import Node
-    if node.kwargs or len(node.args) != 2 or not all(isinstance(a, Node) for a in node.args):
-        return None
-    if node.op == "call_function":
-        ok = node.target in (operator.add, operator.iadd, torch.add)
-        # (an in-place add the join no longer performs: nobody else may be looking at its first operand)
-        if node.target is operator.iadd and len(node.args[0].users) != 1:
-            ok = False
-    else:
-        ok = node.op == "call_method" and node.target == "add"
-    return tuple(node.args) if ok else None
+    return _binary_operands(node, (operator.add, operator.iadd, torch.add), ("add",), operator.iadd)
+
+
+def _mul_operands(node):
+    """The two operand nodes of ``node`` if it is a plain multiply of two tensors (``*``, ``*=``, ``torch.mul`` /
+    ``torch.multiply``, ``Tensor.mul`` / ``Tensor.multiply``: no scalar operand, no ``out=``), else None."""
+    return _binary_operands(node, (operator.mul, operator.imul, torch.mul, torch.multiply), ("mul", "multiply"), operator.imul)
 
 
 def _join_shared_holders(gm, mods, consumer_for, pools: bool = False, avg_pools: bool = False) -> int:
@@ -1538,31 +1531,20 @@ def _join_shared_holders(gm, mods, consumer_for, pools: bool = False, avg_pools:
     nothing in front to absorb (the pair rewrite's).  With ``pools`` a max pool among the users that can run on codes
     (``_pool_plan``) reads the join's codes as well, as a QuantizedMaxPool2d in front of its own consumers; a lone holder ->
     pool pair with nothing to absorb is left to ``_pool_lone_holders``.  With ``avg_pools`` the same holds for an average pool
-    in front of a second holder (``_avg_pool_plan``), as a QuantizedAvgPool2d.  A QuantizedMul among the users (``_mul_holders``,
-    which built it with this holder's quantizer at that operand) reads the join's codes too, at whichever operand position the
-    holder occupies.  Returns the number of wrapped layers replaced."""
-    import operator
-    from torch.fx import Node
+    in front of a second holder (``_avg_pool_plan``), as a QuantizedAvgPool2d.  A QuantizedMul among the users
+    (``_operator_between_holders``, which built it with this holder's quantizer at that operand) reads the join's codes too, at
+    whichever operand position the holder occupies.  Returns the number of wrapped layers replaced."""
     replaced = 0
-    for node in list(gm.graph.nodes):
-        if node.op != "call_module" or node.kwargs or len(node.args) != 1 or not isinstance(node.args[0], Node):
-            continue
-        holder = mods.get(node.target)
-        if not _plain_holder(holder):
-            continue
-        taken = []                                           # F: (user node, its consumer)
-        for user in node.users:
-            wrapper = _module_of(user, mods)
-            if isinstance(wrapper, PytorchQuantizationWrapper) and not user.kwargs and user.args == (node,):
-                fused = consumer_for(wrapper, holder.activation_holder_quantizer)
-                if fused is not None:
-                    taken.append((user, fused))
+    for node, holder in _holder_calls(gm, mods):
+        quantizer = holder.activation_holder_quantizer
+        # F: (user node, its consumer)
+        taken = [(user, _wrapped_consumer(user, node, mods, quantizer, consumer_for)) for user in node.users]
+        taken = [(user, fused) for user, fused in taken if fused is not None]
         pooled = []                                          # P: (pool node, its plan)
         if pools or avg_pools:
-            plans = ((user, _any_pool_plan(user, mods, holder.activation_holder_quantizer, consumer_for, pools, avg_pools))
-                     for user in node.users)
+            plans = ((user, _any_pool_plan(user, mods, quantizer, consumer_for, pools, avg_pools)) for user in node.users)
             pooled = [(user, plan) for user, plan in plans if plan is not None]
-        # M: the QuantizedMul nodes of ``_mul_holders`` that read this holder (built with its quantizer at those operands)
+        # M: the QuantizedMul nodes of ``_operator_between_holders`` that read this holder (built with its quantizer at those operands)
         muls = [user for user in node.users if isinstance(_module_of(user, mods), QuantizedMul) and not user.kwargs]
         if not taken and not pooled and not muls:
             continue
@@ -1615,13 +1597,9 @@ def _pool_lone_holders(gm, mods, consumer_for, pools: bool = True, avg_pools: bo
     (``_pool_plan``) leaves the graph, the QuantizedMaxPool2d that replaces the pool quantizes the holder's input itself.
     With ``avg_pools`` likewise for an average pool in front of a second holder (``_avg_pool_plan``) and its QuantizedAvgPool2d.
     Returns the number of wrapped layers replaced."""
-    from torch.fx import Node
     replaced = 0
-    for node in list(gm.graph.nodes):
-        if node.op != "call_module" or node.kwargs or len(node.args) != 1 or not isinstance(node.args[0], Node) or len(node.users) != 1:
-            continue
-        holder = mods.get(node.target)
-        if not _plain_holder(holder):
+    for node, holder in _holder_calls(gm, mods):
+        if len(node.users) != 1:
             continue
         user = next(iter(node.users))
         plan = _any_pool_plan(user, mods, holder.activation_holder_quantizer, consumer_for, pools, avg_pools)
@@ -1649,137 +1627,54 @@ def _cat_operands(node):
     return list(tensors)
 
 
-def _concat_holders(gm, mods, consumer_for, pools: bool = False) -> int:
-    """``fuse_linear_consumers_fx(concats=True)``: a plain holder whose one argument is a concatenation along the channels
-    (``_cat_operands``) that feeds nothing else, every operand of which is the output of a plain holder, and every user of which
-    is a wrapped layer ``consumer_for`` can take, fed by it alone -- or, with ``pools``, a max pool that can run on codes
-    (``_pool_plan``) -- becomes a QuantizedConcat node together with the concatenation; its users become consumers and pools of
-    its codes.  An operand holder whose only user was the concatenation leaves the graph and the QuantizedConcat quantizes that
-    holder's input; one with other users stays and the QuantizedConcat quantizes its float32 output (the same codes).  Returns
-    the number of wrapped layers replaced."""
-    from torch.fx import Node
+def _operator_between_holders(gm, mods, consumer_for, pools, operands_of, cls, suffix) -> int:
+    """``fuse_linear_consumers_fx(concats=True)`` with ``(_cat_operands, QuantizedConcat, "_concat")`` and ``(muls=True)`` with
+    ``(_mul_operands, QuantizedMul, "_mul")``, one whole pass over the graph each: a plain holder whose one argument is that
+    operator (``operands_of``) and feeds nothing else, every operand of which is the output of a plain holder, and every user of
+    which is a wrapped layer ``consumer_for`` can take, fed by it alone -- or, with ``pools``, a max pool that can run on codes
+    (``_pool_plan``) -- becomes a node of ``cls``, named ``<the holder's name><suffix>``, together with the operator; its users
+    become consumers and pools of its codes.  An operand holder whose only user was the operator leaves the graph and the module
+    quantizes that holder's input (a QuantizedMul a ``[B, C, 1, 1]`` gate inside its kernel); one with other users stays and the
+    module quantizes its float32 output (the same codes) until ``_join_shared_holders`` hands a QuantizedMul the codes.
+    Returns the number of wrapped layers replaced."""
     replaced = 0
-    for node in list(gm.graph.nodes):
-        if node.op != "call_module" or node.kwargs or len(node.args) != 1 or not isinstance(node.args[0], Node) or not node.users:
+    for node, holder in _holder_calls(gm, mods):
+        op = node.args[0]
+        operands = operands_of(op)
+        if not node.users or operands is None or len(op.users) != 1:
             continue
-        holder = mods.get(node.target)
-        if not _plain_holder(holder):
-            continue
-        cat = node.args[0]
-        operands = _cat_operands(cat)
-        if operands is None or len(cat.users) != 1:
-            continue
-        sources = [_module_of(o, mods) for o in operands]
-        if not all(_plain_holder(h) and len(o.args) == 1 and isinstance(o.args[0], Node) and not o.kwargs
-                   for o, h in zip(operands, sources)):
+        sources = [_holder_of(o, mods) for o in operands]
+        if None in sources:
             continue
         quantizer = holder.activation_holder_quantizer
         taken, pooled = [], []
         for user in node.users:
-            wrapper = _module_of(user, mods)
-            if isinstance(wrapper, PytorchQuantizationWrapper) and not user.kwargs and user.args == (node,):
-                fused = consumer_for(wrapper, quantizer)
-                if fused is not None:
-                    taken.append((user, fused))
-                    continue
+            fused = _wrapped_consumer(user, node, mods, quantizer, consumer_for)
+            if fused is not None:
+                taken.append((user, fused))
+                continue
             plan = _pool_plan(user, mods, quantizer, consumer_for) if pools else None
             if plan is None:
                 break
             pooled.append((user, plan))
         else:
             try:
-                concat = QuantizedConcat([h.activation_holder_quantizer for h in sources], quantizer)
+                module = cls([h.activation_holder_quantizer for h in sources], quantizer)
             except (TypeError, ValueError, NotImplementedError):
                 continue
-            name = node.target.replace(".", "_") + "_concat"
-            gm.add_submodule(name, concat)
-            mods[name] = concat
+            name = node.target.replace(".", "_") + suffix
+            gm.add_submodule(name, module)
+            mods[name] = module
             absorbed = [o for o in dict.fromkeys(operands) if len(o.users) == 1]
             with gm.graph.inserting_before(node):
-                cn = gm.graph.call_module(name, tuple(o.args[0] if o in absorbed else o for o in operands))
+                on_codes = gm.graph.call_module(name, tuple(o.args[0] if o in absorbed else o for o in operands))
             for user, fused in taken:
                 _install_consumer(gm, mods, user, fused)
-                user.args = (cn,)
+                user.args = (on_codes,)
                 replaced += 1
             for user, plan in pooled:
-                replaced += _install_pool(gm, mods, user, plan, cn)
-            for gone in (node, cat, *absorbed):
-                gm.graph.erase_node(gone)
-    return replaced
-
-
-def _mul_operands(node):
-    """The two operand nodes of ``node`` if it is a plain multiply of two tensors (``*``, ``*=``, ``torch.mul`` /
-    ``torch.multiply``, ``Tensor.mul`` / ``Tensor.multiply``: no scalar operand, no ``out=``), else None."""
-    import operator
-    from torch.fx import Node
-    if node.kwargs or len(node.args) != 2 or not all(isinstance(a, Node) for a in node.args):
-        return None
-    if node.op == "call_function":
-        ok = node.target in (operator.mul, operator.imul, torch.mul, torch.multiply)
-        # (an in-place multiply the module no longer performs: nobody else may be looking at its first operand)
-        if node.target is operator.imul and len(node.args[0].users) != 1:
-            ok = False
-    else:
-        ok = node.op == "call_method" and node.target in ("mul", "multiply")
-    return tuple(node.args) if ok else None
-
-
-def _mul_holders(gm, mods, consumer_for, pools: bool = False) -> int:
-    """``fuse_linear_consumers_fx(muls=True)``: a plain holder M whose one argument is a multiply of two tensors
-    (``_mul_operands``) that feeds nothing else, each operand the output of a plain holder, and every user of which is a wrapped
-    layer ``consumer_for`` can take, fed by it alone -- or, with ``pools``, a max pool that can run on codes (``_pool_plan``) --
-    becomes a QuantizedMul node together with the multiply; its users become consumers and pools of its codes.  An operand
-    holder whose only user was the multiply leaves the graph and the QuantizedMul quantizes that holder's input (a
-    ``[B, C, 1, 1]`` gate inside its kernel); one with other users stays and the QuantizedMul quantizes its float32 output (the
-    same codes) until ``_join_shared_holders`` hands it the codes.  Returns the number of wrapped layers replaced."""
-    from torch.fx import Node
-    replaced = 0
-    for node in list(gm.graph.nodes):
-        if node.op != "call_module" or node.kwargs or len(node.args) != 1 or not isinstance(node.args[0], Node) or not node.users:
-            continue
-        holder = mods.get(node.target)
-        if not _plain_holder(holder):
-            continue
-        mul = node.args[0]
-        operands = _mul_operands(mul)
-        if operands is None or len(mul.users) != 1:
-            continue
-        sources = [_module_of(o, mods) for o in operands]
-        if not all(_plain_holder(h) and len(o.args) == 1 and isinstance(o.args[0], Node) and not o.kwargs
-                   for o, h in zip(operands, sources)):
-            continue
-        quantizer = holder.activation_holder_quantizer
-        taken, pooled = [], []
-        for user in node.users:
-            wrapper = _module_of(user, mods)
-            if isinstance(wrapper, PytorchQuantizationWrapper) and not user.kwargs and user.args == (node,):
-                fused = consumer_for(wrapper, quantizer)
-                if fused is not None:
-                    taken.append((user, fused))
-                    continue
-            plan = _pool_plan(user, mods, quantizer, consumer_for) if pools else None
-            if plan is None:
-                break
-            pooled.append((user, plan))
-        else:
-            try:
-                qmul = QuantizedMul([h.activation_holder_quantizer for h in sources], quantizer)
-            except (TypeError, ValueError, NotImplementedError):
-                continue
-            name = node.target.replace(".", "_") + "_mul"
-            gm.add_submodule(name, qmul)
-            mods[name] = qmul
-            absorbed = [o for o in dict.fromkeys(operands) if len(o.users) == 1]
-            with gm.graph.inserting_before(node):
-                mn = gm.graph.call_module(name, tuple(o.args[0] if o in absorbed else o for o in operands))
-            for user, fused in taken:
-                _install_consumer(gm, mods, user, fused)
-                user.args = (mn,)
-                replaced += 1
-            for user, plan in pooled:
-                replaced += _install_pool(gm, mods, user, plan, mn)
-            for gone in (node, mul, *absorbed):
+                replaced += _install_pool(gm, mods, user, plan, on_codes)
+            for gone in (node, op, *absorbed):
                 gm.graph.erase_node(gone)
     return replaced
 
@@ -1805,13 +1700,12 @@ def _clamp_range(node, mods):
         if len(node.args) == 1 and not set(node.kwargs) - {"inplace"}:
             rng, inplace = (0.0, 6.0), node.kwargs.get("inplace", False)
     elif node.op == "call_function" and node.target is F.hardtanh:
-        names = ("min_val", "max_val", "inplace")
-        if len(node.args) <= 4 and not set(node.kwargs) - set(names[len(node.args) - 1:]):
-            given = dict(zip(names, node.args[1:]), **node.kwargs)
+        given = _const_args(node, ("min_val", "max_val", "inplace"))
+        if given is not None:
             rng, inplace = (given.get("min_val", -1.0), given.get("max_val", 1.0)), given.get("inplace", False)
     if rng is None or not all(isinstance(v, (int, float)) and math.isfinite(v) for v in rng) or not rng[0] <= rng[1]:
         return None
-    if not isinstance(inplace, bool) or (inplace and len(node.args[0].users) != 1):
+    if not isinstance(inplace, bool) or not _in_place_ok(node, inplace):
         return None
     return float(rng[0]), float(rng[1])
 
@@ -1830,10 +1724,10 @@ def _hard_activation(node, mods):
         if type(m) in (nn.Hardswish, nn.Hardsigmoid):
             kind, inplace = ("hardswish" if type(m) is nn.Hardswish else "hardsigmoid"), m.inplace
     elif node.op == "call_function" and node.target in (F.hardswish, F.hardsigmoid):
-        if len(node.args) <= 2 and not set(node.kwargs) - ({"inplace"} if len(node.args) == 1 else set()):
-            kind = "hardswish" if node.target is F.hardswish else "hardsigmoid"
-            inplace = node.args[1] if len(node.args) == 2 else node.kwargs.get("inplace", False)
-    if kind is None or not isinstance(inplace, bool) or (inplace and len(node.args[0].users) != 1):
+        given = _const_args(node, ("inplace",))
+        if given is not None:
+            kind, inplace = ("hardswish" if node.target is F.hardswish else "hardsigmoid"), given.get("inplace", False)
+    if kind is None or not isinstance(inplace, bool) or not _in_place_ok(node, inplace):
         return None
     return kind
 
@@ -1852,7 +1746,6 @@ def _identities_as_codes(gm, mods) -> int:
     is the float32 output of another join takes that join's codes in its place (``QuantizedJoin(residual_codes=...)``; IEEE
     addition is commutative, so either operand may move to the second place; where both qualify, one is converted), and a join
     whose float32 output then has no users stops writing it.  Returns the number of joins converted."""
-    import operator
 
     def pick(node, index):
         """(the join node, its module) if ``node`` is ``join(...)[index]``."""
@@ -1907,16 +1800,16 @@ def _fold_clamps_into_producers(gm, mods, hard_activations: bool = False) -> int
     -- through at most one clamp activation that feeds nothing else (``_clamp_range``; the ReLU a join absorbed counts), or with
     ``hard_activations=True`` one Hardswish / Hardsigmoid (``_hard_activation``) behind a consumer that takes one
     (``_takes_hard_activation``), which is not folded into the clamp but applied in the consumer's epilogue (``emit_act``) -- to a
-    holder all of whose users are integer consumers (or, with ``pools=True``, QuantizedMaxPool2d modules in front of such), the
-    consumer emits that holder's codes itself, the activation folded into their clamp (``folded_clamp``), and the modules behind
-    take them directly.  The holder is either already inside the one
-    consumer behind it (the pair rewrite) or a residual-free QuantizedJoin that writes no float32 output.  With
-    ``concats=True`` the reader may also be a QuantizedConcat among whose arguments the consumer's output (or its one clamp
-    activation) occurs exactly once, at index i: the consumer then emits the codes of ``operand_code_params(i)``, the clamp
-    folded in, and that one argument becomes the consumer's output.  With ``muls=True`` a QuantizedMul is such a reader too,
-    directly or among the readers of a join's codes, where those codes occur at exactly one of its two operands (``x * x`` is
-    left to the module's float32 quantize path).  Returns the number of producers that now emit codes."""
-    import operator
+    holder all of whose users read codes (``_CODE_READERS``: integer consumers, and the pools the passes before this one put
+    in front of such), the consumer emits that holder's codes itself, the activation folded into their clamp (``folded_clamp``),
+    and the modules behind take them directly.  The holder is either already inside the one reader behind it (the pair
+    rewrites) or a residual-free QuantizedJoin that writes no float32 output.  Which kinds of reader occur is decided by the
+    modules the earlier passes left in the graph, not by a switch of this function.  The reader may also be a QuantizedConcat
+    among whose arguments the consumer's output (or its one clamp activation) occurs exactly once, at index i: the consumer then
+    emits the codes of ``operand_code_params(i)``, the clamp folded in, and that one argument becomes the consumer's output.  A
+    QuantizedMul is such a reader too, directly or among the readers of a join's codes, where those codes occur at exactly one
+    of its two operands (``x * x`` is left to the module's float32 quantize path).  Returns the number of producers that now
+    emit codes."""
     folded = 0
     for node in list(gm.graph.nodes):
         producer = _module_of(node, mods)
@@ -1985,7 +1878,6 @@ def _fuse_residuals_into_producers(gm, mods) -> int:
     and applies the join's ReLU in its own epilogue and emits the join's codes (``mctq_qlinear_i8_res``).  IEEE addition is
     commutative, so either operand may be the product; the one evaluated last is, as the other has to exist when it runs.
     Returns the number of joins removed."""
-    import operator
     order = {n: i for i, n in enumerate(gm.graph.nodes)}
     fused = 0
     for node in list(gm.graph.nodes):
@@ -2277,8 +2169,7 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
 
     class _Tracer(fx.Tracer):
         def is_leaf_module(self, m, qualname):
-            return isinstance(m, (PytorchQuantizationWrapper, PytorchActivationQuantizationHolder, IntegerConsumer, QuantizedJoin,
-                                  QuantizedMaxPool2d, QuantizedAvgPool2d, QuantizedConcat, QuantizedMul)) \
+            return isinstance(m, (PytorchQuantizationWrapper, PytorchActivationQuantizationHolder, IntegerConsumer, _OnCodes)) \
                 or super().is_leaf_module(m, qualname)
 
     graph = _Tracer().trace(model)
@@ -2286,27 +2177,21 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
     mods = dict(gm.named_modules())
     replaced = 0
     consumer_for = lambda wrapper, q: _consumer_for(wrapper, q, uniform_weights, convolutions, depthwise)      # noqa: E731
+    # Two whole passes, concatenations first: a concatenation absorbs an operand holder that sits behind a multiply, which the
+    # multiply pass then no longer sees.
     if concats:
-        replaced = _concat_holders(gm, mods, consumer_for, pools)
+        replaced = _operator_between_holders(gm, mods, consumer_for, pools, _cat_operands, QuantizedConcat, "_concat")
     if muls:
-        replaced += _mul_holders(gm, mods, consumer_for, pools)
+        replaced += _operator_between_holders(gm, mods, consumer_for, pools, _mul_operands, QuantizedMul, "_mul")
     if shared_holders:
         replaced += _join_shared_holders(gm, mods, consumer_for, pools, avg_pools)
     if pools or avg_pools:
         replaced += _pool_lone_holders(gm, mods, consumer_for, pools, avg_pools)
-    for node in list(gm.graph.nodes):
-        if node.op != "call_module" or node.kwargs or len(node.args) != 1:
+    for src, holder in _holder_calls(gm, mods):              # the pair: a holder whose only user is a wrapped layer
+        if len(src.users) != 1:
             continue
-        wrapper = mods.get(node.target)
-        if not isinstance(wrapper, PytorchQuantizationWrapper):
-            continue
-        src = node.args[0]
-        if not isinstance(src, fx.Node) or src.op != "call_module" or len(src.users) != 1 or len(src.args) != 1 or src.kwargs:
-            continue
-        holder = mods.get(src.target)
-        if not _plain_holder(holder):
-            continue
-        fused = _consumer_for(wrapper, holder.activation_holder_quantizer, uniform_weights, convolutions, depthwise)
+        node = next(iter(src.users))
+        fused = _wrapped_consumer(node, src, mods, holder.activation_holder_quantizer, consumer_for)
         if fused is None:
             continue
         _install_consumer(gm, mods, node, fused)
@@ -2315,11 +2200,12 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
         replaced += 1
     if chain:
         for node in gm.graph.nodes:
-            if isinstance(_module_of(node, mods), IntegerConsumer) and len(node.users) == 1:
+            producer = _module_of(node, mods)
+            if isinstance(producer, IntegerConsumer) and len(node.users) == 1:
                 user = next(iter(node.users))
                 nxt = _module_of(user, mods)
                 if isinstance(nxt, _CODE_READERS) and user.args == (node,):
-                    mods[node.target].emit_codes_for = nxt.activation_code_params()
+                    producer.emit_codes_for = nxt.activation_code_params()
     if stay_on_codes:
         _identities_as_codes(gm, mods)
         _fold_clamps_into_producers(gm, mods, hard_activations)

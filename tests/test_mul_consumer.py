@@ -14,6 +14,7 @@ products -- their float32 products are exact and equal the consumers' integer su
 is exact too (tests/test_avgpool_consumer.py)."""
 import functools
 import itertools
+import operator
 import warnings
 
 import numpy as np
@@ -680,6 +681,46 @@ def test_a_block_whose_channels_no_consumer_takes_is_left_alone():
     gm, n = C.fuse_linear_consumers_fx(Narrow().eval(), muls=True, **ALL)
     gm0, n0 = C.fuse_linear_consumers_fx(Narrow().eval(), **ALL)
     assert n == n0 and not _of(gm, C.QuantizedMul) and str(gm.graph) == str(gm0.graph) and torch.equal(gm(x), gm0(x))
+
+
+class MulIntoCat(torch.nn.Module):
+    """holder A, holder G -> mul -> holder M -> cat([M, holder P], 1) -> holder H -> 1 x 1 convolution: M is the holder behind a
+    multiply and an operand holder of a concatenation at once."""
+
+    def __init__(self):
+        super().__init__()
+        self.a, self.g, self.m, self.p = holder_of("s4"), holder_of("u1"), holder_of("u4"), holder_of("u8")
+        self.h, self.last = holder_of("u8"), pot_conv(32, 16, 1, 5)
+
+    def forward(self, x):
+        m = self.m(self.a(x) * self.g(x))
+        return self.last(self.h(torch.cat([m, self.p(x)], 1)))
+
+
+# the call targets after fuse_linear_consumers_fx(MulIntoCat(), **switches), as recorded before the two passes became one function
+MUL_INTO_CAT = {
+    (): (["a", "g", "m", "p", "last_qlinear"], [operator.mul, torch.cat]),
+    ("concats",): (["a", "g", "h_concat", "last_qlinear"], [operator.mul]),
+    ("muls",): (["a", "g", "m", "p", "last_qlinear"], [operator.mul, torch.cat]),
+    ("concats", "muls"): (["a", "g", "h_concat", "last_qlinear"], [operator.mul]),
+}
+
+
+@pytest.mark.parametrize("on", list(MUL_INTO_CAT), ids=lambda on: "+".join(on) or "neither")
+def test_a_concatenation_whose_operand_holder_sits_behind_a_multiply(on):
+    """The concatenations are rewritten in one whole pass, then the multiplies.  With ``concats`` the QuantizedConcat absorbs M
+    and P and reads the float32 product; the multiply stays an operation with and without ``muls``: M's reader is ``torch.cat``,
+    no wrapped layer, so M is no candidate of the multiply pass, and behind the concatenation pass no holder is left behind the
+    multiply.  A and G, which the multiply reads, stay holders.  Every form returns what the rewrite with neither switch does."""
+    from mct_quantizers_amd import consumers as C
+    x = block_input()
+    gm, n = C.fuse_linear_consumers_fx(MulIntoCat().eval(), **dict.fromkeys(on, True))
+    gm0, n0 = C.fuse_linear_consumers_fx(MulIntoCat().eval())
+    assert n == n0 == 1
+    assert (_targets(gm), _targets(gm, "call_function")) == MUL_INTO_CAT[on]
+    assert len(_of(gm, C.QuantizedConcat)) == ("concats" in on) and not _of(gm, C.QuantizedMul)
+    y = gm(x)
+    assert len(torch.unique(y)) > 50 and torch.equal(y, gm0(x))
 
 
 # ---- the C ABI without a GPU -----------------------------------------------------------------------------------------------
