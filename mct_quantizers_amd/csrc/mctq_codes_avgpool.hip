@@ -175,14 +175,6 @@ __global__ __launch_bounds__(kThreads) void codes_avgpool_split_kernel(AvgArgs a
   }
 }
 
-// PyTorch's pooling_output_shape along one axis (dilation 1), as mctq_codes_maxpool.hip
-static int64_t avg_pooled_extent(int64_t n, int64_t pad, int64_t k, int64_t stride, bool ceil_mode) {
-  const int64_t np = n + 2 * pad;
-  int64_t out = (np - k + (ceil_mode ? stride - 1 : 0)) / stride + 1;
-  if (ceil_mode && (out - 1) * stride >= n + pad) --out;
-  return out;
-}
-
 }  // namespace mctq
 
 using namespace mctq;
@@ -194,37 +186,21 @@ int mctq_codes_avgpool_nhwc(const void* codes, void* pooled, int32_t code_dtype,
                             int32_t stride_w, int32_t pad_h, int32_t pad_w, int32_t ceil_mode, int32_t count_include_pad,
                             int32_t divisor_override, int64_t out_height, int64_t out_width, int32_t y_code_dtype, float y_scale,
                             int32_t y_zero_point, int32_t y_quant_min, int32_t y_quant_max, void* stream) {
-  if (batch < 0 || height < 0 || width < 0 || channels < 0) return fail_arg("negative extent");
-  if (kh < 1 || kw < 1) return fail_arg("kernel size below 1");
-  if (stride_h < 1 || stride_w < 1) return fail_arg("stride below 1");
-  if (pad_h < 0 || pad_w < 0) return fail_arg("negative padding");
-  if (pad_h > kh / 2 || pad_w > kw / 2) return fail_arg("padding larger than half the kernel size");
+  WindowGeom g = {batch, height, width, channels, kh, kw, stride_h, stride_w, pad_h, pad_w, 1, 1};      // no dilation
+  if (int rc = geom_check_sizes(g, true)) return rc;
   if ((int64_t)kh * kw > 65536) return fail_arg("more than 65536 taps in a window");
   if (divisor_override < 0) return fail_arg("negative divisor_override");
-  if (channels % 16 != 0) return fail_arg("channels must be a multiple of 16");
-  if (code_dtype != MCTQ_CODE_I8 && code_dtype != MCTQ_CODE_U8) return fail_arg("bad code_dtype");
-  if (code_dtype == MCTQ_CODE_I8 ? (zero_point < -128 || zero_point > 127) : (zero_point < 0 || zero_point > 255))
-    return fail_arg("zero_point is no code of the input's type");
-  if (!(scale > 0.0f) || !__builtin_isfinite(scale)) return fail_arg("scale must be finite and positive");
-  if (!(y_scale > 0.0f) || !__builtin_isfinite(y_scale)) return fail_arg("y_scale must be finite and positive");
+  if (int rc = geom_check_channels(g)) return rc;
+  if (int rc = form_check(code_dtype, zero_point, scale, {"code_dtype", "zero_point", "the input's type", "scale"})) return rc;
+  if (int rc = form_check_scale(y_scale, "y_scale")) return rc;
   QlOut o;
   if (y_code_dtype < 0) return fail_arg("bad y_code_dtype");
   if (int rc = ql_output_form(o, y_code_dtype, y_scale, y_zero_point, y_quant_min, y_quant_max)) return rc;
-  // the kernel's input coordinates oy * stride - pad + ky stay below padded extent + kernel: within int32
-  const int64_t hp = height + 2 * (int64_t)pad_h, wp = width + 2 * (int64_t)pad_w;
-  if (hp + kh > INT32_MAX || wp + kw > INT32_MAX) return fail_arg("padded image extent exceeds 2^31 - 1");
-  if (hp < kh || wp < kw) return fail_arg("the kernel does not fit the padded image (Ho <= 0 or Wo <= 0)");
-  const int64_t ho = avg_pooled_extent(height, pad_h, kh, stride_h, ceil_mode != 0);
-  const int64_t wo = avg_pooled_extent(width, pad_w, kw, stride_w, ceil_mode != 0);
-  // the caller allocated out_height x out_width pixels per image: a disagreement would be an out-of-bounds write
-  if (out_height != ho || out_width != wo) return fail_arg("out_height / out_width are not the pooled extent");
-  if (batch == 0 || channels == 0) return 0;
-  // (padding alone could make room for a kernel on an image without pixels; the clamped loads need one)
-  if (height == 0 || width == 0) return fail_arg("an image of a non-empty batch needs at least one pixel");
-  if (batch > INT32_MAX / (ho * wo)) return fail_arg("too many output pixels for one launch");       // ho * wo < 2^62
-  const int64_t pixels = batch * ho * wo, c16 = channels / 16;
-  // a lane's index, pixel * (channels / 16) + chunk, is a 32-bit number (beyond it: split the batch)
-  if (c16 > UINT32_MAX / pixels) return fail_arg("more than 2^32 - 1 16-channel chunks of output in one launch");
+  if (int rc = geom_check_fit(g, true)) return rc;
+  if (int rc = geom_check_pooled(g, ceil_mode != 0, out_height, out_width)) return rc;
+  if (int rc = geom_count(g)) return rc;
+  if (g.chunks == 0) return 0;
+  const int64_t wo = g.wo, ho = g.ho, pixels = g.pixels, c16 = g.c16;
   if (!codes || !pooled) return fail_arg("NULL pointer");
   if (((((uintptr_t)codes) | ((uintptr_t)pooled)) & 15u) != 0) return fail_arg("codes and pooled must be 16-byte aligned");
   AvgArgs a;
@@ -238,10 +214,8 @@ int mctq_codes_avgpool_nhwc(const void* codes, void* pooled, int32_t code_dtype,
   a.H = (int32_t)height; a.W = (int32_t)width; a.kh = kh; a.kw = kw;
   a.stride_h = stride_h; a.stride_w = stride_w; a.pad_h = pad_h; a.pad_w = pad_w;
   a.include_pad = count_include_pad != 0; a.divisor = divisor_override;
-  const bool is_signed = code_dtype == MCTQ_CODE_I8;
-  a.flip = is_signed ? 0x80808080u : 0u;
-  a.zb = zero_point + (is_signed ? 128 : 0);
-  a.scale = scale;
+  const CodeForm f = code_form(code_dtype, zero_point, scale);
+  a.flip = f.flip; a.zb = f.zb; a.scale = f.scale;
   a.o = o;
   // split form: G = the least power of two >= C / 16, at most 16, chunks of a pixel per workgroup
   uint32_t gshift = 0;
@@ -262,10 +236,7 @@ int mctq_codes_avgpool_nhwc(const void* codes, void* pooled, int32_t code_dtype,
   const hipStream_t s = (hipStream_t)stream;
   if (split) hipLaunchKernelGGL(codes_avgpool_split_kernel, dim3((unsigned)split_blocks), dim3(kThreads), 0, s, a);
   else hipLaunchKernelGGL(codes_avgpool_lane_kernel, dim3((unsigned)lane_blocks), dim3(kThreads), 0, s, a);
-  g_note.shape = "codes_avgpool";
-  g_note.op = is_signed ? (split ? "i8 avg split" : "i8 avg lane") : (split ? "u8 avg split" : "u8 avg lane");
-  g_note.unroll = 1; g_note.nt = 0; g_note.in_bytes = 1; g_note.out_bytes = 1; ++g_note.count;
-  if (g_launch_log) log_launch();
+  note_launch("codes_avgpool", f.is_signed ? (split ? "i8 avg split" : "i8 avg lane") : (split ? "u8 avg split" : "u8 avg lane"), 1, 0, 1, 1);
   return check_launch("mctq_codes_avgpool_nhwc");
 }
 

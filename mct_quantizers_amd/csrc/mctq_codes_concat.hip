@@ -96,20 +96,18 @@ int mctq_codes_concat_nhwc(const mctq_concat_item* items, int32_t count, void* o
   if (count < 1 || count > kConcatMax) return fail_arg("count must be 1 .. 8");
   if (!items) return fail_arg("items is NULL");
   if (pixels < 0) return fail_arg("pixels < 0");
-  if (!(scale > 0.0f) || !__builtin_isfinite(scale)) return fail_arg("scale must be finite and positive");
+  const FormWords ow = {"out_code_dtype", "zero_point", "the output's type", "scale"};
+  if (int rc = form_check_scale(scale, ow.scale)) return rc;
   QlOut o;
-  if (out_code_dtype != MCTQ_CODE_I8 && out_code_dtype != MCTQ_CODE_U8) return fail_arg("bad out_code_dtype");
+  if (int rc = form_check_dtype(out_code_dtype, ow.dtype)) return rc;
   if (int rc = ql_output_form(o, out_code_dtype, scale, zero_point, quant_min, quant_max)) return rc;
   const bool o_signed = out_code_dtype == MCTQ_CODE_I8;
-  if (o_signed ? (zero_point < -128 || zero_point > 127) : (zero_point < 0 || zero_point > 255))
-    return fail_arg("zero_point is no code of the output's type");
+  if (int rc = form_check_zero_point(out_code_dtype, zero_point, ow.zero_point, ow.type)) return rc;
   int64_t row = 0;                                                           // chunks per output row
   for (int k = 0; k < count; ++k) {
     const mctq_concat_item& it = items[k];
-    if (it.code_dtype != MCTQ_CODE_I8 && it.code_dtype != MCTQ_CODE_U8) return fail_arg("bad code_dtype of an operand");
-    if (it.code_dtype == MCTQ_CODE_I8 ? (it.zero_point < -128 || it.zero_point > 127) : (it.zero_point < 0 || it.zero_point > 255))
-      return fail_arg("an operand's zero_point is no code of its type");
-    if (!(it.scale > 0.0f) || !__builtin_isfinite(it.scale)) return fail_arg("an operand's scale must be finite and positive");
+    if (int rc = form_check(it.code_dtype, it.zero_point, it.scale,
+                            {"code_dtype of an operand", "an operand's zero_point", "its type", "an operand's scale"})) return rc;
     if (it.channels <= 0 || it.channels % 16 != 0) return fail_arg("an operand's channels must be a positive multiple of 16");
     if (it.channels / 16 > INT32_MAX - row) return fail_arg("more than 2^31 - 1 16-byte chunks in one launch");
     row += it.channels / 16;
@@ -119,7 +117,6 @@ int mctq_codes_concat_nhwc(const mctq_concat_item* items, int32_t count, void* o
   if (pixels > INT32_MAX / row) return fail_arg("more than 2^31 - 1 16-byte chunks in one launch");
   if (!out) return fail_arg("out is NULL");
   if (((uintptr_t)out & 15u) != 0) return fail_arg("out must be 16-byte aligned");
-  const uintptr_t ob = (uintptr_t)out, oe = ob + (uintptr_t)pixels * (uintptr_t)row * 16u;
   ConcatArgs a;
   a.copy = 0;
   uint32_t end = 0;
@@ -132,15 +129,13 @@ int mctq_codes_concat_nhwc(const mctq_concat_item* items, int32_t count, void* o
     if (!it.codes) return fail_arg("an operand's codes pointer is NULL");
     if (((uintptr_t)it.codes & 15u) != 0) return fail_arg("an operand's codes must be 16-byte aligned");
     // the two byte ranges: a lane would read codes another lane has overwritten
-    const uintptr_t cb = (uintptr_t)it.codes, ce = cb + (uintptr_t)pixels * (uintptr_t)it.channels;
-    if (ob < ce && cb < oe) return fail_arg("out overlaps an operand");
-    const bool k_signed = it.code_dtype == MCTQ_CODE_I8;
+    if (ranges_overlap(out, (size_t)pixels * (size_t)row * 16u, it.codes, (size_t)pixels * (size_t)it.channels))
+      return fail_arg("out overlaps an operand");
+    const CodeForm f = code_form(it.code_dtype, it.zero_point, it.scale);
     end += (uint32_t)(it.channels / 16);
     a.src[k] = static_cast<const u32x4*>(it.codes);
     a.end[k] = end;
-    a.flip[k] = k_signed ? 0x80808080u : 0u;
-    a.zb[k] = (float)(it.zero_point + (k_signed ? 128 : 0));
-    a.scale[k] = it.scale;
+    a.flip[k] = f.flip; a.zb[k] = (float)f.zb; a.scale[k] = f.scale;
     const bool whole = o_signed ? (quant_min == -128 && quant_max == 127) : (quant_min == 0 && quant_max == 255);
     if (g_concat_copy && whole && it.code_dtype == out_code_dtype && it.zero_point == zero_point
         && __builtin_bit_cast(uint32_t, it.scale) == __builtin_bit_cast(uint32_t, scale)
@@ -155,9 +150,7 @@ int mctq_codes_concat_nhwc(const mctq_concat_item* items, int32_t count, void* o
   hipLaunchKernelGGL(codes_concat_kernel, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, a);
   static thread_local char op_text[24];
   snprintf(op_text, sizeof(op_text), "%d -> %s", (int)count, o_signed ? "i8" : "u8");
-  g_note.shape = "codes_concat"; g_note.op = op_text;
-  g_note.unroll = 1; g_note.nt = 0; g_note.in_bytes = 1; g_note.out_bytes = 1; ++g_note.count;
-  if (g_launch_log) log_launch();
+  note_launch("codes_concat", op_text, 1, 0, 1, 1);
   return check_launch("mctq_codes_concat_nhwc");
 }
 

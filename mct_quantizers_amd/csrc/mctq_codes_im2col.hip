@@ -68,22 +68,15 @@ extern "C" {
 int mctq_codes_im2col_nhwc(const void* codes, void* patches, int64_t batch, int64_t height, int64_t width, int64_t channels,
                            int32_t kh, int32_t kw, int32_t stride_h, int32_t stride_w, int32_t pad_h, int32_t pad_w,
                            int32_t dil_h, int32_t dil_w, int32_t pad_code, void* stream) {
-  if (batch < 0 || height < 0 || width < 0 || channels < 0) return fail_arg("negative extent");
-  if (kh < 1 || kw < 1) return fail_arg("kernel size below 1");
-  if (stride_h < 1 || stride_w < 1) return fail_arg("stride below 1");
-  if (dil_h < 1 || dil_w < 1) return fail_arg("dilation below 1");
-  if (pad_h < 0 || pad_w < 0) return fail_arg("negative padding");
+  WindowGeom g = {batch, height, width, channels, kh, kw, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w};
+  if (int rc = geom_check_sizes(g, false)) return rc;
   if (pad_code < -128 || pad_code > 255) return fail_arg("pad_code outside [-128, 255]");
-  if (channels % 16 != 0) return fail_arg("channels must be a multiple of 16");
+  if (int rc = geom_check_channels(g)) return rc;
   constexpr int64_t kMaxK = 1 << 15;
   if (kh > kMaxK || kw > kMaxK || channels > kMaxK || (int64_t)kh * kw * channels > kMaxK)
     return fail_arg("kh * kw * channels > 32768: outside the consumer's limit");
-  // padded extents within int32: the kernel's input coordinates oy * stride + ky * dilation never exceed them
-  const int64_t hp = height + 2 * (int64_t)pad_h, wp = width + 2 * (int64_t)pad_w;
-  if (hp > INT32_MAX || wp > INT32_MAX) return fail_arg("padded image extent exceeds 2^31 - 1");
-  const int64_t span_h = (int64_t)dil_h * (kh - 1) + 1, span_w = (int64_t)dil_w * (kw - 1) + 1;
-  if (hp < span_h || wp < span_w) return fail_arg("the kernel does not fit the padded image (Ho <= 0 or Wo <= 0)");
-  const int64_t ho = (hp - span_h) / stride_h + 1, wo = (wp - span_w) / stride_w + 1;
+  if (int rc = geom_check_fit(g, false)) return rc;
+  const int64_t ho = g.ho, wo = g.wo;
   if (batch == 0) return 0;
   if (batch > INT32_MAX / (ho * wo)) return fail_arg("too many output rows for one launch");       // ho * wo < 2^62
   const int64_t rows = batch * ho * wo, row_chunks = (int64_t)kh * kw * channels / 16;
@@ -106,9 +99,7 @@ int mctq_codes_im2col_nhwc(const void* codes, void* patches, int64_t batch, int6
   a.pad4 = (uint32_t)(pad_code & 0xFF) * 0x01010101u;
   const int64_t blocks = (rows + rows_per_block - 1) / rows_per_block;                                // <= rows < 2^31
   hipLaunchKernelGGL(codes_im2col_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, a);
-  g_note.shape = "codes_im2col"; g_note.op = "byte gather";
-  g_note.unroll = 1; g_note.nt = MCTQ_IM2COL_NT; g_note.in_bytes = 1; g_note.out_bytes = 1; ++g_note.count;
-  if (g_launch_log) log_launch();
+  note_launch("codes_im2col", "byte gather", 1, MCTQ_IM2COL_NT, 1, 1);
   return check_launch("mctq_codes_im2col_nhwc");
 }
 

@@ -19,7 +19,7 @@
 // loads do not depend on a branch.  Every window of a geometry PyTorch accepts has a tap inside the image unless the
 // image is narrower than the dilation; such a window then gives the least code of the type (0 / -128), which is what
 // ATen's integer max pool gives too.
-#include "mctq_consumer.hpp"               // FastDiv, u32x4
+#include "mctq_consumer.hpp"               // FastDiv, u32x4, WindowGeom
 
 // timing experiment (tools/pool_consumer_probe.py, section forms): 1 = 2 x 2 and 3 x 3 kernels run an instance whose tap
 // loops are unrolled at compile time (all loads of a lane in flight at once); 0 (shipped): the run-time loops for every size
@@ -86,15 +86,6 @@ __global__ __launch_bounds__(kThreads) void codes_maxpool_kernel(PoolArgs a) {
   reinterpret_cast<u32x4*>(a.y)[g] = out;
 }
 
-// PyTorch's pooling_output_shape along one axis (padded extent np = n + 2 * pad, span = dil * (k - 1) + 1 <= np): with
-// ceil_mode the division rounds up, and a last window that would start beyond the image plus its left padding is dropped.
-static int64_t pooled_extent(int64_t n, int64_t pad, int64_t span, int64_t stride, bool ceil_mode) {
-  const int64_t np = n + 2 * pad;
-  int64_t out = (np - span + (ceil_mode ? stride - 1 : 0)) / stride + 1;
-  if (ceil_mode && (out - 1) * stride >= n + pad) --out;
-  return out;
-}
-
 }  // namespace mctq
 
 using namespace mctq;
@@ -105,51 +96,33 @@ int mctq_codes_maxpool_nhwc(const void* codes, void* pooled, int32_t code_dtype,
                             int64_t channels, int32_t kh, int32_t kw, int32_t stride_h, int32_t stride_w, int32_t pad_h,
                             int32_t pad_w, int32_t dil_h, int32_t dil_w, int32_t ceil_mode, int64_t out_height, int64_t out_width,
                             void* stream) {
-  if (batch < 0 || height < 0 || width < 0 || channels < 0) return fail_arg("negative extent");
-  if (kh < 1 || kw < 1) return fail_arg("kernel size below 1");
-  if (stride_h < 1 || stride_w < 1) return fail_arg("stride below 1");
-  if (dil_h < 1 || dil_w < 1) return fail_arg("dilation below 1");
-  if (pad_h < 0 || pad_w < 0) return fail_arg("negative padding");
-  if (pad_h > kh / 2 || pad_w > kw / 2) return fail_arg("padding larger than half the kernel size");
-  if (channels % 16 != 0) return fail_arg("channels must be a multiple of 16");
-  if (code_dtype != MCTQ_CODE_I8 && code_dtype != MCTQ_CODE_U8) return fail_arg("bad code_dtype");
-  // the kernel's input coordinates oy * stride - pad + ky * dilation stay below padded extent + span: within int32
-  const int64_t hp = height + 2 * (int64_t)pad_h, wp = width + 2 * (int64_t)pad_w;
-  const int64_t span_h = (int64_t)dil_h * (kh - 1) + 1, span_w = (int64_t)dil_w * (kw - 1) + 1;
-  if (hp + span_h > INT32_MAX || wp + span_w > INT32_MAX) return fail_arg("padded image extent exceeds 2^31 - 1");
-  if (hp < span_h || wp < span_w) return fail_arg("the kernel does not fit the padded image (Ho <= 0 or Wo <= 0)");
-  const int64_t ho = pooled_extent(height, pad_h, span_h, stride_h, ceil_mode != 0);
-  const int64_t wo = pooled_extent(width, pad_w, span_w, stride_w, ceil_mode != 0);
-  // the caller allocated out_height x out_width pixels per image: a disagreement would be an out-of-bounds write
-  if (out_height != ho || out_width != wo) return fail_arg("out_height / out_width are not the pooled extent");
-  if (batch == 0 || channels == 0) return 0;
-  // (padding alone could make room for a kernel on an image without pixels; the clamped loads need one)
-  if (height == 0 || width == 0) return fail_arg("an image of a non-empty batch needs at least one pixel");
-  if (batch > INT32_MAX / (ho * wo)) return fail_arg("too many output pixels for one launch");       // ho * wo < 2^62
-  const int64_t pixels = batch * ho * wo, c16 = channels / 16;
-  // a lane's index, pixel * (channels / 16) + chunk, is a 32-bit number (beyond it: split the batch)
-  if (c16 > UINT32_MAX / pixels) return fail_arg("more than 2^32 - 1 16-channel chunks of output in one launch");
+  WindowGeom g = {batch, height, width, channels, kh, kw, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w};
+  if (int rc = geom_check_sizes(g, true)) return rc;
+  if (int rc = geom_check_channels(g)) return rc;
+  if (int rc = form_check_dtype(code_dtype, "code_dtype")) return rc;
+  if (int rc = geom_check_fit(g, true)) return rc;
+  if (int rc = geom_check_pooled(g, ceil_mode != 0, out_height, out_width)) return rc;
+  if (int rc = geom_count(g)) return rc;
+  if (g.chunks == 0) return 0;
   if (!codes || !pooled) return fail_arg("NULL pointer");
   if (((((uintptr_t)codes) | ((uintptr_t)pooled)) & 15u) != 0) return fail_arg("codes and pooled must be 16-byte aligned");
   PoolArgs a;
   a.x = static_cast<const uint8_t*>(codes);
   a.y = static_cast<uint8_t*>(pooled);
-  a.c16 = FastDiv::make((uint32_t)c16);
-  a.wo = FastDiv::make((uint32_t)wo);
-  a.ho = FastDiv::make((uint32_t)ho);
-  a.chunks = (uint32_t)(pixels * c16);
+  a.c16 = FastDiv::make((uint32_t)g.c16);
+  a.wo = FastDiv::make((uint32_t)g.wo);
+  a.ho = FastDiv::make((uint32_t)g.ho);
+  a.chunks = (uint32_t)g.chunks;
   a.H = (int32_t)height; a.W = (int32_t)width; a.kh = kh; a.kw = kw;
   a.stride_h = stride_h; a.stride_w = stride_w; a.pad_h = pad_h; a.pad_w = pad_w; a.dil_h = dil_h; a.dil_w = dil_w;
-  a.flip = code_dtype == MCTQ_CODE_I8 ? 0x80808080u : 0u;
+  a.flip = code_form(code_dtype).flip;
   const unsigned blocks = (unsigned)(((int64_t)a.chunks + kThreads - 1) / kThreads);                  // <= 2^24
   const hipStream_t s = (hipStream_t)stream;
   const int fixed = MCTQ_POOL_UNROLL && kh == kw && (kh == 2 || kh == 3) ? kh : 0;
   if (fixed == 2) hipLaunchKernelGGL(codes_maxpool_kernel<2>, dim3(blocks), dim3(kThreads), 0, s, a);
   else if (fixed == 3) hipLaunchKernelGGL(codes_maxpool_kernel<3>, dim3(blocks), dim3(kThreads), 0, s, a);
   else hipLaunchKernelGGL(codes_maxpool_kernel<0>, dim3(blocks), dim3(kThreads), 0, s, a);
-  g_note.shape = "codes_maxpool"; g_note.op = code_dtype == MCTQ_CODE_U8 ? "u8 max" : "i8 max";
-  g_note.unroll = fixed ? fixed * fixed : 1; g_note.nt = 0; g_note.in_bytes = 1; g_note.out_bytes = 1; ++g_note.count;
-  if (g_launch_log) log_launch();
+  note_launch("codes_maxpool", code_dtype == MCTQ_CODE_U8 ? "u8 max" : "i8 max", fixed ? fixed * fixed : 1, 0, 1, 1);
   return check_launch("mctq_codes_maxpool_nhwc");
 }
 

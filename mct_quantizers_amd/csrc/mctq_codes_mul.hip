@@ -99,20 +99,15 @@ int mctq_codes_mul_nhwc(const void* a, int32_t a_code_dtype, float a_scale, int3
                         int32_t g_quant_max, int64_t gate_pixels, void* out, int32_t out_code_dtype, int64_t pixels,
                         int64_t channels, float scale, int32_t zero_point, int32_t quant_min, int32_t quant_max, void* stream) {
   if (pixels < 0) return fail_arg("pixels < 0");
-  if (a_code_dtype != MCTQ_CODE_I8 && a_code_dtype != MCTQ_CODE_U8) return fail_arg("bad a_code_dtype");
-  if (g_code_dtype != MCTQ_CODE_I8 && g_code_dtype != MCTQ_CODE_U8) return fail_arg("bad g_code_dtype");
-  if (out_code_dtype != MCTQ_CODE_I8 && out_code_dtype != MCTQ_CODE_U8) return fail_arg("bad out_code_dtype");
-  const bool a_signed = a_code_dtype == MCTQ_CODE_I8, g_signed = g_code_dtype == MCTQ_CODE_I8;
-  const bool o_signed = out_code_dtype == MCTQ_CODE_I8;
-  if (a_signed ? (a_zero_point < -128 || a_zero_point > 127) : (a_zero_point < 0 || a_zero_point > 255))
-    return fail_arg("a_zero_point is no code of a's type");
-  if (g_signed ? (g_zero_point < -128 || g_zero_point > 127) : (g_zero_point < 0 || g_zero_point > 255))
-    return fail_arg("g_zero_point is no code of g's type");
-  if (o_signed ? (zero_point < -128 || zero_point > 127) : (zero_point < 0 || zero_point > 255))
-    return fail_arg("zero_point is no code of the output's type");
-  if (!(a_scale > 0.0f) || !__builtin_isfinite(a_scale)) return fail_arg("a_scale must be finite and positive");
-  if (!(g_scale > 0.0f) || !__builtin_isfinite(g_scale)) return fail_arg("g_scale must be finite and positive");
-  if (!(scale > 0.0f) || !__builtin_isfinite(scale)) return fail_arg("scale must be finite and positive");
+  const struct { int32_t dtype, zp; float scale; FormWords w; } forms[3] = {
+      {a_code_dtype, a_zero_point, a_scale, {"a_code_dtype", "a_zero_point", "a's type", "a_scale"}},
+      {g_code_dtype, g_zero_point, g_scale, {"g_code_dtype", "g_zero_point", "g's type", "g_scale"}},
+      {out_code_dtype, zero_point, scale, {"out_code_dtype", "zero_point", "the output's type", "scale"}}};
+  // every code type, then every zero point, then every scale
+  for (const auto& f : forms) if (int rc = form_check_dtype(f.dtype, f.w.dtype)) return rc;
+  for (const auto& f : forms) if (int rc = form_check_zero_point(f.dtype, f.zp, f.w.zero_point, f.w.type)) return rc;
+  for (const auto& f : forms) if (int rc = form_check_scale(f.scale, f.w.scale)) return rc;
+  const CodeForm fa = code_form(a_code_dtype, a_zero_point, a_scale), fg = code_form(g_code_dtype, g_zero_point, g_scale);
   QlOut o, gq;
   if (int rc = ql_output_form(o, out_code_dtype, scale, zero_point, quant_min, quant_max)) return rc;
   if (gate_pixels < 0) return fail_arg("gate_pixels < 0");
@@ -137,14 +132,13 @@ int mctq_codes_mul_nhwc(const void* a, int32_t a_code_dtype, float a_scale, int3
   // the byte ranges: a lane would read codes another lane has overwritten (a and g may be one buffer: x * x)
   const uintptr_t bytes = (uintptr_t)pixels * (uintptr_t)channels;
   const uintptr_t g_bytes = gate_pixels == 0 ? bytes : bytes / (uintptr_t)gate_pixels * (g_is_f32 ? 4u : 1u);
-  const uintptr_t ob = (uintptr_t)out, oe = ob + bytes;
-  if (ob < (uintptr_t)a + bytes && (uintptr_t)a < oe) return fail_arg("out overlaps a");
-  if (ob < (uintptr_t)g + g_bytes && (uintptr_t)g < oe) return fail_arg("out overlaps g");
+  if (ranges_overlap(out, bytes, a, bytes)) return fail_arg("out overlaps a");
+  if (ranges_overlap(out, bytes, g, g_bytes)) return fail_arg("out overlaps g");
   MulArgs k;
   k.a = static_cast<const u32x4*>(a); k.g = g; k.out = static_cast<u32x4*>(out);
-  k.a_flip = a_signed ? 0x80808080u : 0u; k.g_flip = g_signed ? 0x80808080u : 0u;
-  k.a_zb = (float)(a_zero_point + (a_signed ? 128 : 0)); k.g_zb = (float)(g_zero_point + (g_signed ? 128 : 0));
-  k.a_scale = a_scale; k.g_scale = g_scale;
+  k.a_flip = fa.flip; k.g_flip = fg.flip;
+  k.a_zb = (float)fa.zb; k.g_zb = (float)fg.zb;
+  k.a_scale = fa.scale; k.g_scale = fg.scale;
   k.row = FastDiv::make((uint32_t)row);
   k.img = FastDiv::make((uint32_t)(gate_pixels == 0 ? 1 : gate_pixels));      // (gate_pixels <= pixels < 2^31, or pixels % it != 0)
   k.chunks = (uint32_t)(pixels * row);
@@ -162,10 +156,8 @@ int mctq_codes_mul_nhwc(const void* a, int32_t a_code_dtype, float a_scale, int3
     form = "row f32";
   }
   static thread_local char op_text[40];
-  snprintf(op_text, sizeof(op_text), "%s * %s -> %s %s", a_signed ? "i8" : "u8", g_signed ? "i8" : "u8", o_signed ? "i8" : "u8", form);
-  g_note.shape = "codes_mul"; g_note.op = op_text;
-  g_note.unroll = 1; g_note.nt = 0; g_note.in_bytes = 1; g_note.out_bytes = 1; ++g_note.count;
-  if (g_launch_log) log_launch();
+  snprintf(op_text, sizeof(op_text), "%s * %s -> %s %s", fa.is_signed ? "i8" : "u8", fg.is_signed ? "i8" : "u8", o.mode == 1 ? "i8" : "u8", form);
+  note_launch("codes_mul", op_text, 1, 0, 1, 1);
   return check_launch("mctq_codes_mul_nhwc");
 }
 

@@ -98,11 +98,9 @@ int mctq_fq_codes_nchw_to_nhwc(const void* x, void* codes, int64_t batch, int64_
     hipLaunchKernelGGL((codes_nchw_to_nhwc_kernel<TI>), dim3((unsigned)blocks), dim3(kThreads), 0, st,
                        static_cast<const TI*>(x), static_cast<uint8_t*>(codes), (int)channels, pixels, (int)c_tiles, p_tiles, p,
                        (float)quant_min, (float)quant_max, forms);
-    g_note.shape = "codes_nchw_to_nhwc";
-    g_note.op = vload ? (vstore ? "vector loads + 16-byte stores" : "vector loads + byte stores")
-                      : (vstore ? "scalar loads + 16-byte stores" : "scalar loads + byte stores");
-    g_note.unroll = 4; g_note.nt = 1; g_note.in_bytes = (int)sizeof(TI); g_note.out_bytes = 1; ++g_note.count;
-    if (g_launch_log) log_launch();
+    note_launch("codes_nchw_to_nhwc", vload ? (vstore ? "vector loads + 16-byte stores" : "vector loads + byte stores")
+                                            : (vstore ? "scalar loads + 16-byte stores" : "scalar loads + byte stores"),
+                4, 1, (int)sizeof(TI), 1);
     return check_launch("codes nchw->nhwc launch");
   };
   switch (dtype) {

@@ -1,5 +1,6 @@
-// mctq_consumer.hpp -- what the integer consumer's translation units share (mctq_qlinear.hip, mctq_codes_im2col.hip,
-// mctq_qconv_dw.hip): the output form of a consumer launch and the per-chunk index division.
+// mctq_consumer.hpp -- what the integer consumer's translation units share (mctq_qlinear.hip, mctq_qconv_dw.hip, mctq_fq_join.hip
+// and the mctq_codes_*.hip operations on codes): the output form of a consumer launch, the per-chunk index division, and on
+// the host side the checks of an operand's form, of a window's geometry and of overlapping byte ranges.
 #pragma once
 #include "mctq_kernels.hpp"
 
@@ -131,5 +132,108 @@ struct FastDiv {
 };
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+// ------------------------------------------------------------------------------------------
+// Host side: the argument checks the code-tensor launchers share.  Every step is its own function, so that an entry point
+// runs them in its own order between its other checks; none formats or allocates unless it refuses.
+// ------------------------------------------------------------------------------------------
+static int fail_words(const char* a, const char* b, const char* c = "") {
+  char text[160];
+  snprintf(text, sizeof(text), "%s%s%s", a, b, c);
+  return fail_arg(text);
+}
+
+// The form of an int8 / uint8 code operand as the kernels take it: a code c is the byte (c ^ flip) = c + bias, bias = 128 for
+// int8 and 0 for uint8, and zb = zero_point + bias, so that byte - zb == code - zero_point.
+struct CodeForm { uint32_t flip; int32_t zb; float scale; bool is_signed; };
+static CodeForm code_form(int32_t code_dtype, int32_t zero_point = 0, float scale = 1.0f) {
+  const bool is_signed = code_dtype == MCTQ_CODE_I8;
+  return {is_signed ? 0x80808080u : 0u, zero_point + (is_signed ? 128 : 0), scale, is_signed};
+}
+// The three checks of a form, each with the caller's words for its operand: "bad <dtype>", "<zero_point> is no code of <type>"
+// (behind the first), "<scale> must be finite and positive"
+struct FormWords { const char* dtype; const char* zero_point; const char* type; const char* scale; };
+static int form_check_dtype(int32_t code_dtype, const char* dtype) {
+  return code_dtype == MCTQ_CODE_I8 || code_dtype == MCTQ_CODE_U8 ? 0 : fail_words("bad ", dtype);
+}
+static int form_check_zero_point(int32_t code_dtype, int32_t zp, const char* zero_point, const char* type) {
+  const bool is_code = code_dtype == MCTQ_CODE_I8 ? (zp >= -128 && zp <= 127) : (zp >= 0 && zp <= 255);
+  return is_code ? 0 : fail_words(zero_point, " is no code of ", type);
+}
+static int form_check_scale(float scale, const char* name) {
+  return scale > 0.0f && __builtin_isfinite(scale) ? 0 : fail_words(name, " must be finite and positive");
+}
+static int form_check(int32_t code_dtype, int32_t zp, float scale, const FormWords& w) {
+  if (int rc = form_check_dtype(code_dtype, w.dtype)) return rc;
+  if (int rc = form_check_zero_point(code_dtype, zp, w.zero_point, w.type)) return rc;
+  return form_check_scale(scale, w.scale);
+}
+// a residual operand on codes (mctq_fq_join_rc_f32, mctq_qlinear_i8_res)
+static int residual_form_check(int32_t r_code_dtype, int32_t r_zero_point, float r_scale) {
+  return form_check(r_code_dtype, r_zero_point, r_scale, {"r_code_dtype", "r_zero_point", "the residual's type", "r_scale"});
+}
+
+// two byte ranges share a byte: a lane would read what another lane has overwritten
+static bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+  const uintptr_t ab = (uintptr_t)a, bb = (uintptr_t)b;
+  return ab < bb + b_bytes && bb < ab + a_bytes;
+}
+
+// A kernel, stride, dilation and padding window over a [B, H, W, C] image, one 16-byte chunk (16 channels) of one output
+// pixel per lane.  The caller fills the arguments (dilation 1 where it has none) and leaves the rest 0; the steps below check
+// them and fill the rest.
+struct WindowGeom {
+  int64_t batch, height, width, channels;
+  int32_t kh, kw, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w;
+  int64_t hp, wp, span_h, span_w;                  // padded extents; dilation * (kernel - 1) + 1                    (geom_check_fit)
+  int64_t ho, wo;                                  // output extent: a convolution's (geom_check_fit), a pool's (geom_check_pooled)
+  int64_t pixels, c16, chunks;                     // B * Ho * Wo, C / 16, their product; 0: nothing to do           (geom_count)
+};
+static int geom_check_sizes(const WindowGeom& g, bool half_padding) {      // half_padding: the pools' rule (PyTorch's)
+  if (g.batch < 0 || g.height < 0 || g.width < 0 || g.channels < 0) return fail_arg("negative extent");
+  if (g.kh < 1 || g.kw < 1) return fail_arg("kernel size below 1");
+  if (g.stride_h < 1 || g.stride_w < 1) return fail_arg("stride below 1");
+  if (g.dil_h < 1 || g.dil_w < 1) return fail_arg("dilation below 1");
+  if (g.pad_h < 0 || g.pad_w < 0) return fail_arg("negative padding");
+  if (half_padding && (g.pad_h > g.kh / 2 || g.pad_w > g.kw / 2)) return fail_arg("padding larger than half the kernel size");
+  return 0;
+}
+static int geom_check_channels(const WindowGeom& g) { return g.channels % 16 != 0 ? fail_arg("channels must be a multiple of 16") : 0; }
+// The kernels' input coordinates stay within int32: o * stride + k * dilation never exceeds the padded extent, and where the
+// kernel subtracts the padding only afterwards (with_span) o * stride - pad + k * dilation stays below padded extent + span.
+static int geom_check_fit(WindowGeom& g, bool with_span) {
+  g.hp = g.height + 2 * (int64_t)g.pad_h; g.wp = g.width + 2 * (int64_t)g.pad_w;
+  g.span_h = (int64_t)g.dil_h * (g.kh - 1) + 1; g.span_w = (int64_t)g.dil_w * (g.kw - 1) + 1;
+  if (g.hp + (with_span ? g.span_h : 0) > INT32_MAX || g.wp + (with_span ? g.span_w : 0) > INT32_MAX)
+    return fail_arg("padded image extent exceeds 2^31 - 1");
+  if (g.hp < g.span_h || g.wp < g.span_w) return fail_arg("the kernel does not fit the padded image (Ho <= 0 or Wo <= 0)");
+  g.ho = (g.hp - g.span_h) / g.stride_h + 1; g.wo = (g.wp - g.span_w) / g.stride_w + 1;
+  return 0;
+}
+// PyTorch's pooling_output_shape along one axis (padded extent np = n + 2 * pad, span = dil * (k - 1) + 1 <= np): with
+// ceil_mode the division rounds up, and a last window that would start beyond the image plus its left padding is dropped.
+static int64_t pooled_extent(int64_t n, int64_t pad, int64_t span, int64_t stride, bool ceil_mode) {
+  const int64_t np = n + 2 * pad;
+  int64_t out = (np - span + (ceil_mode ? stride - 1 : 0)) / stride + 1;
+  if (ceil_mode && (out - 1) * stride >= n + pad) --out;
+  return out;
+}
+// the caller allocated out_height x out_width pixels per image: a disagreement would be an out-of-bounds write
+static int geom_check_pooled(WindowGeom& g, bool ceil_mode, int64_t out_height, int64_t out_width) {
+  g.ho = pooled_extent(g.height, g.pad_h, g.span_h, g.stride_h, ceil_mode);
+  g.wo = pooled_extent(g.width, g.pad_w, g.span_w, g.stride_w, ceil_mode);
+  return out_height != g.ho || out_width != g.wo ? fail_arg("out_height / out_width are not the pooled extent") : 0;
+}
+static int geom_count(WindowGeom& g) {
+  if (g.batch == 0 || g.channels == 0) return 0;
+  // (padding alone could make room for a kernel on an image without pixels; the clamped loads need one)
+  if (g.height == 0 || g.width == 0) return fail_arg("an image of a non-empty batch needs at least one pixel");
+  if (g.batch > INT32_MAX / (g.ho * g.wo)) return fail_arg("too many output pixels for one launch");   // ho * wo < 2^62
+  g.pixels = g.batch * g.ho * g.wo; g.c16 = g.channels / 16;
+  // a lane's index, pixel * (channels / 16) + chunk, is a 32-bit number (beyond it: split the batch)
+  if (g.c16 > UINT32_MAX / g.pixels) return fail_arg("more than 2^32 - 1 16-channel chunks of output in one launch");
+  g.chunks = g.pixels * g.c16;
+  return 0;
+}
 
 }  // namespace mctq

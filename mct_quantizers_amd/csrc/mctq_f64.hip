@@ -303,8 +303,7 @@ static int launch_lut64_steps(const Lut64Steps& op, const void* xv, float* y, in
   if (idx32) { if (vec) MCTQ_L64S(uint32_t, true); else MCTQ_L64S(uint32_t, false); }
   else { if (vec) MCTQ_L64S(uint64_t, true); else MCTQ_L64S(uint64_t, false); }
 #undef MCTQ_L64S
-  g_note.shape = "lut64_steps_kernel"; g_note.op = "LutSteps64"; g_note.unroll = 4; g_note.nt = 1; g_note.in_bytes = 8; g_note.out_bytes = 4; ++g_note.count;
-  if (g_launch_log) log_launch();
+  note_launch("lut64_steps_kernel", "LutSteps64", 4, 1, 8, 4);
   return check_launch("float64 LUT threshold-list launch");
 }
 

@@ -149,22 +149,17 @@ static int fq_join_entry(const char* entry, const float* x, const float* residua
   a.op.lo = (float)quant_min; a.op.hi = (float)quant_max;
   a.p = AffineOp::make(scale, zero_point);          // inv = 1.0f / scale on the host, as both launches this one stands for
   a.relu = relu != 0;
-  const bool r_signed = r_code_dtype == MCTQ_CODE_I8;
+  const CodeForm rf = code_form(r_code_dtype, r_zero_point, r_scale);
   a.rcodes = static_cast<const uint8_t*>(r_codes);
-  a.rc_flip = r_signed ? 0x80808080u : 0u;
-  a.rc_zb = (float)(r_zero_point + (r_signed ? 128 : 0));
-  a.rc_scale = r_scale;
+  a.rc_flip = rf.flip; a.rc_zb = (float)rf.zb; a.rc_scale = rf.scale;
   const hipStream_t s = (hipStream_t)stream;
   if (r_codes) launch_fq_join<2>(a, (unsigned)blocks, s);
   else if (residual) launch_fq_join<1>(a, (unsigned)blocks, s);
   else launch_fq_join<0>(a, (unsigned)blocks, s);
   static thread_local char op_text[48];
-  snprintf(op_text, sizeof(op_text), "%s%s-> %s%s%s", r_codes ? (r_signed ? "addc(i8) " : "addc(u8) ") : residual ? "add " : "",
+  snprintf(op_text, sizeof(op_text), "%s%s-> %s%s%s", r_codes ? (rf.is_signed ? "addc(i8) " : "addc(u8) ") : residual ? "add " : "",
            a.relu ? "relu " : "", y ? "f32" : "", y && codes ? " + " : "", !codes ? "" : (code_dtype == MCTQ_CODE_I8 ? "i8" : "u8"));
-  g_note.shape = "fq_join"; g_note.op = op_text;
-  g_note.unroll = 4; g_note.nt = 0;
-  g_note.in_bytes = r_codes ? 5 : 4; g_note.out_bytes = (y ? 4 : 0) + (codes ? 1 : 0); ++g_note.count;
-  if (g_launch_log) log_launch();
+  note_launch("fq_join", op_text, 4, 0, r_codes ? 5 : 4, (y ? 4 : 0) + (codes ? 1 : 0));
   return check_launch(entry);
 }
 
@@ -182,10 +177,7 @@ int mctq_fq_join_rc_f32(const float* x, const void* r_codes, int32_t r_code_dtyp
   if (n < 0) return fail_arg("n < 0");
   if (n == 0) return 0;
   if (!r_codes) return fail_arg("r_codes is NULL");
-  if (r_code_dtype != MCTQ_CODE_I8 && r_code_dtype != MCTQ_CODE_U8) return fail_arg("bad r_code_dtype");
-  if (r_code_dtype == MCTQ_CODE_I8 ? (r_zero_point < -128 || r_zero_point > 127) : (r_zero_point < 0 || r_zero_point > 255))
-    return fail_arg("r_zero_point is no code of the residual's type");
-  if (!(r_scale > 0.0f) || !__builtin_isfinite(r_scale)) return fail_arg("r_scale must be finite and positive");
+  if (int rc = residual_form_check(r_code_dtype, r_zero_point, r_scale)) return rc;
   return fq_join_entry("mctq_fq_join_rc_f32", x, nullptr, r_codes, r_code_dtype, r_scale, r_zero_point, relu, y, codes,
                        code_dtype, n, scale, zero_point, quant_min, quant_max, stream);
 }

@@ -1367,13 +1367,14 @@ extern thread_local LaunchNote g_note;
 // branch per launch.
 extern int g_launch_log;
 void log_launch();
-template <class Op, class TI, class TO>
-inline void note(const char* shape, int unroll, int nt) {
-  g_note.shape = shape; g_note.op = Op::kName; g_note.unroll = unroll; g_note.nt = nt;
-  g_note.in_bytes = (int)sizeof(TI); g_note.out_bytes = (int)sizeof(TO);
+// every launcher's record of its launch (shape and op: strings that outlive the call)
+inline void note_launch(const char* shape, const char* op, int unroll, int nt, int in_bytes, int out_bytes) {
+  g_note.shape = shape; g_note.op = op; g_note.unroll = unroll; g_note.nt = nt; g_note.in_bytes = in_bytes; g_note.out_bytes = out_bytes;
   ++g_note.count;
   if (g_launch_log) log_launch();
 }
+template <class Op, class TI, class TO>
+inline void note(const char* shape, int unroll, int nt) { note_launch(shape, Op::kName, unroll, nt, (int)sizeof(TI), (int)sizeof(TO)); }
 extern int g_paced;          // launches of 3/4 ... 1 round under the paced order of waits (flat_paced_kernel per tensor; shortrows_kernel's
                              // `paced` argument per channel): 0 never, 1 (default) inside that window, 2 whenever the kernel is taken
 extern int g_shortrows;      // rows shorter than a tile through shortrows_kernel: 0 never, 1 (default) where it measured faster, 2 whenever eligible

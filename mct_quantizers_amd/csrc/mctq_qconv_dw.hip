@@ -166,43 +166,29 @@ static int qconv_dw_call(const char* entry, const void* a_codes, int32_t a_code_
                          int32_t act, int64_t batch, int64_t height, int64_t width, int64_t channels,
                          int32_t kh, int32_t kw, int32_t stride_h, int32_t stride_w, int32_t pad_h, int32_t pad_w,
                          int32_t dil_h, int32_t dil_w, void* stream) {
-  if (batch < 0 || height < 0 || width < 0 || channels < 0) return fail_arg("negative extent");
-  if (kh < 1 || kw < 1) return fail_arg("kernel size below 1");
-  if (stride_h < 1 || stride_w < 1) return fail_arg("stride below 1");
-  if (dil_h < 1 || dil_w < 1) return fail_arg("dilation below 1");
-  if (pad_h < 0 || pad_w < 0) return fail_arg("negative padding");
-  if (channels % 16 != 0) return fail_arg("channels must be a multiple of 16");
+  WindowGeom g = {batch, height, width, channels, kh, kw, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w};
+  if (int rc = geom_check_sizes(g, false)) return rc;
+  if (int rc = geom_check_channels(g)) return rc;
   if (kh > 256 || kw > 256 || kh * kw > 256) return fail_arg("kh * kw > 256: outside the depthwise consumer's limit");
-  if (a_code_dtype != MCTQ_CODE_I8 && a_code_dtype != MCTQ_CODE_U8) return fail_arg("bad a_code_dtype");
+  if (int rc = form_check_dtype(a_code_dtype, "a_code_dtype")) return rc;
   const bool u8 = a_code_dtype == MCTQ_CODE_U8;
   // the zero point is the byte a padded tap is given (it then adds (za - za) * w = 0): it has to be a code
-  if (u8 ? (a_zero_point < 0 || a_zero_point > 255) : (a_zero_point < -128 || a_zero_point > 127))
-    return fail_arg("a_zero_point is no code of a_code_dtype");
+  if (int rc = form_check_zero_point(a_code_dtype, a_zero_point, "a_zero_point", "a_code_dtype")) return rc;
   DwArgs a;
   if (int rc = ql_output_form(a.oq, y_code_dtype, y_scale, y_zero_point, y_quant_min, y_quant_max)) return rc;
-  // padded extents within int32: the kernel's input coordinates oy * stride + ky * dilation never exceed them
-  const int64_t hp = height + 2 * (int64_t)pad_h, wp = width + 2 * (int64_t)pad_w;
-  if (hp > INT32_MAX || wp > INT32_MAX) return fail_arg("padded image extent exceeds 2^31 - 1");
-  const int64_t span_h = (int64_t)dil_h * (kh - 1) + 1, span_w = (int64_t)dil_w * (kw - 1) + 1;
-  if (hp < span_h || wp < span_w) return fail_arg("the kernel does not fit the padded image (Ho <= 0 or Wo <= 0)");
-  const int64_t ho = (hp - span_h) / stride_h + 1, wo = (wp - span_w) / stride_w + 1;
-  if (batch == 0 || channels == 0) return 0;
-  // (padding alone could make room for a kernel on an image without pixels; the clamped loads need one)
-  if (height == 0 || width == 0) return fail_arg("an image of a non-empty batch needs at least one pixel");
-  if (batch > INT32_MAX / (ho * wo)) return fail_arg("too many output pixels for one launch");       // ho * wo < 2^62
-  const int64_t pixels = batch * ho * wo, c16 = channels / 16;
-  // a lane's index, pixel * (channels / 16) + chunk, is a 32-bit number (beyond it: split the batch)
-  if (c16 > UINT32_MAX / pixels) return fail_arg("more than 2^32 - 1 16-channel chunks of output in one launch");
+  if (int rc = geom_check_fit(g, false)) return rc;
+  if (int rc = geom_count(g)) return rc;
+  if (g.chunks == 0) return 0;
   if (!a_codes || !w_codes || !w_scales || !y) return fail_arg("NULL pointer");
   if ((((uintptr_t)a_codes | (uintptr_t)w_codes | (uintptr_t)y | (uintptr_t)w_scales | (uintptr_t)w_zero_points |
         (uintptr_t)bias) & 15u) != 0)
     return fail_arg("codes, weights, per-channel tables and output must be 16-byte aligned");
   a.x = static_cast<const uint8_t*>(a_codes);
   a.w = w_codes; a.w_scales = w_scales; a.w_zero_points = w_zero_points; a.bias = bias; a.y = y;
-  a.c16 = FastDiv::make((uint32_t)c16);
-  a.wo = FastDiv::make((uint32_t)wo);
-  a.ho = FastDiv::make((uint32_t)ho);
-  a.chunks = (uint32_t)(pixels * c16);
+  a.c16 = FastDiv::make((uint32_t)g.c16);
+  a.wo = FastDiv::make((uint32_t)g.wo);
+  a.ho = FastDiv::make((uint32_t)g.ho);
+  a.chunks = (uint32_t)g.chunks;
   a.H = (int32_t)height; a.W = (int32_t)width; a.kh = kh; a.kw = kw;
   a.stride_h = stride_h; a.stride_w = stride_w; a.pad_h = pad_h; a.pad_w = pad_w; a.dil_h = dil_h; a.dil_w = dil_w;
   a.za = a_zero_point; a.sa = a_scale; a.act = act;
@@ -211,15 +197,13 @@ static int qconv_dw_call(const char* entry, const void* a_codes, int32_t a_code_
   const bool zp = w_zero_points != nullptr;
   if (u8) { if (zp) launch_qconv_dw<true, true>(a, blocks, s); else launch_qconv_dw<true, false>(a, blocks, s); }
   else { if (zp) launch_qconv_dw<false, true>(a, blocks, s); else launch_qconv_dw<false, false>(a, blocks, s); }
-  g_note.shape = "qconv_dw"; g_note.op = zp ? (u8 ? "u8 x i8 zp" : "i8 x i8 zp") : (u8 ? "u8 x i8" : "i8 x i8");
+  const char* op = zp ? (u8 ? "u8 x i8 zp" : "i8 x i8 zp") : (u8 ? "u8 x i8" : "i8 x i8");
   if (act) {                                       // "u8 x i8 zp hardswish"
     static thread_local char op_text[40];
-    snprintf(op_text, sizeof(op_text), "%s%s", g_note.op, act == 1 ? " hardswish" : " hardsigmoid");
-    g_note.op = op_text;
+    snprintf(op_text, sizeof(op_text), "%s%s", op, act == 1 ? " hardswish" : " hardsigmoid");
+    op = op_text;
   }
-  g_note.unroll = MCTQ_DW_UNROLL3 && kh == 3 && kw == 3 ? 9 : 1; g_note.nt = 0;
-  g_note.in_bytes = 1; g_note.out_bytes = a.oq.mode == 0 ? 4 : 1; ++g_note.count;
-  if (g_launch_log) log_launch();
+  note_launch("qconv_dw", op, MCTQ_DW_UNROLL3 && kh == 3 && kw == 3 ? 9 : 1, 0, 1, a.oq.mode == 0 ? 4 : 1);
   return check_launch(entry);
 }
 

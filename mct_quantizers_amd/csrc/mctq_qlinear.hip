@@ -22,20 +22,18 @@ extern int g_ql_variant;                // tuning hook "ql_variant": 0 = automat
 // what the calling thread launched last (mctq_last_launch): "qlinear_<kernel>_<tile>" with the code widths
 template <bool A_U8>
 static void note_ql(const char* shape, int u = 0, bool zp = false, const QlRes* res = nullptr) {   // zp: the form with weight zero points ran
-  g_note.shape = shape; g_note.op = zp ? (A_U8 ? "u8 x i8 zp" : "i8 x i8 zp") : (A_U8 ? "u8 x i8" : "i8 x i8");
+  const char* op = zp ? (A_U8 ? "u8 x i8 zp" : "i8 x i8 zp") : (A_U8 ? "u8 x i8" : "i8 x i8");
   if (res && res->mode) {                 // the residual form ran: "u8 x i8 res(u8) relu"
     static thread_local char op_text[40];
-    snprintf(op_text, sizeof(op_text), "%s res(%s)%s", g_note.op, res->mode == 1 ? "f32" : res->mode == 2 ? "i8" : "u8",
+    snprintf(op_text, sizeof(op_text), "%s res(%s)%s", op, res->mode == 1 ? "f32" : res->mode == 2 ? "i8" : "u8",
              res->relu ? " relu" : "");
-    g_note.op = op_text;
+    op = op_text;
   } else if (res && res->act) {           // the activation form ran (mctq_qlinear_i8_act): "u8 x i8 hardswish"
     static thread_local char op_text[40];
-    snprintf(op_text, sizeof(op_text), "%s%s", g_note.op, res->act == 1 ? " hardswish" : " hardsigmoid");
-    g_note.op = op_text;
+    snprintf(op_text, sizeof(op_text), "%s%s", op, res->act == 1 ? " hardswish" : " hardsigmoid");
+    op = op_text;
   }
-  g_note.unroll = u; g_note.nt = 0;
-  g_note.in_bytes = 1; g_note.out_bytes = 4; ++g_note.count;
-  if (g_launch_log) log_launch();
+  note_launch(shape, op, u, 0, 1, 4);
 }
 extern int g_ql_stagger;                // tuning hook "ql_stagger": half of the tiled kernel's waves copy after multiplying (default off)
 extern int g_ql_rot;                    // tuning hook "ql_rot": K rotation between the blocks that share a weight tile (default off)
@@ -1449,9 +1447,7 @@ int mctq_codes_rowsum(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_
   if (u8) { if (block) MCTQ_ROWSUM(true, true); else MCTQ_ROWSUM(true, false); }
   else { if (block) MCTQ_ROWSUM(false, true); else MCTQ_ROWSUM(false, false); }
 #undef MCTQ_ROWSUM
-  g_note.shape = "codes_rowsum"; g_note.op = block ? (u8 ? "u8 block per row" : "i8 block per row") : (u8 ? "u8 wave per row" : "i8 wave per row");
-  g_note.unroll = 1; g_note.nt = 0; g_note.in_bytes = 1; g_note.out_bytes = 4; ++g_note.count;
-  if (g_launch_log) log_launch();
+  note_launch("codes_rowsum", block ? (u8 ? "u8 block per row" : "i8 block per row") : (u8 ? "u8 wave per row" : "i8 wave per row"), 1, 0, 1, 4);
   return check_launch("mctq_codes_rowsum");
 }
 
@@ -1486,17 +1482,14 @@ int mctq_qlinear_i8_res(const void* a_codes, int32_t a_code_dtype, int32_t a_zer
   if (M > 0 && N > 0 && M <= INT32_MAX / 2 && N <= INT32_MAX / 2) {
     if (!residual) return fail_arg("residual is NULL");
     if (r_code_dtype >= 0) {                   // the residual as codes: mctq_fq_join_rc_f32's checks
-      if (r_code_dtype != MCTQ_CODE_I8 && r_code_dtype != MCTQ_CODE_U8) return fail_arg("bad r_code_dtype");
-      if (r_code_dtype == MCTQ_CODE_I8 ? (r_zero_point < -128 || r_zero_point > 127) : (r_zero_point < 0 || r_zero_point > 255))
-        return fail_arg("r_zero_point is no code of the residual's type");
-      if (!(r_scale > 0.0f) || !__builtin_isfinite(r_scale)) return fail_arg("r_scale must be finite and positive");
+      if (int rc = residual_form_check(r_code_dtype, r_zero_point, r_scale)) return rc;
     } else if (((uintptr_t)residual & 3u) != 0) {
       return fail_arg("a float32 residual must be 4-byte aligned");
     }
     if (y) {                                   // the two byte ranges: a block would read residuals another has overwritten
-      const uintptr_t yb = (uintptr_t)y, rb = (uintptr_t)residual, elems = (uintptr_t)M * (uintptr_t)N;
-      const uintptr_t ye = yb + elems * (y_code_dtype < 0 ? 4u : 1u), re = rb + elems * (r_code_dtype < 0 ? 4u : 1u);
-      if (yb < re && rb < ye) return fail_arg("y overlaps the residual");
+      const size_t elems = (size_t)M * (size_t)N;
+      if (ranges_overlap(y, elems * (y_code_dtype < 0 ? 4u : 1u), residual, elems * (r_code_dtype < 0 ? 4u : 1u)))
+        return fail_arg("y overlaps the residual");
     }
   }
   c.res = QlRes{residual, r_code_dtype < 0 ? 1 : r_code_dtype == MCTQ_CODE_I8 ? 2 : 3, (int)r_zero_point, r_scale, relu != 0, 0};

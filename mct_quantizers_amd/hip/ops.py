@@ -411,6 +411,40 @@ def _code_of(codes: torch.Tensor) -> int:
     return native.CODE_U8 if codes.dtype == torch.uint8 else native.CODE_I8
 
 
+def _is_codes(t) -> bool:
+    return isinstance(t, torch.Tensor) and t.dtype in (torch.int8, torch.uint8)
+
+
+def _nhwc_codes(x, caller: str):
+    """The checks of a wrapper that takes int8 / uint8 codes [N, H, W, C]."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError(f"{caller} takes [N, H, W, C] tensors")
+    if not _is_codes(x):
+        raise NotImplementedError(f"{caller}: int8 / uint8 codes only, got {x.dtype}")
+
+
+def _check_form(caller: str, dtype, zero_point=None, scale=None, zp_words: str = "the zero point {}", scale_words: str = "the scales"):
+    """The form of an operand on codes of ``dtype``, in ``caller``'s name and its words for the operand: the zero point (where
+    given; ``zp_words`` is formatted with it) is a code of ``dtype``, the scale (or each of several) is finite and positive."""
+    if zero_point is not None:
+        lo, hi = (0, 255) if dtype == torch.uint8 else (-128, 127)
+        if not lo <= zero_point <= hi:
+            raise ValueError(f"{caller}: {zp_words.format(zero_point)} is no {dtype} code")
+    scales = () if scale is None else scale if isinstance(scale, tuple) else (scale,)
+    if not all(0.0 < s < float("inf") for s in scales):
+        raise ValueError(f"{caller}: {scale_words} must be finite and positive")
+
+
+def _out_form(out_form):
+    """``(scale, zero_point, qmin, qmax)`` of a holder -> those four, the torch dtype of its codes and the C ABI's code type."""
+    scale, zero_point, qmin, qmax = float(out_form[0]), int(out_form[1]), int(out_form[2]), int(out_form[3])
+    return (scale, zero_point, qmin, qmax) + _code_dtype(qmin, qmax)
+
+
+def _contiguous(x: torch.Tensor) -> torch.Tensor:
+    return x if x.is_contiguous() else x.contiguous()
+
+
 def _packed_shape(x):
     return tuple(x.shape[:-1]) + (x.shape[-1] // 2,) if x.dim() and x.shape[-1] % 2 == 0 and x.is_contiguous() \
         else (x.numel() // 2,)
@@ -550,14 +584,10 @@ def fq_join(x, scale: float, zero_point: int, qmin: int, qmax: int, residual=Non
         if residual is not None:
             raise ValueError("fq_join: residual and residual_codes exclude each other")
         r_codes, r_scale, r_zp = residual_codes
-        if not isinstance(r_codes, torch.Tensor) or r_codes.dtype not in (torch.int8, torch.uint8):
+        if not _is_codes(r_codes):
             raise TypeError("fq_join: residual_codes takes an int8 / uint8 tensor")
         r_scale, r_zp = float(r_scale), int(r_zp)
-        r_lo, r_hi = (0, 255) if r_codes.dtype == torch.uint8 else (-128, 127)
-        if not r_lo <= r_zp <= r_hi:
-            raise ValueError(f"fq_join: the residual's zero point {r_zp} is no {r_codes.dtype} code")
-        if not 0.0 < r_scale < float("inf"):
-            raise ValueError("fq_join: the residual's scale must be finite and positive")
+        _check_form("fq_join", r_codes.dtype, r_zp, r_scale, "the residual's zero point {}", "the residual's scale")
     tdt = code = None
     if want_codes:
         tdt, code = _code_dtype(qmin, qmax)
@@ -612,16 +642,31 @@ def _conv_out_size(n: int, k: int, s: int, p: int, d: int) -> int:
     return (n + 2 * p - d * (k - 1) - 1) // s + 1
 
 
-def _conv_geometry(h: int, w: int, kernel_size, stride, padding, dilation, caller: str):
+def _pool_out_size(n: int, k: int, s: int, p: int, d: int, ceil_mode: bool) -> int:
+    """Outputs along one axis of ``torch.nn.MaxPool2d``: as ``_conv_out_size``, the division rounded up with ``ceil_mode``, less
+    the last window where it would start beyond the image plus its left padding."""
+    span = n + 2 * p - d * (k - 1) - 1
+    out = (-(-span // s) if ceil_mode else span // s) + 1
+    if ceil_mode and (out - 1) * s >= n + p:
+        out -= 1
+    return out
+
+
+def _conv_geometry(h: int, w: int, kernel_size, stride, padding, dilation, caller: str, ceil_mode=None, dilated: bool = True):
     """A convolution of an ``h`` x ``w`` image, its arguments ints or pairs -> the pairs ``(kh, kw), (sh, sw), (ph, pw), (dh, dw)``
-    and the output size ``(ho, wo)``; ValueError, in ``caller``'s name, for arguments that describe no convolution of it."""
-    (kh, kw), (sh, sw) = _pair(kernel_size, "kernel_size", caller), _pair(stride, "stride", caller)
+    and the output size ``(ho, wo)``; ValueError, in ``caller``'s name, for arguments that describe no convolution of it.
+    With a ``ceil_mode`` it is one of torch's pools: ``stride=None`` means the kernel size, the padding is at most half of it,
+    the output size is ``_pool_out_size``'s; ``dilated=False``: a pool without the argument (``dilation=1``), for the messages."""
+    pool = ceil_mode is not None
+    (kh, kw), (sh, sw) = _pair(kernel_size, "kernel_size", caller), _pair(kernel_size if pool and stride is None else stride, "stride", caller)
     (ph, pw), (dh, dw) = _pair(padding, "padding", caller), _pair(dilation, "dilation", caller)
     if min(kh, kw, sh, sw, dh, dw) < 1 or min(ph, pw) < 0:
-        raise ValueError(f"{caller}: kernel_size, stride and dilation must be at least 1 and padding at least 0")
-    ho, wo = _conv_out_size(h, kh, sh, ph, dh), _conv_out_size(w, kw, sw, pw, dw)
+        raise ValueError(f"{caller}: kernel_size{', stride and dilation' if dilated else ' and stride'} must be at least 1 and padding at least 0")
+    if pool and (ph > kh // 2 or pw > kw // 2):
+        raise ValueError(f"{caller}: padding {ph}x{pw} is larger than half the {kh}x{kw} kernel")
+    ho, wo = _pool_out_size(h, kh, sh, ph, dh, bool(ceil_mode)), _pool_out_size(w, kw, sw, pw, dw, bool(ceil_mode))
     if ho <= 0 or wo <= 0:
-        raise ValueError(f"{caller}: a {kh}x{kw} kernel (dilation {dh}x{dw}) does not fit the padded {h}x{w} image")
+        raise ValueError(f"{caller}: a {kh}x{kw} kernel{f' (dilation {dh}x{dw})' if dilated else ''} does not fit the padded {h}x{w} image")
     return (kh, kw), (sh, sw), (ph, pw), (dh, dw), (ho, wo)
 
 
@@ -631,17 +676,12 @@ def codes_im2col(codes_nhwc, kernel_size, stride=1, padding=0, dilation=1, pad_c
     outside the image hold ``pad_code`` (the activation's zero point: such a tap then adds nothing to the integer
     consumer's sum).  GPU tensors run mctq_codes_im2col_nhwc (C % 16 == 0, kh * kw * C <= 32768); CPU tensors the same
     gather with torch ops, byte for byte."""
-    if not isinstance(codes_nhwc, torch.Tensor) or codes_nhwc.dim() != 4:
-        raise ValueError("codes_im2col takes [N, H, W, C] tensors")
-    if codes_nhwc.dtype not in (torch.int8, torch.uint8):
-        raise NotImplementedError(f"codes_im2col: int8 / uint8 codes only, got {codes_nhwc.dtype}")
+    _nhwc_codes(codes_nhwc, "codes_im2col")
     pad_code = int(pad_code)
-    lo, hi = (0, 255) if codes_nhwc.dtype == torch.uint8 else (-128, 127)
-    if not lo <= pad_code <= hi:
-        raise ValueError(f"codes_im2col: pad_code {pad_code} is no {codes_nhwc.dtype} code")
+    _check_form("codes_im2col", codes_nhwc.dtype, pad_code, zp_words="pad_code {}")
     b, h, w, c = codes_nhwc.shape
     (kh, kw), (sh, sw), (ph, pw), (dh, dw), (ho, wo) = _conv_geometry(h, w, kernel_size, stride, padding, dilation, "codes_im2col")
-    x = codes_nhwc if codes_nhwc.is_contiguous() else codes_nhwc.contiguous()
+    x = _contiguous(codes_nhwc)
     if x.is_cuda:
         y = torch.empty((b * ho * wo, kh * kw * c), dtype=x.dtype, device=x.device)
         _gpu_call("mctq_codes_im2col_nhwc", x, x.data_ptr(), y.data_ptr(), b, h, w, c, kh, kw, sh, sw, ph, pw, dh, dw, pad_code)
@@ -653,16 +693,6 @@ def codes_im2col(codes_nhwc, kernel_size, stride=1, padding=0, dilation=1, pad_c
     return taps.reshape(b * ho * wo, kh * kw * c)
 
 
-def _pool_out_size(n: int, k: int, s: int, p: int, d: int, ceil_mode: bool) -> int:
-    """Outputs along one axis of ``torch.nn.MaxPool2d``: as ``_conv_out_size``, the division rounded up with ``ceil_mode``, less
-    the last window where it would start beyond the image plus its left padding."""
-    span = n + 2 * p - d * (k - 1) - 1
-    out = (-(-span // s) if ceil_mode else span // s) + 1
-    if ceil_mode and (out - 1) * s >= n + p:
-        out -= 1
-    return out
-
-
 def codes_maxpool(codes_nhwc, kernel_size, stride=None, padding=0, dilation=1, ceil_mode: bool = False):
     """``torch.nn.MaxPool2d`` on activation codes: int8 / uint8 codes [B, H, W, C] (what ``fq_codes_nhwc`` returns) -> contiguous
     [B, Ho, Wo, C] of the same type; ``stride=None`` means ``kernel_size``, padded taps are ignored (they stand for -inf, not for
@@ -670,22 +700,11 @@ def codes_maxpool(codes_nhwc, kernel_size, stride=None, padding=0, dilation=1, c
     ``dequantize_codes(codes_maxpool(c), s, z) == F.max_pool2d(dequantize_codes(c, s, z))`` bit for bit (NCHW views of both).
     GPU tensors run mctq_codes_maxpool_nhwc (C % 16 == 0), which is given the output extent allocated here and refuses one
     that is not its own; CPU tensors run ``F.max_pool2d`` on the codes themselves."""
-    if not isinstance(codes_nhwc, torch.Tensor) or codes_nhwc.dim() != 4:
-        raise ValueError("codes_maxpool takes [N, H, W, C] tensors")
-    if codes_nhwc.dtype not in (torch.int8, torch.uint8):
-        raise NotImplementedError(f"codes_maxpool: int8 / uint8 codes only, got {codes_nhwc.dtype}")
+    _nhwc_codes(codes_nhwc, "codes_maxpool")
     b, h, w, c = codes_nhwc.shape
-    (kh, kw), (sh, sw) = _pair(kernel_size, "kernel_size", "codes_maxpool"), _pair(kernel_size if stride is None else stride, "stride", "codes_maxpool")
-    (ph, pw), (dh, dw) = _pair(padding, "padding", "codes_maxpool"), _pair(dilation, "dilation", "codes_maxpool")
-    if min(kh, kw, sh, sw, dh, dw) < 1 or min(ph, pw) < 0:
-        raise ValueError("codes_maxpool: kernel_size, stride and dilation must be at least 1 and padding at least 0")
-    if ph > kh // 2 or pw > kw // 2:
-        raise ValueError(f"codes_maxpool: padding {ph}x{pw} is larger than half the {kh}x{kw} kernel")
     ceil_mode = bool(ceil_mode)
-    ho, wo = _pool_out_size(h, kh, sh, ph, dh, ceil_mode), _pool_out_size(w, kw, sw, pw, dw, ceil_mode)
-    if ho <= 0 or wo <= 0:
-        raise ValueError(f"codes_maxpool: a {kh}x{kw} kernel (dilation {dh}x{dw}) does not fit the padded {h}x{w} image")
-    x = codes_nhwc if codes_nhwc.is_contiguous() else codes_nhwc.contiguous()
+    (kh, kw), (sh, sw), (ph, pw), (dh, dw), (ho, wo) = _conv_geometry(h, w, kernel_size, stride, padding, dilation, "codes_maxpool", ceil_mode)
+    x = _contiguous(codes_nhwc)
     if x.is_cuda:
         if c % 16:
             raise NotImplementedError(f"mctq_codes_maxpool_nhwc needs C % 16 == 0, got C={c}")
@@ -722,35 +741,19 @@ def codes_avgpool(codes_nhwc, in_form, out_form, kernel_size, stride=None, paddi
     tap, 1 written per output element), which is given the output extent allocated here and refuses one that is not its own;
     anything else on the GPU, and every CPU tensor, evaluates the expression above with torch integer and float32 ops, which the
     kernel matches byte for byte."""
-    if not isinstance(codes_nhwc, torch.Tensor) or codes_nhwc.dim() != 4:
-        raise ValueError("codes_avgpool takes [N, H, W, C] tensors")
-    if codes_nhwc.dtype not in (torch.int8, torch.uint8):
-        raise NotImplementedError(f"codes_avgpool: int8 / uint8 codes only, got {codes_nhwc.dtype}")
+    _nhwc_codes(codes_nhwc, "codes_avgpool")
     a_scale, a_zp = float(in_form[0]), int(in_form[1])
-    o_scale, o_zp, qmin, qmax = float(out_form[0]), int(out_form[1]), int(out_form[2]), int(out_form[3])
-    tdt, ocode = _code_dtype(qmin, qmax)
-    lo, hi = (0, 255) if codes_nhwc.dtype == torch.uint8 else (-128, 127)
-    if not lo <= a_zp <= hi:
-        raise ValueError(f"codes_avgpool: the zero point {a_zp} is no {codes_nhwc.dtype} code")
-    if not 0.0 < a_scale < float("inf") or not 0.0 < o_scale < float("inf"):
-        raise ValueError("codes_avgpool: the scales must be finite and positive")
+    o_scale, o_zp, qmin, qmax, tdt, ocode = _out_form(out_form)
+    _check_form("codes_avgpool", codes_nhwc.dtype, a_zp, (a_scale, o_scale))
     if divisor_override is not None and (not isinstance(divisor_override, int) or isinstance(divisor_override, bool)
                                          or divisor_override < 1):
         raise ValueError(f"codes_avgpool: divisor_override must be a positive int or None, got {divisor_override!r}")
     b, h, w, c = codes_nhwc.shape
     if kernel_size is None:
         kernel_size = (h, w)
-    (kh, kw), (sh, sw) = _pair(kernel_size, "kernel_size", "codes_avgpool"), _pair(kernel_size if stride is None else stride, "stride", "codes_avgpool")
-    ph, pw = _pair(padding, "padding", "codes_avgpool")
-    if min(kh, kw, sh, sw) < 1 or min(ph, pw) < 0:
-        raise ValueError("codes_avgpool: kernel_size and stride must be at least 1 and padding at least 0")
-    if ph > kh // 2 or pw > kw // 2:
-        raise ValueError(f"codes_avgpool: padding {ph}x{pw} is larger than half the {kh}x{kw} kernel")
     ceil_mode, count_include_pad = bool(ceil_mode), bool(count_include_pad)
-    ho, wo = _pool_out_size(h, kh, sh, ph, 1, ceil_mode), _pool_out_size(w, kw, sw, pw, 1, ceil_mode)
-    if ho <= 0 or wo <= 0:
-        raise ValueError(f"codes_avgpool: a {kh}x{kw} kernel does not fit the padded {h}x{w} image")
-    x = codes_nhwc if codes_nhwc.is_contiguous() else codes_nhwc.contiguous()
+    (kh, kw), (sh, sw), (ph, pw), _, (ho, wo) = _conv_geometry(h, w, kernel_size, stride, padding, 1, "codes_avgpool", ceil_mode, dilated=False)
+    x = _contiguous(codes_nhwc)
     if x.is_cuda and c % 16 == 0 and kh * kw <= _AVGPOOL_MAX_TAPS:
         y = torch.empty((b, ho, wo, c), dtype=tdt, device=x.device)
         _gpu_call("mctq_codes_avgpool_nhwc", x, x.data_ptr(), y.data_ptr(), _code_of(x), a_zp, a_scale, b, h, w, c, kh, kw, sh, sw,
@@ -801,28 +804,22 @@ def codes_concat(operands, out_form):
     operands = [(c, float(s), int(z)) for c, s, z in operands]
     if not operands:
         raise ValueError("codes_concat needs at least one operand")
-    o_scale, o_zp, qmin, qmax = float(out_form[0]), int(out_form[1]), int(out_form[2]), int(out_form[3])
-    tdt, ocode = _code_dtype(qmin, qmax)
+    o_scale, o_zp, qmin, qmax, tdt, ocode = _out_form(out_form)
     first = operands[0][0]
     for c, s, z in operands:
-        if not isinstance(c, torch.Tensor) or c.dtype not in (torch.int8, torch.uint8) or c.dim() < 1:
+        if not _is_codes(c) or c.dim() < 1:
             raise TypeError("codes_concat takes int8 / uint8 codes [.., C]")
         if c.device != first.device or c.shape[:-1] != first.shape[:-1]:
             raise RuntimeError(f"codes_concat: operands must share the device and the leading shape, got {tuple(c.shape)} on "
                                f"{c.device} next to {tuple(first.shape)} on {first.device}")
-        lo, hi = (0, 255) if c.dtype == torch.uint8 else (-128, 127)
-        if not lo <= z <= hi:
-            raise ValueError(f"codes_concat: the zero point {z} is no {c.dtype} code")
-        if not 0.0 < s < float("inf"):
-            raise ValueError("codes_concat: an operand's scale must be finite and positive")
-    if not 0.0 < o_scale < float("inf"):
-        raise ValueError("codes_concat: the output's scale must be finite and positive")
+        _check_form("codes_concat", c.dtype, z, s, scale_words="an operand's scale")
+    _check_form("codes_concat", None, scale=o_scale, scale_words="the output's scale")
     lead, total = tuple(first.shape[:-1]), sum(c.shape[-1] for c, _, _ in operands)
     o_lo, o_hi = (0, 255) if tdt == torch.uint8 else (-128, 127)
     if (first.is_cuda and len(operands) <= _CONCAT_MAX and all(c.shape[-1] > 0 and c.shape[-1] % 16 == 0 for c, _, _ in operands)
             and o_lo <= o_zp <= o_hi):
         pixels = math.prod(lead)
-        keep = [c if c.is_contiguous() else c.contiguous() for c, _, _ in operands]     # named: they must outlive the launch
+        keep = [_contiguous(c) for c, _, _ in operands]                                 # named: they must outlive the launch
         out = torch.empty(lead + (total,), dtype=tdt, device=first.device)
         items = (native.ConcatItem * len(keep))()
         for it, c, (_, s, z) in zip(items, keep, operands):
@@ -855,12 +852,11 @@ def codes_mul(a, g, out_form, gate_form=None):
     matches byte for byte."""
     (ac, a_scale, a_zp), (gc, g_scale, g_zp) = a, g
     a_scale, a_zp, g_scale, g_zp = float(a_scale), int(a_zp), float(g_scale), int(g_zp)
-    o_scale, o_zp, qmin, qmax = float(out_form[0]), int(out_form[1]), int(out_form[2]), int(out_form[3])
-    tdt, ocode = _code_dtype(qmin, qmax)
-    if not isinstance(ac, torch.Tensor) or ac.dtype not in (torch.int8, torch.uint8) or ac.dim() < 1:
+    o_scale, o_zp, qmin, qmax, tdt, ocode = _out_form(out_form)
+    if not _is_codes(ac) or ac.dim() < 1:
         raise TypeError("codes_mul takes int8 / uint8 codes [.., C] as its first operand")
     if gate_form is None:
-        if not isinstance(gc, torch.Tensor) or gc.dtype not in (torch.int8, torch.uint8) or gc.dim() < 1:
+        if not _is_codes(gc) or gc.dim() < 1:
             raise TypeError("codes_mul takes int8 / uint8 codes [.., C] as its second operand, or float32 values with gate_form")
         g_tdt, g_qmin, g_qmax = gc.dtype, 0, 0
     else:
@@ -871,11 +867,8 @@ def codes_mul(a, g, out_form, gate_form=None):
     if gc.device != ac.device:
         raise RuntimeError(f"codes_mul: operands must share the device, got {ac.device} and {gc.device}")
     for dt, z, what in ((ac.dtype, a_zp, "first"), (g_tdt, g_zp, "second"), (tdt, o_zp, "output")):
-        lo, hi = (0, 255) if dt == torch.uint8 else (-128, 127)
-        if not lo <= z <= hi:
-            raise ValueError(f"codes_mul: the zero point {z} of the {what} form is no {dt} code")
-    if not all(0.0 < s < float("inf") for s in (a_scale, g_scale, o_scale)):
-        raise ValueError("codes_mul: the scales must be finite and positive")
+        _check_form("codes_mul", dt, z, zp_words=f"the zero point {{}} of the {what} form")
+    _check_form("codes_mul", None, scale=(a_scale, g_scale, o_scale))
 
     def gate_of(big, small):
         """small is [B, 1, .., 1, C] next to big [B, .., C]: the pixels per gate row, else None."""
@@ -896,8 +889,7 @@ def codes_mul(a, g, out_form, gate_form=None):
         out = torch.empty(ac.shape, dtype=tdt, device=ac.device)
         if out.numel() == 0:
             return out
-        ak = ac if ac.is_contiguous() else ac.contiguous()      # named: they must outlive the launch
-        gk = gc if gc.is_contiguous() else gc.contiguous()
+        ak, gk = _contiguous(ac), _contiguous(gc)               # named: they must outlive the launch
         _gpu_call("mctq_codes_mul_nhwc", ak, ak.data_ptr(), _code_of(ak), a_scale, a_zp, gk.data_ptr(),
                   native.CODE_U8 if g_tdt == torch.uint8 else native.CODE_I8, g_scale, g_zp, int(gate_form is not None), g_qmin,
                   g_qmax, n, out.data_ptr(), ocode, ak.numel() // ak.shape[-1], ak.shape[-1], o_scale, o_zp, qmin, qmax)

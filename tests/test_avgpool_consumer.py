@@ -296,6 +296,20 @@ def test_codes_avgpool_argument_validation_needs_no_gpu():
     for name, message in (("scale", b"scale must be finite and positive"), ("ys", b"y_scale must be finite and positive")):
         for bad in (0.0, -1.0, float("inf"), float("nan")):
             refused(message, **{name: bad})
+    # wrong in two ways: the window's sizes, the taps, the divisor, the channels, the input's form, the output's, then the fit
+    refused(b"padding larger than half the kernel size", ph=2, kw=30000)
+    refused(b"more than 65536 taps in a window", kh=257, kw=256, ph=0, pw=0, div=-1)
+    refused(b"negative divisor_override", div=-1, C=24)
+    refused(b"channels must be a multiple of 16", C=24, dt=77)
+    refused(b"bad code_dtype", dt=77, zp=256)
+    refused(b"zero_point is no code of the input's type", zp=256, scale=0.0)
+    refused(b"scale must be finite and positive", scale=0.0, ys=0.0)
+    refused(b"y_scale must be finite and positive", ys=0.0, ydt=-1)
+    refused(b"bad y_code_dtype", ydt=-1, kw=9)
+    refused(b"quant_min > quant_max", qmin=9, qmax=8, H=2 ** 31)
+    refused(b"padded image extent exceeds 2^31 - 1", H=2 ** 31 - 4, W=0)              # H + 2 + 3 with the kernel; W: no fit
+    refused(b"the kernel does not fit the padded image (Ho <= 0 or Wo <= 0)", kw=9, pw=1, wo=7)
+    refused(b"out_height / out_width are not the pooled extent", H=0, kh=2, ph=1, sh=1, ho=2, x=None)
     refused(b"quant_min > quant_max", qmin=9, qmax=8)
     refused(b"clamp domain does not fit the code type", qmin=-1)
     refused(b"clamp domain does not fit the code type", ydt=I8, qmin=0, qmax=128)

@@ -550,6 +550,15 @@ def check_refusals(lib, native, P=4096):
     for bad in (0.0, -0.5, float("inf"), float("nan")):
         refused(b"an operand's scale must be finite and positive", items=(one, (Q, 16, U8, 0, bad)))
         refused(b"scale must be finite and positive", scale=bad)
+    # wrong in two ways: the output's scale, its code type, its clamp domain, its zero point, then the operands in their order,
+    # of each the code type, the zero point, the scale
+    refused(b"scale must be finite and positive", scale=0.0, dt=77)
+    refused(b"bad out_code_dtype", dt=77, qmin=9, qmax=8)
+    refused(b"quant_min > quant_max", qmin=9, qmax=8, zp=256)
+    refused(b"zero_point is no code of the output's type", zp=256, items=((Q, 16, 77, 0, 0.1),))
+    refused(b"an operand's zero_point is no code of its type", items=((Q, 16, U8, 256, 0.0),))
+    refused(b"an operand's scale must be finite and positive", items=((Q, 16, U8, 0, 0.0), (Q, 16, 77, 0, 0.1)))
+    refused(b"an operand's scale must be finite and positive", items=((Q, 24, U8, 0, 0.0),))
     refused(b"quant_min > quant_max", qmin=9, qmax=8)
     refused(b"clamp domain does not fit the code type", qmax=256)
     refused(b"clamp domain does not fit the code type", dt=I8, qmin=-129, qmax=127)

@@ -438,6 +438,15 @@ def test_im2col_argument_validation_needs_no_gpu():
     refused(b"too many output rows for one launch", B=2 ** 31, kh=1, kw=1, ph=0, pw=0, H=1, W=1)
     refused(b"too many output rows for one launch", B=2 ** 62, H=2 ** 20, W=2 ** 20, kh=1, kw=1, ph=0, pw=0)
     refused(b"padded image extent exceeds 2^31 - 1", H=2 ** 31)
+    assert call(H=2 ** 31 - 3, B=0) == 0                               # the padded extent alone counts, not the kernel
+    # wrong in two ways: the window's sizes, the pad code, the channels, the limit, the padded extent, the fit, the rows
+    refused(b"negative padding", ph=-1, pad=256)
+    refused(b"pad_code outside [-128, 255]", pad=256, C=24)
+    refused(b"channels must be a multiple of 16", C=24, kh=2 ** 31 - 1)
+    refused(b"kh * kw * channels > 32768: outside the consumer's limit", C=4096, H=2 ** 31)
+    refused(b"padded image extent exceeds 2^31 - 1", H=2 ** 31, kw=16)
+    refused(b"the kernel does not fit the padded image (Ho <= 0 or Wo <= 0)", kh=8, B=2 ** 62)
+    refused(b"too many output rows for one launch", B=2 ** 31, kh=1, kw=1, ph=0, pw=0, H=1, W=1, x=None)
     assert call(B=0) == 0 and call(B=0, x=None, y=None) == 0          # no images: no launch, no pointer is looked at
     assert call(C=0) == 0                                               # no channels: nothing to write
     assert call(pad=-128, B=0) == 0 and call(pad=255, B=0) == 0

@@ -523,6 +523,16 @@ def test_qconv_dw_argument_validation_needs_no_gpu():
     refused(b"clamp domain does not fit the code type", ydt=U8, qmax=256)
     refused(b"clamp domain does not fit the code type", ydt=I8, qmin=-129, qmax=127)
     refused(b"clamp domain does not fit the code type", ydt=I8, qmin=-128, qmax=128)
+    # wrong in two ways: the window's sizes, the channels, the tap limit, the activations' form, the output's, then the fit
+    refused(b"negative padding", ph=-1, C=24)
+    refused(b"channels must be a multiple of 16", C=24, kh=17, kw=16)
+    refused(b"kh * kw > 256: outside the depthwise consumer's limit", kh=17, kw=16, adt=77)
+    refused(b"bad a_code_dtype", adt=77, za=256)
+    refused(b"a_zero_point is no code of a_code_dtype", za=256, ydt=9)
+    refused(b"bad y_code_dtype", ydt=9, H=2 ** 31)
+    refused(b"padded image extent exceeds 2^31 - 1", H=2 ** 31, kw=16)
+    refused(b"the kernel does not fit the padded image (Ho <= 0 or Wo <= 0)", kh=8, a=None)
+    assert call(H=2 ** 31 - 3, B=0) == 0                                                          # the padded extent alone counts, not the kernel
     refused(b"padded image extent exceeds 2^31 - 1", H=2 ** 31)
     refused(b"padded image extent exceeds 2^31 - 1", W=2 ** 31 - 2)                               # + 2 of padding
     refused(b"the kernel does not fit the padded image (Ho <= 0 or Wo <= 0)", kh=8)              # 8 > 5 + 2

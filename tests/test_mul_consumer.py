@@ -757,6 +757,13 @@ def check_refusals(lib, native, P=4096):
         refused(b"a_scale must be finite and positive", a_scale=bad)
         refused(b"g_scale must be finite and positive", g_scale=bad)
         refused(b"scale must be finite and positive", scale=bad)
+    # wrong in two ways: every code type is looked at before any zero point, every zero point before any scale, a before g before out
+    refused(b"bad out_code_dtype", dt=77, a_zp=256)
+    refused(b"bad a_code_dtype", a_dt=77, g_dt=77)
+    refused(b"zero_point is no code of the output's type", zp=256, a_scale=0.0)
+    refused(b"a_zero_point is no code of a's type", a_zp=256, g_zp=128)
+    refused(b"a_scale must be finite and positive", a_scale=0.0, g_scale=0.0, scale=0.0)
+    refused(b"scale must be finite and positive", scale=0.0, qmin=9, qmax=8)
     refused(b"quant_min > quant_max", qmin=9, qmax=8)
     refused(b"clamp domain does not fit the code type", qmax=256)
     refused(b"clamp domain does not fit the code type", dt=I8, qmin=-129, qmax=127)

@@ -514,7 +514,15 @@ def test_codes_maxpool_argument_validation_needs_no_gpu():
     refused(b"more than 2^32 - 1 16-channel chunks of output in one launch", B=2 ** 30, C=64, kh=1, kw=1, sh=1, sw=1, ph=0, pw=0,
             H=1, W=1, ho=1, wo=1)
     refused(b"padded image extent exceeds 2^31 - 1", H=2 ** 31, ho=2 ** 30)
+    refused(b"padded image extent exceeds 2^31 - 1", H=2 ** 31 - 4, W=0)              # H + 2 + 3 with the kernel's span; W: no fit
     refused(b"an image of a non-empty batch needs at least one pixel", H=0, kh=2, ph=1, sh=1, ho=1)
+    # wrong in two ways: the window's sizes, the half-kernel rule, the channels, the code type, the fit, the extent, the pixels
+    refused(b"negative padding", ph=-1, pw=2)
+    refused(b"padding larger than half the kernel size", pw=2, C=24)
+    refused(b"channels must be a multiple of 16", C=24, dt=77)
+    refused(b"bad code_dtype", dt=77, kw=3, dw=4)
+    refused(b"the kernel does not fit the padded image (Ho <= 0 or Wo <= 0)", kw=3, dw=4, wo=7)
+    refused(b"out_height / out_width are not the pooled extent", H=0, kh=2, ph=1, sh=1, ho=2, x=None)
     assert call(B=0) == 0 and call(B=0, x=None, y=None) == 0          # no images: no launch, no pointer is looked at
     assert call(C=0) == 0                                               # no channels: nothing to write
     assert call(B=0, dt=I8) == 0

@@ -481,6 +481,11 @@ def test_qlinear_i8_res_argument_validation_needs_no_gpu():
         refused(b"r_zero_point is no code of the residual's type", rdt=rdt, rz=rz)
     for rs in (0.0, -0.5, float("inf"), float("nan")):
         refused(b"r_scale must be finite and positive", rs=rs)
+    # wrong in two ways: the output's form, then the residual's code type, its zero point, its scale, then the overlap
+    refused(b"bad y_code_dtype", ydt=9, r=None)
+    refused(b"bad r_code_dtype", rdt=77, rz=256)
+    refused(b"r_zero_point is no code of the residual's type", rz=256, rs=0.0)
+    refused(b"r_scale must be finite and positive", rs=0.0, r=P)
     for off in (1, 2, 3):
         refused(b"a float32 residual must be 4-byte aligned", rdt=-1, r=R + off)
     # y [4][8] overlapping the residual: the byte ranges, each in its own element size

@@ -550,6 +550,10 @@ def test_fq_join_rc_argument_validation_needs_no_gpu():
         refused(b"r_zero_point is no code of the residual's type", rdt=rdt, rz=rz)
     for rs in (0.0, -0.5, float("inf"), float("nan")):
         refused(b"r_scale must be finite and positive", rs=rs)
+    # wrong in two ways: the residual's code type, its zero point, its scale, then what mctq_fq_join_f32 looks at
+    refused(b"bad r_code_dtype", rdt=77, rz=256)
+    refused(b"r_zero_point is no code of the residual's type", rz=128, rs=0.0)
+    refused(b"r_scale must be finite and positive", rs=0.0, x=None)
     # ... and everything mctq_fq_join_f32 refuses
     refused(b"x is NULL", x=None)
     refused(b"neither y nor codes is given", y=None, codes=None)
