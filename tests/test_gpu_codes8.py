@@ -29,7 +29,8 @@ U = 4                                                        # AffineCodesOp::kF
 
 # (scale, zero_point, qmin, qmax): the zero point at either end of either domain, domains narrower than the type, a step with an
 # inexact reciprocal, one so large that only the saturating ends of float32 / bfloat16 leave the zero point and one so small
-# that every normal float32 saturates (both outside [2^-100, 2^100], where fetch_lane takes the IEEE division)
+# that every normal float32 saturates (3e-33 < 2^-100: fetch_lane takes the IEEE division; 1e30 is just below 2^100 = 1.27e30,
+# among the largest divisors recip_exact takes)
 PARAMS = ((0.25, -128, -128, 127), (0.2, 127, -128, 127), (0.3, 0, 0, 255), (0.0123, 255, 0, 255), (0.05, 3, -8, 7),
           (0.11, 7, 0, 15), (0.017, 100, 3, 200), (1.7 / 127, 0, -128, 127), (1e30, -1, -128, 127), (3e-33, 100, 0, 255))
 SIGNED = tuple(p for p in PARAMS if p[2] < 0)
@@ -111,10 +112,13 @@ def _assert_codes(got, want_idx, x_np, qmin, what):
 
 class _Frame:
     """One output byte per element in the middle of a 0xA5 frame, ``yoff`` bytes past a 16-byte boundary; the bytes inside start
-    as the complement of ``want_idx`` (``fill`` instead when there is nothing to expect)."""
+    as the complement of ``want_idx`` (``fill`` instead when there is nothing to expect).  Outputs of wider elements
+    (tests/test_gpu_affine_routes.py) give their starting bytes as ``inside``."""
 
-    def __init__(self, want_idx=None, nbytes=None, fill=0x3C, yoff=0):
-        inside = np.full(nbytes, fill, np.uint8) if want_idx is None else ~_bytes(want_idx)
+    def __init__(self, want_idx=None, nbytes=None, fill=0x3C, yoff=0, inside=None):
+        if inside is None:
+            inside = np.full(nbytes, fill, np.uint8) if want_idx is None else ~_bytes(want_idx)
+        inside = np.ascontiguousarray(inside, dtype=np.uint8).reshape(-1)
         self.inside = inside
         self.nb = inside.size
         self.at = GUARD + yoff
