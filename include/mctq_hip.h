@@ -84,6 +84,9 @@ extern "C" {
 /* v10 (additive, the version number stays): + mctq_qlinear_i8_act and mctq_qconv_dw_i8_act, the integer product and the depthwise
  * convolution with a Hardswish / Hardsigmoid in front of the codes they emit (MobileNetV3's layers and the SE gate stay on codes); no
  * existing signature or result changed. */
+/* v10 (additive, the version number stays): + mctq_codes_upsample_nhwc, nearest upsampling (torch.nn.Upsample / F.interpolate,
+ * modes "nearest" and "nearest-exact") on NHWC activation codes in the form of the holder behind it (decoder stages, necks and
+ * segmentation heads stay on codes), + tuning key "upsample_form"; no existing signature or result changed. */
 #define MCTQ_ABI_VERSION 10
 #define MCTQ_E_ARG (-10001)
 
@@ -673,6 +676,43 @@ int mctq_codes_avgpool_nhwc(const void* codes, void* pooled, int32_t code_dtype,
                             int32_t y_zero_point, int32_t y_quant_min, int32_t y_quant_max, void* stream);
 
 /*
+ * Nearest resampling on activation codes (extension; the reference runs ATen's nearest upsample on the float32 output of a
+ * holder and the holder behind it on the result): codes [batch][height][width][channels] (NHWC; int8 -- MCTQ_CODE_I8 -- or
+ * uint8, MCTQ_CODE_U8) of the form (in_scale, in_zero_point) -> out [batch][out_height][out_width][channels] in the form
+ * (out_code_dtype, scale, zero_point, quant_min, quant_max), DEVICE pointers, 16-byte aligned.  The index map is separable and
+ * given in one of two ways: src_rows / src_cols, DEVICE int32 tables of out_height / out_width entries (4-byte aligned) with
+ * factor_h == factor_w == 0 -- any geometry, downsampling included -- or factor_h, factor_w >= 1 with both tables NULL,
+ * out_height == factor_h * height, out_width == factor_w * width and src = dst / factor.  Per output element
+ *     v   = fma(float(code[b][src_rows[ho]][src_cols[wo]][c] - in_zero_point), in_scale, +0)     the holder's float32 output
+ *     out = clamp(rint(v * (1.0f / scale)) + zero_point, quant_min, quant_max)
+ * -- mctq_codes_concat_nhwc's arithmetic with count == 1, the reciprocal computed on the host; nearest interpolation only
+ * moves data, so this is bit for bit the code the holder behind the float32 upsample gives, for every element.  An input
+ * whose form is the output's is stored as loaded, under mctq_codes_concat_nhwc's conditions and its tuning key "concat_copy".
+ * Two forms with the same bytes: "gather", one lane per 16-channel chunk of an OUTPUT pixel (one 16-byte load through the
+ * map, one 16-byte store; every geometry), and "replicate", for integer factors with factor_h * factor_w <= 16, one lane per
+ * 16-channel chunk of an INPUT pixel (one load, one requantization, factor_h * factor_w 16-byte stores).  The launcher chooses
+ * replicate where it is eligible and factor_h * factor_w >= 2 -- measured on 2 x and 4 x upsamples: 1.77 - 2.25 x faster than gather
+ * at batch 64, equal at the launch floor at batch 1 (profiles/EXPERIMENTS.md); other factors not measured -- and gather elsewhere;
+ * tuning key "upsample_form" forces one.
+ * The launcher cannot see the device tables: the kernel clamps every entry into [0, height - 1] / [0, width - 1] before it
+ * forms an address.  A lane reads only chunks below batch * height * width * channels / 16, entries below out_height /
+ * out_width of the tables, and writes only chunks below batch * out_height * out_width * channels / 16.
+ * MCTQ_E_ARG with a mctq_last_error text, before anything is launched, for: a negative extent; channels % 16 != 0; a bad
+ * code_dtype or out_code_dtype; a zero point that is no code of its type (input and output); a scale that is not finite and
+ * positive (input and output); quant_min > quant_max or a domain outside the output type; tables and factors both given, or
+ * neither; one table without the other; a factor below 1; an image extent above 2^31 - 1; integer factors with out_height !=
+ * factor_h * height or out_width != factor_w * width; a non-empty output from an image without pixels; more than 2^31 - 1
+ * 16-byte chunks of output (split the batch); NULL or misaligned pointers of a non-empty problem; an `out` whose bytes overlap
+ * the codes' or a table's.  batch == 0, channels == 0 or an empty output returns 0 without a launch.  mctq_last_launch names
+ * the launch "codes_upsample", op "<in> -> <out> <form>" with the code types "u8" / "i8" and the form "gather" / "replicate".
+ */
+int mctq_codes_upsample_nhwc(const void* codes, void* out, int32_t code_dtype, int32_t in_zero_point, float in_scale,
+                             int64_t batch, int64_t height, int64_t width, int64_t channels, int64_t out_height,
+                             int64_t out_width, int32_t factor_h, int32_t factor_w, const int32_t* src_rows,
+                             const int32_t* src_cols, int32_t out_code_dtype, float scale, int32_t zero_point,
+                             int32_t quant_min, int32_t quant_max, void* stream);
+
+/*
  * Depthwise convolution on activation codes (groups == channels, channel multiplier 1; extension, the reference has no
  * counterpart): what a wrapped depthwise torch.nn.Conv2d computes on fake-quantized operands, evaluated on the codes.
  *     acc[b][oy][ox][c] = sum over the taps (ky, kx) inside the image of
@@ -954,6 +994,10 @@ int mctq_qconv_dw_i8_act(const void* a_codes, int32_t a_code_dtype, int32_t a_ze
  *                  0 = they run the requantization arithmetic like every other operand (the bytes are the same: the tests' proof)
  *   key "avgpool_form" : mctq_codes_avgpool_nhwc: 0 (default) = the launcher chooses between the lane and the split form, 1 = the lane
  *                  form, 2 = the split form (the bytes are the same: the sums are integers)
+ *   key "upsample_form" : mctq_codes_upsample_nhwc: 0 (default) = the launcher chooses (replicate for integer factors with
+ *                  2 <= factor_h * factor_w <= 16, where it measured 1.8 - 2.3 x faster at batch 64 and equal at batch 1; gather
+ *                  elsewhere), 1 = the gather form, 2 = the replicate form where eligible (integer factors with
+ *                  factor_h * factor_w <= 16; gather elsewhere).  The bytes are the same: every output is one input's code
  * Only variants a default dispatcher can select are instantiated; every value of every key is exercised by the GPU tests.
  * Returns 0, or MCTQ_E_ARG for an unknown key/value.  Numerical results never depend on it.
  */

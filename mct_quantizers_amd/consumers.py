@@ -91,12 +91,19 @@ element of the large tensor; the gate ``[B, C, 1, 1]`` may arrive as codes or as
 kernel codes itself.  With ``shared_holders=True`` and ``avg_pools=True`` the holder in front of an SE block never writes float32.
 Measured / not measured: see the README paragraph and ``profiles/EXPERIMENTS.md``.
 
+A nearest upsample behind a holder stays on codes with ``upsamples=True`` (both rewrites): holder A -> ``nn.Upsample`` /
+``F.interpolate`` ("nearest", "nearest-exact") -> holder B, the low-resolution branch of a decoder stage.  Nearest interpolation only
+moves data, so B's codes are A's codes gathered through the upsample's index map and requantized one by one: ``QuantizedUpsample``
+(``mctq_codes_upsample_nhwc``) does that in one launch, 1 byte read and 1 written per output element, and with ``concats=True``
+A -> upsample -> B -> cat([B, S]) -> C -> conv runs holder to holder on codes.
+Measured / not measured: see the README paragraph and ``profiles/EXPERIMENTS.md``.
+
 The four modules derive from ``IntegerConsumer``, which owns what they share: the checks of the quantizers and of the float32
 weight and bias, the cache of the weight's codes, the step from ``forward``'s input to activation codes, ``from_wrapper`` and
 the ``emit_codes_for`` / ``emit_clamp`` output form.  ``QuantizedLinear`` is the product over ``[O, K]`` rows; ``QuantizedConv1x1``
 and ``QuantizedConv2d`` are that product and derive from it; ``QuantizedDepthwiseConv2d`` is not and derives from
 ``IntegerConsumer`` directly.  "Any integer consumer" in the graph rewrites is ``isinstance(m, IntegerConsumer)``.  The modules
-without weights -- the pools, ``QuantizedConcat``, ``QuantizedMul``, ``QuantizedJoin`` -- derive from ``_OnCodes``;
+without weights -- the pools, ``QuantizedUpsample``, ``QuantizedConcat``, ``QuantizedMul``, ``QuantizedJoin`` -- derive from ``_OnCodes``;
 ``_operand_codes`` is the one step from an operand of ``forward`` to codes, theirs and the consumers' (the join has its own kernel).
 
 CPU tensors run the same integer arithmetic with torch ops (host logic for tests, bit-identical to the kernel).
@@ -864,7 +871,7 @@ def _ints_or_pair(v) -> bool:
 
 
 class _OnCodes(nn.Module):
-    """Base of the modules without weights that read or write activation codes -- the pools, QuantizedConcat, QuantizedMul and
+    """Base of the modules without weights that read or write activation codes -- the pools, QuantizedUpsample, QuantizedConcat, QuantizedMul and
     QuantizedJoin: with the wrappers, the holders and the integer consumers, the leaves of the graph rewrite's tracer."""
 
 
@@ -1031,6 +1038,111 @@ class QuantizedAvgPool2d(_OnCodes):
         return y.reshape(y.shape[0], y.shape[3]) if self.flatten else y.permute(0, 3, 1, 2)
 
 
+_NEAREST_MODES = ("nearest", "nearest-exact")
+_ONE_RAMP_MAX = 1 << 24        # pixels of an image whose indices h * W + w are all float32 integers (QuantizedUpsample.index_maps)
+
+
+class QuantizedUpsample(_OnCodes):
+    """``activation holder A -> nearest upsample -> activation holder B`` on integer codes, for the integer consumers, pools and
+    concatenations behind B: a U-Net stage, a YOLO / PANet neck, a segmentation head.  A's float32 output is
+    ``float(code - zp_a) * scale_a`` bit for bit (``ops.dequantize_codes``), nearest interpolation only moves data and B codes
+    every element by itself, so B's codes are A's codes gathered through the upsample's index map and requantized one by one
+    -- ``ops.codes_upsample`` (``mctq_codes_upsample_nhwc``): 1 byte read and 1 written per output element in one launch, where
+    A writes float32, ATen's upsample reads it and writes ``fh * fw`` times as much, and B reads and writes that again.  Nothing
+    is approximated, whatever the geometry.
+
+    ``upsample``: an ``nn.Upsample`` of mode "nearest" or "nearest-exact" (``size`` or ``scale_factor``, ints, floats or pairs,
+    any ``recompute_scale_factor``; downsampling sizes and factors included) or an ``nn.UpsamplingNearest2d`` -- ``eligible`` says
+    which; ``F.interpolate(x, ...)`` with constant arguments is ``nn.Upsample(...)`` of the same arguments.  ``in_quantizer`` (A's)
+    and ``out_quantizer`` (B's): per-tensor affine activation quantizers of at most 8 bits whose zero points are codes of their
+    type; ``out_quantizer=None``: the output form is the input's (no holder behind, as for a max pool), a pure copy of codes.
+
+    ``forward`` takes A's codes (int8 / uint8 of A's code type, NCHW-shaped and NHWC-stored as the consumers and joins emit them)
+    or a float32 [N, C, H, W] tensor, which it quantizes with A's parameters at the LOW resolution (``ops.fq_codes_nhwc``); it
+    returns B's codes, NCHW-shaped and NHWC-stored.  ``activation_code_params`` is the INPUT form, what a producer in front
+    emits; ``output_code_params`` is what the readers behind agree on (``QuantizedAvgPool2d``'s convention).
+
+    The index maps are not derived from PyTorch's scale rules: for every ``(H, W, device)`` first seen, the module resamples an
+    index ramp -- float32 ``[1, 1, H, W]`` holding ``h * W + w``; a row ramp and a column ramp where ``H * W`` > 2^24 -- through
+    the very call it replaces, on that device, reads ``src_rows = out[:, 0] // W`` and ``src_cols = out[0, :] % W``, checks that
+    the map is separable and caches the device int32 maps and the integer factors, if any.  That is one tiny launch and one host
+    read per new shape: a hipGraph capture needs one warm-up forward per input shape first (``capture_forward``'s warm-up is
+    one).  GPU tensors whose C is no multiple of 16 and CPU tensors take torch ops with the same bytes."""
+
+    def __init__(self, upsample, in_quantizer, out_quantizer=None):
+        super().__init__()
+        if not self.eligible(upsample):
+            raise TypeError("QuantizedUpsample takes torch.nn.Upsample layers of mode 'nearest' or 'nearest-exact' with either a "
+                            "size or a scale_factor, a number or a pair of numbers, and torch.nn.UpsamplingNearest2d layers")
+        self.upsample = upsample
+        self.in_quantizer, self.out_quantizer = in_quantizer, out_quantizer
+        self._a_scale, self._a_zp, self._a_qmin, self._a_qmax = _code_form(in_quantizer)
+        self._out_form = self.activation_code_params() if out_quantizer is None else _code_form(out_quantizer)
+        self._maps = {}                                        # (H, W, device) -> (src_rows, src_cols, factors or None)
+
+    @staticmethod
+    def eligible(upsample) -> bool:
+        if type(upsample) not in (nn.Upsample, nn.UpsamplingNearest2d):
+            return False
+        if upsample.mode not in _NEAREST_MODES or upsample.align_corners is not None:
+            return False
+        if getattr(upsample, "recompute_scale_factor", None) not in (None, True, False):
+            return False
+        size, factor = upsample.size, upsample.scale_factor
+        if (size is None) == (factor is None):
+            return False
+        number = lambda e, kinds: isinstance(e, kinds) and not isinstance(e, bool) and e > 0 and math.isfinite(e)     # noqa: E731
+        kinds = (int,) if factor is None else (int, float)
+        v = size if factor is None else factor
+        return number(v, kinds) or (isinstance(v, (tuple, list)) and len(v) == 2 and all(number(e, kinds) for e in v))
+
+    def activation_code_params(self):
+        """(scale, zero_point, qmin, qmax) of the codes this module READS (holder A's): what ``emit_codes_for`` of the layer in
+        front takes."""
+        return self._a_scale, self._a_zp, self._a_qmin, self._a_qmax
+
+    def output_code_params(self):
+        """(scale, zero_point, qmin, qmax) of the codes ``forward`` returns (holder B's, or A's without one)."""
+        return self._out_form
+
+    def extra_repr(self) -> str:
+        return f"size={self.upsample.size}, scale_factor={self.upsample.scale_factor}, mode={self.upsample.mode}"
+
+    def index_maps(self, height: int, width: int, device):
+        """``(src_rows, src_cols, factors)`` of an ``height`` x ``width`` input on ``device``: int32 tensors of lengths Ho / Wo on
+        that device, ``upsample(x) == x[:, :, src_rows][:, :, :, src_cols]``, and ``(fh, fw)`` where both maps are those of integer
+        factors, else None.  Resampled through the module itself and cached."""
+        device = torch.device(device)
+        key = (int(height), int(width), str(device))
+        hit = self._maps.get(key)
+        if hit is not None:
+            return hit
+        h, w = key[0], key[1]
+        with torch.no_grad():
+            ys = torch.arange(h, dtype=torch.float32, device=device).reshape(1, 1, h, 1)
+            xs = torch.arange(w, dtype=torch.float32, device=device).reshape(1, 1, 1, w)
+            if h * w <= _ONE_RAMP_MAX:                         # every index is a float32 integer
+                src = self.upsample(ys * w + xs)[0, 0].to(torch.int64)
+            else:
+                src = self.upsample(ys.expand(1, 1, h, w))[0, 0].to(torch.int64) * w + self.upsample(xs.expand(1, 1, h, w))[0, 0].to(torch.int64)
+            rows, cols = src[:, 0] // w, src[0, :] % w
+            if not torch.equal(src, rows[:, None] * w + cols[None, :]):
+                raise RuntimeError("the upsample's index map is not separable into rows and columns")
+        fh, fw = ops.integer_factor(rows.cpu(), h), ops.integer_factor(cols.cpu(), w)
+        if len(self._maps) > 64:
+            self._maps.clear()
+        hit = self._maps[key] = (rows.to(torch.int32), cols.to(torch.int32), (fh, fw) if fh and fw else None)
+        return hit
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if x.dim() != 4:
+            raise RuntimeError(f"expected [N, C, H, W], got {tuple(x.shape)}")
+        codes = _operand_codes(x, self.activation_code_params(), "QuantizedUpsample", "this upsample's input quantizer")
+        rows, cols, factors = self.index_maps(codes.shape[1], codes.shape[2], codes.device)
+        y = ops.codes_upsample(codes, (self._a_scale, self._a_zp), self._out_form, rows, cols, factors)
+        return y.permute(0, 3, 1, 2)
+
+
 class _OperandsOnCodes(_OnCodes):
     """What QuantizedConcat and QuantizedMul share: several operands, each read as the codes of its own holder's quantizer,
     and one output holder's quantizer, all per-tensor affine of at most 8 bits (``_code_form``)."""
@@ -1179,7 +1291,7 @@ def _consumer_for(wrapper, activation_quantizer, uniform_weights=False, convolut
 
 
 # what reads the activation codes of the module in front as they are
-_CODE_READERS = (IntegerConsumer, QuantizedMaxPool2d, QuantizedAvgPool2d)
+_CODE_READERS = (IntegerConsumer, QuantizedMaxPool2d, QuantizedAvgPool2d, QuantizedUpsample)
 
 
 class _FusedAway(nn.Identity):
@@ -1280,11 +1392,17 @@ def _pool_of(node, mods):
 
 class _PoolPlan(NamedTuple):
     """A pool that can run on codes: the ``module`` that replaces it, the ``suffix`` of its node's name, ``taken`` [(user, its
-    consumer)], the wrapped layers that read its output, and ``gone``, the nodes between the pool and those that leave the graph."""
+    consumer)], the wrapped layers that read its output, and ``gone``, the nodes between the pool and those that leave the graph.
+    An upsample's plan (``_upsample_plan``) also has ``name``, its node's whole name where that is not the pool node's own with the
+    suffix, ``pooled`` [(max pool node, its plan)], the max pools that read its codes, and ``readers``, the QuantizedConcat /
+    QuantizedMul nodes that do."""
     module: nn.Module
     suffix: str
     taken: list
     gone: list
+    name: Optional[str] = None
+    pooled: tuple = ()
+    readers: tuple = ()
 
 
 def _pool_plan(node, mods, quantizer, consumer_for):
@@ -1304,14 +1422,20 @@ def _pool_plan(node, mods, quantizer, consumer_for):
 def _install_pool(gm, mods, node, plan, source) -> int:
     """Makes ``node``, the pool's call, a call of ``plan``'s module on ``source`` (the holder's codes, or the float32 tensor the
     holder read), the wrapped layers of the plan consumers of its output, and erases the nodes between them (an average pool's
-    second holder and flattens); returns the number of consumers."""
-    name = (node.target.replace(".", "_") if node.op == "call_module" else node.name) + plan.suffix
+    second holder and flattens, an upsample's second holder); returns the number of consumers, those behind the max pools of an
+    upsample's plan included."""
+    name = plan.name or (node.target.replace(".", "_") if node.op == "call_module" else node.name) + plan.suffix
     gm.add_submodule(name, plan.module)
     mods[name] = plan.module
     node.op, node.target, node.args, node.kwargs = "call_module", name, (source,), {}
     for user, fused in plan.taken:
         _install_consumer(gm, mods, user, fused)
         user.args = (node,)
+    count = len(plan.taken)
+    for user, behind in plan.pooled:
+        count += _install_pool(gm, mods, user, behind, node)
+    for reader in plan.readers:                              # (where they read the second holder: now this node)
+        reader.args = tuple(node if a in plan.gone else a for a in reader.args)
     gone = list(plan.gone)
     while gone:                                              # users first
         free = [g for g in gone if not g.users]
@@ -1320,7 +1444,7 @@ def _install_pool(gm, mods, node, plan, source) -> int:
         for g in free:
             gm.graph.erase_node(g)
             gone.remove(g)
-    return len(plan.taken)
+    return count
 
 
 def _avg_pool_of(node, mods):
@@ -1420,6 +1544,86 @@ def _avg_pool_plan(node, mods, quantizer, consumer_for):
         return _PoolPlan(QuantizedAvgPool2d(pool, quantizer, out_quantizer, flatten=flat), "_qavgpool", taken, gone + [nxt])
     except (TypeError, ValueError, NotImplementedError):
         return None
+
+
+def _upsample_of(node, mods):
+    """The ``nn.Upsample`` that ``node`` applies to its one tensor operand -- a call of an ``nn.Upsample`` / ``nn.UpsamplingNearest2d``
+    module, or ``F.interpolate`` with constant arguments (``antialias`` false), for which one is built -- if QuantizedUpsample can
+    take it, else None."""
+    from torch.fx import Node
+    if not node.args or not isinstance(node.args[0], Node):
+        return None
+    up = None
+    if node.op == "call_module" and len(node.args) == 1 and not node.kwargs:
+        up = mods.get(node.target)
+    elif node.op == "call_function" and node.target is torch.nn.functional.interpolate:
+        given = _const_args(node, ("size", "scale_factor", "mode", "align_corners", "recompute_scale_factor", "antialias"))
+        if given is None or given.pop("antialias", False) is not False or not isinstance(given.get("mode", "nearest"), str):
+            return None
+        try:
+            up = nn.Upsample(**given)
+        except (TypeError, ValueError):
+            return None
+    return up if QuantizedUpsample.eligible(up) else None
+
+
+def _upsample_plan(node, mods, quantizer, consumer_for, pools: bool = False):
+    """``node`` a user of a plain holder A with ``quantizer``: the plan of a QuantizedUpsample if it is a nearest upsample of A's
+    output (``_upsample_of``) all of whose readers agree on one code form F and read codes.  Its one user may be a plain holder B
+    (F is B's form; B goes into ``gone`` and the node is named ``<B's name>_upsample``), whose users are then the readers; without
+    a B the upsample's own users are, and F is A's form unless a reader below says otherwise.  A reader is a wrapped layer
+    ``consumer_for`` can take, fed by it alone and never a QuantizedLinear; with ``pools`` a max pool that can run on codes
+    (``_pool_plan``); or a QuantizedConcat / QuantizedMul that reads it at exactly one operand, in the form F -- what the
+    concatenation and multiply passes leave where they absorbed B.  Else None: a float32 reader, an activation between the
+    upsample and B, forms that differ."""
+    up = _upsample_of(node, mods)
+    if up is None or not node.users:
+        return None
+    src, gone, name, out_quantizer = node, [], None, None
+    if len(node.users) == 1:
+        nxt = next(iter(node.users))
+        holder = _holder_of(nxt, mods)
+        if holder is not None and nxt.args == (node,):
+            if not nxt.users:
+                return None
+            src, gone, name, out_quantizer = nxt, [nxt], nxt.target.replace(".", "_") + "_upsample", holder.activation_holder_quantizer
+    try:
+        form = _code_form(quantizer if out_quantizer is None else out_quantizer)
+    except (TypeError, ValueError, NotImplementedError):
+        return None
+    operands, others = [], []                                # (reader, its quantizer and form for this operand); the other users
+    for user in src.users:
+        m = _module_of(user, mods)
+        if not isinstance(m, (QuantizedConcat, QuantizedMul)):
+            others.append(user)
+            continue
+        if user.kwargs or sum(a is src for a in user.args) != 1:
+            return None
+        at = next(i for i, a in enumerate(user.args) if a is src)
+        operands.append((user, m.operand_quantizers[at], m.operand_code_params(at)))
+    if not gone and operands and operands[0][2] != form:     # no B, and not A's form: F is what the operand is read as
+        if others:
+            return None                                      # (a layer or a pool would read A's form)
+        out_quantizer, form = operands[0][1:]
+    if any(f != form for _, _, f in operands):
+        return None
+    reads_as = quantizer if out_quantizer is None else out_quantizer
+    taken, pooled = [], []
+    for user in others:
+        fused = _wrapped_consumer(user, src, mods, reads_as, consumer_for)
+        if fused is not None and type(fused) is not QuantizedLinear:
+            taken.append((user, fused))
+            continue
+        behind = _pool_plan(user, mods, reads_as, consumer_for) if fused is None and pools else None
+        if behind is None:
+            return None
+        pooled.append((user, behind))
+    readers = [user for user, _, _ in operands]
+    try:
+        module = QuantizedUpsample(up, quantizer, out_quantizer)
+    except (TypeError, ValueError, NotImplementedError):
+        return None
+    return _PoolPlan(module, "_upsample", taken, gone, name, tuple(pooled), tuple(readers))
 
 
 class QuantizedJoin(_OnCodes):
@@ -1525,7 +1729,7 @@ def _mul_operands(node):
     return _binary_operands(node, (operator.mul, operator.imul, torch.mul, torch.multiply), ("mul", "multiply"), operator.imul)
 
 
-def _join_shared_holders(gm, mods, consumer_for, pools: bool = False, avg_pools: bool = False) -> int:
+def _join_shared_holders(gm, mods, consumer_for, pools: bool = False, avg_pools: bool = False, upsamples: bool = False) -> int:
     """``fuse_linear_consumers_fx(shared_holders=True)``: every plain holder with wrapped layers among its users that
     ``consumer_for(wrapper, quantizer)`` can take becomes a QuantizedJoin, unless it is a lone holder -> layer pair with
     nothing in front to absorb (the pair rewrite's).  With ``pools`` a max pool among the users that can run on codes
@@ -1533,16 +1737,20 @@ def _join_shared_holders(gm, mods, consumer_for, pools: bool = False, avg_pools:
     pool pair with nothing to absorb is left to ``_pool_lone_holders``.  With ``avg_pools`` the same holds for an average pool
     in front of a second holder (``_avg_pool_plan``), as a QuantizedAvgPool2d.  A QuantizedMul among the users
     (``_operator_between_holders``, which built it with this holder's quantizer at that operand) reads the join's codes too, at
-    whichever operand position the holder occupies.  Returns the number of wrapped layers replaced."""
+    whichever operand position the holder occupies.  With ``upsamples`` a nearest upsample among the users whose readers all read
+    codes (``_upsample_plan``) does so as a QuantizedUpsample, and the holder behind such an upsample is left to that plan.
+    Returns the number of wrapped layers replaced."""
     replaced = 0
     for node, holder in _holder_calls(gm, mods):
+        if upsamples and node.users and _behind_planned_upsample(node, mods, consumer_for, pools):
+            continue
         quantizer = holder.activation_holder_quantizer
         # F: (user node, its consumer)
         taken = [(user, _wrapped_consumer(user, node, mods, quantizer, consumer_for)) for user in node.users]
         taken = [(user, fused) for user, fused in taken if fused is not None]
         pooled = []                                          # P: (pool node, its plan)
-        if pools or avg_pools:
-            plans = ((user, _any_pool_plan(user, mods, quantizer, consumer_for, pools, avg_pools)) for user in node.users)
+        if pools or avg_pools or upsamples:
+            plans = ((user, _any_pool_plan(user, mods, quantizer, consumer_for, pools, avg_pools, upsamples)) for user in node.users)
             pooled = [(user, plan) for user, plan in plans if plan is not None]
         # M: the QuantizedMul nodes of ``_operator_between_holders`` that read this holder (built with its quantizer at those operands)
         muls = [user for user in node.users if isinstance(_module_of(user, mods), QuantizedMul) and not user.kwargs]
@@ -1584,25 +1792,37 @@ def _join_shared_holders(gm, mods, consumer_for, pools: bool = False, avg_pools:
     return replaced
 
 
-def _any_pool_plan(node, mods, quantizer, consumer_for, pools: bool, avg_pools: bool):
-    """``_pool_plan`` (with ``pools``) or else ``_avg_pool_plan`` (with ``avg_pools``) of ``node``, or None."""
+def _any_pool_plan(node, mods, quantizer, consumer_for, pools: bool, avg_pools: bool, upsamples: bool = False):
+    """``_pool_plan`` (with ``pools``), or else ``_avg_pool_plan`` (with ``avg_pools``), or else ``_upsample_plan`` (with
+    ``upsamples``) of ``node``, or None."""
     plan = _pool_plan(node, mods, quantizer, consumer_for) if pools else None
     if plan is None and avg_pools:
         plan = _avg_pool_plan(node, mods, quantizer, consumer_for)
+    if plan is None and upsamples:
+        plan = _upsample_plan(node, mods, quantizer, consumer_for, pools)
     return plan
 
 
-def _pool_lone_holders(gm, mods, consumer_for, pools: bool = True, avg_pools: bool = False) -> int:
+def _behind_planned_upsample(node, mods, consumer_for, pools: bool) -> bool:
+    """``node``, a plain holder's call, is the second holder of an upsample that will run on codes (``_upsample_plan`` of its
+    argument, a user of another plain holder): it belongs to that plan, whatever the number of its users."""
+    up = node.args[0]
+    first = _holder_of(up.args[0], mods) if _upsample_of(up, mods) is not None else None
+    return first is not None and _upsample_plan(up, mods, first.activation_holder_quantizer, consumer_for, pools) is not None
+
+
+def _pool_lone_holders(gm, mods, consumer_for, pools: bool = True, avg_pools: bool = False, upsamples: bool = False) -> int:
     """``fuse_linear_consumers_fx(pools=True)``, the pair: a plain holder whose only user is a max pool that can run on codes
     (``_pool_plan``) leaves the graph, the QuantizedMaxPool2d that replaces the pool quantizes the holder's input itself.
-    With ``avg_pools`` likewise for an average pool in front of a second holder (``_avg_pool_plan``) and its QuantizedAvgPool2d.
+    With ``avg_pools`` likewise for an average pool in front of a second holder (``_avg_pool_plan``) and its QuantizedAvgPool2d,
+    with ``upsamples`` for a nearest upsample (``_upsample_plan``) and its QuantizedUpsample.
     Returns the number of wrapped layers replaced."""
     replaced = 0
     for node, holder in _holder_calls(gm, mods):
         if len(node.users) != 1:
             continue
         user = next(iter(node.users))
-        plan = _any_pool_plan(user, mods, holder.activation_holder_quantizer, consumer_for, pools, avg_pools)
+        plan = _any_pool_plan(user, mods, holder.activation_holder_quantizer, consumer_for, pools, avg_pools, upsamples)
         if plan is None:
             continue
         replaced += _install_pool(gm, mods, user, plan, node.args[0])
@@ -1912,7 +2132,7 @@ def _fuse_residuals_into_producers(gm, mods) -> int:
 
 def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights: bool = False,
                           convolutions: bool = False, depthwise: bool = False, pools: bool = False,
-                          avg_pools: bool = False) -> int:
+                          avg_pools: bool = False, upsamples: bool = False) -> int:
     """In every ``nn.Sequential`` of ``model``: an activation holder directly followed by a wrapped ``nn.Linear`` with
     a symmetric, power-of-two or LUT weights quantizer (int8 codebook values, at most 256 entries) becomes (Identity,
     QuantizedLinear); a wrapped pointwise ``nn.Conv2d`` likewise becomes a QuantizedConv1x1.  Returns the number of pairs
@@ -1953,7 +2173,13 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
     taking B's codes.  The pool is an ``nn.AvgPool2d`` (padding at most half the kernel size) or an ``nn.AdaptiveAvgPool2d`` of
     output size 1; the flatten form needs the global pool.  With ``chain=True`` a consumer in front emits A's codes.  Counted
     as one pair.  Where A's scale and every window's divisor are powers of two the codes are bit for bit those of the float32
-    chain, elsewhere the exact mean rounded twice (``QuantizedAvgPool2d``)."""
+    chain, elsewhere the exact mean rounded twice (``QuantizedAvgPool2d``).
+
+    ``upsamples=True`` also takes (holder A, ``nn.Upsample`` / ``nn.UpsamplingNearest2d`` in a nearest mode, holder B, wrapped
+    convolution the consumer can take) and the same run without B: they become (Identity, QuantizedUpsample, [Identity,] consumer),
+    the upsample and B running as one launch on A's codes (``mctq_codes_upsample_nhwc``) and the consumer taking B's codes (A's
+    without a B).  With ``chain=True`` a consumer in front emits A's codes.  Counted as one pair.  Nearest interpolation only moves
+    data, so the codes are bit for bit those of the float32 chain (``QuantizedUpsample``)."""
     replaced = 0
     for seq in [m for m in model.modules() if isinstance(m, nn.Sequential)]:
         for i in range(len(seq) - 3 if avg_pools else 0):
@@ -1977,6 +2203,25 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
             if flat:
                 seq[i + 3] = _FusedAway()
             seq[i + 4 if flat else i + 3] = fused
+            replaced += 1
+        for i in range(len(seq) - 2 if upsamples else 0):
+            holder, up = seq[i], seq[i + 1]
+            second = seq[i + 2] if _plain_holder(seq[i + 2]) and i + 3 < len(seq) else None
+            wrapper = seq[i + 2] if second is None else seq[i + 3]
+            if not _plain_holder(holder) or not QuantizedUpsample.eligible(up) or not isinstance(wrapper, PytorchQuantizationWrapper):
+                continue
+            reads_as = (holder if second is None else second).activation_holder_quantizer
+            fused = _consumer_for(wrapper, reads_as, uniform_weights, convolutions, depthwise)
+            if fused is None or type(fused) is QuantizedLinear:
+                continue
+            try:
+                qup = QuantizedUpsample(up, holder.activation_holder_quantizer, None if second is None else reads_as)
+            except (TypeError, ValueError, NotImplementedError):
+                continue
+            seq[i], seq[i + 1] = _FusedAway(), qup
+            if second is not None:
+                seq[i + 2] = _FusedAway()
+            seq[i + 2 if second is None else i + 3] = fused
             replaced += 1
         for i in range(len(seq) - 2 if pools else 0):
             holder, pool, wrapper = seq[i], seq[i + 1], seq[i + 2]
@@ -2013,7 +2258,7 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
                              convolutions: bool = False, depthwise: bool = False, shared_holders: bool = False,
                              stay_on_codes: bool = False, pools: bool = False, fused_residuals: bool = False,
                              concats: bool = False, avg_pools: bool = False, muls: bool = False,
-                             hard_activations: bool = False):
+                             hard_activations: bool = False, upsamples: bool = False):
     """The same rewrite on an arbitrary module graph (MCT-exported models are not ``nn.Sequential``): traces ``model``
     with torch.fx keeping wrappers and holders as leaves, and wherever an activation holder's ONLY consumer is a
     wrapped ``nn.Linear`` the integer consumer can take (symmetric, power-of-two or LUT weights, and with
@@ -2158,7 +2403,36 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
     activation run on the tiled kernels, not the faster register-pinned ones (as with a residual): the rewrite has no cost
     model and folds them all the same (measured on 4096 x 4096 x 256: the tiled launch with the activation 31 us, the
     register-pinned launch 22 us, the three launches it replaces 54 us together; tools/hard_act_probe.py,
-    profiles/EXPERIMENTS.md)."""
+    profiles/EXPERIMENTS.md).
+
+    ``upsamples=True`` (needs no other switch) keeps a nearest upsample behind a holder on codes: a U-Net stage, a YOLO / PANet
+    neck, a segmentation head.  The candidate is a plain holder A one of whose users is a nearest upsample of its output -- a call
+    of an ``nn.Upsample`` of mode "nearest" or "nearest-exact" (``size`` or ``scale_factor``, any ``recompute_scale_factor``) or of
+    an ``nn.UpsamplingNearest2d``, or ``F.interpolate`` with constant arguments in one of those modes, ``antialias=False`` and
+    ``align_corners=None`` -- every reader of which agrees on one code form F.  (a) The upsample's one user is a plain holder B
+    (F is B's form) and every user of B is a wrapped layer the consumer can take under the other switches, fed by B alone (never a
+    QuantizedLinear), or with ``pools=True`` a max pool that can run on codes: the upsample and B become one QuantizedUpsample
+    node (``mctq_codes_upsample_nhwc``: A's codes gathered through the index map and requantized into B's form, 1 byte read and 1
+    written per output element) named ``<B's name>_upsample``, and the users consumers and pools of its codes, counted in the
+    returned total.  (b) Without a B the upsample's users are such layers and pools directly; F is A's form and the node a pure
+    copy of codes.  (c) With ``concats=True`` / ``muls=True`` a reader may be a QuantizedConcat / QuantizedMul that reads the
+    upsample's float32 output, or B's, at exactly one operand -- what those passes, which run first, leave where they absorbed
+    B: F is then ``operand_code_params(i)`` and that argument becomes the node's codes, so that A -> upsample -> B ->
+    cat([B, S]) -> C -> conv, the decoder stage, runs holder to holder on codes.  Holder A is treated as for ``pools``: read by
+    the upsample alone with nothing in front to absorb it leaves the graph and the module quantizes, at the low resolution;
+    with ``shared_holders=True`` a join in A's place hands the node its codes and writes no float32 when no float32 user
+    remains; with ``stay_on_codes=True`` the node is a reader of A's codes, so that conv -> ReLU -> A -> upsample -> B -> conv
+    runs codes to codes with the ReLU folded into the emitted clamp.  The index maps are read from the replaced call itself, per
+    input shape (``QuantizedUpsample``): a hipGraph capture needs one warm-up forward first, as ``capture_forward`` makes.  Left
+    alone: a float32 user of the upsample or of B (FPN's ``lateral + upsample(top)``: a residual join does not read a
+    QuantizedUpsample's codes yet); the modes bilinear, bicubic and area (ATen's interpolation expression is not reproduced bit
+    for bit); ``antialias=True``; ``align_corners`` given; a ``size`` that is no constant (``size=skip.shape[2:]``);
+    ``nn.PixelShuffle`` and ``nn.ConvTranspose2d``; 3-D and 5-D inputs (a ``size`` / ``scale_factor`` of one or three entries);
+    an activation between the upsample and B.  A holder's float32 output is ``float(code - zp) * scale`` bit for bit and nearest
+    interpolation only moves data, so the codes are bit for bit those B gives the float32 upsample, for any geometry and channel
+    count (counts that are no multiple of 16 take torch ops), and the model rewritten with ``upsamples=True`` returns, bit for
+    bit, what the same rewrite without it returns wherever the float32 products of the layers behind are exact; otherwise it
+    differs by the accumulation rounding of those products, like every wrapped layer that becomes a consumer."""
     import torch.fx as fx
     if stay_on_codes and not shared_holders:
         raise ValueError("stay_on_codes=True needs shared_holders=True")
@@ -2183,10 +2457,11 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
         replaced = _operator_between_holders(gm, mods, consumer_for, pools, _cat_operands, QuantizedConcat, "_concat")
     if muls:
         replaced += _operator_between_holders(gm, mods, consumer_for, pools, _mul_operands, QuantizedMul, "_mul")
+    # (an upsample's plan is made where a pool's is, in these two passes: it sees the QuantizedConcat / QuantizedMul nodes above)
     if shared_holders:
-        replaced += _join_shared_holders(gm, mods, consumer_for, pools, avg_pools)
-    if pools or avg_pools:
-        replaced += _pool_lone_holders(gm, mods, consumer_for, pools, avg_pools)
+        replaced += _join_shared_holders(gm, mods, consumer_for, pools, avg_pools, upsamples)
+    if pools or avg_pools or upsamples:
+        replaced += _pool_lone_holders(gm, mods, consumer_for, pools, avg_pools, upsamples)
     for src, holder in _holder_calls(gm, mods):              # the pair: a holder whose only user is a wrapped layer
         if len(src.users) != 1:
             continue

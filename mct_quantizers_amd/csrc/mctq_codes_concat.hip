@@ -19,7 +19,7 @@
 // ql_code(join_residual(code - zp, s)) == code: (code - zp) * s * (1 / s) lies within 255 * 3 * 2^-24 of the integer
 // code - zp.  The launcher marks only scales in [2^-100, 2^100], where neither the product nor the reciprocal can
 // overflow or underflow.
-#include "mctq_consumer.hpp"               // FastDiv, u32x4, QlOut, ql_code, join_residual
+#include "mctq_consumer.hpp"               // FastDiv, u32x4, QlOut, requant_chunk, form_is_copied
 
 namespace mctq {
 
@@ -69,19 +69,7 @@ __global__ __launch_bounds__(kThreads) void codes_concat_kernel(ConcatArgs a) {
   const bool copy = ((a.copy >> k_of) & 1u) != 0;
   // pixel < pixels and cc - start < width: the chunk index is below pixels * C_k / 16, and below 2^31 as g is
   u32x4 v = src[pixel * width + (cc - start)];
-  if (!copy) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const uint32_t u = v[q] ^ flip;
-      uint32_t w = 0;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float d = (float)((u >> (8 * j)) & 0xffu) - zb;                // float(code - zero_point), exact
-        w |= ((uint32_t)ql_code(join_residual(d, scale), a.o) & 0xffu) << (8 * j);
-      }
-      v[q] = w;
-    }
-  }
+  if (!copy) v = requant_chunk(v, flip, zb, scale, a.o);
   a.out[g] = v;
 }
 
@@ -136,10 +124,7 @@ int mctq_codes_concat_nhwc(const mctq_concat_item* items, int32_t count, void* o
     a.src[k] = static_cast<const u32x4*>(it.codes);
     a.end[k] = end;
     a.flip[k] = f.flip; a.zb[k] = (float)f.zb; a.scale[k] = f.scale;
-    const bool whole = o_signed ? (quant_min == -128 && quant_max == 127) : (quant_min == 0 && quant_max == 255);
-    if (g_concat_copy && whole && it.code_dtype == out_code_dtype && it.zero_point == zero_point
-        && __builtin_bit_cast(uint32_t, it.scale) == __builtin_bit_cast(uint32_t, scale)
-        && it.scale >= 0x1p-100f && it.scale <= 0x1p100f)
+    if (g_concat_copy && form_is_copied(it.code_dtype, it.zero_point, it.scale, out_code_dtype, zero_point, scale, quant_min, quant_max))
       a.copy |= 1u << k;
   }
   a.out = static_cast<u32x4*>(out);

@@ -133,6 +133,24 @@ struct FastDiv {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
+// One 16-byte chunk of codes of the form (flip, zb, scale) -- CodeForm's, below -- into the output form o, code by code:
+// ql_code(join_residual(float(code - zero_point), scale)), the code the holder behind gives the holder's float32 output.
+// Shared by the concatenation (mctq_codes_concat.hip) and the nearest upsampling (mctq_codes_upsample.hip).
+__device__ __forceinline__ u32x4 requant_chunk(u32x4 v, uint32_t flip, float zb, float scale, const QlOut& o) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const uint32_t u = v[q] ^ flip;
+    uint32_t w = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float d = (float)((u >> (8 * j)) & 0xffu) - zb;                  // float(code - zero_point), exact
+      w |= ((uint32_t)ql_code(join_residual(d, scale), o) & 0xffu) << (8 * j);
+    }
+    v[q] = w;
+  }
+  return v;
+}
+
 // ------------------------------------------------------------------------------------------
 // Host side: the argument checks the code-tensor launchers share.  Every step is its own function, so that an entry point
 // runs them in its own order between its other checks; none formats or allocates unless it refuses.
@@ -177,6 +195,18 @@ static int residual_form_check(int32_t r_code_dtype, int32_t r_zero_point, float
 static bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
   const uintptr_t ab = (uintptr_t)a, bb = (uintptr_t)b;
   return ab < bb + b_bytes && bb < ab + a_bytes;
+}
+
+// The copy rule of the requantizing launchers (requant_chunk's callers): an operand whose form is the output's -- the same code
+// type, zero point and float32 scale bits, a clamp domain that holds every code of the type -- comes out as it went in, for
+// every code: (code - zp) * s * (1 / s) lies within 255 * 3 * 2^-24 of the integer code - zp.  Only scales in
+// [2^-100, 2^100], where neither the product nor the reciprocal can overflow or underflow.
+static bool form_is_copied(int32_t code_dtype, int32_t zero_point, float scale, int32_t out_code_dtype, int32_t out_zero_point,
+                           float out_scale, int32_t quant_min, int32_t quant_max) {
+  const bool whole = out_code_dtype == MCTQ_CODE_I8 ? (quant_min == -128 && quant_max == 127) : (quant_min == 0 && quant_max == 255);
+  return whole && code_dtype == out_code_dtype && zero_point == out_zero_point
+      && __builtin_bit_cast(uint32_t, scale) == __builtin_bit_cast(uint32_t, out_scale)
+      && scale >= 0x1p-100f && scale <= 0x1p100f;
 }
 
 // A kernel, stride, dilation and padding window over a [B, H, W, C] image, one 16-byte chunk (16 channels) of one output

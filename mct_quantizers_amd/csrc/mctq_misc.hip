@@ -25,7 +25,8 @@ int g_ql_band = 0;
 int g_ql_stagger = 0;         // tiled consumer kernel: half of the waves copy after multiplying (experiment: no gain)
 int g_ql_rot = 0;            // tiled consumer kernel: blocks that share a weight tile start at different K offsets (experiment: no gain)
 int g_avgpool_form = 0;      // mctq_codes_avgpool_nhwc: 0 = the launcher chooses, 1 = lane form, 2 = split form (the result is the same)
-int g_concat_copy = 1;       // mctq_codes_concat_nhwc: operands in the output's own form are copied, not requantized (0: never; the result is the same)
+int g_concat_copy = 1;       // mctq_codes_concat_nhwc, mctq_codes_upsample_nhwc: operands in the output's own form are copied, not requantized (0: never; the result is the same)
+int g_upsample_form = 0;     // mctq_codes_upsample_nhwc: 0 = the launcher chooses (replicate for integer factors of 2 .. 16 outputs per input), 1 = gather form, 2 = replicate form where eligible (the result is the same)
 
 static const char* launch_log_path() {
   const char* p = getenv("MCTQ_LAUNCH_LOG");
@@ -220,6 +221,11 @@ int mctq_set_tuning(const char* key, int32_t value) {
   if (!strcmp(key, "avgpool_form")) {
     if (value < 0 || value > 2) return fail_arg("avgpool_form must be 0 (auto), 1 (lane) or 2 (split)");
     g_avgpool_form = value;
+    return 0;
+  }
+  if (!strcmp(key, "upsample_form")) {
+    if (value < 0 || value > 2) return fail_arg("upsample_form must be 0 (auto), 1 (gather) or 2 (replicate)");
+    g_upsample_form = value;
     return 0;
   }
   return fail_arg("unknown tuning key");

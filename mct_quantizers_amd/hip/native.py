@@ -156,6 +156,9 @@ SIGNATURES = {
     "mctq_codes_avgpool_nhwc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float]   # codes, pooled, type, zero point, scale
                                 + [ctypes.c_int64] * 4 + [ctypes.c_int32] * 9 + [ctypes.c_int64] * 2     # B, H, W, C; geometry, ceil_mode, count_include_pad, divisor_override; Ho, Wo
                                 + [ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),  # output form; stream
+    "mctq_codes_upsample_nhwc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float]  # codes, out, type, zero point, scale
+                                 + [ctypes.c_int64] * 6 + [ctypes.c_int32] * 2 + [ctypes.c_void_p] * 2     # B, H, W, C, Ho, Wo; factors; src_rows, src_cols
+                                 + [ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),  # output form; stream
     "mctq_qconv_dw_i8": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,   # a_codes, type, zero point, scale
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,  # w_codes, w_scales, w_zero_points, bias
                                         ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_int32,

@@ -833,6 +833,73 @@ def codes_concat(operands, out_form):
         return torch.cat(parts, -1).contiguous()
 
 
+def integer_factor(src, n_in: int):
+    """``f`` if the host-side index map ``src`` (a sequence or CPU tensor of ints) is that of an integer factor over ``n_in`` inputs
+    -- ``len(src) == f * n_in`` and ``src == arange(len(src)) // f``, f >= 1 -- else None."""
+    src = [int(v) for v in (src.tolist() if isinstance(src, torch.Tensor) else src)]
+    if n_in < 1 or not src or len(src) % n_in:
+        return None
+    f = len(src) // n_in
+    return f if src == [i // f for i in range(len(src))] else None
+
+
+def codes_upsample(codes_nhwc, in_form, out_form, src_rows, src_cols, factors=None):
+    """Nearest resampling on activation codes, in the form of the holder behind it: int8 / uint8 codes [B, H, W, C] of the form
+    ``in_form = (scale, zero_point)`` -> contiguous [B, Ho, Wo, C] codes of ``_code_dtype(qmin, qmax)`` in ``out_form = (scale,
+    zero_point, qmin, qmax)``.  ``src_rows`` / ``src_cols``: integer index vectors (tensors) of lengths Ho / Wo, the source row of
+    every output row and the source column of every output column -- what ``torch.nn.Upsample`` / ``F.interpolate`` in the
+    modes "nearest" and "nearest-exact" compute, up- or downsampling alike:
+
+        fq_codes(dequantize_codes(codes.index_select(1, src_rows).index_select(2, src_cols), s_in, z_in), ..., qmin, qmax, s, z)
+
+    -- a holder's float32 output is ``dequantize_codes`` of its codes bit for bit and nearest interpolation only moves data, so
+    these are the codes the holder behind the float32 upsample of a holder's output gives.  ``factors = (fh, fw)``: the caller's
+    word that the maps are those of integer factors (``integer_factor``); None has maps on the CPU examined here, maps on the GPU
+    are passed to the kernel as they are (no host read).  GPU tensors with C % 16 == 0 take one launch of
+    mctq_codes_upsample_nhwc (1 byte read per output element or less, 1 written); anything else on the GPU, and every CPU
+    tensor, evaluates the expression above with torch ops, which the kernel matches byte for byte.  Both clamp every map entry
+    into ``[0, H - 1]`` / ``[0, W - 1]`` first: no table can make either read outside the image."""
+    _nhwc_codes(codes_nhwc, "codes_upsample")
+    a_scale, a_zp = float(in_form[0]), int(in_form[1])
+    o_scale, o_zp, qmin, qmax, tdt, ocode = _out_form(out_form)
+    _check_form("codes_upsample", codes_nhwc.dtype, a_zp, (a_scale, o_scale))
+    for m, what in ((src_rows, "src_rows"), (src_cols, "src_cols")):
+        if not isinstance(m, torch.Tensor) or m.dim() != 1 or m.dtype.is_floating_point or m.dtype in (torch.bool, torch.complex64, torch.complex128):
+            raise TypeError(f"codes_upsample: {what} must be a 1-D integer tensor")
+    b, h, w, c = codes_nhwc.shape
+    ho, wo = src_rows.numel(), src_cols.numel()
+    if ho and wo and 0 in (h, w):
+        raise ValueError(f"codes_upsample: a {ho}x{wo} output needs an image of at least one pixel, got {h}x{w}")
+    x = _contiguous(codes_nhwc)
+    o_lo, o_hi = (0, 255) if tdt == torch.uint8 else (-128, 127)
+    if x.is_cuda and c % 16 == 0 and o_lo <= o_zp <= o_hi:
+        y = torch.empty((b, ho, wo, c), dtype=tdt, device=x.device)
+        if y.numel() == 0:
+            return y
+        if factors is None and not src_rows.is_cuda and not src_cols.is_cuda:
+            fh, fw = integer_factor(src_rows, h), integer_factor(src_cols, w)
+            factors = (fh, fw) if fh and fw else None
+        if factors is not None:
+            fh, fw = int(factors[0]), int(factors[1])
+            if fh < 1 or fw < 1 or ho != fh * h or wo != fw * w:
+                raise ValueError(f"codes_upsample: factors {fh}x{fw} do not take {h}x{w} to {ho}x{wo}")
+            _gpu_call("mctq_codes_upsample_nhwc", x, x.data_ptr(), y.data_ptr(), _code_of(x), a_zp, a_scale, b, h, w, c, ho, wo,
+                      fh, fw, None, None, ocode, o_scale, o_zp, qmin, qmax)
+            return y
+        rows = _contiguous(src_rows.to(device=x.device, dtype=torch.int32))          # named: they must outlive the launch
+        cols = _contiguous(src_cols.to(device=x.device, dtype=torch.int32))
+        _gpu_call("mctq_codes_upsample_nhwc", x, x.data_ptr(), y.data_ptr(), _code_of(x), a_zp, a_scale, b, h, w, c, ho, wo,
+                  0, 0, rows.data_ptr(), cols.data_ptr(), ocode, o_scale, o_zp, qmin, qmax)
+        return y
+    if not x.is_cuda:
+        _cpu_route_allowed()
+    with torch.no_grad():
+        rows = src_rows.to(device=x.device, dtype=torch.int64).clamp(0, max(h - 1, 0))
+        cols = src_cols.to(device=x.device, dtype=torch.int64).clamp(0, max(w - 1, 0))
+        moved = x.index_select(1, rows).index_select(2, cols)
+        return fq_codes(dequantize_codes(moved, a_scale, a_zp), None, None, None, qmin, qmax, o_scale, o_zp).contiguous()
+
+
 def codes_mul(a, g, out_form, gate_form=None):
     """``torch.mul`` of two holder outputs on activation codes, in the form of the holder behind it.  ``a = (codes, scale,
     zero_point)``, int8 / uint8 codes ``[.., C]`` (channels last); ``g = (tensor, scale, zero_point)``, codes likewise or, with
