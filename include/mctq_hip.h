@@ -87,6 +87,9 @@ extern "C" {
 /* v10 (additive, the version number stays): + mctq_codes_upsample_nhwc, nearest upsampling (torch.nn.Upsample / F.interpolate,
  * modes "nearest" and "nearest-exact") on NHWC activation codes in the form of the holder behind it (decoder stages, necks and
  * segmentation heads stay on codes), + tuning key "upsample_form"; no existing signature or result changed. */
+/* v10 (additive, the version number stays): + mctq_codes_im2col_pad_nhwc, the patch matrix for any channel count with rows padded
+ * to whole 16-byte chunks (the integer consumers then take layers whose K is no multiple of 16: a CNN's stem, bottleneck widths of
+ * 24 / 40 / 72, SE squeeze widths), + tuning key "im2col_grain"; no existing signature or result changed. */
 #define MCTQ_ABI_VERSION 10
 #define MCTQ_E_ARG (-10001)
 
@@ -539,6 +542,29 @@ int mctq_fq_codes_nchw_to_nhwc(const void* x, void* codes, int64_t batch, int64_
 int mctq_codes_im2col_nhwc(const void* codes, void* patches, int64_t batch, int64_t height, int64_t width, int64_t channels,
                            int32_t kh, int32_t kw, int32_t stride_h, int32_t stride_w, int32_t pad_h, int32_t pad_w,
                            int32_t dil_h, int32_t dil_w, int32_t pad_code, void* stream);
+
+/*
+ * The same patch matrix for ANY channel count (channels >= 1), its rows padded to whole 16-byte chunks: codes
+ * [batch][height][width][channels] -> patches [batch * Ho * Wo][Kp], K = kh * kw * channels, Kp = 16 * ceil(K / 16) <= 32768,
+ * both DEVICE, 16-byte aligned.  Column k < K holds what mctq_codes_im2col_nhwc writes there (a tap outside the image: the byte
+ * pad_code & 0xFF); columns K .. Kp - 1 hold pad_code & 0xFF.  With pad_code = the activation's zero point and weight rows
+ * [N][Kp] whose last Kp - K codes are 0, the product mctq_qlinear_* computes over Kp columns is the product over K columns
+ * exactly: a padded column adds a * 0 = 0 to the int32 sum and 0 to w_rowsum[n], and (a_zero_point - a_zero_point) = 0 to
+ * mctq_codes_rowsum's sums, so weight zero points are covered too.  For channels % 16 == 0 the bytes are those of
+ * mctq_codes_im2col_nhwc.  height = width = kh = kw = 1 re-pitches [batch][channels] rows to [batch][Kp].
+ * A lane assembles one 16-byte chunk of an output row from pieces of G bytes and stores it once: G = 4 (aligned dword loads)
+ * where channels % 4 == 0 -- a piece then never straddles two taps or the row's end -- and G = 1 (byte loads) elsewhere; tuning
+ * key "im2col_grain" forces one.  Every load address is formed from coordinates clamped into the image: no load reads outside
+ * `codes`, whatever the geometry.
+ * MCTQ_E_ARG with a mctq_last_error text for: negative extents; a kernel size, stride or dilation below 1; negative padding;
+ * pad_code outside [-128, 255]; kh * kw * channels > 32768; "im2col_grain" 4 with channels % 4 != 0; a padded extent above
+ * 2^31 - 1; Ho <= 0 or Wo <= 0; an image without pixels in a non-empty batch; more than 2^31 - 1 output rows; NULL or misaligned
+ * pointers of a non-empty problem.  batch == 0 or channels == 0 returns 0 without a launch.  mctq_last_launch names the launch
+ * "codes_im2col_pad", op "padded gather G=4" / "padded gather G=1".
+ */
+int mctq_codes_im2col_pad_nhwc(const void* codes, void* patches, int64_t batch, int64_t height, int64_t width, int64_t channels,
+                               int32_t kh, int32_t kw, int32_t stride_h, int32_t stride_w, int32_t pad_h, int32_t pad_w,
+                               int32_t dil_h, int32_t dil_w, int32_t pad_code, void* stream);
 
 /*
  * Max pooling on activation codes (extension; the reference runs ATen's float32 max pool on the holder's output):
@@ -998,6 +1024,9 @@ int mctq_qconv_dw_i8_act(const void* a_codes, int32_t a_code_dtype, int32_t a_ze
  *                  2 <= factor_h * factor_w <= 16, where it measured 1.8 - 2.3 x faster at batch 64 and equal at batch 1; gather
  *                  elsewhere), 1 = the gather form, 2 = the replicate form where eligible (integer factors with
  *                  factor_h * factor_w <= 16; gather elsewhere).  The bytes are the same: every output is one input's code
+ *   key "im2col_grain" : mctq_codes_im2col_pad_nhwc: bytes per load piece, 0 (default) = by rule (4 where channels % 4 == 0, 1
+ *                  elsewhere), 1 = byte loads, 4 = dword loads (MCTQ_E_ARG from the entry point where channels % 4 != 0).  The
+ *                  bytes are the same
  * Only variants a default dispatcher can select are instantiated; every value of every key is exercised by the GPU tests.
  * Returns 0, or MCTQ_E_ARG for an unknown key/value.  Numerical results never depend on it.
  */

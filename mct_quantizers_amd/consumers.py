@@ -98,6 +98,13 @@ moves data, so B's codes are A's codes gathered through the upsample's index map
 A -> upsample -> B -> cat([B, S]) -> C -> conv runs holder to holder on codes.
 Measured / not measured: see the README paragraph and ``profiles/EXPERIMENTS.md``.
 
+Layers whose K is no multiple of 16 -- a CNN's stem, bottleneck widths of 24 / 40 / 72, SE squeeze widths -- run on codes with
+``any_channels=True`` (both rewrites; ``QuantizedLinear``, ``QuantizedConv1x1``, ``QuantizedConv2d``): the weight rows are kept padded with
+the code 0 to ``Kp = 16 * ceil(K / 16)`` columns and the activation rows are written at that pitch with the zero-point code in their
+tail (``ops.codes_im2col(..., pad_to=16)``, ``mctq_codes_im2col_pad_nhwc``).  A padded column adds ``qa * 0`` to the sum, 0 to the weight's
+row sum and ``za - za`` to the activation's, so the product kernels are unchanged and the result is the product over K columns exactly.
+Measured / not measured: see the README paragraph and ``profiles/EXPERIMENTS.md``.
+
 The four modules derive from ``IntegerConsumer``, which owns what they share: the checks of the quantizers and of the float32
 weight and bias, the cache of the weight's codes, the step from ``forward``'s input to activation codes, ``from_wrapper`` and
 the ``emit_codes_for`` / ``emit_clamp`` output form.  ``QuantizedLinear`` is the product over ``[O, K]`` rows; ``QuantizedConv1x1``
@@ -527,9 +534,10 @@ class IntegerConsumer(nn.Module):
 
     _takes = None
 
-    def __init__(self, layer, weights_quantizer, activation_quantizer, weight=None):
+    def __init__(self, layer, weights_quantizer, activation_quantizer, weight=None, any_channels: bool = False):
         super().__init__()
-        if not self.eligible(layer):
+        # (any_channels: QuantizedLinear and the convolutions that are its product; the keyword is passed on only where it is set)
+        if not (self.eligible(layer, any_channels=True) if any_channels else self.eligible(layer)):
             raise TypeError(f"{type(self).__name__} takes {self._takes}")
         self._lut_weights = _is_lut_weights(weights_quantizer)
         self._uniform_weights = _is_uniform_weights(weights_quantizer)
@@ -583,12 +591,13 @@ class IntegerConsumer(nn.Module):
         return "" if self.emit_act is None else f"emit_act={self.emit_act!r}"
 
     @classmethod
-    def from_wrapper(cls, wrapper: PytorchQuantizationWrapper, activation_quantizer):
+    def from_wrapper(cls, wrapper: PytorchQuantizationWrapper, activation_quantizer, any_channels: bool = False):
         quantizers = wrapper.weights_quantizers
-        if list(quantizers) != ["weight"] or not cls.eligible(wrapper.layer):
+        extra = {"any_channels": True} if any_channels else {}
+        if list(quantizers) != ["weight"] or not cls.eligible(wrapper.layer, **extra):
             raise TypeError(f"expected wrapped {cls._takes} with one quantizer on 'weight'")
         # (the wrapper owns the float weight as its parameter)
-        return cls(wrapper.layer, quantizers["weight"], activation_quantizer, weight=wrapper.weight)
+        return cls(wrapper.layer, quantizers["weight"], activation_quantizer, weight=wrapper.weight, **extra)
 
     def activation_code_params(self):
         """(scale, zero_point, qmin, qmax) of this layer's activation codes: what ``emit_codes_for`` of the layer in front takes."""
@@ -680,11 +689,21 @@ def _padding(conv):
 def _take_conv_geometry(consumer, conv):
     """The geometry a convolution consumer reads on ``forward``.  A tap outside the image adds nothing because it holds the
     activation's zero-point code, which therefore has to be a code."""
-    if not consumer._a_qmin <= consumer._a_zp <= consumer._a_qmax:
-        raise NotImplementedError("the activation zero point lies outside the codes' domain: it cannot be the pad byte")
+    _check_pad_byte(consumer)
     consumer.in_channels = conv.in_channels
     consumer.kernel_size, consumer.stride, consumer.dilation = tuple(conv.kernel_size), tuple(conv.stride), tuple(conv.dilation)
     consumer.padding = _padding(conv)
+
+
+def _check_pad_byte(consumer):
+    """A padded tap or column adds nothing because it holds the activation's zero-point code, which therefore has to be a code."""
+    if not consumer._a_qmin <= consumer._a_zp <= consumer._a_qmax:
+        raise NotImplementedError("the activation zero point lies outside the codes' domain: it cannot be the pad byte")
+
+
+def _padded_k(k: int) -> int:
+    """Kp = 16 * ceil(K / 16): the row pitch of a layer taken with ``any_channels``."""
+    return -(-k // 16) * 16
 
 
 def _check_nchw(x, channels):
@@ -696,20 +715,46 @@ class QuantizedLinear(IntegerConsumer):
     """``activation quantizer -> PytorchQuantizationWrapper(nn.Linear)`` on integer codes (``IntegerConsumer`` for the
     quantizers it takes): the product over rows.  The weight codes are kept as ``[O, K]`` rows with their row sums; at most 4
     bits per weight -- codes, or the indices of a codebook of at most 16 entries -- are also kept packed, to stream half the
-    bytes when there are few activation rows."""
+    bytes when there are few activation rows.
+
+    ``any_channels=True`` also takes layers whose K is no multiple of 16 (the kernels' row pitch): the weight codes are then kept
+    as ``[O, Kp]`` rows, ``Kp = 16 * ceil(K / 16) <= 32768``, their last ``Kp - K`` columns the code 0, and ``forward`` re-pitches
+    the activation codes to ``[M, Kp]`` rows whose last columns hold the zero-point code (``ops.codes_im2col(..., pad_to=16)``,
+    one more launch for a Linear or a pointwise convolution; a k x k convolution's patch matrix is gathered at that pitch in the
+    first place).  A padded column adds ``qa * 0`` to the sum, 0 to the weight's row sum and ``za - za`` to the activation's, so the
+    product is the product over K columns exactly, weight zero points included.  That needs the zero point inside the clamp
+    domain (NotImplementedError otherwise).  Padded rows are never packed to 4 bits (index 0 of a codebook decodes to
+    ``lut[0]``, not to 0).  A layer with K % 16 == 0 is the layer built without the keyword: same buffers, same launches."""
 
     _takes = "torch.nn.Linear layers"
 
-    def __init__(self, linear, weights_quantizer, activation_quantizer, weight=None):
-        super().__init__(linear, weights_quantizer, activation_quantizer, weight)
+    def __init__(self, linear, weights_quantizer, activation_quantizer, weight=None, any_channels: bool = False):
+        super().__init__(linear, weights_quantizer, activation_quantizer, weight, any_channels)
         # [O, K] of a Linear, [O, C, 1, 1] of a pointwise and [O, C, kh, kw] of a k x k convolution
         self.out_features, self.in_features = self.weight.shape[0], math.prod(self.weight.shape[1:])
         self._w_rowsum = self._w_codes4 = None
         self._w_idx4 = self._lut16 = None                # LUT weights of at most 16 entries: packed indices + host codebook
+        # any_channels: the pitch of the weight and activation rows where K is no multiple of 16; None: rows of K columns
+        self._k_pitch = _padded_k(self.in_features) if any_channels and self.in_features % 16 else None
+        if self._k_pitch is not None:
+            if self._k_pitch > _MAX_K:
+                raise TypeError(f"{type(self).__name__} takes K <= {_MAX_K} (padded to a multiple of 16), got K={self.in_features}")
+            _check_pad_byte(self)
 
     @staticmethod
-    def eligible(layer) -> bool:
+    def eligible(layer, any_channels: bool = False) -> bool:
         return isinstance(layer, nn.Linear)
+
+    def extra_repr(self) -> str:
+        parts = [super().extra_repr()] + ([] if self._k_pitch is None else [f"k_pitch={self._k_pitch}"])
+        return ", ".join(p for p in parts if p)
+
+    def _pitched_rows(self, codes):
+        """Activation codes [M, K] (or NHWC [B, H, W, C] of a pointwise convolution) -> the rows the product takes: [M, K], or
+        with a pitch [M, Kp], the last columns holding the zero-point code."""
+        if self._k_pitch is None:
+            return codes.reshape(-1, self.in_features)
+        return ops.codes_im2col(codes, 1, pad_to=16, pad_code=self._a_zp)
 
     def _as_rows(self, t):
         """Codes or codebook indices shaped like the weight -> [O, K] in the order of the activation rows."""
@@ -717,6 +762,8 @@ class QuantizedLinear(IntegerConsumer):
 
     def _store_weight_codes(self, codes, lut):
         codes = self._as_rows(codes)
+        if self._k_pitch is not None:                    # the code 0 in the padded columns: they add nothing to any sum
+            codes = torch.nn.functional.pad(codes, (0, self._k_pitch - self.in_features))
         self._w_codes = codes.contiguous()
         self._w_rowsum = codes.sum(dim=1, dtype=torch.int32).contiguous()
         can_pack = self.weight.is_cuda and self.in_features % 16 == 0
@@ -729,7 +776,8 @@ class QuantizedLinear(IntegerConsumer):
         lead = x.shape[:-1]
         if residual is not None:
             residual = residual.reshape(-1, self.out_features)
-        return self._rows_product(self._activation_codes(x.reshape(-1, self.in_features)), residual).reshape(*lead, self.out_features)
+        rows = self._pitched_rows(self._activation_codes(x.reshape(-1, self.in_features)))
+        return self._rows_product(rows, residual).reshape(*lead, self.out_features)
 
     def _residual_rows(self, residual):
         """A convolution's residual -- [B, O, Ho, Wo], NCHW-shaped and NHWC-stored as consumers and joins emit it -- as
@@ -781,7 +829,7 @@ class QuantizedConv1x1(QuantizedLinear):
     _takes = "1x1, stride-1, unpadded, undilated, ungrouped nn.Conv2d layers"
 
     @staticmethod
-    def eligible(conv) -> bool:
+    def eligible(conv, any_channels: bool = False) -> bool:
         return (isinstance(conv, nn.Conv2d) and conv.kernel_size == (1, 1) and conv.stride == (1, 1)
                 and conv.padding in ((0, 0), 0, "valid") and conv.dilation == (1, 1) and conv.groups == 1
                 and conv.padding_mode == "zeros")
@@ -789,7 +837,7 @@ class QuantizedConv1x1(QuantizedLinear):
     def forward(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
         _check_nchw(x, self.in_features)
         b, _, h, w_ = x.shape
-        y = self._rows_product(self._activation_codes(x).reshape(b * h * w_, self.in_features), self._residual_rows(residual))
+        y = self._rows_product(self._pitched_rows(self._activation_codes(x)), self._residual_rows(residual))
         return y.reshape(b, h, w_, self.out_features).permute(0, 3, 1, 2)
 
 
@@ -800,20 +848,22 @@ class QuantizedConv2d(QuantizedLinear):
     data-movement launch; the matrix is materialised: kh * kw bytes per input element at stride 1) and the weight codes
     are kept as ``[O, kh, kw, C]`` rows; everything behind that is QuantizedLinear's.  Padded taps hold the activation's
     zero-point code, so they add ``(za - za) * qw = 0`` to the sum: zero padding is exact.  That needs the zero point
-    inside the clamp domain, ``in_channels % 16 == 0`` and ``kh * kw * in_channels <= 32768``.  ``padding="same"`` only
+    inside the clamp domain, ``in_channels % 16 == 0`` (any ``in_channels`` with ``any_channels=True``: the rows of the patch matrix
+    are then padded to a multiple of 16 columns, ``QuantizedLinear``) and ``kh * kw * in_channels <= 32768``.  ``padding="same"`` only
     where every ``dilation * (k - 1)`` is even (PyTorch pads one side more otherwise).  The result has the NCHW shape
     with channels-last strides."""
 
     _takes = f"ungrouped, zero-padded (symmetric) nn.Conv2d layers with in_channels % 16 == 0 and kh * kw * in_channels <= {_MAX_K}"
 
-    def __init__(self, conv, weights_quantizer, activation_quantizer, weight=None):
-        super().__init__(conv, weights_quantizer, activation_quantizer, weight)
+    def __init__(self, conv, weights_quantizer, activation_quantizer, weight=None, any_channels: bool = False):
+        super().__init__(conv, weights_quantizer, activation_quantizer, weight, any_channels)
         _take_conv_geometry(self, conv)
 
     @staticmethod
-    def eligible(conv) -> bool:
+    def eligible(conv, any_channels: bool = False) -> bool:
+        """``any_channels`` only lifts ``in_channels % 16 == 0`` (to Kp = 16 * ceil(K / 16) <= 32768, which K <= 32768 is)."""
         return (isinstance(conv, nn.Conv2d) and conv.groups == 1 and conv.padding_mode == "zeros"
-                and _padding(conv) is not None and conv.in_channels % 16 == 0
+                and _padding(conv) is not None and (any_channels or conv.in_channels % 16 == 0)
                 and conv.kernel_size[0] * conv.kernel_size[1] * conv.in_channels <= _MAX_K)
 
     def _as_rows(self, t):
@@ -823,7 +873,8 @@ class QuantizedConv2d(QuantizedLinear):
     def forward(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
         _check_nchw(x, self.in_channels)
         b, _, h, w_ = x.shape
-        rows = ops.codes_im2col(self._activation_codes(x), self.kernel_size, self.stride, self.padding, self.dilation, self._a_zp)
+        rows = ops.codes_im2col(self._activation_codes(x), self.kernel_size, self.stride, self.padding, self.dilation, self._a_zp,
+                                pad_to=1 if self._k_pitch is None else 16)
         y = self._rows_product(rows, self._residual_rows(residual))
         ho, wo = map(ops._conv_out_size, (h, w_), self.kernel_size, self.stride, self.padding, self.dilation)
         return y.reshape(b, ho, wo, self.out_features).permute(0, 3, 1, 2)
@@ -1261,20 +1312,22 @@ class QuantizedMul(_OperandsOnCodes):
 
 
 # In the order they are tried: (class, the switch of the rewrites that enables it or None, what fusing asks of the layer beyond
-# ``eligible``).  The rows kernels need K % 16 == 0 and K <= _MAX_K, which QuantizedConv2d's ``eligible`` holds itself.
+# ``eligible``, given the layer and ``any_channels``).  The rows kernels need K % 16 == 0 and K <= _MAX_K, which QuantizedConv2d's
+# ``eligible`` holds itself; with ``any_channels`` rows of any K are padded to Kp = 16 * ceil(K / 16), and Kp <= _MAX_K is K <= _MAX_K.
 _CONSUMERS = (
-    (QuantizedLinear, None, lambda layer: layer.in_features % 16 == 0 and layer.in_features <= _MAX_K),
-    (QuantizedConv1x1, None, lambda layer: layer.in_channels % 16 == 0 and layer.in_channels <= _MAX_K),
+    (QuantizedLinear, None, lambda layer, any_channels: (any_channels or layer.in_features % 16 == 0) and layer.in_features <= _MAX_K),
+    (QuantizedConv1x1, None, lambda layer, any_channels: (any_channels or layer.in_channels % 16 == 0) and layer.in_channels <= _MAX_K),
     (QuantizedConv2d, "convolutions", None),
     (QuantizedDepthwiseConv2d, "depthwise", None),
 )
 
 
-def _consumer_for(wrapper, activation_quantizer, uniform_weights=False, convolutions=False, depthwise=False):
+def _consumer_for(wrapper, activation_quantizer, uniform_weights=False, convolutions=False, depthwise=False, any_channels=False):
     """The integer consumer that can stand in for ``wrapper`` fed by ``activation_quantizer``, or None.  Uniform weights
     only with ``uniform_weights``; convolutions that need a patch matrix (QuantizedConv2d) only with ``convolutions``;
-    depthwise convolutions (QuantizedDepthwiseConv2d) only with ``depthwise``.  Half-precision layers are refused by the
-    classes: the integer consumer would change the output type."""
+    depthwise convolutions (QuantizedDepthwiseConv2d) only with ``depthwise``; layers whose K is no multiple of 16 only with
+    ``any_channels`` (QuantizedLinear and the convolutions that are its product; never the depthwise convolution).  Half-precision
+    layers are refused by the classes: the integer consumer would change the output type."""
     layer = getattr(wrapper, "layer", None)
     if list(getattr(wrapper, "weights_quantizers", {})) != ["weight"]:
         return None
@@ -1282,9 +1335,10 @@ def _consumer_for(wrapper, activation_quantizer, uniform_weights=False, convolut
         return None
     enabled = {None: True, "convolutions": convolutions, "depthwise": depthwise}
     for cls, switch, fits in _CONSUMERS:
-        if enabled[switch] and cls.eligible(layer) and (fits is None or fits(layer)):
+        extra = {"any_channels": True} if any_channels and issubclass(cls, QuantizedLinear) else {}
+        if enabled[switch] and cls.eligible(layer, **extra) and (fits is None or fits(layer, bool(extra))):
             try:
-                return cls.from_wrapper(wrapper, activation_quantizer)
+                return cls.from_wrapper(wrapper, activation_quantizer, **extra)
             except (TypeError, NotImplementedError):
                 return None
     return None
@@ -2132,7 +2186,7 @@ def _fuse_residuals_into_producers(gm, mods) -> int:
 
 def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights: bool = False,
                           convolutions: bool = False, depthwise: bool = False, pools: bool = False,
-                          avg_pools: bool = False, upsamples: bool = False) -> int:
+                          avg_pools: bool = False, upsamples: bool = False, any_channels: bool = False) -> int:
     """In every ``nn.Sequential`` of ``model``: an activation holder directly followed by a wrapped ``nn.Linear`` with
     a symmetric, power-of-two or LUT weights quantizer (int8 codebook values, at most 256 entries) becomes (Identity,
     QuantizedLinear); a wrapped pointwise ``nn.Conv2d`` likewise becomes a QuantizedConv1x1.  Returns the number of pairs
@@ -2179,7 +2233,18 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
     convolution the consumer can take) and the same run without B: they become (Identity, QuantizedUpsample, [Identity,] consumer),
     the upsample and B running as one launch on A's codes (``mctq_codes_upsample_nhwc``) and the consumer taking B's codes (A's
     without a B).  With ``chain=True`` a consumer in front emits A's codes.  Counted as one pair.  Nearest interpolation only moves
-    data, so the codes are bit for bit those of the float32 chain (``QuantizedUpsample``)."""
+    data, so the codes are bit for bit those of the float32 chain (``QuantizedUpsample``).
+
+    ``any_channels=True`` (composes with every other switch) also takes the pairs whose K is no multiple of 16: a wrapped
+    ``nn.Linear`` or pointwise convolution of any ``in_features`` / ``in_channels`` <= 32768 -- bottleneck widths of 24, 40, 72, SE
+    squeeze widths -- and, with ``convolutions=True``, a k x k convolution of any ``in_channels`` (a CNN's stem).  Such a consumer
+    keeps its weight rows padded with the code 0 to ``Kp = 16 * ceil(K / 16)`` columns and re-pitches its activation codes to rows
+    of ``Kp`` columns whose tail holds the zero-point code (``mctq_codes_im2col_pad_nhwc``: one more launch per Linear or pointwise
+    layer; the patch matrix of a k x k convolution is gathered at that pitch in the first place), so the product is exactly the
+    product over K columns, weight zero points included.  It needs the activation zero point inside its clamp domain; pairs
+    without are left alone.  Layers with K % 16 == 0 become the consumers they become without the switch; depthwise convolutions
+    and the pools, concatenations, multiplies and upsamples on codes keep their own conditions.  By default such pairs are left
+    alone: at the launch floor the re-pitch launch of a small pointwise layer can cost what the rewrite saves."""
     replaced = 0
     for seq in [m for m in model.modules() if isinstance(m, nn.Sequential)]:
         for i in range(len(seq) - 3 if avg_pools else 0):
@@ -2192,7 +2257,7 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
             wrapper = seq[i + 4] if flat else seq[i + 3]
             if not isinstance(wrapper, PytorchQuantizationWrapper):
                 continue
-            fused = _consumer_for(wrapper, second.activation_holder_quantizer, uniform_weights, convolutions, depthwise)
+            fused = _consumer_for(wrapper, second.activation_holder_quantizer, uniform_weights, convolutions, depthwise, any_channels)
             if fused is None or (type(fused) is QuantizedLinear) != flat:
                 continue
             try:
@@ -2211,7 +2276,7 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
             if not _plain_holder(holder) or not QuantizedUpsample.eligible(up) or not isinstance(wrapper, PytorchQuantizationWrapper):
                 continue
             reads_as = (holder if second is None else second).activation_holder_quantizer
-            fused = _consumer_for(wrapper, reads_as, uniform_weights, convolutions, depthwise)
+            fused = _consumer_for(wrapper, reads_as, uniform_weights, convolutions, depthwise, any_channels)
             if fused is None or type(fused) is QuantizedLinear:
                 continue
             try:
@@ -2227,7 +2292,7 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
             holder, pool, wrapper = seq[i], seq[i + 1], seq[i + 2]
             if not _plain_holder(holder) or not QuantizedMaxPool2d.eligible(pool) or not isinstance(wrapper, PytorchQuantizationWrapper):
                 continue
-            fused = _consumer_for(wrapper, holder.activation_holder_quantizer, uniform_weights, convolutions, depthwise)
+            fused = _consumer_for(wrapper, holder.activation_holder_quantizer, uniform_weights, convolutions, depthwise, any_channels)
             if fused is None or type(fused) is QuantizedLinear:
                 continue
             try:
@@ -2240,7 +2305,7 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
             holder, wrapper = seq[i], seq[i + 1]
             if not _plain_holder(holder) or not isinstance(wrapper, PytorchQuantizationWrapper):
                 continue
-            fused = _consumer_for(wrapper, holder.activation_holder_quantizer, uniform_weights, convolutions, depthwise)
+            fused = _consumer_for(wrapper, holder.activation_holder_quantizer, uniform_weights, convolutions, depthwise, any_channels)
             if fused is None:
                 continue
             seq[i] = _FusedAway()
@@ -2258,7 +2323,7 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
                              convolutions: bool = False, depthwise: bool = False, shared_holders: bool = False,
                              stay_on_codes: bool = False, pools: bool = False, fused_residuals: bool = False,
                              concats: bool = False, avg_pools: bool = False, muls: bool = False,
-                             hard_activations: bool = False, upsamples: bool = False):
+                             hard_activations: bool = False, upsamples: bool = False, any_channels: bool = False):
     """The same rewrite on an arbitrary module graph (MCT-exported models are not ``nn.Sequential``): traces ``model``
     with torch.fx keeping wrappers and holders as leaves, and wherever an activation holder's ONLY consumer is a
     wrapped ``nn.Linear`` the integer consumer can take (symmetric, power-of-two or LUT weights, and with
@@ -2432,7 +2497,16 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
     interpolation only moves data, so the codes are bit for bit those B gives the float32 upsample, for any geometry and channel
     count (counts that are no multiple of 16 take torch ops), and the model rewritten with ``upsamples=True`` returns, bit for
     bit, what the same rewrite without it returns wherever the float32 products of the layers behind are exact; otherwise it
-    differs by the accumulation rounding of those products, like every wrapped layer that becomes a consumer."""
+    differs by the accumulation rounding of those products, like every wrapped layer that becomes a consumer.
+
+    ``any_channels=True`` (needs no other switch and composes with all of them) lifts the ``K % 16 == 0`` condition of "a wrapped
+    layer the consumer can take" everywhere above, as for ``fuse_linear_consumers``: wrapped ``nn.Linear`` layers and pointwise
+    convolutions of any K <= 32768, and with ``convolutions=True`` k x k convolutions of any ``in_channels`` (the stem of a CNN behind
+    an input holder, the expand layer behind a 24-channel bottleneck, an SE block's ``fc2``).  Such a consumer pads its weight rows
+    with the code 0 and re-pitches its activation codes to ``Kp = 16 * ceil(K / 16)`` columns (``mctq_codes_im2col_pad_nhwc``), which
+    leaves the integer sum as it is; everything a consumer can emit -- codes, folded clamps, activations, residuals -- works
+    unchanged.  It needs the activation zero point inside its clamp domain.  Depthwise convolutions keep ``in_channels % 16 == 0``,
+    and the pools, concatenations, multiplies and upsamples on codes keep their torch routes for such channel counts."""
     import torch.fx as fx
     if stay_on_codes and not shared_holders:
         raise ValueError("stay_on_codes=True needs shared_holders=True")
@@ -2450,7 +2524,7 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
     gm = fx.GraphModule(model, graph)
     mods = dict(gm.named_modules())
     replaced = 0
-    consumer_for = lambda wrapper, q: _consumer_for(wrapper, q, uniform_weights, convolutions, depthwise)      # noqa: E731
+    consumer_for = lambda wrapper, q: _consumer_for(wrapper, q, uniform_weights, convolutions, depthwise, any_channels)      # noqa: E731
     # Two whole passes, concatenations first: a concatenation absorbs an operand holder that sits behind a multiply, which the
     # multiply pass then no longer sees.
     if concats:

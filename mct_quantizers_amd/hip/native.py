@@ -143,6 +143,8 @@ SIGNATURES = {
                                                   ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
     "mctq_codes_im2col_nhwc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                               ctypes.c_int64] + [ctypes.c_int32] * 9 + [ctypes.c_void_p]),
+    "mctq_codes_im2col_pad_nhwc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                                  ctypes.c_int64] + [ctypes.c_int32] * 9 + [ctypes.c_void_p]),
     "mctq_codes_maxpool_nhwc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32] + [ctypes.c_int64] * 4    # codes, pooled, type; B, H, W, C
                                 + [ctypes.c_int32] * 9 + [ctypes.c_int64] * 2 + [ctypes.c_void_p]),                # geometry, ceil_mode; Ho, Wo; stream
     "mctq_codes_concat_nhwc": (ctypes.c_int, [ctypes.POINTER(ConcatItem), ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,    # items, count, out, out type

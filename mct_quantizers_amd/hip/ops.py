@@ -670,27 +670,41 @@ def _conv_geometry(h: int, w: int, kernel_size, stride, padding, dilation, calle
     return (kh, kw), (sh, sw), (ph, pw), (dh, dw), (ho, wo)
 
 
-def codes_im2col(codes_nhwc, kernel_size, stride=1, padding=0, dilation=1, pad_code: int = 0):
+def codes_im2col(codes_nhwc, kernel_size, stride=1, padding=0, dilation=1, pad_code: int = 0, pad_to: int = 1):
     """The patch matrix of a convolution over activation codes: contiguous int8 / uint8 codes [B, H, W, C] (what
     ``fq_codes_nhwc`` returns) -> [B * Ho * Wo, kh * kw * C], row (b, oy, ox), column (ky * kw + kx) * C + c; taps
     outside the image hold ``pad_code`` (the activation's zero point: such a tap then adds nothing to the integer
     consumer's sum).  GPU tensors run mctq_codes_im2col_nhwc (C % 16 == 0, kh * kw * C <= 32768); CPU tensors the same
-    gather with torch ops, byte for byte."""
+    gather with torch ops, byte for byte.
+
+    ``pad_to=16`` (1, the default, or 16): the rows are padded with ``pad_code`` to ``Kp = 16 * ceil(K / 16)`` columns,
+    K = kh * kw * C, for any C >= 1 -- the rows the integer consumers take where K is no multiple of 16.  GPU tensors with
+    K % 16 == 0 and C % 16 == 0 keep the launch above; every other GPU tensor runs mctq_codes_im2col_pad_nhwc (Kp <= 32768);
+    CPU tensors the gather above with the columns appended.  A 2-D ``[M, K]`` codes tensor is then taken as ``[M, 1, 1, K]``:
+    the row re-pitch of a Linear or pointwise layer."""
+    if pad_to not in (1, 16):
+        raise ValueError(f"codes_im2col: pad_to must be 1 or 16, got {pad_to!r}")
+    if pad_to == 16 and isinstance(codes_nhwc, torch.Tensor) and codes_nhwc.dim() == 2:
+        codes_nhwc = codes_nhwc.reshape(codes_nhwc.shape[0], 1, 1, codes_nhwc.shape[1])
     _nhwc_codes(codes_nhwc, "codes_im2col")
     pad_code = int(pad_code)
     _check_form("codes_im2col", codes_nhwc.dtype, pad_code, zp_words="pad_code {}")
     b, h, w, c = codes_nhwc.shape
     (kh, kw), (sh, sw), (ph, pw), (dh, dw), (ho, wo) = _conv_geometry(h, w, kernel_size, stride, padding, dilation, "codes_im2col")
     x = _contiguous(codes_nhwc)
+    k = kh * kw * c
+    kp = -(-k // pad_to) * pad_to
     if x.is_cuda:
-        y = torch.empty((b * ho * wo, kh * kw * c), dtype=x.dtype, device=x.device)
-        _gpu_call("mctq_codes_im2col_nhwc", x, x.data_ptr(), y.data_ptr(), b, h, w, c, kh, kw, sh, sw, ph, pw, dh, dw, pad_code)
+        y = torch.empty((b * ho * wo, kp), dtype=x.dtype, device=x.device)
+        name = "mctq_codes_im2col_nhwc" if pad_to == 1 or (k % 16 == 0 and c % 16 == 0) else "mctq_codes_im2col_pad_nhwc"
+        _gpu_call(name, x, x.data_ptr(), y.data_ptr(), b, h, w, c, kh, kw, sh, sw, ph, pw, dh, dw, pad_code)
         return y
     _cpu_route_allowed()
     xp = torch.nn.functional.pad(x, (0, 0, pw, pw, ph, ph), value=pad_code)              # [B, H + 2 ph, W + 2 pw, C]
     sb, sy, sx, sc = xp.stride()
     taps = xp.as_strided((b, ho, wo, kh, kw, c), (sb, sy * sh, sx * sw, sy * dh, sx * dw, sc))
-    return taps.reshape(b * ho * wo, kh * kw * c)
+    rows = taps.reshape(b * ho * wo, k)
+    return rows if kp == k else torch.nn.functional.pad(rows, (0, kp - k), value=pad_code)
 
 
 def codes_maxpool(codes_nhwc, kernel_size, stride=None, padding=0, dilation=1, ceil_mode: bool = False):

@@ -204,13 +204,15 @@ def _bottleneck_class():
     return Bottleneck
 
 
-def wrapped_resnet50(device="cuda", weights: str = "symmetric", holders: bool = True, pooled_holder: bool = False):
+def wrapped_resnet50(device="cuda", weights: str = "symmetric", holders: bool = True, pooled_holder: bool = False,
+                     input_holder: bool = False):
     """ResNet-50 as an MCT export looks (batch norms folded into the convolutions): 53 wrapped convolutions + the wrapped
     classifier, their weights from ``make_model_weights("resnet50")`` in forward order, 8-bit per-channel symmetric
     weights quantizers (``weights="lut"``: 16-entry codebook LUT quantizers), an unsigned 8-bit activation holder behind
     every ReLU.  ``pooled_holder=True`` puts the same holder behind the global average pool as well, as an MCT export has it
-    (the classifier then reads a quantized mean); the default is the model without it.  Pure workload: random weights, no
-    checkpoint."""
+    (the classifier then reads a quantized mean); the default is the model without it.  ``input_holder=True`` puts a signed
+    8-bit symmetric holder in front of the stem, as an MCT export has it on its input (the stem, 3 input channels, can then run
+    on codes with ``any_channels=True``); the default is the model without it.  Pure workload: random weights, no checkpoint."""
     import torch
     import torch.nn as nn
     import mct_quantizers_amd as mq
@@ -246,6 +248,9 @@ def wrapped_resnet50(device="cuda", weights: str = "symmetric", holders: bool = 
         return Bottleneck(c1, a1, c2, a2, c3, down, act())
 
     layers = [wrap(nn.Conv2d(3, 64, 7, stride=2, padding=3, bias=False)), act(), nn.MaxPool2d(3, 2, 1)]
+    if input_holder:
+        layers.insert(0, mq.PytorchActivationQuantizationHolder(
+            Q.ActivationSymmetricInferableQuantizer(num_bits=8, threshold=[4.0], signed=True)))
     cin = 64
     for width, blocks, stride in ((64, 3, 1), (128, 4, 2), (256, 6, 2), (512, 3, 2)):
         for b in range(blocks):
