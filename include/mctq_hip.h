@@ -90,6 +90,9 @@ extern "C" {
 /* v10 (additive, the version number stays): + mctq_codes_im2col_pad_nhwc, the patch matrix for any channel count with rows padded
  * to whole 16-byte chunks (the integer consumers then take layers whose K is no multiple of 16: a CNN's stem, bottleneck widths of
  * 24 / 40 / 72, SE squeeze widths), + tuning key "im2col_grain"; no existing signature or result changed. */
+/* v10 (additive, the version number stays): + mctq_codes_table, an elementwise function between two activation holders as a
+ * 256-entry byte table on codes (sigmoid, SiLU, GELU, tanh and the other smooth activations stay on codes), + tuning key
+ * "table_chunks"; no existing signature or result changed. */
 #define MCTQ_ABI_VERSION 10
 #define MCTQ_E_ARG (-10001)
 
@@ -739,6 +742,26 @@ int mctq_codes_upsample_nhwc(const void* codes, void* out, int32_t code_dtype, i
                              int32_t quant_min, int32_t quant_max, void* stream);
 
 /*
+ * An elementwise function between two activation holders on codes (extension; the reference runs the function on the float32
+ * output of holder A and holder B on the result): out[i] = table[raw byte in[i]] for i < n.  Holder A's float32 output takes at
+ * most 256 values, one per code, and both the function and holder B work element by element, so B's code is a function of A's
+ * code.  table: 256 bytes on the DEVICE, 4-byte aligned, indexed by the RAW byte of the input (an int8 code c at entry (uint8_t)c),
+ * its entries the raw bytes of the output codes -- the caller builds it by running the replaced function on the 256 dequantized
+ * codes (ops.code_table).  in, out: DEVICE pointers, 16-byte aligned, n bytes each, any n >= 0 (flat: no shape, no channel count).
+ * in_code_dtype / out_code_dtype (MCTQ_CODE_I8 or MCTQ_CODE_U8) are checked and name the launch; the bytes do not depend on them.
+ * A workgroup keeps the table in 256 B of LDS (64 lanes load one dword each, one barrier); a lane owns "table_chunks" (tuning key:
+ * 1, 2 or 4, default 4) chunks of 16 bytes, issues all of their loads before the first lookup, and writes one plain 16-byte store
+ * per chunk; the n % 16 tail bytes are read and written byte by byte by one lane.  No byte outside [out, out + n) is written.
+ * MCTQ_E_ARG with a mctq_last_error text, before anything is launched, for: n < 0; a bad in_code_dtype or out_code_dtype; more
+ * than 2^31 - 1 16-byte chunks (split the tensor); with n > 0, a NULL pointer, an in or out that is not 16-byte aligned, a table
+ * that is not 4-byte aligned, an `out` whose bytes overlap in's or the table's.  n == 0 returns 0 without a launch.
+ * mctq_last_launch names the launch "codes_table", op "<in> -> <out> blocks=<workgroups>" with the code types "u8" / "i8", U = the
+ * chunks per lane: a workgroup covers 256 * U * 16 bytes.
+ */
+int mctq_codes_table(const void* in, int32_t in_code_dtype, void* out, int32_t out_code_dtype, int64_t n, const void* table,
+                     void* stream);
+
+/*
  * Depthwise convolution on activation codes (groups == channels, channel multiplier 1; extension, the reference has no
  * counterpart): what a wrapped depthwise torch.nn.Conv2d computes on fake-quantized operands, evaluated on the codes.
  *     acc[b][oy][ox][c] = sum over the taps (ky, kx) inside the image of
@@ -1027,6 +1050,7 @@ int mctq_qconv_dw_i8_act(const void* a_codes, int32_t a_code_dtype, int32_t a_ze
  *   key "im2col_grain" : mctq_codes_im2col_pad_nhwc: bytes per load piece, 0 (default) = by rule (4 where channels % 4 == 0, 1
  *                  elsewhere), 1 = byte loads, 4 = dword loads (MCTQ_E_ARG from the entry point where channels % 4 != 0).  The
  *                  bytes are the same
+ *   key "table_chunks" : mctq_codes_table: 16-byte chunks per lane, 1, 2 or 4 (default 4).  The bytes are the same
  * Only variants a default dispatcher can select are instantiated; every value of every key is exercised by the GPU tests.
  * Returns 0, or MCTQ_E_ARG for an unknown key/value.  Numerical results never depend on it.
  */

@@ -105,12 +105,24 @@ tail (``ops.codes_im2col(..., pad_to=16)``, ``mctq_codes_im2col_pad_nhwc``).  A 
 row sum and ``za - za`` to the activation's, so the product kernels are unchanged and the result is the product over K columns exactly.
 Measured / not measured: see the README paragraph and ``profiles/EXPERIMENTS.md``.
 
+The smooth activations between two holders -- sigmoid, SiLU, GELU, tanh, Mish, ELU, LeakyReLU, ... -- stay on codes with
+``activation_tables=True`` (both rewrites): holder A -> 1 to 4 elementwise activations -> holder B.  A's float32 output takes at most
+256 values, ``f`` maps each value by itself and B codes each element by itself, so B's code is a function of A's code: a 256-entry byte
+table, built by running the replaced call itself on the 256 dequantized values on the tensor's device.  ``QuantizedActivationTable``
+(``mctq_codes_table``) applies it in one launch, 1 byte read and 1 written per element, for any element and channel count.  The table is
+the definition: on the GPU, where ATen applies one scalar functor per element whatever its position, the codes are bit for bit those
+of the float32 chain (tests/test_gpu_table_consumer.py, every accepted function); on the CPU, where ATen's vector body and scalar
+tail round differently, they equal the chain's wherever its float32 value equals the table's and are within one code next to a
+rounding tie elsewhere.  Out of scope: the lookup inside the producing consumer's epilogue (``emit_table``, beside ``emit_act``).
+Measured / not measured: see the README paragraph and ``profiles/EXPERIMENTS.md``.
+
 The four modules derive from ``IntegerConsumer``, which owns what they share: the checks of the quantizers and of the float32
 weight and bias, the cache of the weight's codes, the step from ``forward``'s input to activation codes, ``from_wrapper`` and
 the ``emit_codes_for`` / ``emit_clamp`` output form.  ``QuantizedLinear`` is the product over ``[O, K]`` rows; ``QuantizedConv1x1``
 and ``QuantizedConv2d`` are that product and derive from it; ``QuantizedDepthwiseConv2d`` is not and derives from
 ``IntegerConsumer`` directly.  "Any integer consumer" in the graph rewrites is ``isinstance(m, IntegerConsumer)``.  The modules
-without weights -- the pools, ``QuantizedUpsample``, ``QuantizedConcat``, ``QuantizedMul``, ``QuantizedJoin`` -- derive from ``_OnCodes``;
+without weights -- the pools, ``QuantizedUpsample``, ``QuantizedActivationTable``, ``QuantizedConcat``, ``QuantizedMul``, ``QuantizedJoin`` --
+derive from ``_OnCodes``;
 ``_operand_codes`` is the one step from an operand of ``forward`` to codes, theirs and the consumers' (the join has its own kernel).
 
 CPU tensors run the same integer arithmetic with torch ops (host logic for tests, bit-identical to the kernel).
@@ -922,8 +934,8 @@ def _ints_or_pair(v) -> bool:
 
 
 class _OnCodes(nn.Module):
-    """Base of the modules without weights that read or write activation codes -- the pools, QuantizedUpsample, QuantizedConcat, QuantizedMul and
-    QuantizedJoin: with the wrappers, the holders and the integer consumers, the leaves of the graph rewrite's tracer."""
+    """Base of the modules without weights that read or write activation codes -- the pools, QuantizedUpsample, QuantizedActivationTable,
+    QuantizedConcat, QuantizedMul and QuantizedJoin: with the wrappers, the holders and the integer consumers, the leaves of the graph rewrite's tracer."""
 
 
 class QuantizedMaxPool2d(_OnCodes):
@@ -1194,6 +1206,94 @@ class QuantizedUpsample(_OnCodes):
         return y.permute(0, 3, 1, 2)
 
 
+_TABLE_CHAIN_MAX = 4           # activations in a row that one QuantizedActivationTable takes
+
+
+class QuantizedActivationTable(_OnCodes):
+    """``activation holder A -> elementwise activation(s) -> activation holder B`` on integer codes, for the integer consumers,
+    pools and concatenations behind B: EfficientNet- and YOLO-style ``conv -> holder -> SiLU -> holder -> conv``, GELU blocks,
+    sigmoid gates, LeakyReLU necks.  A's float32 output is ``float(code - zp_a) * scale_a`` bit for bit (``ops.dequantize_codes``),
+    so it takes at most 256 values; an elementwise ``f`` maps each value by itself and B codes each element by itself, so B's code
+    is a function of A's code: a 256-entry byte table -- ``ops.codes_table`` (``mctq_codes_table``): 1 byte read and 1 written per
+    element in one launch, where A writes float32, ATen's ``f`` reads and writes it, and B and the reader's quantize launch read
+    it again.
+
+    The table is the definition: B's code of ``f``, evaluated on the [256] dequantized values by the replaced call itself on the
+    tensor's device (``ops.code_table``).  On the GPU, ATen's elementwise kernels apply one scalar functor per element whatever
+    its position, the shape or the layout, so the codes are bit for bit those of the float32 chain A -> f -> B on that GPU, the
+    transcendental functions included (tests/test_gpu_table_consumer.py checks every accepted function with strict equality).  On
+    the CPU that does not hold: ATen's vector body and scalar tail give different last bits for sigmoid, SiLU, softplus, ELU, Mish,
+    tanh and GELU, so there the codes equal the chain's wherever the chain's float32 value equals the table's, and elsewhere can
+    differ by one code next to a rounding tie.
+
+    ``fn``: one module or a sequence of 1 to 4 modules, applied in order, each of a type ``eligible`` accepts -- ``nn.Sigmoid``,
+    ``Tanh``, ``SiLU``, ``GELU`` (both approximations), ``Mish``, ``Softplus``, ``ELU``, ``CELU``, ``SELU``, ``LeakyReLU``,
+    ``Hardswish``, ``Hardsigmoid``, ``Hardtanh``, ``ReLU``, ``ReLU6``, ``LogSigmoid``, ``Softsign``, ``Tanhshrink``, and no subclass
+    of them: elementwise, without learnable, per-channel or random state and without a training mode.  ``in_quantizer`` (A's) and
+    ``out_quantizer`` (B's): per-tensor affine activation quantizers of at most 8 bits whose zero points are codes of their type.
+
+    ``forward`` takes A's codes (int8 / uint8 of A's code type) or a float32 tensor, which it quantizes with A's parameters, of
+    any rank -- a 4-D one NCHW-shaped and NHWC-stored as the consumers and joins emit it -- and returns B's codes in the same shape
+    and layout.  ``activation_code_params`` is the INPUT form, what a producer in front emits; ``output_code_params`` is B's
+    (``QuantizedAvgPool2d``'s convention).  Tables are cached per device and built on first use there, with a few tiny launches
+    and no host read: a hipGraph capture needs one warm-up forward first (``capture_forward``'s warm-up is one).  Any element
+    and channel count takes the kernel."""
+
+    TYPES = (nn.Sigmoid, nn.Tanh, nn.SiLU, nn.GELU, nn.Mish, nn.Softplus, nn.ELU, nn.CELU, nn.SELU, nn.LeakyReLU, nn.Hardswish,
+             nn.Hardsigmoid, nn.Hardtanh, nn.ReLU, nn.ReLU6, nn.LogSigmoid, nn.Softsign, nn.Tanhshrink)
+
+    def __init__(self, fn, in_quantizer, out_quantizer):
+        super().__init__()
+        fns = list(fn) if isinstance(fn, (list, tuple, nn.Sequential, nn.ModuleList)) else [fn]
+        if not 1 <= len(fns) <= _TABLE_CHAIN_MAX or not all(self.eligible(f) for f in fns):
+            raise TypeError(f"QuantizedActivationTable takes 1 to {_TABLE_CHAIN_MAX} elementwise activation modules of the types "
+                            + ", ".join(t.__name__ for t in self.TYPES) + " (no subclasses)")
+        self.fns = nn.ModuleList(fns)
+        self.in_quantizer, self.out_quantizer = in_quantizer, out_quantizer
+        self._a_scale, self._a_zp, self._a_qmin, self._a_qmax = _code_form(in_quantizer)
+        self._out_form = _code_form(out_quantizer)
+        self._out_dtype = ops._code_dtype(self._out_form[2], self._out_form[3])[0]
+        self._tables = {}                                      # device -> uint8 [256]
+
+    @staticmethod
+    def eligible(fn) -> bool:
+        if type(fn) not in QuantizedActivationTable.TYPES:
+            return False
+        if type(fn) is nn.GELU and fn.approximate not in ("none", "tanh"):
+            return False
+        return True
+
+    def activation_code_params(self):
+        """(scale, zero_point, qmin, qmax) of the codes this module READS (holder A's): what ``emit_codes_for`` of the layer in
+        front takes."""
+        return self._a_scale, self._a_zp, self._a_qmin, self._a_qmax
+
+    def output_code_params(self):
+        """(scale, zero_point, qmin, qmax) of the codes ``forward`` returns (holder B's): what the readers behind agree on."""
+        return self._out_form
+
+    def extra_repr(self) -> str:
+        return "fn=" + " -> ".join(type(f).__name__ for f in self.fns)
+
+    def _apply_fns(self, x):
+        for f in self.fns:
+            x = f(x)
+        return x
+
+    def table(self, device):
+        """The byte table on ``device`` (``ops.code_table`` of the activations in order), built on first use there."""
+        key = str(torch.device(device))
+        hit = self._tables.get(key)
+        if hit is None:
+            hit = self._tables[key] = ops.code_table(self._apply_fns, self.activation_code_params(), self._out_form, device)
+        return hit
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        codes = _operand_codes(x, self.activation_code_params(), "QuantizedActivationTable", "this activation's input quantizer")
+        y = ops.codes_table(codes, self.table(codes.device), self._out_dtype)
+        return y.permute(0, 3, 1, 2) if x.dim() == 4 else y
+
+
 class _OperandsOnCodes(_OnCodes):
     """What QuantizedConcat and QuantizedMul share: several operands, each read as the codes of its own holder's quantizer,
     and one output holder's quantizer, all per-tensor affine of at most 8 bits (``_code_form``)."""
@@ -1345,7 +1445,7 @@ def _consumer_for(wrapper, activation_quantizer, uniform_weights=False, convolut
 
 
 # what reads the activation codes of the module in front as they are
-_CODE_READERS = (IntegerConsumer, QuantizedMaxPool2d, QuantizedAvgPool2d, QuantizedUpsample)
+_CODE_READERS = (IntegerConsumer, QuantizedMaxPool2d, QuantizedAvgPool2d, QuantizedUpsample, QuantizedActivationTable)
 
 
 class _FusedAway(nn.Identity):
@@ -1621,26 +1721,28 @@ def _upsample_of(node, mods):
     return up if QuantizedUpsample.eligible(up) else None
 
 
-def _upsample_plan(node, mods, quantizer, consumer_for, pools: bool = False):
-    """``node`` a user of a plain holder A with ``quantizer``: the plan of a QuantizedUpsample if it is a nearest upsample of A's
-    output (``_upsample_of``) all of whose readers agree on one code form F and read codes.  Its one user may be a plain holder B
-    (F is B's form; B goes into ``gone`` and the node is named ``<B's name>_upsample``), whose users are then the readers; without
-    a B the upsample's own users are, and F is A's form unless a reader below says otherwise.  A reader is a wrapped layer
-    ``consumer_for`` can take, fed by it alone and never a QuantizedLinear; with ``pools`` a max pool that can run on codes
-    (``_pool_plan``); or a QuantizedConcat / QuantizedMul that reads it at exactly one operand, in the form F -- what the
-    concatenation and multiply passes leave where they absorbed B.  Else None: a float32 reader, an activation between the
-    upsample and B, forms that differ."""
-    up = _upsample_of(node, mods)
-    if up is None or not node.users:
+def _between_holders_plan(first, chain, mods, quantizer, consumer_for, pools, build, suffix, copies: bool, rows: bool):
+    """What ``_upsample_plan`` and ``_table_plan`` share.  ``first`` is a user of a plain holder A with ``quantizer`` and ``chain`` the
+    nodes behind it that belong to the operation with it (the further activations of a table; none for an upsample); the plan is
+    that of the module ``build(out_quantizer)`` if all the readers of the last node agree on one code form F and read codes.  Its
+    one user may be a plain holder B (F is B's form; B goes into ``gone`` with the chain and the node is named ``<B's name><suffix>``),
+    whose users are then the readers; without a B the last node's own users are, and F is A's form (``copies``: the module then
+    copies codes, ``build(None)``) unless a reader below says otherwise; without ``copies`` a reader below has to say.  A reader is
+    a wrapped layer ``consumer_for`` can take, fed by it alone (a QuantizedLinear only with ``rows``); with ``pools`` a max pool
+    that can run on codes (``_pool_plan``); or a QuantizedConcat / QuantizedMul that reads it at exactly one operand, in the form
+    F -- what the concatenation and multiply passes leave where they absorbed B.  Else None: a float32 reader, anything else
+    between the operation and B, forms that differ."""
+    last = chain[-1] if chain else first
+    if not last.users:
         return None
-    src, gone, name, out_quantizer = node, [], None, None
-    if len(node.users) == 1:
-        nxt = next(iter(node.users))
+    src, gone, name, out_quantizer = last, list(chain), None, None
+    if len(last.users) == 1:
+        nxt = next(iter(last.users))
         holder = _holder_of(nxt, mods)
-        if holder is not None and nxt.args == (node,):
+        if holder is not None and nxt.args == (last,):
             if not nxt.users:
                 return None
-            src, gone, name, out_quantizer = nxt, [nxt], nxt.target.replace(".", "_") + "_upsample", holder.activation_holder_quantizer
+            src, gone, name, out_quantizer = nxt, gone + [nxt], nxt.target.replace(".", "_") + suffix, holder.activation_holder_quantizer
     try:
         form = _code_form(quantizer if out_quantizer is None else out_quantizer)
     except (TypeError, ValueError, NotImplementedError):
@@ -1655,17 +1757,19 @@ def _upsample_plan(node, mods, quantizer, consumer_for, pools: bool = False):
             return None
         at = next(i for i, a in enumerate(user.args) if a is src)
         operands.append((user, m.operand_quantizers[at], m.operand_code_params(at)))
-    if not gone and operands and operands[0][2] != form:     # no B, and not A's form: F is what the operand is read as
+    if src is last and operands and (not copies or operands[0][2] != form):   # no B: F is what the operand is read as
         if others:
             return None                                      # (a layer or a pool would read A's form)
         out_quantizer, form = operands[0][1:]
+    if out_quantizer is None and not copies:
+        return None                                          # (no B and no operand that supplies the form)
     if any(f != form for _, _, f in operands):
         return None
     reads_as = quantizer if out_quantizer is None else out_quantizer
     taken, pooled = [], []
     for user in others:
         fused = _wrapped_consumer(user, src, mods, reads_as, consumer_for)
-        if fused is not None and type(fused) is not QuantizedLinear:
+        if fused is not None and (rows or type(fused) is not QuantizedLinear):
             taken.append((user, fused))
             continue
         behind = _pool_plan(user, mods, reads_as, consumer_for) if fused is None and pools else None
@@ -1674,10 +1778,102 @@ def _upsample_plan(node, mods, quantizer, consumer_for, pools: bool = False):
         pooled.append((user, behind))
     readers = [user for user, _, _ in operands]
     try:
-        module = QuantizedUpsample(up, quantizer, out_quantizer)
+        module = build(out_quantizer)
     except (TypeError, ValueError, NotImplementedError):
         return None
-    return _PoolPlan(module, "_upsample", taken, gone, name, tuple(pooled), tuple(readers))
+    return _PoolPlan(module, suffix, taken, gone, name, tuple(pooled), tuple(readers))
+
+
+def _upsample_plan(node, mods, quantizer, consumer_for, pools: bool = False):
+    """``node`` a user of a plain holder A with ``quantizer``: the plan of a QuantizedUpsample if it is a nearest upsample of A's
+    output (``_upsample_of``) all of whose readers agree on one code form F and read codes (``_between_holders_plan``: through a
+    plain holder B or directly, then in A's form or a QuantizedConcat / QuantizedMul operand's; never a QuantizedLinear).  Else
+    None: a float32 reader, an activation between the upsample and B, forms that differ."""
+    up = _upsample_of(node, mods)
+    if up is None:
+        return None
+    return _between_holders_plan(node, [], mods, quantizer, consumer_for, pools, lambda out: QuantizedUpsample(up, quantizer, out),
+                                 "_upsample", copies=True, rows=False)
+
+
+def _activation_functions():
+    """Functional spelling -> (module type, the constant arguments it may be given, in positional order)."""
+    F = torch.nn.functional
+    return {torch.sigmoid: (nn.Sigmoid, ()), F.sigmoid: (nn.Sigmoid, ()), torch.tanh: (nn.Tanh, ()), F.tanh: (nn.Tanh, ()),
+            torch.relu: (nn.ReLU, ()), F.relu: (nn.ReLU, ("inplace",)), F.silu: (nn.SiLU, ("inplace",)),
+            F.gelu: (nn.GELU, ("approximate",)), F.mish: (nn.Mish, ("inplace",)), F.softplus: (nn.Softplus, ("beta", "threshold")),
+            F.elu: (nn.ELU, ("alpha", "inplace")), F.celu: (nn.CELU, ("alpha", "inplace")), F.selu: (nn.SELU, ("inplace",)),
+            F.leaky_relu: (nn.LeakyReLU, ("negative_slope", "inplace")), F.hardswish: (nn.Hardswish, ("inplace",)),
+            F.hardsigmoid: (nn.Hardsigmoid, ("inplace",)), F.hardtanh: (nn.Hardtanh, ("min_val", "max_val", "inplace")),
+            F.relu6: (nn.ReLU6, ("inplace",)), F.logsigmoid: (nn.LogSigmoid, ()), F.softsign: (nn.Softsign, ()),
+            F.tanhshrink: (nn.Tanhshrink, ())}
+
+
+_ACTIVATION_METHODS = {"sigmoid": nn.Sigmoid, "tanh": nn.Tanh, "relu": nn.ReLU}
+
+
+def _activation_of(node, mods):
+    """The activation module that ``node`` applies to its one tensor operand, if QuantizedActivationTable can take it: a call of
+    a module of one of its types, the functional spelling with constant arguments (``torch.sigmoid`` / ``torch.tanh`` /
+    ``torch.relu`` and the ``F.*`` counterparts of the types), for which a module is built, or ``x.sigmoid()`` / ``x.tanh()`` /
+    ``x.relu()``.  In-place forms only where nobody else looks at the input (``_in_place_ok``).  Else None."""
+    from torch.fx import Node
+    if not node.args or not isinstance(node.args[0], Node):
+        return None
+    fn, inplace = None, False
+    if node.op == "call_module":
+        if len(node.args) == 1 and not node.kwargs:
+            fn = mods.get(node.target)
+            inplace = getattr(fn, "inplace", False)
+    elif node.op == "call_function":
+        found = _activation_functions().get(node.target)
+        given = _const_args(node, found[1]) if found is not None else None
+        if given is None:
+            return None
+        inplace = given.pop("inplace", False)
+        if not all(isinstance(v, (int, float, str)) and not isinstance(v, bool) for v in given.values()):
+            return None
+        try:
+            fn = found[0](**given)
+        except (TypeError, ValueError):
+            return None
+    elif node.op == "call_method" and node.target in _ACTIVATION_METHODS and len(node.args) == 1 and not node.kwargs:
+        fn = _ACTIVATION_METHODS[node.target]()
+    if fn is None or not QuantizedActivationTable.eligible(fn):
+        return None
+    if not isinstance(inplace, bool) or not _in_place_ok(node, inplace):
+        return None
+    return fn
+
+
+def _table_chain(node, mods):
+    """``([nodes], [modules])`` of the run of 1 to 4 elementwise activations (``_activation_of``) that starts at ``node``, each but
+    the last with the next as its one user; None if ``node`` is no such activation or the run is longer."""
+    nodes, fns = [], []
+    while True:
+        fn = _activation_of(node, mods)
+        if fn is None:
+            break
+        nodes.append(node)
+        fns.append(fn)
+        if len(node.users) != 1:
+            break
+        node = next(iter(node.users))
+    return (nodes, fns) if 1 <= len(nodes) <= _TABLE_CHAIN_MAX else None
+
+
+def _table_plan(node, mods, quantizer, consumer_for, pools: bool = False):
+    """``node`` a user of a plain holder A with ``quantizer``: the plan of a QuantizedActivationTable if it starts a run of 1 to 4
+    elementwise activations of A's output (``_table_chain``) whose readers agree on one code form F and read codes
+    (``_between_holders_plan``): the run's one user a plain holder B, every user of which reads codes in B's form, or without a B
+    a QuantizedConcat / QuantizedMul operand that supplies the form.  Else None: no B and no such operand, a float32 reader of the
+    run or of B, anything not eligible in the run, a node of it with two tensor operands or a scalar one."""
+    found = _table_chain(node, mods)
+    if found is None:
+        return None
+    nodes, fns = found
+    return _between_holders_plan(node, nodes[1:], mods, quantizer, consumer_for, pools,
+                                 lambda out: QuantizedActivationTable(fns, quantizer, out), "_table", copies=False, rows=True)
 
 
 class QuantizedJoin(_OnCodes):
@@ -1783,7 +1979,8 @@ def _mul_operands(node):
     return _binary_operands(node, (operator.mul, operator.imul, torch.mul, torch.multiply), ("mul", "multiply"), operator.imul)
 
 
-def _join_shared_holders(gm, mods, consumer_for, pools: bool = False, avg_pools: bool = False, upsamples: bool = False) -> int:
+def _join_shared_holders(gm, mods, consumer_for, pools: bool = False, avg_pools: bool = False, upsamples: bool = False,
+                         activation_tables: bool = False) -> int:
     """``fuse_linear_consumers_fx(shared_holders=True)``: every plain holder with wrapped layers among its users that
     ``consumer_for(wrapper, quantizer)`` can take becomes a QuantizedJoin, unless it is a lone holder -> layer pair with
     nothing in front to absorb (the pair rewrite's).  With ``pools`` a max pool among the users that can run on codes
@@ -1792,19 +1989,22 @@ def _join_shared_holders(gm, mods, consumer_for, pools: bool = False, avg_pools:
     in front of a second holder (``_avg_pool_plan``), as a QuantizedAvgPool2d.  A QuantizedMul among the users
     (``_operator_between_holders``, which built it with this holder's quantizer at that operand) reads the join's codes too, at
     whichever operand position the holder occupies.  With ``upsamples`` a nearest upsample among the users whose readers all read
-    codes (``_upsample_plan``) does so as a QuantizedUpsample, and the holder behind such an upsample is left to that plan.
+    codes (``_upsample_plan``) does so as a QuantizedUpsample, and the holder behind such an upsample is left to that plan; with
+    ``activation_tables`` likewise a run of elementwise activations (``_table_plan``), as a QuantizedActivationTable.
     Returns the number of wrapped layers replaced."""
     replaced = 0
     for node, holder in _holder_calls(gm, mods):
-        if upsamples and node.users and _behind_planned_upsample(node, mods, consumer_for, pools):
+        if (upsamples or activation_tables) and node.users and \
+                _behind_planned_operation(node, mods, consumer_for, pools, upsamples, activation_tables):
             continue
         quantizer = holder.activation_holder_quantizer
         # F: (user node, its consumer)
         taken = [(user, _wrapped_consumer(user, node, mods, quantizer, consumer_for)) for user in node.users]
         taken = [(user, fused) for user, fused in taken if fused is not None]
         pooled = []                                          # P: (pool node, its plan)
-        if pools or avg_pools or upsamples:
-            plans = ((user, _any_pool_plan(user, mods, quantizer, consumer_for, pools, avg_pools, upsamples)) for user in node.users)
+        if pools or avg_pools or upsamples or activation_tables:
+            plans = ((user, _any_pool_plan(user, mods, quantizer, consumer_for, pools, avg_pools, upsamples, activation_tables))
+                     for user in node.users)
             pooled = [(user, plan) for user, plan in plans if plan is not None]
         # M: the QuantizedMul nodes of ``_operator_between_holders`` that read this holder (built with its quantizer at those operands)
         muls = [user for user in node.users if isinstance(_module_of(user, mods), QuantizedMul) and not user.kwargs]
@@ -1846,37 +2046,55 @@ def _join_shared_holders(gm, mods, consumer_for, pools: bool = False, avg_pools:
     return replaced
 
 
-def _any_pool_plan(node, mods, quantizer, consumer_for, pools: bool, avg_pools: bool, upsamples: bool = False):
+def _any_pool_plan(node, mods, quantizer, consumer_for, pools: bool, avg_pools: bool, upsamples: bool = False,
+                   activation_tables: bool = False):
     """``_pool_plan`` (with ``pools``), or else ``_avg_pool_plan`` (with ``avg_pools``), or else ``_upsample_plan`` (with
-    ``upsamples``) of ``node``, or None."""
+    ``upsamples``), or else ``_table_plan`` (with ``activation_tables``) of ``node``, or None."""
     plan = _pool_plan(node, mods, quantizer, consumer_for) if pools else None
     if plan is None and avg_pools:
         plan = _avg_pool_plan(node, mods, quantizer, consumer_for)
     if plan is None and upsamples:
         plan = _upsample_plan(node, mods, quantizer, consumer_for, pools)
+    if plan is None and activation_tables:
+        plan = _table_plan(node, mods, quantizer, consumer_for, pools)
     return plan
 
 
-def _behind_planned_upsample(node, mods, consumer_for, pools: bool) -> bool:
-    """``node``, a plain holder's call, is the second holder of an upsample that will run on codes (``_upsample_plan`` of its
-    argument, a user of another plain holder): it belongs to that plan, whatever the number of its users."""
-    up = node.args[0]
-    first = _holder_of(up.args[0], mods) if _upsample_of(up, mods) is not None else None
-    return first is not None and _upsample_plan(up, mods, first.activation_holder_quantizer, consumer_for, pools) is not None
+def _behind_planned_operation(node, mods, consumer_for, pools: bool, upsamples: bool, activation_tables: bool) -> bool:
+    """``node``, a plain holder's call, is the second holder of an upsample or of a run of activations that will run on codes
+    (``_upsample_plan`` / ``_table_plan`` of the user of another plain holder that leads to it): it belongs to that plan, whatever
+    the number of its users."""
+    from torch.fx import Node
+    first = node.args[0]
+    for _ in range(_TABLE_CHAIN_MAX if activation_tables else 1):
+        if not first.args or not isinstance(first.args[0], Node):
+            return False
+        holder = _holder_of(first.args[0], mods)
+        if holder is not None:                               # ``first`` is the user of a holder A that leads here
+            quantizer = holder.activation_holder_quantizer
+            plan = _upsample_plan(first, mods, quantizer, consumer_for, pools) if upsamples else None
+            if plan is None and activation_tables:
+                plan = _table_plan(first, mods, quantizer, consumer_for, pools)
+            return plan is not None and node in plan.gone
+        first = first.args[0]
+    return False
 
 
-def _pool_lone_holders(gm, mods, consumer_for, pools: bool = True, avg_pools: bool = False, upsamples: bool = False) -> int:
+def _pool_lone_holders(gm, mods, consumer_for, pools: bool = True, avg_pools: bool = False, upsamples: bool = False,
+                       activation_tables: bool = False) -> int:
     """``fuse_linear_consumers_fx(pools=True)``, the pair: a plain holder whose only user is a max pool that can run on codes
     (``_pool_plan``) leaves the graph, the QuantizedMaxPool2d that replaces the pool quantizes the holder's input itself.
     With ``avg_pools`` likewise for an average pool in front of a second holder (``_avg_pool_plan``) and its QuantizedAvgPool2d,
-    with ``upsamples`` for a nearest upsample (``_upsample_plan``) and its QuantizedUpsample.
+    with ``upsamples`` for a nearest upsample (``_upsample_plan``) and its QuantizedUpsample, with ``activation_tables`` for a run
+    of elementwise activations (``_table_plan``) and its QuantizedActivationTable.
     Returns the number of wrapped layers replaced."""
     replaced = 0
     for node, holder in _holder_calls(gm, mods):
         if len(node.users) != 1:
             continue
         user = next(iter(node.users))
-        plan = _any_pool_plan(user, mods, holder.activation_holder_quantizer, consumer_for, pools, avg_pools, upsamples)
+        plan = _any_pool_plan(user, mods, holder.activation_holder_quantizer, consumer_for, pools, avg_pools, upsamples,
+                              activation_tables)
         if plan is None:
             continue
         replaced += _install_pool(gm, mods, user, plan, node.args[0])
@@ -2186,7 +2404,8 @@ def _fuse_residuals_into_producers(gm, mods) -> int:
 
 def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights: bool = False,
                           convolutions: bool = False, depthwise: bool = False, pools: bool = False,
-                          avg_pools: bool = False, upsamples: bool = False, any_channels: bool = False) -> int:
+                          avg_pools: bool = False, upsamples: bool = False, any_channels: bool = False,
+                          activation_tables: bool = False) -> int:
     """In every ``nn.Sequential`` of ``model``: an activation holder directly followed by a wrapped ``nn.Linear`` with
     a symmetric, power-of-two or LUT weights quantizer (int8 codebook values, at most 256 entries) becomes (Identity,
     QuantizedLinear); a wrapped pointwise ``nn.Conv2d`` likewise becomes a QuantizedConv1x1.  Returns the number of pairs
@@ -2244,7 +2463,15 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
     product over K columns, weight zero points included.  It needs the activation zero point inside its clamp domain; pairs
     without are left alone.  Layers with K % 16 == 0 become the consumers they become without the switch; depthwise convolutions
     and the pools, concatenations, multiplies and upsamples on codes keep their own conditions.  By default such pairs are left
-    alone: at the launch floor the re-pitch launch of a small pointwise layer can cost what the rewrite saves."""
+    alone: at the launch floor the re-pitch launch of a small pointwise layer can cost what the rewrite saves.
+
+    ``activation_tables=True`` (composes with every other switch) also takes (holder A, one elementwise activation module
+    ``QuantizedActivationTable.eligible`` accepts -- ``nn.Sigmoid``, ``SiLU``, ``GELU``, ``Tanh``, ``LeakyReLU``, ... -- holder B, wrapped layer
+    the consumer can take): it becomes (Identity, QuantizedActivationTable, Identity, consumer), the activation and B running as one
+    launch on A's codes (``mctq_codes_table``: B's code of ``f`` as a 256-entry byte table, built by the replaced call on A's 256
+    values) and the consumer taking B's codes.  With ``chain=True`` a consumer in front emits A's codes.  Counted as one pair.  The
+    table is the definition: bit for bit the float32 chain on the GPU, within one code next to a rounding tie on the CPU
+    (``QuantizedActivationTable``)."""
     replaced = 0
     for seq in [m for m in model.modules() if isinstance(m, nn.Sequential)]:
         for i in range(len(seq) - 3 if avg_pools else 0):
@@ -2288,6 +2515,20 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
                 seq[i + 2] = _FusedAway()
             seq[i + 2 if second is None else i + 3] = fused
             replaced += 1
+        for i in range(len(seq) - 3 if activation_tables else 0):
+            holder, fn, second, wrapper = seq[i], seq[i + 1], seq[i + 2], seq[i + 3]
+            if not _plain_holder(holder) or not _plain_holder(second) or not QuantizedActivationTable.eligible(fn) \
+                    or not isinstance(wrapper, PytorchQuantizationWrapper):
+                continue
+            fused = _consumer_for(wrapper, second.activation_holder_quantizer, uniform_weights, convolutions, depthwise, any_channels)
+            if fused is None:
+                continue
+            try:
+                table = QuantizedActivationTable(fn, holder.activation_holder_quantizer, second.activation_holder_quantizer)
+            except (TypeError, ValueError, NotImplementedError):
+                continue
+            seq[i], seq[i + 1], seq[i + 2], seq[i + 3] = _FusedAway(), table, _FusedAway(), fused
+            replaced += 1
         for i in range(len(seq) - 2 if pools else 0):
             holder, pool, wrapper = seq[i], seq[i + 1], seq[i + 2]
             if not _plain_holder(holder) or not QuantizedMaxPool2d.eligible(pool) or not isinstance(wrapper, PytorchQuantizationWrapper):
@@ -2323,7 +2564,8 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
                              convolutions: bool = False, depthwise: bool = False, shared_holders: bool = False,
                              stay_on_codes: bool = False, pools: bool = False, fused_residuals: bool = False,
                              concats: bool = False, avg_pools: bool = False, muls: bool = False,
-                             hard_activations: bool = False, upsamples: bool = False, any_channels: bool = False):
+                             hard_activations: bool = False, upsamples: bool = False, any_channels: bool = False,
+                             activation_tables: bool = False):
     """The same rewrite on an arbitrary module graph (MCT-exported models are not ``nn.Sequential``): traces ``model``
     with torch.fx keeping wrappers and holders as leaves, and wherever an activation holder's ONLY consumer is a
     wrapped ``nn.Linear`` the integer consumer can take (symmetric, power-of-two or LUT weights, and with
@@ -2459,7 +2701,7 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
     alone: producers the entry points do not take (a product with uniform, 4-bit or LUT weights or one that already takes a
     residual; the depthwise convolution takes every weight kind); a holder with a float32 reader; an activation whose input
     has other users; two activations in a row (a join that absorbed a ReLU behind the Hardswish); sigmoid, SiLU, GELU, tanh,
-    which no epilogue can reproduce bit for bit.  The kernels evaluate the float32 expression of ATen's GPU kernels,
+    which no epilogue can reproduce bit for bit (between two holders they run as a byte table: ``activation_tables=True``, below).  The kernels evaluate the float32 expression of ATen's GPU kernels,
     ``x * min(max(x + 3, 0), 6) * (1.0f / 6.0f)``, equal to them for every float32 bit pattern, on the same float32 value the
     consumer would have written, so on the GPU the result is bit for bit that of the same rewrite without the switch, NaNs
     and infinities included.  On the CPU the consumers apply ``F.hardswish`` / ``F.hardsigmoid`` (ATen's CPU kernels divide by 6:
@@ -2506,7 +2748,37 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
     with the code 0 and re-pitches its activation codes to ``Kp = 16 * ceil(K / 16)`` columns (``mctq_codes_im2col_pad_nhwc``), which
     leaves the integer sum as it is; everything a consumer can emit -- codes, folded clamps, activations, residuals -- works
     unchanged.  It needs the activation zero point inside its clamp domain.  Depthwise convolutions keep ``in_channels % 16 == 0``,
-    and the pools, concatenations, multiplies and upsamples on codes keep their torch routes for such channel counts."""
+    and the pools, concatenations, multiplies and upsamples on codes keep their torch routes for such channel counts.
+
+    ``activation_tables=True`` (needs no other switch and composes with all of them) keeps the elementwise activations between two
+    holders on codes, the smooth ones included: EfficientNet- and YOLO-style conv -> holder -> SiLU -> holder -> conv, GELU blocks,
+    sigmoid gates, LeakyReLU necks.  The candidate is a plain holder A one of whose users starts a run of 1 to 4 eligible nodes, each
+    with one tensor operand and (but for the last) the next as its one user, behind which stands a plain holder B.  Eligible
+    (``QuantizedActivationTable.eligible``) are calls of modules of exactly the types ``nn.Sigmoid``, ``Tanh``, ``SiLU``, ``GELU`` (both
+    approximations), ``Mish``, ``Softplus``, ``ELU``, ``CELU``, ``SELU``, ``LeakyReLU``, ``Hardswish``, ``Hardsigmoid``, ``Hardtanh``, ``ReLU``,
+    ``ReLU6``, ``LogSigmoid``, ``Softsign``, ``Tanhshrink``, and the functional and method spellings with constant arguments, which are
+    mapped onto such a module: ``torch.sigmoid``, ``torch.tanh``, ``torch.relu``, the ``F.*`` counterparts of the types, ``x.sigmoid()``,
+    ``x.tanh()``, ``x.relu()``; in-place forms only where nobody else reads the input.  B's users must all read codes in B's form: wrapped
+    layers the consumer can take under the other switches, fed by B alone; with ``pools=True`` max pools that can run on codes; or
+    the QuantizedConcat / QuantizedMul operand that absorbed B (``concats`` / ``muls``, which run first), which then supplies the
+    form.  The run and B become one QuantizedActivationTable node named ``<B's name>_table`` (``mctq_codes_table``: ``out[i] =
+    table[in[i]]``, 1 byte read and 1 written per element, any element and channel count) whose ``fn`` is the run in order, and the
+    users consumers and pools of its codes, counted in the returned total.  Holder A is treated as for ``pools``: read by the run alone
+    with nothing in front to absorb it leaves the graph and the module quantizes its input; with ``shared_holders=True`` a join in
+    A's place hands the node its codes; with ``stay_on_codes=True`` the node is a reader of A's codes, so that conv -> [ReLU / ReLU6 /
+    Hardtanh] -> A -> f -> B -> conv runs codes to codes.  Tables are built on first use per device, with a few tiny launches and no
+    host read: a hipGraph capture needs one warm-up forward first, as ``capture_forward`` makes.  Left alone: no B (except behind such
+    an operand); a float32 user of ``f`` or of B; anything not eligible in the run -- learnable or per-channel state (``PReLU``),
+    random or mode-dependent (``RReLU``, dropout), across elements (softmax, GLU) -- or more than four nodes; a node with two tensor
+    operands (``x * sigmoid(x)`` written out); a scalar operand; a quantizer wider than 8 bits.  The exactness contract: the table is
+    the definition -- B's code of ``f`` evaluated on A's [256] values by the replaced call on the tensor's device.  On the GPU ATen's
+    elementwise kernels apply one scalar functor per element whatever its position, shape or layout, so the node's codes are bit for
+    bit those of the float32 chain A -> f -> B on that GPU and the model returns what the same rewrite without the switch returns
+    (tests/test_gpu_table_consumer.py checks every accepted function with strict equality; one that failed would leave the list).
+    On the CPU ATen's vector body and scalar tail give different last bits for sigmoid, SiLU, softplus, ELU, Mish, tanh and GELU
+    (0.007 - 0.08 % of elements, erf-GELU 2.6 %): there the node equals the chain wherever the chain's float32 value equals the
+    table's and can differ by one code next to a rounding tie elsewhere.  Out of scope: looking the table up inside the producing
+    consumer's epilogue (``emit_table``, beside ``emit_act``), which would remove the launch."""
     import torch.fx as fx
     if stay_on_codes and not shared_holders:
         raise ValueError("stay_on_codes=True needs shared_holders=True")
@@ -2533,9 +2805,9 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
         replaced += _operator_between_holders(gm, mods, consumer_for, pools, _mul_operands, QuantizedMul, "_mul")
     # (an upsample's plan is made where a pool's is, in these two passes: it sees the QuantizedConcat / QuantizedMul nodes above)
     if shared_holders:
-        replaced += _join_shared_holders(gm, mods, consumer_for, pools, avg_pools, upsamples)
-    if pools or avg_pools or upsamples:
-        replaced += _pool_lone_holders(gm, mods, consumer_for, pools, avg_pools, upsamples)
+        replaced += _join_shared_holders(gm, mods, consumer_for, pools, avg_pools, upsamples, activation_tables)
+    if pools or avg_pools or upsamples or activation_tables:
+        replaced += _pool_lone_holders(gm, mods, consumer_for, pools, avg_pools, upsamples, activation_tables)
     for src, holder in _holder_calls(gm, mods):              # the pair: a holder whose only user is a wrapped layer
         if len(src.users) != 1:
             continue

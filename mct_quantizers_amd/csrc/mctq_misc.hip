@@ -27,6 +27,7 @@ int g_ql_rot = 0;            // tiled consumer kernel: blocks that share a weigh
 int g_avgpool_form = 0;      // mctq_codes_avgpool_nhwc: 0 = the launcher chooses, 1 = lane form, 2 = split form (the result is the same)
 int g_concat_copy = 1;       // mctq_codes_concat_nhwc, mctq_codes_upsample_nhwc: operands in the output's own form are copied, not requantized (0: never; the result is the same)
 int g_im2col_grain = 0;      // mctq_codes_im2col_pad_nhwc: bytes per load piece, 0 = by rule (4 where channels % 4 == 0, else 1), 1, 4 (the result is the same)
+int g_table_chunks = 4;      // mctq_codes_table: 16-byte chunks per lane, 1, 2 or 4 (the result is the same)
 int g_upsample_form = 0;     // mctq_codes_upsample_nhwc: 0 = the launcher chooses (replicate for integer factors of 2 .. 16 outputs per input), 1 = gather form, 2 = replicate form where eligible (the result is the same)
 
 static const char* launch_log_path() {
@@ -227,6 +228,11 @@ int mctq_set_tuning(const char* key, int32_t value) {
   if (!strcmp(key, "upsample_form")) {
     if (value < 0 || value > 2) return fail_arg("upsample_form must be 0 (auto), 1 (gather) or 2 (replicate)");
     g_upsample_form = value;
+    return 0;
+  }
+  if (!strcmp(key, "table_chunks")) {
+    if (value != 1 && value != 2 && value != 4) return fail_arg("table_chunks must be 1, 2 or 4");
+    g_table_chunks = value;
     return 0;
   }
   if (!strcmp(key, "im2col_grain")) {

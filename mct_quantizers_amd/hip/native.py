@@ -161,6 +161,8 @@ SIGNATURES = {
     "mctq_codes_upsample_nhwc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float]  # codes, out, type, zero point, scale
                                  + [ctypes.c_int64] * 6 + [ctypes.c_int32] * 2 + [ctypes.c_void_p] * 2     # B, H, W, C, Ho, Wo; factors; src_rows, src_cols
                                  + [ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),  # output form; stream
+    "mctq_codes_table": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,    # in, its type, out, its type, n
+                                        ctypes.c_void_p, ctypes.c_void_p]),                                             # table, stream
     "mctq_qconv_dw_i8": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,   # a_codes, type, zero point, scale
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,  # w_codes, w_scales, w_zero_points, bias
                                         ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_int32,

@@ -914,6 +914,64 @@ def codes_upsample(codes_nhwc, in_form, out_form, src_rows, src_cols, factors=No
         return fq_codes(dequantize_codes(moved, a_scale, a_zp), None, None, None, qmin, qmax, o_scale, o_zp).contiguous()
 
 
+def code_table(fn, in_form, out_form, device):
+    """The byte table of an elementwise function between two holders: ``fn`` applied to the output of a holder A of the form
+    ``in_form = (scale, zero_point, qmin, qmax)`` and coded by a holder B of ``out_form`` (likewise), as a uint8 tensor [256] on
+    ``device`` indexed by the RAW byte of A's code (an int8 code c at entry ``c & 0xff``) and holding the raw byte of B's code.
+    A's float32 output is ``dequantize_codes`` of its codes bit for bit, so it takes at most 256 values; the table is
+
+        fq_codes(fn(dequantize_codes(arange(256, uint8).view(A's type), s_a, z_a)), None, None, None, qmin_b, qmax_b, s_b, z_b)
+
+    -- the replaced call itself, run on ``device`` on a fresh copy of the 256 values under ``no_grad``, and B's own coding
+    function, so that NaN and infinite results are coded exactly as B codes them.  The table is the definition of the node that
+    applies it (``codes_table``).  TypeError if ``fn`` does not return a float32 tensor of shape [256]."""
+    a_scale, a_zp, a_qmin, a_qmax, a_tdt, _ = _out_form(in_form)
+    o_scale, o_zp, qmin, qmax, tdt, _ = _out_form(out_form)
+    _check_form("code_table", a_tdt, a_zp, a_scale, "the input's zero point {}", "the input's scale")
+    _check_form("code_table", tdt, o_zp, o_scale, "the output's zero point {}", "the output's scale")
+    device = torch.device(device)
+    if device.type == "cpu":
+        _cpu_route_allowed()
+    with torch.no_grad():
+        raw = torch.arange(256, dtype=torch.int16, device=device).to(torch.uint8)
+        x = dequantize_codes(raw.view(a_tdt), a_scale, a_zp)
+        y = fn(x.clone())
+        if not isinstance(y, torch.Tensor) or y.dtype != torch.float32 or tuple(y.shape) != (256,):
+            got = f"{y.dtype} {tuple(y.shape)}" if isinstance(y, torch.Tensor) else type(y).__name__
+            raise TypeError(f"code_table: fn must return a float32 tensor of shape [256], got {got}")
+        codes = fq_codes(y.to(device).contiguous(), None, None, None, qmin, qmax, o_scale, o_zp)
+        return codes.view(torch.uint8).contiguous()
+
+
+def codes_table(codes, table, out_dtype):
+    """``table[raw byte of codes]`` as codes of ``out_dtype`` (torch.int8 / torch.uint8): an elementwise function between two
+    holders applied to int8 / uint8 ``codes`` of any shape through its byte table (``code_table``; uint8 [256] on the codes'
+    device).  The result has the codes' shape and, for dense tensors, their strides.  GPU tensors take one launch of
+    mctq_codes_table over the storage (1 byte read and 1 written per element; any element count, no channel rule); a GPU tensor
+    that is not dense, or whose first byte is not 16-byte aligned, is compacted first.  CPU tensors take
+    ``table[codes.view(uint8).long()].view(out_dtype)``: the same bytes."""
+    if not _is_codes(codes):
+        raise TypeError("codes_table takes int8 / uint8 codes")
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.uint8 or tuple(table.shape) != (256,):
+        raise TypeError("codes_table: the table must be a uint8 tensor of shape [256]")
+    if out_dtype not in (torch.int8, torch.uint8):
+        raise TypeError(f"codes_table: out_dtype must be torch.int8 or torch.uint8, got {out_dtype}")
+    if table.device != codes.device:
+        raise RuntimeError(f"codes_table: the table must be on the codes' device, got {table.device} and {codes.device}")
+    if codes.is_cuda:
+        x = codes if _is_dense(codes) else codes.contiguous()
+        if x.data_ptr() % 16:
+            x = x.clone()                                       # (preserve_format: a dense tensor keeps its strides)
+        y = torch.empty_like(x, dtype=out_dtype)
+        t = _contiguous(table)                                  # named: it must outlive the launch
+        if x.numel():
+            _gpu_call("mctq_codes_table", x, x.data_ptr(), _code_of(x), y.data_ptr(),
+                      native.CODE_U8 if out_dtype == torch.uint8 else native.CODE_I8, x.numel(), t.data_ptr())
+        return y
+    _cpu_route_allowed()
+    return table[codes.view(torch.uint8).long()].view(out_dtype)
+
+
 def codes_mul(a, g, out_form, gate_form=None):
     """``torch.mul`` of two holder outputs on activation codes, in the form of the holder behind it.  ``a = (codes, scale,
     zero_point)``, int8 / uint8 codes ``[.., C]`` (channels last); ``g = (tensor, scale, zero_point)``, codes likewise or, with
