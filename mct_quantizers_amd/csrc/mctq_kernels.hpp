@@ -638,6 +638,16 @@ struct LutCellsOp : LutCommon {
   typedef LutCellsBook Book;
   __device__ __forceinline__ uint32_t book_words() const { return ((uint32_t)n_words + 3u) & ~3u; }
 
+  // The cell index sits BEHIND the list and LutStepsOp reads the first 2 P + 2 words only: the same buffer, the same
+  // results, a book of 8 P + 8 bytes.  launch_channels takes it where the parameter window does not fit beside this book.
+  __host__ LutStepsOp lean() const {
+    LutStepsOp op;
+    static_cast<LutCommon&>(op) = static_cast<const LutCommon&>(*this);
+    op.steps = steps; op.P = P;
+    return op;
+  }
+  __host__ size_t lean_bytes() const { return (size_t)((2 * P + 2 + 3) & ~3) * sizeof(float); }
+
   __device__ __forceinline__ Book setup(float* lds) const {
     for (int j = threadIdx.x; j < n_words; j += kThreads) lds[j] = steps[j];
     __syncthreads();
@@ -701,6 +711,12 @@ template <class Op, class = void>
 struct HasTile : std::false_type {};
 template <class Op>
 struct HasTile<Op, std::void_t<decltype(&Op::template tile<true, 4>)>> : std::true_type {};
+
+// an op whose book may leave no room for the smallest parameter window names a form of itself with a smaller book
+template <class Op, class = void>
+struct HasLean : std::false_type {};
+template <class Op>
+struct HasLean<Op, std::void_t<decltype(&Op::lean)>> : std::true_type {};
 
 template <class Op, class = void>
 struct HasPrefetch : std::false_type {};
@@ -1729,7 +1745,10 @@ static int launch_channels(const Op& op, const void* xv, void* yv, int64_t outer
   if (inner > 0x7fffffffLL || channels > 0x7fffffffLL) return fail_arg("inner/channels exceed 2^31-1");
   const uint32_t V = vec_ok ? io::N : 1;
   // lane-vectors per lane: 4, or ONE when the parameter window of a 4-wide tile would not fit LDS (tiny inner with many
-  // channels and a large codebook).  Unaligned tensors (one element per lane access) always fit with 4.
+  // channels and a large codebook).  The one-vector tile of a float32 OUTPUT and the tile of an unaligned tensor (one element per
+  // lane access, 4 per lane) are both 1024 elements: up to 1025 staged rows of 16 bytes.  That fits beside every book but the
+  // threshold list with a cell index of 1025 ... 2048 centres (49 184 bytes: room for 1021 rows); such a launch runs the op's
+  // lean form instead (LutCellsOp::lean: the binary search over the list alone, 16 KiB), for either alignment.
   int wu = 4;
   uint32_t tile = 0, stride = 0;
   size_t lds = 0;
@@ -1741,7 +1760,12 @@ static int launch_channels(const Op& op, const void* xv, void* yv, int64_t outer
     lds = book_bytes + (size_t)stride * Op::kWords * sizeof(float);
     if (lds <= 64 * 1024 || wu == 1 || !vec_ok) break;
   }
-  if (lds > 64 * 1024) return fail_arg("parameter window exceeds 64 KiB of LDS");
+  if (lds > 64 * 1024) {
+    if constexpr (HasLean<Op>::value)
+      return launch_channels<TI, TO>(op.lean(), xv, yv, outer, channels, inner, op.lean_bytes(), st);
+    else
+      return fail_arg("parameter window exceeds 64 KiB of LDS");
+  }
   const int64_t blocks = (n + tile - 1) / tile;
   if (blocks > 0x7fffffffLL) return fail_arg("tensor too large for one launch");
   const bool idx32 = n <= (int64_t)0xffffffffLL - (int64_t)tile;

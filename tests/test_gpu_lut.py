@@ -316,7 +316,7 @@ def test_half_activation_lut_clip_bounds_follow_the_tensor_type(lib):
         kw = c["kwargs"]
         assert bits_equal(y32.cpu().numpy(), O.lut_quantize(x32, kw["lut_values"], kw["threshold"][0], kw["signed"],
                                                             kw["lut_values_bitwidth"], 1e-8))
-    assert kinds <= {"LutTableOp", "LutCompactOp", "LutStepsOp", "LutCellsOp"} and kinds, kinds
+    assert kinds <= {"LutTableOp", "LutStepsOp", "LutCellsOp"} and kinds, kinds
 
 
 def test_lut_quantizers_follow_attribute_assignment(lib):
