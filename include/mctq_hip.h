@@ -93,6 +93,9 @@ extern "C" {
 /* v10 (additive, the version number stays): + mctq_codes_table, an elementwise function between two activation holders as a
  * 256-entry byte table on codes (sigmoid, SiLU, GELU, tanh and the other smooth activations stay on codes), + tuning key
  * "table_chunks"; no existing signature or result changed. */
+/* v10 (additive, the version number stays): + mctq_qconv_grouped_i8, the grouped convolution on NHWC activation codes as a direct
+ * convolution on the integer matrix cores (the 3 x 3 layer of a ResNeXt / RegNet bottleneck stays on codes); no existing signature or
+ * result changed. */
 #define MCTQ_ABI_VERSION 10
 #define MCTQ_E_ARG (-10001)
 
@@ -796,6 +799,43 @@ int mctq_qconv_dw_i8(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_p
                      int64_t batch, int64_t height, int64_t width, int64_t channels,
                      int32_t kh, int32_t kw, int32_t stride_h, int32_t stride_w, int32_t pad_h, int32_t pad_w,
                      int32_t dil_h, int32_t dil_w, void* stream);
+
+/*
+ * Grouped convolution on activation codes (extension; the reference fake-quantizes weight and activation and runs the
+ * float32 grouped conv2d): 2 <= groups, Cg = channels / groups input and Og = out_channels / groups output channels per
+ * group, output channel n = g * Og + o:
+ *     acc[b][oy][ox][n] = sum over taps (ky, kx) inside the image, cg < Cg of
+ *                         (a[b][iy][ix][g * Cg + cg] - a_zero_point) * (w[n][cg][ky][kx] - zw[n])
+ *     y[b][oy][ox][n]   = float(acc) * (a_scale * w_scales[n]) + bias[n]
+ * zw = 0 when w_zero_points is NULL.  Taps outside the image add nothing (the kernel gives such a tap the zero-point byte:
+ * a_zero_point must be a code of the activations' type).  The int32 sum is exact (Kg = kh * kw * Cg <= 32768 terms of
+ * |a - za| <= 255 times |w - zw| <= 255: below 2^31); then one float32 multiply of the two scales, one float32 multiply and
+ * one float32 add, each rounded once -- the arithmetic of mctq_qlinear_i8.  Output forms as for mctq_qconv_dw_i8:
+ * y_code_dtype < 0 -> y is float32 [batch][Ho][Wo][out_channels]; MCTQ_CODE_I8 / _U8 -> y holds the next layer's codes.
+ *     Ho = (height + 2 pad_h - dil_h (kh - 1) - 1) / stride_h + 1,   Wo likewise.
+ * a_codes [batch][height][width][channels] (NHWC) int8 or uint8 (a_code_dtype).  w_codes int8 [groups][Ogp][Kgp] with
+ * Ogp = 16 * ceil(Og / 16), Kgp = 64 * ceil(Kg / 64): row o < Og of group g holds output channel g * Og + o in the K order
+ * (ky, kx, cg), column k = (ky * kw + kx) * Cg + cg; rows o >= Og and columns k >= Kg hold the code 0.  The codes are in the
+ * int8-ranged domain of mctq_qlinear_i8_zp's weights.  w_scales float32[out_channels]; w_rowsum int32[out_channels], the sum
+ * of channel n's Kg codes; w_zero_points int32[out_channels], each in [-128, 127], or NULL; bias float32[out_channels] or
+ * NULL.  All DEVICE pointers, 16-byte aligned.
+ * One wave owns 16 consecutive output pixels x up to 64 output channels of one group (v_mfma_i32_16x16x64_i8); a block is
+ * four waves; grid ceil(pixels / 64) x groups * ceil(Ogp / 64).  No patch matrix, no LDS, no atomics.
+ * MCTQ_E_ARG with a mctq_last_error text, before any pointer is read or anything is launched, for: negative extents; a
+ * kernel size, stride or dilation below 1; negative padding; groups < 2; channels or out_channels that are no positive
+ * multiple of groups; Cg % 4 != 0; kh * kw * Cg > 32768; a bad a_code_dtype; a_zero_point outside the code type's range; a
+ * bad output form (mctq_qlinear_i8_codes' checks); a padded extent above 2^31 - 1; Ho <= 0 or Wo <= 0; a non-empty batch of
+ * images without pixels; more than 2^31 - 1 output pixels; more than 65535 grid slices (groups * ceil(Ogp / 64)); NULL or
+ * misaligned pointers of a non-empty problem.  batch == 0 returns 0 without a launch.
+ * mctq_last_launch names the launch "qconv_grouped", op "u8 x i8" / "i8 x i8", with " zp" appended when w_zero_points was
+ * given, and U = the piece size (16, 8 or 4 bytes: the largest of them that divides Cg) the activation chunks were assembled from.
+ */
+int mctq_qconv_grouped_i8(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
+                          const int8_t* w_codes, const float* w_scales, const int32_t* w_rowsum, const int32_t* w_zero_points,
+                          const float* bias, void* y, int32_t y_code_dtype, float y_scale, int32_t y_zero_point,
+                          int32_t y_quant_min, int32_t y_quant_max, int64_t batch, int64_t height, int64_t width,
+                          int64_t channels, int64_t out_channels, int32_t groups, int32_t kh, int32_t kw, int32_t stride_h,
+                          int32_t stride_w, int32_t pad_h, int32_t pad_w, int32_t dil_h, int32_t dil_w, void* stream);
 
 /*
  * The join in front of an activation holder that several layers share (extension; the reference runs an ATen add, an ATen

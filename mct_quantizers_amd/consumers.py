@@ -37,6 +37,12 @@ MobileNet-style block) have no reduction over channels and so no patch matrix wo
 input element, ``kh * kw`` integer multiply-accumulates per output element, the same epilogue and output forms.  With it the
 expand -> depthwise -> project layers of such a block can be chained on codes.
 
+The other grouped convolutions (``2 <= groups``, ``Cg = in_channels / groups`` a multiple of 4: the 3x3 layer of a ResNeXt or RegNet
+bottleneck, ShuffleNet's grouped pointwise layers) are G small products: ``QuantizedGroupedConv2d`` (opt-in, ``grouped=True``) runs
+``mctq_qconv_grouped_i8``, a direct convolution on the NHWC codes on the integer matrix cores -- no patch matrix, one launch for all
+groups, the weight codes kept as ``[O, kh, kw, Cg]`` and zero-padded to ``[G, Ogp, Kgp]`` for the kernel, the same epilogue and output
+forms.  Layers with 1 to 3 channels per group stay on the float32 path.
+
 Holders with several users (the end of a residual block: the next block's first convolution, and its identity add or its
 downsample convolution) are ``fuse_linear_consumers_fx(..., shared_holders=True)``'s: such a holder becomes a ``QuantizedJoin``,
 which folds the residual add and the ReLU in front of it and returns both the fake-quantized float32 tensor, for the users that
@@ -116,11 +122,11 @@ tail round differently, they equal the chain's wherever its float32 value equals
 rounding tie elsewhere.  Out of scope: the lookup inside the producing consumer's epilogue (``emit_table``, beside ``emit_act``).
 Measured / not measured: see the README paragraph and ``profiles/EXPERIMENTS.md``.
 
-The four modules derive from ``IntegerConsumer``, which owns what they share: the checks of the quantizers and of the float32
+The five modules derive from ``IntegerConsumer``, which owns what they share: the checks of the quantizers and of the float32
 weight and bias, the cache of the weight's codes, the step from ``forward``'s input to activation codes, ``from_wrapper`` and
 the ``emit_codes_for`` / ``emit_clamp`` output form.  ``QuantizedLinear`` is the product over ``[O, K]`` rows; ``QuantizedConv1x1``
-and ``QuantizedConv2d`` are that product and derive from it; ``QuantizedDepthwiseConv2d`` is not and derives from
-``IntegerConsumer`` directly.  "Any integer consumer" in the graph rewrites is ``isinstance(m, IntegerConsumer)``.  The modules
+and ``QuantizedConv2d`` are that product and derive from it; ``QuantizedDepthwiseConv2d`` and ``QuantizedGroupedConv2d`` are not and
+derive from ``IntegerConsumer`` directly.  "Any integer consumer" in the graph rewrites is ``isinstance(m, IntegerConsumer)``.  The modules
 without weights -- the pools, ``QuantizedUpsample``, ``QuantizedActivationTable``, ``QuantizedConcat``, ``QuantizedMul``, ``QuantizedJoin`` --
 derive from ``_OnCodes``;
 ``_operand_codes`` is the one step from an operand of ``forward`` to codes, theirs and the consumers' (the join has its own kernel).
@@ -432,6 +438,87 @@ def qconv_dw_i8(a_codes_nhwc: torch.Tensor, a_zero_point: int, a_scale: float, w
             taps = xp[:, ky * dh:ky * dh + (ho - 1) * sh + 1:sh, kx * dw:kx * dw + (wo - 1) * sw + 1:sw, :]
             acc += taps * w32[ky, kx]
     return _cpu_epilogue(acc, a_scale, w_scales, bias, out_codes, act=act)
+
+
+def pack_grouped_weights(w_codes: torch.Tensor, groups: int):
+    """int8 codes [O, kh, kw, Cg] -> (the layout ``mctq_qconv_grouped_i8`` reads, the row sums): int8 ``[G, Ogp, Kgp]`` with
+    ``Ogp = 16 * ceil(Og / 16)`` and ``Kgp = 64 * ceil(Kg / 64)``, ``Kg = kh * kw * Cg``, row ``o`` of group ``g`` output channel
+    ``g * Og + o`` in the K order (ky, kx, cg), padded rows and columns the code 0; int32 ``[O]``, the sum of each channel's codes."""
+    O = w_codes.shape[0]
+    kg, og = math.prod(w_codes.shape[1:]), O // groups
+    rows = w_codes.reshape(groups, og, kg)
+    padded = torch.nn.functional.pad(rows, (0, -kg % 64, 0, -og % 16)).contiguous()
+    return padded, rows.sum(dim=2, dtype=torch.int32).reshape(O).contiguous()
+
+
+def qconv_grouped_i8(a_codes_nhwc: torch.Tensor, a_zero_point: int, a_scale: float, w_codes: torch.Tensor, w_scales: torch.Tensor,
+                     bias: Optional[torch.Tensor], groups: int, kernel_size, stride=1, padding=0, dilation=1, out_codes=None,
+                     w_zero_points: Optional[torch.Tensor] = None, *, packed=None) -> torch.Tensor:
+    """Grouped convolution on codes: a_codes_nhwc [B, H, W, C] int8/uint8, ``groups >= 2`` groups of ``Cg = C / groups`` input and
+    ``Og = O / groups`` output channels, w_codes [O, kh, kw, Cg] int8 (zero point 0 unless ``w_zero_points``, int32 [O] each in
+    [-128, 127], is given), w_scales / bias float32 [O] -> float32 [B, Ho, Wo, O], with ``n = g * Og + o``
+
+        y[b][oy][ox][n] = float(sum over taps inside the image, cg < Cg of (a[..][g * Cg + cg] - a_zero_point) * (w[n][ky][kx][cg] - zw[n]))
+                          * (a_scale * w_scales[n]) + bias[n]
+
+    or with ``out_codes = (scale, zero_point, qmin, qmax[, lo, hi])`` the codes of that activation quantizer, bit-identical to
+    ``ops.fq_codes`` of the float32 result.  ``kernel_size``, ``stride``, ``padding`` and ``dilation`` are ints or pairs.
+    GPU tensors run ``mctq_qconv_grouped_i8`` (Cg % 4 == 0, kh * kw * Cg <= 32768) on the padded weight layout and the row sums
+    of ``pack_grouped_weights`` -- built here, or given as ``packed`` by a caller that keeps them; CPU tensors run the same integer
+    arithmetic with torch ops, for any Cg."""
+    if not isinstance(a_codes_nhwc, torch.Tensor) or a_codes_nhwc.dim() != 4 or a_codes_nhwc.dtype not in (torch.int8, torch.uint8):
+        raise TypeError("qconv_grouped_i8 takes int8 / uint8 codes [B, H, W, C]")
+    b, h, w_, c = a_codes_nhwc.shape
+    (kh, kw), (sh, sw), (ph, pw), (dh, dw), (ho, wo) = ops._conv_geometry(h, w_, kernel_size, stride, padding, dilation, "qconv_grouped_i8")
+    groups = int(groups)
+    if groups < 2 or c % groups:
+        raise ValueError(f"qconv_grouped_i8: groups={groups} must be at least 2 and divide the {c} channels")
+    cg = c // groups
+    if (not isinstance(w_codes, torch.Tensor) or w_codes.dtype != torch.int8 or w_codes.device != a_codes_nhwc.device or w_codes.dim() != 4
+            or tuple(w_codes.shape[1:]) != (kh, kw, cg) or w_codes.shape[0] == 0 or w_codes.shape[0] % groups):
+        raise TypeError(f"w_codes must be an int8 tensor [O, {kh}, {kw}, {cg}] with O a positive multiple of {groups} on "
+                        f"{a_codes_nhwc.device}, got {getattr(w_codes, 'dtype', None)} {tuple(getattr(w_codes, 'shape', ()))} on "
+                        f"{getattr(w_codes, 'device', None)}")
+    o = w_codes.shape[0]
+    og = o // groups
+    _check_consumer_operands(a_codes_nhwc, w_scales, None, bias, w_zero_points)
+    if w_scales.numel() != o or (bias is not None and bias.numel() != o):
+        raise RuntimeError(f"w_scales and bias must have one entry per output channel ({o})")
+    a_zero_point = int(a_zero_point)
+    lo, hi = (0, 255) if a_codes_nhwc.dtype == torch.uint8 else (-128, 127)
+    if not lo <= a_zero_point <= hi:
+        raise ValueError(f"qconv_grouped_i8: a_zero_point {a_zero_point} is no {a_codes_nhwc.dtype} code")
+    if a_codes_nhwc.is_cuda:
+        if cg % 4 or kh * kw * cg > _MAX_K:
+            raise NotImplementedError(f"mctq_qconv_grouped_i8 needs Cg % 4 == 0 and kh * kw * Cg <= {_MAX_K}, got Cg={cg}, {kh}x{kw}")
+        w_padded, w_rowsum = pack_grouped_weights(w_codes, groups) if packed is None else packed
+        _check_consumer_operands(a_codes_nhwc, w_scales, w_rowsum, None)
+        want = (groups, -(-og // 16) * 16, -(-(kh * kw * cg) // 64) * 64)
+        if (w_padded.dtype != torch.int8 or w_padded.device != a_codes_nhwc.device or tuple(w_padded.shape) != want
+                or not w_padded.is_contiguous() or w_rowsum.numel() != o):
+            raise TypeError(f"packed must be pack_grouped_weights' (int8 {list(want)}, int32 [{o}]) on {a_codes_nhwc.device}")
+        x = a_codes_nhwc.contiguous()
+        tdt, *form = _output_form(out_codes)
+        y = x.new_empty((b, ho, wo, o), dtype=tdt)
+        ops._gpu_call("mctq_qconv_grouped_i8", x, x.data_ptr(), ops._code_of(x), a_zero_point, float(a_scale), w_padded.data_ptr(),
+                      w_scales.data_ptr(), w_rowsum.data_ptr(), None if w_zero_points is None else w_zero_points.data_ptr(),
+                      None if bias is None else bias.data_ptr(), y.data_ptr(), *form, b, h, w_, c, o, groups, kh, kw, sh, sw, ph, pw,
+                      dh, dw)
+        return y
+    ops._cpu_route_allowed()
+    w32 = w_codes.to(torch.int32)
+    if w_zero_points is not None:
+        w32 = w32 - w_zero_points.to(torch.int32).reshape(o, 1, 1, 1)
+    w32 = w32.reshape(groups, og, kh, kw, cg)
+    # a padded tap holds a - za = 0: it adds nothing
+    xp = torch.nn.functional.pad(a_codes_nhwc.to(torch.int32) - a_zero_point, (0, 0, pw, pw, ph, ph))
+    xp = xp.reshape(b, h + 2 * ph, w_ + 2 * pw, groups, cg)
+    acc = torch.zeros((b, ho, wo, groups, og), dtype=torch.int32)
+    for ky in range(kh):
+        for kx in range(kw):
+            taps = xp[:, ky * dh:ky * dh + (ho - 1) * sh + 1:sh, kx * dw:kx * dw + (wo - 1) * sw + 1:sw]
+            acc += torch.einsum("bhwgc,goc->bhwgo", taps, w32[:, :, ky, kx])
+    return _cpu_epilogue(acc.reshape(b, ho, wo, o), a_scale, w_scales, bias, out_codes)
 
 
 def pack_w4(codes: torch.Tensor) -> torch.Tensor:
@@ -928,6 +1015,55 @@ class QuantizedDepthwiseConv2d(IntegerConsumer):
         return y.permute(0, 3, 1, 2)
 
 
+class QuantizedGroupedConv2d(IntegerConsumer):
+    """``activation quantizer -> PytorchQuantizationWrapper(grouped nn.Conv2d)`` on integer codes: ``2 <= groups`` with
+    ``Cg = in_channels / groups`` a multiple of 4 (which leaves the depthwise layers to QuantizedDepthwiseConv2d), any ``Og =
+    out_channels / groups``, any kernel size with ``kh * kw * Cg <= 32768``, stride, dilation and symmetric zero padding -- the
+    3 x 3 layer of a ResNeXt or RegNet bottleneck, ShuffleNet's grouped pointwise layers.  It is G small products, run by
+    ``qconv_grouped_i8`` as one direct convolution on the NHWC codes (``mctq_qconv_grouped_i8``: the integer matrix cores, no
+    patch matrix, one launch for all groups).  The weight codes are kept as ``[O, kh, kw, Cg]`` and, for the kernel, zero-padded
+    to ``[G, Ogp, Kgp]`` with their row sums (``pack_grouped_weights``).  A tap outside the image adds nothing, which the kernel
+    gets by giving it the activation's zero-point code: that needs the zero point inside the clamp domain.  All weight families
+    of IntegerConsumer (a per-channel axis is the output-channel axis 0); chaining, ``emit_codes_for`` and ``emit_clamp`` as for
+    the other consumers; no residual and no ``emit_act``.  The result has the NCHW shape with channels-last strides."""
+
+    _takes = (f"zero-padded (symmetric) nn.Conv2d layers with groups >= 2, in_channels / groups a multiple of 4 and "
+              f"kh * kw * in_channels / groups <= {_MAX_K}")
+
+    def __init__(self, conv, weights_quantizer, activation_quantizer, weight=None):
+        super().__init__(conv, weights_quantizer, activation_quantizer, weight)
+        _take_conv_geometry(self, conv)
+        self.groups, self.out_channels = conv.groups, conv.out_channels
+        self._w_packed = None                            # pack_grouped_weights of the codes: the kernel's layout, the row sums
+
+    @staticmethod
+    def eligible(conv) -> bool:
+        if not isinstance(conv, nn.Conv2d) or conv.groups < 2 or QuantizedDepthwiseConv2d.eligible(conv):
+            return False
+        cg = conv.in_channels // conv.groups
+        return (cg % 4 == 0 and conv.padding_mode == "zeros" and _padding(conv) is not None
+                and conv.kernel_size[0] * conv.kernel_size[1] * cg <= _MAX_K)
+
+    def extra_repr(self) -> str:
+        parts = [super().extra_repr(), f"groups={self.groups}"]
+        return ", ".join(p for p in parts if p)
+
+    def _store_weight_codes(self, codes, lut):
+        self._w_codes = codes.reshape(self.weight.shape).permute(0, 2, 3, 1).contiguous()          # [O, Cg, kh, kw] -> [O, kh, kw, Cg]
+        self._w_packed = pack_grouped_weights(self._w_codes, self.groups)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        _check_nchw(x, self.in_channels)
+        if self.emit_residual is not None or self.emit_act is not None:
+            raise NotImplementedError("QuantizedGroupedConv2d takes no residual and no activation in its epilogue")
+        self._refresh_weight_codes()
+        codes = self._activation_codes(x)
+        y = qconv_grouped_i8(codes, self._a_zp, self._a_scale, self._w_codes, self._w_scales, self._bias_for(codes), self.groups,
+                             self.kernel_size, self.stride, self.padding, self.dilation, self._out_codes(), self._w_zps,
+                             packed=self._w_packed)
+        return y.permute(0, 3, 1, 2)
+
+
 def _ints_or_pair(v) -> bool:
     one = lambda e: isinstance(e, int) and not isinstance(e, bool)                     # noqa: E731
     return one(v) or (isinstance(v, (tuple, list)) and len(v) == 2 and all(one(e) for e in v))
@@ -1419,21 +1555,24 @@ _CONSUMERS = (
     (QuantizedConv1x1, None, lambda layer, any_channels: (any_channels or layer.in_channels % 16 == 0) and layer.in_channels <= _MAX_K),
     (QuantizedConv2d, "convolutions", None),
     (QuantizedDepthwiseConv2d, "depthwise", None),
+    (QuantizedGroupedConv2d, "grouped", None),
 )
 
 
-def _consumer_for(wrapper, activation_quantizer, uniform_weights=False, convolutions=False, depthwise=False, any_channels=False):
+def _consumer_for(wrapper, activation_quantizer, uniform_weights=False, convolutions=False, depthwise=False, any_channels=False,
+                  grouped=False):
     """The integer consumer that can stand in for ``wrapper`` fed by ``activation_quantizer``, or None.  Uniform weights
     only with ``uniform_weights``; convolutions that need a patch matrix (QuantizedConv2d) only with ``convolutions``;
-    depthwise convolutions (QuantizedDepthwiseConv2d) only with ``depthwise``; layers whose K is no multiple of 16 only with
-    ``any_channels`` (QuantizedLinear and the convolutions that are its product; never the depthwise convolution).  Half-precision
+    depthwise convolutions (QuantizedDepthwiseConv2d) only with ``depthwise``; the other grouped convolutions
+    (QuantizedGroupedConv2d) only with ``grouped``; layers whose K is no multiple of 16 only with ``any_channels`` (QuantizedLinear
+    and the convolutions that are its product; never the depthwise or the grouped convolution).  Half-precision
     layers are refused by the classes: the integer consumer would change the output type."""
     layer = getattr(wrapper, "layer", None)
     if list(getattr(wrapper, "weights_quantizers", {})) != ["weight"]:
         return None
     if _is_uniform_weights(wrapper.weights_quantizers["weight"]) and not uniform_weights:
         return None
-    enabled = {None: True, "convolutions": convolutions, "depthwise": depthwise}
+    enabled = {None: True, "convolutions": convolutions, "depthwise": depthwise, "grouped": grouped}
     for cls, switch, fits in _CONSUMERS:
         extra = {"any_channels": True} if any_channels and issubclass(cls, QuantizedLinear) else {}
         if enabled[switch] and cls.eligible(layer, **extra) and (fits is None or fits(layer, bool(extra))):
@@ -2405,7 +2544,7 @@ def _fuse_residuals_into_producers(gm, mods) -> int:
 def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights: bool = False,
                           convolutions: bool = False, depthwise: bool = False, pools: bool = False,
                           avg_pools: bool = False, upsamples: bool = False, any_channels: bool = False,
-                          activation_tables: bool = False) -> int:
+                          activation_tables: bool = False, grouped: bool = False) -> int:
     """In every ``nn.Sequential`` of ``model``: an activation holder directly followed by a wrapped ``nn.Linear`` with
     a symmetric, power-of-two or LUT weights quantizer (int8 codebook values, at most 256 entries) becomes (Identity,
     QuantizedLinear); a wrapped pointwise ``nn.Conv2d`` likewise becomes a QuantizedConv1x1.  Returns the number of pairs
@@ -2425,7 +2564,16 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
     ``depthwise=True`` also fuses wrapped depthwise ``nn.Conv2d`` layers (``groups == in_channels == out_channels``, symmetric
     zero padding, ``in_channels % 16 == 0``, ``kh * kw`` <= 256, the activation zero point inside its clamp domain) into a
     QuantizedDepthwiseConv2d, a direct convolution on the codes without a patch matrix.  It is independent of
-    ``convolutions``: neither switch implies the other, and other grouped convolutions are always left alone.
+    ``convolutions``: neither switch implies the other, and other grouped convolutions are always left alone unless
+    ``grouped=True``.
+
+    ``grouped=True`` also fuses the other wrapped grouped ``nn.Conv2d`` layers (``groups >= 2``, ``in_channels / groups`` a
+    multiple of 4, symmetric zero padding, ``kh * kw * in_channels / groups`` <= 32768, the activation zero point inside its
+    clamp domain) into a QuantizedGroupedConv2d: the 3 x 3 layer of a ResNeXt or RegNet bottleneck, ShuffleNet's grouped
+    pointwise layers -- one direct convolution on the codes on the integer matrix cores (``mctq_qconv_grouped_i8``), without a
+    patch matrix.  It is independent of ``convolutions`` and ``depthwise`` and composes with every other switch; depthwise
+    layers stay ``depthwise``'s, and layers with 1 to 3 channels per group stay on the float32 path.  By default such pairs are
+    left alone.
 
     ``chain=True``: where one QuantizedLinear feeds the next directly, the float32 tensor between them is never
     materialised -- the first emits the second's activation codes from its epilogue (same codes, bit for bit, as
@@ -2484,7 +2632,7 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
             wrapper = seq[i + 4] if flat else seq[i + 3]
             if not isinstance(wrapper, PytorchQuantizationWrapper):
                 continue
-            fused = _consumer_for(wrapper, second.activation_holder_quantizer, uniform_weights, convolutions, depthwise, any_channels)
+            fused = _consumer_for(wrapper, second.activation_holder_quantizer, uniform_weights, convolutions, depthwise, any_channels, grouped)
             if fused is None or (type(fused) is QuantizedLinear) != flat:
                 continue
             try:
@@ -2503,7 +2651,7 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
             if not _plain_holder(holder) or not QuantizedUpsample.eligible(up) or not isinstance(wrapper, PytorchQuantizationWrapper):
                 continue
             reads_as = (holder if second is None else second).activation_holder_quantizer
-            fused = _consumer_for(wrapper, reads_as, uniform_weights, convolutions, depthwise, any_channels)
+            fused = _consumer_for(wrapper, reads_as, uniform_weights, convolutions, depthwise, any_channels, grouped)
             if fused is None or type(fused) is QuantizedLinear:
                 continue
             try:
@@ -2520,7 +2668,7 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
             if not _plain_holder(holder) or not _plain_holder(second) or not QuantizedActivationTable.eligible(fn) \
                     or not isinstance(wrapper, PytorchQuantizationWrapper):
                 continue
-            fused = _consumer_for(wrapper, second.activation_holder_quantizer, uniform_weights, convolutions, depthwise, any_channels)
+            fused = _consumer_for(wrapper, second.activation_holder_quantizer, uniform_weights, convolutions, depthwise, any_channels, grouped)
             if fused is None:
                 continue
             try:
@@ -2533,7 +2681,7 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
             holder, pool, wrapper = seq[i], seq[i + 1], seq[i + 2]
             if not _plain_holder(holder) or not QuantizedMaxPool2d.eligible(pool) or not isinstance(wrapper, PytorchQuantizationWrapper):
                 continue
-            fused = _consumer_for(wrapper, holder.activation_holder_quantizer, uniform_weights, convolutions, depthwise, any_channels)
+            fused = _consumer_for(wrapper, holder.activation_holder_quantizer, uniform_weights, convolutions, depthwise, any_channels, grouped)
             if fused is None or type(fused) is QuantizedLinear:
                 continue
             try:
@@ -2546,7 +2694,7 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
             holder, wrapper = seq[i], seq[i + 1]
             if not _plain_holder(holder) or not isinstance(wrapper, PytorchQuantizationWrapper):
                 continue
-            fused = _consumer_for(wrapper, holder.activation_holder_quantizer, uniform_weights, convolutions, depthwise, any_channels)
+            fused = _consumer_for(wrapper, holder.activation_holder_quantizer, uniform_weights, convolutions, depthwise, any_channels, grouped)
             if fused is None:
                 continue
             seq[i] = _FusedAway()
@@ -2565,14 +2713,17 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
                              stay_on_codes: bool = False, pools: bool = False, fused_residuals: bool = False,
                              concats: bool = False, avg_pools: bool = False, muls: bool = False,
                              hard_activations: bool = False, upsamples: bool = False, any_channels: bool = False,
-                             activation_tables: bool = False):
+                             activation_tables: bool = False, grouped: bool = False):
     """The same rewrite on an arbitrary module graph (MCT-exported models are not ``nn.Sequential``): traces ``model``
     with torch.fx keeping wrappers and holders as leaves, and wherever an activation holder's ONLY consumer is a
     wrapped ``nn.Linear`` the integer consumer can take (symmetric, power-of-two or LUT weights, and with
     ``uniform_weights=True`` uniform weights, as for ``fuse_linear_consumers``), replaces the pair by one
     ``QuantizedLinear`` node; wrapped pointwise convolutions likewise, and with ``convolutions=True`` the other
-    convolutions a QuantizedConv2d can take, and with ``depthwise=True`` the depthwise convolutions a QuantizedDepthwiseConv2d
-    can take.
+    convolutions a QuantizedConv2d can take, with ``depthwise=True`` the depthwise convolutions a QuantizedDepthwiseConv2d
+    can take, and with ``grouped=True`` the other grouped convolutions a QuantizedGroupedConv2d can take (other grouped
+    convolutions are always left alone unless ``grouped=True``; the switch needs no other and composes with all of them: such a
+    consumer reads and emits codes like the other convolution consumers, takes folded clamps, and takes no residual and no
+    Hardswish / Hardsigmoid in its epilogue).
     Returns ``(graph_module, wrapped_layers_replaced)``.  Holders with several consumers (residual branches) stay, unless
     ``shared_holders=True``:
 
@@ -2796,7 +2947,7 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
     gm = fx.GraphModule(model, graph)
     mods = dict(gm.named_modules())
     replaced = 0
-    consumer_for = lambda wrapper, q: _consumer_for(wrapper, q, uniform_weights, convolutions, depthwise, any_channels)      # noqa: E731
+    consumer_for = lambda wrapper, q: _consumer_for(wrapper, q, uniform_weights, convolutions, depthwise, any_channels, grouped)      # noqa: E731
     # Two whole passes, concatenations first: a concatenation absorbs an operand holder that sits behind a multiply, which the
     # multiply pass then no longer sees.
     if concats:
