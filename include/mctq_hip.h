@@ -96,6 +96,9 @@ extern "C" {
 /* v10 (additive, the version number stays): + mctq_qconv_grouped_i8, the grouped convolution on NHWC activation codes as a direct
  * convolution on the integer matrix cores (the 3 x 3 layer of a ResNeXt / RegNet bottleneck stays on codes); no existing signature or
  * result changed. */
+/* v10 (additive, the version number stays): + mctq_qconv_transposed_i8, the transposed convolution on NHWC activation codes as
+ * one stride-1 correlation per output phase on the integer matrix cores (the learned upsampling of a decoder stage stays on codes);
+ * no existing signature or result changed. */
 #define MCTQ_ABI_VERSION 10
 #define MCTQ_E_ARG (-10001)
 
@@ -836,6 +839,50 @@ int mctq_qconv_grouped_i8(const void* a_codes, int32_t a_code_dtype, int32_t a_z
                           int32_t y_quant_min, int32_t y_quant_max, int64_t batch, int64_t height, int64_t width,
                           int64_t channels, int64_t out_channels, int32_t groups, int32_t kh, int32_t kw, int32_t stride_h,
                           int32_t stride_w, int32_t pad_h, int32_t pad_w, int32_t dil_h, int32_t dil_w, void* stream);
+
+/*
+ * Transposed convolution on activation codes (extension; the reference fake-quantizes weight and activation and runs the
+ * float32 conv_transpose2d): nn.ConvTranspose2d with groups == 1 and dilation == 1,
+ *     Ho = (height - 1) stride_h - 2 pad_h + kh + out_pad_h,   Wo likewise,
+ *     acc[b][oy][ox][o] = sum over c, ky, kx with iy * stride_h = oy + pad_h - ky, ix * stride_w = ox + pad_w - kx,
+ *                         0 <= iy < height, 0 <= ix < width of (a[b][iy][ix][c] - a_zero_point) * (w[c][o][ky][kx] - zw[o])
+ *     y[b][oy][ox][o]   = float(acc) * (a_scale * w_scales[o]) + bias[o]
+ * zw = 0 when w_zero_points is NULL.  The int32 sum is exact (at most 32768 terms of |a - za| <= 255 times |w - zw| <= 255:
+ * below 2^31); then one float32 multiply of the two scales, one float32 multiply and one float32 add, each rounded once --
+ * the arithmetic of mctq_qlinear_i8.  Output forms as for mctq_qconv_grouped_i8: y_code_dtype < 0 -> y is float32
+ * [batch][Ho][Wo][out_channels]; MCTQ_CODE_I8 / _U8 -> y holds the next layer's codes.
+ * Phases: an output pixel has the phase (ry, rx) = ((oy + pad_h) mod stride_h, (ox + pad_w) mod stride_w), p = ry * stride_w +
+ * rx of P = stride_h * stride_w, and the quotient (qy, qx) = ((oy + pad_h) div stride_h, (ox + pad_w) div stride_w).  Only
+ * the taps ky = ry + stride_h * ty, ty < Ty(ry) = max(0, ceil((kh - ry) / stride_h)), and kx = rx + stride_w * tx, tx < Tx(rx)
+ * likewise, reach it, and tap (ty, tx) reads the input pixel (qy - ty, qx - tx); one outside the image adds nothing (the
+ * kernel gives such a tap the zero-point byte: a_zero_point must be a code of the activations' type).  K(p) = Ty * Tx *
+ * channels; a phase with K(p) == 0 (kernel smaller than the stride) holds the bias alone.
+ * a_codes [batch][height][width][channels] (NHWC) int8 or uint8 (a_code_dtype).  w_codes int8 [P][Op][Kp] with Op = 16 *
+ * ceil(out_channels / 16), Kp = 64 * ceil(max over p of K(p) / 64): row o < out_channels of phase p holds output channel o
+ * in the K order (ty, tx, c), column k = (ty * Tx + tx) * channels + c the code of w[c][o][ry + stride_h * ty][rx +
+ * stride_w * tx]; rows o >= out_channels and columns k >= K(p) hold the code 0.  The codes are in the int8-ranged domain of
+ * mctq_qlinear_i8_zp's weights.  w_scales float32[out_channels]; w_rowsum int32[P][out_channels], the sum of row o's K(p)
+ * codes of phase p; w_zero_points int32[out_channels], each in [-128, 127], or NULL; bias float32[out_channels] or NULL.  All
+ * DEVICE pointers, 16-byte aligned.
+ * One wave owns 16 consecutive pixels of one phase x up to 64 output channels (v_mfma_i32_16x16x64_i8); a block is four
+ * waves; grid ceil(max over p of the phase's pixels / 64) x P * ceil(Op / 64).  No LDS, no atomics.
+ * MCTQ_E_ARG with a mctq_last_error text, before any pointer is read or anything is launched, for: negative extents; a
+ * kernel size or stride below 1; a stride above 4; negative padding or output padding; an output padding that is not
+ * smaller than the stride; channels or out_channels of 0; channels % 16 != 0; ceil(kh / stride_h) * ceil(kw / stride_w) *
+ * channels > 32768; a bad a_code_dtype; a_zero_point outside the code type's range; a bad output form
+ * (mctq_qlinear_i8_codes' checks); height or width above 2^31 - 1; Ho <= 0 or Wo <= 0; Ho + pad_h or Wo + pad_w above
+ * 2^31 - 1; a non-empty batch of images without pixels; more than 2^31 - 1 output pixels; a codes or output tensor of 2^63
+ * bytes or more; more than 65535 grid slices (P * ceil(Op / 64)); NULL or misaligned pointers of a non-empty problem.
+ * batch == 0 returns 0 without a launch.
+ * mctq_last_launch names the launch "qconv_transposed", op "u8 x i8" / "i8 x i8", with " zp" appended when w_zero_points
+ * was given, U = the number of phases P, and out4B / out1B the output's element width.
+ */
+int mctq_qconv_transposed_i8(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale,
+                             const int8_t* w_codes, const float* w_scales, const int32_t* w_rowsum, const int32_t* w_zero_points,
+                             const float* bias, void* y, int32_t y_code_dtype, float y_scale, int32_t y_zero_point,
+                             int32_t y_quant_min, int32_t y_quant_max, int64_t batch, int64_t height, int64_t width,
+                             int64_t channels, int64_t out_channels, int32_t kh, int32_t kw, int32_t stride_h, int32_t stride_w,
+                             int32_t pad_h, int32_t pad_w, int32_t out_pad_h, int32_t out_pad_w, void* stream);
 
 /*
  * The join in front of an activation holder that several layers share (extension; the reference runs an ATen add, an ATen

@@ -43,6 +43,11 @@ bottleneck, ShuffleNet's grouped pointwise layers) are G small products: ``Quant
 groups, the weight codes kept as ``[O, kh, kw, Cg]`` and zero-padded to ``[G, Ogp, Kgp]`` for the kernel, the same epilogue and output
 forms.  Layers with 1 to 3 channels per group stay on the float32 path.
 
+Transposed convolutions (``nn.ConvTranspose2d`` with ``groups == 1`` and dilation 1: the learned upsampling of a decoder stage) are
+one stride-1 correlation per output phase ``((oy + ph) mod sh, (ox + pw) mod sw)``: ``QuantizedConvTranspose2d`` (opt-in,
+``transposed=True``) runs ``mctq_qconv_transposed_i8``, all ``sh * sw`` phases in one launch on the integer matrix cores, the weight
+codes kept as ``[O, kh, kw, C]`` and per phase as ``[P, Op, Kp]`` for the kernel, the same epilogue and output forms.
+
 Holders with several users (the end of a residual block: the next block's first convolution, and its identity add or its
 downsample convolution) are ``fuse_linear_consumers_fx(..., shared_holders=True)``'s: such a holder becomes a ``QuantizedJoin``,
 which folds the residual add and the ReLU in front of it and returns both the fake-quantized float32 tensor, for the users that
@@ -122,11 +127,11 @@ tail round differently, they equal the chain's wherever its float32 value equals
 rounding tie elsewhere.  Out of scope: the lookup inside the producing consumer's epilogue (``emit_table``, beside ``emit_act``).
 Measured / not measured: see the README paragraph and ``profiles/EXPERIMENTS.md``.
 
-The five modules derive from ``IntegerConsumer``, which owns what they share: the checks of the quantizers and of the float32
+The six modules derive from ``IntegerConsumer``, which owns what they share: the checks of the quantizers and of the float32
 weight and bias, the cache of the weight's codes, the step from ``forward``'s input to activation codes, ``from_wrapper`` and
 the ``emit_codes_for`` / ``emit_clamp`` output form.  ``QuantizedLinear`` is the product over ``[O, K]`` rows; ``QuantizedConv1x1``
-and ``QuantizedConv2d`` are that product and derive from it; ``QuantizedDepthwiseConv2d`` and ``QuantizedGroupedConv2d`` are not and
-derive from ``IntegerConsumer`` directly.  "Any integer consumer" in the graph rewrites is ``isinstance(m, IntegerConsumer)``.  The modules
+and ``QuantizedConv2d`` are that product and derive from it; ``QuantizedDepthwiseConv2d``, ``QuantizedGroupedConv2d`` and
+``QuantizedConvTranspose2d`` are not and derive from ``IntegerConsumer`` directly.  "Any integer consumer" in the graph rewrites is ``isinstance(m, IntegerConsumer)``.  The modules
 without weights -- the pools, ``QuantizedUpsample``, ``QuantizedActivationTable``, ``QuantizedConcat``, ``QuantizedMul``, ``QuantizedJoin`` --
 derive from ``_OnCodes``;
 ``_operand_codes`` is the one step from an operand of ``forward`` to codes, theirs and the consumers' (the join has its own kernel).
@@ -521,6 +526,114 @@ def qconv_grouped_i8(a_codes_nhwc: torch.Tensor, a_zero_point: int, a_scale: flo
     return _cpu_epilogue(acc.reshape(b, ho, wo, o), a_scale, w_scales, bias, out_codes)
 
 
+_MAX_TRANSPOSED_STRIDE = 4                               # mctq_qconv_transposed_i8 keeps its per-phase tables at this size
+
+
+def _transposed_taps(k: int, s: int):
+    """Taps per residue of one axis of a transposed convolution: ``T(r) = max(0, ceil((k - r) / s))`` for r < s."""
+    return [max(0, -(-(k - r) // s)) for r in range(s)]
+
+
+def _transposed_geometry(h: int, w: int, kernel_size, stride, padding, output_padding, caller: str):
+    """A transposed convolution (dilation 1) of an ``h`` x ``w`` image, its arguments ints or pairs -> the pairs ``(kh, kw),
+    (sh, sw), (ph, pw), (oph, opw)`` and the output size ``(ho, wo)``, ``ho = (h - 1) * sh - 2 * ph + kh + oph``; ValueError, in
+    ``caller``'s name, for arguments PyTorch refuses."""
+    (kh, kw), (sh, sw) = ops._pair(kernel_size, "kernel_size", caller), ops._pair(stride, "stride", caller)
+    (ph, pw), (oph, opw) = ops._pair(padding, "padding", caller), ops._pair(output_padding, "output_padding", caller)
+    if min(kh, kw, sh, sw) < 1 or min(ph, pw, oph, opw) < 0:
+        raise ValueError(f"{caller}: kernel_size and stride must be at least 1, padding and output_padding at least 0")
+    if oph >= sh or opw >= sw:
+        raise ValueError(f"{caller}: output_padding {oph}x{opw} must be smaller than the stride {sh}x{sw}")
+    ho, wo = (h - 1) * sh - 2 * ph + kh + oph, (w - 1) * sw - 2 * pw + kw + opw
+    if ho <= 0 or wo <= 0:
+        raise ValueError(f"{caller}: padding {ph}x{pw} leaves no output of the {h}x{w} image")
+    return (kh, kw), (sh, sw), (ph, pw), (oph, opw), (ho, wo)
+
+
+def pack_transposed_weights(w_codes: torch.Tensor, stride):
+    """int8 codes [O, kh, kw, C] of a transposed convolution -> (the layout ``mctq_qconv_transposed_i8`` reads, the row sums):
+    int8 ``[P, Op, Kp]`` with ``P = sh * sw`` phases, ``Op = 16 * ceil(O / 16)`` and ``Kp = 64 * ceil(max K / 64)``; phase
+    ``ry * sw + rx`` holds the taps ``ky = ry + sh * ty``, ``kx = rx + sw * tx`` -- row ``o`` in the K order (ty, tx, c),
+    ``K = Ty * Tx * C`` columns -- padded rows and columns the code 0; int32 ``[P, O]``, the sum of each row's codes."""
+    sh, sw = ops._pair(stride, "stride", "pack_transposed_weights")
+    o, kh, kw, c = w_codes.shape
+    kp = -(-(_transposed_taps(kh, sh)[0] * _transposed_taps(kw, sw)[0] * c) // 64) * 64
+    packed = w_codes.new_zeros((sh * sw, -(-o // 16) * 16, kp))
+    rowsum = torch.zeros((sh * sw, o), dtype=torch.int32, device=w_codes.device)
+    for ry in range(sh):
+        for rx in range(sw):
+            rows = w_codes[:, ry::sh, rx::sw, :].reshape(o, -1)
+            packed[ry * sw + rx, :o, :rows.shape[1]] = rows
+            rowsum[ry * sw + rx] = rows.sum(dim=1, dtype=torch.int32)
+    return packed, rowsum
+
+
+def qconv_transposed_i8(a_codes_nhwc: torch.Tensor, a_zero_point: int, a_scale: float, w_codes: torch.Tensor, w_scales: torch.Tensor,
+                        bias: Optional[torch.Tensor], kernel_size, stride=1, padding=0, output_padding=0, out_codes=None,
+                        w_zero_points: Optional[torch.Tensor] = None, *, packed=None) -> torch.Tensor:
+    """Transposed convolution on codes (``nn.ConvTranspose2d`` with ``groups == 1`` and ``dilation == 1``): a_codes_nhwc
+    [B, H, W, C] int8/uint8, w_codes [O, kh, kw, C] int8 (zero point 0 unless ``w_zero_points``, int32 [O] each in [-128, 127], is
+    given), w_scales / bias float32 [O] -> float32 [B, Ho, Wo, O], ``Ho = (H - 1) * sh - 2 * ph + kh + oph``,
+
+        y[b][oy][ox][o] = float(sum over c, ky, kx with iy * sh = oy + ph - ky, ix * sw = ox + pw - kx inside the image of
+                                (a[b][iy][ix][c] - a_zero_point) * (w[o][ky][kx][c] - zw[o])) * (a_scale * w_scales[o]) + bias[o]
+
+    or with ``out_codes = (scale, zero_point, qmin, qmax[, lo, hi])`` the codes of that activation quantizer, bit-identical to
+    ``ops.fq_codes`` of the float32 result.  ``kernel_size``, ``stride``, ``padding`` and ``output_padding`` are ints or pairs.
+    GPU tensors run ``mctq_qconv_transposed_i8`` (C % 16 == 0, strides <= 4, at most 32768 columns per phase) on the per-phase
+    weight layout and the row sums of ``pack_transposed_weights`` -- built here, or given as ``packed`` by a caller that keeps
+    them; CPU tensors run the same integer arithmetic with torch ops (one strided ``+=`` per tap into a padded canvas, then the
+    crop), for any C and any stride."""
+    if not isinstance(a_codes_nhwc, torch.Tensor) or a_codes_nhwc.dim() != 4 or a_codes_nhwc.dtype not in (torch.int8, torch.uint8):
+        raise TypeError("qconv_transposed_i8 takes int8 / uint8 codes [B, H, W, C]")
+    b, h, w_, c = a_codes_nhwc.shape
+    (kh, kw), (sh, sw), (ph, pw), (oph, opw), (ho, wo) = _transposed_geometry(h, w_, kernel_size, stride, padding, output_padding,
+                                                                              "qconv_transposed_i8")
+    if (not isinstance(w_codes, torch.Tensor) or w_codes.dtype != torch.int8 or w_codes.device != a_codes_nhwc.device or w_codes.dim() != 4
+            or tuple(w_codes.shape[1:]) != (kh, kw, c) or w_codes.shape[0] == 0):
+        raise TypeError(f"w_codes must be an int8 tensor [O, {kh}, {kw}, {c}] with O >= 1 on {a_codes_nhwc.device}, got "
+                        f"{getattr(w_codes, 'dtype', None)} {tuple(getattr(w_codes, 'shape', ()))} on {getattr(w_codes, 'device', None)}")
+    o = w_codes.shape[0]
+    _check_consumer_operands(a_codes_nhwc, w_scales, None, bias, w_zero_points)
+    if w_scales.numel() != o or (bias is not None and bias.numel() != o):
+        raise RuntimeError(f"w_scales and bias must have one entry per output channel ({o})")
+    a_zero_point = int(a_zero_point)
+    lo, hi = (0, 255) if a_codes_nhwc.dtype == torch.uint8 else (-128, 127)
+    if not lo <= a_zero_point <= hi:
+        raise ValueError(f"qconv_transposed_i8: a_zero_point {a_zero_point} is no {a_codes_nhwc.dtype} code")
+    if a_codes_nhwc.is_cuda:
+        max_k = _transposed_taps(kh, sh)[0] * _transposed_taps(kw, sw)[0] * c
+        if c % 16 or max(sh, sw) > _MAX_TRANSPOSED_STRIDE or max_k > _MAX_K:
+            raise NotImplementedError(f"mctq_qconv_transposed_i8 needs C % 16 == 0, strides <= {_MAX_TRANSPOSED_STRIDE} and at most "
+                                      f"{_MAX_K} columns per phase, got C={c}, {kh}x{kw}, stride {sh}x{sw}")
+        w_packed, w_rowsum = pack_transposed_weights(w_codes, (sh, sw)) if packed is None else packed
+        _check_consumer_operands(a_codes_nhwc, w_scales, w_rowsum, None)
+        want = (sh * sw, -(-o // 16) * 16, -(-max_k // 64) * 64)
+        if (w_packed.dtype != torch.int8 or w_packed.device != a_codes_nhwc.device or tuple(w_packed.shape) != want
+                or not w_packed.is_contiguous() or tuple(w_rowsum.shape) != (sh * sw, o)):
+            raise TypeError(f"packed must be pack_transposed_weights' (int8 {list(want)}, int32 [{sh * sw}, {o}]) on {a_codes_nhwc.device}")
+        x = a_codes_nhwc.contiguous()
+        tdt, *form = _output_form(out_codes)
+        y = x.new_empty((b, ho, wo, o), dtype=tdt)
+        ops._gpu_call("mctq_qconv_transposed_i8", x, x.data_ptr(), ops._code_of(x), a_zero_point, float(a_scale), w_packed.data_ptr(),
+                      w_scales.data_ptr(), w_rowsum.data_ptr(), None if w_zero_points is None else w_zero_points.data_ptr(),
+                      None if bias is None else bias.data_ptr(), y.data_ptr(), *form, b, h, w_, c, o, kh, kw, sh, sw, ph, pw, oph, opw)
+        return y
+    ops._cpu_route_allowed()
+    w32 = w_codes.to(torch.int32)
+    if w_zero_points is not None:
+        w32 = w32 - w_zero_points.to(torch.int32).reshape(o, 1, 1, 1)
+    a32 = a_codes_nhwc.to(torch.int32) - a_zero_point
+    # the scatter form: input pixel (iy, ix) adds its tap (ky, kx) to canvas pixel (iy * sh + ky, ix * sw + kx); the output is
+    # the canvas from (ph, pw) on, and rows / columns the output padding adds beyond the last tap stay 0
+    canvas = torch.zeros((b, (h - 1) * sh + kh + oph, (w_ - 1) * sw + kw + opw, o), dtype=torch.int32)
+    for ky in range(kh):
+        for kx in range(kw):
+            canvas[:, ky:ky + (h - 1) * sh + 1:sh, kx:kx + (w_ - 1) * sw + 1:sw] += torch.einsum("bhwc,oc->bhwo", a32, w32[:, ky, kx])
+    acc = canvas[:, ph:ph + ho, pw:pw + wo].contiguous()
+    return _cpu_epilogue(acc, a_scale, w_scales, bias, out_codes)
+
+
 def pack_w4(codes: torch.Tensor) -> torch.Tensor:
     """int8 codes in [-8, 7], [N, K] with K % 8 == 0 -> the consumer's 4-bit layout, uint8 [N, K / 2]: per group of 8
     consecutive k, byte j = (code[j] & 0xF) | (code[j + 4] << 4) (include/mctq_hip.h: mctq_qlinear_w4a8)."""
@@ -628,10 +741,12 @@ class IntegerConsumer(nn.Module):
     ``weight``: the float weight to own in place of ``layer.weight`` (a wrapper has replaced that by a plain tensor and owns the
     parameter itself).  The float weight stays the module's parameter; its codes are rebuilt when it changes.
 
-    A subclass says which layers it takes (``eligible``, ``_takes`` for the messages), in which layout it keeps the weight
+    A subclass says which layers it takes (``eligible``, ``_takes`` for the messages), which axis of its weight holds the output
+    channels (``_out_axis``: 0, and 1 for a transposed convolution -- a per-channel quantizer must run along it), in which layout it keeps the weight
     codes (``_store_weight_codes``) and runs the product (``forward``)."""
 
     _takes = None
+    _out_axis = 0                                        # the weight's output-channel axis (1: nn.ConvTranspose2d's [C, O, kh, kw])
 
     def __init__(self, layer, weights_quantizer, activation_quantizer, weight=None, any_channels: bool = False):
         super().__init__()
@@ -648,8 +763,11 @@ class IntegerConsumer(nn.Module):
         elif not self._uniform_weights and (not hasattr(weights_quantizer, "quantize_to_codes")
                                             or not hasattr(weights_quantizer, "threshold_np")):
             raise TypeError("the weights quantizer must be symmetric, power-of-two (zero point 0), uniform or a LUT quantizer")
-        if weights_quantizer.per_channel and weights_quantizer.channel_axis % 2 != 0:
+        if weights_quantizer.per_channel and self._out_axis == 0 and weights_quantizer.channel_axis % 2 != 0:
             raise NotImplementedError("per-channel weight scales must run along the output channels (axis 0)")
+        if weights_quantizer.per_channel and self._out_axis != 0 and weights_quantizer.channel_axis % 4 != self._out_axis:
+            # (a [C, O, kh, kw] weight: scales along the input channels of a transposed convolution cannot go into an epilogue)
+            raise NotImplementedError(f"per-channel weight scales must run along the output channels (axis {self._out_axis})")
         if weights_quantizer.num_bits > 8 or activation_quantizer.num_bits > 8:
             raise NotImplementedError("codes wider than 8 bits")
         weight, bias = layer.weight if weight is None else weight, layer.bias
@@ -748,7 +866,7 @@ class IntegerConsumer(nn.Module):
         codes, scales, zps, lut = self._weight_codes(w)
 
         def per_channel(t):
-            return (t.expand(w.shape[0]) if t.numel() == 1 else t).contiguous()
+            return (t.expand(w.shape[self._out_axis]) if t.numel() == 1 else t).contiguous()
 
         self._w_scales = per_channel(scales.to(device=w.device, dtype=torch.float32).reshape(-1))
         if zps is not None:
@@ -1061,6 +1179,61 @@ class QuantizedGroupedConv2d(IntegerConsumer):
         y = qconv_grouped_i8(codes, self._a_zp, self._a_scale, self._w_codes, self._w_scales, self._bias_for(codes), self.groups,
                              self.kernel_size, self.stride, self.padding, self.dilation, self._out_codes(), self._w_zps,
                              packed=self._w_packed)
+        return y.permute(0, 3, 1, 2)
+
+
+class QuantizedConvTranspose2d(IntegerConsumer):
+    """``activation quantizer -> PytorchQuantizationWrapper(nn.ConvTranspose2d)`` on integer codes: ``groups == 1``, ``dilation ==
+    1``, ``in_channels % 16 == 0``, strides of at most 4, any kernel size, padding and output padding whose largest phase has at
+    most 32768 columns (``ceil(kh / sh) * ceil(kw / sw) * in_channels``) -- the learned 2 x 2 stride-2 upsampling of a U-Net
+    decoder, the 4 x 4 stride-2 one of a segmentation head or a GAN generator, 3 x 3 stride 2 with ``output_padding=1``.  The
+    output pixels of one phase ``((oy + ph) mod sh, (ox + pw) mod sw)`` are a plain stride-1 correlation of the NHWC codes with
+    that phase's sub-kernel, so ``qconv_transposed_i8`` runs the layer as ``sh * sw`` such products in one launch
+    (``mctq_qconv_transposed_i8``: the integer matrix cores, no zero-stuffed input, no patch matrix).  The ``[C, O, kh, kw]``
+    weight's codes are kept as ``[O, kh, kw, C]`` and, for the kernel, per phase as ``[P, Op, Kp]`` with their row sums
+    (``pack_transposed_weights``).  A tap outside the image adds nothing, which the kernel gets by giving it the activation's
+    zero-point code: that needs the zero point inside the clamp domain.  All weight families of IntegerConsumer; the output
+    channels are the weight's axis 1, so a per-channel quantizer runs along axis 1 (one along the input channels, axis 0,
+    cannot go into an epilogue and is refused); chaining, ``emit_codes_for`` and ``emit_clamp`` as for the other consumers; no
+    residual and no ``emit_act``.  The result has the NCHW shape with channels-last strides."""
+
+    _takes = (f"zero-padded nn.ConvTranspose2d layers with groups == 1, dilation 1, in_channels a multiple of 16, strides <= "
+              f"{_MAX_TRANSPOSED_STRIDE} and ceil(kh / sh) * ceil(kw / sw) * in_channels <= {_MAX_K}")
+    _out_axis = 1
+
+    def __init__(self, conv, weights_quantizer, activation_quantizer, weight=None):
+        super().__init__(conv, weights_quantizer, activation_quantizer, weight)
+        _check_pad_byte(self)
+        self.in_channels, self.out_channels = conv.in_channels, conv.out_channels
+        self.kernel_size, self.stride = tuple(conv.kernel_size), tuple(conv.stride)
+        self.padding, self.output_padding = tuple(conv.padding), tuple(conv.output_padding)
+        self._w_packed = None                            # pack_transposed_weights of the codes: the kernel's layout, the row sums
+
+    @staticmethod
+    def eligible(conv) -> bool:
+        if not isinstance(conv, nn.ConvTranspose2d) or conv.groups != 1 or tuple(conv.dilation) != (1, 1):
+            return False
+        (kh, kw), (sh, sw) = conv.kernel_size, conv.stride
+        return (conv.in_channels % 16 == 0 and conv.padding_mode == "zeros" and max(sh, sw) <= _MAX_TRANSPOSED_STRIDE
+                and _transposed_taps(kh, sh)[0] * _transposed_taps(kw, sw)[0] * conv.in_channels <= _MAX_K)
+
+    def extra_repr(self) -> str:
+        parts = [super().extra_repr(), f"kernel_size={self.kernel_size}, stride={self.stride}"]
+        return ", ".join(p for p in parts if p)
+
+    def _store_weight_codes(self, codes, lut):
+        self._w_codes = codes.reshape(self.weight.shape).permute(1, 2, 3, 0).contiguous()          # [C, O, kh, kw] -> [O, kh, kw, C]
+        self._w_packed = pack_transposed_weights(self._w_codes, self.stride)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        _check_nchw(x, self.in_channels)
+        if self.emit_residual is not None or self.emit_act is not None:
+            raise NotImplementedError("QuantizedConvTranspose2d takes no residual and no activation in its epilogue")
+        self._refresh_weight_codes()
+        codes = self._activation_codes(x)
+        y = qconv_transposed_i8(codes, self._a_zp, self._a_scale, self._w_codes, self._w_scales, self._bias_for(codes),
+                                self.kernel_size, self.stride, self.padding, self.output_padding, self._out_codes(), self._w_zps,
+                                packed=self._w_packed)
         return y.permute(0, 3, 1, 2)
 
 
@@ -1556,23 +1729,25 @@ _CONSUMERS = (
     (QuantizedConv2d, "convolutions", None),
     (QuantizedDepthwiseConv2d, "depthwise", None),
     (QuantizedGroupedConv2d, "grouped", None),
+    (QuantizedConvTranspose2d, "transposed", None),
 )
 
 
 def _consumer_for(wrapper, activation_quantizer, uniform_weights=False, convolutions=False, depthwise=False, any_channels=False,
-                  grouped=False):
+                  grouped=False, transposed=False):
     """The integer consumer that can stand in for ``wrapper`` fed by ``activation_quantizer``, or None.  Uniform weights
     only with ``uniform_weights``; convolutions that need a patch matrix (QuantizedConv2d) only with ``convolutions``;
     depthwise convolutions (QuantizedDepthwiseConv2d) only with ``depthwise``; the other grouped convolutions
-    (QuantizedGroupedConv2d) only with ``grouped``; layers whose K is no multiple of 16 only with ``any_channels`` (QuantizedLinear
-    and the convolutions that are its product; never the depthwise or the grouped convolution).  Half-precision
+    (QuantizedGroupedConv2d) only with ``grouped``; transposed convolutions (QuantizedConvTranspose2d) only with ``transposed``;
+    layers whose K is no multiple of 16 only with ``any_channels`` (QuantizedLinear and the convolutions that are its product;
+    never the depthwise, the grouped or the transposed convolution).  Half-precision
     layers are refused by the classes: the integer consumer would change the output type."""
     layer = getattr(wrapper, "layer", None)
     if list(getattr(wrapper, "weights_quantizers", {})) != ["weight"]:
         return None
     if _is_uniform_weights(wrapper.weights_quantizers["weight"]) and not uniform_weights:
         return None
-    enabled = {None: True, "convolutions": convolutions, "depthwise": depthwise, "grouped": grouped}
+    enabled = {None: True, "convolutions": convolutions, "depthwise": depthwise, "grouped": grouped, "transposed": transposed}
     for cls, switch, fits in _CONSUMERS:
         extra = {"any_channels": True} if any_channels and issubclass(cls, QuantizedLinear) else {}
         if enabled[switch] and cls.eligible(layer, **extra) and (fits is None or fits(layer, bool(extra))):
@@ -2544,7 +2719,7 @@ def _fuse_residuals_into_producers(gm, mods) -> int:
 def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights: bool = False,
                           convolutions: bool = False, depthwise: bool = False, pools: bool = False,
                           avg_pools: bool = False, upsamples: bool = False, any_channels: bool = False,
-                          activation_tables: bool = False, grouped: bool = False) -> int:
+                          activation_tables: bool = False, grouped: bool = False, transposed: bool = False) -> int:
     """In every ``nn.Sequential`` of ``model``: an activation holder directly followed by a wrapped ``nn.Linear`` with
     a symmetric, power-of-two or LUT weights quantizer (int8 codebook values, at most 256 entries) becomes (Identity,
     QuantizedLinear); a wrapped pointwise ``nn.Conv2d`` likewise becomes a QuantizedConv1x1.  Returns the number of pairs
@@ -2574,6 +2749,13 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
     patch matrix.  It is independent of ``convolutions`` and ``depthwise`` and composes with every other switch; depthwise
     layers stay ``depthwise``'s, and layers with 1 to 3 channels per group stay on the float32 path.  By default such pairs are
     left alone.
+
+    ``transposed=True`` also fuses wrapped ``nn.ConvTranspose2d`` layers (``groups == 1``, dilation 1, ``in_channels % 16 == 0``,
+    strides of at most 4, ``ceil(kh / sh) * ceil(kw / sw) * in_channels`` <= 32768, any padding and output padding, the activation
+    zero point inside its clamp domain, a per-channel weights quantizer along the output channels, axis 1) into a
+    QuantizedConvTranspose2d: the learned upsampling of a decoder stage -- one stride-1 correlation per output phase on the codes
+    on the integer matrix cores (``mctq_qconv_transposed_i8``), without a zero-stuffed input.  It is independent of
+    ``convolutions`` and composes with every other switch.  By default such pairs are left alone.
 
     ``chain=True``: where one QuantizedLinear feeds the next directly, the float32 tensor between them is never
     materialised -- the first emits the second's activation codes from its epilogue (same codes, bit for bit, as
@@ -2632,7 +2814,7 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
             wrapper = seq[i + 4] if flat else seq[i + 3]
             if not isinstance(wrapper, PytorchQuantizationWrapper):
                 continue
-            fused = _consumer_for(wrapper, second.activation_holder_quantizer, uniform_weights, convolutions, depthwise, any_channels, grouped)
+            fused = _consumer_for(wrapper, second.activation_holder_quantizer, uniform_weights, convolutions, depthwise, any_channels, grouped, transposed)
             if fused is None or (type(fused) is QuantizedLinear) != flat:
                 continue
             try:
@@ -2651,7 +2833,7 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
             if not _plain_holder(holder) or not QuantizedUpsample.eligible(up) or not isinstance(wrapper, PytorchQuantizationWrapper):
                 continue
             reads_as = (holder if second is None else second).activation_holder_quantizer
-            fused = _consumer_for(wrapper, reads_as, uniform_weights, convolutions, depthwise, any_channels, grouped)
+            fused = _consumer_for(wrapper, reads_as, uniform_weights, convolutions, depthwise, any_channels, grouped, transposed)
             if fused is None or type(fused) is QuantizedLinear:
                 continue
             try:
@@ -2668,7 +2850,7 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
             if not _plain_holder(holder) or not _plain_holder(second) or not QuantizedActivationTable.eligible(fn) \
                     or not isinstance(wrapper, PytorchQuantizationWrapper):
                 continue
-            fused = _consumer_for(wrapper, second.activation_holder_quantizer, uniform_weights, convolutions, depthwise, any_channels, grouped)
+            fused = _consumer_for(wrapper, second.activation_holder_quantizer, uniform_weights, convolutions, depthwise, any_channels, grouped, transposed)
             if fused is None:
                 continue
             try:
@@ -2681,7 +2863,7 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
             holder, pool, wrapper = seq[i], seq[i + 1], seq[i + 2]
             if not _plain_holder(holder) or not QuantizedMaxPool2d.eligible(pool) or not isinstance(wrapper, PytorchQuantizationWrapper):
                 continue
-            fused = _consumer_for(wrapper, holder.activation_holder_quantizer, uniform_weights, convolutions, depthwise, any_channels, grouped)
+            fused = _consumer_for(wrapper, holder.activation_holder_quantizer, uniform_weights, convolutions, depthwise, any_channels, grouped, transposed)
             if fused is None or type(fused) is QuantizedLinear:
                 continue
             try:
@@ -2694,7 +2876,7 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
             holder, wrapper = seq[i], seq[i + 1]
             if not _plain_holder(holder) or not isinstance(wrapper, PytorchQuantizationWrapper):
                 continue
-            fused = _consumer_for(wrapper, holder.activation_holder_quantizer, uniform_weights, convolutions, depthwise, any_channels, grouped)
+            fused = _consumer_for(wrapper, holder.activation_holder_quantizer, uniform_weights, convolutions, depthwise, any_channels, grouped, transposed)
             if fused is None:
                 continue
             seq[i] = _FusedAway()
@@ -2713,7 +2895,7 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
                              stay_on_codes: bool = False, pools: bool = False, fused_residuals: bool = False,
                              concats: bool = False, avg_pools: bool = False, muls: bool = False,
                              hard_activations: bool = False, upsamples: bool = False, any_channels: bool = False,
-                             activation_tables: bool = False, grouped: bool = False):
+                             activation_tables: bool = False, grouped: bool = False, transposed: bool = False):
     """The same rewrite on an arbitrary module graph (MCT-exported models are not ``nn.Sequential``): traces ``model``
     with torch.fx keeping wrappers and holders as leaves, and wherever an activation holder's ONLY consumer is a
     wrapped ``nn.Linear`` the integer consumer can take (symmetric, power-of-two or LUT weights, and with
@@ -2723,7 +2905,9 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
     can take, and with ``grouped=True`` the other grouped convolutions a QuantizedGroupedConv2d can take (other grouped
     convolutions are always left alone unless ``grouped=True``; the switch needs no other and composes with all of them: such a
     consumer reads and emits codes like the other convolution consumers, takes folded clamps, and takes no residual and no
-    Hardswish / Hardsigmoid in its epilogue).
+    Hardswish / Hardsigmoid in its epilogue), and with ``transposed=True`` the transposed convolutions a QuantizedConvTranspose2d
+    can take (always left alone otherwise; independent of ``convolutions``, composes with every switch, reads and emits codes and
+    folded clamps like the grouped consumer; a call of the module with an ``output_size`` argument is left alone).
     Returns ``(graph_module, wrapped_layers_replaced)``.  Holders with several consumers (residual branches) stay, unless
     ``shared_holders=True``:
 
@@ -2885,7 +3069,7 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
     alone: a float32 user of the upsample or of B (FPN's ``lateral + upsample(top)``: a residual join does not read a
     QuantizedUpsample's codes yet); the modes bilinear, bicubic and area (ATen's interpolation expression is not reproduced bit
     for bit); ``antialias=True``; ``align_corners`` given; a ``size`` that is no constant (``size=skip.shape[2:]``);
-    ``nn.PixelShuffle`` and ``nn.ConvTranspose2d``; 3-D and 5-D inputs (a ``size`` / ``scale_factor`` of one or three entries);
+    ``nn.PixelShuffle`` (``nn.ConvTranspose2d`` is ``transposed=True``'s); 3-D and 5-D inputs (a ``size`` / ``scale_factor`` of one or three entries);
     an activation between the upsample and B.  A holder's float32 output is ``float(code - zp) * scale`` bit for bit and nearest
     interpolation only moves data, so the codes are bit for bit those B gives the float32 upsample, for any geometry and channel
     count (counts that are no multiple of 16 take torch ops), and the model rewritten with ``upsamples=True`` returns, bit for
@@ -2947,7 +3131,7 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
     gm = fx.GraphModule(model, graph)
     mods = dict(gm.named_modules())
     replaced = 0
-    consumer_for = lambda wrapper, q: _consumer_for(wrapper, q, uniform_weights, convolutions, depthwise, any_channels, grouped)      # noqa: E731
+    consumer_for = lambda wrapper, q: _consumer_for(wrapper, q, uniform_weights, convolutions, depthwise, any_channels, grouped, transposed)      # noqa: E731
     # Two whole passes, concatenations first: a concatenation absorbs an operand holder that sits behind a multiply, which the
     # multiply pass then no longer sees.
     if concats:

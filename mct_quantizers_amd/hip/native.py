@@ -179,6 +179,12 @@ SIGNATURES = {
                                              ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_int32,
                                              ctypes.c_int32]                                                      # y and its output form
                               + [ctypes.c_int64] * 5 + [ctypes.c_int32] * 9 + [ctypes.c_void_p]),           # B, H, W, C, O; groups, geometry; stream
+    "mctq_qconv_transposed_i8": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,   # a_codes, type, zero point, scale
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,  # w_codes, w_scales, w_rowsum, w_zero_points
+                                                ctypes.c_void_p,                                                     # bias
+                                                ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_int32,
+                                                ctypes.c_int32]                                                      # y and its output form
+                                 + [ctypes.c_int64] * 5 + [ctypes.c_int32] * 8 + [ctypes.c_void_p]),        # B, H, W, C, O; kernel, stride, padding, output padding; stream
     "mctq_fq_join_f32": (ctypes.c_int, [_c_f32p, _c_f32p, ctypes.c_int32, _c_f32p, ctypes.c_void_p, ctypes.c_int32,   # x, residual, relu, y, codes, code_dtype
                                         ctypes.c_int64, ctypes.c_float, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                         ctypes.c_void_p]),                                                            # n, scale, zero_point, qmin, qmax, stream
