@@ -99,6 +99,9 @@ extern "C" {
 /* v10 (additive, the version number stays): + mctq_qconv_transposed_i8, the transposed convolution on NHWC activation codes as
  * one stride-1 correlation per output phase on the integer matrix cores (the learned upsampling of a decoder stage stays on codes);
  * no existing signature or result changed. */
+/* v10 (additive, the version number stays): + mctq_qmatmul_i8, the batched product of two activation-code tensors by strides on
+ * the integer matrix cores (the Q.K^T and P.V products of an attention block stay on codes); no existing signature or result
+ * changed. */
 #define MCTQ_ABI_VERSION 10
 #define MCTQ_E_ARG (-10001)
 
@@ -883,6 +886,39 @@ int mctq_qconv_transposed_i8(const void* a_codes, int32_t a_code_dtype, int32_t 
                              int32_t y_quant_min, int32_t y_quant_max, int64_t batch, int64_t height, int64_t width,
                              int64_t channels, int64_t out_channels, int32_t kh, int32_t kw, int32_t stride_h, int32_t stride_w,
                              int32_t pad_h, int32_t pad_w, int32_t out_pad_h, int32_t out_pad_w, void* stream);
+
+/*
+ * Batched matrix product of two activation-code tensors (extension; the reference fake-quantizes both operands and runs the
+ * float32 torch.matmul): holder x holder, the Q.K^T and P.V products of an attention block.  Per batch (b0, b1)
+ *     acc[m][n] = sum over k < K of (a[m][k] - a_zero_point) * (b[k][n] - b_zero_point)
+ *     y[m][n]   = float(acc) * (a_scale * b_scale)
+ * The int32 sum is exact (K <= 32768 terms of |a - za| <= 255 times |b - zb| <= 255: below 2^31); then one float32 multiply
+ * of the two scales and one float32 multiply, each rounded once.  No bias, no residual, no activation.  Output forms as for
+ * mctq_qconv_grouped_i8: y_code_dtype < 0 -> y is float32 [batch0][batch1][m][n], contiguous; MCTQ_CODE_I8 / _U8 -> y holds
+ * the codes of (y_scale, y_zero_point) clamped to [y_quant_min, y_quant_max].
+ * Operands are views given by strides in elements (= bytes): a_codes is [batch0][batch1][m][k] with the strides a_stride_b0,
+ * a_stride_b1, a_stride_row and unit stride along k; b_codes is [batch0][batch1][n][k] (transposed_b != 0: "NT", Q.K^T) or
+ * [batch0][batch1][k][n] (transposed_b == 0: "NN", P.V; n % 16 == 0) likewise.  A batch stride of 0 broadcasts that operand.
+ * Each is int8 or uint8 (its code dtype), in any pair.  The K-contiguous operands (a_codes; b_codes in the NT form) are read
+ * in whole 16-byte chunks up to Kp = 16 * ceil(k / 16): the caller guarantees that bytes k .. Kp - 1 of every row exist and
+ * hold that operand's zero-point code (mctq_codes_im2col_pad_nhwc writes such rows).  In the NN form each 64 x 64 tile of b is
+ * transposed through LDS.  All DEVICE pointers, 16-byte aligned; all strides non-negative multiples of 16.
+ * One wave owns 16 rows x up to 64 columns (v_mfma_i32_16x16x64_i8); a block is four waves; grid ceil(m / 64) x
+ * ceil(n / 64) x batch0 * batch1.  No atomics, no split-K.
+ * MCTQ_E_ARG with a mctq_last_error text, before any pointer is read or anything is launched, for: a bad code dtype; a zero
+ * point outside its code type's range; a scale that is not finite and positive; negative extents; k outside 1 .. 32768; a
+ * bad output form (mctq_qlinear_i8_codes' checks); n % 16 != 0 in the NN form; m above 2^31 - 65 or n above 65535 * 64;
+ * batch0 * batch1 > 65535; negative or misaligned strides, or a row stride shorter than the (padded) row; an output of 2^63
+ * bytes or more; NULL or misaligned pointers of a non-empty problem; an output that overlaps an operand.  An empty extent
+ * (batch0, batch1, m or n == 0) returns 0 without a launch.
+ * mctq_last_launch names the launch "qmatmul_nt" / "qmatmul_nn", op "i8 x i8" / "u8 x i8" / "i8 x u8" / "u8 x u8" (a x b),
+ * U = 1 * (the column-sum MFMA ran: za' != 0) + 2 * (the row-sum MFMA ran: zb' != 0), z' = z - 128 for uint8 codes.
+ */
+int mctq_qmatmul_i8(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_point, float a_scale, int64_t a_stride_b0,
+                    int64_t a_stride_b1, int64_t a_stride_row, const void* b_codes, int32_t b_code_dtype, int32_t b_zero_point,
+                    float b_scale, int64_t b_stride_b0, int64_t b_stride_b1, int64_t b_stride_row, int32_t transposed_b, void* y,
+                    int32_t y_code_dtype, float y_scale, int32_t y_zero_point, int32_t y_quant_min, int32_t y_quant_max,
+                    int64_t batch0, int64_t batch1, int64_t m, int64_t n, int64_t k, void* stream);
 
 /*
  * The join in front of an activation holder that several layers share (extension; the reference runs an ATen add, an ATen

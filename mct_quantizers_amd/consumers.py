@@ -127,12 +127,24 @@ tail round differently, they equal the chain's wherever its float32 value equals
 rounding tie elsewhere.  Out of scope: the lookup inside the producing consumer's epilogue (``emit_table``, beside ``emit_act``).
 Measured / not measured: see the README paragraph and ``profiles/EXPERIMENTS.md``.
 
+The activation x activation products stay on codes with ``fuse_linear_consumers_fx(..., matmuls=True)``: ``torch.matmul`` / ``@`` /
+``torch.bmm`` of two holder outputs through reshapes and permutes -- the ``Q @ K.transpose(-1, -2)`` and ``P @ V`` of every attention
+block as an MCT export of a ViT, DeiT, Swin or BERT decomposes it.  Both operands are ``float(code - zp) * scale`` bit for bit, so the
+product is the exact integer ``sum_k (qa - za) * (qb - zb)`` scaled once by ``float32(sa) * float32(sb)``: ``QuantizedMatmul``
+(``qmatmul_i8``, ``mctq_qmatmul_i8``) runs it on the integer matrix cores with its operands taken by strides -- ``[B, T, H, D]`` storage
+read as ``[B, H, T, D]`` goes to the kernel as it is -- and returns float32 or the codes of the holder behind it; with
+``stay_on_codes=True`` the q / k / v consumers emit the operands' codes and the context's codes feed the projection, so Q, K, V and the
+context never exist in float32.  It equals the float32 chain bit for bit where that chain's product is exact (power-of-two scales,
+``255 * 255 * K < 2^24``) and differs by its accumulation rounding elsewhere.
+Measured / not measured: see the README paragraph and ``profiles/EXPERIMENTS.md``.
+
 The six modules derive from ``IntegerConsumer``, which owns what they share: the checks of the quantizers and of the float32
 weight and bias, the cache of the weight's codes, the step from ``forward``'s input to activation codes, ``from_wrapper`` and
 the ``emit_codes_for`` / ``emit_clamp`` output form.  ``QuantizedLinear`` is the product over ``[O, K]`` rows; ``QuantizedConv1x1``
 and ``QuantizedConv2d`` are that product and derive from it; ``QuantizedDepthwiseConv2d``, ``QuantizedGroupedConv2d`` and
 ``QuantizedConvTranspose2d`` are not and derive from ``IntegerConsumer`` directly.  "Any integer consumer" in the graph rewrites is ``isinstance(m, IntegerConsumer)``.  The modules
-without weights -- the pools, ``QuantizedUpsample``, ``QuantizedActivationTable``, ``QuantizedConcat``, ``QuantizedMul``, ``QuantizedJoin`` --
+without weights -- the pools, ``QuantizedUpsample``, ``QuantizedActivationTable``, ``QuantizedConcat``, ``QuantizedMul``, ``QuantizedMatmul``,
+``QuantizedJoin`` --
 derive from ``_OnCodes``;
 ``_operand_codes`` is the one step from an operand of ``forward`` to codes, theirs and the consumers' (the join has its own kernel).
 
@@ -632,6 +644,116 @@ def qconv_transposed_i8(a_codes_nhwc: torch.Tensor, a_zero_point: int, a_scale: 
             canvas[:, ky:ky + (h - 1) * sh + 1:sh, kx:kx + (w_ - 1) * sw + 1:sw] += torch.einsum("bhwc,oc->bhwo", a32, w32[:, ky, kx])
     acc = canvas[:, ph:ph + ho, pw:pw + wo].contiguous()
     return _cpu_epilogue(acc, a_scale, w_scales, bias, out_codes)
+
+
+_MATMUL_MAX_BATCH = 65535                                # grid z of one mctq_qmatmul_i8 launch: beyond it the batch is split along B0
+_MATMUL_MAX_M, _MATMUL_MAX_N = (1 << 31) - 65, 65535 * 64
+
+
+def _matmul_form(codes, form, name):
+    """``(scale, zero_point)`` of an operand of ``qmatmul_i8`` (the first two entries of ``form``), checked against its codes."""
+    if not isinstance(codes, torch.Tensor) or codes.dtype not in (torch.int8, torch.uint8):
+        raise TypeError(f"qmatmul_i8 takes int8 / uint8 codes, got {getattr(codes, 'dtype', type(codes).__name__)} for {name}")
+    if codes.dim() < 1:
+        raise RuntimeError(f"qmatmul_i8: {name} must have at least one dimension")
+    scale, zp = float(form[0]), int(form[1])
+    ops._check_form("qmatmul_i8", codes.dtype, zp, scale, zp_words=f"{name}'s zero point {{}}", scale_words=f"{name}'s scale")
+    return scale, zp
+
+
+def _matmul_view(codes, zp, k_contiguous: bool):
+    """An operand of ``mctq_qmatmul_i8`` as the kernel takes it, a view wherever that is possible: unit stride along the last
+    dimension, every other stride a non-negative multiple of 16, a 16-byte aligned pointer, rows that do not overlap.  A
+    K-contiguous operand whose K is no multiple of 16 is re-pitched to rows of ``Kp = 16 * ceil(K / 16)`` columns whose tail
+    holds the zero-point code (``ops.codes_im2col(..., pad_to=16)``: one more launch); any other view that fails is copied."""
+    rows, cols = codes.shape[-2:]
+    if k_contiguous and cols % 16:
+        return ops.codes_im2col(codes.reshape(-1, cols), 1, pad_to=16, pad_code=zp).reshape(*codes.shape[:-1], -1)
+    strides_ok = all(codes.shape[d] == 1 or (codes.stride(d) >= 0 and codes.stride(d) % 16 == 0) for d in range(codes.dim() - 1))
+    if codes.stride(-1) == 1 and strides_ok and codes.data_ptr() % 16 == 0 and (rows == 1 or codes.stride(-2) >= cols):
+        return codes
+    return codes.clone(memory_format=torch.contiguous_format)
+
+
+def _matmul_strides(t):
+    """(B0, B1, rows) strides of a 4-D view for the kernel: a dimension of size 1 is never stepped along."""
+    return tuple(0 if t.shape[d] == 1 else t.stride(d) for d in range(3))
+
+
+def qmatmul_i8(a_codes: torch.Tensor, a_form, b_codes: torch.Tensor, b_form, *, transposed_b: bool, out_codes=None) -> torch.Tensor:
+    """Batched matrix product of two activation-code tensors: a_codes ``[..., M, K]`` and b_codes ``[..., N, K]``
+    (``transposed_b=True``, the Q.K^T form, "NT") or ``[..., K, N]`` (``transposed_b=False``, the P.V form, "NN"), int8 or uint8 in any
+    pair, each per-tensor affine with ``form = (scale, zero_point)``; leading dimensions broadcast as ``torch.matmul``'s do (and
+    1-D operands are taken as it takes them) ->
+
+        acc[m][n] = sum_k (a[m][k] - za) * (b[k][n] - zb)          an exact integer: K <= 32768, 255 * 255 * 32768 < 2^31
+        y = float32(acc) * s,   s = float32(sa) * float32(sb)       one float32 multiply each, as ``_cpu_epilogue``
+
+    float32, or with ``out_codes = (scale, zero_point, qmin, qmax[, lo, hi])`` the codes of that activation quantizer, bit-identical
+    to ``ops.fq_codes`` of the float32 result.  No bias, no residual, no activation.
+
+    GPU tensors with one or two batch dimensions (after broadcasting; both operands at least 2-D, one at least 3-D) run
+    ``mctq_qmatmul_i8`` on views: ``[B, T, H, D]`` storage read as ``[B, H, T, D]`` goes to the kernel as it is, a broadcast operand
+    with a batch stride of 0.  A view is copied only where a stride or the pointer is no multiple of 16 bytes or the last
+    dimension is not contiguous; a K-contiguous operand with ``K % 16 != 0`` (the 197-wide probability rows of a ViT) is re-pitched
+    to ``Kp = 16 * ceil(K / 16)`` columns with the zero-point code in the tail -- one more launch (two where the view is not
+    contiguous), as ``any_channels`` costs.  More than 65535 batches are split along the first batch dimension.  Every other GPU
+    case -- 2-D or 1-D operands, more than two batch dimensions, ``N % 16 != 0`` in the NN form, sizes beyond one launch -- and CPU
+    tensors run the same contract with exact torch ops (CPU: an int64 product; GPU: a float64 product, exact since
+    ``|acc| < 2^53``).
+
+    Where the float32 ``torch.matmul`` of the two dequantized operands is exact (power-of-two scales, ``255 * 255 * K < 2^24``) the
+    result equals that chain bit for bit; elsewhere it differs by the float32 accumulation rounding of the chain."""
+    import numpy as np
+    a_scale, a_zp = _matmul_form(a_codes, a_form, "a_codes")
+    b_scale, b_zp = _matmul_form(b_codes, b_form, "b_codes")
+    if a_codes.device != b_codes.device:
+        raise RuntimeError(f"qmatmul_i8: a_codes on {a_codes.device}, b_codes on {b_codes.device}")
+    transposed_b = bool(transposed_b) and b_codes.dim() >= 2              # (the transpose of a vector is the vector)
+    K = a_codes.shape[-1]
+    b_k = b_codes.shape[-1] if transposed_b or b_codes.dim() == 1 else b_codes.shape[-2]
+    if b_k != K:
+        raise _k_mismatch(K, b_k, "the second operand")
+    if not 1 <= K <= _MAX_K:
+        raise NotImplementedError(f"qmatmul_i8 needs 1 <= K <= {_MAX_K}, got K={K}")
+    if out_codes is not None:
+        _with_clamp(out_codes)
+    if a_codes.is_cuda and a_codes.dim() >= 2 and b_codes.dim() >= 2 and max(a_codes.dim(), b_codes.dim()) in (3, 4):
+        M, N = a_codes.shape[-2], b_codes.shape[-2 if transposed_b else -1]
+        batch = torch.broadcast_shapes(a_codes.shape[:-2], b_codes.shape[:-2])
+        b0, b1 = (1, *batch) if len(batch) == 1 else batch
+        if (transposed_b or N % 16 == 0) and b1 <= _MATMUL_MAX_BATCH and M <= _MATMUL_MAX_M and N <= _MATMUL_MAX_N:
+            tdt, *form = _output_form(out_codes)
+            y = a_codes.new_empty((b0, b1, M, N), dtype=tdt)
+            if y.numel():
+                a4 = _matmul_view(a_codes, a_zp, True)
+                b4 = _matmul_view(b_codes, b_zp, transposed_b)
+                if a4.shape[:-2] != batch:
+                    a4 = a4.expand(*batch, *a4.shape[-2:])
+                if b4.shape[:-2] != batch:
+                    b4 = b4.expand(*batch, *b4.shape[-2:])
+                if len(batch) == 1:
+                    a4, b4 = a4.unsqueeze(0), b4.unsqueeze(0)
+                step = max(1, _MATMUL_MAX_BATCH // b1)
+                for at in range(0, b0, step):
+                    a_, b_ = (a4, b4) if step >= b0 else (a4[at:at + step], b4[at:at + step])
+                    # (a slab of a split batch is written to a buffer of its own: its offset inside y need not be 16-byte aligned)
+                    y_ = y if step >= b0 else y.new_empty((a_.shape[0], b1, M, N))
+                    ops._gpu_call("mctq_qmatmul_i8", a_, a_.data_ptr(), ops._code_of(a_), a_zp, a_scale, *_matmul_strides(a_),
+                                  b_.data_ptr(), ops._code_of(b_), b_zp, b_scale, *_matmul_strides(b_), int(transposed_b),
+                                  y_.data_ptr(), *form, y_.shape[0], b1, M, N, K)
+                    if y_ is not y:
+                        y[at:at + step].copy_(y_)
+            return y.reshape(*batch, M, N)
+    elif not a_codes.is_cuda:
+        ops._cpu_route_allowed()
+    wide = torch.float64 if a_codes.is_cuda else torch.int64
+    a_wide, b_wide = a_codes.to(wide) - a_zp, b_codes.to(wide) - b_zp
+    acc = torch.matmul(a_wide, b_wide.transpose(-1, -2) if transposed_b else b_wide)
+    with np.errstate(all="ignore"):
+        s = float(np.float32(a_scale) * np.float32(b_scale))
+    y = acc.to(torch.float32) * s
+    return y if out_codes is None else _cpu_out_codes(y, out_codes)
 
 
 def pack_w4(codes: torch.Tensor) -> torch.Tensor:
@@ -1244,7 +1366,7 @@ def _ints_or_pair(v) -> bool:
 
 class _OnCodes(nn.Module):
     """Base of the modules without weights that read or write activation codes -- the pools, QuantizedUpsample, QuantizedActivationTable,
-    QuantizedConcat, QuantizedMul and QuantizedJoin: with the wrappers, the holders and the integer consumers, the leaves of the graph rewrite's tracer."""
+    QuantizedConcat, QuantizedMul, QuantizedMatmul and QuantizedJoin: with the wrappers, the holders and the integer consumers, the leaves of the graph rewrite's tracer."""
 
 
 class QuantizedMaxPool2d(_OnCodes):
@@ -1604,15 +1726,16 @@ class QuantizedActivationTable(_OnCodes):
 
 
 class _OperandsOnCodes(_OnCodes):
-    """What QuantizedConcat and QuantizedMul share: several operands, each read as the codes of its own holder's quantizer,
-    and one output holder's quantizer, all per-tensor affine of at most 8 bits (``_code_form``)."""
+    """What QuantizedConcat, QuantizedMul and QuantizedMatmul share: several operands, each read as the codes of its own holder's
+    quantizer, and one output holder's quantizer, all per-tensor affine of at most 8 bits (``_code_form``).  With
+    ``float_output`` (QuantizedMatmul) the output quantizer may be missing: the module then returns float32."""
 
-    def __init__(self, operand_quantizers, activation_quantizer):
+    def __init__(self, operand_quantizers, activation_quantizer, float_output: bool = False):
         super().__init__()
         self.operand_quantizers = tuple(operand_quantizers)
         self.activation_quantizer = activation_quantizer
         self._forms = tuple(_code_form(q) for q in self.operand_quantizers)
-        self._out_form = _code_form(activation_quantizer)
+        self._out_form = None if float_output and activation_quantizer is None else _code_form(activation_quantizer)
 
     def operand_code_params(self, i: int):
         """(scale, zero_point, qmin, qmax) of the codes operand ``i`` is read as."""
@@ -1718,6 +1841,40 @@ class QuantizedMul(_OperandsOnCodes):
             y = ops.codes_mul((self._codes_of(0, x0, False), s0, z0), (self._codes_of(1, x1, False), s1, z1), self._out_form)
             return y.contiguous(memory_format=torch.channels_last) if y.dim() == 4 else y
         return y.permute(0, 3, 1, 2) if y.dim() == 4 else y
+
+
+class QuantizedMatmul(_OperandsOnCodes):
+    """``activation holders A, B -> torch.matmul / @ / torch.bmm [-> activation holder C]`` on integer codes: the activation x
+    activation product, in practice the two products of every attention block, ``Q @ K.transpose(-1, -2)`` and ``P @ V``.  Both
+    operands are ``float(code - zp) * scale`` bit for bit, so the product is the exact integer sum of ``(qa - za) * (qb - zb)`` scaled
+    once -- ``qmatmul_i8`` (``mctq_qmatmul_i8``, the integer matrix cores), where the float32 chain runs two holders and a float32
+    matmul; it differs from that chain only by the chain's own float32 accumulation rounding (not at all where that is exact:
+    power-of-two scales and ``255 * 255 * K < 2^24``).
+
+    ``operand_quantizers``: the two operand holders' quantizers, in the order of ``forward``'s operands; ``activation_quantizer``:
+    C's, or None.  Per-tensor affine activation quantizers of at most 8 bits whose zero points are codes of their type.
+    ``transposed_b=True``: the second operand arrives as ``[..., N, K]`` and the product is taken with its last two dimensions
+    swapped, without moving data (the ``k.transpose(-1, -2)`` of the scores).  ``forward(x0, x1)`` takes each operand as the codes
+    of its quantizer (int8 / uint8 of its code type) or as a float32 tensor, which it quantizes in that operand's form -- the
+    holder's input and its output give the same codes; these operands are matrices, not images: their shape and strides are
+    what they are, a permuted ``[B, T, H, D]`` view goes to the kernel as it is.  It returns float32, or with an
+    ``activation_quantizer`` that holder's codes (contiguous ``[..., M, N]``), which a QuantizedLinear or another QuantizedMatmul of
+    that quantizer takes as they are -- through reshapes and permutes, which only move data.  ``activation_code_params`` is the
+    OUTPUT form (None for float32), ``operand_code_params(i)`` what ``emit_codes_for`` of the layer in front of operand ``i`` takes."""
+
+    def __init__(self, operand_quantizers, activation_quantizer=None, transposed_b: bool = False):
+        operand_quantizers = tuple(operand_quantizers)
+        if len(operand_quantizers) != 2:
+            raise ValueError("QuantizedMatmul takes the quantizers of two operands")
+        super().__init__(operand_quantizers, activation_quantizer, float_output=True)
+        self.transposed_b = bool(transposed_b)
+
+    def extra_repr(self) -> str:
+        return f"transposed_b={self.transposed_b}, output={'float32' if self._out_form is None else 'codes'}"
+
+    def forward(self, x0: torch.Tensor, x1: torch.Tensor) -> torch.Tensor:
+        a, b = self._codes_of(0, x0, nhwc=False), self._codes_of(1, x1, nhwc=False)
+        return qmatmul_i8(a, self._forms[0][:2], b, self._forms[1][:2], transposed_b=self.transposed_b, out_codes=self._out_form)
 
 
 # In the order they are tried: (class, the switch of the rewrites that enables it or None, what fusing asks of the layer beyond
@@ -2302,7 +2459,8 @@ def _join_shared_holders(gm, mods, consumer_for, pools: bool = False, avg_pools:
     pool pair with nothing to absorb is left to ``_pool_lone_holders``.  With ``avg_pools`` the same holds for an average pool
     in front of a second holder (``_avg_pool_plan``), as a QuantizedAvgPool2d.  A QuantizedMul among the users
     (``_operator_between_holders``, which built it with this holder's quantizer at that operand) reads the join's codes too, at
-    whichever operand position the holder occupies.  With ``upsamples`` a nearest upsample among the users whose readers all read
+    whichever operand position the holder occupies, and so does a user that leads, through layout-only nodes, to operands of a
+    QuantizedMatmul built with this holder's quantizer (``_matmuls_on_codes``).  With ``upsamples`` a nearest upsample among the users whose readers all read
     codes (``_upsample_plan``) does so as a QuantizedUpsample, and the holder behind such an upsample is left to that plan; with
     ``activation_tables`` likewise a run of elementwise activations (``_table_plan``), as a QuantizedActivationTable.
     Returns the number of wrapped layers replaced."""
@@ -2322,6 +2480,13 @@ def _join_shared_holders(gm, mods, consumer_for, pools: bool = False, avg_pools:
             pooled = [(user, plan) for user, plan in plans if plan is not None]
         # M: the QuantizedMul nodes of ``_operator_between_holders`` that read this holder (built with its quantizer at those operands)
         muls = [user for user in node.users if isinstance(_module_of(user, mods), QuantizedMul) and not user.kwargs]
+        # ... and the users that lead, through layout-only nodes, to operands of a QuantizedMatmul built with this quantizer
+        # (``_matmuls_on_codes``): they move the join's codes as they would have moved the float32 tensor
+        try:
+            muls += [user for user in node.users
+                     if _reads_as_matmul_operands(user, node, _code_form(quantizer), mods) and all(user is not t for t in muls)]
+        except (TypeError, ValueError, NotImplementedError):
+            pass
         if not taken and not pooled and not muls:
             continue
         on_codes = [t for t, _ in taken] + [t for t, _ in pooled] + muls
@@ -2485,6 +2650,213 @@ def _operator_between_holders(gm, mods, consumer_for, pools, operands_of, cls, s
     return replaced
 
 
+_LAYOUT_METHODS = ("reshape", "view", "permute", "transpose", "contiguous", "flatten", "unflatten")
+_LAYOUT_FUNCTIONS = (torch.reshape, torch.permute, torch.transpose, torch.flatten, torch.unflatten)
+
+
+def _layout_input(node):
+    """The tensor operand of ``node`` if it is a layout-only node, else None: ``reshape``, ``view``, ``permute``, ``transpose``,
+    ``contiguous``, ``flatten``, ``unflatten`` (methods, or the ``torch.`` functions of those names) with integer arguments --
+    never a ``view(dtype)`` --, ``operator.getitem`` with one constant integer index, or ``.mT``.  Such a node only moves data, so it
+    commutes with coding: the codes of its output are its output on the codes.  The one list of both sides of a QuantizedMatmul."""
+    from torch.fx import Node
+    if not node.args or not isinstance(node.args[0], Node):
+        return None
+
+    def ints(v):
+        if isinstance(v, (tuple, list, torch.Size)):
+            return all(ints(e) for e in v)
+        return isinstance(v, (int, torch.memory_format)) and not isinstance(v, bool)
+
+    rest = node.args[1:]
+    if node.op == "call_function" and node.target is operator.getitem:
+        ok = len(rest) == 1 and isinstance(rest[0], int) and not isinstance(rest[0], bool) and not node.kwargs
+    elif node.op == "call_function" and node.target is getattr:
+        ok = rest == ("mT",)
+    else:
+        ok = (node.op == "call_method" and node.target in _LAYOUT_METHODS) or \
+            (node.op == "call_function" and node.target in _LAYOUT_FUNCTIONS)
+        ok = ok and ints(rest) and ints(tuple(node.kwargs.values()))
+    return node.args[0] if ok else None
+
+
+def _layout_name(node) -> str:
+    return node.target if node.op == "call_method" else getattr(node.target, "__name__", "")
+
+
+def _behind_layout_chain(node):
+    """The node a layout-only chain that ends in ``node`` starts from (``node`` itself where it is no layout node)."""
+    while _layout_input(node) is not None:
+        node = _layout_input(node)
+    return node
+
+
+def _layout_rank(node):
+    """The rank of a layout node's output where its own arguments or those of the chain in front tell it, else None."""
+    src = _layout_input(node)
+    if src is None:
+        return None
+    name, rest = _layout_name(node), node.args[1:]
+    if name in ("permute", "reshape", "view"):
+        return len(rest[0]) if len(rest) == 1 and isinstance(rest[0], (tuple, list)) else len(rest) or None
+    if name in ("transpose", "contiguous", "getattr"):
+        return _layout_rank(src)
+    if name == "getitem":
+        rank = _layout_rank(src)
+        return None if rank is None else rank - 1
+    return None
+
+
+def _swaps_last_two(node) -> bool:
+    """``node`` is ``x.transpose(-1, -2)`` / ``torch.transpose(x, -1, -2)``, in either order, a positive-index spelling of it (where
+    the chain in front tells the rank: behind a permute, reshape or view), or ``x.mT``."""
+    if _layout_input(node) is None:
+        return False
+    name = _layout_name(node)
+    if name == "getattr":
+        return True
+    if name != "transpose":
+        return False
+    dims = tuple(node.args[1:]) + tuple(node.kwargs.get(k) for k in ("dim0", "dim1") if k in node.kwargs)
+    if len(dims) != 2:
+        return False
+    if set(dims) == {-1, -2}:
+        return True
+    rank = _layout_rank(node)
+    return rank is not None and {d % rank for d in dims} == {rank - 1, rank - 2}
+
+
+def _matmul_operands(node):
+    """The two operand nodes of ``node`` if it is ``torch.matmul`` / ``@`` / ``Tensor.matmul`` / ``torch.bmm`` of two tensors without
+    keyword arguments, else None."""
+    from torch.fx import Node
+    if node.kwargs or len(node.args) != 2 or not all(isinstance(a, Node) for a in node.args):
+        return None
+    if node.op == "call_function":
+        ok = node.target in (torch.matmul, operator.matmul, torch.bmm)
+    else:
+        ok = node.op == "call_method" and node.target == "matmul"
+    return tuple(node.args) if ok else None
+
+
+def _reads_as_matmul_operands(user, via, form, mods) -> bool:
+    """``user`` reads ``via`` -- a tensor that is, or stands for, codes of ``form`` -- only as such codes: a QuantizedMatmul that
+    takes it at operands of that form, or a layout-only node (``_layout_input``) every user of which does in turn."""
+    m = _module_of(user, mods)
+    if isinstance(m, QuantizedMatmul):
+        return not user.kwargs and len(user.args) == 2 and \
+            all(m.operand_code_params(i) == tuple(form) for i, a in enumerate(user.args) if a is via)
+    if _layout_input(user) is not via or not user.users:
+        return False
+    return all(_reads_as_matmul_operands(u, user, form, mods) for u in user.users)
+
+
+def _matmul_operand_form(node, mods):
+    """The one form (scale, zero_point, qmin, qmax) in which every user of ``node`` reads it as a QuantizedMatmul operand,
+    through layout-only nodes (``_reads_as_matmul_operands``), or None."""
+    at = node
+    while at.users:                                      # any one leaf names the form; all of them must agree on it
+        user = next(iter(at.users))
+        m = _module_of(user, mods)
+        if isinstance(m, QuantizedMatmul):
+            form = next((m.operand_code_params(i) for i, a in enumerate(user.args) if a is at), None)
+            if form is None or not all(_reads_as_matmul_operands(u, node, form, mods) for u in node.users):
+                return None
+            return form
+        if _layout_input(user) is not at:
+            return None
+        at = user
+    return None
+
+
+def _matmuls_on_codes(gm, mods, consumer_for) -> int:
+    """``fuse_linear_consumers_fx(matmuls=True)``, three steps.  (1) Every matmul node (``_matmul_operands``) each operand of which
+    leads back to a plain holder's output through layout-only nodes (``_layout_input``) becomes a QuantizedMatmul node with the two
+    holders' quantizers; a final swap of the last two dimensions on the second operand that feeds nothing else
+    (``_swaps_last_two``) is absorbed as ``transposed_b=True`` and leaves the graph.  (2) A plain holder that is the one user of such
+    a node and every user of which reads codes -- through layout-only nodes: a wrapped ``nn.Linear`` ``consumer_for`` can take, fed
+    by it alone, which becomes a QuantizedLinear; an operand of a QuantizedMatmul of that form -- is absorbed: the node emits
+    its codes.  Likewise where the node's one user is a QuantizedConcat / QuantizedMul that absorbed the holder and reads the
+    node at one operand.  (3) An operand holder every user of which leads to QuantizedMatmul operands leaves the graph: the
+    module quantizes that holder's input (or, with ``stay_on_codes``, the layer in front emits the codes); a holder with other
+    users stays and the module quantizes its float32 output -- the same codes.  Returns the number of wrapped layers replaced."""
+    replaced, made = 0, []
+    for node in list(gm.graph.nodes):
+        operands = _matmul_operands(node)
+        if operands is None:
+            continue
+        x0, x1 = operands
+        transposed = _swaps_last_two(x1) and len(x1.users) == 1
+        ends = (x0, x1.args[0] if transposed else x1)
+        holders = [_holder_of(_behind_layout_chain(e), mods) for e in ends]
+        if None in holders:
+            continue
+        try:
+            module = QuantizedMatmul([h.activation_holder_quantizer for h in holders], None, transposed_b=transposed)
+        except (TypeError, ValueError, NotImplementedError):
+            continue
+        name = node.name + "_qmatmul"
+        gm.add_submodule(name, module)
+        mods[name] = module
+        with gm.graph.inserting_before(node):
+            new = gm.graph.call_module(name, ends)
+        node.replace_all_uses_with(new)
+        gm.graph.erase_node(node)
+        if transposed:
+            gm.graph.erase_node(x1)
+        made.append(new)
+    for new in made:                                         # (2) the holder behind
+        if len(new.users) != 1:
+            continue
+        behind = next(iter(new.users))
+        module, reader = mods[new.target], _module_of(behind, mods)
+        taken, quantizer = [], None
+        if isinstance(reader, (QuantizedConcat, QuantizedMul)) and not behind.kwargs and sum(a is new for a in behind.args) == 1:
+            quantizer, hnode = reader.operand_quantizers[next(i for i, a in enumerate(behind.args) if a is new)], None
+        else:
+            holder, hnode = _holder_of(behind, mods), behind
+            if holder is None or not hnode.users:
+                continue
+            quantizer = holder.activation_holder_quantizer
+            try:
+                form = _code_form(quantizer)
+            except (TypeError, ValueError, NotImplementedError):
+                continue
+
+            def reads_codes(user, via):
+                fused = _wrapped_consumer(user, via, mods, quantizer, consumer_for)
+                if fused is not None:
+                    taken.append((user, fused))
+                    return type(fused) is QuantizedLinear
+                if isinstance(_module_of(user, mods), QuantizedMatmul):
+                    return _reads_as_matmul_operands(user, via, form, mods)
+                return _layout_input(user) is via and bool(user.users) and all(reads_codes(u, user) for u in user.users)
+
+            if not all(reads_codes(u, hnode) for u in hnode.users):
+                continue
+        try:
+            emitting = QuantizedMatmul(module.operand_quantizers, quantizer, transposed_b=module.transposed_b)
+        except (TypeError, ValueError, NotImplementedError):
+            continue
+        setattr(gm, new.target, emitting)                    # (the name has no dots: step (1) made it)
+        mods[new.target] = emitting
+        for user, fused in taken:
+            _install_consumer(gm, mods, user, fused)
+            replaced += 1
+        if hnode is not None:
+            hnode.replace_all_uses_with(new)
+            gm.graph.erase_node(hnode)
+    for node, holder in _holder_calls(gm, mods):             # (3) the operand holders nobody else reads
+        try:
+            form = _code_form(holder.activation_holder_quantizer)
+        except (TypeError, ValueError, NotImplementedError):
+            continue
+        if node.users and all(_reads_as_matmul_operands(u, node, form, mods) for u in node.users):
+            node.replace_all_uses_with(node.args[0])
+            gm.graph.erase_node(node)
+    return replaced
+
+
 def _clamp_range(node, mods):
     """(a, b) if ``node`` is a clamp activation of one tensor that ``folded_clamp`` can fold -- a ReLU (as ``_relu_input``),
     ``nn.ReLU6`` / ``F.relu6``, ``nn.Hardtanh`` / ``F.hardtanh`` with finite ``min_val <= max_val`` -- else None.  In-place forms
@@ -2591,13 +2963,17 @@ def _identities_as_codes(gm, mods) -> int:
 
 def _reads_codes_once(reader, codes, form, mods) -> bool:
     """``reader`` takes the node ``codes`` -- activation codes of ``form`` -- at exactly one operand and reads it as that form:
-    a module of ``_CODE_READERS`` whose one argument it is, or a QuantizedMul, which has two operands, at one of them."""
+    a module of ``_CODE_READERS`` whose one argument it is, or a QuantizedMul or QuantizedMatmul, which have two operands, at one
+    of them -- or a layout-only node behind which every reader is a QuantizedMatmul operand of that form
+    (``_reads_as_matmul_operands``)."""
     m = _module_of(reader, mods)
+    if m is None:
+        return _reads_as_matmul_operands(reader, codes, form, mods)
     if reader.kwargs or sum(a is codes for a in reader.args) != 1:
         return False
     if isinstance(m, _CODE_READERS):
         return len(reader.args) == 1
-    return isinstance(m, QuantizedMul) and len(reader.args) == 2 and \
+    return isinstance(m, (QuantizedMul, QuantizedMatmul)) and len(reader.args) == 2 and \
         m.operand_code_params(0 if reader.args[0] is codes else 1) == tuple(form)
 
 
@@ -2614,12 +2990,25 @@ def _fold_clamps_into_producers(gm, mods, hard_activations: bool = False) -> int
     among whose arguments the consumer's output (or its one clamp activation) occurs exactly once, at index i: the consumer then
     emits the codes of ``operand_code_params(i)``, the clamp folded in, and that one argument becomes the consumer's output.  A
     QuantizedMul is such a reader too, directly or among the readers of a join's codes, where those codes occur at exactly one
-    of its two operands (``x * x`` is left to the module's float32 quantize path).  Returns the number of producers that now
-    emit codes."""
+    of its two operands (``x * x`` is left to the module's float32 quantize path).  A QuantizedMatmul is such a reader as well,
+    directly (a clamp activation in between is folded) or -- without an activation -- through layout-only nodes
+    (``_layout_input``: the reshape and permute between a q / k / v layer and the product, which then move int8): every user of the
+    consumer must lead to QuantizedMatmul operands of one form (``_matmul_operand_form``), which the consumer then emits.  Returns
+    the number of producers that now emit codes."""
     folded = 0
     for node in list(gm.graph.nodes):
         producer = _module_of(node, mods)
-        if not isinstance(producer, IntegerConsumer) or producer.emit_codes_for is not None or len(node.users) != 1:
+        if not isinstance(producer, IntegerConsumer) or producer.emit_codes_for is not None:
+            continue
+        if node.users and _module_of(next(iter(node.users)), mods) is None:
+            # every user leads, through layout-only nodes and no activation, to QuantizedMatmul operands of one form (the holder
+            # in between went into them: _matmuls_on_codes): the producer emits that form and the chain moves int8
+            form = _matmul_operand_form(node, mods)
+            if form is not None and len(node.args) == 1:
+                producer.emit_codes_for = form
+                folded += 1
+                continue
+        if len(node.users) != 1:
             continue
         nxt, act, rng, hard = next(iter(node.users)), None, (-math.inf, math.inf), None
         if _clamp_range(nxt, mods) is not None and len(nxt.users) == 1:
@@ -2633,7 +3022,7 @@ def _fold_clamps_into_producers(gm, mods, hard_activations: bool = False) -> int
             continue
         behind, gone, src, concat_args = mods.get(nxt.target), [nxt], act or node, None
         via = src                                        # what the readers read now
-        if isinstance(behind, (QuantizedConcat, QuantizedMul)):
+        if isinstance(behind, (QuantizedConcat, QuantizedMul, QuantizedMatmul)):
             if sum(a is src for a in nxt.args) != 1:
                 continue                                 # (the same tensor at two places -- x * x, two forms of a cat: left alone)
             at = next(i for i, a in enumerate(nxt.args) if a is src)
@@ -2895,7 +3284,8 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
                              stay_on_codes: bool = False, pools: bool = False, fused_residuals: bool = False,
                              concats: bool = False, avg_pools: bool = False, muls: bool = False,
                              hard_activations: bool = False, upsamples: bool = False, any_channels: bool = False,
-                             activation_tables: bool = False, grouped: bool = False, transposed: bool = False):
+                             activation_tables: bool = False, grouped: bool = False, transposed: bool = False,
+                             matmuls: bool = False):
     """The same rewrite on an arbitrary module graph (MCT-exported models are not ``nn.Sequential``): traces ``model``
     with torch.fx keeping wrappers and holders as leaves, and wherever an activation holder's ONLY consumer is a
     wrapped ``nn.Linear`` the integer consumer can take (symmetric, power-of-two or LUT weights, and with
@@ -3113,7 +3503,37 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
     On the CPU ATen's vector body and scalar tail give different last bits for sigmoid, SiLU, softplus, ELU, Mish, tanh and GELU
     (0.007 - 0.08 % of elements, erf-GELU 2.6 %): there the node equals the chain wherever the chain's float32 value equals the
     table's and can differ by one code next to a rounding tie elsewhere.  Out of scope: looking the table up inside the producing
-    consumer's epilogue (``emit_table``, beside ``emit_act``), which would remove the launch."""
+    consumer's epilogue (``emit_table``, beside ``emit_act``), which would remove the launch.
+
+    ``matmuls=True`` (needs no other switch and composes with all of them; two operands need a graph, so ``fuse_linear_consumers``
+    has no such form) keeps the activation x activation products on codes: the ``Q @ K.transpose(-1, -2)`` and ``P @ V`` of an
+    attention block as an MCT export of a ViT, DeiT, Swin or BERT decomposes it.  The candidate is a ``torch.matmul`` /
+    ``operator.matmul`` (``@``) / ``Tensor.matmul`` / ``torch.bmm`` node of two tensors without keyword arguments, each operand of
+    which leads back to a plain holder's output through a layout-only chain: zero or more ``reshape``, ``view``, ``permute``,
+    ``transpose``, ``contiguous``, ``flatten``, ``unflatten`` nodes with constant integer arguments and ``operator.getitem`` nodes with
+    one constant integer index (``_layout_input``, the one list used on both sides; such nodes only move data, so they commute
+    with coding -- which is why a chain node may have other users as well: a fused ``qkv`` tensor is permuted once and indexed
+    three times).  The node becomes a QuantizedMatmul (``mctq_qmatmul_i8``) with the two holders' quantizers.  A final
+    ``transpose(-1, -2)`` on the second operand -- either order, a positive-index spelling behind a permute, reshape or view that
+    tells the rank, or ``.mT`` -- that feeds nothing else is absorbed as ``transposed_b=True`` and not executed.  The operand holders
+    are treated as ``concats`` / ``muls`` treat them: one whose every user leads to QuantizedMatmul operands leaves the graph, its
+    input runs through the chain and the module quantizes it; one with other users stays and the module quantizes its
+    float32 output, the same codes; with ``shared_holders=True`` a holder that became a join hands its codes to the chain.  A
+    plain holder directly behind the matmul, which feeds nothing else, is absorbed -- the module emits that holder's codes -- if
+    every user of it reads codes, directly or through layout-only chains: a wrapped ``nn.Linear`` the consumer can take under
+    the other switches, fed by it alone (it becomes a QuantizedLinear, counted in the returned total), an operand of another
+    QuantizedMatmul, and a QuantizedConcat / QuantizedMul that absorbed the holder and reads the node at one operand.
+    Otherwise the node returns float32 and the holder stays: the scores' case, whose scale multiply and softmax are float32.
+    With ``stay_on_codes=True`` a consumer every user of which leads, through a layout-only chain without a clamp activation, to
+    QuantizedMatmul operands of one form emits ``operand_code_params(i)``, and the chain moves int8: ``Linear -> holder -> reshape
+    -> permute -> matmul`` and ``matmul -> holder -> permute -> reshape -> Linear`` run codes to codes; Q, K, V and the context
+    never exist in float32.  Left alone: ``F.scaled_dot_product_attention`` and ``nn.MultiheadAttention``; the ``* scale`` /
+    ``/ sqrt(d)`` and the softmax between the two products; ``einsum``, ``baddbmm``, ``addmm``; an operand that reaches no holder;
+    quantizers wider than 8 bits or per-channel; half precision; a producer that writes its codes at the padded pitch directly
+    (a K that is no multiple of 16, a ViT's 197 probabilities per row, costs one re-pitch launch per forward, as
+    ``any_channels`` does).  The integer sum is exact, so the model returns, bit for bit, what the same rewrite without the switch
+    returns wherever the float32 products it replaces (and those of the layers behind an absorbed holder) are exact --
+    power-of-two scales, ``255 * 255 * K < 2^24``; otherwise it differs by the accumulation rounding of those float32 products."""
     import torch.fx as fx
     if stay_on_codes and not shared_holders:
         raise ValueError("stay_on_codes=True needs shared_holders=True")
@@ -3138,6 +3558,8 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
         replaced = _operator_between_holders(gm, mods, consumer_for, pools, _cat_operands, QuantizedConcat, "_concat")
     if muls:
         replaced += _operator_between_holders(gm, mods, consumer_for, pools, _mul_operands, QuantizedMul, "_mul")
+    if matmuls:                                              # (behind the two: it sees the QuantizedConcat / QuantizedMul nodes)
+        replaced += _matmuls_on_codes(gm, mods, consumer_for)
     # (an upsample's plan is made where a pool's is, in these two passes: it sees the QuantizedConcat / QuantizedMul nodes above)
     if shared_holders:
         replaced += _join_shared_holders(gm, mods, consumer_for, pools, avg_pools, upsamples, activation_tables)

@@ -26,7 +26,7 @@ SOURCES = [os.path.join(CSRC, f) for f in ("mctq_batched_lut.hip", "mctq_lut_ste
                                              "mctq_f64.hip", "mctq_grid.hip", "mctq_codes4.hip", "mctq_codes_nhwc.hip",
                                              "mctq_codes_im2col.hip", "mctq_codes_im2col_pad.hip", "mctq_codes_maxpool.hip", "mctq_codes_concat.hip", "mctq_codes_avgpool.hip",
                                              "mctq_codes_mul.hip", "mctq_codes_upsample.hip", "mctq_codes_table.hip", "mctq_qconv_dw.hip", "mctq_qconv_grouped.hip", "mctq_qconv_transposed.hip",
-                                             "mctq_fq_join.hip", "mctq_misc.hip")]
+                                             "mctq_qmatmul.hip", "mctq_fq_join.hip", "mctq_misc.hip")]
 HEADERS = [os.path.join(REPO, "include", "mctq_hip.h"), os.path.join(CSRC, "mctq_kernels.hpp"),
            os.path.join(CSRC, "mctq_table_builder.h"), os.path.join(CSRC, "mctq_batched.hpp"),
            os.path.join(CSRC, "mctq_lut_index.hpp"), os.path.join(CSRC, "mctq_consumer.hpp")]

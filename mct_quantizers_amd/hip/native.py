@@ -185,6 +185,13 @@ SIGNATURES = {
                                                 ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_int32,
                                                 ctypes.c_int32]                                                      # y and its output form
                                  + [ctypes.c_int64] * 5 + [ctypes.c_int32] * 8 + [ctypes.c_void_p]),        # B, H, W, C, O; kernel, stride, padding, output padding; stream
+    "mctq_qmatmul_i8": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,             # a_codes, type, zero point, scale
+                                       ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,                              # a's strides: B0, B1, rows
+                                       ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,             # b_codes, type, zero point, scale
+                                       ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,              # b's strides; transposed_b
+                                       ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_int32,
+                                       ctypes.c_int32]                                                              # y and its output form
+                        + [ctypes.c_int64] * 5 + [ctypes.c_void_p]),                                                # B0, B1, M, N, K; stream
     "mctq_fq_join_f32": (ctypes.c_int, [_c_f32p, _c_f32p, ctypes.c_int32, _c_f32p, ctypes.c_void_p, ctypes.c_int32,   # x, residual, relu, y, codes, code_dtype
                                         ctypes.c_int64, ctypes.c_float, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                         ctypes.c_void_p]),                                                            # n, scale, zero_point, qmin, qmax, stream

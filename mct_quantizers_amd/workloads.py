@@ -262,3 +262,90 @@ def wrapped_resnet50(device="cuda", weights: str = "symmetric", holders: bool = 
             Q.ActivationSymmetricInferableQuantizer(num_bits=8, threshold=[8.0], signed=False))]
     layers += [nn.Flatten(), wrap(nn.Linear(2048, 1000, bias=False))]
     return nn.Sequential(*layers).to(device).eval()
+
+
+def _attention_class():
+    """One attention block over already wrapped layers and holders; a module attribute for the same reason as ``_Bottleneck``.
+    Every reshape and permute has constant arguments (the batch is ``-1``), as a traced MCT export has them."""
+    import torch.nn as nn
+    if "_AttentionBlock" in globals():
+        return globals()["_AttentionBlock"]
+
+    class AttentionBlock(nn.Module):
+        def __init__(self, dim, heads, tokens, norm, a_in, qkv, a_qkv, a_scores, a_scaled, a_probs, a_ctx, proj):
+            super().__init__()
+            self.dim, self.heads, self.tokens, self.head_dim = dim, heads, tokens, dim // heads
+            self.scale = float(self.head_dim) ** -0.5
+            self.norm, self.a_in = norm, a_in
+            self.fused = len(qkv) == 1
+            if self.fused:
+                self.qkv, self.a_qkv = qkv[0], a_qkv[0]
+            else:
+                (self.q, self.k, self.v), (self.a_q, self.a_k, self.a_v) = qkv, a_qkv
+            self.a_scores, self.a_scaled, self.a_probs, self.a_ctx, self.proj = a_scores, a_scaled, a_probs, a_ctx, proj
+
+        def forward(self, x):
+            x = self.a_in(self.norm(x))
+            if self.fused:
+                qkv = self.a_qkv(self.qkv(x)).reshape(-1, self.tokens, 3, self.heads, self.head_dim).permute(2, 0, 3, 1, 4)
+                q, k, v = qkv[0], qkv[1], qkv[2]
+            else:
+                q, k, v = (a(layer(x)).reshape(-1, self.tokens, self.heads, self.head_dim).permute(0, 2, 1, 3)
+                           for layer, a in ((self.q, self.a_q), (self.k, self.a_k), (self.v, self.a_v)))
+            scores = self.a_scores(q @ k.transpose(-1, -2))
+            probs = self.a_probs(self.a_scaled(scores * self.scale).softmax(dim=-1))
+            ctx = self.a_ctx(probs @ v)
+            return self.proj(ctx.permute(0, 2, 1, 3).reshape(-1, self.tokens, self.dim))
+
+    AttentionBlock.__name__ = AttentionBlock.__qualname__ = "_AttentionBlock"
+    AttentionBlock.__module__ = __name__
+    globals()["_AttentionBlock"] = AttentionBlock
+    return AttentionBlock
+
+
+def wrapped_attention_block(dim: int = 64, heads: int = 2, tokens: int = 17, device="cpu", fused_qkv: bool = False,
+                            uniform: bool = False, bias: bool = False, seed: int = 0):
+    """One pre-norm attention block as an MCT export of a ViT / DeiT / BERT layer decomposes it: LayerNorm -> holder -> separate
+    wrapped q / k / v ``nn.Linear`` layers, each -> holder -> ``[B, T, H, D]`` reshape -> permute -> ``q @ k.transpose(-1, -2)`` ->
+    holder -> ``* scale`` -> holder -> softmax -> holder -> ``@ v`` -> holder -> permute -> reshape -> wrapped ``nn.Linear``.
+    ``fused_qkv=True``: one timm-style ``qkv`` Linear and holder, ``reshape(-1, T, 3, H, D).permute(2, 0, 3, 1, 4)`` and three
+    ``getitem`` nodes.  Input ``[B, tokens, dim]``; the reshapes carry ``tokens`` as a constant, the batch is free.
+
+    Quantizers: 8-bit power-of-two weights (per output channel) and, by default, 8-bit symmetric holders with power-of-two
+    thresholds -- every scale a power of two, so that with ``dim <= 64`` every float32 product of the block is exact and its
+    rewrites can be compared bit for bit.  ``uniform=True``: 8-bit uniform holders over odd ranges instead (zero points that are
+    not 0, scales that are no powers of two).  ``bias``: the four Linear layers' (multiples of 2^-6).  Pure workload: seeded
+    random weights, no checkpoint."""
+    import torch
+    import torch.nn as nn
+    import mct_quantizers_amd as mq
+    Q = mq.pytorch_quantizers
+    gen = torch.Generator().manual_seed(seed)
+
+    def wrap(cin, cout):
+        layer = nn.Linear(cin, cout, bias=bias)
+        with torch.no_grad():
+            layer.weight.copy_(torch.randn(cout, cin, generator=gen) * 0.25)
+            if bias:
+                layer.bias.copy_(torch.randint(-32, 33, (cout,), generator=gen) / 64.0)
+        q = Q.WeightsPOTInferableQuantizer(num_bits=8, threshold=[1.0] * cout, per_channel=True, channel_axis=0)
+        return mq.PytorchQuantizationWrapper(layer.to(device), {"weight": q})
+
+    ranges = iter(((-3.1, 2.7), (-2.9, 3.3), (-3.4, 2.5), (-3.0, 3.1), (-20.5, 27.0), (-5.5, 6.1), (0.0, 0.93), (-1.7, 2.2)))
+
+    def holder(threshold, signed=True):
+        lo_hi = next(ranges)
+        if uniform:
+            return mq.PytorchActivationQuantizationHolder(Q.ActivationUniformInferableQuantizer(8, [lo_hi[0]], [lo_hi[1]]))
+        return mq.PytorchActivationQuantizationHolder(Q.ActivationSymmetricInferableQuantizer(8, [threshold], signed))
+
+    a_in = holder(4.0)
+    if fused_qkv:
+        qkv, a_qkv = [wrap(dim, 3 * dim)], [holder(4.0)]
+        next(ranges), next(ranges)
+    else:
+        qkv, a_qkv = [wrap(dim, dim) for _ in range(3)], [holder(4.0) for _ in range(3)]
+    a_scores, a_scaled, a_probs, a_ctx = holder(32.0), holder(8.0), holder(1.0, signed=False), holder(2.0)
+    block = _attention_class()(dim, heads, tokens, nn.LayerNorm(dim), a_in, qkv, a_qkv, a_scores, a_scaled, a_probs, a_ctx,
+                               wrap(dim, dim))
+    return block.to(device).eval()
