@@ -771,6 +771,38 @@ int mctq_codes_table(const void* in, int32_t in_code_dtype, void* out, int32_t o
                      void* stream);
 
 /*
+ * Softmax over the rows of a code tensor between two activation holders A and B (extension, additive to v10; the reference runs
+ * torch.softmax on A's float32 output and B on the result): the softmax of an attention block on codes.  Defined on integers, so
+ * that no summation order enters the result.  Row r is the length bytes at in + r * in_pitch; per row
+ *     c_j    = pre_table ? pre_table[raw byte j] : raw byte j      A's code, of the type in_code_dtype
+ *     cmax   = max_j c_j,  d_j = cmax - c_j                         0 .. 255; A's zero point cancels
+ *     S      = sum_j E[d_j]                                         exact, unsigned 64-bit; E = exp_table
+ *     p_j    = float32(E[d_j]) / float32(S)                         both conversions round to nearest, one IEEE float32 division
+ *     code_j = clamp(rint(p_j * (1 / out_scale)) + out_zero_point, out_quant_min, out_quant_max)
+ * exp_table: 256 uint32 on the DEVICE, 4-byte aligned, E[d] = rint(exp(-d * (double)(float)scale_a) * 2^24) (E[0] = 2^24), built by
+ * the caller in float64 (ops.softmax_exp_table).  pre_table: NULL, or 256 bytes on the DEVICE, 4-byte aligned, indexed by the raw
+ * input byte and holding the raw byte of A's code -- an elementwise prefix between a holder A0 and A ("* scale", activation
+ * functions) folded into the launch (ops.code_table).  Row r is written at out + r * out_pitch: length codes, then pad_code (a
+ * code of the output's type: B's zero point) in the columns length .. out_pitch - 1 -- rows at the pitch the integer product
+ * reads.  in, out: DEVICE pointers, 16-byte aligned; rows may start at any byte.  A row is read once as the 16-byte-aligned
+ * chunks that cover it, kept in registers and written once; no byte outside [in, in + (rows - 1) * in_pitch + length) is read,
+ * none outside [out, out + rows * out_pitch) written.  Two forms with the same bytes: one wave per row (rows whose chunks number
+ * at most 256), one workgroup per row (at most 2048); the launcher takes the wave form wherever it fits, tuning key
+ * "softmax_form" forces the block form.
+ * MCTQ_E_ARG with a mctq_last_error text, before anything is launched, for: negative rows or length; a bad code type; an
+ * out_scale that is not finite and positive; a pad_code that is no code of the output's type; a clamp domain outside the type;
+ * a pitch below length; with rows, length > 0: more than 2^31 - 1 bytes of input or output, a NULL in / out / exp_table, an in
+ * or out that is not 16-byte aligned, a table that is not 4-byte aligned, an `out` that overlaps in or a table, a row of more
+ * than 2048 chunks (32768 bytes where every row starts on a chunk, about 32 bytes less elsewhere).  rows == 0 or length == 0
+ * returns 0 without a launch.  mctq_last_launch names the launch "codes_softmax", op "<in> -> <out> wave|block[ pre]", U = the
+ * chunks per lane.
+ */
+int mctq_codes_softmax(const void* in, int32_t in_code_dtype, void* out, int32_t out_code_dtype, float out_scale,
+                       int32_t out_zero_point, int32_t out_quant_min, int32_t out_quant_max, int64_t rows, int64_t length,
+                       int64_t in_pitch, int64_t out_pitch, int32_t pad_code, const void* exp_table, const void* pre_table,
+                       void* stream);
+
+/*
  * Depthwise convolution on activation codes (groups == channels, channel multiplier 1; extension, the reference has no
  * counterpart): what a wrapped depthwise torch.nn.Conv2d computes on fake-quantized operands, evaluated on the codes.
  *     acc[b][oy][ox][c] = sum over the taps (ky, kx) inside the image of
@@ -1174,6 +1206,10 @@ int mctq_qconv_dw_i8_act(const void* a_codes, int32_t a_code_dtype, int32_t a_ze
  *                  elsewhere), 1 = byte loads, 4 = dword loads (MCTQ_E_ARG from the entry point where channels % 4 != 0).  The
  *                  bytes are the same
  *   key "table_chunks" : mctq_codes_table: 16-byte chunks per lane, 1, 2 or 4 (default 4).  The bytes are the same
+ *   key "softmax_form" : mctq_codes_softmax: 0 (default) = the launcher chooses, the wave form wherever a row fits it (measured on
+ *                  six attention shapes where both fit: the wave form won four, 1.6 - 3.5 x, and tied the two small batch-1
+ *                  launches, 12 x 128 x 128 and 12 x 197 x 197, within 7 %; the block form won none), 1 = the wave form
+ *                  where it fits, 2 = the block form.  The bytes are the same: the sums are integers
  * Only variants a default dispatcher can select are instantiated; every value of every key is exercised by the GPU tests.
  * Returns 0, or MCTQ_E_ARG for an unknown key/value.  Numerical results never depend on it.
  */

@@ -138,6 +138,14 @@ context never exist in float32.  It equals the float32 chain bit for bit where t
 ``255 * 255 * K < 2^24``) and differs by its accumulation rounding elsewhere.
 Measured / not measured: see the README paragraph and ``profiles/EXPERIMENTS.md``.
 
+The softmax between those two products stays on codes with ``fuse_linear_consumers_fx(..., softmaxes=True)``: holder A0 -> ``* scale`` ->
+holder A -> ``softmax(dim=-1)`` -> holder B becomes one ``QuantizedSoftmax`` (``ops.codes_softmax``, ``mctq_codes_softmax``), 1 byte read and 1
+written per element.  The contract is an integer softmax -- a uint32 table ``E[d] = rint(exp(-d * scale_a) * 2^24)`` of the distance to the
+row's largest code, an exact integer sum, one IEEE float32 division per element -- so no summation order enters it: CPU and GPU and every
+kernel form give the same bytes, and against the float32 chain a code can differ by one, next to a rounding tie only.  The prefix is a byte
+table inside the launch; the product in front emits the scores as codes and the product behind reads the probabilities at its own pitch.
+Measured / not measured: see the README paragraph and ``profiles/EXPERIMENTS.md``.
+
 The six modules derive from ``IntegerConsumer``, which owns what they share: the checks of the quantizers and of the float32
 weight and bias, the cache of the weight's codes, the step from ``forward``'s input to activation codes, ``from_wrapper`` and
 the ``emit_codes_for`` / ``emit_clamp`` output form.  ``QuantizedLinear`` is the product over ``[O, K]`` rows; ``QuantizedConv1x1``
@@ -680,7 +688,8 @@ def _matmul_strides(t):
     return tuple(0 if t.shape[d] == 1 else t.stride(d) for d in range(3))
 
 
-def qmatmul_i8(a_codes: torch.Tensor, a_form, b_codes: torch.Tensor, b_form, *, transposed_b: bool, out_codes=None) -> torch.Tensor:
+def qmatmul_i8(a_codes: torch.Tensor, a_form, b_codes: torch.Tensor, b_form, *, transposed_b: bool, out_codes=None,
+               a_padded_k=None) -> torch.Tensor:
     """Batched matrix product of two activation-code tensors: a_codes ``[..., M, K]`` and b_codes ``[..., N, K]``
     (``transposed_b=True``, the Q.K^T form, "NT") or ``[..., K, N]`` (``transposed_b=False``, the P.V form, "NN"), int8 or uint8 in any
     pair, each per-tensor affine with ``form = (scale, zero_point)``; leading dimensions broadcast as ``torch.matmul``'s do (and
@@ -702,6 +711,10 @@ def qmatmul_i8(a_codes: torch.Tensor, a_form, b_codes: torch.Tensor, b_form, *, 
     tensors run the same contract with exact torch ops (CPU: an int64 product; GPU: a float64 product, exact since
     ``|acc| < 2^53``).
 
+    ``a_padded_k=K``: a_codes is ``[..., M, Kp]``, ``Kp = 16 * ceil(K / 16)``, rows of K codes with the zero-point code in their tail --
+    what ``ops.codes_softmax(..., pad_to=16)`` writes.  A contiguous, 16-byte aligned GPU tensor then goes to the kernel as it is:
+    the re-pitch launch is saved.  The result is that of the K columns.
+
     Where the float32 ``torch.matmul`` of the two dequantized operands is exact (power-of-two scales, ``255 * 255 * K < 2^24``) the
     result equals that chain bit for bit; elsewhere it differs by the float32 accumulation rounding of the chain."""
     import numpy as np
@@ -711,6 +724,14 @@ def qmatmul_i8(a_codes: torch.Tensor, a_form, b_codes: torch.Tensor, b_form, *, 
         raise RuntimeError(f"qmatmul_i8: a_codes on {a_codes.device}, b_codes on {b_codes.device}")
     transposed_b = bool(transposed_b) and b_codes.dim() >= 2              # (the transpose of a vector is the vector)
     K = a_codes.shape[-1]
+    pitched = None                                                        # a_codes as the kernel takes them, where they arrive so
+    if a_padded_k is not None:
+        K = int(a_padded_k)
+        if a_codes.dim() < 2 or a_codes.shape[-1] != _padded_k(K):
+            raise RuntimeError(f"qmatmul_i8: a_padded_k={K} needs a_codes [..., M, {_padded_k(K)}], got {tuple(a_codes.shape)}")
+        if a_codes.is_contiguous() and a_codes.data_ptr() % 16 == 0:
+            pitched = a_codes
+        a_codes = a_codes[..., :K]
     b_k = b_codes.shape[-1] if transposed_b or b_codes.dim() == 1 else b_codes.shape[-2]
     if b_k != K:
         raise _k_mismatch(K, b_k, "the second operand")
@@ -726,7 +747,7 @@ def qmatmul_i8(a_codes: torch.Tensor, a_form, b_codes: torch.Tensor, b_form, *, 
             tdt, *form = _output_form(out_codes)
             y = a_codes.new_empty((b0, b1, M, N), dtype=tdt)
             if y.numel():
-                a4 = _matmul_view(a_codes, a_zp, True)
+                a4 = pitched if pitched is not None else _matmul_view(a_codes, a_zp, True)
                 b4 = _matmul_view(b_codes, b_zp, transposed_b)
                 if a4.shape[:-2] != batch:
                     a4 = a4.expand(*batch, *a4.shape[-2:])
@@ -1725,6 +1746,89 @@ class QuantizedActivationTable(_OnCodes):
         return y.permute(0, 3, 1, 2) if x.dim() == 4 else y
 
 
+class _ScalarStep(nn.Module):
+    """``x * value`` / ``x / value`` with a Python number: an elementwise step of a QuantizedSoftmax prefix (the ``* scale`` of an
+    attention block), kept as a module so that the model stays picklable."""
+
+    def __init__(self, op: str, value):
+        super().__init__()
+        self.op, self.value = op, value
+
+    def extra_repr(self) -> str:
+        return f"{self.op} {self.value!r}"
+
+    def forward(self, x):
+        return x * self.value if self.op == "mul" else x / self.value
+
+
+class QuantizedSoftmax(_OnCodes):
+    """``activation holder A0 -> [elementwise prefix -> holder A] -> softmax(dim=-1) -> activation holder B`` on integer codes: the
+    stretch between the two products of an attention block, ``a_scores -> * scale -> a_scaled -> softmax -> a_probs``, its largest
+    tensor.  ``ops.codes_softmax`` (``mctq_codes_softmax``): one launch, 1 byte read and 1 written per element, where the float32
+    chain runs a scalar multiply, a holder, ATen's softmax, a second holder and a quantize launch over 4-byte elements.
+
+    The contract is defined on integers, so that it does not depend on a summation order and the CPU route and every kernel form
+    give the same bytes.  Per row of A's codes ``c_j``: ``d_j = max c - c_j``; ``E[d] = rint(exp(-d * scale_a) * 2^24)``, a uint32
+    table built in float64; ``S = sum_j E[d_j]``, an exact integer; ``p_j = float32(E[d_j]) / float32(S)``, one IEEE division;
+    B's code of ``p_j``.  Against the float32 chain A -> softmax -> B it can differ by one code, and only next to a rounding tie.
+    The prefix -- what stands between A0 and A, and A itself -- is elementwise on A0's at most 256 values: a byte table, built by
+    running those calls on the 256 dequantized values (``ops.code_table``) and looked up inside the same launch.
+
+    ``in_quantizer``: the first holder's (A0's; A's where there is no prefix); ``prefix``: None or ``(callables, A's quantizer)``;
+    ``out_quantizer``: B's.  Per-tensor affine activation quantizers of at most 8 bits whose zero points are codes of their type.
+    ``forward`` takes codes of ``in_quantizer`` (``activation_code_params``) or a float32 tensor, which it quantizes in that form,
+    of any rank -- the softmax runs over the last dimension -- and returns B's codes (``output_code_params``) in the same shape;
+    with ``pad_rows`` the last dimension is padded to a multiple of 16 with B's zero-point code, the rows a QuantizedMatmul with
+    ``a_padded`` takes without its re-pitch launch.  Tables are cached per device and built on first use there."""
+
+    def __init__(self, in_quantizer, out_quantizer, prefix=None, pad_rows: bool = False):
+        super().__init__()
+        self.in_quantizer, self.out_quantizer = in_quantizer, out_quantizer
+        self._in_form = _code_form(in_quantizer)
+        self._out_form = _code_form(out_quantizer)
+        self.has_prefix = prefix is not None                   # (A0 and A may share one quantizer: the steps between them still count)
+        fns, a_quantizer = prefix if prefix is not None else ((), in_quantizer)
+        self.fns = nn.ModuleList(fns)
+        self.a_quantizer = a_quantizer
+        self._a_form = _code_form(a_quantizer)
+        self.pad_rows = bool(pad_rows)
+        self._tables = {}                                      # device -> (exp table, pre-table or None)
+
+    def activation_code_params(self):
+        """(scale, zero_point, qmin, qmax) of the codes this module READS: what the producer in front emits."""
+        return self._in_form
+
+    def output_code_params(self):
+        """(scale, zero_point, qmin, qmax) of the codes ``forward`` returns (holder B's)."""
+        return self._out_form
+
+    def extra_repr(self) -> str:
+        return f"prefix={len(self.fns)} step(s), pad_rows={self.pad_rows}" if self.has_prefix else f"pad_rows={self.pad_rows}"
+
+    def _prefix(self, x):
+        for f in self.fns:                                     # (``ops.code_table`` codes the result in A's form: holder A)
+            x = f(x)
+        return x
+
+    def tables(self, device):
+        """``(exp table, pre-table or None)`` on ``device``, built on first use there."""
+        key = str(torch.device(device))
+        hit = self._tables.get(key)
+        if hit is None:
+            exp = torch.from_numpy(ops.softmax_exp_table(self._a_form[0]).view("int32")).to(device)
+            pre = None
+            if self.has_prefix:
+                pre = ops.code_table(self._prefix, self._in_form, self._a_form, device)
+            hit = self._tables[key] = (exp, pre)
+        return hit
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        codes = _operand_codes(x, self._in_form, "QuantizedSoftmax", "this softmax's input quantizer", nhwc=False)
+        exp, pre = self.tables(codes.device)
+        return ops.codes_softmax(codes, self._a_form, self._out_form, pre_table=pre, pad_to=16 if self.pad_rows else None,
+                                 exp_table=exp)
+
+
 class _OperandsOnCodes(_OnCodes):
     """What QuantizedConcat, QuantizedMul and QuantizedMatmul share: several operands, each read as the codes of its own holder's
     quantizer, and one output holder's quantizer, all per-tensor affine of at most 8 bits (``_code_form``).  With
@@ -1868,13 +1972,17 @@ class QuantizedMatmul(_OperandsOnCodes):
             raise ValueError("QuantizedMatmul takes the quantizers of two operands")
         super().__init__(operand_quantizers, activation_quantizer, float_output=True)
         self.transposed_b = bool(transposed_b)
+        self.a_padded = False                                  # the first operand may arrive at the padded pitch (QuantizedSoftmax.pad_rows)
 
     def extra_repr(self) -> str:
         return f"transposed_b={self.transposed_b}, output={'float32' if self._out_form is None else 'codes'}"
 
     def forward(self, x0: torch.Tensor, x1: torch.Tensor) -> torch.Tensor:
         a, b = self._codes_of(0, x0, nhwc=False), self._codes_of(1, x1, nhwc=False)
-        return qmatmul_i8(a, self._forms[0][:2], b, self._forms[1][:2], transposed_b=self.transposed_b, out_codes=self._out_form)
+        k = b.shape[-1] if self.transposed_b or b.dim() == 1 else b.shape[-2]
+        padded = getattr(self, "a_padded", False) and a.shape[-1] != k
+        return qmatmul_i8(a, self._forms[0][:2], b, self._forms[1][:2], transposed_b=self.transposed_b, out_codes=self._out_form,
+                          a_padded_k=k if padded else None)
 
 
 # In the order they are tried: (class, the switch of the rewrites that enables it or None, what fusing asks of the layer beyond
@@ -2769,7 +2877,124 @@ def _matmul_operand_form(node, mods):
     return None
 
 
-def _matmuls_on_codes(gm, mods, consumer_for) -> int:
+def _softmax_input(node, mods):
+    """The tensor operand of ``node`` if it is a softmax over the last dimension that QuantizedSoftmax can take: a call of an
+    ``nn.Softmax`` with ``dim=-1``, or ``F.softmax`` / ``torch.softmax`` / ``Tensor.softmax`` with the constant ``dim=-1`` and no
+    ``dtype``.  Else None (another ``dim``, ``log_softmax``, a ``dtype=`` argument)."""
+    from torch.fx import Node
+    if not node.args or not isinstance(node.args[0], Node):
+        return None
+    if node.op == "call_module":
+        m = mods.get(node.target)
+        ok = type(m) is nn.Softmax and m.dim == -1 and len(node.args) == 1 and not node.kwargs
+    else:
+        ok = (node.op == "call_function" and node.target in (torch.softmax, torch.nn.functional.softmax)) or \
+            (node.op == "call_method" and node.target == "softmax")
+        given = _const_args(node, ("dim", "_stacklevel", "dtype")) if ok else None
+        ok = given is not None and given.get("dim") == -1 and not isinstance(given.get("dim"), bool) and given.get("dtype") is None
+    return node.args[0] if ok else None
+
+
+def _scalar_step(node):
+    """``(tensor operand, _ScalarStep)`` if ``node`` multiplies or divides one tensor by a Python number -- ``x * c``, ``c * x``,
+    ``x / c``, ``torch.mul`` / ``torch.div`` / ``Tensor.mul`` / ``Tensor.div`` without keyword arguments -- else None."""
+    from torch.fx import Node
+    if node.kwargs or len(node.args) != 2:
+        return None
+    if node.op == "call_function" and node.target in (operator.mul, torch.mul, torch.multiply):
+        op = "mul"
+    elif node.op == "call_function" and node.target in (operator.truediv, torch.div, torch.true_divide):
+        op = "div"
+    elif node.op == "call_method" and node.target in ("mul", "div"):
+        op = node.target
+    else:
+        return None
+    number = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool)           # noqa: E731
+    x, c = node.args
+    if op == "mul" and number(x) and isinstance(c, Node):
+        x, c = c, x
+    return (x, _ScalarStep(op, c)) if isinstance(x, Node) and number(c) else None
+
+
+def _softmaxes_on_codes(gm, mods, consumer_for) -> int:
+    """``fuse_linear_consumers_fx(softmaxes=True)``.  The candidate is a softmax over the last dimension (``_softmax_input``) of
+    the output of a plain holder A that feeds nothing else, whose one user is a plain holder B every user of which reads codes
+    in B's form: an operand of a QuantizedMatmul, through its layout nodes (``_reads_as_matmul_operands``), or a wrapped
+    ``nn.Linear`` ``consumer_for`` can take, fed by B alone.  In front of A an elementwise prefix is taken where it leads back to a
+    plain holder A0: at most one multiplication or division by a Python number (``_scalar_step``) and at most four activations
+    (``_activation_of``), each feeding the next alone.  A0 .. B become one QuantizedSoftmax node ``<B's name>_softmax``; a holder
+    A0 with other users stays and the node quantizes its output, the same codes.  Where B's one user is a QuantizedMatmul
+    that takes it directly as its first operand alone, the node writes its rows at the padded pitch (``pad_rows``) and the
+    product reads them as they are (``a_padded``).  Returns the number of wrapped layers replaced."""
+    replaced = 0
+    for node in list(gm.graph.nodes):
+        a_node = _softmax_input(node, mods)
+        holder_a = _holder_of(a_node, mods) if a_node is not None else None
+        if holder_a is None or len(a_node.users) != 1 or len(node.users) != 1:
+            continue
+        b_node = next(iter(node.users))
+        holder_b = _holder_of(b_node, mods)
+        if holder_b is None or b_node.args != (node,) or not b_node.users:
+            continue
+        quantizer_b = holder_b.activation_holder_quantizer
+        try:
+            form_b = _code_form(quantizer_b)
+        except (TypeError, ValueError, NotImplementedError):
+            continue
+        taken = []
+        for user in b_node.users:
+            fused = _wrapped_consumer(user, b_node, mods, quantizer_b, consumer_for)
+            if type(fused) is QuantizedLinear:
+                taken.append((user, fused))
+            elif fused is not None or not _reads_as_matmul_operands(user, b_node, form_b, mods):
+                break
+        else:
+            # the prefix, walked from A towards A0
+            steps, chain, at, scalars = [], [], a_node.args[0], 0
+            while len(at.users) == 1 and len(steps) < _TABLE_CHAIN_MAX + 1:
+                scalar, fn = _scalar_step(at), _activation_of(at, mods)
+                if scalar is not None and scalars == 0:
+                    scalars, (src, step) = 1, scalar
+                elif fn is not None and len(steps) - scalars < _TABLE_CHAIN_MAX:
+                    src, step = at.args[0], fn
+                else:
+                    break
+                steps.insert(0, step)
+                chain.append(at)
+                at = src
+            holder_0 = _holder_of(at, mods) if steps else None
+            if holder_0 is not None and (len(at.users) == 1 or all(u in chain for u in at.users)):
+                gone, source = [a_node] + chain + [at], at.args[0]            # A0 feeds the prefix alone: the node quantizes its input
+            elif holder_0 is not None:
+                gone, source = [a_node] + chain, at
+            else:
+                steps, gone, source = [], [a_node], a_node.args[0]            # no prefix: A is the first holder
+            try:
+                prefix = (steps, holder_a.activation_holder_quantizer) if holder_0 is not None else None
+                first = holder_0.activation_holder_quantizer if holder_0 is not None else holder_a.activation_holder_quantizer
+                module = QuantizedSoftmax(first, quantizer_b, prefix)
+            except (TypeError, ValueError, NotImplementedError):
+                continue
+            name = b_node.target.replace(".", "_") + "_softmax"
+            gm.add_submodule(name, module)
+            mods[name] = module
+            with gm.graph.inserting_before(b_node):
+                new = gm.graph.call_module(name, (source,))
+            b_node.replace_all_uses_with(new)
+            for dead in [b_node, node] + gone:
+                gm.graph.erase_node(dead)
+            for user, fused in taken:
+                _install_consumer(gm, mods, user, fused)
+                replaced += 1
+            if len(new.users) == 1:
+                reader = next(iter(new.users))
+                product = _module_of(reader, mods)
+                if isinstance(product, QuantizedMatmul) and not reader.kwargs and reader.args[0] is new and reader.args[1] is not new:
+                    module.pad_rows = product.a_padded = True
+    return replaced
+
+
+def _matmuls_on_codes(gm, mods, consumer_for, softmaxes: bool = False) -> int:
     """``fuse_linear_consumers_fx(matmuls=True)``, three steps.  (1) Every matmul node (``_matmul_operands``) each operand of which
     leads back to a plain holder's output through layout-only nodes (``_layout_input``) becomes a QuantizedMatmul node with the two
     holders' quantizers; a final swap of the last two dimensions on the second operand that feeds nothing else
@@ -2805,13 +3030,17 @@ def _matmuls_on_codes(gm, mods, consumer_for) -> int:
         if transposed:
             gm.graph.erase_node(x1)
         made.append(new)
+    if softmaxes:                                            # (between the steps: it needs the products as modules and the holders
+        replaced += _softmaxes_on_codes(gm, mods, consumer_for)     # behind the softmaxes still in the graph, which step (3) takes)
     for new in made:                                         # (2) the holder behind
         if len(new.users) != 1:
             continue
         behind = next(iter(new.users))
         module, reader = mods[new.target], _module_of(behind, mods)
         taken, quantizer = [], None
-        if isinstance(reader, (QuantizedConcat, QuantizedMul)) and not behind.kwargs and sum(a is new for a in behind.args) == 1:
+        if isinstance(reader, QuantizedSoftmax) and not behind.kwargs and behind.args == (new,):
+            quantizer, hnode = reader.in_quantizer, None     # (the softmax absorbed the holder: the scores leave as its codes)
+        elif isinstance(reader, (QuantizedConcat, QuantizedMul)) and not behind.kwargs and sum(a is new for a in behind.args) == 1:
             quantizer, hnode = reader.operand_quantizers[next(i for i, a in enumerate(behind.args) if a is new)], None
         else:
             holder, hnode = _holder_of(behind, mods), behind
@@ -2838,6 +3067,7 @@ def _matmuls_on_codes(gm, mods, consumer_for) -> int:
             emitting = QuantizedMatmul(module.operand_quantizers, quantizer, transposed_b=module.transposed_b)
         except (TypeError, ValueError, NotImplementedError):
             continue
+        emitting.a_padded = module.a_padded
         setattr(gm, new.target, emitting)                    # (the name has no dots: step (1) made it)
         mods[new.target] = emitting
         for user, fused in taken:
@@ -3285,7 +3515,7 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
                              concats: bool = False, avg_pools: bool = False, muls: bool = False,
                              hard_activations: bool = False, upsamples: bool = False, any_channels: bool = False,
                              activation_tables: bool = False, grouped: bool = False, transposed: bool = False,
-                             matmuls: bool = False):
+                             matmuls: bool = False, softmaxes: bool = False):
     """The same rewrite on an arbitrary module graph (MCT-exported models are not ``nn.Sequential``): traces ``model``
     with torch.fx keeping wrappers and holders as leaves, and wherever an activation holder's ONLY consumer is a
     wrapped ``nn.Linear`` the integer consumer can take (symmetric, power-of-two or LUT weights, and with
@@ -3528,12 +3758,31 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
     QuantizedMatmul operands of one form emits ``operand_code_params(i)``, and the chain moves int8: ``Linear -> holder -> reshape
     -> permute -> matmul`` and ``matmul -> holder -> permute -> reshape -> Linear`` run codes to codes; Q, K, V and the context
     never exist in float32.  Left alone: ``F.scaled_dot_product_attention`` and ``nn.MultiheadAttention``; the ``* scale`` /
-    ``/ sqrt(d)`` and the softmax between the two products; ``einsum``, ``baddbmm``, ``addmm``; an operand that reaches no holder;
+    ``/ sqrt(d)`` and the softmax between the two products (``softmaxes=True``, below, takes them); ``einsum``, ``baddbmm``, ``addmm``; an operand that reaches no holder;
     quantizers wider than 8 bits or per-channel; half precision; a producer that writes its codes at the padded pitch directly
     (a K that is no multiple of 16, a ViT's 197 probabilities per row, costs one re-pitch launch per forward, as
     ``any_channels`` does).  The integer sum is exact, so the model returns, bit for bit, what the same rewrite without the switch
     returns wherever the float32 products it replaces (and those of the layers behind an absorbed holder) are exact --
-    power-of-two scales, ``255 * 255 * K < 2^24``; otherwise it differs by the accumulation rounding of those float32 products."""
+    power-of-two scales, ``255 * 255 * K < 2^24``; otherwise it differs by the accumulation rounding of those float32 products.
+
+    ``softmaxes=True`` (needs no other switch and composes with all of them; fx only) keeps the softmax between two holders on
+    codes: with ``matmuls=True`` the stretch between the two products of an attention block, ``a_scores -> * scale -> a_scaled ->
+    softmax -> a_probs``.  The candidate is a softmax over the last dimension -- a call of an ``nn.Softmax(dim=-1)``, ``F.softmax`` /
+    ``torch.softmax`` / ``Tensor.softmax`` with the constant ``dim=-1`` and no ``dtype=`` -- of the output of a plain holder A that
+    feeds nothing else, whose one user is a plain holder B.  All users of B must read codes: operands of a QuantizedMatmul,
+    through its layout nodes, or wrapped ``nn.Linear`` layers the consumer can take under the other switches, fed by B alone
+    (counted in the returned total).  In front of A an elementwise prefix is taken where it leads back to a plain holder A0: at
+    most one ``* c`` / ``/ c`` / ``torch.mul`` / ``torch.div`` / ``Tensor.mul`` / ``Tensor.div`` with one Python-number operand and 1 to 4
+    functions ``activation_tables`` accepts, each feeding the next alone.  A0 .. B become one QuantizedSoftmax node named
+    ``<B's name>_softmax`` (``mctq_codes_softmax``: 1 byte read and 1 written per element, the prefix as a byte table inside the
+    launch).  The pass runs between the steps of ``matmuls``: the QuantizedMatmul in front absorbs A0 and emits its codes, the
+    scores' case, so that with both switches and ``stay_on_codes`` Q, K, V, scores, probabilities and context never exist in
+    float32.  Where B feeds the first operand of a QuantizedMatmul directly the node writes its rows at the pitch of 16 that
+    product reads (``pad_rows`` / ``a_padded``): the re-pitch launch of a 197-wide row goes.  The contract is QuantizedSoftmax's, an
+    integer softmax that no summation order enters: CPU and GPU, and every kernel form, give the same bytes; against the float32
+    chain A -> softmax -> B a code can differ by one, and only next to a rounding tie.  Left alone: another ``dim``; an additive
+    mask or any tensor operand between the holders; ``log_softmax``; a float32 user of the softmax or of B; no holder B;
+    quantizers wider than 8 bits or per-channel; ``F.scaled_dot_product_attention``."""
     import torch.fx as fx
     if stay_on_codes and not shared_holders:
         raise ValueError("stay_on_codes=True needs shared_holders=True")
@@ -3559,7 +3808,9 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
     if muls:
         replaced += _operator_between_holders(gm, mods, consumer_for, pools, _mul_operands, QuantizedMul, "_mul")
     if matmuls:                                              # (behind the two: it sees the QuantizedConcat / QuantizedMul nodes)
-        replaced += _matmuls_on_codes(gm, mods, consumer_for)
+        replaced += _matmuls_on_codes(gm, mods, consumer_for, softmaxes)
+    elif softmaxes:
+        replaced += _softmaxes_on_codes(gm, mods, consumer_for)
     # (an upsample's plan is made where a pool's is, in these two passes: it sees the QuantizedConcat / QuantizedMul nodes above)
     if shared_holders:
         replaced += _join_shared_holders(gm, mods, consumer_for, pools, avg_pools, upsamples, activation_tables)

@@ -163,6 +163,9 @@ SIGNATURES = {
                                  + [ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),  # output form; stream
     "mctq_codes_table": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,    # in, its type, out, its type, n
                                         ctypes.c_void_p, ctypes.c_void_p]),                                             # table, stream
+    "mctq_codes_softmax": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_float,    # in, its type, out, its type, scale
+                                          ctypes.c_int32, ctypes.c_int32, ctypes.c_int32] + [ctypes.c_int64] * 4         # zero point, qmin, qmax; rows, L, in_pitch, out_pitch
+                           + [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),                       # pad_code, exp_table, pre_table, stream
     "mctq_qconv_dw_i8": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,   # a_codes, type, zero point, scale
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,  # w_codes, w_scales, w_zero_points, bias
                                         ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_int32,

@@ -972,6 +972,81 @@ def codes_table(codes, table, out_dtype):
     return table[codes.view(torch.uint8).long()].view(out_dtype)
 
 
+_SOFTMAX_MAX_CHUNKS = 2048      # 16-byte chunks of one row of a mctq_codes_softmax launch (its block form: 256 lanes x 8)
+
+
+def softmax_exp_table(scale: float):
+    """The table of ``codes_softmax`` for an input holder of ``scale``: uint32 [256] (a numpy array),
+    ``E[d] = rint(exp(-d * float64(float32(scale))) * 2^24)``, evaluated in float64; ``E[0] = 2^24``."""
+    import numpy as np
+    s = np.float64(np.float32(scale))
+    return np.rint(np.exp(-np.arange(256, dtype=np.float64) * s) * 2.0 ** 24).astype(np.uint32)
+
+
+def codes_softmax(codes, in_form, out_form, pre_table=None, pad_to=None, exp_table=None):
+    """``softmax(dim=-1)`` between two holders on codes: int8 / uint8 ``codes`` of any rank >= 1 -> the codes of holder B,
+    ``out_form = (scale, zero_point, qmin, qmax)``, in the same shape.  ``in_form = (scale, zero_point, ...)`` is that of holder A,
+    directly in front of the softmax.  ``pre_table`` (uint8 [256] on the codes' device, ``code_table``): an elementwise prefix
+    between the holder that wrote ``codes`` and A, applied first -- ``c = pre_table[raw byte]``, A's code; without it ``codes`` are
+    A's.  The contract is on integers, so that no summation order enters it.  Per row of A-codes ``c_j``, j < L:
+
+        d_j    = max_j c_j - c_j                                   0 .. 255; A's zero point cancels
+        S      = sum_j E[d_j]                                      an exact integer (at most 2^39); E = softmax_exp_table(scale_a)
+        p_j    = float32(E[d_j]) / float32(S)                      one IEEE float32 division
+        code_j = clamp(rint(p_j * (1 / scale_b)) + zp_b, qmin, qmax)
+
+    ``pad_to=16``: the last dimension of the result is ``16 * ceil(L / 16)`` and its tail holds B's zero-point code -- the rows the
+    integer product takes as its first operand (``qmatmul_i8(..., a_padded_k=L)``).  ``exp_table``: the uint32 [256] table as an
+    int32 tensor on the codes' device (a caller that keeps it); built and uploaded here otherwise.  GPU tensors whose last
+    dimension is contiguous take one launch of mctq_codes_softmax (1 byte read and 1 written per element) for rows of up to
+    32768 elements; longer rows, a last dimension that is not contiguous and CPU tensors evaluate the lines above with torch
+    ops -- an int64 sum --, which the kernel matches byte for byte."""
+    if not _is_codes(codes) or codes.dim() < 1:
+        raise TypeError("codes_softmax takes int8 / uint8 codes of at least one dimension")
+    if pad_to not in (None, 16):
+        raise ValueError(f"codes_softmax: pad_to must be None or 16, got {pad_to!r}")
+    a_scale, a_zp = float(in_form[0]), int(in_form[1])
+    o_scale, o_zp, qmin, qmax, tdt, ocode = _out_form(out_form)
+    _check_form("codes_softmax", None, scale=(a_scale, o_scale))
+    _check_form("codes_softmax", tdt, o_zp, zp_words="the output's zero point {}")
+    if pre_table is not None:
+        if not isinstance(pre_table, torch.Tensor) or pre_table.dtype != torch.uint8 or tuple(pre_table.shape) != (256,):
+            raise TypeError("codes_softmax: pre_table must be a uint8 tensor of shape [256]")
+        if pre_table.device != codes.device:
+            raise RuntimeError(f"codes_softmax: pre_table must be on the codes' device, got {pre_table.device} and {codes.device}")
+    # A's code type: with a pre-table the type of its entries, which in_form's clamp domain names; the codes' own otherwise
+    a_tdt = _code_dtype(int(in_form[2]), int(in_form[3]))[0] if pre_table is not None and len(in_form) >= 4 else codes.dtype
+    L = codes.shape[-1]
+    lp = -(-L // 16) * 16 if pad_to == 16 else L
+    rows = codes.numel() // L if L else 0
+    out_shape = tuple(codes.shape[:-1]) + (lp,)
+    if rows == 0:
+        return codes.new_empty(out_shape, dtype=tdt)
+    if exp_table is None:
+        exp_table = torch.from_numpy(softmax_exp_table(a_scale).view("int32")).to(codes.device)
+    chunks = -(-lp // 16) if L % 16 == 0 else (lp + 30) // 16 + 1                   # the launcher's count
+    if codes.is_cuda and codes.stride(-1) == 1 and chunks <= _SOFTMAX_MAX_CHUNKS and rows * lp < 2 ** 31:
+        x = _contiguous(codes)
+        if x.data_ptr() % 16:
+            x = x.clone()
+        y = torch.empty(out_shape, dtype=tdt, device=x.device)
+        e, t = _contiguous(exp_table), None if pre_table is None else _contiguous(pre_table)     # named: they must outlive the launch
+        _gpu_call("mctq_codes_softmax", x, x.data_ptr(), native.CODE_U8 if a_tdt == torch.uint8 else native.CODE_I8, y.data_ptr(),
+                  ocode, o_scale, o_zp, qmin, qmax, rows, L, L, lp, o_zp, e.data_ptr(), None if t is None else t.data_ptr())
+        return y
+    if not codes.is_cuda:
+        _cpu_route_allowed()
+    with torch.no_grad():
+        c = codes if pre_table is None else pre_table[codes.view(torch.uint8).long()]
+        c = c.view(a_tdt).to(torch.int64)
+        e = (exp_table.to(torch.int64) & 0xffffffff)[c.amax(-1, keepdim=True) - c]
+        p = e.to(torch.float32) / e.sum(-1, keepdim=True).to(torch.float32)
+        f32 = lambda v: torch.tensor(v, dtype=torch.float64, device=codes.device).to(torch.float32)               # noqa: E731
+        q = torch.round(p * (torch.tensor(1.0, dtype=torch.float32, device=codes.device) / f32(o_scale))) + float(o_zp)
+        y = torch.clamp(q, qmin, qmax).to(tdt)
+        return y if lp == L else torch.nn.functional.pad(y, (0, lp - L), value=o_zp)
+
+
 def codes_mul(a, g, out_form, gate_form=None):
     """``torch.mul`` of two holder outputs on activation codes, in the form of the holder behind it.  ``a = (codes, scale,
     zero_point)``, int8 / uint8 codes ``[.., C]`` (channels last); ``g = (tensor, scale, zero_point)``, codes likewise or, with
