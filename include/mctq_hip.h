@@ -803,6 +803,34 @@ int mctq_codes_softmax(const void* in, int32_t in_code_dtype, void* out, int32_t
                        void* stream);
 
 /*
+ * LayerNorm over the rows of a code tensor between two activation holders A and B (extension, additive to v10; the reference
+ * runs torch.nn.LayerNorm on A's float32 output and B on the result): the norms of a transformer layer on codes.  Mean and
+ * variance are exact integers, so that no summation order enters the result.  Row r is the length bytes at in + r * length,
+ * codes c_j of the type in_code_dtype; per row, with L = length,
+ *     u_j    = c_j - in_zero_point                                  |u_j| <= 255
+ *     S1     = sum_j u_j,  S2 = sum_j u_j^2                         exact integers
+ *     n_j    = L * u_j - S1,  V = L * S2 - S1^2                     exact; |n_j| < 2^24, 0 <= V < 2^47
+ *     r      = float32(1.0 / sqrt(float64(V) + k_term))             IEEE float64 add, square root and division, one rounding
+ *     y_j    = (float32(n_j) * r) * gamma_j + beta_j                two float32 multiplies and one float32 add, not fused
+ *     code_j = clamp(rint(y_j * (1 / out_scale)) + out_zero_point, out_quant_min, out_quant_max)
+ * k_term = eps * L^2 / (double)(float)scale_a^2, formed by the caller in float64 (ops.codes_layernorm): LayerNorm's
+ * (x - mean) / sqrt(var + eps) of x = u * scale_a with numerator and denominator multiplied by L / scale_a.  gamma, beta:
+ * length float32 each on the DEVICE (ones and zeros for a norm without them).  in, out, gamma, beta: DEVICE pointers, 16-byte
+ * aligned; length a multiple of 16, at most 8192; out is written at the same pitch.  A row is read once as 16-byte chunks,
+ * kept in registers and written once; gamma and beta are read once per wave (wave form) or workgroup (block form), not once
+ * per row: the grid is persistent.  Two forms with the same bytes: one wave per row at a time (length <= 2048), one workgroup
+ * per row at a time (<= 8192); tuning keys "layernorm_form" and "layernorm_blocks".
+ * MCTQ_E_ARG with a mctq_last_error text, before anything is launched, for: negative rows or length; a bad code type; a zero
+ * point that is no code of its type; an out_scale that is not finite and positive; a clamp domain outside the type; a length
+ * that is no multiple of 16 or exceeds 8192; a k_term that is not finite and positive; with rows, length > 0: more than
+ * 2^31 - 1 bytes, a NULL or misaligned pointer, an `out` that overlaps in, gamma or beta.  rows == 0 or length == 0 returns 0
+ * without a launch.  mctq_last_launch names the launch "codes_layernorm", op "<in> -> <out> wave|block", U = the chunks per lane.
+ */
+int mctq_codes_layernorm(const void* in, int32_t in_code_dtype, int32_t in_zero_point, void* out, int32_t out_code_dtype,
+                         float out_scale, int32_t out_zero_point, int32_t out_quant_min, int32_t out_quant_max, int64_t rows,
+                         int64_t length, const void* gamma, const void* beta, double k_term, void* stream);
+
+/*
  * Depthwise convolution on activation codes (groups == channels, channel multiplier 1; extension, the reference has no
  * counterpart): what a wrapped depthwise torch.nn.Conv2d computes on fake-quantized operands, evaluated on the codes.
  *     acc[b][oy][ox][c] = sum over the taps (ky, kx) inside the image of
@@ -1210,6 +1238,11 @@ int mctq_qconv_dw_i8_act(const void* a_codes, int32_t a_code_dtype, int32_t a_ze
  *                  six attention shapes where both fit: the wave form won four, 1.6 - 3.5 x, and tied the two small batch-1
  *                  launches, 12 x 128 x 128 and 12 x 197 x 197, within 7 %; the block form won none), 1 = the wave form
  *                  where it fits, 2 = the block form.  The bytes are the same: the sums are integers
+ *   key "layernorm_form" : mctq_codes_layernorm: 0 (default) = the launcher chooses, the wave form wherever a row fits it
+ *                  (length <= 2048), 1 = the wave form where it fits, 2 = the block form.  The bytes are the same
+ *   key "layernorm_blocks" : mctq_codes_layernorm: 0 (default) = the launcher chooses the grid (eight workgroups per CU, or one
+ *                  worker per row where that is fewer), 1 .. 65536 = that many workgroups, each of which walks its share of the
+ *                  rows.  The bytes are the same
  * Only variants a default dispatcher can select are instantiated; every value of every key is exercised by the GPU tests.
  * Returns 0, or MCTQ_E_ARG for an unknown key/value.  Numerical results never depend on it.
  */

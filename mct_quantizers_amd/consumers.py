@@ -146,6 +146,13 @@ kernel form give the same bytes, and against the float32 chain a code can differ
 table inside the launch; the product in front emits the scores as codes and the product behind reads the probabilities at its own pitch.
 Measured / not measured: see the README paragraph and ``profiles/EXPERIMENTS.md``.
 
+The LayerNorm of a transformer layer stays on codes with ``fuse_linear_consumers_fx(..., layernorms=True)``: residual-stream holder A ->
+``nn.LayerNorm`` -> holder B -> wrapped Linear(s) becomes one ``QuantizedLayerNorm`` (``ops.codes_layernorm``, ``mctq_codes_layernorm``), 1 byte
+read and 1 written per element.  Mean and variance of a row are exact integers in A's codes, ``1 / sqrt`` is one float64 line and the rest
+float32 without fusing, so no summation order enters the contract: CPU and GPU and every kernel form give the same bytes, and against
+the float32 chain a code can differ by one, next to a rounding tie only.
+Measured / not measured: see the README paragraph and ``profiles/EXPERIMENTS.md``.
+
 The six modules derive from ``IntegerConsumer``, which owns what they share: the checks of the quantizers and of the float32
 weight and bias, the cache of the weight's codes, the step from ``forward``'s input to activation codes, ``from_wrapper`` and
 the ``emit_codes_for`` / ``emit_clamp`` output form.  ``QuantizedLinear`` is the product over ``[O, K]`` rows; ``QuantizedConv1x1``
@@ -1829,6 +1836,72 @@ class QuantizedSoftmax(_OnCodes):
                                  exp_table=exp)
 
 
+class QuantizedLayerNorm(_OnCodes):
+    """``activation holder A -> nn.LayerNorm -> activation holder B`` on integer codes: the two norms of a pre-norm transformer
+    layer, between the holder on the residual stream and the holder in front of q / k / v or fc1.  ``ops.codes_layernorm``
+    (``mctq_codes_layernorm``): one launch, 1 byte read and 1 written per element, where the float32 chain runs A, ATen's layer
+    norm, B and a quantize launch over 4-byte elements.
+
+    A's output is ``(c - zp_a) * s_a``, so mean and variance of a row are exact integers in the codes: with ``u = c - zp_a``,
+    ``S1 = sum u``, ``S2 = sum u^2``, the contract is ``r = float32(1 / sqrt(float64(L * S2 - S1^2) + eps * L^2 / s_a^2))``,
+    ``y_j = (float32(L * u_j - S1) * r) * gamma_j + beta_j`` in float32, not fused, then B's code of ``y_j``.  No summation order
+    enters it, so the CPU route and every kernel form give the same bytes; against the float32 chain A -> LayerNorm -> B a code
+    can differ by one, and only next to a rounding tie.
+
+    ``in_quantizer``: A's; ``norm``: the ``nn.LayerNorm``, kept as a submodule (``state_dict`` keys, ``.to()``), one normalized
+    dimension, ``eps > 0``, float32 parameters or none (ones and zeros stand in for a missing ``weight`` / ``bias``);
+    ``out_quantizer``: B's.  Per-tensor affine activation quantizers of at most 8 bits whose zero points are codes of their
+    type.  ``forward`` takes A's codes (``activation_code_params``) or a float32 tensor, which it quantizes in A's form, of any
+    rank -- the norm runs over the last dimension -- and returns B's codes (``output_code_params``) in the same shape."""
+
+    def __init__(self, in_quantizer, norm, out_quantizer):
+        super().__init__()
+        if not self.eligible(norm):
+            raise TypeError("QuantizedLayerNorm takes torch.nn.LayerNorm layers over one dimension with eps > 0 and float32 parameters")
+        self.in_quantizer, self.out_quantizer = in_quantizer, out_quantizer
+        self._in_form = _code_form(in_quantizer)
+        self._out_form = _code_form(out_quantizer)
+        self.norm = norm
+        self._defaults = {}                                    # device -> (ones, zeros) for the parameters the norm lacks
+
+    @staticmethod
+    def eligible(norm) -> bool:
+        if type(norm) is not nn.LayerNorm or len(norm.normalized_shape) != 1 or norm.training:
+            return False
+        if not isinstance(norm.eps, (int, float)) or not 0.0 < norm.eps < math.inf:
+            return False
+        return all(p is None or p.dtype == torch.float32 for p in (norm.weight, norm.bias))
+
+    def activation_code_params(self):
+        """(scale, zero_point, qmin, qmax) of the codes this module READS: what the producer in front emits."""
+        return self._in_form
+
+    def output_code_params(self):
+        """(scale, zero_point, qmin, qmax) of the codes ``forward`` returns (holder B's)."""
+        return self._out_form
+
+    def extra_repr(self) -> str:
+        return f"eps={self.norm.eps}"
+
+    def _parameters_on(self, device):
+        weight, bias = self.norm.weight, self.norm.bias
+        if weight is None or bias is None:
+            key = str(device)
+            if key not in self._defaults:
+                size = self.norm.normalized_shape[0]
+                self._defaults[key] = (torch.ones(size, device=device), torch.zeros(size, device=device))
+            ones, zeros = self._defaults[key]
+            weight, bias = ones if weight is None else weight, zeros if bias is None else bias
+        return weight, bias
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if x.dim() < 1 or x.shape[-1] != self.norm.normalized_shape[0]:
+            raise RuntimeError(f"expected [..., {self.norm.normalized_shape[0]}], got {tuple(x.shape)}")
+        codes = _operand_codes(x, self._in_form, "QuantizedLayerNorm", "this norm's input quantizer", nhwc=False)
+        weight, bias = self._parameters_on(codes.device)
+        return ops.codes_layernorm(codes, self._in_form, self._out_form, weight, bias, self.norm.eps)
+
+
 class _OperandsOnCodes(_OnCodes):
     """What QuantizedConcat, QuantizedMul and QuantizedMatmul share: several operands, each read as the codes of its own holder's
     quantizer, and one output holder's quantizer, all per-tensor affine of at most 8 bits (``_code_form``).  With
@@ -2024,7 +2097,8 @@ def _consumer_for(wrapper, activation_quantizer, uniform_weights=False, convolut
 
 
 # what reads the activation codes of the module in front as they are
-_CODE_READERS = (IntegerConsumer, QuantizedMaxPool2d, QuantizedAvgPool2d, QuantizedUpsample, QuantizedActivationTable)
+_CODE_READERS = (IntegerConsumer, QuantizedMaxPool2d, QuantizedAvgPool2d, QuantizedUpsample, QuantizedActivationTable,
+                 QuantizedLayerNorm)
 
 
 class _FusedAway(nn.Identity):
@@ -2595,6 +2669,9 @@ def _join_shared_holders(gm, mods, consumer_for, pools: bool = False, avg_pools:
                      if _reads_as_matmul_operands(user, node, _code_form(quantizer), mods) and all(user is not t for t in muls)]
         except (TypeError, ValueError, NotImplementedError):
             pass
+        # ... and the QuantizedLayerNorm nodes of ``_layernorms_on_codes`` that read this holder (built with its quantizer)
+        muls += [user for user in node.users if isinstance(_module_of(user, mods), QuantizedLayerNorm) and not user.kwargs
+                 and user.args == (node,) and _module_of(user, mods).in_quantizer is quantizer]
         if not taken and not pooled and not muls:
             continue
         on_codes = [t for t, _ in taken] + [t for t, _ in pooled] + muls
@@ -2991,6 +3068,88 @@ def _softmaxes_on_codes(gm, mods, consumer_for) -> int:
                 product = _module_of(reader, mods)
                 if isinstance(product, QuantizedMatmul) and not reader.kwargs and reader.args[0] is new and reader.args[1] is not new:
                     module.pad_rows = product.a_padded = True
+    return replaced
+
+
+def _layernorm_of(node, mods):
+    """``(tensor operand, nn.LayerNorm)`` if ``node`` is a LayerNorm over the last dimension that QuantizedLayerNorm can take: a
+    call of an ``nn.LayerNorm`` module, or ``F.layer_norm`` with a constant one-dimensional ``normalized_shape`` and ``eps`` and
+    parameters that are ``get_attr`` nodes or None, for which a module is built around those parameters.  Else None."""
+    from torch.fx import Node
+    if not node.args or not isinstance(node.args[0], Node):
+        return None
+    norm = None
+    if node.op == "call_module" and len(node.args) == 1 and not node.kwargs:
+        norm = mods.get(node.target)
+    elif node.op == "call_function" and node.target is torch.nn.functional.layer_norm:
+        names = ("normalized_shape", "weight", "bias", "eps")
+        rest = node.args[1:]
+        if len(rest) > len(names) or set(node.kwargs) - set(names[len(rest):]):
+            return None
+        given = dict(zip(names, rest), **node.kwargs)
+        shape, params = given.get("normalized_shape"), []
+        if isinstance(shape, int) and not isinstance(shape, bool):
+            shape = (shape,)
+        if not isinstance(shape, (tuple, list, torch.Size)) or len(shape) != 1 or not isinstance(shape[0], int) \
+                or isinstance(given.get("eps", 1e-5), Node):
+            return None
+        for name in ("weight", "bias"):
+            p = given.get(name)
+            if isinstance(p, Node):
+                if p.op != "get_attr":
+                    return None
+                try:
+                    p = node.graph.owning_module.get_parameter(p.target)
+                except AttributeError:                       # a buffer or a plain tensor attribute: left alone
+                    return None
+            if p is not None and not isinstance(p, nn.Parameter):
+                return None
+            params.append(p)
+        norm = nn.LayerNorm(shape[0], eps=given.get("eps", 1e-5), elementwise_affine=False).eval()
+        # The model's own Parameters, tied: the node's ``norm.weight`` / ``norm.bias`` and the attributes the call read are one
+        # tensor under two ``state_dict`` keys, as tied weights are; training or loading either name moves both.
+        norm.weight, norm.bias = params
+    return (node.args[0], norm) if QuantizedLayerNorm.eligible(norm) else None
+
+
+def _layernorms_on_codes(gm, mods, consumer_for) -> int:
+    """``fuse_linear_consumers_fx(layernorms=True)``.  The candidate is a LayerNorm over the last dimension (``_layernorm_of``) of
+    the output of a plain holder A, whose one user is a plain holder B every user of which is a wrapped ``nn.Linear``
+    ``consumer_for`` can take, fed by B alone (the three of q / k / v, one fused qkv, fc1).  A, the norm and B become one
+    QuantizedLayerNorm node ``<B's name>_layernorm`` and the layers behind it consumers.  A holder A that the norm alone reads
+    leaves the graph and the node quantizes A's input; one with other users (the residual add) stays, and the node quantizes
+    its float32 output -- the same codes -- until ``_join_shared_holders`` makes A a join and hands the node its codes.
+    Returns the number of wrapped layers replaced."""
+    replaced = 0
+    for node in list(gm.graph.nodes):
+        found = _layernorm_of(node, mods)
+        if found is None or len(node.users) != 1:
+            continue
+        a_node, norm = found
+        holder_a, b_node = _holder_of(a_node, mods), next(iter(node.users))
+        holder_b = _holder_of(b_node, mods)
+        if holder_a is None or holder_b is None or b_node.args != (node,) or not b_node.users:
+            continue
+        quantizer_b = holder_b.activation_holder_quantizer
+        taken = _wrapped_users(b_node, mods, quantizer_b, consumer_for, rows=True)
+        if taken is None:
+            continue
+        try:
+            module = QuantizedLayerNorm(holder_a.activation_holder_quantizer, norm, quantizer_b)
+        except (TypeError, ValueError, NotImplementedError):
+            continue
+        name = b_node.target.replace(".", "_") + "_layernorm"
+        gm.add_submodule(name, module)
+        mods[name] = module
+        alone = len(a_node.users) == 1
+        with gm.graph.inserting_before(b_node):
+            new = gm.graph.call_module(name, (a_node.args[0] if alone else a_node,))
+        b_node.replace_all_uses_with(new)
+        for dead in [b_node, node] + ([a_node] if alone else []):
+            gm.graph.erase_node(dead)
+        for user, fused in taken:
+            _install_consumer(gm, mods, user, fused)
+            replaced += 1
     return replaced
 
 
@@ -3515,7 +3674,7 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
                              concats: bool = False, avg_pools: bool = False, muls: bool = False,
                              hard_activations: bool = False, upsamples: bool = False, any_channels: bool = False,
                              activation_tables: bool = False, grouped: bool = False, transposed: bool = False,
-                             matmuls: bool = False, softmaxes: bool = False):
+                             matmuls: bool = False, softmaxes: bool = False, layernorms: bool = False):
     """The same rewrite on an arbitrary module graph (MCT-exported models are not ``nn.Sequential``): traces ``model``
     with torch.fx keeping wrappers and holders as leaves, and wherever an activation holder's ONLY consumer is a
     wrapped ``nn.Linear`` the integer consumer can take (symmetric, power-of-two or LUT weights, and with
@@ -3782,7 +3941,23 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
     integer softmax that no summation order enters: CPU and GPU, and every kernel form, give the same bytes; against the float32
     chain A -> softmax -> B a code can differ by one, and only next to a rounding tie.  Left alone: another ``dim``; an additive
     mask or any tensor operand between the holders; ``log_softmax``; a float32 user of the softmax or of B; no holder B;
-    quantizers wider than 8 bits or per-channel; ``F.scaled_dot_product_attention``."""
+    quantizers wider than 8 bits or per-channel; ``F.scaled_dot_product_attention``.
+
+    ``layernorms=True`` (needs no other switch and composes with all of them; fx only) keeps the LayerNorm between two holders on
+    codes: the two norms of a pre-norm transformer layer, ``residual-stream holder A -> LayerNorm -> holder B -> wrapped
+    Linear(s)``.  The candidate is a call of an ``nn.LayerNorm`` module, or ``F.layer_norm`` with constant arguments, over the last
+    dimension only, with ``eps > 0`` and float32 parameters (or none), of the output of a plain holder A; its one user is a
+    plain holder B all of whose users are wrapped ``nn.Linear`` layers the consumer can take under the other switches, fed by B
+    alone -- q / k / v, a fused qkv, fc1 (counted in the returned total).  A, the norm and B become one QuantizedLayerNorm node
+    ``<B's name>_layernorm`` (``mctq_codes_layernorm``: 1 byte read and 1 written per element).  A leaves the graph when the norm
+    alone reads it; with other users (the residual add) it stays and the node quantizes its float32 output, the same codes;
+    with ``shared_holders=True`` it becomes a join that hands the node its codes, and with ``stay_on_codes=True`` a consumer in
+    front of A emits them.  The contract is QuantizedLayerNorm's: mean and variance are exact integers in the codes, so CPU and
+    GPU, and every kernel form, give the same bytes; against the float32 chain A -> LayerNorm -> B a code can differ by one, and
+    only next to a rounding tie.  Left alone: a norm without a holder A in front (the first layer's norm on raw embeddings;
+    ``workloads.wrapped_attention_block`` as it stands); no holder B; a float32 user of the norm or of B; ``eps <= 0``; half
+    precision parameters; more than one normalized dimension; ``RMSNorm``, ``GroupNorm``, ``BatchNorm``; training mode;
+    quantizers wider than 8 bits or per-channel."""
     import torch.fx as fx
     if stay_on_codes and not shared_holders:
         raise ValueError("stay_on_codes=True needs shared_holders=True")
@@ -3811,6 +3986,8 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
         replaced += _matmuls_on_codes(gm, mods, consumer_for, softmaxes)
     elif softmaxes:
         replaced += _softmaxes_on_codes(gm, mods, consumer_for)
+    if layernorms:                                           # (in front of the joins: a holder A with other users becomes one)
+        replaced += _layernorms_on_codes(gm, mods, consumer_for)
     # (an upsample's plan is made where a pool's is, in these two passes: it sees the QuantizedConcat / QuantizedMul nodes above)
     if shared_holders:
         replaced += _join_shared_holders(gm, mods, consumer_for, pools, avg_pools, upsamples, activation_tables)

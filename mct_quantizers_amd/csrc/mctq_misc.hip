@@ -29,6 +29,8 @@ int g_concat_copy = 1;       // mctq_codes_concat_nhwc, mctq_codes_upsample_nhwc
 int g_im2col_grain = 0;      // mctq_codes_im2col_pad_nhwc: bytes per load piece, 0 = by rule (4 where channels % 4 == 0, else 1), 1, 4 (the result is the same)
 int g_table_chunks = 4;      // mctq_codes_table: 16-byte chunks per lane, 1, 2 or 4 (the result is the same)
 int g_softmax_form = 0;      // mctq_codes_softmax: 0 = the launcher chooses (the wave form wherever it fits), 1 = wave form, 2 = block form (the result is the same)
+int g_layernorm_form = 0;    // mctq_codes_layernorm: 0 = the launcher chooses (the wave form wherever it fits), 1 = wave form, 2 = block form (the result is the same)
+int g_layernorm_blocks = 0;  // mctq_codes_layernorm: 0 = the launcher chooses the grid, otherwise the number of workgroups (the result is the same)
 int g_upsample_form = 0;     // mctq_codes_upsample_nhwc: 0 = the launcher chooses (replicate for integer factors of 2 .. 16 outputs per input), 1 = gather form, 2 = replicate form where eligible (the result is the same)
 
 static const char* launch_log_path() {
@@ -229,6 +231,16 @@ int mctq_set_tuning(const char* key, int32_t value) {
   if (!strcmp(key, "softmax_form")) {
     if (value < 0 || value > 2) return fail_arg("softmax_form must be 0 (auto), 1 (wave) or 2 (block)");
     g_softmax_form = value;
+    return 0;
+  }
+  if (!strcmp(key, "layernorm_form")) {
+    if (value < 0 || value > 2) return fail_arg("layernorm_form must be 0 (auto), 1 (wave) or 2 (block)");
+    g_layernorm_form = value;
+    return 0;
+  }
+  if (!strcmp(key, "layernorm_blocks")) {
+    if (value < 0 || value > 65536) return fail_arg("layernorm_blocks must be 0 (auto) or a grid size of at most 65536");
+    g_layernorm_blocks = value;
     return 0;
   }
   if (!strcmp(key, "upsample_form")) {

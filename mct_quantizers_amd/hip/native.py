@@ -166,6 +166,9 @@ SIGNATURES = {
     "mctq_codes_softmax": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_float,    # in, its type, out, its type, scale
                                           ctypes.c_int32, ctypes.c_int32, ctypes.c_int32] + [ctypes.c_int64] * 4         # zero point, qmin, qmax; rows, L, in_pitch, out_pitch
                            + [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),                       # pad_code, exp_table, pre_table, stream
+    "mctq_codes_layernorm": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,  # in, its type, zero point, out, its type
+                                            ctypes.c_float, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,    # scale, zero point, qmin, qmax; rows
+                                            ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p]),  # L, gamma, beta, k_term, stream
     "mctq_qconv_dw_i8": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,   # a_codes, type, zero point, scale
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,  # w_codes, w_scales, w_zero_points, bias
                                         ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_int32,

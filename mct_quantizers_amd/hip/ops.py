@@ -29,6 +29,7 @@ from typing import Tuple
 
 import math
 import os
+import struct
 
 import torch
 
@@ -1045,6 +1046,70 @@ def codes_softmax(codes, in_form, out_form, pre_table=None, pad_to=None, exp_tab
         q = torch.round(p * (torch.tensor(1.0, dtype=torch.float32, device=codes.device) / f32(o_scale))) + float(o_zp)
         y = torch.clamp(q, qmin, qmax).to(tdt)
         return y if lp == L else torch.nn.functional.pad(y, (0, lp - L), value=o_zp)
+
+
+_LAYERNORM_MAX_LENGTH = 8192    # codes of one row of a mctq_codes_layernorm launch (its block form: 256 lanes x 2 chunks x 16)
+
+
+def codes_layernorm(codes, in_form, out_form, weight, bias, eps):
+    """``LayerNorm`` over the last dimension between two holders on codes: int8 / uint8 ``codes`` of any rank >= 1, those of
+    holder A with ``in_form = (scale, zero_point, ...)`` -> the codes of holder B, ``out_form = (scale, zero_point, qmin, qmax)``,
+    in the same shape.  ``weight`` (gamma), ``bias`` (beta): float32 ``[L]`` on the codes' device; ``eps > 0``.  Mean and variance
+    are exact integers, so that no summation order enters the contract.  Per row of A-codes ``c_j``, j < L:
+
+        u_j    = c_j - zp_a                                        integer, |u_j| <= 255
+        S1     = sum_j u_j,  S2 = sum_j u_j^2                      exact integers
+        n_j    = L * u_j - S1                                      exact integer, |n_j| <= 510 L
+        V      = L * S2 - S1^2                                     exact int64, >= 0
+        r      = float32(1.0 / sqrt(float64(V) + K))               K = eps * L^2 / float64(float32(scale_a))^2, in float64
+        xh_j   = float32(n_j) * r                                  one float32 multiply
+        y_j    = xh_j * gamma_j + beta_j                           one float32 multiply, one float32 add, not fused
+        code_j = clamp(rint(y_j * (1 / scale_b)) + zp_b, qmin, qmax)
+
+    which is ``(x - mean) / sqrt(var + eps)`` of ``x = u * scale_a`` with numerator and denominator multiplied by ``L / scale_a``.
+    GPU tensors whose last dimension is contiguous take one launch of mctq_codes_layernorm (1 byte read and 1 written per
+    element) where ``L % 16 == 0`` and ``L <= 8192``; every other row length and CPU tensors evaluate the lines above with torch
+    ops -- int64 sums, one float64 line for ``r``, then float32 --, which the kernel matches byte for byte."""
+    if not _is_codes(codes) or codes.dim() < 1:
+        raise TypeError("codes_layernorm takes int8 / uint8 codes of at least one dimension")
+    a_scale, a_zp = float(in_form[0]), int(in_form[1])
+    o_scale, o_zp, qmin, qmax, tdt, ocode = _out_form(out_form)
+    _check_form("codes_layernorm", codes.dtype, a_zp, scale=(a_scale, o_scale), zp_words="the input's zero point {}")
+    _check_form("codes_layernorm", tdt, o_zp, zp_words="the output's zero point {}")
+    eps = float(eps)
+    if not 0.0 < eps < float("inf"):
+        raise ValueError(f"codes_layernorm: eps must be finite and positive, got {eps!r}")
+    L = codes.shape[-1]
+    for name, p in (("weight", weight), ("bias", bias)):
+        if not isinstance(p, torch.Tensor) or p.dtype != torch.float32 or tuple(p.shape) != (L,):
+            raise TypeError(f"codes_layernorm: {name} must be a float32 tensor of shape [{L}]")
+        if p.device != codes.device:
+            raise RuntimeError(f"codes_layernorm: {name} must be on the codes' device, got {p.device} and {codes.device}")
+    rows = codes.numel() // L if L else 0
+    if rows == 0:
+        return codes.new_empty(codes.shape, dtype=tdt)
+    s32 = struct.unpack("f", struct.pack("f", a_scale))[0]                        # float64(float32(scale_a))
+    k_term = eps * L * L / s32 ** 2                                               # Python floats: IEEE float64, left to right
+    if not 0.0 < k_term < float("inf"):
+        raise ValueError("codes_layernorm: eps * L^2 / scale^2 must be finite and positive")
+    if codes.is_cuda and codes.stride(-1) == 1 and L % 16 == 0 and L <= _LAYERNORM_MAX_LENGTH and rows * L < 2 ** 31:
+        x = _contiguous(codes)
+        x, g, b = (t if t.data_ptr() % 16 == 0 else t.clone() for t in (x, _contiguous(weight), _contiguous(bias)))
+        y = torch.empty(codes.shape, dtype=tdt, device=x.device)
+        _gpu_call("mctq_codes_layernorm", x, x.data_ptr(), _code_of(x), a_zp, y.data_ptr(), ocode, o_scale, o_zp, qmin, qmax,
+                  rows, L, g.data_ptr(), b.data_ptr(), k_term)
+        return y
+    if not codes.is_cuda:
+        _cpu_route_allowed()
+    with torch.no_grad():
+        u = codes.to(torch.int64) - a_zp
+        s1 = u.sum(-1, keepdim=True)
+        n, v = L * u - s1, L * (u * u).sum(-1, keepdim=True) - s1 * s1
+        r = (1.0 / torch.sqrt(v.to(torch.float64) + k_term)).to(torch.float32)
+        y = (n.to(torch.float32) * r) * weight + bias
+        f32 = lambda t: torch.tensor(t, dtype=torch.float64, device=codes.device).to(torch.float32)               # noqa: E731
+        q = torch.round(y * (torch.tensor(1.0, dtype=torch.float32, device=codes.device) / f32(o_scale))) + float(o_zp)
+        return torch.clamp(q, qmin, qmax).to(tdt)
 
 
 def codes_mul(a, g, out_form, gate_form=None):

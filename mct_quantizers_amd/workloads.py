@@ -349,3 +349,74 @@ def wrapped_attention_block(dim: int = 64, heads: int = 2, tokens: int = 17, dev
     block = _attention_class()(dim, heads, tokens, nn.LayerNorm(dim), a_in, qkv, a_qkv, a_scores, a_scaled, a_probs, a_ctx,
                                wrap(dim, dim))
     return block.to(device).eval()
+
+
+def _encoder_class():
+    """One pre-norm encoder layer around an ``_AttentionBlock`` (which begins with norm1 and its holder), with a holder on the
+    residual stream; a module attribute for the same reason as ``_Bottleneck``."""
+    import torch.nn as nn
+    if "_EncoderBlock" in globals():
+        return globals()["_EncoderBlock"]
+
+    class EncoderBlock(nn.Module):
+        def __init__(self, a_x, attn, a_proj, a_res, norm2, a_n2, fc1, act, a_h, fc2, a_fc2, a_out):
+            super().__init__()
+            self.a_x, self.attn, self.a_proj, self.a_res = a_x, attn, a_proj, a_res
+            self.norm2, self.a_n2, self.fc1, self.act, self.a_h, self.fc2, self.a_fc2, self.a_out = norm2, a_n2, fc1, act, a_h, fc2, a_fc2, a_out
+
+        def forward(self, x):
+            x = self.a_x(x)
+            x = self.a_res(x + self.a_proj(self.attn(x)))
+            h = self.a_h(self.act(self.fc1(self.a_n2(self.norm2(x)))))
+            return self.a_out(x + self.a_fc2(self.fc2(h)))
+
+    EncoderBlock.__name__ = EncoderBlock.__qualname__ = "_EncoderBlock"
+    EncoderBlock.__module__ = __name__
+    globals()["_EncoderBlock"] = EncoderBlock
+    return EncoderBlock
+
+
+def wrapped_encoder_block(dim: int = 64, heads: int = 2, tokens: int = 17, hidden: int = 128, device="cpu", uniform: bool = False,
+                          seed: int = 0):
+    """One pre-norm encoder layer as an MCT export of a ViT / DeiT / BERT layer decomposes it, with a holder on the residual
+    stream: ``a_x -> norm1 -> a_in -> [the attention of wrapped_attention_block] -> a_proj``, ``a_res = holder(a_x + a_proj) ->
+    norm2 -> a_n2 -> fc1 -> GELU -> a_h -> fc2 -> a_fc2 -> a_out = holder(a_res + a_fc2)``.  Both norms stand between two holders,
+    the pattern ``fuse_linear_consumers_fx(..., layernorms=True)`` takes.  Input ``[B, tokens, dim]``.
+
+    Quantizers as ``wrapped_attention_block``'s: 8-bit power-of-two weights and symmetric holders with power-of-two thresholds,
+    or with ``uniform=True`` uniform holders over odd ranges.  The LayerNorm parameters are seeded and not trivial (gamma around
+    1, beta around 0).  Pure workload: seeded random weights, no checkpoint."""
+    import torch
+    import torch.nn as nn
+    import mct_quantizers_amd as mq
+    Q = mq.pytorch_quantizers
+    gen = torch.Generator().manual_seed(seed + 1)
+    attn = wrapped_attention_block(dim, heads, tokens, device=device, uniform=uniform, seed=seed)
+
+    def wrap(cin, cout):
+        layer = nn.Linear(cin, cout, bias=False)
+        with torch.no_grad():
+            layer.weight.copy_(torch.randn(cout, cin, generator=gen) * 0.25)
+        q = Q.WeightsPOTInferableQuantizer(num_bits=8, threshold=[1.0] * cout, per_channel=True, channel_axis=0)
+        return mq.PytorchQuantizationWrapper(layer, {"weight": q})
+
+    ranges = iter(((-4.3, 3.9), (-3.6, 4.1), (-7.2, 6.8), (-3.3, 3.7), (-0.2, 4.4), (-3.8, 3.5), (-7.5, 8.3)))
+
+    def holder(threshold):
+        lo_hi = next(ranges)
+        if uniform:
+            return mq.PytorchActivationQuantizationHolder(Q.ActivationUniformInferableQuantizer(8, [lo_hi[0]], [lo_hi[1]]))
+        return mq.PytorchActivationQuantizationHolder(Q.ActivationSymmetricInferableQuantizer(8, [threshold], True))
+
+    def norm():
+        layer = nn.LayerNorm(dim)
+        with torch.no_grad():
+            layer.weight.copy_(1.0 + 0.25 * torch.randn(dim, generator=gen))
+            layer.bias.copy_(0.1 * torch.randn(dim, generator=gen))
+        return layer
+
+    with torch.no_grad():
+        attn.norm.load_state_dict(norm().state_dict())
+    a_x, a_proj, a_res, a_n2, a_h, a_fc2, a_out = (holder(t) for t in (4.0, 4.0, 8.0, 4.0, 4.0, 4.0, 8.0))
+    block = _encoder_class()(a_x, attn, a_proj, a_res, norm(), a_n2, wrap(dim, hidden), nn.GELU(), a_h, wrap(hidden, dim), a_fc2, a_out)
+    return block.to(device).eval()
