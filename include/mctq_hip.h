@@ -102,6 +102,9 @@ extern "C" {
 /* v10 (additive, the version number stays): + mctq_qmatmul_i8, the batched product of two activation-code tensors by strides on
  * the integer matrix cores (the Q.K^T and P.V products of an attention block stay on codes); no existing signature or result
  * changed. */
+/* v10 (additive, the version number stays): + mctq_qattention_i8, Q.K^T, the softmax on codes and P.V of an attention block in one
+ * launch, byte for byte the result of mctq_qmatmul_i8 -> mctq_codes_softmax -> mctq_qmatmul_i8; no existing signature or result
+ * changed. */
 #define MCTQ_ABI_VERSION 10
 #define MCTQ_E_ARG (-10001)
 
@@ -979,6 +982,39 @@ int mctq_qmatmul_i8(const void* a_codes, int32_t a_code_dtype, int32_t a_zero_po
                     float b_scale, int64_t b_stride_b0, int64_t b_stride_b1, int64_t b_stride_row, int32_t transposed_b, void* y,
                     int32_t y_code_dtype, float y_scale, int32_t y_zero_point, int32_t y_quant_min, int32_t y_quant_max,
                     int64_t batch0, int64_t batch1, int64_t m, int64_t n, int64_t k, void* stream);
+
+/*
+ * The core of an attention block on codes in one launch (extension): per batch (b0, b1), with q [m][d], k [t][d], v [t][dv],
+ *     s = mctq_qmatmul_i8(q, k, transposed_b = 1) as the codes of holder A0 (s_*)
+ *     p = mctq_codes_softmax(s, pre_table, exp_table) as the codes of holder B (p_*), rows padded with p_zero_point
+ *     y = mctq_qmatmul_i8(p, v, transposed_b = 0) in the output form (y_*: y_code_dtype < 0 -> float32)
+ * and the result is that of these three launches byte for byte: both int32 sums are exact, the softmax's sum is an exact integer
+ * and every float32 step is the same single IEEE operation.  The [m][t] codes live in LDS only.  a_code_dtype is the code type
+ * of holder A, directly in front of the softmax (its scale enters through exp_table = E[256] of mctq_codes_softmax, its zero point
+ * cancels); pre_table (256 bytes, A0's raw byte -> A's, may be NULL: then A is A0 and a_code_dtype must be s_code_dtype).
+ * Operands are views by strides in bytes under mctq_qmatmul_i8's rules: unit stride along d / dv, batch and row strides
+ * non-negative multiples of 16 (a batch stride of 0 broadcasts), 16-byte aligned DEVICE pointers; int8 / uint8 in any mix.  y is
+ * contiguous [batch0][batch1][m][dv].  Limits: d and dv multiples of 16 in 16 .. 128, t <= 1024, batch0 * batch1 <= 65535.
+ * A workgroup of four waves owns 64 rows of one (b0, b1): grid ceil(m / 64) x 1 x batch0 * batch1; v_mfma_i32_16x16x64_i8.
+ * MCTQ_E_ARG with a mctq_last_error text, before any pointer is read or anything is launched, for: a bad code dtype, zero point
+ * or scale of q, k, v or p; a bad s_code_dtype, a_code_dtype or s_scale; a bad form of s, p or y (mctq_qlinear_i8_codes' checks);
+ * no pre_table and a_code_dtype != s_code_dtype; negative extents; d, dv or t outside the limits; m above 2^31 - 65;
+ * batch0 * batch1 > 65535; negative or misaligned strides, or a row stride shorter than the row; NULL or misaligned pointers of a
+ * non-empty problem (tables: 4-byte aligned); an output that overlaps an operand or a table.  An empty extent (batch0, batch1, m
+ * or t == 0) returns 0 without a launch and writes nothing.
+ * mctq_last_launch names the launch "qattention", op "<q> x <k> . <p> x <v>" with " pre" appended when pre_table was given,
+ * U = 1 * (zq' != 0) + 2 * (zk' != 0) + 4 * (zp' != 0) + 8 * (zv' != 0): the ones-MFMAs that ran (ZA / ZB of either product),
+ * z' = z - 128 for uint8 codes.
+ */
+int mctq_qattention_i8(const void* q_codes, int32_t q_code_dtype, int32_t q_zero_point, float q_scale, int64_t q_stride_b0,
+                       int64_t q_stride_b1, int64_t q_stride_row, const void* k_codes, int32_t k_code_dtype, int32_t k_zero_point,
+                       float k_scale, int64_t k_stride_b0, int64_t k_stride_b1, int64_t k_stride_row, const void* v_codes,
+                       int32_t v_code_dtype, int32_t v_zero_point, float v_scale, int64_t v_stride_b0, int64_t v_stride_b1,
+                       int64_t v_stride_row, int32_t s_code_dtype, float s_scale, int32_t s_zero_point, int32_t s_quant_min,
+                       int32_t s_quant_max, int32_t a_code_dtype, int32_t p_code_dtype, float p_scale, int32_t p_zero_point,
+                       int32_t p_quant_min, int32_t p_quant_max, const void* exp_table, const void* pre_table, void* y,
+                       int32_t y_code_dtype, float y_scale, int32_t y_zero_point, int32_t y_quant_min, int32_t y_quant_max,
+                       int64_t batch0, int64_t batch1, int64_t m, int64_t t, int64_t d, int64_t dv, void* stream);
 
 /*
  * The join in front of an activation holder that several layers share (extension; the reference runs an ATen add, an ATen

@@ -146,6 +146,11 @@ kernel form give the same bytes, and against the float32 chain a code can differ
 table inside the launch; the product in front emits the scores as codes and the product behind reads the probabilities at its own pitch.
 Measured / not measured: see the README paragraph and ``profiles/EXPERIMENTS.md``.
 
+Those three launches run as one with ``fuse_linear_consumers_fx(..., matmuls=True, softmaxes=True, attentions=True)``: the two products and
+the softmax between them become one ``QuantizedAttention`` (``qattention_i8``, ``mctq_qattention_i8``), whose workgroups keep the score and
+probability codes of 64 query rows in LDS.  The contract is the composition of the three, so the bytes are the same; shapes outside the
+kernel's limits run the three calls.  Measured / not measured: see the README paragraph and ``profiles/EXPERIMENTS.md``.
+
 The LayerNorm of a transformer layer stays on codes with ``fuse_linear_consumers_fx(..., layernorms=True)``: residual-stream holder A ->
 ``nn.LayerNorm`` -> holder B -> wrapped Linear(s) becomes one ``QuantizedLayerNorm`` (``ops.codes_layernorm``, ``mctq_codes_layernorm``), 1 byte
 read and 1 written per element.  Mean and variance of a row are exact integers in A's codes, ``1 / sqrt`` is one float64 line and the rest
@@ -782,6 +787,87 @@ def qmatmul_i8(a_codes: torch.Tensor, a_form, b_codes: torch.Tensor, b_form, *, 
         s = float(np.float32(a_scale) * np.float32(b_scale))
     y = acc.to(torch.float32) * s
     return y if out_codes is None else _cpu_out_codes(y, out_codes)
+
+
+_ATTENTION_MAX_T, _ATTENTION_MAX_D = 1024, 128          # one mctq_qattention_i8 launch: the strip of T codes a row lives in LDS
+
+
+def qattention_i8(q_codes: torch.Tensor, q_form, k_codes: torch.Tensor, k_form, v_codes: torch.Tensor, v_form, *, scores_form,
+                  a_form, probs_form, pre_table=None, exp_table=None, out_codes=None) -> torch.Tensor:
+    """The core of an attention block on codes: q ``[..., M, D]``, k ``[..., T, D]``, v ``[..., T, Dv]``, int8 or uint8 in any mix,
+    each per-tensor affine with ``form = (scale, zero_point)`` -> the context ``[..., M, Dv]``, float32 or with ``out_codes`` the codes
+    of that quantizer.  ``scores_form`` is that of holder A0 behind ``Q @ K^T``, ``a_form`` that of holder A directly in front of
+    the softmax, ``probs_form`` that of holder B behind it (each ``(scale, zero_point, qmin, qmax)``); ``pre_table`` the optional
+    uint8 [256] table A0 -> A (``ops.code_table``; without it A is A0), ``exp_table`` ``ops.softmax_exp_table(a_form[0])`` as an int32
+    tensor on the codes' device (built here otherwise).  The result is, bit for bit on every device and in every kernel form,
+
+        s = qmatmul_i8(q, q_form, k, k_form, transposed_b=True, out_codes=scores_form)
+        p = ops.codes_softmax(s, a_form, probs_form, pre_table=pre_table, pad_to=16, exp_table=exp_table)
+        y = qmatmul_i8(p, probs_form[:2], v, v_form, transposed_b=False, out_codes=out_codes, a_padded_k=T)
+
+    -- nothing new: both integer sums are exact, the softmax's sum is an exact integer and every float32 step is one IEEE operation.
+    GPU tensors with one or two batch dimensions (after broadcasting), ``D`` and ``Dv`` multiples of 16 up to 128 and ``1 <= T <=
+    1024`` run one launch of ``mctq_qattention_i8``, which keeps the ``T`` codes of 64 rows in LDS and never writes ``[M, T]`` to
+    memory; the operands go in as views under ``qmatmul_i8``'s rules (a permuted and indexed ``[B, T, 3, H, D]`` qkv tensor as it is,
+    a broadcast operand with a batch stride of 0).  Every other shape, and CPU tensors, run the three calls above."""
+    q_scale, q_zp = _matmul_form(q_codes, q_form, "q_codes")
+    k_scale, k_zp = _matmul_form(k_codes, k_form, "k_codes")
+    v_scale, v_zp = _matmul_form(v_codes, v_form, "v_codes")
+    if not q_codes.device == k_codes.device == v_codes.device:
+        raise RuntimeError(f"qattention_i8: q_codes on {q_codes.device}, k_codes on {k_codes.device}, v_codes on {v_codes.device}")
+    if min(q_codes.dim(), k_codes.dim(), v_codes.dim()) < 2:
+        raise RuntimeError("qattention_i8: q, k and v must have at least two dimensions")
+    (M, D), (T, Dk), (Tv, Dv) = q_codes.shape[-2:], k_codes.shape[-2:], v_codes.shape[-2:]
+    if Dk != D:
+        raise _k_mismatch(D, Dk, "k_codes")
+    if Tv != T:
+        raise _k_mismatch(T, Tv, "v_codes")
+    s_scale, s_zp, _, _, s_lo, s_hi = _with_clamp(scores_form)
+    p_scale, p_zp, p_qmin, p_qmax, p_tdt, p_code = ops._out_form(probs_form)
+    s_tdt, s_code = ops._code_dtype(int(scores_form[2]), int(scores_form[3]))
+    ops._check_form("qattention_i8", s_tdt, int(s_zp), (float(s_scale), float(a_form[0])), "the scores' zero point {}")
+    ops._check_form("qattention_i8", p_tdt, p_zp, p_scale, "the probabilities' zero point {}", "the probabilities' scale")
+    if out_codes is not None:
+        _with_clamp(out_codes)
+    dims = max(q_codes.dim(), k_codes.dim(), v_codes.dim())
+    if q_codes.is_cuda and dims in (3, 4) and D % 16 == 0 and Dv % 16 == 0 and D <= _ATTENTION_MAX_D and Dv <= _ATTENTION_MAX_D \
+            and 1 <= T <= _ATTENTION_MAX_T and M <= _MATMUL_MAX_M:
+        batch = torch.broadcast_shapes(q_codes.shape[:-2], k_codes.shape[:-2], v_codes.shape[:-2])
+        b0, b1 = (1, *batch) if len(batch) == 1 else batch
+        if b1 <= _MATMUL_MAX_BATCH:
+            if pre_table is not None and (pre_table.dtype != torch.uint8 or tuple(pre_table.shape) != (256,)
+                                          or pre_table.device != q_codes.device):
+                raise TypeError("qattention_i8: pre_table must be a uint8 tensor of shape [256] on the codes' device")
+            # A's code type: with a pre-table the type of its entries, which a_form's clamp domain names; the scores' own otherwise
+            a_code = ops._code_dtype(int(a_form[2]), int(a_form[3]))[1] if pre_table is not None else s_code
+            tdt, *form = _output_form(out_codes)
+            y = q_codes.new_empty((b0, b1, M, Dv), dtype=tdt)
+            if y.numel():
+                if exp_table is None:
+                    exp_table = torch.from_numpy(ops.softmax_exp_table(float(a_form[0])).view("int32")).to(q_codes.device)
+                e, t = ops._contiguous(exp_table), None if pre_table is None else ops._contiguous(pre_table)
+                views = []
+                for x, zp in ((q_codes, q_zp), (k_codes, k_zp), (v_codes, v_zp)):
+                    x4 = _matmul_view(x, zp, False)               # (D and Dv are multiples of 16: nothing to re-pitch)
+                    if x4.shape[:-2] != batch:
+                        x4 = x4.expand(*batch, *x4.shape[-2:])
+                    views.append(x4.unsqueeze(0) if len(batch) == 1 else x4)
+                step = max(1, _MATMUL_MAX_BATCH // b1)
+                for at in range(0, b0, step):
+                    q_, k_, v_ = views if step >= b0 else [x[at:at + step] for x in views]
+                    y_ = y if step >= b0 else y.new_empty((q_.shape[0], b1, M, Dv))
+                    ops._gpu_call("mctq_qattention_i8", q_, q_.data_ptr(), ops._code_of(q_), q_zp, q_scale, *_matmul_strides(q_),
+                                  k_.data_ptr(), ops._code_of(k_), k_zp, k_scale, *_matmul_strides(k_),
+                                  v_.data_ptr(), ops._code_of(v_), v_zp, v_scale, *_matmul_strides(v_),
+                                  s_code, float(s_scale), int(s_zp), s_lo, s_hi, a_code, p_code, p_scale, p_zp, p_qmin, p_qmax,
+                                  e.data_ptr(), None if t is None else t.data_ptr(), y_.data_ptr(), *form,
+                                  y_.shape[0], b1, M, T, D, Dv)
+                    if y_ is not y:
+                        y[at:at + step].copy_(y_)
+            return y.reshape(*batch, M, Dv)
+    s = qmatmul_i8(q_codes, q_form, k_codes, k_form, transposed_b=True, out_codes=scores_form)
+    p = ops.codes_softmax(s, a_form, probs_form, pre_table=pre_table, pad_to=16, exp_table=exp_table)
+    return qmatmul_i8(p, probs_form[:2], v_codes, v_form, transposed_b=False, out_codes=out_codes, a_padded_k=T)
 
 
 def pack_w4(codes: torch.Tensor) -> torch.Tensor:
@@ -1768,7 +1854,41 @@ class _ScalarStep(nn.Module):
         return x * self.value if self.op == "mul" else x / self.value
 
 
-class QuantizedSoftmax(_OnCodes):
+class _SoftmaxForms(_OnCodes):
+    """What QuantizedSoftmax and QuantizedAttention share: the forms of holder A0 (``in_quantizer``), of holder A behind the optional
+    elementwise prefix (``prefix = (callables, A's quantizer)``) and of holder B (``out_quantizer``), and the two tables, cached
+    per device."""
+
+    def _set_softmax(self, in_quantizer, out_quantizer, prefix):
+        self.in_quantizer, self.out_quantizer = in_quantizer, out_quantizer
+        self._in_form = _code_form(in_quantizer)
+        self._probs_form = _code_form(out_quantizer)
+        self.has_prefix = prefix is not None                   # (A0 and A may share one quantizer: the steps between them still count)
+        fns, a_quantizer = prefix if prefix is not None else ((), in_quantizer)
+        self.fns = nn.ModuleList(fns)
+        self.a_quantizer = a_quantizer
+        self._a_form = _code_form(a_quantizer)
+        self._tables = {}                                      # device -> (exp table, pre-table or None)
+
+    def _prefix(self, x):
+        for f in self.fns:                                     # (``ops.code_table`` codes the result in A's form: holder A)
+            x = f(x)
+        return x
+
+    def tables(self, device):
+        """``(exp table, pre-table or None)`` on ``device``, built on first use there."""
+        key = str(torch.device(device))
+        hit = self._tables.get(key)
+        if hit is None:
+            exp = torch.from_numpy(ops.softmax_exp_table(self._a_form[0]).view("int32")).to(device)
+            pre = None
+            if self.has_prefix:
+                pre = ops.code_table(self._prefix, self._in_form, self._a_form, device)
+            hit = self._tables[key] = (exp, pre)
+        return hit
+
+
+class QuantizedSoftmax(_SoftmaxForms):
     """``activation holder A0 -> [elementwise prefix -> holder A] -> softmax(dim=-1) -> activation holder B`` on integer codes: the
     stretch between the two products of an attention block, ``a_scores -> * scale -> a_scaled -> softmax -> a_probs``, its largest
     tensor.  ``ops.codes_softmax`` (``mctq_codes_softmax``): one launch, 1 byte read and 1 written per element, where the float32
@@ -1790,16 +1910,9 @@ class QuantizedSoftmax(_OnCodes):
 
     def __init__(self, in_quantizer, out_quantizer, prefix=None, pad_rows: bool = False):
         super().__init__()
-        self.in_quantizer, self.out_quantizer = in_quantizer, out_quantizer
-        self._in_form = _code_form(in_quantizer)
-        self._out_form = _code_form(out_quantizer)
-        self.has_prefix = prefix is not None                   # (A0 and A may share one quantizer: the steps between them still count)
-        fns, a_quantizer = prefix if prefix is not None else ((), in_quantizer)
-        self.fns = nn.ModuleList(fns)
-        self.a_quantizer = a_quantizer
-        self._a_form = _code_form(a_quantizer)
+        self._set_softmax(in_quantizer, out_quantizer, prefix)
+        self._out_form = self._probs_form
         self.pad_rows = bool(pad_rows)
-        self._tables = {}                                      # device -> (exp table, pre-table or None)
 
     def activation_code_params(self):
         """(scale, zero_point, qmin, qmax) of the codes this module READS: what the producer in front emits."""
@@ -1811,23 +1924,6 @@ class QuantizedSoftmax(_OnCodes):
 
     def extra_repr(self) -> str:
         return f"prefix={len(self.fns)} step(s), pad_rows={self.pad_rows}" if self.has_prefix else f"pad_rows={self.pad_rows}"
-
-    def _prefix(self, x):
-        for f in self.fns:                                     # (``ops.code_table`` codes the result in A's form: holder A)
-            x = f(x)
-        return x
-
-    def tables(self, device):
-        """``(exp table, pre-table or None)`` on ``device``, built on first use there."""
-        key = str(torch.device(device))
-        hit = self._tables.get(key)
-        if hit is None:
-            exp = torch.from_numpy(ops.softmax_exp_table(self._a_form[0]).view("int32")).to(device)
-            pre = None
-            if self.has_prefix:
-                pre = ops.code_table(self._prefix, self._in_form, self._a_form, device)
-            hit = self._tables[key] = (exp, pre)
-        return hit
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         codes = _operand_codes(x, self._in_form, "QuantizedSoftmax", "this softmax's input quantizer", nhwc=False)
@@ -2056,6 +2152,40 @@ class QuantizedMatmul(_OperandsOnCodes):
         padded = getattr(self, "a_padded", False) and a.shape[-1] != k
         return qmatmul_i8(a, self._forms[0][:2], b, self._forms[1][:2], transposed_b=self.transposed_b, out_codes=self._out_form,
                           a_padded_k=k if padded else None)
+
+
+class QuantizedAttention(_OperandsOnCodes, _SoftmaxForms):
+    """``Q @ K^T -> holder A0 -> [elementwise prefix -> holder A] -> softmax(dim=-1) -> holder B -> @ V [-> holder C]`` on integer
+    codes in one launch: the QuantizedMatmul, QuantizedSoftmax and QuantizedMatmul of an attention block as one module --
+    ``qattention_i8`` (``mctq_qattention_i8``), which keeps the scores and probabilities of 64 query rows in LDS, where the three
+    modules write and read the block's largest tensor ``[B, H, T, T]`` twice.  The contract is the composition of the three, bit for
+    bit; shapes outside the kernel's limits (``T > 1024``, ``D`` or ``Dv`` above 128 or no multiple of 16) and CPU tensors run the
+    three calls.
+
+    ``operand_quantizers``: those of q, k and v, in the order of ``forward``'s operands; ``scores_quantizer``, ``probs_quantizer`` and
+    ``prefix``: ``in_quantizer``, ``out_quantizer`` and ``prefix`` of the QuantizedSoftmax this module replaces;
+    ``activation_quantizer``: the context holder's, or None for float32.  ``forward(q, k, v)`` takes each operand as the codes of its
+    quantizer or as a float32 tensor, which it quantizes in that operand's form; k arrives as ``[..., T, D]`` (the transpose of the
+    scores is taken without moving data).  Tables are cached per device and built on first use there.  ``activation_code_params``
+    is the OUTPUT form (None for float32), ``operand_code_params(i)`` what ``emit_codes_for`` of the layer in front of operand ``i``
+    takes."""
+
+    def __init__(self, operand_quantizers, scores_quantizer, probs_quantizer, prefix=None, activation_quantizer=None):
+        operand_quantizers = tuple(operand_quantizers)
+        if len(operand_quantizers) != 3:
+            raise ValueError("QuantizedAttention takes the quantizers of three operands (q, k, v)")
+        super().__init__(operand_quantizers, activation_quantizer, float_output=True)
+        self._set_softmax(scores_quantizer, probs_quantizer, prefix)
+
+    def extra_repr(self) -> str:
+        return f"output={'float32' if self._out_form is None else 'codes'}"
+
+    def forward(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+        q, k, v = (self._codes_of(i, x, nhwc=False) for i, x in enumerate((q, k, v)))
+        exp, pre = self.tables(q.device)
+        return qattention_i8(q, self._forms[0][:2], k, self._forms[1][:2], v, self._forms[2][:2], scores_form=self._in_form,
+                             a_form=self._a_form, probs_form=self._probs_form, pre_table=pre, exp_table=exp,
+                             out_codes=self._out_form)
 
 
 # In the order they are tried: (class, the switch of the rewrites that enables it or None, what fusing asks of the layer beyond
@@ -3071,6 +3201,47 @@ def _softmaxes_on_codes(gm, mods, consumer_for) -> int:
     return replaced
 
 
+def _attentions_on_codes(gm, mods) -> int:
+    """``fuse_linear_consumers_fx(attentions=True)``, the last pass.  The candidate is a QuantizedMatmul node with
+    ``transposed_b=True`` that emits codes, whose one user is a QuantizedSoftmax node with ``args == (node,)``, whose one user is a
+    QuantizedMatmul node with ``transposed_b=False`` that reads it directly as operand 0 (and not as operand 1), the forms agreeing
+    along the way.  The three nodes become one QuantizedAttention node ``<context node's name>_attention`` that reads the same
+    three operands in the same forms and emits the same output form.  Returns the number of nodes made."""
+    made = 0
+    for node in list(gm.graph.nodes):
+        scores = _module_of(node, mods)
+        if not isinstance(scores, QuantizedMatmul) or not scores.transposed_b or scores.activation_code_params() is None \
+                or node.kwargs or len(node.args) != 2 or len(node.users) != 1:
+            continue
+        soft_node = next(iter(node.users))
+        soft = _module_of(soft_node, mods)
+        if not isinstance(soft, QuantizedSoftmax) or soft_node.kwargs or soft_node.args != (node,) or len(soft_node.users) != 1:
+            continue
+        ctx_node = next(iter(soft_node.users))
+        ctx = _module_of(ctx_node, mods)
+        if not isinstance(ctx, QuantizedMatmul) or ctx.transposed_b or ctx_node.kwargs or len(ctx_node.args) != 2 \
+                or ctx_node.args[0] is not soft_node or ctx_node.args[1] is soft_node:
+            continue
+        if scores.activation_code_params() != soft.activation_code_params() or ctx.operand_code_params(0) != soft.output_code_params():
+            continue
+        prefix = (list(soft.fns), soft.a_quantizer) if soft.has_prefix else None
+        module = QuantizedAttention((*scores.operand_quantizers, ctx.operand_quantizers[1]), soft.in_quantizer, soft.out_quantizer,
+                                    prefix, ctx.activation_quantizer)
+        name = ctx_node.name + "_attention"
+        gm.add_submodule(name, module)
+        mods[name] = module
+        with gm.graph.inserting_before(ctx_node):
+            new = gm.graph.call_module(name, (*node.args, ctx_node.args[1]))
+        ctx_node.replace_all_uses_with(new)
+        for dead in (ctx_node, soft_node, node):
+            gm.graph.erase_node(dead)
+            if not any(n.op == "call_module" and n.target == dead.target for n in gm.graph.nodes):
+                gm.delete_submodule(dead.target)
+                mods.pop(dead.target, None)
+        made += 1
+    return made
+
+
 def _layernorm_of(node, mods):
     """``(tensor operand, nn.LayerNorm)`` if ``node`` is a LayerNorm over the last dimension that QuantizedLayerNorm can take: a
     call of an ``nn.LayerNorm`` module, or ``F.layer_norm`` with a constant one-dimensional ``normalized_shape`` and ``eps`` and
@@ -3674,7 +3845,8 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
                              concats: bool = False, avg_pools: bool = False, muls: bool = False,
                              hard_activations: bool = False, upsamples: bool = False, any_channels: bool = False,
                              activation_tables: bool = False, grouped: bool = False, transposed: bool = False,
-                             matmuls: bool = False, softmaxes: bool = False, layernorms: bool = False):
+                             matmuls: bool = False, softmaxes: bool = False, layernorms: bool = False,
+                             attentions: bool = False):
     """The same rewrite on an arbitrary module graph (MCT-exported models are not ``nn.Sequential``): traces ``model``
     with torch.fx keeping wrappers and holders as leaves, and wherever an activation holder's ONLY consumer is a
     wrapped ``nn.Linear`` the integer consumer can take (symmetric, power-of-two or LUT weights, and with
@@ -3957,8 +4129,25 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
     only next to a rounding tie.  Left alone: a norm without a holder A in front (the first layer's norm on raw embeddings;
     ``workloads.wrapped_attention_block`` as it stands); no holder B; a float32 user of the norm or of B; ``eps <= 0``; half
     precision parameters; more than one normalized dimension; ``RMSNorm``, ``GroupNorm``, ``BatchNorm``; training mode;
-    quantizers wider than 8 bits or per-channel."""
+    quantizers wider than 8 bits or per-channel.
+
+    ``attentions=True`` (needs ``matmuls=True`` and ``softmaxes=True``, ValueError otherwise; fx only) runs the core of an attention
+    block as one launch.  It is the last pass, so every pass above sees the modules it knows.  The candidate is a QuantizedMatmul
+    with ``transposed_b=True`` that emits codes, whose one user is a QuantizedSoftmax that reads it alone, whose one user is a
+    QuantizedMatmul with ``transposed_b=False`` that reads it directly as its first operand.  The three nodes become one
+    QuantizedAttention node ``<context node's name>_attention`` (``mctq_qattention_i8``: the scores and probabilities of 64 query
+    rows stay in LDS, ``[B, H, T, T]`` is never written) which reads the same three operands in the same forms and emits the same
+    output form, so the producers in front and the readers behind stay as they are.  The contract is the composition of the three
+    modules' contracts, which no summation order enters: the model's output is the same bit for bit with and without the switch,
+    on the CPU and on the GPU; shapes outside the kernel's limits (``T > 1024``, ``D`` or ``Dv`` above 128 or no multiple of 16) run
+    the three calls inside the module.  The returned total does not count these nodes (no wrapped layer is replaced).  Left alone:
+    a second reader of the scores or of the probabilities; a layout node between the softmax and the second product; a first
+    product in the NN form; the probabilities as the second operand; additive masks and causal attention (the softmax pass leaves
+    them alone); ``F.scaled_dot_product_attention`` and ``nn.MultiheadAttention``; the q / k / v Linears and the output projection
+    stay layers of their own."""
     import torch.fx as fx
+    if attentions and not (matmuls and softmaxes):
+        raise ValueError("attentions=True needs matmuls=True and softmaxes=True")
     if stay_on_codes and not shared_holders:
         raise ValueError("stay_on_codes=True needs shared_holders=True")
     if fused_residuals and not stay_on_codes:
@@ -4017,6 +4206,8 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
         _fold_clamps_into_producers(gm, mods, hard_activations)
     if fused_residuals:
         _fuse_residuals_into_producers(gm, mods)
+    if attentions:                                           # (last: every pass above has seen the three modules it knows)
+        _attentions_on_codes(gm, mods)
     gm.graph.lint()
     gm.recompile()
     return gm, replaced

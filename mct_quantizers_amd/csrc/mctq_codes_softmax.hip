@@ -29,7 +29,7 @@
 // codes byte by byte.  An output chunk that lies wholly inside the row's out_pitch bytes is one 16-byte store; the first and the
 // last chunk, where a neighbouring row shares them, are stored byte by byte.  No byte outside [out + r * out_pitch, + out_pitch)
 // is written by row r's lanes.
-#include "mctq_consumer.hpp"               // u32x4, QlOut, ql_code, form_check_dtype, ranges_overlap
+#include "mctq_codes_softmax.hpp"          // the three passes over one chunk; u32x4, QlOut, form_check_dtype, ranges_overlap
 
 namespace mctq {
 
@@ -83,14 +83,7 @@ __device__ __forceinline__ void softmax_store(const SoftmaxArgs& a, uint32_t t, 
   uint8_t* dst = a.out + (t - ob) + 16u * m;
   if (e0 >= 0 && e0 + 16 <= width) {
     const int nv = min(max(L - e0, 0), 16);                                       // leading bytes that are codes
-    u32x4 w;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int nb = min(max(nv - 4 * q, 0), 4);
-      const uint32_t keep = nb >= 4 ? 0xffffffffu : (1u << (8 * nb)) - 1u;
-      w[q] = (codes[q] & keep) | (a.pad & ~keep);
-    }
-    *reinterpret_cast<u32x4*>(dst) = w;
+    *reinterpret_cast<u32x4*>(dst) = softmax_chunk_pad(codes, nv, a.pad);
     return;
   }
 #pragma unroll
@@ -141,21 +134,7 @@ __global__ __launch_bounds__(kThreads) void codes_softmax_kernel(SoftmaxArgs a) 
   for (int u = 0; u < CH; ++u) {
     const int k = (int)(lane + (uint32_t)u * LANES) - (int)sh;
     const int lo = (int)ia - 16 * k, hi = (int)(ia + a.L) - 16 * k;               // byte j of the chunk is element j - lo: lo <= j < hi
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const uint32_t w = v[u][q];
-      uint32_t packed = 0;
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        const int j = 4 * q + b;
-        uint32_t c = (w >> (8 * b)) & 0xffu;
-        if (PRE) c = pre8[c];
-        c = (j >= lo && j < hi) ? (c ^ a.flip) : 0u;
-        mx = max(mx, c);
-        packed |= c << (8 * b);
-      }
-      v[u][q] = packed;
-    }
+    softmax_chunk_order<PRE>(v[u], pre8, a.flip, lo, hi, mx);
   }
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, off));
@@ -171,11 +150,7 @@ __global__ __launch_bounds__(kThreads) void codes_softmax_kernel(SoftmaxArgs a) 
   for (int u = 0; u < CH; ++u) {
     const int k = (int)(lane + (uint32_t)u * LANES) - (int)sh;
     const int lo = (int)ia - 16 * k, hi = (int)(ia + a.L) - 16 * k;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const uint32_t c = (v[u][j >> 2] >> (8 * (j & 3))) & 0xffu;
-      part += (j >= lo && j < hi) ? etab[mx - c] : 0u;
-    }
+    part += softmax_chunk_sum(v[u], etab, mx, lo, hi);
   }
   unsigned long long sum = part;
 #pragma unroll
@@ -190,18 +165,7 @@ __global__ __launch_bounds__(kThreads) void codes_softmax_kernel(SoftmaxArgs a) 
   // pass 3: one division per element, 16 codes per chunk (bytes outside the row: some code, never stored)
   u32x4 r[CH];
 #pragma unroll
-  for (int u = 0; u < CH; ++u)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      uint32_t word = 0;
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        const uint32_t c = (v[u][q] >> (8 * b)) & 0xffu;
-        const float p = (float)etab[mx - c] / fs;
-        word |= ((uint32_t)ql_code(p, a.o) & 0xffu) << (8 * b);
-      }
-      r[u][q] = word;
-    }
+  for (int u = 0; u < CH; ++u) r[u] = softmax_chunk_codes(v[u], etab, mx, fs, a.o);
   if (!active) return;
 
   if (ia == ob) {                                                                 // the code chunks are the output chunks

@@ -198,6 +198,15 @@ SIGNATURES = {
                                        ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_int32,
                                        ctypes.c_int32]                                                              # y and its output form
                         + [ctypes.c_int64] * 5 + [ctypes.c_void_p]),                                                # B0, B1, M, N, K; stream
+    "mctq_qattention_i8": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,          # q_codes, type, zero point, scale
+                                          ctypes.c_int64, ctypes.c_int64, ctypes.c_int64] * 3                        # its strides: B0, B1, rows; k and v likewise
+                           + [ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,       # the scores' form (holder A0)
+                              ctypes.c_int32,                                                                       # A's code type
+                              ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,       # the probabilities' form (holder B)
+                              ctypes.c_void_p, ctypes.c_void_p,                                                     # exp_table, pre_table
+                              ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_int32,
+                              ctypes.c_int32]                                                                       # y and its output form
+                           + [ctypes.c_int64] * 6 + [ctypes.c_void_p]),                                             # B0, B1, M, T, D, Dv; stream
     "mctq_fq_join_f32": (ctypes.c_int, [_c_f32p, _c_f32p, ctypes.c_int32, _c_f32p, ctypes.c_void_p, ctypes.c_int32,   # x, residual, relu, y, codes, code_dtype
                                         ctypes.c_int64, ctypes.c_float, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                         ctypes.c_void_p]),                                                            # n, scale, zero_point, qmin, qmax, stream
