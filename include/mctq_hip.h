@@ -105,6 +105,10 @@ extern "C" {
 /* v10 (additive, the version number stays): + mctq_qattention_i8, Q.K^T, the softmax on codes and P.V of an attention block in one
  * launch, byte for byte the result of mctq_qmatmul_i8 -> mctq_codes_softmax -> mctq_qmatmul_i8; no existing signature or result
  * changed. */
+/* v10 (additive, the version number stays): + mctq_codes_upsample_bilinear_nhwc, bilinear upsampling (torch.nn.Upsample /
+ * F.interpolate, mode "bilinear", either align_corners) on NHWC activation codes with 11-bit fixed-point weights, in the form of the
+ * holder behind it (segmentation heads and dense-prediction decoders stay on codes), + tuning key "bilinear_strip"; no existing
+ * signature or result changed. */
 #define MCTQ_ABI_VERSION 10
 #define MCTQ_E_ARG (-10001)
 
@@ -754,6 +758,40 @@ int mctq_codes_upsample_nhwc(const void* codes, void* out, int32_t code_dtype, i
                              int32_t quant_min, int32_t quant_max, void* stream);
 
 /*
+ * Bilinear resampling on activation codes (extension; the reference runs ATen's bilinear upsample on the float32 output of a
+ * holder and the holder behind it on the result): codes [batch][height][width][channels] (NHWC; int8 -- MCTQ_CODE_I8 -- or
+ * uint8, MCTQ_CODE_U8) of the form (in_scale, in_zero_point) -> out [batch][out_height][out_width][channels] in the form
+ * (out_code_dtype, scale, zero_point, quant_min, quant_max), DEVICE pointers, 16-byte aligned.  The blend is separable with
+ * fixed-point weights of WB = 11 bits; each axis has three DEVICE int32 tables (4-byte aligned) of out_height / out_width
+ * entries: row0 / col0 and row1 / col1, source indices, and row_w1 / col_w1, the weight of the second in [0, 2^WB] (the
+ * first has 2^WB less that).  Per output element, on integers,
+ *     h(r)  = (2^WB - col_w1[wo]) * (code[b][r][col0[wo]][c] - in_zero_point) + col_w1[wo] * (code[b][r][col1[wo]][c] - in_zero_point)
+ *     acc   = (2^WB - row_w1[ho]) * h(row0[ho]) + row_w1[ho] * h(row1[ho])            |acc| <= 2^22 * 255: an exact int32
+ *     y     = float(acc) * (in_scale * 2^-22)                                         one conversion, one multiply
+ *     out   = clamp(rint(y * (1.0f / scale)) + zero_point, quant_min, quant_max)
+ * -- no summation order enters, so every instance of the kernel and the torch route of ops.codes_upsample_bilinear give the
+ * same bytes.  Against a float64 bilinear interpolation of the dequantized codes, coded in float64, a code differs by at most
+ * one and only next to a rounding tie (each weight is off by at most 2^-(WB+1)); where the weights are dyadic (scale factors 2
+ * and 4, align_corners false) and the scales powers of two it is the float32 chain bit for bit.  A lane owns 16 channels of
+ * one output column for a strip of R consecutive output rows and keeps the two horizontally blended input rows it is between;
+ * tuning key "bilinear_strip" chooses R.  The launcher cannot see the device tables: the kernel clamps every index into
+ * [0, height - 1] / [0, width - 1] and every weight into [0, 2^WB] before use.  A lane reads only chunks below batch * height *
+ * width * channels / 16, entries below out_height / out_width of the tables, and writes only chunks below batch * out_height *
+ * out_width * channels / 16.
+ * MCTQ_E_ARG with a mctq_last_error text, before anything is launched, for: a negative extent; channels % 16 != 0; a bad
+ * code_dtype or out_code_dtype; a zero point that is no code of its type; a scale that is not finite and positive; a clamp
+ * domain outside the output type; an image extent above 2^31 - 1; a non-empty output from an image without pixels; more than
+ * 2^31 - 1 16-byte chunks of output (split the batch); NULL or misaligned pointers of a non-empty problem; an `out` whose bytes
+ * overlap the codes' or a table's.  batch == 0, channels == 0 or an empty output returns 0 without a launch.
+ * mctq_last_launch names the launch "codes_bilinear", op "<in> -> <out> strip <R>" with the code types "u8" / "i8".
+ */
+int mctq_codes_upsample_bilinear_nhwc(const void* codes, void* out, int32_t code_dtype, int32_t in_zero_point, float in_scale,
+                                      int64_t batch, int64_t height, int64_t width, int64_t channels, int64_t out_height,
+                                      int64_t out_width, const int32_t* row0, const int32_t* row1, const int32_t* row_w1,
+                                      const int32_t* col0, const int32_t* col1, const int32_t* col_w1, int32_t out_code_dtype,
+                                      float scale, int32_t zero_point, int32_t quant_min, int32_t quant_max, void* stream);
+
+/*
  * An elementwise function between two activation holders on codes (extension; the reference runs the function on the float32
  * output of holder A and holder B on the result): out[i] = table[raw byte in[i]] for i < n.  Holder A's float32 output takes at
  * most 256 values, one per code, and both the function and holder B work element by element, so B's code is a function of A's
@@ -1266,6 +1304,9 @@ int mctq_qconv_dw_i8_act(const void* a_codes, int32_t a_code_dtype, int32_t a_ze
  *                  2 <= factor_h * factor_w <= 16, where it measured 1.8 - 2.3 x faster at batch 64 and equal at batch 1; gather
  *                  elsewhere), 1 = the gather form, 2 = the replicate form where eligible (integer factors with
  *                  factor_h * factor_w <= 16; gather elsewhere).  The bytes are the same: every output is one input's code
+ *   key "bilinear_strip" : mctq_codes_upsample_bilinear_nhwc: consecutive output rows a lane walks, 0 (default) = the launcher
+ *                  chooses by grid arithmetic (the longest of 8 and 4 that leaves four workgroups per CU and two strips per image,
+ *                  else 1), 1 = one row (the per-pixel form), 4, 8.  The bytes are the same: the contract is on integers
  *   key "im2col_grain" : mctq_codes_im2col_pad_nhwc: bytes per load piece, 0 (default) = by rule (4 where channels % 4 == 0, 1
  *                  elsewhere), 1 = byte loads, 4 = dword loads (MCTQ_E_ARG from the entry point where channels % 4 != 0).  The
  *                  bytes are the same

@@ -109,6 +109,12 @@ moves data, so B's codes are A's codes gathered through the upsample's index map
 A -> upsample -> B -> cat([B, S]) -> C -> conv runs holder to holder on codes.
 Measured / not measured: see the README paragraph and ``profiles/EXPERIMENTS.md``.
 
+A bilinear upsample between two holders stays on codes with ``bilinear_upsamples=True`` (both rewrites): holder A -> ``nn.Upsample``
+/ ``F.interpolate`` ("bilinear", either ``align_corners``) -> holder B, a segmentation head or a dense-prediction decoder.  A blend
+creates new values, so ``QuantizedBilinearUpsample`` (``mctq_codes_upsample_bilinear_nhwc``) states a contract on integers -- four taps,
+11-bit fixed-point weights per axis, an exact int32 sum, one conversion and one multiply -- that every route reproduces byte for
+byte and that stays within one code of the float64 interpolation, next to rounding ties only.
+
 Layers whose K is no multiple of 16 -- a CNN's stem, bottleneck widths of 24 / 40 / 72, SE squeeze widths -- run on codes with
 ``any_channels=True`` (both rewrites; ``QuantizedLinear``, ``QuantizedConv1x1``, ``QuantizedConv2d``): the weight rows are kept padded with
 the code 0 to ``Kp = 16 * ceil(K / 16)`` columns and the activation rows are written at that pitch with the zero-point code in their
@@ -1479,7 +1485,7 @@ def _ints_or_pair(v) -> bool:
 
 
 class _OnCodes(nn.Module):
-    """Base of the modules without weights that read or write activation codes -- the pools, QuantizedUpsample, QuantizedActivationTable,
+    """Base of the modules without weights that read or write activation codes -- the pools, QuantizedUpsample, QuantizedBilinearUpsample, QuantizedActivationTable,
     QuantizedConcat, QuantizedMul, QuantizedMatmul and QuantizedJoin: with the wrappers, the holders and the integer consumers, the leaves of the graph rewrite's tracer."""
 
 
@@ -1650,6 +1656,20 @@ _NEAREST_MODES = ("nearest", "nearest-exact")
 _ONE_RAMP_MAX = 1 << 24        # pixels of an image whose indices h * W + w are all float32 integers (QuantizedUpsample.index_maps)
 
 
+def _constant_resample_geometry(upsample) -> bool:
+    """The ``size`` / ``scale_factor`` rule QuantizedUpsample and QuantizedBilinearUpsample share: exactly one of the two, a positive
+    finite number or a pair of them (ints for a ``size``: 4-D inputs only), and a ``recompute_scale_factor`` of None or a bool."""
+    if getattr(upsample, "recompute_scale_factor", None) not in (None, True, False):
+        return False
+    size, factor = upsample.size, upsample.scale_factor
+    if (size is None) == (factor is None):
+        return False
+    number = lambda e, kinds: isinstance(e, kinds) and not isinstance(e, bool) and e > 0 and math.isfinite(e)     # noqa: E731
+    kinds = (int,) if factor is None else (int, float)
+    v = size if factor is None else factor
+    return number(v, kinds) or (isinstance(v, (tuple, list)) and len(v) == 2 and all(number(e, kinds) for e in v))
+
+
 class QuantizedUpsample(_OnCodes):
     """``activation holder A -> nearest upsample -> activation holder B`` on integer codes, for the integer consumers, pools and
     concatenations behind B: a U-Net stage, a YOLO / PANet neck, a segmentation head.  A's float32 output is
@@ -1694,15 +1714,7 @@ class QuantizedUpsample(_OnCodes):
             return False
         if upsample.mode not in _NEAREST_MODES or upsample.align_corners is not None:
             return False
-        if getattr(upsample, "recompute_scale_factor", None) not in (None, True, False):
-            return False
-        size, factor = upsample.size, upsample.scale_factor
-        if (size is None) == (factor is None):
-            return False
-        number = lambda e, kinds: isinstance(e, kinds) and not isinstance(e, bool) and e > 0 and math.isfinite(e)     # noqa: E731
-        kinds = (int,) if factor is None else (int, float)
-        v = size if factor is None else factor
-        return number(v, kinds) or (isinstance(v, (tuple, list)) and len(v) == 2 and all(number(e, kinds) for e in v))
+        return _constant_resample_geometry(upsample)
 
     def activation_code_params(self):
         """(scale, zero_point, qmin, qmax) of the codes this module READS (holder A's): what ``emit_codes_for`` of the layer in
@@ -1748,6 +1760,92 @@ class QuantizedUpsample(_OnCodes):
         codes = _operand_codes(x, self.activation_code_params(), "QuantizedUpsample", "this upsample's input quantizer")
         rows, cols, factors = self.index_maps(codes.shape[1], codes.shape[2], codes.device)
         y = ops.codes_upsample(codes, (self._a_scale, self._a_zp), self._out_form, rows, cols, factors)
+        return y.permute(0, 3, 1, 2)
+
+
+class QuantizedBilinearUpsample(_OnCodes):
+    """``activation holder A -> bilinear upsample -> activation holder B`` on integer codes, for the integer consumers, pools and
+    concatenations behind B: DeepLab / FCN / LR-ASPP heads, SegFormer and DPT decoders, BiFPN, U-Nets with
+    ``nn.Upsample(mode="bilinear")``.  A blend creates new values, so unlike ``QuantizedUpsample`` this module has a contract of
+    its own, on integers (``ops.codes_upsample_bilinear``, ``mctq_codes_upsample_bilinear_nhwc``): the four taps of an output
+    element are blended with fixed-point weights of 11 bits per axis into an exact int32, which is converted, scaled and coded by
+    B with one rounding each -- 1 byte read per input element and 1 written per output element in one launch, where A writes
+    float32, ATen's interpolation reads it and writes the upsampled tensor, and B reads and writes that again.  No order of
+    evaluation enters the contract: CPU and GPU, and every kernel form, give the same bytes.  Against the float64 interpolation
+    of A's output coded by B in float64 a code differs by at most one, and only next to a rounding tie; for the scale factors
+    2 and 4 without ``align_corners`` (dyadic weights) and power-of-two scales the codes are those of the float32 chain bit for
+    bit.
+
+    ``upsample``: an ``nn.Upsample`` of mode "bilinear" (``size`` or ``scale_factor``, ints, floats or pairs, any
+    ``recompute_scale_factor``, ``align_corners`` None, False or True; downsampling included) or an ``nn.UpsamplingBilinear2d`` --
+    ``eligible`` says which; ``F.interpolate(x, ...)`` with constant arguments and without ``antialias`` is ``nn.Upsample(...)`` of the
+    same arguments.  ``in_quantizer`` (A's) and ``out_quantizer`` (B's, required: there is no form to inherit): per-tensor affine
+    activation quantizers of at most 8 bits whose zero points are codes of their type.  ``forward``, ``activation_code_params``
+    and ``output_code_params`` are ``QuantizedUpsample``'s: codes or float32 in, NCHW-shaped and NHWC-stored codes out.
+
+    The tables are not derived from PyTorch's scale rules: for every ``(H, W)`` first seen the module resamples a float64 row ramp
+    and a float64 column ramp through the very call it replaces, on the CPU -- the result is the source coordinate ``s`` of every
+    output row and column -- and keeps ``i0 = floor(s)``, ``i1 = min(i0 + 1, n - 1)`` and ``w1 = rint((s - i0) * 2^11)``
+    (``ops.bilinear_tables``) as int32 tensors on the input's device.  That is two tiny CPU calls and one upload per new shape: a
+    hipGraph capture needs one warm-up forward per input shape first (``capture_forward``'s warm-up is one).  GPU tensors whose C
+    is no multiple of 16 and CPU tensors take torch integer ops with the same bytes."""
+
+    def __init__(self, upsample, in_quantizer, out_quantizer):
+        super().__init__()
+        if not self.eligible(upsample):
+            raise TypeError("QuantizedBilinearUpsample takes torch.nn.Upsample layers of mode 'bilinear' with either a size or a "
+                            "scale_factor, a number or a pair of numbers, and torch.nn.UpsamplingBilinear2d layers")
+        if out_quantizer is None:
+            raise TypeError("QuantizedBilinearUpsample needs the quantizer of the holder behind it: a blend has no form to inherit")
+        self.upsample = upsample
+        self.in_quantizer, self.out_quantizer = in_quantizer, out_quantizer
+        self._a_scale, self._a_zp, self._a_qmin, self._a_qmax = _code_form(in_quantizer)
+        self._out_form = _code_form(out_quantizer)
+        self._tables = {}                                      # (H, W, device) -> ((r0, r1, wr), (c0, c1, wc))
+
+    @staticmethod
+    def eligible(upsample) -> bool:
+        if type(upsample) not in (nn.Upsample, nn.UpsamplingBilinear2d):
+            return False
+        if upsample.mode != "bilinear" or upsample.align_corners not in (None, False, True):
+            return False
+        return _constant_resample_geometry(upsample)
+
+    activation_code_params = QuantizedUpsample.activation_code_params
+    output_code_params = QuantizedUpsample.output_code_params
+
+    def extra_repr(self) -> str:
+        return (f"size={self.upsample.size}, scale_factor={self.upsample.scale_factor}, mode={self.upsample.mode}, "
+                f"align_corners={self.upsample.align_corners}")
+
+    def tables(self, height: int, width: int, device):
+        """``((r0, r1, wr), (c0, c1, wc))`` of an ``height`` x ``width`` input: int32 tensors of lengths Ho / Wo on ``device``, what
+        ``ops.codes_upsample_bilinear`` takes.  Resampled through the module itself, in float64 on the CPU, and cached."""
+        device = torch.device(device)
+        key = (int(height), int(width), str(device))
+        hit = self._tables.get(key)
+        if hit is not None:
+            return hit
+        h, w = key[0], key[1]
+        with torch.no_grad():
+            ys = self.upsample(torch.arange(h, dtype=torch.float64).reshape(1, 1, h, 1).expand(1, 1, h, w))[0, 0]
+            xs = self.upsample(torch.arange(w, dtype=torch.float64).reshape(1, 1, 1, w).expand(1, 1, h, w))[0, 0]
+            # (a blend of equal float64 values along the other axis may move them by an ulp: 2^-52, against weights of 2^-11)
+            if not torch.allclose(ys, ys[:, :1].expand_as(ys), rtol=0.0, atol=1e-9) \
+                    or not torch.allclose(xs, xs[:1, :].expand_as(xs), rtol=0.0, atol=1e-9):
+                raise RuntimeError("the upsample's interpolation is not separable into rows and columns")
+            rows, cols = ops.bilinear_tables(ys[:, 0], h), ops.bilinear_tables(xs[0, :], w)
+        if len(self._tables) > 64:
+            self._tables.clear()
+        hit = self._tables[key] = (tuple(t.to(device) for t in rows), tuple(t.to(device) for t in cols))
+        return hit
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if x.dim() != 4:
+            raise RuntimeError(f"expected [N, C, H, W], got {tuple(x.shape)}")
+        codes = _operand_codes(x, self.activation_code_params(), "QuantizedBilinearUpsample", "this upsample's input quantizer")
+        rows, cols = self.tables(codes.shape[1], codes.shape[2], codes.device)
+        y = ops.codes_upsample_bilinear(codes, (self._a_scale, self._a_zp), self._out_form, rows, cols)
         return y.permute(0, 3, 1, 2)
 
 
@@ -2227,8 +2325,8 @@ def _consumer_for(wrapper, activation_quantizer, uniform_weights=False, convolut
 
 
 # what reads the activation codes of the module in front as they are
-_CODE_READERS = (IntegerConsumer, QuantizedMaxPool2d, QuantizedAvgPool2d, QuantizedUpsample, QuantizedActivationTable,
-                 QuantizedLayerNorm)
+_CODE_READERS = (IntegerConsumer, QuantizedMaxPool2d, QuantizedAvgPool2d, QuantizedUpsample, QuantizedBilinearUpsample,
+                 QuantizedActivationTable, QuantizedLayerNorm)
 
 
 class _FusedAway(nn.Identity):
@@ -2483,10 +2581,11 @@ def _avg_pool_plan(node, mods, quantizer, consumer_for):
         return None
 
 
-def _upsample_of(node, mods):
-    """The ``nn.Upsample`` that ``node`` applies to its one tensor operand -- a call of an ``nn.Upsample`` / ``nn.UpsamplingNearest2d``
-    module, or ``F.interpolate`` with constant arguments (``antialias`` false), for which one is built -- if QuantizedUpsample can
-    take it, else None."""
+def _upsample_of(node, mods, cls=None):
+    """The ``nn.Upsample`` that ``node`` applies to its one tensor operand -- a call of an ``nn.Upsample`` / ``nn.UpsamplingNearest2d`` /
+    ``nn.UpsamplingBilinear2d`` module, or ``F.interpolate`` with constant arguments (``antialias`` false), for which one is built --
+    if ``cls`` (QuantizedUpsample by default, or QuantizedBilinearUpsample) can take it, else None."""
+    cls = cls or QuantizedUpsample
     from torch.fx import Node
     if not node.args or not isinstance(node.args[0], Node):
         return None
@@ -2501,7 +2600,7 @@ def _upsample_of(node, mods):
             up = nn.Upsample(**given)
         except (TypeError, ValueError):
             return None
-    return up if QuantizedUpsample.eligible(up) else None
+    return up if cls.eligible(up) else None
 
 
 def _between_holders_plan(first, chain, mods, quantizer, consumer_for, pools, build, suffix, copies: bool, rows: bool):
@@ -2567,16 +2666,20 @@ def _between_holders_plan(first, chain, mods, quantizer, consumer_for, pools, bu
     return _PoolPlan(module, suffix, taken, gone, name, tuple(pooled), tuple(readers))
 
 
-def _upsample_plan(node, mods, quantizer, consumer_for, pools: bool = False):
+def _upsample_plan(node, mods, quantizer, consumer_for, pools: bool = False, kinds=(QuantizedUpsample,)):
     """``node`` a user of a plain holder A with ``quantizer``: the plan of a QuantizedUpsample if it is a nearest upsample of A's
     output (``_upsample_of``) all of whose readers agree on one code form F and read codes (``_between_holders_plan``: through a
     plain holder B or directly, then in A's form or a QuantizedConcat / QuantizedMul operand's; never a QuantizedLinear).  Else
-    None: a float32 reader, an activation between the upsample and B, forms that differ."""
-    up = _upsample_of(node, mods)
-    if up is None:
-        return None
-    return _between_holders_plan(node, [], mods, quantizer, consumer_for, pools, lambda out: QuantizedUpsample(up, quantizer, out),
-                                 "_upsample", copies=True, rows=False)
+    None: a float32 reader, an activation between the upsample and B, forms that differ.  ``kinds``: the classes to plan for, what
+    the switches ``upsamples`` and ``bilinear_upsamples`` turn on; a QuantizedBilinearUpsample (node suffix ``_bilinear``) copies
+    nothing, so it needs a B or such an operand to name F."""
+    for cls in kinds:
+        up = _upsample_of(node, mods, cls)
+        if up is not None:
+            nearest = cls is QuantizedUpsample
+            return _between_holders_plan(node, [], mods, quantizer, consumer_for, pools, lambda out: cls(up, quantizer, out),
+                                         "_upsample" if nearest else "_bilinear", copies=nearest, rows=False)
+    return None
 
 
 def _activation_functions():
@@ -2762,7 +2865,7 @@ def _mul_operands(node):
     return _binary_operands(node, (operator.mul, operator.imul, torch.mul, torch.multiply), ("mul", "multiply"), operator.imul)
 
 
-def _join_shared_holders(gm, mods, consumer_for, pools: bool = False, avg_pools: bool = False, upsamples: bool = False,
+def _join_shared_holders(gm, mods, consumer_for, pools: bool = False, avg_pools: bool = False, upsamples=(),
                          activation_tables: bool = False) -> int:
     """``fuse_linear_consumers_fx(shared_holders=True)``: every plain holder with wrapped layers among its users that
     ``consumer_for(wrapper, quantizer)`` can take becomes a QuantizedJoin, unless it is a lone holder -> layer pair with
@@ -2840,21 +2943,22 @@ def _join_shared_holders(gm, mods, consumer_for, pools: bool = False, avg_pools:
     return replaced
 
 
-def _any_pool_plan(node, mods, quantizer, consumer_for, pools: bool, avg_pools: bool, upsamples: bool = False,
+def _any_pool_plan(node, mods, quantizer, consumer_for, pools: bool, avg_pools: bool, upsamples=(),
                    activation_tables: bool = False):
     """``_pool_plan`` (with ``pools``), or else ``_avg_pool_plan`` (with ``avg_pools``), or else ``_upsample_plan`` (with
-    ``upsamples``), or else ``_table_plan`` (with ``activation_tables``) of ``node``, or None."""
+    ``upsamples``), or else ``_table_plan`` (with ``activation_tables``) of ``node``, or None.  ``upsamples``, here and in the
+    passes that call this: the tuple of upsample classes to plan for (``_upsample_plan``'s ``kinds``), empty for none."""
     plan = _pool_plan(node, mods, quantizer, consumer_for) if pools else None
     if plan is None and avg_pools:
         plan = _avg_pool_plan(node, mods, quantizer, consumer_for)
     if plan is None and upsamples:
-        plan = _upsample_plan(node, mods, quantizer, consumer_for, pools)
+        plan = _upsample_plan(node, mods, quantizer, consumer_for, pools, upsamples)
     if plan is None and activation_tables:
         plan = _table_plan(node, mods, quantizer, consumer_for, pools)
     return plan
 
 
-def _behind_planned_operation(node, mods, consumer_for, pools: bool, upsamples: bool, activation_tables: bool) -> bool:
+def _behind_planned_operation(node, mods, consumer_for, pools: bool, upsamples, activation_tables: bool) -> bool:
     """``node``, a plain holder's call, is the second holder of an upsample or of a run of activations that will run on codes
     (``_upsample_plan`` / ``_table_plan`` of the user of another plain holder that leads to it): it belongs to that plan, whatever
     the number of its users."""
@@ -2866,7 +2970,7 @@ def _behind_planned_operation(node, mods, consumer_for, pools: bool, upsamples: 
         holder = _holder_of(first.args[0], mods)
         if holder is not None:                               # ``first`` is the user of a holder A that leads here
             quantizer = holder.activation_holder_quantizer
-            plan = _upsample_plan(first, mods, quantizer, consumer_for, pools) if upsamples else None
+            plan = _upsample_plan(first, mods, quantizer, consumer_for, pools, upsamples) if upsamples else None
             if plan is None and activation_tables:
                 plan = _table_plan(first, mods, quantizer, consumer_for, pools)
             return plan is not None and node in plan.gone
@@ -2874,7 +2978,7 @@ def _behind_planned_operation(node, mods, consumer_for, pools: bool, upsamples: 
     return False
 
 
-def _pool_lone_holders(gm, mods, consumer_for, pools: bool = True, avg_pools: bool = False, upsamples: bool = False,
+def _pool_lone_holders(gm, mods, consumer_for, pools: bool = True, avg_pools: bool = False, upsamples=(),
                        activation_tables: bool = False) -> int:
     """``fuse_linear_consumers_fx(pools=True)``, the pair: a plain holder whose only user is a max pool that can run on codes
     (``_pool_plan``) leaves the graph, the QuantizedMaxPool2d that replaces the pool quantizes the holder's input itself.
@@ -3668,7 +3772,8 @@ def _fuse_residuals_into_producers(gm, mods) -> int:
 def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights: bool = False,
                           convolutions: bool = False, depthwise: bool = False, pools: bool = False,
                           avg_pools: bool = False, upsamples: bool = False, any_channels: bool = False,
-                          activation_tables: bool = False, grouped: bool = False, transposed: bool = False) -> int:
+                          activation_tables: bool = False, grouped: bool = False, transposed: bool = False,
+                          bilinear_upsamples: bool = False) -> int:
     """In every ``nn.Sequential`` of ``model``: an activation holder directly followed by a wrapped ``nn.Linear`` with
     a symmetric, power-of-two or LUT weights quantizer (int8 codebook values, at most 256 entries) becomes (Identity,
     QuantizedLinear); a wrapped pointwise ``nn.Conv2d`` likewise becomes a QuantizedConv1x1.  Returns the number of pairs
@@ -3733,6 +3838,13 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
     without a B).  With ``chain=True`` a consumer in front emits A's codes.  Counted as one pair.  Nearest interpolation only moves
     data, so the codes are bit for bit those of the float32 chain (``QuantizedUpsample``).
 
+    ``bilinear_upsamples=True`` (composes with every other switch) also takes (holder A, ``nn.Upsample`` of mode "bilinear" /
+    ``nn.UpsamplingBilinear2d``, holder B, wrapped convolution the consumer can take): they become (Identity,
+    QuantizedBilinearUpsample, Identity, consumer), the upsample and B running as one launch on A's codes
+    (``mctq_codes_upsample_bilinear_nhwc``) and the consumer taking B's codes.  B is required: a blend has no form to inherit.
+    Counted as one pair.  The codes are those of QuantizedBilinearUpsample's integer contract: within one code of the float32
+    chain next to a rounding tie, equal to it for the factors 2 and 4 without ``align_corners`` and power-of-two scales.
+
     ``any_channels=True`` (composes with every other switch) also takes the pairs whose K is no multiple of 16: a wrapped
     ``nn.Linear`` or pointwise convolution of any ``in_features`` / ``in_channels`` <= 32768 -- bottleneck widths of 24, 40, 72, SE
     squeeze widths -- and, with ``convolutions=True``, a k x k convolution of any ``in_channels`` (a CNN's stem).  Such a consumer
@@ -3775,18 +3887,20 @@ def fuse_linear_consumers(model: nn.Module, chain: bool = False, uniform_weights
                 seq[i + 3] = _FusedAway()
             seq[i + 4 if flat else i + 3] = fused
             replaced += 1
-        for i in range(len(seq) - 2 if upsamples else 0):
+        up_kinds = ((QuantizedUpsample,) if upsamples else ()) + ((QuantizedBilinearUpsample,) if bilinear_upsamples else ())
+        for i in range(len(seq) - 2 if up_kinds else 0):
             holder, up = seq[i], seq[i + 1]
             second = seq[i + 2] if _plain_holder(seq[i + 2]) and i + 3 < len(seq) else None
             wrapper = seq[i + 2] if second is None else seq[i + 3]
-            if not _plain_holder(holder) or not QuantizedUpsample.eligible(up) or not isinstance(wrapper, PytorchQuantizationWrapper):
+            cls = next((k for k in up_kinds if k.eligible(up)), None)
+            if not _plain_holder(holder) or cls is None or not isinstance(wrapper, PytorchQuantizationWrapper):
                 continue
             reads_as = (holder if second is None else second).activation_holder_quantizer
             fused = _consumer_for(wrapper, reads_as, uniform_weights, convolutions, depthwise, any_channels, grouped, transposed)
             if fused is None or type(fused) is QuantizedLinear:
                 continue
-            try:
-                qup = QuantizedUpsample(up, holder.activation_holder_quantizer, None if second is None else reads_as)
+            try:                                               # (a bilinear upsample without a second holder: TypeError)
+                qup = cls(up, holder.activation_holder_quantizer, None if second is None else reads_as)
             except (TypeError, ValueError, NotImplementedError):
                 continue
             seq[i], seq[i + 1] = _FusedAway(), qup
@@ -3846,7 +3960,7 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
                              hard_activations: bool = False, upsamples: bool = False, any_channels: bool = False,
                              activation_tables: bool = False, grouped: bool = False, transposed: bool = False,
                              matmuls: bool = False, softmaxes: bool = False, layernorms: bool = False,
-                             attentions: bool = False):
+                             attentions: bool = False, bilinear_upsamples: bool = False):
     """The same rewrite on an arbitrary module graph (MCT-exported models are not ``nn.Sequential``): traces ``model``
     with torch.fx keeping wrappers and holders as leaves, and wherever an activation holder's ONLY consumer is a
     wrapped ``nn.Linear`` the integer consumer can take (symmetric, power-of-two or LUT weights, and with
@@ -4027,6 +4141,21 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
     bit, what the same rewrite without it returns wherever the float32 products of the layers behind are exact; otherwise it
     differs by the accumulation rounding of those products, like every wrapped layer that becomes a consumer.
 
+    ``bilinear_upsamples=True`` (needs no other switch and composes with all of them, ``upsamples`` included, which keeps leaving
+    bilinear nodes alone) keeps a bilinear upsample between two holders on codes: a DeepLab / FCN / LR-ASPP head, a SegFormer or
+    DPT decoder, BiFPN, a U-Net with ``nn.Upsample(mode="bilinear")``.  The candidate is a plain holder A one of whose users is a
+    call of an ``nn.Upsample`` of mode "bilinear" (``size`` or ``scale_factor``, any ``recompute_scale_factor``, ``align_corners`` None,
+    False or True), of an ``nn.UpsamplingBilinear2d``, or ``F.interpolate`` with constant arguments in that mode and
+    ``antialias=False``, whose one user is a plain holder B; the readers of B are those of ``upsamples``' case (a), or the
+    QuantizedConcat / QuantizedMul operand that absorbed B (case (c)).  The upsample and B become one QuantizedBilinearUpsample
+    node ``<B's name>_bilinear`` (``mctq_codes_upsample_bilinear_nhwc``: 1 byte read per input element, 1 written per output
+    element), through the same plan as ``upsamples``, so holder A is treated the same way.  A blend creates new values: there is
+    no case (b), a B (or such an operand) has to name the form.  The contract is QuantizedBilinearUpsample's, on integers with
+    11-bit weights: CPU and GPU, and every kernel form, give the same bytes; against the float32 chain A -> upsample -> B a code
+    can differ by one, and only next to a rounding tie, and for the factors 2 and 4 without ``align_corners`` and power-of-two
+    scales it is that chain bit for bit.  Left alone: a non-constant ``size``; ``antialias=True``; the modes bicubic and area; a
+    float32 reader of the upsample or of B; 3-D and 5-D inputs; an activation between the upsample and B.
+
     ``any_channels=True`` (needs no other switch and composes with all of them) lifts the ``K % 16 == 0`` condition of "a wrapped
     layer the consumer can take" everywhere above, as for ``fuse_linear_consumers``: wrapped ``nn.Linear`` layers and pointwise
     convolutions of any K <= 32768, and with ``convolutions=True`` k x k convolutions of any ``in_channels`` (the stem of a CNN behind
@@ -4178,10 +4307,11 @@ def fuse_linear_consumers_fx(model: nn.Module, chain: bool = False, uniform_weig
     if layernorms:                                           # (in front of the joins: a holder A with other users becomes one)
         replaced += _layernorms_on_codes(gm, mods, consumer_for)
     # (an upsample's plan is made where a pool's is, in these two passes: it sees the QuantizedConcat / QuantizedMul nodes above)
+    up_kinds = ((QuantizedUpsample,) if upsamples else ()) + ((QuantizedBilinearUpsample,) if bilinear_upsamples else ())
     if shared_holders:
-        replaced += _join_shared_holders(gm, mods, consumer_for, pools, avg_pools, upsamples, activation_tables)
-    if pools or avg_pools or upsamples or activation_tables:
-        replaced += _pool_lone_holders(gm, mods, consumer_for, pools, avg_pools, upsamples, activation_tables)
+        replaced += _join_shared_holders(gm, mods, consumer_for, pools, avg_pools, up_kinds, activation_tables)
+    if pools or avg_pools or up_kinds or activation_tables:
+        replaced += _pool_lone_holders(gm, mods, consumer_for, pools, avg_pools, up_kinds, activation_tables)
     for src, holder in _holder_calls(gm, mods):              # the pair: a holder whose only user is a wrapped layer
         if len(src.users) != 1:
             continue

@@ -32,6 +32,7 @@ int g_softmax_form = 0;      // mctq_codes_softmax: 0 = the launcher chooses (th
 int g_layernorm_form = 0;    // mctq_codes_layernorm: 0 = the launcher chooses (the wave form wherever it fits), 1 = wave form, 2 = block form (the result is the same)
 int g_layernorm_blocks = 0;  // mctq_codes_layernorm: 0 = the launcher chooses the grid, otherwise the number of workgroups (the result is the same)
 int g_upsample_form = 0;     // mctq_codes_upsample_nhwc: 0 = the launcher chooses (replicate for integer factors of 2 .. 16 outputs per input), 1 = gather form, 2 = replicate form where eligible (the result is the same)
+int g_bilinear_strip = 0;    // mctq_codes_upsample_bilinear_nhwc: output rows a lane walks, 0 = the launcher chooses (grid arithmetic), 1 (per pixel), 4 or 8 (the result is the same)
 
 static const char* launch_log_path() {
   const char* p = getenv("MCTQ_LAUNCH_LOG");
@@ -241,6 +242,11 @@ int mctq_set_tuning(const char* key, int32_t value) {
   if (!strcmp(key, "layernorm_blocks")) {
     if (value < 0 || value > 65536) return fail_arg("layernorm_blocks must be 0 (auto) or a grid size of at most 65536");
     g_layernorm_blocks = value;
+    return 0;
+  }
+  if (!strcmp(key, "bilinear_strip")) {
+    if (value != 0 && value != 1 && value != 4 && value != 8) return fail_arg("bilinear_strip must be 0 (auto), 1, 4 or 8");
+    g_bilinear_strip = value;
     return 0;
   }
   if (!strcmp(key, "upsample_form")) {

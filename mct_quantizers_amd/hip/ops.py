@@ -915,6 +915,85 @@ def codes_upsample(codes_nhwc, in_form, out_form, src_rows, src_cols, factors=No
         return fq_codes(dequantize_codes(moved, a_scale, a_zp), None, None, None, qmin, qmax, o_scale, o_zp).contiguous()
 
 
+BILINEAR_WEIGHT_BITS = 11      # WB of codes_upsample_bilinear: 2^(2 * WB) * 255 < 2^31, the blend of four codes is an exact int32
+
+
+def bilinear_tables(src, n_in: int):
+    """``(i0, i1, w1)`` of one axis of ``codes_upsample_bilinear``, int32 CPU tensors, from the float64 source coordinate ``src`` of
+    every output index (a 1-D CPU tensor) over ``n_in`` inputs: ``i0 = floor(src)`` clamped into ``[0, n_in - 1]``, ``i1 =
+    min(i0 + 1, n_in - 1)``, ``w1 = rint((src - i0) * 2^WB)`` clamped into ``[0, 2^WB]``."""
+    one = 1 << BILINEAR_WEIGHT_BITS
+    src = src.to(torch.float64)
+    i0 = src.floor().clamp(0, max(n_in - 1, 0))
+    w1 = torch.round((src - i0) * one).clamp(0, one)
+    i0 = i0.to(torch.int32)
+    return i0, (i0 + 1).clamp(max=max(n_in - 1, 0)), w1.to(torch.int32)
+
+
+def codes_upsample_bilinear(codes_nhwc, in_form, out_form, row_tables, col_tables):
+    """Bilinear resampling on activation codes, in the form of the holder behind it: int8 / uint8 codes [B, H, W, C] of the form
+    ``in_form = (scale, zero_point)`` -> contiguous [B, Ho, Wo, C] codes of ``_code_dtype(qmin, qmax)`` in ``out_form = (scale,
+    zero_point, qmin, qmax)``.  ``row_tables = (r0, r1, wr)`` and ``col_tables = (c0, c1, wc)``: integer vectors (tensors) of
+    lengths Ho / Wo -- two source indices and the weight of the second in ``[0, 2^WB]``, ``WB = 11`` (``bilinear_tables``); the
+    first has ``2^WB`` less that.  The contract is on integers, so that no order of evaluation enters it.  Per output element
+
+        h(r)  = (2^WB - wc[ox]) * (c[r][c0[ox]] - z_in) + wc[ox] * (c[r][c1[ox]] - z_in)
+        acc   = (2^WB - wr[oy]) * h(r0[oy]) + wr[oy] * h(r1[oy])         |acc| <= 2^22 * 255 < 2^31
+        y     = float32(acc) * (float32(s_in) * 2^-22)                   one conversion, one IEEE multiply
+        code  = clamp(rint(y * (1 / s)) + z, qmin, qmax)
+
+    Against ``F.interpolate(mode="bilinear")`` in float64 of the dequantized codes, coded in float64, a code differs by at most
+    one, and only next to a rounding tie: a weight is off by at most ``2^-(WB+1)`` per axis.  Where the weights are dyadic (factors
+    2 and 4 without ``align_corners``) and the scales powers of two these are bit for bit the codes of the float32 chain.  GPU
+    tensors with C % 16 == 0 take one launch of mctq_codes_upsample_bilinear_nhwc (1 byte read per input element, 1 written per
+    output element); anything else on the GPU, and every CPU tensor, evaluates the lines above with torch integer ops, which the
+    kernel matches byte for byte.  Both clamp every index into the image and every weight into ``[0, 2^WB]`` first: no table can
+    make either read outside the image."""
+    _nhwc_codes(codes_nhwc, "codes_upsample_bilinear")
+    a_scale, a_zp = float(in_form[0]), int(in_form[1])
+    o_scale, o_zp, qmin, qmax, tdt, ocode = _out_form(out_form)
+    _check_form("codes_upsample_bilinear", codes_nhwc.dtype, a_zp, (a_scale, o_scale))
+    _check_form("codes_upsample_bilinear", tdt, o_zp, zp_words="the output's zero point {}")
+    tables = tuple(row_tables) + tuple(col_tables)
+    if len(tables) != 6:
+        raise TypeError("codes_upsample_bilinear: row_tables and col_tables are (i0, i1, w1) each")
+    for m in tables:
+        if not isinstance(m, torch.Tensor) or m.dim() != 1 or m.dtype.is_floating_point or m.dtype in (torch.bool, torch.complex64, torch.complex128):
+            raise TypeError("codes_upsample_bilinear: a table must be a 1-D integer tensor")
+    b, h, w, c = codes_nhwc.shape
+    ho, wo = tables[0].numel(), tables[3].numel()
+    if any(m.numel() != (ho if i < 3 else wo) for i, m in enumerate(tables)):
+        raise ValueError("codes_upsample_bilinear: the three tables of an axis must have one length")
+    if ho and wo and 0 in (h, w):
+        raise ValueError(f"codes_upsample_bilinear: a {ho}x{wo} output needs an image of at least one pixel, got {h}x{w}")
+    x = _contiguous(codes_nhwc)
+    if x.is_cuda and c % 16 == 0:
+        y = torch.empty((b, ho, wo, c), dtype=tdt, device=x.device)
+        if y.numel() == 0:
+            return y
+        keep = [_contiguous(m.to(device=x.device, dtype=torch.int32)) for m in tables]      # named: they must outlive the launch
+        _gpu_call("mctq_codes_upsample_bilinear_nhwc", x, x.data_ptr(), y.data_ptr(), _code_of(x), a_zp, a_scale, b, h, w, c, ho, wo,
+                  *(m.data_ptr() for m in keep), ocode, o_scale, o_zp, qmin, qmax)
+        return y
+    if not x.is_cuda:
+        _cpu_route_allowed()
+    if 0 in (b, c, ho, wo):
+        return x.new_empty((b, ho, wo, c), dtype=tdt)
+    with torch.no_grad():
+        one = 1 << BILINEAR_WEIGHT_BITS
+        r0, r1, wr, c0, c1, wc = (m.to(device=x.device, dtype=torch.int64) for m in tables)
+        r0, r1, c0, c1 = r0.clamp(0, h - 1), r1.clamp(0, h - 1), c0.clamp(0, w - 1), c1.clamp(0, w - 1)
+        wr, wc = wr.clamp(0, one)[None, :, None, None], wc.clamp(0, one)[None, None, :, None]
+        d = x.to(torch.int64) - a_zp
+        hz = (one - wc) * d.index_select(2, c0) + wc * d.index_select(2, c1)             # [B, H, Wo, C]
+        acc = (one - wr) * hz.index_select(1, r0) + wr * hz.index_select(1, r1)          # [B, Ho, Wo, C], exact
+        f32 = lambda v: torch.tensor(v, dtype=torch.float64, device=x.device).to(torch.float32)               # noqa: E731
+        v = acc.to(torch.float32) * (f32(a_scale) * f32(2.0 ** -22))
+        q = torch.round(v * (torch.tensor(1.0, dtype=torch.float32, device=x.device) / f32(o_scale))) + float(o_zp)
+        q = torch.clamp(torch.nan_to_num(q, nan=float(qmin)), qmin, qmax)
+        return q.to(tdt).contiguous()
+
+
 def code_table(fn, in_form, out_form, device):
     """The byte table of an elementwise function between two holders: ``fn`` applied to the output of a holder A of the form
     ``in_form = (scale, zero_point, qmin, qmax)`` and coded by a holder B of ``out_form`` (likewise), as a uint8 tensor [256] on
